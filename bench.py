@@ -15,11 +15,15 @@ per GPU (weak scaling: the global filter has N_gpus * 2^20 particles), T = K obs
 simulator, seed 20260101).  ``--model c4``: configs[3] -- a log-Gaussian Cox process (FilterLgcp, precision 2, ~10 sub-steps per
 event), N = 2^24 particles IN TOTAL (strong scaling: 2^24 / N_gpus per GPU; ``--particles`` overrides the total).
 At every N the W warm-up steps start the filter and the timed legs CONTINUE it -- value = particles * K / wall seconds of K
-more steps (cssm_pf_ll_filter_more / its sharded form; median of ``repeats`` legs, max over ranks per leg), the cloud resident
+more steps (cssm_pf_ll_filter_more / its sharded form; median of ``repeats`` legs -- N = 1: one unless asked -- max over ranks per leg), the cloud resident
 in HBM, the K observations' records built and uploaded inside the timed call.  N > 1: plus a profiled pass whose per-rank
 kernel / collective times, plan and resumes go into the line (``per_rank``).
 
-Extra objects on the JSON line (N = 1 only): ``roofline`` for the dominant kernel from HIP events on its launch
+``--dump-outputs DIR``: behind the timed legs, what the last one returned and the cloud it left, as DIR/<name>.npy (dump_outputs).
+The inputs depend on the arguments alone (synthetic data, fixed seeds), so two builds can be compared output for output.
+
+N = 1: a plain run sets up, warms up, times the K steps (one leg unless ``--repeats``) and prints the line; ``--full`` adds the
+extra objects below.  Extra objects on the JSON line (N = 1 with ``--full``): ``roofline`` for the dominant kernel from HIP events on its launch
 stream, ``roofline_16m`` the same kernel at N = 2^24 (the north-star size) for the bench model (d = 3) and for
 Poisson-Brownian (d = 1), and ``cpu_baseline``: the CPU restatement of the reference path (oracle/, one thread as
 the reference runs) on a bounded sample of the same workload.
@@ -167,15 +171,37 @@ def _offspring_roofline(n, per):
             "avg_launch_us": t * 1e6, "achieved": 12 * n / t / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": 12 * n / t / 1e9 / HBM_PEAK_GBS}
 
 
+SETTLE_S = 0.1     # untimed device work of a plain run ahead of the warm-up steps (run_single: settle)
+DUMP_BYTES = {"particles": 32 << 20, "ancestors": 16 << 20, "ll_steps": 4 << 20, "ess_steps": 4 << 20}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64, 64 MB at most in all.  An array larger than its share in DUMP_BYTES
+    is cut to a fixed sample along its last axis: np.sort(default_rng(0).choice(length, share, replace=False)) -- the same for every
+    run of the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        cap = DUMP_BYTES.get(name, 1 << 20) // 8
+        if a.size > cap:
+            rows = a.size // a.shape[-1]
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[-1], cap // rows, replace=False))
+            a = a[..., idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def run_single(args, emit=print):
     import torch  # first: its import takes long enough for the GPU clocks to idle down
     from composablestatespacemodels_amd.filter import NativePf
     K, W = args.steps, args.warmup
     lgcp = args.model == "c4"
     n = args.particles if args.particles > 0 else (N_16M if lgcp else N_PER_GPU)
-    R = args.repeats if args.repeats > 0 else (3 if K >= 200 else 25)
+    R = args.repeats if args.repeats > 0 else 1                   # timed legs of K steps each: --steps K times K steps
+    Rx = args.repeats if args.repeats > 0 else (3 if K >= 200 else 25)   # (--full: the roofline legs' count, as before)
     W = max(W, 1)                      # (the filter has to be running before K more steps can be timed)
-    model, t, y, has = build_workload(W + 7 * R * K + 16, args.model)
+    model, t, y, has = build_workload(W + R * K, args.model)
+    if args.full:                      # the roofline legs run on a series of their own
+        _, tx, yx, hx = build_workload(W + 7 * Rx * K + 16, args.model)
     import ctypes as C
 
     def handle():
@@ -200,12 +226,12 @@ def run_single(args, emit=print):
         torch.cuda.synchronize()
         pf.run(t[:W], y[:W], has[:W])
         walls, devs, calls, idle = [], [], [], []
-        ll = ess_t = None
+        ll = ll_t = ess_t = None
         for r in range(R):
             lo = W + r * K
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            ll, _, ess_t = pf.run_more(t[lo:lo + K], y[lo:lo + K], has[lo:lo + K])
+            ll, ll_t, ess_t = pf.run_more(t[lo:lo + K], y[lo:lo + K], has[lo:lo + K])
             t1 = time.perf_counter()
             torch.cuda.synchronize()
             t2 = time.perf_counter()
@@ -217,13 +243,30 @@ def run_single(args, emit=print):
         if not all(idle):
             raise SystemExit("bench.py: the filter's stream was not idle behind torch.cuda.synchronize()")
         d = pf.d
+        if args.dump_outputs:          # what a caller of the last leg receives, and the cloud its last step left
+            dump_outputs(args.dump_outputs, {"ll": [ll], "ll_steps": ll_t, "ess_steps": ess_t,
+                                             "particles": pf.particles(), "ancestors": pf.ancestors()})
         pf.close()
         return walls, ll, ess_t, d, devs, calls
+
+    def settle():
+        """A plain run's stand-in for the roofline legs that --full runs first: a handle of its own runs SETTLE_S of untimed series
+        (at most 64 observations each) ahead of the warm-up steps and is closed behind the timed legs -- the legs of a GPU that has
+        idled run up to 15 % slower for their first few ms (see below); nothing of it is reported."""
+        pf = handle()
+        L = min(len(t), 64)
+        t0 = time.perf_counter()
+        while True:
+            pf.run(t[:L], y[:L], has[:L])
+            if time.perf_counter() - t0 >= SETTLE_S:
+                break
+        keep.append(pf)
 
     def roofline_legs():
         """Kernel times of legs of the same shape on a handle of their own: the streaming ceiling of the box, the device time of R legs (HIP
         events around their per-observation kernels: CSSM_OPT_LOOP_EVENTS -- off in the timed legs, the two event packets cost a 20-step
         call ~5 us), R legs with every kernel bracketed, and the same with the structure specialisation switched off."""
+        t, y, has, R = tx, yx, hx, Rx     # (their own series; R as the timed legs had it before --full)
         pf = handle()
         copy = C.c_double(0.0)
         copy_gbs = None
@@ -264,16 +307,21 @@ def run_single(args, emit=print):
         keep.append(pf)                  # (closed behind the timed legs: a hipFree is a device synchronisation and an idle gap)
         return copy_gbs, loop_ms, per, pair_s, roof_generic
 
-    # Order: the roofline legs FIRST.  W = 5 warm-up steps are 0.1 ms of device work, and the legs of a process that has kept the GPU busy
+    # Order (--full): the roofline legs FIRST.  W = 5 warm-up steps are 0.1 ms of device work, and the legs of a process that has kept the GPU busy
     # for a few ms in all run 5-15 % slower than every later one (leg after leg of the same handle: 522 493 461 465 468 ... 445 us, level
     # after ~15 legs): timed first, the legs of 20 steps measure that ramp, not the filter.  BENCH_TIMED_FIRST=1 restores that order.
     # ... and the timed filter's handle is CREATED ahead of them and the roofline handle closed behind the timed legs, so that no allocation, no
     # hipFree and no idle gap stands between the roofline legs and the W warm-up steps: a GPU that has idled for a millisecond or more runs the
     # legs 1.5-5 ms into new work up to 14 % slower before it settles (tools/leg_drift.py, device clock stamps: 434 434 445 456 467 496 491
     # 481 472 456 448 436 ... 425 us per 20-observation leg; uncorrelated with the data, back after 2 s of idling) -- the rising legs of
-    # BENCH_r05.  The timed region is what the contract says: W warm-up steps, then R legs of exactly K.
+    # BENCH_r05.  A plain run puts settle() where the roofline legs were.  The timed region is what the contract says: W warm-up steps,
+    # then R legs of exactly K (R = 1 unless --repeats says otherwise).
     keep = []
-    if os.environ.get("BENCH_TIMED_FIRST", "0") == "1":
+    if not args.full:
+        timed_pf = handle()
+        settle()
+        walls, ll, ess_t, d, devs, calls = timed_legs(timed_pf)
+    elif os.environ.get("BENCH_TIMED_FIRST", "0") == "1":
         walls, ll, ess_t, d, devs, calls = timed_legs()
         copy_gbs, loop_ms, per, pair_s, roof_generic = roofline_legs()
     else:
@@ -283,6 +331,28 @@ def run_single(args, emit=print):
     for h in keep:
         h.close()
     wall = float(np.median(walls))
+    out = {
+        "metric": METRIC, "value": n * K / wall, "unit": "particle-steps/s",
+        "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": wall * 1e3 / K, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": workload_text(args.model, n, K),
+                   "particles_per_gpu": n, "observations": K, "latent_dim": d, "seed": 20260101},
+        "repeats": R, "value_is": "median over `repeats` timed legs of K steps each (default one leg: --steps K times K steps; every leg counts, none is discarded: the legs 2-5 ms behind the idle gap in front of the filter run slower on the DEVICE -- device_ms_each), continuing the filter the warm-up steps started (cssm_pf_ll_filter_more); ahead of the warm-up steps a handle of their own runs untimed series (a plain run: 0.1 s of them; --full: the roofline legs), the timed filter's handle is created ahead of those and the other handle closed behind the timed legs (no allocation, hipFree or idle gap in front of the W warm-up steps)", "wall_ms_each": [w * 1e3 for w in walls],
+        "device_ms_each": [x * 1e3 for x in devs],
+        "device_ms_each_is": "per timed leg, the GPU's constant 100 MHz clock (s_memrealtime) at the first instruction of the leg's first kernel and in its closing kernel (cssm_pf_last_device_us): device time of the very legs wall_ms_each times, no event packets on the queue",
+        "call_ms_each": [x * 1e3 for x in calls],
+        "call_ms_each_is": "host time of cssm_pf_ll_filter_more alone (the K steps' results are in host memory when it returns); wall_ms_each = torch.cuda.synchronize() -> call -> torch.cuda.synchronize()",
+        "host_share": 1.0 - float(np.median(devs)) / wall,
+        "ll": ll, "ess_last": int(ess_t[-1]),
+        "runtime": {"HSA_ENABLE_INTERRUPT": os.environ.get("HSA_ENABLE_INTERRUPT"), "note": "the ROCm runtime's completion wait as the caller left it (round 5 set 0 = polling; round 6's A/B on this very command, three interleaved pairs on one box: 22.55 / 23.15 / 22.87 us per step polling, 22.79 / 23.15 / 22.48 with interrupts -- no difference, setting removed: profiles/r06_ab_hsa_interrupt.txt)"},
+    }
+    if args.full:
+        out.update(full_single(args, NativePf, n, d, lgcp, copy_gbs, loop_ms, per, pair_s, roof_generic))
+    emit(json.dumps(out))
+
+
+def full_single(args, NativePf, n, d, lgcp, copy_gbs, loop_ms, per, pair_s, roof_generic):
+    """--full, N = 1: the objects of the line beside the headline figure (roofline legs, live PMC passes, 2^24 rooflines, CPU baseline)."""
     traffic, traffic_source = None, None
     tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
     if os.path.exists(tpath):
@@ -308,23 +378,11 @@ def run_single(args, emit=print):
     roof["traffic"] = traffic
     roof["traffic_source"] = traffic_source
     out = {
-        "metric": METRIC, "value": n * K / wall, "unit": "particle-steps/s",
-        "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": wall * 1e3 / K, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": workload_text(args.model, n, K),
-                   "particles_per_gpu": n, "observations": K, "latent_dim": d, "seed": 20260101},
-        "repeats": R, "value_is": "median over `repeats` timed legs of K steps each (every leg counts, none is discarded: the legs 2-5 ms behind the idle gap in front of the filter run slower on the DEVICE -- device_ms_each), continuing the filter the warm-up steps started (cssm_pf_ll_filter_more); the roofline legs (a handle of their own) run before them, the timed filter's handle is created ahead of those and the roofline handle closed behind the timed legs (no allocation, hipFree or idle gap in front of the W warm-up steps)", "wall_ms_each": [w * 1e3 for w in walls],
         "roofline": roof,
         "roofline_generic": roof_generic,
         "kernels_us": kernels_us,
         "roofline_resampling": _offspring_roofline(n, per),
-        "device_ms_each": [x * 1e3 for x in devs],
-        "device_ms_each_is": "per timed leg, the GPU's constant 100 MHz clock (s_memrealtime) at the first instruction of the leg's first kernel and in its closing kernel (cssm_pf_last_device_us): device time of the very legs wall_ms_each times, no event packets on the queue",
-        "call_ms_each": [x * 1e3 for x in calls],
-        "call_ms_each_is": "host time of cssm_pf_ll_filter_more alone (the K steps' results are in host memory when it returns); wall_ms_each = torch.cuda.synchronize() -> call -> torch.cuda.synchronize()",
-        "host_share": 1.0 - float(np.median(devs)) / wall,
-        "device_loop_ms": loop_ms, "ll": ll, "ess_last": int(ess_t[-1]),
-        "runtime": {"HSA_ENABLE_INTERRUPT": os.environ.get("HSA_ENABLE_INTERRUPT"), "note": "the ROCm runtime's completion wait as the caller left it (round 5 set 0 = polling; round 6's A/B on this very command, three interleaved pairs on one box: 22.55 / 23.15 / 22.87 us per step polling, 22.79 / 23.15 / 22.48 with interrupts -- no difference, setting removed: profiles/r06_ab_hsa_interrupt.txt)"},
+        "device_loop_ms": loop_ms,
     }
     if lgcp:
         roof["note"] = ("an LGCP step runs its ~10 sub-steps of Philox + Box-Muller + exp per particle in registers: the kernel is compute-bound by "
@@ -334,7 +392,7 @@ def run_single(args, emit=print):
         out["roofline_16m"] = roofline_16m(NativePf, copy_gbs, args.fused)
     if not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline()
-    emit(json.dumps(out))
+    return out
 
 
 def live_traffic(n, model, timeout_s=150.0, fused=None):
@@ -757,6 +815,8 @@ def run_multi(args, emit=print):
                          "rccl": shard.lib.cssm_rccl_library().decode() if gpu else None},
             "per_rank": every,
             "ll": ll, "ess_last": ess}))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"ll": [ll], "ess": [ess]})
     if gpu:
         shard.close()
         f.comm.close()
@@ -830,11 +890,13 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--particles", type=int, default=0, help="particles per GPU (c2 / c1: default 2^20) or in total (c4: default 2^24)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed K-step series (0: 3 for K >= 200, else 25); the median is reported")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-16m", action="store_true", help="skip the roofline_16m leg")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live HBM-traffic passes (two rocprofv3 --pmc child runs); roofline.traffic then comes from profiles/traffic_latest.json")
-    ap.add_argument("--no-generic", action="store_true", help="skip the roofline_generic leg (the same kernel with the model's structure as data)")
+    ap.add_argument("--repeats", type=int, default=0, help="timed K-step series, the median is reported (0: N = 1 one, so that K steps are timed -- the roofline legs of --full keep 3 for K >= 200, else 25; N > 1 3 for K >= 200, else 25)")
+    ap.add_argument("--full", action="store_true", help="N = 1: beside the headline figure, the roofline legs, the live HBM-traffic passes, roofline_16m and cpu_baseline (the --no-* switches below leave parts out); without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed leg returned (ll, ll_steps, ess_steps) and the cloud its last step left (particles, ancestors) as DIR/<name>.npy, float64, 64 MB at most (larger arrays: a fixed, seeded sample); N > 1: rank 0's ll and ess")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-16m", action="store_true", help="--full: skip the roofline_16m leg")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the live HBM-traffic passes (two rocprofv3 --pmc child runs); roofline.traffic then comes from profiles/traffic_latest.json")
+    ap.add_argument("--no-generic", action="store_true", help="--full: skip the roofline_generic leg (the same kernel with the model's structure as data)")
     ap.add_argument("--fused", type=int, default=None, help="CSSM_OPT_FUSED_SUMS override (single GPU)")
     ap.add_argument("--model", default="c2", choices=["c2", "c1", "c4"], help="c2: the bench workload (BASELINE configs[1], d = 3, weak scaling); c4: BASELINE configs[3], the log-Gaussian Cox process at N = 2^24 in total (strong scaling); c1: Poisson-Brownian (configs[0], d = 1) -- profiling runs only")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo", "gloo-gpu"], help="gloo: CPU rehearsal of the N-rank path with the test-only oracle shard; gloo-gpu: rehearsal with real GPU shards sharing the devices there are (peer windows over hipIpc, control plane on gloo) -- not a measurement")

@@ -1,13 +1,16 @@
 #!/bin/bash
 # Round 6's measurement session in one call (GPU box, repo root): bench lines, rocprofv3 kernel statistics, PMC passes, the sharded path at
-# world 1, all five BASELINE configurations.  Outputs under gpurun_out/; copy_r06.sh (below) files the summaries into profiles/.
+# world 1, all five BASELINE configurations.  The bench lines go under $OUT (default bench_out), the rest where each tool writes; the
+# summaries were filed into profiles/ by hand.
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 mkdir -p gpurun_out
 echo "== bench lines"
-python3 bench.py > gpurun_out/r06_bench_line.json 2> gpurun_out/r06_bench_line.err; echo "default rc=$?"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r06_bench_line_steps20.json 2> gpurun_out/r06_bench_line_steps20.err; echo "steps20 rc=$?"
-python3 bench.py --model c4 --steps 100 --warmup 10 --no-cpu > gpurun_out/r06_bench_line_c4_lgcp_single_gpu.json 2>/dev/null; echo "c4 rc=$?"
+python3 bench.py --full > "$OUT"/r06_bench_line.json 2> "$OUT"/r06_bench_line.err; echo "default rc=$?"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT"/r06_bench_line_steps20.json 2> "$OUT"/r06_bench_line_steps20.err; echo "steps20 rc=$?"
+python3 bench.py --model c4 --steps 100 --warmup 10 --full --no-cpu > "$OUT"/r06_bench_line_c4_lgcp_single_gpu.json 2>/dev/null; echo "c4 rc=$?"
 echo "== sharded, world 1"
 python3 bench.py --sharded --steps 500 --warmup 20 > gpurun_out/r06_sharded_world1_c2.json 2>/dev/null; echo "sh c2 rc=$?"
 python3 bench.py --sharded --steps 20 --warmup 5 > gpurun_out/r06_sharded_world1_c2_steps20.json 2>/dev/null; echo "sh c2 k20 rc=$?"
