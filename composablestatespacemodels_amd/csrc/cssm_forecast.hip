@@ -1,0 +1,316 @@
+// cssm_forecast.hip -- forecasts from the filtered cloud: ParticleFilter.getForecast / getMeanForecast (model/ParticleFilter.scala:
+// 368-409) and the scan of SimulateData.forecast + summariseForecast over future times (model/Data.scala:196-231), and the stateless
+// observation draw on given etas (cssm_obs_draw).  See include/cssm_pf.h for the contract, include/cssm_obs_draws.h for the draws.
+//
+// One call = chunks of horizons.  Per chunk: k_forecast<D> (one thread per particle PAIR, so that every Philox block of the
+// transition serves both particles, as in k_propagate) gathers the pair once -- from the handle's current cloud through the same
+// indirection k_summary_fill reads, or from the carry buffer of the chunk before -- and runs the chunk's horizons with the state in
+// registers: transition (CSSM_STREAM_STEP under `key` at step h), gamma and eta at t[h], one observation draw (CSSM_STREAM_OBS), the
+// d + 2 order keys and the block's fp64 partial sums per horizon.  Then one radix selection (k_sel_hist / k_sel_pick, grid.y = the
+// chunk's rows) and k_forecast_finish (means and the order statistics per row).  The filter's own buffers are only read.
+#include "cssm_internal.h"
+#include "cssm_kernels.hip.h"
+#include "../../include/cssm_obs_draws.h"
+
+#include <cmath>
+
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restrict__ src, size_t src_stride, const uint32_t* __restrict__ anc,
+                                                         const double* __restrict__ src2, size_t src2_stride, uint32_t n_split,
+                                                         double* __restrict__ carry, int from_carry, int to_carry, uint64_t n,
+                                                         const StepRec* __restrict__ recs, uint32_t h0, uint32_t hc, ModelK mk, uint64_t key,
+                                                         cssm_obs_params op, const double* __restrict__ logtab,
+                                                         unsigned long long* __restrict__ keys, double* __restrict__ partial,
+                                                         double* __restrict__ samples) {
+  constexpr int R = D + 2;   // rows per horizon: the D state components, eta, the observation
+  __shared__ double s_p[CSSM_BLOCK / 64][R];
+  const double* tab = stage_log_table(logtab);
+  const uint64_t npairs = (n + 1) / 2;
+  const uint64_t p = (uint64_t)blockIdx.x * CSSM_BLOCK + threadIdx.x;
+  const bool live = p < npairs;
+  const uint64_t ia = 2 * p, ib = ia + 1;
+  const bool hasb = live && ib < n;
+  const size_t rows = (size_t)hc * R;
+  double xa[D], xb[D];
+  auto load = [&](uint64_t i, int k) -> double {
+    if (from_carry) return carry[(size_t)k * n + i];
+    const size_t j = anc ? (size_t)anc[i] : (size_t)i;
+    return (src2 && j >= n_split)
+        ? (src2_stride == 0 ? ld_sys_f64(src2 + (size_t)(j - n_split) * (size_t)(D + 1) + k) : ld_sys_f64(src2 + (size_t)k * src2_stride + (j - n_split)))
+        : src[(size_t)k * src_stride + j];
+  };
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    xa[k] = live ? load(ia, k) : 0.0;
+    xb[k] = hasb ? load(ib, k) : 0.0;
+  }
+  for (uint32_t j = 0; j < hc; ++j) {
+    const StepRec* rec = recs + j;
+    const uint32_t h = h0 + j;
+    double ga = 0.0, gb = 0.0, ea = 0.0, eb = 0.0, oa = 0.0, ob = 0.0;
+    if (live) {
+      if (hasb) propagate_pair<D>(mk, rec, rec->dt, key, ia, h, tab, xa, xb);
+      else propagate_one<D>(mk, rec, rec->dt, key, ia, h, tab, xa);
+      ga = gamma_of<D>(mk, rec, xa);
+      ea = link_of(mk.obs_kind, ga);
+      cssm_obs_stream sa = cssm_obs_stream_at(key, ia, h);
+      oa = cssm_obs_draw_one(&op, ea, &sa, tab);
+      unsigned long long* kr = keys + (size_t)j * R * n;
+#pragma unroll
+      for (int k = 0; k < D; ++k) kr[(size_t)k * n + ia] = cssm_order_key(xa[k]);
+      kr[(size_t)D * n + ia] = cssm_order_key(ea);
+      kr[(size_t)(D + 1) * n + ia] = cssm_order_key(oa);
+      if (hasb) {
+        gb = gamma_of<D>(mk, rec, xb);
+        eb = link_of(mk.obs_kind, gb);
+        cssm_obs_stream sb = cssm_obs_stream_at(key, ib, h);
+        ob = cssm_obs_draw_one(&op, eb, &sb, tab);
+#pragma unroll
+        for (int k = 0; k < D; ++k) kr[(size_t)k * n + ib] = cssm_order_key(xb[k]);
+        kr[(size_t)D * n + ib] = cssm_order_key(eb);
+        kr[(size_t)(D + 1) * n + ib] = cssm_order_key(ob);
+      }
+      if (samples) {   // rows of horizon j: state..., gamma, eta, obs
+        double* sr = samples + (size_t)j * (D + 3) * n;
+#pragma unroll
+        for (int k = 0; k < D; ++k) sr[(size_t)k * n + ia] = xa[k];
+        sr[(size_t)D * n + ia] = ga; sr[(size_t)(D + 1) * n + ia] = ea; sr[(size_t)(D + 2) * n + ia] = oa;
+        if (hasb) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) sr[(size_t)k * n + ib] = xb[k];
+          sr[(size_t)D * n + ib] = gb; sr[(size_t)(D + 1) * n + ib] = eb; sr[(size_t)(D + 2) * n + ib] = ob;
+        }
+      }
+    }
+    // the block's partial sums of the horizon's R rows (threads without particles add zeros)
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      double v = (k < D) ? xa[k % D] + xb[k % D] : (k == D ? ea + eb : oa + ob);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < R) {
+      double v = 0.0;
+      for (int w = 0; w < CSSM_BLOCK / 64; ++w) v += s_p[w][threadIdx.x];
+      partial[(size_t)blockIdx.x * rows + (size_t)j * R + threadIdx.x] = v;
+    }
+    __syncthreads();
+  }
+  if (to_carry && live) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      carry[(size_t)k * n + ia] = xa[k];
+      if (hasb) carry[(size_t)k * n + ib] = xb[k];
+    }
+  }
+}
+
+// per row of the chunk: out[3 row] = mean (block partials / n), out[3 row + 1 / + 2] = the two selected order statistics
+static __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast_finish(const SelState* __restrict__ st, const double* __restrict__ partial, int nblocks,
+                                                                       int rows, uint64_t n, double* __restrict__ out) {
+  __shared__ double s_w[CSSM_BLOCK / 64];
+  const int row = blockIdx.x;
+  double v = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += CSSM_BLOCK) v += partial[(size_t)b * rows + row];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int w = 0; w < CSSM_BLOCK / 64; ++w) s += s_w[w];
+    out[3 * (size_t)row] = s / (double)n;
+    out[3 * (size_t)row + 1] = cssm_order_unkey(st[row].prefix[0]);
+    out[3 * (size_t)row + 2] = cssm_order_unkey(st[row].prefix[1]);
+  }
+}
+
+static __global__ __launch_bounds__(CSSM_BLOCK) void k_obs_draw(cssm_obs_params op, const double* __restrict__ eta, uint64_t n, uint64_t key,
+                                                                uint32_t step, const double* __restrict__ logtab, double* __restrict__ out) {
+  const double* tab = stage_log_table(logtab);
+  for (uint64_t i = (uint64_t)blockIdx.x * CSSM_BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * CSSM_BLOCK) {
+    cssm_obs_stream s = cssm_obs_stream_at(key, i, step);
+    out[i] = cssm_obs_draw_one(&op, eta[i], &s, tab);
+  }
+}
+
+// the reference's exception for a model without the scale its observation needs (model/Model.scala:150,179,214,247,291,342),
+// and LogGaussianCox.observation = ??? (:364)
+static int obs_params(int kind, int has_scale, double scale, int df, cssm_obs_params* op) {
+  const int rc = cssm_obs_params_make(kind, has_scale, scale, df, op);
+  if (rc == 0) return CSSM_OK;
+  if (rc == -1) {
+    const char* what = "";
+    switch (kind) {
+      case CSSM_OBS_GAUSSIAN: what = "Must provide SD parameter for LinearModel / No SD parameter provided to SeasonalModel"; break;
+      case CSSM_OBS_NEGBIN: what = "No scale parameter provided to Negativebinomial Model"; break;
+      case CSSM_OBS_ZIP: what = "Must provide probability parameter for zero inflated Poisson Model"; break;
+      case CSSM_OBS_STUDENT_T: what = "No scale parameter provided to Student T Model"; break;
+      default: what = "Must provide shape parameter for Beta Model"; break;
+    }
+    return fail(CSSM_EINVAL_ARG, "the observation model needs the scale parameter of the leftmost leaf (the reference throws Exception(\"%s\"))", what);
+  }
+  if (rc == -3) return fail(CSSM_EINVAL_ARG, "Student-t observations need df >= 1 (got %d)", df);
+  if (kind == CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_ARG, "a log-Gaussian Cox process has no observation distribution to draw from "
+                                 "(the reference's LogGaussianCox.observation is ???: scala.NotImplementedError)");
+  return fail(CSSM_EINVAL_ARG, "unknown obs_kind %d", kind);
+}
+
+extern "C" int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_scale, double scale, int df, uint64_t key, uint32_t step,
+                             double* out, int device) {
+  if (!eta || !out) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (n < 1) return fail(CSSM_EINVAL_ARG, "n must be at least 1");
+  cssm_obs_params op;
+  int rc = obs_params(obs_kind, has_scale, scale, df, &op);
+  if (rc) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range", device);
+  HIP_TRY(hipSetDevice(device));
+  double *de = nullptr, *dout = nullptr, *dtab = nullptr;
+  if (hipMalloc(&de, n * 8) != hipSuccess || hipMalloc(&dout, n * 8) != hipSuccess || hipMalloc(&dtab, sizeof(CSSM_TAB)) != hipSuccess)
+    rc = fail(CSSM_ENOMEM, "hipMalloc");
+  if (!rc && (hipMemcpy(de, eta, n * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dtab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice) != hipSuccess))
+    rc = fail(CSSM_EHIP, "upload");
+  if (!rc) {
+    hipLaunchKernelGGL(k_obs_draw, dim3(grid_for(n, CSSM_BLOCK, kGridCap)), dim3(CSSM_BLOCK), 0, 0, op, de, (uint64_t)n, key, step, dtab, dout);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(CSSM_EHIP, "cssm_obs_draw: %s", hipGetErrorString(e));
+  }
+  if (de) (void)hipFree(de);
+  if (dout) (void)hipFree(dout);
+  if (dtab) (void)hipFree(dtab);
+  return rc;
+}
+
+extern "C" int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t key, double interval, double* state_mean, double* state_lower,
+                                double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
+                                double* obs_upper, double* samples) {
+  if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
+  if (pf->sharded) return fail(CSSM_ESTATE, "forecasts of a sharded filter are not supported: forecast from a single-GPU handle");
+  if (!pf->initialised) return fail(CSSM_ESTATE, "not initialised");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (H == 0) return CSSM_OK;
+  if (!t) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (H > 0xffffffffull) return fail(CSSM_EINVAL_ARG, "too many horizons");
+  cssm_obs_params op;
+  int rc = obs_params(pf->obs_kind, pf->obs_has_scale, pf->obs_scale, pf->obs_df, &op);
+  if (rc) return rc;
+  for (size_t h = 0; h < H; ++h) {
+    const double prev = h ? t[h - 1] : pf->t;
+    if (!std::isfinite(t[h])) return fail(CSSM_EINVAL_ARG, "t[%zu] is not finite", h);
+    if (!(t[h] >= prev))
+      return fail(CSSM_EINVAL_ARG, h ? "t must be non-decreasing (t[%zu] = %.17g < %.17g)" : "t[%zu] = %.17g is before the cloud's time %.17g", h, t[h], prev);
+  }
+  HIP_TRY(hipSetDevice(pf->device));
+  const int d = pf->d, R = d + 2;
+  const uint64_t n = pf->n;
+  // horizons per chunk: the order keys of a chunk (R rows of n keys per horizon) within the cap; grid.y of the selection <= 65535
+  const size_t cap = pf->forecast_cap ? pf->forecast_cap : ((size_t)1 << 30);
+  size_t hc = cap / ((size_t)R * n * 8);
+  hc = std::max<size_t>(1, std::min<size_t>({hc, H, (size_t)(65535 / R)}));
+  const size_t rows_max = hc * (size_t)R;
+  const uint64_t npairs = (n + 1) / 2;
+  const int nb_f = (int)((npairs + CSSM_BLOCK - 1) / CSSM_BLOCK);
+  const int nb_s = grid_for(n, CSSM_BLOCK, 1024);
+  const long long idxr = (long long)std::floor(interval * (double)n);   // ranks as summary_impl forms them
+  auto clampr = [&](long long r) { return (unsigned long long)std::min<long long>(std::max<long long>(r, 0), (long long)n - 1); };
+  std::vector<StepRec> hrec(H);
+  for (size_t h = 0; h < H; ++h) cssm_build_rec(pf, h ? t[h - 1] : pf->t, t[h], 0.0, 0, (uint32_t)h, &hrec[h]);
+  std::vector<SelState> hst(rows_max);
+  std::vector<double> hout(3 * rows_max);
+  StepRec* drec = nullptr; double* carry = nullptr; unsigned long long* keys = nullptr; double* partial = nullptr; SelState* st = nullptr;
+  uint32_t* hist = nullptr; double* out = nullptr; double* dsamp = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  double ms_kernel = 0.0, ms_select = 0.0;
+  const bool chunked = hc < H;
+#define FC_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(CSSM_EHIP, "%s: %s", #expr, hipGetErrorString(e__)); goto done; } } while (0)
+#define FC_ALLOC(p, bytes) do { if (hipMalloc(&(p), (bytes)) != hipSuccess) { rc = fail(CSSM_ENOMEM, "hipMalloc(%zu) for the forecast", (size_t)(bytes)); goto done; } } while (0)
+  FC_ALLOC(drec, H * sizeof(StepRec));
+  FC_ALLOC(keys, rows_max * n * 8);
+  FC_ALLOC(partial, (size_t)nb_f * rows_max * 8);
+  FC_ALLOC(st, rows_max * sizeof(SelState));
+  FC_ALLOC(hist, rows_max * 512 * 4);
+  FC_ALLOC(out, 3 * rows_max * 8);
+  if (chunked) FC_ALLOC(carry, (size_t)d * n * 8);
+  if (samples) FC_ALLOC(dsamp, hc * (size_t)(d + 3) * n * 8);
+  for (int i = 0; i < 3; ++i) FC_TRY(hipEventCreate(&ev[i]));
+  FC_TRY(hipMemcpyAsync(drec, hrec.data(), H * sizeof(StepRec), hipMemcpyHostToDevice, pf->stream));
+  for (size_t h0 = 0; h0 < H; h0 += hc) {
+    const size_t hn = std::min(hc, H - h0), rows = hn * (size_t)R;
+    for (size_t r = 0; r < rows; ++r) {
+      const bool state_row = (int)(r % R) < d;   // getCredibleInterval (:496-501) vs getOrderStatistic (:455-460)
+      hst[r].prefix[0] = hst[r].prefix[1] = 0;
+      hst[r].rank[0] = clampr(state_row ? (long long)n - idxr - 1 : (long long)n - idxr);
+      hst[r].rank[1] = clampr(state_row ? idxr - 1 : idxr);
+    }
+    FC_TRY(hipMemcpyAsync(st, hst.data(), rows * sizeof(SelState), hipMemcpyHostToDevice, pf->stream));
+    FC_TRY(hipMemsetAsync(hist, 0, rows * 512 * 4, pf->stream));
+    FC_TRY(hipEventRecord(ev[0], pf->stream));
+    {
+      const int from_carry = h0 > 0, to_carry = chunked && h0 + hn < H;
+      const bool use_anc = !from_carry && pf->anc_valid;
+      DISPATCH_D(d, hipLaunchKernelGGL(k_forecast<D>, dim3(nb_f), dim3(CSSM_BLOCK), 0, pf->stream, pf->src, pf->src_stride,
+                                       (const uint32_t*)(use_anc ? pf->anc : nullptr), use_anc ? pf->src2 : nullptr, pf->src2_stride,
+                                       pf->n_split, carry, from_carry, to_carry, n, (const StepRec*)(drec + h0), (uint32_t)h0, (uint32_t)hn,
+                                       pf->mk, key, op, (const double*)pf->d_logtab, keys, partial, dsamp));
+    }
+    FC_TRY(hipGetLastError());
+    FC_TRY(hipEventRecord(ev[1], pf->stream));
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      hipLaunchKernelGGL(k_sel_hist, dim3(nb_s, (unsigned)rows), dim3(CSSM_BLOCK), 0, pf->stream, (const unsigned long long*)keys, (size_t)n, n,
+                         (const SelState*)st, shift, hist);
+      hipLaunchKernelGGL(k_sel_pick, dim3((unsigned)rows), dim3(2), 0, pf->stream, st, shift, hist);
+    }
+    hipLaunchKernelGGL(k_forecast_finish, dim3((unsigned)rows), dim3(CSSM_BLOCK), 0, pf->stream, (const SelState*)st, (const double*)partial, nb_f,
+                       (int)rows, n, out);
+    FC_TRY(hipGetLastError());
+    FC_TRY(hipEventRecord(ev[2], pf->stream));
+    FC_TRY(hipMemcpyAsync(hout.data(), out, 3 * rows * 8, hipMemcpyDeviceToHost, pf->stream));
+    if (samples) FC_TRY(hipMemcpyAsync(samples + h0 * (size_t)(d + 3) * n, dsamp, hn * (size_t)(d + 3) * n * 8, hipMemcpyDeviceToHost, pf->stream));
+    FC_TRY(hipStreamSynchronize(pf->stream));
+    {
+      float a = 0.f, b = 0.f;
+      FC_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+      FC_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+      ms_kernel += a; ms_select += b;
+    }
+    for (size_t j = 0; j < hn; ++j) {
+      const size_t h = h0 + j;
+      const double* o = hout.data() + 3 * j * (size_t)R;
+      for (int k = 0; k < d; ++k) {
+        if (state_mean) state_mean[h * d + k] = o[3 * k];
+        if (state_lower) state_lower[h * d + k] = o[3 * k + 1];
+        if (state_upper) state_upper[h * d + k] = o[3 * k + 2];
+      }
+      if (eta_mean) eta_mean[h] = o[3 * d];
+      if (eta_lower) eta_lower[h] = o[3 * d + 1];
+      if (eta_upper) eta_upper[h] = o[3 * d + 2];
+      if (obs_mean) obs_mean[h] = o[3 * (d + 1)];
+      if (obs_lower) obs_lower[h] = o[3 * (d + 1) + 1];
+      if (obs_upper) obs_upper[h] = o[3 * (d + 1) + 2];
+    }
+  }
+  pf->forecast_ms[0] = ms_kernel;
+  pf->forecast_ms[1] = ms_select;
+done:
+#undef FC_TRY
+#undef FC_ALLOC
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  { void* ptrs[] = {drec, carry, keys, partial, st, hist, out, dsamp}; for (void* q : ptrs) if (q) (void)hipFree(q); }
+  return rc;
+}
+
+extern "C" int cssm_pf_forecast_last_ms(cssm_pf* pf, double* ms2) {
+  if (!pf || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (pf->forecast_ms[0] < 0.0) return fail(CSSM_ESTATE, "no forecast has run on this handle");
+  ms2[0] = pf->forecast_ms[0];
+  ms2[1] = pf->forecast_ms[1];
+  return CSSM_OK;
+}
+
+extern "C" uint64_t cssm_pf_observation_index(const cssm_pf* pf) { return pf ? pf->step : 0; }

@@ -145,6 +145,12 @@ struct cssm_pf : HostModel {
   size_t prof_used = 0;
   double prof_ms[CSSM_NKERNELS] = {0};
   uint64_t prof_cnt[CSSM_NKERNELS] = {0};
+  // forecasts (cssm_forecast.hip): the leftmost leaf's scale as stored (BetaModel.observation takes it as it is), the key-buffer cap
+  // (CSSM_OPT_FORECAST_CAP; 0 = 1 GiB) and the device times of the last call (cssm_pf_forecast_last_ms; < 0: none yet)
+  int obs_has_scale = 0;
+  double obs_scale = 0.0;
+  size_t forecast_cap = 0;
+  double forecast_ms[2] = {-1.0, -1.0};
 };
 
 // begin/end of one profiled launch

@@ -181,6 +181,7 @@ static int create_common(const cssm_model_desc* desc, uint64_t n_global, uint64_
   pf->opt_fused = 1;   // two launches per observation at every size (measured with the slim single-GPU kernels: 18.7 vs 20.0 us at
                             // N = 100 000, 34.0 vs 35.4 at 2^20, 336 vs 356 at 2^24); an outlying observation is redone in place
   int rc = cssm_build_model(pf, desc, false);
+  if (rc == CSSM_OK) { pf->obs_has_scale = desc->leaves[0].has_scale; pf->obs_scale = desc->leaves[0].scale; }
   if (rc == CSSM_OK) rc = alloc_handle(pf);
   if (rc != CSSM_OK) { const std::string keep = cssm_last_error(); cssm_pf_destroy(pf); return fail(rc, "%s", keep.c_str()); }
   *out = pf;
@@ -226,6 +227,7 @@ extern "C" int cssm_pf_set_params(cssm_pf* pf, const cssm_model_desc* desc) {
   HIP_TRY(hipSetDevice(pf->device));
   int rc = cssm_build_model(pf, desc, true);
   if (rc) return rc;
+  pf->obs_has_scale = desc->leaves[0].has_scale; pf->obs_scale = desc->leaves[0].scale;
   return upload_init_params(pf);
 }
 
@@ -1075,6 +1077,11 @@ extern "C" int cssm_pf_set_option(cssm_pf* pf, int option, int value) {
   if (option == CSSM_OPT_GROUP_SUMS) { pf->opt_grp = value ? 1 : 0; return CSSM_OK; }
   if (option == CSSM_OPT_WAVE_SUMS) { pf->opt_wave = value == 2 ? 2 : (value ? 1 : 0); return CSSM_OK; }
   if (option == CSSM_OPT_LOOP_EVENTS) { pf->opt_events = value ? 1 : 0; return CSSM_OK; }
+  if (option == CSSM_OPT_FORECAST_CAP) {
+    if (value < 0) return fail(CSSM_EINVAL_ARG, "the forecast key-buffer cap is a number of KiB >= 0");
+    pf->forecast_cap = (size_t)value * 1024;
+    return CSSM_OK;
+  }
   if (option == CSSM_OPT_SPECIALISE) { pf->opt_spec = (value == 2) ? 2 : (value ? 1 : 0); return CSSM_OK; }
   if (option == CSSM_OPT_WHOLE_TILES) {   // launch geometry only: the arrays hold up to four sub-units per unit either way
     if (pf->sharded) return fail(CSSM_ESTATE, "sharded handles always run whole tiles");

@@ -45,6 +45,8 @@ class NativePf:
         self.n = int(n)
         self.d = int(self.lib.cssm_pf_dim(self._h))
         self.generation = 0
+        self.model = model
+        self.seed = int(seed) & (2**64 - 1)
         # the same entry point bound once more with untyped pointers: run_more hands it raw array addresses
         self._ll_filter_more_raw = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double),
                                                C.c_void_p, C.c_void_p)(("cssm_pf_ll_filter_more", self.lib))
@@ -65,9 +67,11 @@ class NativePf:
     def set_params(self, model: Model, lgcp_precision: int = 0):
         self._desc = model.descriptor(lgcp_precision)
         _abi.check(self.lib.cssm_pf_set_params(self._h, self._desc.ptr()))
+        self.model = model
 
     def reseed(self, seed: int):
         _abi.check(self.lib.cssm_pf_reseed(self._h, int(seed) & (2**64 - 1)))
+        self.seed = int(seed) & (2**64 - 1)
 
     def init(self, t0: float):
         _abi.check(self.lib.cssm_pf_init(self._h, float(t0)))
@@ -193,6 +197,39 @@ class NativePf:
         _abi.check(self.lib.cssm_pf_summary(self._h, float(interval), _p(m), _p(lo), _p(hi), C.byref(em), C.byref(el), C.byref(eu)))
         return m, lo, hi, em.value, el.value, eu.value
 
+    def observation_index(self) -> int:
+        """Observations the current cloud has seen (cssm_pf_observation_index)."""
+        return int(self.lib.cssm_pf_observation_index(self._h))
+
+    def forecast_key(self) -> int:
+        """The default Philox key of a forecast of the current cloud: cssm_pf_run_key(seed, 2^63 | observation index) -- two forecasts
+        of one state draw the same, forecasts of different states different streams, none the filter's own."""
+        return int(self.lib.cssm_pf_run_key(self.seed, (1 << 63) | self.observation_index()))
+
+    def forecast(self, t, key: Optional[int] = None, interval: float = 0.975, want_samples: bool = False):
+        """cssm_pf_forecast over the times t[0..H): dict of per-horizon arrays state_mean / state_lower / state_upper [H, d],
+        eta_mean / eta_lower / eta_upper / obs_mean / obs_lower / obs_upper [H], and with want_samples samples [H, d + 3, N]
+        (rows: the d states, gamma, eta, obs).  The filter itself is not touched (its generation does not change)."""
+        t = np.ascontiguousarray(np.atleast_1d(np.asarray(t, dtype=np.float64)))
+        H = len(t)
+        key = self.forecast_key() if key is None else int(key) & (2**64 - 1)
+        out = {k: np.zeros((H, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
+        out.update({k: np.zeros(H) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        samples = np.zeros((H, self.d + 3, self.n)) if want_samples else None
+        _abi.check(self.lib.cssm_pf_forecast(self._h, _p(t), H, key, float(interval), _p(out["state_mean"]), _p(out["state_lower"]),
+                                             _p(out["state_upper"]), _p(out["eta_mean"]), _p(out["eta_lower"]), _p(out["eta_upper"]),
+                                             _p(out["obs_mean"]), _p(out["obs_lower"]), _p(out["obs_upper"]),
+                                             _p(samples) if want_samples else None))
+        out["samples"] = samples
+        out["key"] = key
+        return out
+
+    def forecast_last_ms(self) -> Tuple[float, float]:
+        """(k_forecast, selection) device milliseconds of the last forecast (cssm_pf_forecast_last_ms)."""
+        ms = np.zeros(2)
+        _abi.check(self.lib.cssm_pf_forecast_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1])
+
     def interpolate(self, t, y, has=None, interval: float = 0.975, reference_pairing: bool = False):
         """cssm_pf_interpolate: (ll, mean[T+1,d], lower, upper, eta_of_mean[T+1], eta_lower, eta_upper)."""
         t = np.ascontiguousarray(t, dtype=np.float64)
@@ -285,6 +322,7 @@ class NativePfBatch:
         """Chain k as a NativePf view (inspection only; the batch owns the handle)."""
         v = _PfView.__new__(_PfView)
         v.lib = self.lib; v._h = C.c_void_p(self.lib.cssm_pfb_chain(self._h, int(k))); v.n = self.n; v.d = self.d; v.generation = 0
+        v.model = None; v.seed = 0
         return v
 
 
@@ -411,6 +449,26 @@ class PfOut:  # ParticleFilter.scala:20-26
     etaIntervals: CredibleInterval
     state: np.ndarray
     stateIntervals: List[CredibleInterval]
+
+
+@dataclass(frozen=True)
+class ForecastOut:  # ParticleFilter.scala:71-78
+    t: float
+    obs: float
+    obsIntervals: CredibleInterval
+    eta: float
+    etaIntervals: CredibleInterval
+    state: np.ndarray
+    stateIntervals: List[CredibleInterval]
+
+
+@dataclass(frozen=True)
+class ObservationWithState:  # ParticleFilter.scala:381-382, one per particle there; here struct-of-arrays over the N particles
+    t: float
+    observation: np.ndarray   # [N]
+    eta: np.ndarray           # [N]
+    gamma: np.ndarray         # [N]
+    sdeState: np.ndarray      # [d, N]
 
 
 @dataclass(frozen=True)
@@ -614,6 +672,45 @@ class ParticleFilter:
             raise RuntimeError("the cloud summaries need the filter's current PfState (the cloud lives on the device)")
         return s._owner
 
+    # ---- forecasts (ParticleFilter.scala:368-409, Data.scala:196-231): the handle's parameters, one device call
+    @staticmethod
+    def _forecast_handle(s: "PfState", mod: Model) -> NativePf:
+        pf = ParticleFilter._current(s)
+        if mod is not pf.model and _model_signature(mod) != _model_signature(pf.model):
+            raise ValueError("forecasts use the filter's own model and parameters: `mod` must be the model the filter was built with")
+        return pf
+
+    @staticmethod
+    def _key(pf: NativePf, seed: Optional[int]) -> int:
+        return pf.forecast_key() if seed is None else int(seed)
+
+    @staticmethod
+    def getForecast(s: "PfState", mod: Model, t: float, seed: Optional[int] = None) -> ObservationWithState:
+        """getForecast (:368-387): every particle pushed to t, gamma = f(x, t), eta = link(gamma), one observation draw -- as arrays."""
+        pf = ParticleFilter._forecast_handle(s, mod)
+        r = pf.forecast([t], ParticleFilter._key(pf, seed), 0.975, want_samples=True)
+        sm = r["samples"][0]
+        d = pf.d
+        return ObservationWithState(float(t), sm[d + 2].copy(), sm[d + 1].copy(), sm[d].copy(), sm[:d].copy())
+
+    @staticmethod
+    def getMeanForecast(s: "PfState", mod: Model, t: float, interval: float, seed: Optional[int] = None) -> ForecastOut:
+        """getMeanForecast (:389-409), the observations drawn once."""
+        return ParticleFilter.forecast(s, mod, [t], interval, seed)[0]
+
+    @staticmethod
+    def forecast(s: "PfState", mod: Model, times: Sequence[float], interval: float = 0.975, seed: Optional[int] = None) -> List[ForecastOut]:
+        """SimulateData.forecast + summariseForecast (Data.scala:196-231): horizon h starts from horizon h - 1's states; one ForecastOut
+        per time, all formed in one device call."""
+        pf = ParticleFilter._forecast_handle(s, mod)
+        times = [float(v) for v in times]
+        r = pf.forecast(times, ParticleFilter._key(pf, seed), float(interval))
+        return [ForecastOut(tt, float(r["obs_mean"][h]), CredibleInterval(float(r["obs_lower"][h]), float(r["obs_upper"][h])),
+                            float(r["eta_mean"][h]), CredibleInterval(float(r["eta_lower"][h]), float(r["eta_upper"][h])),
+                            r["state_mean"][h].copy(),
+                            [CredibleInterval(float(a), float(b)) for a, b in zip(r["state_lower"][h], r["state_upper"][h])])
+                for h, tt in enumerate(times)]
+
     @staticmethod
     def meanState(s: "PfState") -> np.ndarray:
         """ParticleFilter.meanState (:475-477) of the state's cloud: per-component means, formed on the device."""
@@ -644,3 +741,14 @@ class ParticleFilter:
     @staticmethod
     def mean(s: Sequence[float]) -> float:  # :522-524
         return float(np.sum(s)) / len(s)
+
+
+def _model_signature(mod: Optional[Model]):
+    """Structure and stored parameters of a model as its descriptor states them (two models that drive a handle identically)."""
+    if mod is None:
+        return None
+    desc = mod.descriptor()
+    arr = lambda p, k: tuple(p[i] for i in range(k)) if k else ()
+    leaves = tuple((L.sde_kind, L.dim, L.f_kind, L.period, L.harmonics, L.has_scale, L.scale, arr(L.m0, L.n_m0), arr(L.c0, L.n_c0),
+                    arr(L.mu, L.n_mu), arr(L.phi, L.n_phi), arr(L.sigma, L.n_sigma)) for L in desc.leaf_array)
+    return (desc.desc.obs_kind, desc.desc.obs_df, leaves)

@@ -13,7 +13,8 @@ Reference (paths relative to src/main/scala/com/github/jonnylaw/model/):
   is recognised by the NUMBER of fields (3 Brownian, 4 GenBrownian, 5 OU) -- jsonFormats.scala:29-77.
 * ``MetropState`` ``{"ll", "params", "sde": {"time", "state"}, "accepted"}`` -- jsonFormats.scala:121-122,
   written one per line by Streaming.pmmhToJson (Streaming.scala:42-58).
-* CSV lines of ``Parameters`` / ``MetropState`` / ``PfOut`` -- CsvFormat.scala:33-47,53-61,75-83.
+* CSV lines of ``Parameters`` / ``MetropState`` / ``PfOut`` -- CsvFormat.scala:33-47,53-61,75-83; of ``ForecastOut`` --
+  CsvFormat.scala:84-85, whose intervals print through the case class's ``toString`` (``CredibleInterval(l,u)``).
 """
 from __future__ import annotations
 
@@ -22,7 +23,7 @@ from typing import Iterable, Iterator, List, Optional, Sequence
 
 import numpy as np
 
-from .filter import CredibleInterval, PfOut, StateSpace
+from .filter import CredibleInterval, ForecastOut, PfOut, StateSpace
 from .model import (BrownianParameter, GenBrownianParameter, OuParameter, ParamNode, Parameters, TimedObservation)
 from .pmmh import MetropState
 
@@ -159,6 +160,33 @@ def pfout_csv(o: PfOut) -> str:  # Show[PfOut], CsvFormat.scala:75-83
     state = ", ".join(repr(float(v)) for v in o.state)
     ivals = ", ".join(f"{repr(float(c.lower))}, {repr(float(c.upper))}" for c in o.stateIntervals)
     return f"{o.time}, {obs}, {repr(float(o.eta))}, {repr(float(o.etaIntervals.lower))}, {repr(float(o.etaIntervals.upper))}, {state}, {ivals}"
+
+
+def _ci_str(c: CredibleInterval) -> str:   # the case class's toString: CredibleInterval(lower,upper)
+    return f"CredibleInterval({repr(float(c.lower))},{repr(float(c.upper))})"
+
+
+def forecast_out_csv(o: ForecastOut) -> str:  # Show[ForecastOut], CsvFormat.scala:84-85
+    state = ", ".join(repr(float(v)) for v in o.state)
+    ivals = ", ".join(_ci_str(c) for c in o.stateIntervals)   # stateIntervals.mkString(", "): toString again, not Show
+    return f"{o.t}, {repr(float(o.obs))}, {_ci_str(o.obsIntervals)}, {repr(float(o.eta))}, {_ci_str(o.etaIntervals)}, {state}, {ivals}"
+
+
+def forecast_out_from_csv(line: str) -> ForecastOut:
+    """The inverse of forecast_out_csv (the latent dimension follows from the number of fields)."""
+    f = [x.strip() for x in line.strip().split(", ")]
+
+    def ci(x: str) -> CredibleInterval:
+        if not (x.startswith("CredibleInterval(") and x.endswith(")")):
+            raise ValueError(f"not a CredibleInterval: {x!r}")
+        a, b = x[len("CredibleInterval("):-1].split(",")
+        return CredibleInterval(float(a), float(b))
+
+    d = (len(f) - 5) // 2
+    if len(f) != 5 + 2 * d or d < 1:
+        raise ValueError("a ForecastOut line has 5 + 2 d fields")
+    return ForecastOut(float(f[0]), float(f[1]), ci(f[2]), float(f[3]), ci(f[4]), np.array([float(v) for v in f[5:5 + d]]),
+                       [ci(v) for v in f[5 + d:]])
 
 
 def state_space_csv(s: StateSpace) -> str:  # Show[StateSpace], CsvFormat.scala:49-51

@@ -1,0 +1,229 @@
+/*
+ * cssm_obs_draws.h -- observation samplers of the numerics contract: `mod.observation(gamma).draw` of every observation model
+ * (model/Model.scala:145-150, 169-180, 209-213, 242-246, 267, 282-292, 316, 340-342), as the forecasts of
+ * model/ParticleFilter.scala:368-409 and model/Data.scala:196-231 draw them.
+ *
+ * Plain C99 over include/cssm_numerics.h, compiled unchanged by gcc (host) and by hipcc for gfx950 (device), both with
+ * -ffp-contract=off: the only elementary functions are cssm_exp, cssm_log, cssm_lgamma, cssm_sqrt, cssm_fma, cssm_u01* and
+ * cssm_normal_pair64, plus the exact __builtin_floor / __builtin_fabs -- no libm or OCML call, so a host build and the device
+ * give the same bits.  A separate header so that the hipRTC sources and the oracle build (which include cssm_numerics.h)
+ * do not change, and no existing variate does either.
+ *
+ * Counter layout.  Observation draws have a stream tag of their own, CSSM_STREAM_OBS = 8, and ONE stream per particle (not
+ * the paired streams of the transitions): counter (key, gid = global particle id, step = horizon index h, tag 8,
+ * block = b).  A draw consumes whole Philox blocks in order, b = 0, 1, 2, ...; every attempt of a rejection loop takes
+ * exactly one block, so attempt j of particle i at horizon h is one fixed block.  Composite draws continue the block count
+ * of their first part (NegBin: the gamma's attempts, then the Poisson's).
+ *
+ * Algorithms, per observation model (eta = link(gamma); every reference `observation` depends on gamma only through it):
+ *   Poisson(lambda)           lambda < 10: inversion by sequential search on one uniform (block 0 words 0-1); the search
+ *                             stops where the cumulative sum no longer grows (u within rounding of 1).  10 <= lambda < 2^52:
+ *                             PTRS (Hoermann 1993, "The transformed rejection method for generating Poisson random
+ *                             variables"), one block per attempt (U from words 0-1, V from words 2-3).  lambda >= 2^52:
+ *                             floor(lambda + sqrt(lambda) z) (the normal limit; doubles are integers there).
+ *                             lambda = 0 -> 0; lambda = +inf -> +inf; NaN or lambda < 0 -> NaN.
+ *   Gaussian(eta, sd)         eta + sd z, z = first normal of block 0; sd = exp(scale).
+ *   Gamma(shape, scale)       Marsaglia & Tsang (2000): shape >= 1 one block per attempt (z from words 0-1 through
+ *                             cssm_normal_pair64, U from words 2-3, the squeeze U < 1 - 0.0331 z^4 first); shape < 1:
+ *                             Gamma(shape + 1) U^(1/shape), the boost uniform U from block 0 and the attempts from block 1.
+ *                             shape <= 0 or NaN -> NaN; shape = +inf -> +inf.
+ *   NegBin(eta, size)         Gamma(size, scale = eta / size), then Poisson of it; size = exp(scale).
+ *   ZIP(eta, p)               u < p ? 0 : Poisson(eta), u from block 0, the Poisson from block 1; p = logistic(scale).
+ *   Bernoulli(eta)            u < eta (eta already clamped to {0, 1} beyond |gamma| > 6 by link).
+ *   Student-t(eta, v, df)     eta + v t, t = z / sqrt(chi2 / df), z = first normal of block 0, chi2 = 2 Gamma(df / 2) from
+ *                             block 1 on; v = exp(scale).
+ *   Beta(eta, b)              X / (X + Y), X = Gamma(eta), Y = Gamma(b) (Y's blocks follow X's); b = the stored scale as it is
+ *                             (BetaModel.observation, model/Model.scala:340-342).  A non-positive shape gives NaN, and so
+ *                             does 0 / 0 when both gammas underflow.
+ * Rejection loops give up after CSSM_OBS_MAX_ATTEMPTS attempts (the acceptance rates are above 0.88: never reached in
+ * practice) and return a deterministic value (Poisson: floor(lambda); Gamma: its mode-like d = shape - 1/3), so every draw
+ * terminates in bounded time on the device.
+ */
+#ifndef CSSM_OBS_DRAWS_H
+#define CSSM_OBS_DRAWS_H
+
+#include "cssm_numerics.h"
+#include "cssm_pf.h"
+
+#ifdef __cplusplus
+extern "C++" {
+#endif
+
+#define CSSM_STREAM_OBS 8u          /* observation draws of forecasts: counter (key, gid, horizon, 8, block) */
+#define CSSM_OBS_PTRS_MIN 10.0      /* Poisson: inversion below, PTRS from here on */
+#define CSSM_OBS_NORMAL_MIN 0x1.0p52 /* Poisson: the normal limit from here on */
+#define CSSM_OBS_MAX_ATTEMPTS 64
+
+/* the per-model constants of a draw (cssm_obs_params_make) */
+typedef struct {
+  int kind;    /* CSSM_OBS_* */
+  int df;      /* Student-t degrees of freedom */
+  double p0;   /* Gaussian sd, NegBin size, ZIP p, Student-t v, Beta b */
+} cssm_obs_params;
+
+/* 0, or -1: the model needs the scale parameter and has none; -2: no observation distribution (LGCP) or unknown kind;
+ * -3: Student-t with df < 1. */
+CSSM_HD int cssm_obs_params_make(int kind, int has_scale, double scale, int df, cssm_obs_params* out) {
+  out->kind = kind; out->df = df; out->p0 = 0.0;
+  switch (kind) {
+    case CSSM_OBS_POISSON: case CSSM_OBS_BERNOULLI: return 0;
+    case CSSM_OBS_GAUSSIAN: case CSSM_OBS_NEGBIN:
+      if (!has_scale) return -1;
+      out->p0 = cssm_exp(scale);
+      return 0;
+    case CSSM_OBS_STUDENT_T:
+      if (!has_scale) return -1;
+      if (df < 1) return -3;
+      out->p0 = cssm_exp(scale);
+      return 0;
+    case CSSM_OBS_ZIP: {
+      if (!has_scale) return -1;
+      const double ev = cssm_exp(scale);
+      out->p0 = ev / (1.0 + ev);   /* exp(v) / (1 + exp(v)), model/Model.scala:284 */
+      return 0;
+    }
+    case CSSM_OBS_BETA:
+      if (!has_scale) return -1;
+      out->p0 = scale;
+      return 0;
+    default: return -2;
+  }
+}
+
+/* one particle's stream of Philox blocks */
+typedef struct {
+  uint64_t key, gid;
+  uint32_t step, block;
+} cssm_obs_stream;
+
+CSSM_HD cssm_obs_stream cssm_obs_stream_at(uint64_t key, uint64_t gid, uint32_t step) {
+  cssm_obs_stream s; s.key = key; s.gid = gid; s.step = step; s.block = 0u; return s;
+}
+CSSM_HD cssm_u32x4 cssm_obs_next(cssm_obs_stream* s) {
+  const cssm_u32x4 b = cssm_philox_draw(s->key, s->gid, s->step, CSSM_STREAM_OBS, s->block);
+  s->block += 1u;
+  return b;
+}
+
+/* Poisson(lambda) */
+CSSM_HD double cssm_obs_poisson(double lam, cssm_obs_stream* s, const double* tab) {
+  if (lam != lam || lam < 0.0) return cssm_nan();
+  if (lam == 0.0) return 0.0;
+  if (lam > 0x1.fffffffffffffp1023) return cssm_inf();
+  if (lam < CSSM_OBS_PTRS_MIN) {        /* inversion: the first k with F(k) > u */
+    const cssm_u32x4 b = cssm_obs_next(s);
+    const double u = cssm_u01(b.v[0], b.v[1]);
+    double p = cssm_exp(-lam), F = p, k = 0.0;
+    while (u >= F) {
+      k = k + 1.0;
+      p = p * lam / k;
+      const double Fn = F + p;
+      if (Fn == F) break;               /* u within rounding of 1: the tail the sum cannot resolve */
+      F = Fn;
+    }
+    return k;
+  }
+  if (lam >= CSSM_OBS_NORMAL_MIN) {
+    const cssm_u32x4 b = cssm_obs_next(s);
+    double z0, z1;
+    cssm_normal_pair64(b.v[0], b.v[1], tab, &z0, &z1);
+    const double k = __builtin_floor(lam + cssm_sqrt(lam) * z0);
+    return k < 0.0 ? 0.0 : k;
+  }
+  /* PTRS, Hoermann (1993), with the constants of the paper */
+  const double slam = cssm_sqrt(lam), loglam = cssm_log(lam);
+  const double bb = 0.931 + 2.53 * slam;
+  const double a = -0.059 + 0.02483 * bb;
+  const double invalpha = 1.1239 + 1.1328 / (bb - 3.4);
+  const double vr = 0.9277 - 3.6224 / (bb - 2.0);
+  const double log_invalpha = cssm_log(invalpha);
+  for (int it = 0; it < CSSM_OBS_MAX_ATTEMPTS; ++it) {
+    const cssm_u32x4 b = cssm_obs_next(s);
+    const double U = cssm_u01(b.v[0], b.v[1]) - 0.5;
+    const double V = cssm_u01_open0(b.v[2], b.v[3]);
+    const double us = 0.5 - __builtin_fabs(U);
+    const double k = __builtin_floor((2.0 * a / us + bb) * U + lam + 0.43);
+    if (us >= 0.07 && V <= vr) return k;
+    if (k < 0.0 || (us < 0.013 && V > us)) continue;
+    const double lhs = (cssm_log(V) + log_invalpha) - cssm_log(a / (us * us) + bb);
+    const double rhs = (-lam + k * loglam) - cssm_lgamma(k + 1.0);
+    if (lhs <= rhs) return k;
+  }
+  return __builtin_floor(lam);
+}
+
+/* Gamma(shape, 1) */
+CSSM_HD double cssm_obs_gamma1(double shape, cssm_obs_stream* s, const double* tab) {
+  if (shape != shape || shape <= 0.0) return cssm_nan();
+  if (shape > 0x1.fffffffffffffp1023) return cssm_inf();
+  double boost = 1.0;
+  double a = shape;
+  if (shape < 1.0) {                    /* Gamma(a) = Gamma(a + 1) U^(1/a) */
+    const cssm_u32x4 b = cssm_obs_next(s);
+    boost = cssm_exp(cssm_log(cssm_u01_open0(b.v[0], b.v[1])) / shape);
+    a = shape + 1.0;
+  }
+  const double d = a - 1.0 / 3.0;
+  const double c = 1.0 / cssm_sqrt(9.0 * d);
+  for (int it = 0; it < CSSM_OBS_MAX_ATTEMPTS; ++it) {
+    const cssm_u32x4 b = cssm_obs_next(s);
+    double z, z1;
+    cssm_normal_pair64(b.v[0], b.v[1], tab, &z, &z1);
+    const double U = cssm_u01_open0(b.v[2], b.v[3]);
+    double v = 1.0 + c * z;
+    if (v <= 0.0) continue;
+    v = (v * v) * v;
+    const double z2 = z * z;
+    if (U < 1.0 - 0.0331 * (z2 * z2)) return (d * v) * boost;
+    if (cssm_log(U) < 0.5 * z2 + d * ((1.0 - v) + cssm_log(v))) return (d * v) * boost;
+  }
+  return d * boost;
+}
+
+/* One observation of model p.kind given eta = link(gamma) */
+CSSM_HD double cssm_obs_draw_one(const cssm_obs_params* p, double eta, cssm_obs_stream* s, const double* tab) {
+  switch (p->kind) {
+    case CSSM_OBS_POISSON: return cssm_obs_poisson(eta, s, tab);
+    case CSSM_OBS_GAUSSIAN: {
+      const cssm_u32x4 b = cssm_obs_next(s);
+      double z0, z1;
+      cssm_normal_pair64(b.v[0], b.v[1], tab, &z0, &z1);
+      return eta + p->p0 * z0;
+    }
+    case CSSM_OBS_NEGBIN: {
+      const double size = p->p0;
+      const double lam = cssm_obs_gamma1(size, s, tab) * (eta / size);
+      return cssm_obs_poisson(lam, s, tab);
+    }
+    case CSSM_OBS_ZIP: {
+      const cssm_u32x4 b = cssm_obs_next(s);
+      const double u = cssm_u01(b.v[0], b.v[1]);
+      const double k = cssm_obs_poisson(eta, s, tab);   /* drawn either way, as the reference's for-comprehension does */
+      return (u < p->p0) ? 0.0 : k;
+    }
+    case CSSM_OBS_BERNOULLI: {
+      const cssm_u32x4 b = cssm_obs_next(s);
+      return (cssm_u01(b.v[0], b.v[1]) < eta) ? 1.0 : 0.0;
+    }
+    case CSSM_OBS_STUDENT_T: {
+      const cssm_u32x4 b = cssm_obs_next(s);
+      double z0, z1;
+      cssm_normal_pair64(b.v[0], b.v[1], tab, &z0, &z1);
+      const double df = (double)p->df;
+      const double chi2 = 2.0 * cssm_obs_gamma1(0.5 * df, s, tab);
+      return eta + p->p0 * (z0 / cssm_sqrt(chi2 / df));
+    }
+    case CSSM_OBS_BETA: {
+      if (p->p0 != p->p0 || p->p0 <= 0.0) return cssm_nan();
+      const double x = cssm_obs_gamma1(eta, s, tab);
+      const double y = cssm_obs_gamma1(p->p0, s, tab);
+      return x / (x + y);
+    }
+    default: return cssm_nan();
+  }
+}
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CSSM_OBS_DRAWS_H */

@@ -281,6 +281,10 @@ int cssm_pf_stream_idle(cssm_pf* pf);
  * whose units have several tiles (more than 2^20 particles) of models with at most two latent components -- where the STEP gains --, 2
  * (verification, A/B) wherever the geometry allows, 0 = never: k_offspring_self (every weight converted and scanned in 128 bits). */
 #define CSSM_OPT_WAVE_SUMS 10
+/* CSSM_OPT_FORECAST_CAP (value in KiB; default 0 = 1 GiB): cssm_pf_forecast runs its horizons in chunks whose order keys
+ * ((d + 2) x N x 8 bytes per horizon) fit in this many KiB (at least one horizon per chunk).  Results do not depend on it (tests
+ * lower it to run the chunked path at small N). */
+#define CSSM_OPT_FORECAST_CAP 11
 int cssm_pf_set_option(cssm_pf* pf, int option, int value);
 /* Counters of the run-time specialisation in this process: out4 = {kernels compiled, kernels loaded from the disk cache, launches of
  * run-time-compiled kernels, failures (each reported once on stderr)}. */
@@ -358,6 +362,38 @@ int cssm_pf_get_proposed(cssm_pf* pf, double* out_dN);
  * fp64 sums (agreement with the reference's sequential sum: ~1e-13 relative). */
 int cssm_pf_summary(cssm_pf* pf, double interval, double* state_mean, double* state_lower, double* state_upper,
                     double* eta_of_mean, double* eta_lower, double* eta_upper);
+
+/* Forecasts from the current cloud: SimulateData.forecast + summariseForecast (model/Data.scala:196-231) -- the scan of
+ * ParticleFilter.getMeanForecast (model/ParticleFilter.scala:389-409) over the future times t[0..H) -- in one call.  The source is
+ * exactly the cloud cssm_pf_summary summarises (also between cssm_pf_propagate and cssm_pf_adopt); horizon h starts from the states
+ * of horizon h - 1 (h = 0: the cloud, at the handle's time) and
+ *   x_h   = stepFunction(t[h] - t[h-1]) of every particle: the transition an unweighted filter step with Philox key `key` and
+ *           observation index h draws (CSSM_STREAM_STEP, paired streams) -- dt = 0 allowed;
+ *   gamma = f(x_h, t[h]), eta = link(gamma), obs = one draw of mod.observation(gamma) (include/cssm_obs_draws.h, counter
+ *           (key, particle, h, CSSM_STREAM_OBS, block)).
+ * Per horizon: state_mean[h*d + k] = meanState, state_lower / _upper = getallCredibleIntervals (ranks N - idx - 1, idx - 1);
+ * eta_mean / obs_mean = the plain means of the etas and observations (:401-405, not link(f(mean))), eta_ / obs_lower / _upper =
+ * getOrderStatistic (ranks N - idx, idx); idx = floor(interval N), ranks clamped to [0, N).  Order statistics are exact (radix
+ * selection), means are fp64 block sums.  samples (optional, host): H x (d + 3) x N doubles, row r of horizon h at
+ * samples[(h (d + 3) + r) N + i]: the d states, gamma, eta, obs of particle i.  Any output may be NULL.
+ * The filter is not touched: cloud, time, observation index, ll, ESS, weights and Philox key stay as they were.
+ * Errors: CSSM_ESTATE (not initialised; a sharded handle), CSSM_EINVAL_ARG (interval outside (0, 1]; t not finite, before the
+ * cloud's time or decreasing; LGCP, whose observation the reference leaves unimplemented, model/Model.scala:364; a model without
+ * the scale its observation needs, with the reference's exception named).  Deviations D10-D12. */
+int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t key, double interval, double* state_mean, double* state_lower,
+                     double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
+                     double* obs_upper, double* samples);
+/* Device time of the last cssm_pf_forecast (HIP events around its kernels), ms2[0] = k_forecast, ms2[1] = the radix selection and
+ * the finishing kernel, summed over chunks.  CSSM_ESTATE before the first forecast. */
+int cssm_pf_forecast_last_ms(cssm_pf* pf, double* ms2);
+/* The handle's observation index: the number of observations the current cloud has seen (the default forecast key of the Python
+ * mirror is cssm_pf_run_key(seed, 2^63 | this)). */
+uint64_t cssm_pf_observation_index(const cssm_pf* pf);
+/* mod.observation(gamma).draw on the device for given etas (the `Resample[A]`-like stateless seam of the forecasts):
+ * out[i] = the draw of particle i at horizon `step` under `key` -- what cssm_pf_forecast draws for eta[i] -- with the leftmost leaf's
+ * stored scale (has_scale, scale) and Student-t's df.  Errors as cssm_pf_forecast's for the model; CSSM_EHIP without a device. */
+int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_scale, double scale, int df, uint64_t key, uint32_t step,
+                  double* out, int device);
 
 /* FilterInterpolate (model/ParticleFilter.scala:273-311, ParticleFilter.interpolate :335-337): the filter whose
  * particles are whole paths, so that a weighted step resamples the paths and missing observations are

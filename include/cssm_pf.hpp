@@ -170,11 +170,23 @@ struct Resampling {
   }
 };
 
+// ParticleFilter.scala:14, :71-78 (one per forecast time: SimulateData.forecast + summariseForecast, Data.scala:196-231)
+struct CredibleInterval { double lower, upper; };
+struct ForecastOut {
+  double t;
+  double obs;
+  CredibleInterval obsIntervals;
+  double eta;
+  CredibleInterval etaIntervals;
+  Vec state;
+  std::vector<CredibleInterval> stateIntervals;
+};
+
 // Filter(mod, resample) with resample = Resampling.systematicResampling (or CSSM_RESAMPLE_* through `resampler`)
 class Filter {
  public:
   Filter(const ParamModel& mod, uint64_t particles, uint64_t seed = 20260101, int device = 0, int resampler = CSSM_RESAMPLE_SYSTEMATIC)
-      : d_(mod.dimension()), n_(particles) {
+      : d_(mod.dimension()), n_(particles), seed_(seed) {
     check(cssm_pf_create(mod.desc(), particles, seed, device, &h_));
     if (resampler != CSSM_RESAMPLE_SYSTEMATIC) check(cssm_pf_set_option(h_, CSSM_OPT_RESAMPLER, resampler));
   }
@@ -209,7 +221,23 @@ class Filter {
     return {ll, out};
   }
   Vec particles() { Vec out((size_t)d_ * n_); check(cssm_pf_get_particles(h_, out.data())); return out; }   // SoA [d][N]
-  void setParams(const ParamModel& mod, uint64_t seed) { check(cssm_pf_set_params(h_, mod.desc())); check(cssm_pf_reseed(h_, seed)); }
+  void setParams(const ParamModel& mod, uint64_t seed) { check(cssm_pf_set_params(h_, mod.desc())); check(cssm_pf_reseed(h_, seed)); seed_ = seed; }
+  // forecasts of the current cloud at `times` (ParticleFilter.getMeanForecast, :389-409, scanned as Data.scala:196-231) under the
+  // filter's own parameters; key 0 = the default key cssm_pf_run_key(seed, 2^63 | observation index).  The filter is not touched.
+  std::vector<ForecastOut> forecast(const Vec& times, double interval = 0.975, uint64_t key = 0) {
+    const size_t H = times.size();
+    if (key == 0) key = cssm_pf_run_key(seed_, (1ull << 63) | cssm_pf_observation_index(h_));
+    Vec sm(H * d_), sl(H * d_), su(H * d_), em(H), el(H), eu(H), om(H), ol(H), ou(H);
+    check(cssm_pf_forecast(h_, times.data(), H, key, interval, sm.data(), sl.data(), su.data(), em.data(), el.data(), eu.data(), om.data(),
+                           ol.data(), ou.data(), nullptr));
+    std::vector<ForecastOut> out;
+    for (size_t h = 0; h < H; ++h) {
+      ForecastOut f{times[h], om[h], {ol[h], ou[h]}, em[h], {el[h], eu[h]}, Vec(sm.begin() + h * d_, sm.begin() + (h + 1) * d_), {}};
+      for (int k = 0; k < d_; ++k) f.stateIntervals.push_back({sl[h * d_ + k], su[h * d_ + k]});
+      out.push_back(std::move(f));
+    }
+    return out;
+  }
   cssm_pf* handle() { return h_; }
 
  private:
@@ -219,6 +247,7 @@ class Filter {
   cssm_pf* h_ = nullptr;
   int d_;
   uint64_t n_;
+  uint64_t seed_;
 };
 
 }  // namespace cssm
