@@ -103,6 +103,8 @@ SYMBOLS = [
     ("cssm_pf_get_proposed", C.c_int, [_h, _dp]),
     ("cssm_pf_summary", C.c_int, [_h, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_pf_forecast", C.c_int, [_h, _dp, C.c_size_t, C.c_uint64, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("cssm_pf_forecast_posterior", C.c_int, [_h, _descp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp, C.c_size_t, _u32p, C.c_uint64,
+                                             C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p]),
     ("cssm_pf_forecast_last_ms", C.c_int, [_h, _dp]),
     ("cssm_pf_observation_index", C.c_uint64, [_h]),
     ("cssm_obs_draw", C.c_int, [C.c_int, _dp, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_uint32, _dp, C.c_int]),

@@ -10,6 +10,7 @@
 // chunk's rows) and k_forecast_finish (means and the order statistics per row).  The filter's own buffers are only read.
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
+#include "cssm_sde_coef.h"
 #include "../../include/cssm_obs_draws.h"
 
 #include <cmath>
@@ -107,6 +108,188 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restric
   }
 }
 
+// ---- forecasts from a joint posterior sample (cssm_pf_forecast_posterior): particle i starts from the state of pair pick_i and
+// moves under that pair's parameter set.  A particle's set is the 3 D constrained values (mu, phi, sigma) of its posterior row, held in
+// registers up to D = 8 and read from the row (L2-resident: M x (3 D + 1) doubles) above, where two particles' sets would spill.
+template <int D, bool REG = (D <= 8)>
+struct PostParams {
+  double v[3 * D];
+  __device__ __forceinline__ void load(const double* __restrict__ row) {
+#pragma unroll
+    for (int k = 0; k < 3 * D; ++k) v[k] = row[k];
+  }
+  __device__ __forceinline__ double mu(int k) const { return v[3 * k]; }
+  __device__ __forceinline__ double phi(int k) const { return v[3 * k + 1]; }
+  __device__ __forceinline__ double sigma(int k) const { return v[3 * k + 2]; }
+};
+template <int D>
+struct PostParams<D, false> {
+  const double* row;
+  __device__ __forceinline__ void load(const double* __restrict__ r) { row = r; }
+  __device__ __forceinline__ double mu(int k) const { return row[3 * k]; }
+  __device__ __forceinline__ double phi(int k) const { return row[3 * k + 1]; }
+  __device__ __forceinline__ double sigma(int k) const { return row[3 * k + 2]; }
+};
+
+// transition_one (cssm_device.hip.h) with the component's coefficients evaluated from the particle's own parameters
+// (cssm_sde_coef: what cssm_build_rec puts into a record for them) -- the same arithmetic, so equal parameters give equal bits
+template <class P>
+__device__ __forceinline__ void transition_post(int kind, const P& prm, int k, double dt, double& xk, double zk) {
+  double c[4];
+  cssm_sde_coef(kind, prm.mu(k), prm.phi(k), prm.sigma(k), dt, c);
+  const double p0 = c[0], p1 = c[1], p2 = c[2], p3 = c[3];
+  if (kind == CSSM_SDE_BROWNIAN) {
+    xk = p3 * zk + xk;
+  } else if (kind == CSSM_SDE_GEN_BROWNIAN) {
+    double mean = xk + p0;
+    xk = p3 * zk + mean;
+  } else if (kind == CSSM_SDE_OU) {
+    double mean = p0 + (xk - p0) * p1;
+    xk = p3 * zk + mean;
+  } else {
+    double dW = p3 * zk;
+    double a = (p0 + p1 * xk) * dt;
+    double b = p2 * dW;
+    xk = (xk + a) + b;
+  }
+}
+
+// propagate_pair with a parameter set per particle: the pair's Philox blocks in the same order, normal q -> particle q / D,
+// component q % D
+template <int D, class P>
+__device__ __forceinline__ void propagate_pair_post(const ModelK& mk, double dt, uint64_t seed, uint64_t gid_even, uint32_t step,
+                                                    const double* tab, const P& pa, const P& pb, double (&xa)[D], double (&xb)[D]) {
+  const uint64_t stream = cssm_pair_stream(gid_even);
+  auto feed = [&](int q, double e) {            // (q is a compile-time constant wherever this is called)
+    if (q < D) transition_post(mk.kind(q % D), pa, q % D, dt, xa[q % D], e);
+    else if (q < 2 * D) transition_post(mk.kind((q - D + D) % D), pb, (q - D + D) % D, dt, xb[(q - D + D) % D], e);
+  };
+#pragma unroll
+  for (int B = 0; B < (D + 1) / 2; ++B) {
+    const cssm_u32x4 blk = cssm_philox_draw(seed, stream, step, CSSM_STREAM_STEP, (uint32_t)B);
+    double e0, e1;
+    cssm_normal_pair64(blk.v[0], blk.v[1], tab, &e0, &e1);
+    feed(4 * B, e0); feed(4 * B + 1, e1);
+    if (2 * B + 1 < D) {
+      cssm_normal_pair64(blk.v[2], blk.v[3], tab, &e0, &e1);
+      feed(4 * B + 2, e0); feed(4 * B + 3, e1);
+    }
+  }
+}
+// ... and for one particle of either parity (the last, unpaired particle of an odd cloud), keyed as propagate_one
+template <int D, class P>
+__device__ __forceinline__ void propagate_one_post(const ModelK& mk, double dt, uint64_t seed, uint64_t gid, uint32_t step,
+                                                   const double* tab, const P& pa, double (&x)[D]) {
+  double z[D];
+  draw_normals<D>(seed, gid, step, CSSM_STREAM_STEP, tab, z);
+#pragma unroll
+  for (int k = 0; k < D; ++k) transition_post(mk.kind(k), pa, k, dt, x[k], z[k]);
+}
+
+// k_forecast with the particle's pair: the first chunk gathers x0[pick_i] (M x D), every chunk loads row pick_i of `rows`
+// (M x (3 D + 1): the parameter set, then the observation constant p0).  pick_i = pick[i], or the draw cssm_posterior_pick(key, i, M)
+// when pick is null; pick_out (optional) receives it in the first chunk.  Everything else -- Philox streams, f from the handle's
+// records, the order keys, partial sums, samples and the carry -- is k_forecast's.
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_forecast_post(const double* __restrict__ x0, const double* __restrict__ rows, uint64_t M,
+                                                              const uint32_t* __restrict__ pick, uint32_t* __restrict__ pick_out,
+                                                              double* __restrict__ carry, int from_carry, int to_carry, uint64_t n,
+                                                              const StepRec* __restrict__ recs, uint32_t h0, uint32_t hc, ModelK mk, uint64_t key,
+                                                              int obs_df, const double* __restrict__ logtab,
+                                                              unsigned long long* __restrict__ keys, double* __restrict__ partial,
+                                                              double* __restrict__ samples) {
+  constexpr int R = D + 2;   // rows per horizon: the D state components, eta, the observation
+  constexpr size_t S = 3 * D + 1;
+  __shared__ double s_p[CSSM_BLOCK / 64][R];
+  const double* tab = stage_log_table(logtab);
+  const uint64_t npairs = (n + 1) / 2;
+  const uint64_t p = (uint64_t)blockIdx.x * CSSM_BLOCK + threadIdx.x;
+  const bool live = p < npairs;
+  const uint64_t ia = 2 * p, ib = ia + 1;
+  const bool hasb = live && ib < n;
+  const size_t rows_c = (size_t)hc * R;
+  auto pick_of = [&](uint64_t i) -> uint64_t { return pick ? (uint64_t)pick[i] : (uint64_t)cssm_posterior_pick(key, i, M); };
+  const uint64_t ma = live ? pick_of(ia) : 0, mb = hasb ? pick_of(ib) : 0;
+  if (pick_out && !from_carry) {
+    if (live) pick_out[ia] = (uint32_t)ma;
+    if (hasb) pick_out[ib] = (uint32_t)mb;
+  }
+  PostParams<D> pa, pb;
+  pa.load(rows + ma * S);
+  pb.load(rows + mb * S);
+  cssm_obs_params opa, opb;
+  opa.kind = opb.kind = mk.obs_kind; opa.df = opb.df = obs_df;
+  opa.p0 = rows[ma * S + 3 * D];
+  opb.p0 = rows[mb * S + 3 * D];
+  double xa[D], xb[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    xa[k] = live ? (from_carry ? carry[(size_t)k * n + ia] : x0[ma * D + k]) : 0.0;
+    xb[k] = hasb ? (from_carry ? carry[(size_t)k * n + ib] : x0[mb * D + k]) : 0.0;
+  }
+  for (uint32_t j = 0; j < hc; ++j) {
+    const StepRec* rec = recs + j;
+    const uint32_t h = h0 + j;
+    double ga = 0.0, gb = 0.0, ea = 0.0, eb = 0.0, oa = 0.0, ob = 0.0;
+    if (live) {
+      if (hasb) propagate_pair_post<D>(mk, rec->dt, key, ia, h, tab, pa, pb, xa, xb);
+      else propagate_one_post<D>(mk, rec->dt, key, ia, h, tab, pa, xa);
+      ga = gamma_of<D>(mk, rec, xa);
+      ea = link_of(mk.obs_kind, ga);
+      cssm_obs_stream sa = cssm_obs_stream_at(key, ia, h);
+      oa = cssm_obs_draw_one(&opa, ea, &sa, tab);
+      unsigned long long* kr = keys + (size_t)j * R * n;
+#pragma unroll
+      for (int k = 0; k < D; ++k) kr[(size_t)k * n + ia] = cssm_order_key(xa[k]);
+      kr[(size_t)D * n + ia] = cssm_order_key(ea);
+      kr[(size_t)(D + 1) * n + ia] = cssm_order_key(oa);
+      if (hasb) {
+        gb = gamma_of<D>(mk, rec, xb);
+        eb = link_of(mk.obs_kind, gb);
+        cssm_obs_stream sb = cssm_obs_stream_at(key, ib, h);
+        ob = cssm_obs_draw_one(&opb, eb, &sb, tab);
+#pragma unroll
+        for (int k = 0; k < D; ++k) kr[(size_t)k * n + ib] = cssm_order_key(xb[k]);
+        kr[(size_t)D * n + ib] = cssm_order_key(eb);
+        kr[(size_t)(D + 1) * n + ib] = cssm_order_key(ob);
+      }
+      if (samples) {   // rows of horizon j: state..., gamma, eta, obs
+        double* sr = samples + (size_t)j * (D + 3) * n;
+#pragma unroll
+        for (int k = 0; k < D; ++k) sr[(size_t)k * n + ia] = xa[k];
+        sr[(size_t)D * n + ia] = ga; sr[(size_t)(D + 1) * n + ia] = ea; sr[(size_t)(D + 2) * n + ia] = oa;
+        if (hasb) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) sr[(size_t)k * n + ib] = xb[k];
+          sr[(size_t)D * n + ib] = gb; sr[(size_t)(D + 1) * n + ib] = eb; sr[(size_t)(D + 2) * n + ib] = ob;
+        }
+      }
+    }
+    // the block's partial sums of the horizon's R rows, summed as k_forecast sums them
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      double v = (k < D) ? xa[k % D] + xb[k % D] : (k == D ? ea + eb : oa + ob);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < R) {
+      double v = 0.0;
+      for (int w = 0; w < CSSM_BLOCK / 64; ++w) v += s_p[w][threadIdx.x];
+      partial[(size_t)blockIdx.x * rows_c + (size_t)j * R + threadIdx.x] = v;
+    }
+    __syncthreads();
+  }
+  if (to_carry && live) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      carry[(size_t)k * n + ia] = xa[k];
+      if (hasb) carry[(size_t)k * n + ib] = xb[k];
+    }
+  }
+}
+
 // per row of the chunk: out[3 row] = mean (block partials / n), out[3 row + 1 / + 2] = the two selected order statistics
 static __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast_finish(const SelState* __restrict__ st, const double* __restrict__ partial, int nblocks,
                                                                        int rows, uint64_t n, double* __restrict__ out) {
@@ -187,25 +370,27 @@ extern "C" int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_
   return rc;
 }
 
-extern "C" int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t key, double interval, double* state_mean, double* state_lower,
-                                double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
-                                double* obs_upper, double* samples) {
-  if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
-  if (pf->sharded) return fail(CSSM_ESTATE, "forecasts of a sharded filter are not supported: forecast from a single-GPU handle");
-  if (!pf->initialised) return fail(CSSM_ESTATE, "not initialised");
-  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
-  if (H == 0) return CSSM_OK;
-  if (!t) return fail(CSSM_EINVAL_ARG, "null argument");
-  if (H > 0xffffffffull) return fail(CSSM_EINVAL_ARG, "too many horizons");
-  cssm_obs_params op;
-  int rc = obs_params(pf->obs_kind, pf->obs_has_scale, pf->obs_scale, pf->obs_df, &op);
-  if (rc) return rc;
+// Horizon times after t_start: finite and non-decreasing (`start` names t_start in the message)
+static int check_times(const double* t, size_t H, double t_start, const char* start) {
   for (size_t h = 0; h < H; ++h) {
-    const double prev = h ? t[h - 1] : pf->t;
+    const double prev = h ? t[h - 1] : t_start;
     if (!std::isfinite(t[h])) return fail(CSSM_EINVAL_ARG, "t[%zu] is not finite", h);
-    if (!(t[h] >= prev))
-      return fail(CSSM_EINVAL_ARG, h ? "t must be non-decreasing (t[%zu] = %.17g < %.17g)" : "t[%zu] = %.17g is before the cloud's time %.17g", h, t[h], prev);
+    if (!(t[h] >= prev)) {
+      if (h) return fail(CSSM_EINVAL_ARG, "t must be non-decreasing (t[%zu] = %.17g < %.17g)", h, t[h], prev);
+      return fail(CSSM_EINVAL_ARG, "t[%zu] = %.17g is before %s %.17g", h, t[h], start, prev);
+    }
   }
+  return CSSM_OK;
+}
+
+// The chunked driver of both forecasts.  Per chunk of horizons [h0, h0 + hn): launch(h0, hn, recs of the chunk, carry, from_carry,
+// to_carry, keys, partial, samples, blocks) runs the forecast kernel (nb_f blocks, one thread per particle pair), then one radix
+// selection over the chunk's rows and k_forecast_finish; the results land in the outputs, the device times in pf->forecast_ms.
+template <class Launch>
+static int forecast_chunks(cssm_pf* pf, double t_start, const double* t, size_t H, double interval, double* state_mean, double* state_lower,
+                           double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
+                           double* obs_upper, double* samples, Launch&& launch) {
+  int rc = CSSM_OK;
   HIP_TRY(hipSetDevice(pf->device));
   const int d = pf->d, R = d + 2;
   const uint64_t n = pf->n;
@@ -220,7 +405,7 @@ extern "C" int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t
   const long long idxr = (long long)std::floor(interval * (double)n);   // ranks as summary_impl forms them
   auto clampr = [&](long long r) { return (unsigned long long)std::min<long long>(std::max<long long>(r, 0), (long long)n - 1); };
   std::vector<StepRec> hrec(H);
-  for (size_t h = 0; h < H; ++h) cssm_build_rec(pf, h ? t[h - 1] : pf->t, t[h], 0.0, 0, (uint32_t)h, &hrec[h]);
+  for (size_t h = 0; h < H; ++h) cssm_build_rec(pf, h ? t[h - 1] : t_start, t[h], 0.0, 0, (uint32_t)h, &hrec[h]);
   std::vector<SelState> hst(rows_max);
   std::vector<double> hout(3 * rows_max);
   StepRec* drec = nullptr; double* carry = nullptr; unsigned long long* keys = nullptr; double* partial = nullptr; SelState* st = nullptr;
@@ -251,14 +436,7 @@ extern "C" int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t
     FC_TRY(hipMemcpyAsync(st, hst.data(), rows * sizeof(SelState), hipMemcpyHostToDevice, pf->stream));
     FC_TRY(hipMemsetAsync(hist, 0, rows * 512 * 4, pf->stream));
     FC_TRY(hipEventRecord(ev[0], pf->stream));
-    {
-      const int from_carry = h0 > 0, to_carry = chunked && h0 + hn < H;
-      const bool use_anc = !from_carry && pf->anc_valid;
-      DISPATCH_D(d, hipLaunchKernelGGL(k_forecast<D>, dim3(nb_f), dim3(CSSM_BLOCK), 0, pf->stream, pf->src, pf->src_stride,
-                                       (const uint32_t*)(use_anc ? pf->anc : nullptr), use_anc ? pf->src2 : nullptr, pf->src2_stride,
-                                       pf->n_split, carry, from_carry, to_carry, n, (const StepRec*)(drec + h0), (uint32_t)h0, (uint32_t)hn,
-                                       pf->mk, key, op, (const double*)pf->d_logtab, keys, partial, dsamp));
-    }
+    launch(h0, hn, (const StepRec*)(drec + h0), carry, (int)(h0 > 0), (int)(chunked && h0 + hn < H), keys, partial, dsamp, nb_f);
     FC_TRY(hipGetLastError());
     FC_TRY(hipEventRecord(ev[1], pf->stream));
     for (int shift = 56; shift >= 0; shift -= 8) {
@@ -302,6 +480,98 @@ done:
 #undef FC_ALLOC
   for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   { void* ptrs[] = {drec, carry, keys, partial, st, hist, out, dsamp}; for (void* q : ptrs) if (q) (void)hipFree(q); }
+  return rc;
+}
+
+extern "C" int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t key, double interval, double* state_mean, double* state_lower,
+                                double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
+                                double* obs_upper, double* samples) {
+  if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
+  if (pf->sharded) return fail(CSSM_ESTATE, "forecasts of a sharded filter are not supported: forecast from a single-GPU handle");
+  if (!pf->initialised) return fail(CSSM_ESTATE, "not initialised");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (H == 0) return CSSM_OK;
+  if (!t) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (H > 0xffffffffull) return fail(CSSM_EINVAL_ARG, "too many horizons");
+  cssm_obs_params op;
+  int rc = obs_params(pf->obs_kind, pf->obs_has_scale, pf->obs_scale, pf->obs_df, &op);
+  if (rc) return rc;
+  rc = check_times(t, H, pf->t, "the cloud's time");
+  if (rc) return rc;
+  const uint64_t n = pf->n;
+  return forecast_chunks(pf, pf->t, t, H, interval, state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower,
+                         obs_upper, samples,
+                         [&](size_t h0, size_t hn, const StepRec* recs, double* carry, int from_carry, int to_carry, unsigned long long* keys,
+                             double* partial, double* dsamp, int nb_f) {
+                           const bool use_anc = !from_carry && pf->anc_valid;
+                           DISPATCH_D(pf->d, hipLaunchKernelGGL(k_forecast<D>, dim3(nb_f), dim3(CSSM_BLOCK), 0, pf->stream, pf->src, pf->src_stride,
+                                                                (const uint32_t*)(use_anc ? pf->anc : nullptr), use_anc ? pf->src2 : nullptr,
+                                                                pf->src2_stride, pf->n_split, carry, from_carry, to_carry, n, recs, (uint32_t)h0,
+                                                                (uint32_t)hn, pf->mk, key, op, (const double*)pf->d_logtab, keys, partial, dsamp));
+                         });
+}
+
+extern "C" int cssm_pf_forecast_posterior(cssm_pf* pf, const cssm_model_desc* desc, const double* theta, size_t n_theta, const double* x, size_t M,
+                                          double t0, const double* t, size_t H, const uint32_t* pick, uint64_t key, double interval,
+                                          double* state_mean, double* state_lower, double* state_upper, double* eta_mean, double* eta_lower,
+                                          double* eta_upper, double* obs_mean, double* obs_lower, double* obs_upper, double* samples,
+                                          uint32_t* pick_out) {
+  if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
+  if (pf->sharded) return fail(CSSM_ESTATE, "forecasts of a sharded filter are not supported: forecast from a single-GPU handle");
+  if (!desc || !theta || !x) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (M == 0) return fail(CSSM_EINVAL_ARG, "the posterior sample is empty (M = 0)");
+  if (M > 0xffffffffull) return fail(CSSM_EINVAL_ARG, "the posterior sample has more than 2^32 - 1 rows");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (!std::isfinite(t0)) return fail(CSSM_EINVAL_ARG, "t0 is not finite");
+  if (H && !t) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (H > 0xffffffffull) return fail(CSSM_EINVAL_ARG, "too many horizons");
+  if (!desc->leaves || desc->n_leaves < 1) return fail(CSSM_EINVAL_DESC, "null model descriptor");
+  cssm_obs_params op;   // (the model's observation: LGCP has none; each row's constant goes into `rows`)
+  int rc = obs_params(pf->obs_kind, desc->leaves[0].has_scale, desc->leaves[0].scale, pf->obs_df, &op);
+  if (rc) return rc;
+  std::vector<double> rows;
+  rc = cssm_posterior_rows(pf, desc, theta, n_theta, M, rows);
+  if (rc) return rc;
+  const int d = pf->d;
+  for (size_t m = 0; m < M; ++m)
+    for (int k = 0; k < d; ++k)
+      if (!std::isfinite(x[m * d + k])) return fail(CSSM_EINVAL_ARG, "x row %zu: component %d is not finite", m, k);
+  const uint64_t n = pf->n;
+  if (pick)
+    for (uint64_t i = 0; i < n; ++i)
+      if (pick[i] >= M) return fail(CSSM_EINVAL_ARG, "pick[%llu] = %u is not below M = %zu", (unsigned long long)i, pick[i], M);
+  rc = check_times(t, H, t0, "t0 =");
+  if (rc) return rc;
+  if (H == 0) {   // nothing to forecast: the picks alone
+    if (pick_out) for (uint64_t i = 0; i < n; ++i) pick_out[i] = pick ? pick[i] : cssm_posterior_pick(key, i, M);
+    return CSSM_OK;
+  }
+  HIP_TRY(hipSetDevice(pf->device));
+  double *dx = nullptr, *drows = nullptr;
+  uint32_t *dpick = nullptr, *dpick_out = nullptr;
+#define FP_ALLOC(p, bytes) do { if (hipMalloc(&(p), (bytes)) != hipSuccess) { rc = fail(CSSM_ENOMEM, "hipMalloc(%zu) for the forecast", (size_t)(bytes)); goto done; } } while (0)
+#define FP_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(CSSM_EHIP, "%s: %s", #expr, hipGetErrorString(e__)); goto done; } } while (0)
+  FP_ALLOC(dx, M * (size_t)d * 8);
+  FP_ALLOC(drows, rows.size() * 8);
+  if (pick) FP_ALLOC(dpick, n * 4);
+  if (pick_out) FP_ALLOC(dpick_out, n * 4);
+  FP_TRY(hipMemcpy(dx, x, M * (size_t)d * 8, hipMemcpyHostToDevice));
+  FP_TRY(hipMemcpy(drows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+  if (pick) FP_TRY(hipMemcpy(dpick, pick, n * 4, hipMemcpyHostToDevice));
+  rc = forecast_chunks(pf, t0, t, H, interval, state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower,
+                       obs_upper, samples,
+                       [&](size_t h0, size_t hn, const StepRec* recs, double* carry, int from_carry, int to_carry, unsigned long long* keys,
+                           double* partial, double* dsamp, int nb_f) {
+                         DISPATCH_D(d, hipLaunchKernelGGL(k_forecast_post<D>, dim3(nb_f), dim3(CSSM_BLOCK), 0, pf->stream, (const double*)dx,
+                                                          (const double*)drows, (uint64_t)M, (const uint32_t*)dpick, dpick_out, carry, from_carry,
+                                                          to_carry, n, recs, (uint32_t)h0, (uint32_t)hn, pf->mk, key, pf->obs_df,
+                                                          (const double*)pf->d_logtab, keys, partial, dsamp));
+                       });
+  if (!rc && pick_out) FP_TRY(hipMemcpy(pick_out, dpick_out, n * 4, hipMemcpyDeviceToHost));
+done:
+#undef FP_ALLOC
+#undef FP_TRY
+  { void* ptrs[] = {dx, drows, dpick, dpick_out}; for (void* q : ptrs) if (q) (void)hipFree(q); }
   return rc;
 }
 

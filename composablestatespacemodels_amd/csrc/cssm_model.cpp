@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "cssm_records.h"
+#include "cssm_sde_coef.h"
+#include "../../include/cssm_obs_draws.h"
 
 // ------------------------------------------------------------------------------------ errors
 
@@ -164,17 +166,7 @@ void cssm_build_rec(const HostModel* pf, double t_prev, double t, double y, int 
   r->dt = dt;
   for (int k = 0; k < pf->d; ++k) {
     const Comp& c = pf->comp[k];
-    double* p = r->coef[k];
-    switch (c.kind) {
-      case CSSM_SDE_BROWNIAN: p[3] = std::sqrt(c.sigma * dt); break;
-      case CSSM_SDE_GEN_BROWNIAN: p[0] = c.mu * dt; p[3] = std::sqrt(c.sigma * dt); break;
-      case CSSM_SDE_OU: {
-        const double var = (c.sigma * c.sigma / (c.phi * 2.0)) * (1.0 - cssm_exp(c.phi * -2.0 * dt));
-        p[0] = c.mu; p[1] = cssm_exp(-c.phi * dt); p[3] = std::sqrt(var);
-        break;
-      }
-      default: p[0] = c.mu; p[1] = c.phi; p[2] = c.sigma; p[3] = std::sqrt(dt); break;
-    }
+    cssm_sde_coef(c.kind, c.mu, c.phi, c.sigma, dt, r->coef[k]);
     if (c.f_kind == CSSM_F_FIRST) {
       r->fco[k] = (c.idx == 0) ? 1.0 : 0.0;
     } else {
@@ -364,6 +356,48 @@ void cssm_pmmh_chain_decide(cssm_pmmh_chain* c, size_t it, double pll, const dou
   *ll_out = c->cur_ll; *acc_out = c->acc;
   memcpy(theta_out, c->cur.data(), c->n_theta * 8);
   memcpy(state_out, c->cur_state.data(), (size_t)c->d * 8);
+}
+
+// cssm_pf_forecast_posterior (cssm_forecast.hip): M parameter rows in flatten order, each written into `desc`'s slots as a PMMH chain
+// writes its proposals, validated and constraint-transformed by the descriptor path, -> rows[m * (3 d + 1) + ...] = (mu, phi, sigma)
+// of every component, then the observation constant p0 (cssm_obs_params_make).  The structure must be the handle's.
+int cssm_posterior_rows(const HostModel* pf, const cssm_model_desc* desc, const double* theta, size_t n_theta, size_t M,
+                        std::vector<double>& rows) {
+  OwnedDesc o;
+  int rc = own_desc(desc, &o);
+  if (rc) return rc;
+  HostModel tmp;
+  rc = build_model_into(&tmp, &o.desc);
+  if (rc) return rc;
+  bool same = tmp.d == pf->d && tmp.obs_kind == pf->obs_kind && tmp.obs_df == pf->obs_df;
+  for (int i = 0; same && i < CSSM_MAX_DIM / 4; ++i) same = tmp.mk.comp[i] == pf->mk.comp[i];
+  if (!same) return fail(CSSM_EINVAL_DESC, "the descriptor's model structure (cssm_model_structure, d, obs_kind, obs_df) differs from the handle's");
+  if (n_theta != o.slots.size()) return fail(CSSM_EINVAL_ARG, "n_theta = %zu, the descriptor flattens to %zu", n_theta, o.slots.size());
+  const int d = tmp.d;
+  const size_t S = 3 * (size_t)d + 1;
+  rows.assign(M * S, 0.0);
+  for (size_t m = 0; m < M; ++m) {
+    const double* th = theta + m * n_theta;
+    for (size_t j = 0; j < n_theta; ++j) {
+      if (!std::isfinite(th[j])) return fail(CSSM_EINVAL_ARG, "theta row %zu: entry %zu is not finite", m, j);
+      *o.slots[j] = th[j];
+    }
+    rc = build_model_into(&tmp, &o.desc);
+    if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "theta row %zu: %s", m, keep.c_str()); }
+    double* r = rows.data() + m * S;
+    for (int k = 0; k < d; ++k) {
+      const Comp& c = tmp.comp[k];
+      r[3 * k] = c.mu; r[3 * k + 1] = c.phi; r[3 * k + 2] = c.sigma;
+      if (!std::isfinite(c.mu) || !std::isfinite(c.phi) || !std::isfinite(c.sigma))
+        return fail(CSSM_EINVAL_ARG, "theta row %zu: component %d's constrained parameters are not finite", m, k);
+    }
+    cssm_obs_params op;
+    if (cssm_obs_params_make(tmp.obs_kind, o.desc.leaves[0].has_scale, o.desc.leaves[0].scale, tmp.obs_df, &op) == 0) {
+      if (!std::isfinite(op.p0)) return fail(CSSM_EINVAL_ARG, "theta row %zu: the observation scale %.17g gives a non-finite constant", m, o.desc.leaves[0].scale);
+      r[3 * d] = op.p0;
+    }
+  }
+  return CSSM_OK;
 }
 
 extern "C" int cssm_pmmh_run(cssm_pf* pf, const cssm_model_desc* desc, const double* theta0, size_t n_theta, double delta,

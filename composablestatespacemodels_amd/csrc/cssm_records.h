@@ -99,6 +99,10 @@ int cssm_fail(int code, const char* fmt, ...);   // sets the thread-local messag
 int cssm_build_model(HostModel* m, const cssm_model_desc* desc, bool update);
 // Everything of one observation that does not depend on the particle (records for the kernels).
 void cssm_build_rec(const HostModel* m, double t_prev, double t, double y, int has_obs, uint32_t step, StepRec* r);
+#if !defined(__HIPCC_RTC__)
+// The parameter rows of cssm_pf_forecast_posterior: (mu, phi, sigma) per component and the observation constant, 3 d + 1 per row.
+int cssm_posterior_rows(const HostModel* m, const cssm_model_desc* desc, const double* theta, size_t n_theta, size_t M, std::vector<double>& rows);
+#endif
 // LGCP with a time-dependent f (FilterLgcp.calcWeight evaluates f at every simulated time, model/ParticleFilter.scala:193-205):
 // append the n_sub x d coefficient rows of records recs[first .. first + count) to `table` and set their fsub_off;
 // CSSM_ENOMEM if the table would exceed 1 GiB.  No-op for every other model.

@@ -25,7 +25,7 @@ from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .model import Data, Model, TimedObservation, split_data
+from .model import Data, Model, Parameters, TimedObservation, UnparamModel, split_data
 
 _dp = C.POINTER(C.c_double)
 
@@ -224,6 +224,42 @@ class NativePf:
         out["key"] = key
         return out
 
+    def forecast_posterior(self, theta, x, t0: float, times, key: Optional[int] = None, interval: float = 0.975, pick=None,
+                           want_samples: bool = False):
+        """cssm_pf_forecast_posterior: forecasts from a joint posterior sample of M pairs -- theta[M, n_theta] in flatten order and
+        x[M, d], their states at t0 -- with this handle's N particles, particle i on pair pick[i] (drawn under `key` when pick is
+        None).  The same dict as ``forecast``, plus pick[N] (uint32).  The handle's model gives the structure; its cloud, time and
+        parameters are not used or touched."""
+        theta = np.ascontiguousarray(np.atleast_2d(np.asarray(theta, dtype=np.float64)))
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(theta.shape[0], -1))
+        M, nt = theta.shape
+        if x.shape != (M, self.d):
+            raise ValueError(f"x must be M x d = {M} x {self.d} (got {x.shape})")
+        t = np.ascontiguousarray(np.atleast_1d(np.asarray(times, dtype=np.float64)))
+        H = len(t)
+        key = self.forecast_key() if key is None else int(key) & (2**64 - 1)
+        pk = None
+        if pick is not None:
+            p = np.asarray(pick)
+            if p.shape != (self.n,) or (p < 0).any():
+                raise ValueError(f"pick must hold N = {self.n} non-negative indices")
+            pk = np.ascontiguousarray(p, dtype=np.uint32)
+        out = {k: np.zeros((H, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
+        out.update({k: np.zeros(H) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        samples = np.zeros((H, self.d + 3, self.n)) if want_samples else None
+        pick_out = np.zeros(self.n, dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        _abi.check(self.lib.cssm_pf_forecast_posterior(self._h, self._desc.ptr(), _p(theta), nt, _p(x), M, float(t0), _p(t), H,
+                                                       _p(pk, u32) if pk is not None else None, key, float(interval),
+                                                       _p(out["state_mean"]), _p(out["state_lower"]), _p(out["state_upper"]),
+                                                       _p(out["eta_mean"]), _p(out["eta_lower"]), _p(out["eta_upper"]), _p(out["obs_mean"]),
+                                                       _p(out["obs_lower"]), _p(out["obs_upper"]), _p(samples) if want_samples else None,
+                                                       _p(pick_out, u32)))
+        out["samples"] = samples
+        out["key"] = key
+        out["pick"] = pick_out
+        return out
+
     def forecast_last_ms(self) -> Tuple[float, float]:
         """(k_forecast, selection) device milliseconds of the last forecast (cssm_pf_forecast_last_ms)."""
         ms = np.zeros(2)
@@ -289,7 +325,8 @@ class NativePfBatch:
     def __init__(self, model: Model, n: int, chains: int, device: int = 0):
         self.lib = _abi.load_library()
         self._h = C.c_void_p()
-        _abi.check(self.lib.cssm_pfb_create(model.descriptor().ptr(), int(n), int(chains), int(device), C.byref(self._h)))
+        self._desc = model.descriptor()
+        _abi.check(self.lib.cssm_pfb_create(self._desc.ptr(), int(n), int(chains), int(device), C.byref(self._h)))
         self.B, self.n = int(chains), int(n)
         self.d = int(self.lib.cssm_pf_dim(self.lib.cssm_pfb_chain(self._h, 0)))
 
@@ -322,7 +359,7 @@ class NativePfBatch:
         """Chain k as a NativePf view (inspection only; the batch owns the handle)."""
         v = _PfView.__new__(_PfView)
         v.lib = self.lib; v._h = C.c_void_p(self.lib.cssm_pfb_chain(self._h, int(k))); v.n = self.n; v.d = self.d; v.generation = 0
-        v.model = None; v.seed = 0
+        v.model = None; v.seed = 0; v._desc = self._desc
         return v
 
 
@@ -705,11 +742,24 @@ class ParticleFilter:
         pf = ParticleFilter._forecast_handle(s, mod)
         times = [float(v) for v in times]
         r = pf.forecast(times, ParticleFilter._key(pf, seed), float(interval))
-        return [ForecastOut(tt, float(r["obs_mean"][h]), CredibleInterval(float(r["obs_lower"][h]), float(r["obs_upper"][h])),
-                            float(r["eta_mean"][h]), CredibleInterval(float(r["eta_lower"][h]), float(r["eta_upper"][h])),
-                            r["state_mean"][h].copy(),
-                            [CredibleInterval(float(a), float(b)) for a, b in zip(r["state_lower"][h], r["state_upper"][h])])
-                for h, tt in enumerate(times)]
+        return _forecast_outs(times, r)
+
+    @staticmethod
+    def forecastPosterior(posterior, unparam: UnparamModel, t0: float, times: Sequence[float], n: int, interval: float = 0.975,
+                          seed: Optional[int] = None, params: Optional[Parameters] = None) -> List[ForecastOut]:
+        """SimulateData.forecast(unparamModel, t, n)(posterior) + summariseForecast (Data.scala:196-231): n particles, each on a pair
+        (theta, x) drawn from the joint posterior sample, pushed from t0 through `times` under its own parameters; one ForecastOut per
+        time, all formed in one device call.  `posterior`: MetropStates (e.g. formats.read_pmmh_json(path, burn_in, thin)), or the
+        arrays (theta[M, n_theta], last_state[M, d]) of pmmh_native* (pmmh.posterior_rows selects burn-in and thinning) with `params`
+        the parameter tree the rows flatten.  seed = the Philox key of the draws; None: the default key of a fresh filter."""
+        theta, x, template = _posterior_arrays(posterior, params)
+        pf = NativePf(unparam.run(template.withFlat(theta[0])), int(n))
+        try:
+            times = [float(v) for v in times]
+            r = pf.forecast_posterior(theta, x, float(t0), times, pf.forecast_key() if seed is None else int(seed), float(interval))
+        finally:
+            pf.close()
+        return _forecast_outs(times, r)
 
     @staticmethod
     def meanState(s: "PfState") -> np.ndarray:
@@ -741,6 +791,37 @@ class ParticleFilter:
     @staticmethod
     def mean(s: Sequence[float]) -> float:  # :522-524
         return float(np.sum(s)) / len(s)
+
+
+def _forecast_outs(times: Sequence[float], r) -> List[ForecastOut]:
+    """One ForecastOut per time from the per-horizon arrays of NativePf.forecast / forecast_posterior."""
+    return [ForecastOut(tt, float(r["obs_mean"][h]), CredibleInterval(float(r["obs_lower"][h]), float(r["obs_upper"][h])),
+                        float(r["eta_mean"][h]), CredibleInterval(float(r["eta_lower"][h]), float(r["eta_upper"][h])),
+                        r["state_mean"][h].copy(),
+                        [CredibleInterval(float(a), float(b)) for a, b in zip(r["state_lower"][h], r["state_upper"][h])])
+            for h, tt in enumerate(times)]
+
+
+def _posterior_arrays(posterior, params: Optional[Parameters]):
+    """(theta[M, n_theta], x[M, d], a parameter tree of the rows' shape) from MetropStates or from (theta, last_state) arrays."""
+    if isinstance(posterior, tuple) and len(posterior) == 2 and not hasattr(posterior[0], "params"):
+        if params is None:
+            raise ValueError("a posterior given as (theta, last_state) arrays needs `params`, the parameter tree its rows flatten")
+        theta = np.atleast_2d(np.asarray(posterior[0], dtype=np.float64))
+        x = np.asarray(posterior[1], dtype=np.float64).reshape(theta.shape[0], -1)
+        template = params
+    else:
+        states = list(posterior)
+        if not states:
+            raise ValueError("the posterior sample is empty")
+        if any(s.sde is None for s in states):
+            raise ValueError("every MetropState needs its sampled state (sde)")
+        theta = np.array([s.params.flattenParams() for s in states], dtype=np.float64)
+        x = np.array([np.asarray(s.sde, dtype=np.float64).ravel() for s in states])
+        template = states[0].params
+    if theta.shape[0] == 0:
+        raise ValueError("the posterior sample is empty")
+    return np.ascontiguousarray(theta), np.ascontiguousarray(x), template
 
 
 def _model_signature(mod: Optional[Model]):

@@ -214,3 +214,14 @@ def pmmh_native_speculative(unparam: UnparamModel, init: Parameters, data, n: in
     finally:
         lib.cssm_pfb_destroy(hb)
     return ll, th, acc, last
+
+
+def posterior_rows(theta, last_state, burn_in: int = 0, thin: int = 1):
+    """The posterior sample of a chain's output arrays (theta[iters, n_theta], last_state[iters, d]): the rows formats.read_pmmh_json
+    keeps of the same chain written one MetropState per line -- ``burn_in`` dropped, then every ``thin``-th."""
+    if burn_in < 0 or thin < 1:
+        raise ValueError("burn_in >= 0 and thin >= 1")
+    theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+    last_state = np.asarray(last_state, dtype=np.float64).reshape(theta.shape[0], -1)
+    keep = np.arange(burn_in, theta.shape[0], thin)
+    return theta[keep], last_state[keep]

@@ -90,6 +90,16 @@ CSSM_HD int cssm_obs_params_make(int kind, int has_scale, double scale, int df, 
   }
 }
 
+/* The joint posterior pair particle i forecasts from (cssm_pf_forecast_posterior): Streaming.createDist's `sampleOne` of the
+ * posterior sample (Resampling.scala:151-154), abs(nextInt) % M, with nextInt = word 0 of the counter (key, i, 0, CSSM_STREAM_POST, 0)
+ * -- the same |int32| mod M form as the handle's sampleOne index of `filter`. */
+#define CSSM_STREAM_POST 9u
+CSSM_HD uint32_t cssm_posterior_pick(uint64_t key, uint64_t i, uint64_t M) {
+  const int32_t r = (int32_t)cssm_philox_draw(key, i, 0u, CSSM_STREAM_POST, 0u).v[0];
+  const uint32_t a = r < 0 ? (uint32_t)0 - (uint32_t)r : (uint32_t)r;
+  return (uint32_t)((uint64_t)a % M);
+}
+
 /* one particle's stream of Philox blocks */
 typedef struct {
   uint64_t key, gid;

@@ -383,8 +383,28 @@ int cssm_pf_summary(cssm_pf* pf, double interval, double* state_mean, double* st
 int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t key, double interval, double* state_mean, double* state_lower,
                      double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
                      double* obs_upper, double* samples);
-/* Device time of the last cssm_pf_forecast (HIP events around its kernels), ms2[0] = k_forecast, ms2[1] = the radix selection and
- * the finishing kernel, summed over chunks.  CSSM_ESTATE before the first forecast. */
+/* Forecasts from a joint posterior sample p(x, theta | y): SimulateData.forecast(unparamModel, t, n)(s: Rand[(Parameters, State)]) +
+ * summariseForecast (model/Data.scala:196-231), the posterior given as M pairs -- theta[m * n_theta ..] in flatten order (cssm_desc_flatten,
+ * the theta rows of cssm_pmmh_run*) and x[m * d ..] the state of pair m at time t0 (their last_state rows).  N = the handle's particle
+ * count is the reference's n; particle i takes pair pick_i (Streaming.createDist = sampleOne, Resampling.scala:151-154):
+ *   pick_i = pick[i] if `pick` is given (N host indices < M), else |int32(word 0 of Philox(key, i, 0, CSSM_STREAM_POST, 0))| mod M
+ *            (cssm_posterior_pick, include/cssm_obs_draws.h);
+ * and from x[pick_i] at t0 runs cssm_pf_forecast's horizons under theta_{pick_i}: the same normals (CSSM_STREAM_STEP, `key`, horizon h,
+ * paired streams) with its own transition coefficients, f(x, t) of the handle's model (f has no parameters), one observation with its own
+ * scale (CSSM_STREAM_OBS).  Summaries, samples layout and ranks are cssm_pf_forecast's.  pick_out (optional, N): the pair of each particle.
+ * `desc` gives the structure, which must be the handle's (cssm_model_structure words, d, obs_kind, obs_df); each row is written into its
+ * parameter slots, validated and constraint-transformed as cssm_pf_set_params would.  The handle only lends its device, stream, contract
+ * table and particle count: its cloud, time, parameters, key, ll, ESS and observation index stay as they were (any single-GPU handle,
+ * cssm_pfb_chain views included, initialised or not).  The device times land where cssm_pf_forecast_last_ms reads them.
+ * Errors: CSSM_ESTATE (sharded handle); CSSM_EINVAL_DESC (structure differs from the handle's); CSSM_EINVAL_ARG (M = 0, n_theta not
+ * the descriptor's, a non-finite theta or x entry or a row the model rejects -- naming the row --, pick[i] >= M, interval outside (0, 1],
+ * t not finite, before t0 or decreasing; LGCP and models without the scale their observation needs, as cssm_pf_forecast). */
+int cssm_pf_forecast_posterior(cssm_pf* pf, const cssm_model_desc* desc, const double* theta, size_t n_theta, const double* x, size_t M,
+                               double t0, const double* t, size_t H, const uint32_t* pick, uint64_t key, double interval,
+                               double* state_mean, double* state_lower, double* state_upper, double* eta_mean, double* eta_lower,
+                               double* eta_upper, double* obs_mean, double* obs_lower, double* obs_upper, double* samples, uint32_t* pick_out);
+/* Device time of the last cssm_pf_forecast or cssm_pf_forecast_posterior (HIP events around its kernels), ms2[0] = k_forecast or
+ * k_forecast_post, ms2[1] = the radix selection and the finishing kernel, summed over chunks.  CSSM_ESTATE before the first forecast. */
 int cssm_pf_forecast_last_ms(cssm_pf* pf, double* ms2);
 /* The handle's observation index: the number of observations the current cloud has seen (the default forecast key of the Python
  * mirror is cssm_pf_run_key(seed, 2^63 | this)). */

@@ -230,17 +230,36 @@ class Filter {
     Vec sm(H * d_), sl(H * d_), su(H * d_), em(H), el(H), eu(H), om(H), ol(H), ou(H);
     check(cssm_pf_forecast(h_, times.data(), H, key, interval, sm.data(), sl.data(), su.data(), em.data(), el.data(), eu.data(), om.data(),
                            ol.data(), ou.data(), nullptr));
+    return forecast_outs(times, sm, sl, su, em, el, eu, om, ol, ou);
+  }
+  // forecasts from a joint posterior sample (SimulateData.forecast + summariseForecast, Data.scala:196-231): M pairs, theta rows in
+  // flatten order (M x n_theta, e.g. cssm_pmmh_run's theta output) and their states at t0 (M x d, its last_state); this filter's N
+  // particles each take a pair (drawn under `key`; key 0 = the default key as in forecast).  `structure`: the model the rows
+  // parameterise (the filter's structure).  The filter is not touched.
+  std::vector<ForecastOut> forecastPosterior(const ParamModel& structure, const Vec& theta, size_t n_theta, const Vec& x, double t0,
+                                             const Vec& times, double interval = 0.975, uint64_t key = 0) {
+    const size_t H = times.size(), M = n_theta ? theta.size() / n_theta : 0;
+    if (M * n_theta != theta.size() || x.size() != M * (size_t)d_) throw std::invalid_argument("theta must be M x n_theta and x M x d");
+    if (key == 0) key = cssm_pf_run_key(seed_, (1ull << 63) | cssm_pf_observation_index(h_));
+    Vec sm(H * d_), sl(H * d_), su(H * d_), em(H), el(H), eu(H), om(H), ol(H), ou(H);
+    check(cssm_pf_forecast_posterior(h_, structure.desc(), theta.data(), n_theta, x.data(), M, t0, times.data(), H, nullptr, key, interval,
+                                     sm.data(), sl.data(), su.data(), em.data(), el.data(), eu.data(), om.data(), ol.data(), ou.data(),
+                                     nullptr, nullptr));
+    return forecast_outs(times, sm, sl, su, em, el, eu, om, ol, ou);
+  }
+  cssm_pf* handle() { return h_; }
+
+ private:
+  std::vector<ForecastOut> forecast_outs(const Vec& times, const Vec& sm, const Vec& sl, const Vec& su, const Vec& em, const Vec& el,
+                                         const Vec& eu, const Vec& om, const Vec& ol, const Vec& ou) const {
     std::vector<ForecastOut> out;
-    for (size_t h = 0; h < H; ++h) {
+    for (size_t h = 0; h < times.size(); ++h) {
       ForecastOut f{times[h], om[h], {ol[h], ou[h]}, em[h], {el[h], eu[h]}, Vec(sm.begin() + h * d_, sm.begin() + (h + 1) * d_), {}};
       for (int k = 0; k < d_; ++k) f.stateIntervals.push_back({sl[h * d_ + k], su[h * d_ + k]});
       out.push_back(std::move(f));
     }
     return out;
   }
-  cssm_pf* handle() { return h_; }
-
- private:
   static void split(const std::vector<Data>& data, Vec& t, Vec& y, std::vector<uint8_t>& has) {
     for (auto& d : data) { t.push_back(d.t); y.push_back(d.observation.value_or(0.0)); has.push_back(d.observation ? 1 : 0); }
   }
