@@ -327,6 +327,9 @@ int cssm_upload_recs(cssm_pf* pf, size_t first, size_t count, bool chain) {
     hipLaunchKernelGGL(k_put_rec, dim3(1), dim3(128), 0, pf->stream, pf->h_recs[first], pf->d_recs + first, stamp);
     HIP_TRY(hipGetLastError());
   } else if (by_copy || !pf->h_recs_dev || count > 0x7fffffffu) {
+    // (no kernel carries record 0 on this path, so nothing stamps the call's first instruction: the stamp of an EARLIER call must
+    //  not stand in for it -- cssm_pf_last_device_us would report an interval that spans several calls.  Zero = "no stamp".)
+    if (stamp) HIP_TRY(hipMemsetAsync(&stamp->t_first, 0, sizeof(stamp->t_first), pf->stream));
     HIP_TRY(hipMemcpyAsync(pf->d_recs + first, pf->h_recs + first, count * sizeof(StepRec), hipMemcpyHostToDevice, pf->stream));
   } else {
     hipLaunchKernelGGL(k_fetch_recs, dim3((uint32_t)count), dim3(128), 0, pf->stream, (const StepRec*)(pf->h_recs_dev + first), pf->d_recs + first, stamp);
@@ -718,7 +721,9 @@ extern "C" int cssm_pf_propagate(cssm_pf* pf, double t, double obs, int has_obs)
   rc = cssm_launch_propagate(pf, pf->d_recs);
   pf->safe_sums = false;
   if (rc) return rc;
-  pf->wmode = false;
+  // (an observation without a datum stores no log-weights: `logw` still holds what the last weighted step left, weights or
+  //  log-weights, and the getters must go on saying which)
+  if (pf->obs_kind == CSSM_OBS_LGCP || pf->h_recs[0].has_obs) pf->wmode = false;
   // nobody decodes this step's running max on the device: clear every set of max slots AND of group sums for the next weighted
   // step (wparity restarts at 0 below: a native fused step that ran on set 0 before this call left its group sums there, and
   // k_offspring's publisher clears only the two sets it does not use -- the next native step would add onto them)

@@ -141,7 +141,9 @@ int cssm_pf_create_shard(const cssm_model_desc* desc, uint64_t n_global, uint64_
 void cssm_pf_destroy(cssm_pf* pf);
 
 /* New parameters for the same model structure, without reallocating: one call per PMMH
- * proposal (model/PMMH.scala:71, `pf(propParams)`). */
+ * proposal (model/PMMH.scala:71, `pf(propParams)`).  Allowed at any moment, also between the observations of a running series
+ * (the cloud stays, the next transition and weights use the new parameters).  A descriptor of another structure is refused with
+ * CSSM_EINVAL_DESC and leaves the handle exactly as it was. */
 int cssm_pf_set_params(cssm_pf* pf, const cssm_model_desc* desc);
 
 /* New Philox key (a fresh filter run must not reuse variates). */
@@ -163,7 +165,12 @@ int cssm_pf_init_from(cssm_pf* pf, double t0, const double* state_d);
 
 /* stepFilter (model/ParticleFilter.scala:116-132; LGCP: :210-226).  `has_obs` = 0 is the
  * `None` branch (:121): propagate only, ll and ess unchanged.  ll_out = accumulated
- * log-likelihood, ess_out = floor(1 / sum(normalised w^2)) (:431-434). */
+ * log-likelihood, ess_out = floor(1 / sum(normalised w^2)) (:431-434).
+ * t is not compared with the handle's clock on the host: a time BEFORE it gives a negative increment, the transition's variance
+ * and with it every log-weight is NaN, and a weighted step returns CSSM_ENONFINITE like any other step whose weights are unusable
+ * (LGCP: the number of sub-steps is ceil(dt / delta), so a negative increment is the caller's error and undefined).  After a call
+ * that returned CSSM_ENONFINITE the series is over: the cloud is undefined until cssm_pf_init / _init_from / a batch call draws a
+ * new one, which then behaves exactly as on a new handle. */
 int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out);
 
 /* stepFilter split at the resampler, for a `Resample[A]` the library does not have natively (any host function:
@@ -171,7 +178,12 @@ int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out,
  * cloud to t, weigh it; `has_obs` = 0: propagate only); the host reads the proposed cloud and the log-weights
  * (cssm_pf_get_proposed, cssm_pf_get_logw), forms w1 = exp(w - max), applies its resampler, and hands the resampled cloud
  * (SoA, d x N, host) back with cssm_pf_adopt together with the new ll and ess (:126-130).  A parity path: the cloud crosses
- * PCIe twice per observation.  After cssm_pf_propagate without cssm_pf_adopt the proposed cloud is the current one. */
+ * PCIe twice per observation.  After cssm_pf_propagate without cssm_pf_adopt the proposed cloud is the current one.
+ * Between the two calls parameters, key and options may change and every read-only call may run.  No native resampling stands
+ * behind a propagated or adopted cloud: cssm_pf_get_ancestors gives the identity, and after cssm_pf_adopt cssm_pf_get_proposed
+ * gives the adopted cloud (it replaced the proposed one in place).  A weighted cssm_pf_propagate keeps log-weights
+ * (cssm_pf_get_logw); one WITHOUT a datum stores none and leaves weights / log-weights and their getters as the last weighted
+ * step left them. */
 int cssm_pf_propagate(cssm_pf* pf, double t, double obs, int has_obs);
 int cssm_pf_adopt(cssm_pf* pf, const double* state_dN, double ll, int32_t ess);
 
@@ -179,7 +191,10 @@ int cssm_pf_adopt(cssm_pf* pf, const double* state_dN, double ll, int32_t ess);
 
 /* llFilter (model/ParticleFilter.scala:137-140): t0 = min t, init, fold stepFilter over the
  * data in the order given.  Optional outputs (may be NULL): ll_t[T] running log-likelihood
- * after each datum, ess_t[T].  No host synchronisation happens inside the loop. */
+ * after each datum, ess_t[T].  No host synchronisation happens inside the loop.
+ * T = 0 is refused with CSSM_EINVAL_ARG (the reference's minBy throws on an empty Vector) by all three batch calls and leaves the
+ * handle as it was; an observation without a datum reports the ESS before it (a continued call that starts on one: the ESS the
+ * handle had -- N behind a new cloud, the caller's behind cssm_pf_adopt). */
 int cssm_pf_ll_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs,
                       size_t T, double* ll_out, double* ll_t, int32_t* ess_t);
 /* The same for T MORE observations of a filter that is already running (initialised by cssm_pf_init / _init_from, or left
@@ -208,7 +223,9 @@ int cssm_pf_last_loop_ms(cssm_pf* pf, float* ms_out);
  * call's closing kernel (k_finish) stamps it again and hands both to the host with the results.  *us_out = first instruction of the
  * call's first kernel -> the closing kernel's copy of the results, in microseconds (resolution 10 ns).  What bench.py reports per
  * timed leg (`device_ms_each`) beside the host's wall time.  CSSM_ESTATE if the last call left no pair of stamps (a call that drew
- * a new cloud: the scalars are reset behind its first kernel). */
+ * a new cloud: the scalars are reset behind its first kernel; a call whose records travelled by hipMemcpyAsync -- environment
+ * CSSM_UPLOAD_MEMCPY=1 -- where no kernel carries record 0: the stamp is then cleared, never left over from an earlier call).
+ * The interval never spans more than the one call. */
 int cssm_pf_last_device_us(cssm_pf* pf, double* us_out);
 
 /* 1 if nothing is queued or running on the handle's stream (hipStreamQuery: every launch of the calls so far has completed as the runtime
@@ -216,7 +233,14 @@ int cssm_pf_last_device_us(cssm_pf* pf, double* us_out);
  * a caller that wants the runtime's own confirmation (bench.py does, right behind its timed region) asks here -- no wait, no packet. */
 int cssm_pf_stream_idle(cssm_pf* pf);
 
-/* Debug/verification options.  CSSM_OPT_EXACT_OFFSPRING = 1 makes the offspring kernel evaluate the
+/* Debug/verification options.  cssm_pf_set_option may be called at ANY moment, also between two observations of a running series and
+ * between cssm_pf_propagate and cssm_pf_adopt: a new value holds from the next launch on, whatever the filter left behind.  Every
+ * option below except CSSM_OPT_RESAMPLER is a VERIFICATION SWITCH: results are bit-identical in every setting and across every
+ * switch in the middle of a series (tests/test_gpu_call_sequences.py drives reused handles through seeded sequences of switches and
+ * compares every call with the oracle).  CSSM_OPT_RESAMPLER changes results: from the next weighted observation on the new
+ * resampler selects the ancestors.  An unknown option or a value outside an option's range where one is checked (CSSM_OPT_RESAMPLER,
+ * a negative CSSM_OPT_FORECAST_CAP) is refused with CSSM_EINVAL_ARG and changes nothing.
+ * CSSM_OPT_EXACT_OFFSPRING = 1 makes the offspring kernel evaluate the
  * contract's exact predicate for every particle instead of only where its fp64 position estimate is
  * within the error band of a slot boundary; results are identical by construction (tests compare).
  * Value 2 (systematic resampling): every third particle only -- threads then hand over single particles, as the
@@ -343,7 +367,9 @@ int cssm_pf_get_particles(cssm_pf* pf, double* out_dN);
 int cssm_pf_get_ancestors(cssm_pf* pf, uint32_t* out_N);
 /* Log-weights of the last weighted step, before resampling (model/ParticleFilter.scala:123) -- where the handle keeps them: LGCP
  * filters, the multinomial resampler, cssm_pf_propagate, CSSM_OPT_FUSED_SUMS = 0, an observation that was redone relative to
- * the max.  Otherwise CSSM_ESTATE: the fused kernel stores the WEIGHTS in their place, see cssm_pf_get_weights. */
+ * the max.  Otherwise CSSM_ESTATE: the fused kernel stores the WEIGHTS in their place, see cssm_pf_get_weights.  Which of the two is
+ * kept follows the LAST weighted observation (not the options' current values); exactly one of the two getters answers.  Before the
+ * first weighted observation since the cloud was drawn the buffer's contents are unspecified. */
 int cssm_pf_get_logw(cssm_pf* pf, double* out_N);
 /* The weights w1_i = exp(min(w_i - c, 2^-20)) of the last weighted step -- what stepFilter hands its resampler as the second
  * argument, rescaled by the observation's reference level c instead of the max (model/ParticleFilter.scala:125-126;

@@ -704,6 +704,15 @@ void oracle_pf_set_particles(oracle_pf* pf, const double* soa) {
   for (uint64_t i = 0; i < pf->n; ++i) for (int k = 0; k < pf->d; ++k) pf->x[i * pf->d + k] = soa[(uint64_t)k * pf->n + i];
 }
 
+/* The second half of a step split at the resampler (cssm_pf_adopt): the host's resampled cloud (SoA in, [d][n]) becomes the
+ * current one together with the log-likelihood and ESS the host formed (model/ParticleFilter.scala:126-130).  No native
+ * resampling stands behind this cloud: the ancestors are the identity, and no max predicts the next level. */
+void oracle_pf_adopt(oracle_pf* pf, const double* soa, double ll, int32_t ess) {
+  oracle_pf_set_particles(pf, soa);
+  for (uint64_t i = 0; i < pf->n; ++i) pf->anc[i] = (uint32_t)i;
+  pf->ll = ll; pf->ess = ess;
+}
+
 /* ------------------------------------------------------------------ A9 drivers */
 
 /* Resampling.sampleOne, model/Resampling.scala:151-154: abs(nextInt) % size */

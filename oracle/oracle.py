@@ -63,6 +63,7 @@ def lib() -> C.CDLL:
             "oracle_pf_set_shard": (None, [vp, C.c_uint64, C.c_uint64]),
             "oracle_pf_propagate_only": (C.c_int, [vp, C.c_double, C.c_double, C.c_int]),
             "oracle_pf_set_particles": (None, [vp, _dp]),
+            "oracle_pf_adopt": (None, [vp, _dp, C.c_double, C.c_int32]),
             "oracle_pf_num_particles": (C.c_uint64, [vp]),
             "oracle_pf_dim": (C.c_int, [vp]),
             "oracle_pf_get_particles": (None, [vp, _dp]),
@@ -208,6 +209,12 @@ class OraclePf:
         a = np.ascontiguousarray(soa, dtype=np.float64)
         assert a.shape == (self.d, self.n)
         lib().oracle_pf_set_particles(self._h, _p(a))
+
+    def adopt(self, soa, ll, ess):
+        """cssm_pf_adopt: the host-resampled cloud with the ll and ESS the host formed; ancestors become the identity."""
+        a = np.ascontiguousarray(soa, dtype=np.float64)
+        assert a.shape == (self.d, self.n)
+        lib().oracle_pf_adopt(self._h, _p(a), float(ll), int(ess))
 
     def summary(self, interval=0.975):
         m, lo, hi = np.zeros(self.d), np.zeros(self.d), np.zeros(self.d)
