@@ -28,6 +28,7 @@ OBS_POISSON, OBS_GAUSSIAN, OBS_LGCP = 0, 1, 2
 OBS_NEGBIN, OBS_ZIP, OBS_BERNOULLI, OBS_STUDENT_T, OBS_BETA = 3, 4, 5, 6, 7
 MAX_DIM = 16
 MAX_LEAVES = 16
+FLEET_MAX_N = 4096   # CSSM_FLEET_MAX_N
 
 _dp = C.POINTER(C.c_double)
 
@@ -165,6 +166,22 @@ SYMBOLS = [
     ("cssm_pfb_filter", C.c_int, [_h, C.POINTER(_descp), _u64p, _dp, _dp, _u8p, C.c_size_t, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_pmmh_run_batched", C.c_int, [_h, _descp, _dp, C.c_size_t, C.c_double, _dp, _dp, _u8p, C.c_size_t, _u64p, C.c_size_t, _dp, _dp, _i32p, _dp]),
     ("cssm_pmmh_run_speculative", C.c_int, [_h, _descp, _dp, C.c_size_t, C.c_double, _dp, _dp, _u8p, C.c_size_t, C.c_uint64, C.c_size_t, _dp, _dp, _i32p, _dp]),
+    ("cssm_fleet_create", C.c_int, [_descp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_h)]),
+    ("cssm_fleet_destroy", None, [_h]),
+    ("cssm_fleet_num_series", C.c_uint32, [_h]),
+    ("cssm_fleet_num_particles", C.c_uint64, [_h]),
+    ("cssm_fleet_set_params", C.c_int, [_h, C.POINTER(_descp)]),
+    ("cssm_fleet_reseed", C.c_int, [_h, _u64p]),
+    ("cssm_fleet_set_option", C.c_int, [_h, C.c_int, C.c_int]),
+    ("cssm_fleet_ll_filter", C.c_int, [_h, _u64p, _dp, _dp, _u8p, _dp, _dp, _i32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_init", C.c_int, [_h, _dp]),
+    ("cssm_fleet_step", C.c_int, [_h, _u8p, _dp, _dp, _u8p, _dp, _i32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_summary", C.c_int, [_h, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("cssm_fleet_get_particles", C.c_int, [_h, C.c_uint32, _dp]),
+    ("cssm_fleet_get_ancestors", C.c_int, [_h, C.c_uint32, _u32p]),
+    ("cssm_fleet_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_fleet_pack_record", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32,
+                                         _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("cssm_diag_copy_ceiling", C.c_int, [C.c_int, C.c_size_t, C.c_int, _dp]),
     ("cssm_contract_eval", C.c_int, [C.c_int, C.c_int, _dp, C.c_size_t, _dp, C.c_size_t]),
     ("cssm_desc_flatten", C.c_int, [_descp, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -1,0 +1,533 @@
+// cssm_fleet.hip -- host side of the fleet filter (include/cssm_pf.h, "fleet of independent series"): S series of one model structure,
+// N <= CSSM_FLEET_MAX_N particles each, parameters / Philox key / data / clock of its own per series, advanced by ONE launch whose
+// blocks are the series (cssm_fleet.hip.h: k_fleet_series, one object per latent dimension).  Also k_fleet_summary (getIntervals of
+// every series, one block per (series, row)).  A fleet call never degenerates into S single-handle runs: what the kernels do not
+// serve is refused when the fleet is created or parameterised.
+//
+// Per-observation constants: the host builds every record with cssm_build_rec -- the function the single handle uses, so its bits by
+// construction -- and uploads the compact form (FleetRecHead + 5 d doubles: 80 + 40 d bytes per observation, not sizeof(StepRec)).
+// Records of different series are independent: large calls build them on a few host threads.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <thread>
+
+#include "cssm_internal.h"
+#include "cssm_kernels.hip.h"
+#include "cssm_fleet.hip.h"
+
+static_assert(CSSM_FLEET_MAX_N <= 4096, "k_fleet_summary sorts at most 4096 keys in LDS; k_fleet_series holds 12 bytes per particle there");
+
+struct cssm_fleet {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // filter / step call, summary
+  uint32_t n = 0, S = 0;
+  int d = 0, threads = 64;
+  size_t lds = 0;
+  HostModel base;                       // the structure every series shares
+  std::vector<HostModel> models;        // per series: parameters, key (HostModel::seed), n_global = n
+  std::vector<double> t;                // per series: its clock
+  std::vector<uint32_t> step;           // ... its observation index (Philox counter word; parity = the buffer that holds its cloud)
+  std::vector<uint8_t> live;            // ... a cloud exists (initialised and not failed since)
+  bool par_dirty = true;
+  // device
+  double* state = nullptr; uint32_t* anc = nullptr; FleetSeries* ser = nullptr; FleetPar* par = nullptr; double* logtab = nullptr;
+  unsigned char* d_stage = nullptr; size_t stage_cap = 0;
+  double* d_ll_t = nullptr; int32_t* d_ess_t = nullptr; size_t res_cap = 0;
+  double* d_tmp = nullptr;              // d x n: cssm_fleet_get_particles
+  double* d_sm = nullptr; size_t sm_cap = 0;   // summary: [S][d] f coefficients, [S][d + 1][3] results, [S] buffer numbers
+  // host staging (pinned)
+  unsigned char* h_stage = nullptr; size_t h_stage_cap = 0;
+  std::vector<FleetSeries> h_ser;
+  float ms_call = -1.f, ms_summary = -1.f;
+};
+
+#define FLEET_SERVED "cssm_pf_* (one handle per series) and cssm_pfb_* (batch of chains) serve it"
+
+template <class F>
+static void fleet_parallel(size_t count, size_t work, F f) {
+  unsigned nt = std::thread::hardware_concurrency();
+  nt = std::min<unsigned>(nt ? nt : 1u, 8u);
+  if (work < 8192 || count < 2 * nt || nt < 2) { f((size_t)0, count); return; }
+  std::vector<std::thread> th;
+  const size_t per = (count + nt - 1) / nt;
+  for (unsigned q = 0; q < nt; ++q) {
+    const size_t lo = std::min(count, q * per), hi = std::min(count, lo + per);
+    if (lo < hi) th.emplace_back([=] { f(lo, hi); });
+  }
+  for (auto& x : th) x.join();
+}
+
+static void fleet_pack_rec(const HostModel& m, double t_prev, double t, double y, int has, uint32_t step, unsigned char* dst) {
+  StepRec r;
+  cssm_build_rec(&m, t_prev, t, y, has, step, &r);
+  FleetRecHead h;
+  h.y = r.y; h.c[0] = r.c[0]; h.c[1] = r.c[1]; h.c[2] = r.c[2]; h.c[3] = r.c[3]; h.cdf = r.cdf; h.u = r.u; h.dt = r.dt; h.ref = r.ref;
+  h.has_obs = r.has_obs; h.step = r.step;
+  memcpy(dst, &h, sizeof h);
+  double* tail = reinterpret_cast<double*>(dst + sizeof h);
+  for (int k = 0; k < m.d; ++k) for (int q = 0; q < 4; ++q) tail[4 * k + q] = r.coef[k][q];
+  for (int k = 0; k < m.d; ++k) tail[4 * m.d + k] = r.fco[k];
+}
+
+// getIntervals of every series (model/ParticleFilter.scala:415-424), one block per (series, row); rows 0 .. D-1 the state components,
+// row D eta = link(f(x, t)).  The row's N values are sorted in LDS as order-preserving keys (bitonic network over the next power of
+// two, padded with the largest key): the order statistics are exact.  The mean is a plain fp64 sum / N.
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_summary(const double* __restrict__ state, const uint32_t* __restrict__ anc,
+                                                              const uint32_t* __restrict__ cur, const double* __restrict__ fco, uint32_t n,
+                                                              uint32_t np2, ModelK mk, uint32_t lo_state, uint32_t hi_state,
+                                                              uint32_t lo_eta, uint32_t hi_eta, double* __restrict__ out) {
+  extern __shared__ unsigned long long s_keys[];
+  __shared__ double s_p[CSSM_BLOCK / 64];
+  const uint32_t k = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
+  double* o = out + ((size_t)k * (D + 1) + row) * 3u;
+  const uint32_t c = cur[k];
+  if (c > 1u) {                                                 // (uniform) no cloud: not initialised, or failed since
+    if (tid < 3u) o[tid] = cssm_nan();
+    return;
+  }
+  const double* src = state + ((size_t)k * 2u + c) * D * n;
+  const uint32_t* ga = anc + (size_t)k * n;
+  double acc = 0.0;
+  for (uint32_t i = tid; i < np2; i += CSSM_BLOCK) {
+    unsigned long long key = ~0ull;
+    if (i < n) {
+      const uint32_t j = ga[i];
+      double v;
+      if (row < (uint32_t)D) {
+        v = src[(size_t)row * n + j];
+      } else {
+        double x[D];
+#pragma unroll
+        for (int q = 0; q < D; ++q) x[q] = src[(size_t)q * n + j];
+        v = link_of(mk.obs_kind, gamma_coef<D>(mk, fco + (size_t)k * D, x));
+      }
+      acc += v;
+      key = cssm_order_key(v);
+    }
+    s_keys[i] = key;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((tid & 63u) == 0u) s_p[tid >> 6] = acc;
+  for (uint32_t k2 = 2u; k2 <= np2; k2 <<= 1) {
+    for (uint32_t j = k2 >> 1; j > 0u; j >>= 1) {
+      __syncthreads();
+      for (uint32_t i = tid; i < np2; i += CSSM_BLOCK) {
+        const uint32_t p = i ^ j;
+        if (p > i) {
+          const unsigned long long x = s_keys[i], y = s_keys[p];
+          const bool up = (i & k2) == 0u;
+          if ((x > y) == up) { s_keys[i] = y; s_keys[p] = x; }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < CSSM_BLOCK / 64; ++w) s += s_p[w];
+    o[0] = s / (double)n;
+    o[1] = cssm_order_unkey(s_keys[row < (uint32_t)D ? lo_state : lo_eta]);
+    o[2] = cssm_order_unkey(s_keys[row < (uint32_t)D ? hi_state : hi_eta]);
+  }
+}
+
+// link(f(mean, t)) on the host (cssm_eta_of_mean of cssm_pf.hip takes a handle; the same statements on the model alone)
+static double fleet_eta_of_mean(const HostModel& m, const double* fco, const double* mean) {
+  double g = 0.0, acc = 0.0;
+  for (int k = 0; k < m.d; ++k) {
+    const int fm = m.mk.fmode(k);
+    if (fm == FM_START) acc = fco[k] * mean[k]; else if (fm == FM_ADD) acc = acc + fco[k] * mean[k];
+    if (m.mk.leaf_end(k)) g = m.mk.first_leaf(k) ? acc : g + acc;
+  }
+  switch (m.obs_kind) {
+    case CSSM_OBS_POISSON: case CSSM_OBS_NEGBIN: case CSSM_OBS_ZIP: return cssm_exp(g);
+    case CSSM_OBS_BERNOULLI: return (g > 6.0) ? 1.0 : ((g < -6.0) ? 0.0 : 1.0 / (1.0 + cssm_exp(-g)));
+    case CSSM_OBS_BETA: return cssm_exp(-g);
+    default: return g;
+  }
+}
+
+extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
+  if (!f) return;
+  (void)hipSetDevice(f->device);
+  if (f->stream) (void)hipStreamSynchronize(f->stream);
+  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_sm};
+  for (void* p : ptrs) if (p) (void)hipFree(p);
+  if (f->h_stage) (void)hipHostFree(f->h_stage);
+  for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
+  if (f->stream) (void)hipStreamDestroy(f->stream);
+  delete f;
+}
+
+extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out) {
+  if (!out) return fail(CSSM_EINVAL_ARG, "out is null");
+  *out = nullptr;
+  if (n_particles < 1 || n_particles > CSSM_FLEET_MAX_N)
+    return fail(CSSM_EINVAL_ARG, "a fleet holds 1 .. %d particles per series (a cloud lives in one workgroup's LDS), not %llu; " FLEET_SERVED,
+                CSSM_FLEET_MAX_N, (unsigned long long)n_particles);
+  if (n_series < 1) return fail(CSSM_EINVAL_ARG, "a fleet needs at least one series");
+  HostModel base;
+  int rc = cssm_build_model(&base, desc, false);
+  if (rc) return rc;
+  if (base.obs_kind == CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_DESC, "the fleet filter does not serve the LGCP observation model (sub-stepped events); " FLEET_SERVED);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range (%d devices)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  cssm_fleet* f = new cssm_fleet();
+  f->device = device; f->n = (uint32_t)n_particles; f->S = n_series; f->d = base.d;
+  base.n_global = n_particles; base.seed = 0;
+  f->base = base;
+  const uint32_t S = n_series, n = f->n;
+  f->models.assign(S, base);
+  f->t.assign(S, 0.0); f->step.assign(S, 0u); f->live.assign(S, 0); f->h_ser.resize(S);
+  // block size: about four particles per thread, whole waves, at most CSSM_FLEET_MAX_THREADS (results do not depend on it)
+  f->threads = (int)std::min<uint32_t>(CSSM_FLEET_MAX_THREADS, std::max<uint32_t>(64u, ((n + 3u) / 4u + 63u) & ~63u));
+  f->lds = (size_t)((n + 1u) & ~1u) * 8u + (size_t)n * 4u;
+  auto bail = [&](int code, const char* what) { cssm_fleet_destroy(f); return fail(code, "fleet of %u series x %u particles: %s", S, n, what); };
+  if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) return bail(CSSM_EHIP, "hipStreamCreate");
+  for (hipEvent_t& e : f->ev) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
+  const size_t rows = (size_t)S * 2u * f->d * n;
+  if (hipMalloc(&f->state, rows * 8) != hipSuccess || hipMalloc(&f->anc, (size_t)S * n * 4) != hipSuccess ||
+      hipMalloc(&f->ser, (size_t)S * sizeof(FleetSeries)) != hipSuccess || hipMalloc(&f->par, (size_t)S * sizeof(FleetPar)) != hipSuccess ||
+      hipMalloc(&f->logtab, sizeof(CSSM_TAB)) != hipSuccess || hipMalloc(&f->d_tmp, (size_t)f->d * n * 8) != hipSuccess)
+    return bail(CSSM_ENOMEM, "device memory (16 d N bytes of state per series)");
+  if (hipMemcpyAsync(f->logtab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice, f->stream) != hipSuccess ||
+      hipMemsetAsync(f->ser, 0, (size_t)S * sizeof(FleetSeries), f->stream) != hipSuccess ||
+      hipStreamSynchronize(f->stream) != hipSuccess)
+    return bail(CSSM_EHIP, "uploading the contract's table");
+  *out = f;
+  return CSSM_OK;
+}
+
+extern "C" uint32_t cssm_fleet_num_series(const cssm_fleet* f) { return f ? f->S : 0u; }
+extern "C" uint64_t cssm_fleet_num_particles(const cssm_fleet* f) { return f ? f->n : 0u; }
+
+extern "C" int cssm_fleet_set_option(cssm_fleet* f, int option, int value) {
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  if (option != CSSM_OPT_RESAMPLER) return fail(CSSM_EINVAL_ARG, "a fleet has no option %d", option);
+  if (value != CSSM_RESAMPLE_SYSTEMATIC)
+    return fail(CSSM_EINVAL_ARG, "the fleet filter resamples systematically only (resampler %d asked for); " FLEET_SERVED, value);
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_set_params(cssm_fleet* f, const cssm_model_desc* const* descs) {
+  if (!f || !descs) return fail(CSSM_EINVAL_ARG, "null argument");
+  // all or nothing: a descriptor of another structure leaves the fleet as it was
+  std::vector<HostModel> next(f->S);
+  const cssm_model_desc* last = nullptr;
+  for (uint32_t k = 0; k < f->S; ++k) {
+    if (k > 0 && descs[k] == last) { next[k] = next[k - 1]; continue; }     // (pointers may repeat)
+    next[k] = f->base;
+    const int rc = cssm_build_model(&next[k], descs[k], true);
+    if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "series %u: %s", k, keep.c_str()); }
+    last = descs[k];
+  }
+  for (uint32_t k = 0; k < f->S; ++k) { next[k].seed = f->models[k].seed; next[k].n_global = f->n; }
+  f->models.swap(next);
+  f->par_dirty = true;
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_reseed(cssm_fleet* f, const uint64_t* seeds) {
+  if (!f || !seeds) return fail(CSSM_EINVAL_ARG, "null argument");
+  for (uint32_t k = 0; k < f->S; ++k) f->models[k].seed = seeds[k];
+  f->par_dirty = true;
+  return CSSM_OK;
+}
+
+static int fleet_upload_par(cssm_fleet* f) {
+  if (!f->par_dirty) return CSSM_OK;
+  std::vector<FleetPar> hp(f->S);
+  for (uint32_t k = 0; k < f->S; ++k) {
+    const HostModel& m = f->models[k];
+    memset(&hp[k], 0, sizeof(FleetPar));
+    hp[k].seed = m.seed;
+    for (int c = 0; c < m.d; ++c) { hp[k].m0[c] = m.comp[c].m0; hp[k].sd0[c] = std::sqrt(m.comp[c].c0); }
+  }
+  HIP_TRY(hipMemcpyAsync(f->par, hp.data(), (size_t)f->S * sizeof(FleetPar), hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));   // (hp is pageable and dies here)
+  f->par_dirty = false;
+  return CSSM_OK;
+}
+
+// staging layout of a launch: [S + 1 offsets (u64)] [S control words (u32), padded to 8 bytes] [R compact records]
+static size_t fleet_stage_head(const cssm_fleet* f) { return ((size_t)f->S + 1u) * 8u + (((size_t)f->S * 4u + 7u) & ~(size_t)7u); }
+
+static int fleet_ensure(cssm_fleet* f, size_t R) {
+  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d);
+  if (need > f->h_stage_cap) {
+    if (f->h_stage) (void)hipHostFree(f->h_stage);
+    f->h_stage = nullptr; f->h_stage_cap = 0;
+    if (hipHostMalloc((void**)&f->h_stage, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of pinned staging", need);
+    f->h_stage_cap = need + need / 4;
+  }
+  if (need > f->stage_cap) {
+    if (f->d_stage) (void)hipFree(f->d_stage);
+    f->d_stage = nullptr; f->stage_cap = 0;
+    if (hipMalloc(&f->d_stage, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of records", need);
+    f->stage_cap = need + need / 4;
+  }
+  const size_t rr = std::max<size_t>(R, 1);
+  if (rr > f->res_cap) {
+    if (f->d_ll_t) (void)hipFree(f->d_ll_t);
+    if (f->d_ess_t) (void)hipFree(f->d_ess_t);
+    f->d_ll_t = nullptr; f->d_ess_t = nullptr; f->res_cap = 0;
+    if (hipMalloc(&f->d_ll_t, (rr + rr / 4) * 8) != hipSuccess || hipMalloc(&f->d_ess_t, (rr + rr / 4) * 4) != hipSuccess)
+      return fail(CSSM_ENOMEM, "fleet: per-observation results");
+    f->res_cap = rr + rr / 4;
+  }
+  return CSSM_OK;
+}
+
+// upload the staged launch, run it, bring the series' scalars (and, asked for, the per-observation results) back; synchronises
+static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t) {
+  int rc = fleet_upload_par(f);
+  if (rc) return rc;
+  const size_t head = fleet_stage_head(f), bytes = head + R * CSSM_FLEET_REC_BYTES(f->d);
+  HIP_TRY(hipEventRecord(f->ev[0], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->d_stage, f->h_stage, bytes, hipMemcpyHostToDevice, f->stream));
+  if (R) {   // records a failed series never reaches read as NaN / -1
+    HIP_TRY(hipMemsetAsync(f->d_ll_t, 0xff, R * 8, f->stream));
+    HIP_TRY(hipMemsetAsync(f->d_ess_t, 0xff, R * 4, f->stream));
+  }
+  FleetLaunch l;
+  l.args.n = f->n; l.args.state = f->state; l.args.anc = f->anc; l.args.ser = f->ser; l.args.par = f->par;
+  l.args.off = reinterpret_cast<const unsigned long long*>(f->d_stage);
+  l.args.ctl = reinterpret_cast<const uint32_t*>(f->d_stage + ((size_t)f->S + 1u) * 8u);
+  l.args.recs = f->d_stage + head;
+  l.args.ll_t = f->d_ll_t; l.args.ess_t = f->d_ess_t; l.args.logtab = f->logtab; l.args.mk = f->base.mk;
+  l.n_series = f->S; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+  int hrc = 0;
+  switch (f->d) {
+#define FLEET_CASE(D) case D: hrc = cssm_fleet_launch_d##D(l); break;
+    FLEET_CASE(1) FLEET_CASE(2) FLEET_CASE(3) FLEET_CASE(4) FLEET_CASE(5) FLEET_CASE(6) FLEET_CASE(7) FLEET_CASE(8)
+    FLEET_CASE(9) FLEET_CASE(10) FLEET_CASE(11) FLEET_CASE(12) FLEET_CASE(13) FLEET_CASE(14) FLEET_CASE(15) FLEET_CASE(16)
+#undef FLEET_CASE
+    default: return fail(CSSM_EINVAL_DESC, "latent dimension %d", f->d);
+  }
+  if (hrc) return fail(CSSM_EHIP, "k_fleet_series: %s", hipGetErrorString((hipError_t)hrc));
+  HIP_TRY(hipMemcpyAsync(f->h_ser.data(), f->ser, (size_t)f->S * sizeof(FleetSeries), hipMemcpyDeviceToHost, f->stream));
+  if (R && ll_t) HIP_TRY(hipMemcpyAsync(ll_t, f->d_ll_t, R * 8, hipMemcpyDeviceToHost, f->stream));
+  if (R && ess_t) HIP_TRY(hipMemcpyAsync(ess_t, f->d_ess_t, R * 4, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipEventRecord(f->ev[1], f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  if (hipEventElapsedTime(&f->ms_call, f->ev[0], f->ev[1]) != hipSuccess) f->ms_call = -1.f;
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                    double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out) {
+  if (!f || !off || !ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  const uint32_t S = f->S;
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  for (uint32_t k = 0; k < S; ++k)
+    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
+                                         k + 1, (unsigned long long)off[k + 1]);
+  const size_t R = (size_t)off[S];
+  if (R && (!t || !y)) return fail(CSSM_EINVAL_ARG, "null data");
+  HIP_TRY(hipSetDevice(f->device));
+  int rc = fleet_ensure(f, R);
+  if (rc) return rc;
+  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
+  uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
+  unsigned char* h_recs = f->h_stage + fleet_stage_head(f);
+  const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
+  for (uint32_t k = 0; k <= S; ++k) h_off[k] = off[k];
+  std::vector<double> t0(S, 0.0);
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+      h_ctl[k] = (b > a) ? CSSM_FLEET_CTL_INIT : 0u;
+      if (b == a) continue;
+      double m = t[a];
+      for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;      // data.minBy(_.t).t
+      t0[k] = m;
+      double tp = m;
+      for (size_t s = a; s < b; ++s) {
+        fleet_pack_rec(f->models[k], tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), h_recs + s * RB);
+        tp = t[s];
+      }
+    }
+  });
+  rc = fleet_launch(f, R, ll_t, ess_t);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < S; ++k) {
+    const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+    if (b == a) { rc_out[k] = CSSM_EINVAL_ARG; ll_out[k] = cssm_nan(); continue; }   // (the reference's minBy throws on an empty Vector)
+    const FleetSeries& s = f->h_ser[k];
+    if (s.err) {
+      rc_out[k] = CSSM_ENONFINITE; ll_out[k] = cssm_nan(); f->live[k] = 0;
+    } else {
+      rc_out[k] = CSSM_OK; ll_out[k] = s.ll; f->live[k] = 1; f->t[k] = t[b - 1]; f->step[k] = (uint32_t)(b - a);
+    }
+  }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_init(cssm_fleet* f, const double* t0) {
+  if (!f || !t0) return fail(CSSM_EINVAL_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->device));
+  int rc = fleet_ensure(f, 0);
+  if (rc) return rc;
+  const uint32_t S = f->S;
+  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
+  uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
+  for (uint32_t k = 0; k <= S; ++k) h_off[k] = 0;
+  for (uint32_t k = 0; k < S; ++k) h_ctl[k] = CSSM_FLEET_CTL_INIT;
+  rc = fleet_launch(f, 0, nullptr, nullptr);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < S; ++k) { f->live[k] = 1; f->t[k] = t0[k]; f->step[k] = 0u; }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                               double* ll_out, int32_t* ess_out, int* rc_out) {
+  if (!f || !t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  const uint32_t S = f->S;
+  bool any_live = false;
+  for (uint32_t k = 0; k < S; ++k) any_live = any_live || f->live[k];
+  if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
+  HIP_TRY(hipSetDevice(f->device));
+  int rc = fleet_ensure(f, S);
+  if (rc) return rc;
+  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
+  uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
+  unsigned char* h_recs = f->h_stage + fleet_stage_head(f);
+  const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
+  size_t R = 0;
+  for (uint32_t k = 0; k < S; ++k) {
+    h_off[k] = R; h_ctl[k] = 0u;
+    if ((!active || active[k]) && f->live[k]) ++R;
+  }
+  h_off[S] = R;
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k)
+      if (h_off[k + 1] > h_off[k])
+        fleet_pack_rec(f->models[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1, f->step[k], h_recs + (size_t)h_off[k] * RB);
+  });
+  rc = fleet_launch(f, R, nullptr, nullptr);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < S; ++k) {
+    if (active && !active[k]) { rc_out[k] = CSSM_OK; continue; }            // untouched
+    if (!f->live[k]) { rc_out[k] = CSSM_ESTATE; continue; }                 // no cloud: never initialised, or failed since
+    const FleetSeries& s = f->h_ser[k];
+    if (s.err) { rc_out[k] = CSSM_ENONFINITE; f->live[k] = 0; continue; }
+    rc_out[k] = CSSM_OK; f->t[k] = t[k]; f->step[k] += 1u;
+    if (ll_out) ll_out[k] = s.ll;
+    if (ess_out) ess_out[k] = s.ess;
+  }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_mean, double* state_lower, double* state_upper,
+                                  double* eta_of_mean, double* eta_lower, double* eta_upper) {
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  HIP_TRY(hipSetDevice(f->device));
+  const uint32_t S = f->S, n = f->n;
+  const int d = f->d, rows = d + 1;
+  // layout of d_sm (doubles): [S][d] f coefficients | [S][rows][3] results | [S] buffer numbers (u32, two per double)
+  const size_t n_fco = (size_t)S * d, n_out = (size_t)S * rows * 3, n_cur = ((size_t)S + 1) / 2, need = n_fco + n_out + n_cur;
+  if (need > f->sm_cap) {
+    if (f->d_sm) (void)hipFree(f->d_sm);
+    f->d_sm = nullptr; f->sm_cap = 0;
+    if (hipMalloc(&f->d_sm, need * 8) != hipSuccess) return fail(CSSM_ENOMEM, "fleet summary buffers");
+    f->sm_cap = need;
+  }
+  std::vector<double> hbuf(need, 0.0);
+  uint32_t* hcur = reinterpret_cast<uint32_t*>(hbuf.data() + n_fco + n_out);
+  fleet_parallel(S, (size_t)S * 4, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      StepRec r;
+      cssm_build_rec(&f->models[k], f->t[k], f->t[k], 0.0, 0, f->step[k], &r);   // F(t) of the series' own time
+      for (int c = 0; c < d; ++c) hbuf[k * d + c] = r.fco[c];
+      hcur[k] = f->live[k] ? (f->step[k] & 1u) : 0xffffffffu;
+    }
+  });
+  // ranks, 0-based ascending (cssm_pf_summary): states (N - index - 1, index - 1), eta (N - index, index), index = floor(interval N)
+  const long long idxr = (long long)std::floor(interval * (double)n);
+  auto clampr = [&](long long r) { return (uint32_t)std::min<long long>(std::max<long long>(r, 0), (long long)n - 1); };
+  uint32_t np2 = 2u;
+  while (np2 < n) np2 <<= 1;
+  double* d_fco = f->d_sm; double* d_out = f->d_sm + n_fco;
+  const uint32_t* d_cur = reinterpret_cast<const uint32_t*>(f->d_sm + n_fco + n_out);
+  HIP_TRY(hipEventRecord(f->ev[2], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->d_sm, hbuf.data(), need * 8, hipMemcpyHostToDevice, f->stream));
+  DISPATCH_D(d, hipLaunchKernelGGL(k_fleet_summary<D>, dim3(S, rows), dim3(CSSM_BLOCK), (size_t)np2 * 8u, f->stream, f->state, f->anc, d_cur, d_fco, n, np2,
+                                   f->base.mk, clampr((long long)n - idxr - 1), clampr(idxr - 1), clampr((long long)n - idxr), clampr(idxr), d_out));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(hbuf.data() + n_fco, d_out, n_out * 8, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipEventRecord(f->ev[3], f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  if (hipEventElapsedTime(&f->ms_summary, f->ev[2], f->ev[3]) != hipSuccess) f->ms_summary = -1.f;
+  const double* ho = hbuf.data() + n_fco;
+  for (uint32_t k = 0; k < S; ++k) {
+    double mean[CSSM_MAX_DIM];
+    for (int c = 0; c < d; ++c) {
+      const double* o = ho + ((size_t)k * rows + c) * 3;
+      mean[c] = o[0];
+      if (state_mean) state_mean[(size_t)k * d + c] = o[0];
+      if (state_lower) state_lower[(size_t)k * d + c] = o[1];
+      if (state_upper) state_upper[(size_t)k * d + c] = o[2];
+    }
+    const double* oe = ho + ((size_t)k * rows + d) * 3;
+    if (eta_lower) eta_lower[k] = oe[1];
+    if (eta_upper) eta_upper[k] = oe[2];
+    if (eta_of_mean) eta_of_mean[k] = f->live[k] ? fleet_eta_of_mean(f->models[k], hbuf.data() + (size_t)k * d, mean) : cssm_nan();   // :420
+  }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_get_particles(cssm_fleet* f, uint32_t k, double* out_dN) {
+  if (!f || !out_dN) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (k >= f->S) return fail(CSSM_EINVAL_ARG, "series %u of %u", k, f->S);
+  if (!f->live[k]) return fail(CSSM_ESTATE, "series %u has no cloud (not initialised, or its weights were unusable)", k);
+  HIP_TRY(hipSetDevice(f->device));
+  const uint32_t n = f->n;
+  const double* src = f->state + ((size_t)k * 2u + (f->step[k] & 1u)) * f->d * n;
+  hipLaunchKernelGGL(k_gather, dim3(grid_for(n, 256, 64)), dim3(256), 0, f->stream, src, (size_t)n, f->anc + (size_t)k * n, f->d_tmp, (size_t)n, (uint64_t)n,
+                     f->d, (const double*)nullptr, (size_t)0, 0u);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_dN, f->d_tmp, (size_t)f->d * n * 8, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_get_ancestors(cssm_fleet* f, uint32_t k, uint32_t* out_N) {
+  if (!f || !out_N) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (k >= f->S) return fail(CSSM_EINVAL_ARG, "series %u of %u", k, f->S);
+  if (!f->live[k]) return fail(CSSM_ESTATE, "series %u has no cloud (not initialised, or its weights were unusable)", k);
+  HIP_TRY(hipSetDevice(f->device));
+  HIP_TRY(hipMemcpyAsync(out_N, f->anc + (size_t)k * f->n, (size_t)f->n * 4, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_last_ms(cssm_fleet* f, double* ms2) {
+  if (!f || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
+  ms2[0] = (double)f->ms_call; ms2[1] = (double)f->ms_summary;
+  return CSSM_OK;
+}
+
+// The compact record of one observation as the fleet uploads it (tests: its fields against cssm_build_rec's StepRec).  No device.
+extern "C" int cssm_fleet_pack_record(const cssm_model_desc* desc, uint64_t n_particles, uint64_t seed, double t_prev, double t, double y,
+                                      int has_obs, uint32_t step, unsigned char* out, size_t cap, size_t* bytes) {
+  if (!out || !bytes) return fail(CSSM_EINVAL_ARG, "null argument");
+  HostModel m;
+  const int rc = cssm_build_model(&m, desc, false);
+  if (rc) return rc;
+  m.n_global = n_particles; m.seed = seed;
+  *bytes = CSSM_FLEET_REC_BYTES(m.d);
+  if (cap < *bytes) return fail(CSSM_EINVAL_ARG, "record of %zu bytes, room for %zu", *bytes, cap);
+  fleet_pack_rec(m, t_prev, t, y, has_obs, step, out);
+  return CSSM_OK;
+}

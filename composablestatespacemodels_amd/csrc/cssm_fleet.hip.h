@@ -1,0 +1,243 @@
+// cssm_fleet.hip.h -- the fleet filter (include/cssm_pf.h, "fleet of independent series"): S small clouds of one model structure, ONE
+// WORKGROUP PER SERIES.  A cloud of N <= CSSM_FLEET_MAX_N particles keeps its log-weights, its weights and its ancestors in the block's
+// LDS, so nothing of a series ever crosses a block: no atomics on global memory, no flag another block waits for, no cooperative
+// launch -- the parallelism of a launch is the number of series (grid.x = S).  k_fleet_series is instantiated per latent dimension in
+// its own object (cssm_fleet_d.hip, -DCSSM_FLEET_D=d), as k_propagate is; cssm_fleet.hip holds the host side and k_fleet_summary.
+//
+// Every arithmetic statement of the contract is the existing device function: draw_normals / propagate_one, transition, gamma_of,
+// logdens, cssm_ref_choose, cssm_exp_le0, cssm_fix_from_unit, wave_scan_u128, cssm_sys_count*, cssm_ess_of.  What is new here is only
+// the order they run in and where their operands live.
+#pragma once
+
+#include "cssm_device.hip.h"
+
+#define CSSM_FLEET_MAX_THREADS 512   /* 8 waves: two per SIMD, so every instantiation may use 256 vector registers */
+#define CSSM_FLEET_WAVES(D) ((D) <= 4 ? 4 : 2)   /* waves per SIMD the register allocation aims at (the table and the A/B) */
+
+// What the host uploads per (series, observation): the fields of cssm_build_rec's StepRec the kernels of a non-LGCP model read, with
+// exactly the d components in use -- 80 + 40 d bytes (120 at d = 1, 200 at d = 3, 720 at d = 16) instead of sizeof(StepRec).  The
+// block expands it into a StepRec in LDS, so the device functions above read it through the pointer they always took.
+struct FleetRecHead {
+  double y, c[4], cdf, u, dt, ref;
+  int32_t has_obs;
+  uint32_t step;
+};   // followed by d x 4 transition coefficients (StepRec::coef) and d f coefficients (StepRec::fco)
+#define CSSM_FLEET_REC_BYTES(d) (sizeof(FleetRecHead) + (size_t)(d) * 40u)
+
+// per series, on the device: the Philox key and the initial-state parameters (x0 = sd0 z + m0) ...
+struct FleetPar {
+  uint64_t seed;
+  double m0[CSSM_MAX_DIM], sd0[CSSM_MAX_DIM];
+};
+// ... and what a launch leaves for the next one and for the host
+struct FleetSeries {
+  double ll;
+  int32_t ess;
+  uint32_t err;        // bits 0 / 1 as Scalars::err: a NaN log-weight / no usable weight
+  uint32_t fail_rec;   // index (within the launch's records of this series) of the observation that set err
+  uint32_t pad_;
+};
+
+#define CSSM_FLEET_CTL_INIT 1u   /* draw the initial cloud before the series' first record of this launch */
+
+struct FleetArgs {
+  uint32_t n;                        // particles per series
+  double* state;                     // [S][2][d][n]: record `step` reads buffer step & 1 and writes the other
+  uint32_t* anc;                     // [S][n]
+  FleetSeries* ser;                  // [S]
+  const FleetPar* par;               // [S]
+  const unsigned long long* off;     // [S + 1]: series k owns the launch's records off[k] .. off[k + 1] - 1
+  const uint32_t* ctl;               // [S]: CSSM_FLEET_CTL_*
+  const unsigned char* recs;         // compact records, CSSM_FLEET_REC_BYTES(d) each
+  double* ll_t;                      // per record of the launch
+  int32_t* ess_t;
+  const double* logtab;
+  ModelK mk;
+};
+
+// a - b mod 2^128 (integers: exact)
+__device__ __forceinline__ cssm_u128 fleet_u128_sub(cssm_u128 a, cssm_u128 b) {
+  cssm_u128 r;
+  r.lo = a.lo - b.lo;
+  r.hi = a.hi - b.hi - (a.lo < b.lo ? 1u : 0u);
+  return r;
+}
+
+// cnt(C) of the contract for the cumulative sum `run` (include/cssm_numerics.h, systematic grid): the exact predicate, always
+__device__ __forceinline__ uint32_t fleet_end_slot(cssm_u128 run, double totd, double u, uint32_t n, bool pow2, double inv_n) {
+  const double C = cssm_u128_to_double(run) / totd;
+  const uint32_t c = (uint32_t)(pow2 ? cssm_sys_count_pow2(C, u, n, inv_n) : cssm_sys_count(C, u, n));
+  return (c > n) ? n : c;
+}
+
+// llFilter / stepFilter of series blockIdx.x over its records of this launch (model/ParticleFilter.scala:105-140).
+// Dynamic LDS: n_even doubles (log-weights, then the weights in their place) + n ancestors.
+template <int D>
+__global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_series(const FleetArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+  __shared__ StepRec s_rec;
+  __shared__ cssm_u128 s_wS[CSSM_FLEET_MAX_THREADS / 64], s_wS2[CSSM_FLEET_MAX_THREADS / 64];
+  __shared__ unsigned long long s_wmax[CSSM_FLEET_MAX_THREADS / 64];
+  __shared__ uint32_t s_wm[CSSM_FLEET_MAX_THREADS / 64], s_wbad[CSSM_FLEET_MAX_THREADS / 64];
+  const uint32_t n = a.n, k = blockIdx.x, tid = threadIdx.x, bs = blockDim.x;
+  const uint32_t lane = tid & 63u, wid = tid >> 6, nw = bs >> 6;
+  double* s_lw = reinterpret_cast<double*>(s_dyn);
+  uint32_t* s_anc = reinterpret_cast<uint32_t*>(s_dyn + (size_t)((n + 1u) & ~1u) * 8u);
+  const unsigned long long r0 = a.off[k], r1 = a.off[k + 1];
+  const uint32_t ctl = a.ctl[k];
+  if (!(ctl & CSSM_FLEET_CTL_INIT) && r0 >= r1) return;      // (uniform) nothing for this series in this launch: untouched
+  const double* tab = stage_log_table(a.logtab);
+  const FleetPar* par = a.par + k;
+  const uint64_t seed = par->seed;
+  double* st = a.state + (size_t)k * 2u * D * n;
+  uint32_t* ganc = a.anc + (size_t)k * n;
+  double ll; int32_t ess; uint32_t err = 0u, fail_rec = 0u;
+  if (ctl & CSSM_FLEET_CTL_INIT) {
+    // initialiseState (:105-108): x0 = sqrt(c0) z + m0 into buffer 0, identity ancestors, ll = 0, ess = N
+    for (uint32_t i = tid; i < n; i += bs) {
+      double z[D];
+      draw_normals<D>(seed, (uint64_t)i, 0u, CSSM_STREAM_INIT, tab, z);
+#pragma unroll
+      for (int c = 0; c < D; ++c) st[(size_t)c * n + i] = par->sd0[c] * z[c] + par->m0[c];
+      s_anc[i] = i;
+    }
+    ll = 0.0; ess = (int32_t)n;
+  } else {
+    for (uint32_t i = tid; i < n; i += bs) s_anc[i] = ganc[i];
+    ll = a.ser[k].ll; ess = a.ser[k].ess;
+  }
+  const bool pow2 = (n & (n - 1u)) == 0u;
+  const double inv_n = 1.0 / (double)n;
+  const uint32_t it = (n + bs - 1u) / bs;                      // particles per thread of the scan phases (contiguous)
+  const uint32_t j0 = tid * it;
+  const uint32_t j1 = (j0 + it < n) ? j0 + it : n;             // (j0 >= n: an empty range)
+  constexpr uint32_t RB = (uint32_t)CSSM_FLEET_REC_BYTES(D);
+  for (unsigned long long r = r0; r < r1; ++r) {               // bounded by the series' length
+    __syncthreads();                                            // the cloud / ancestors of the record before; s_rec is free
+    {
+      const unsigned char* g = a.recs + (size_t)r * RB;
+      const FleetRecHead* h = reinterpret_cast<const FleetRecHead*>(g);
+      const double* tail = reinterpret_cast<const double*>(g + sizeof(FleetRecHead));
+      if (tid == 0) {
+        s_rec.y = h->y; s_rec.c[0] = h->c[0]; s_rec.c[1] = h->c[1]; s_rec.c[2] = h->c[2]; s_rec.c[3] = h->c[3];
+        s_rec.cdf = h->cdf; s_rec.u = h->u; s_rec.dt = h->dt; s_rec.ref = h->ref; s_rec.has_obs = h->has_obs; s_rec.step = h->step;
+      }
+      if (tid < 4u * D) s_rec.coef[tid >> 2][tid & 3u] = tail[tid];
+      if (tid < (uint32_t)D) s_rec.fco[tid] = tail[4 * D + tid];
+    }
+    __syncthreads();
+    const StepRec* rec = &s_rec;
+    const uint32_t step = rec->step;
+    const bool weighted = rec->has_obs != 0;
+    const double* src = st + (size_t)(step & 1u) * D * n;
+    double* dst = st + (size_t)((step & 1u) ^ 1u) * D * n;
+    // 1. gather through the previous ancestors, transition, f, log-density (:118, :123)
+    double tmax = -cssm_inf();
+    bool bad = false;
+    for (uint32_t i = tid; i < n; i += bs) {
+      const uint32_t j = s_anc[i];
+      double x[D];
+#pragma unroll
+      for (int c = 0; c < D; ++c) x[c] = src[(size_t)c * n + j];
+      propagate_one<D>(a.mk, rec, rec->dt, seed, (uint64_t)i, step, tab, x);
+#pragma unroll
+      for (int c = 0; c < D; ++c) dst[(size_t)c * n + i] = x[c];
+      if (weighted) {
+        double lw = logdens<-1>(a.mk, rec, gamma_of<D>(a.mk, rec, x), tab);
+        if (lw != lw) { bad = true; lw = -cssm_inf(); }
+        tmax = (lw > tmax) ? lw : tmax;
+        s_lw[i] = lw;
+      }
+    }
+    if (!weighted) {                                            // (uniform) the None branch (:121): the cloud moves, nothing else
+      __syncthreads();
+      for (uint32_t i = tid; i < n; i += bs) s_anc[i] = i;
+      if (tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
+      continue;
+    }
+    // 2. the block's own max is at hand before any weight is formed: the level is chosen in place
+    {
+      const unsigned long long km = wave_max_u64(cssm_order_key(tmax));
+      const bool anyb = __any(bad);
+      if (lane == 0u) { s_wmax[wid] = km; s_wbad[wid] = anyb ? 1u : 0u; }
+    }
+    __syncthreads();
+    unsigned long long kmax = 0ull; uint32_t anybad = 0u;
+    for (uint32_t w = 0; w < nw; ++w) { kmax = (s_wmax[w] > kmax) ? s_wmax[w] : kmax; anybad |= s_wbad[w]; }
+    const double gmax = cssm_order_unkey(kmax);
+    if (anybad || !(gmax > -cssm_inf()) || !(gmax < cssm_inf())) {   // (uniform) unusable weights: the series is over
+      err = anybad ? 1u : 2u; fail_rec = (uint32_t)(r - r0);
+      break;
+    }
+    const double ref = cssm_ref_choose(rec->ref, gmax);
+    // 3. weights on the 2^-96 grid, their sums, the block scan (:125, :127-128)
+    cssm_u128 sa = cssm_u128_zero(), sb = cssm_u128_zero();
+    for (uint32_t j = j0; j < j1; ++j) {
+      const double w1 = cssm_exp_le0(cssm_min_c(s_lw[j] - ref, CSSM_REF_BELOW));
+      s_lw[j] = w1;
+      sa = cssm_u128_add(sa, cssm_fix_from_unit(w1));
+      sb = cssm_u128_add(sb, cssm_fix_from_unit(w1 * w1));
+    }
+    for (uint32_t i = tid; i < n; i += bs) s_anc[i] = 0u;      // (every thread gathered before the barrier above)
+    const cssm_u128 inc = wave_scan_u128(sa, (int)lane);
+    const cssm_u128 wb2 = wave_sum_u128(sb);
+    if (lane == 63u) { s_wS[wid] = inc; s_wS2[wid] = wb2; }
+    __syncthreads();
+    cssm_u128 tot = cssm_u128_zero(), tot2 = cssm_u128_zero(), off = cssm_u128_zero();
+    for (uint32_t w = 0; w < nw; ++w) {
+      if (w < wid) off = cssm_u128_add(off, s_wS[w]);
+      tot = cssm_u128_add(tot, s_wS[w]); tot2 = cssm_u128_add(tot2, s_wS2[w]);
+    }
+    if (cssm_u128_is_zero(tot)) { err = 2u; fail_rec = (uint32_t)(r - r0); break; }   // (uniform)
+    ll = ll + ref + cssm_log(cssm_fix_to_double(tot) / (double)n);
+    ess = cssm_ess_of(tot, tot2);
+    // 4. systematic resampling (model/Resampling.scala:36-72): particle j owns the slots [cnt(C_{j-1}), cnt(C_j)); it drops its
+    //    index at the first of them, an inclusive max-scan over the slots fills the runs (indices grow with the slots; an empty
+    //    slot reads 0, which is also particle 0's marker: the slots before every other marker can only be its run)
+    {
+      const double totd = cssm_u128_to_double(tot);
+      const double u = rec->u;
+      cssm_u128 run = fleet_u128_sub(cssm_u128_add(off, inc), sa);   // exclusive prefix of the thread's first particle
+      uint32_t prev = 0u;
+      if (j0 < j1 && j0 > 0u) prev = fleet_end_slot(run, totd, u, n, pow2, inv_n);
+      for (uint32_t j = j0; j < j1; ++j) {
+        run = cssm_u128_add(run, cssm_fix_from_unit(s_lw[j]));
+        const uint32_t e = fleet_end_slot(run, totd, u, n, pow2, inv_n);
+        if (e > prev) s_anc[prev] = j;
+        prev = (e > prev) ? e : prev;
+      }
+    }
+    __syncthreads();
+    {
+      uint32_t m = 0u;
+      for (uint32_t s = j0; s < j1; ++s) { const uint32_t v = s_anc[s]; m = (v > m) ? v : m; }
+      const uint32_t incl = wave_scan_max_u32(m);
+      uint32_t carry = dpp0<0x138 /* wave_shr:1 */, 0xf>(incl);
+      if (lane == 63u) s_wm[wid] = incl;
+      __syncthreads();
+      for (uint32_t w = 0; w < wid; ++w) carry = (s_wm[w] > carry) ? s_wm[w] : carry;
+      for (uint32_t s = j0; s < j1; ++s) {
+        const uint32_t v = s_anc[s];
+        carry = (v > carry) ? v : carry;
+        s_anc[s] = carry;
+      }
+    }
+    if (tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < n; i += bs) ganc[i] = s_anc[i];
+  if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.ser[k] = o; }
+}
+
+struct FleetLaunch {
+  FleetArgs args;
+  uint32_t n_series;
+  int threads;
+  size_t lds;
+  hipStream_t stream;
+};
+// one per latent dimension, defined in cssm_fleet_d.hip
+#define CSSM_DECL_FLEET(D) int cssm_fleet_launch_d##D(const FleetLaunch& l);
+CSSM_DECL_FLEET(1) CSSM_DECL_FLEET(2) CSSM_DECL_FLEET(3) CSSM_DECL_FLEET(4) CSSM_DECL_FLEET(5) CSSM_DECL_FLEET(6) CSSM_DECL_FLEET(7) CSSM_DECL_FLEET(8)
+CSSM_DECL_FLEET(9) CSSM_DECL_FLEET(10) CSSM_DECL_FLEET(11) CSSM_DECL_FLEET(12) CSSM_DECL_FLEET(13) CSSM_DECL_FLEET(14) CSSM_DECL_FLEET(15) CSSM_DECL_FLEET(16)
+#undef CSSM_DECL_FLEET

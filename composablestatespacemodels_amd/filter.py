@@ -363,6 +363,138 @@ class NativePfBatch:
         return v
 
 
+class NativePfFleet:
+    """``cssm_fleet*``: S series of one model structure, N <= ``_abi.FLEET_MAX_N`` particles each, parameters / key / data / clock of
+    its own per series; ONE launch advances all of them, one workgroup per series (include/cssm_pf.h, "fleet of independent
+    series").  Per series every result has the bits of a ``NativePf`` of its own."""
+
+    def __init__(self, model: Model, n: int, series: int, device: int = 0):
+        self.lib = _abi.load_library()
+        self._h = C.c_void_p()
+        self._desc = model.descriptor()
+        _abi.check(self.lib.cssm_fleet_create(self._desc.ptr(), int(n), int(series), int(device), C.byref(self._h)))
+        self.S, self.n = int(series), int(n)
+        words = (C.c_uint32 * (_abi.MAX_DIM // 4))()
+        d = C.c_int32()
+        _abi.check(self.lib.cssm_model_structure(self._desc.ptr(), words, C.byref(d)))
+        self.d = int(d.value)
+        self.generation = 0
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.cssm_fleet_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_params(self, models: Sequence[Model]):
+        if len(models) != self.S:
+            raise ValueError("one model per series")
+        cache = {}
+        descs = [cache.setdefault(id(m), m.descriptor()) for m in models]   # (pointers may repeat)
+        arr = (C.POINTER(_abi.ModelDesc) * self.S)(*[C.pointer(d.desc) for d in descs])
+        _abi.check(self.lib.cssm_fleet_set_params(self._h, arr))
+
+    def reseed(self, seeds: Sequence[int]):
+        if len(seeds) != self.S:
+            raise ValueError("one seed per series")
+        sd = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
+        _abi.check(self.lib.cssm_fleet_reseed(self._h, _p(sd, C.POINTER(C.c_uint64))))
+
+    def set_option(self, option: int, value: int):
+        _abi.check(self.lib.cssm_fleet_set_option(self._h, int(option), int(value)))
+
+    @staticmethod
+    def pack(datas):
+        """The ragged arrays of ``cssm_fleet_ll_filter`` from a sequence of ``(t, y, has)`` triples (``has`` may be None = all
+        observed): ``(off uint64[S + 1], t, y, has uint8)``, C-contiguous.  An empty series is refused here, before any device call
+        (the reference's ``minBy`` throws on an empty Vector)."""
+        off = np.zeros(len(datas) + 1, dtype=np.uint64)
+        ts, ys, hs = [], [], []
+        for k, tr in enumerate(datas):
+            t, y = np.asarray(tr[0], dtype=np.float64).ravel(), np.asarray(tr[1], dtype=np.float64).ravel()
+            h = tr[2] if len(tr) > 2 else None
+            h = np.ones(len(t), dtype=np.uint8) if h is None else np.asarray(h, dtype=np.uint8).ravel()
+            if len(t) == 0:
+                raise ValueError(f"series {k} has no records (the reference's minBy throws on an empty Vector)")
+            if len(y) != len(t) or len(h) != len(t):
+                raise ValueError(f"series {k}: t, y and has differ in length")
+            off[k + 1] = off[k] + np.uint64(len(t))
+            ts.append(t); ys.append(y); hs.append(h)
+
+        def cat(v, ty):
+            return np.ascontiguousarray(np.concatenate(v) if v else np.zeros(0), dtype=ty)
+        return off, cat(ts, np.float64), cat(ys, np.float64), cat(hs, np.uint8)
+
+    def ll_filter(self, datas):
+        """llFilter of every series: ``(ll[S], [ll_t of series k], [ess_t of series k], rc[S])``; rc[k] != 0 is series k's own status
+        (-5: its weights were unusable; its later ll_t read NaN)."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        return self.ll_filter_packed(*self.pack(datas))
+
+    def ll_filter_packed(self, off, t, y, has):
+        """``ll_filter`` on arrays ``pack`` made (a caller that filters the same fleet repeatedly packs once)."""
+        R = int(off[-1])
+        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
+        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_ll_filter(self._h, _p(off, C.POINTER(C.c_uint64)), _p(t), _p(y), _p(has, C.POINTER(C.c_uint8)), _p(ll),
+                                                 _p(ll_t), _p(ess_t, C.POINTER(C.c_int32)), _p(rc, C.POINTER(C.c_int))))
+        o = [int(v) for v in off]
+        return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], rc
+
+    def init(self, t0):
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (self.S,)), dtype=np.float64)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_init(self._h, _p(t0)))
+
+    def step(self, t, y, has=None, active=None):
+        """One observation for the active series (``active`` None = all): ``(ll[S], ess[S], rc[S])``; entries of inactive series are
+        NaN / -1 / 0."""
+        t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+        if len(t) != self.S or len(y) != self.S:
+            raise ValueError("one (t, y) per series")
+        hp = ap = None
+        if has is not None:
+            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
+        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32); rc = np.zeros(self.S, dtype=np.int32)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_step(self._h, ap, _p(t), _p(y), hp, _p(ll), _p(ess, C.POINTER(C.c_int32)), _p(rc, C.POINTER(C.c_int))))
+        return ll, ess, rc
+
+    def summary(self, interval: float = 0.975):
+        """(state_mean[S, d], state_lower[S, d], state_upper[S, d], eta_of_mean[S], eta_lower[S], eta_upper[S])."""
+        m, lo, hi = np.zeros((self.S, self.d)), np.zeros((self.S, self.d)), np.zeros((self.S, self.d))
+        em, el, eu = np.zeros(self.S), np.zeros(self.S), np.zeros(self.S)
+        _abi.check(self.lib.cssm_fleet_summary(self._h, float(interval), _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu)))
+        return m, lo, hi, em, el, eu
+
+    def particles(self, k: int) -> np.ndarray:
+        out = np.zeros((self.d, self.n))
+        _abi.check(self.lib.cssm_fleet_get_particles(self._h, int(k), _p(out)))
+        return out
+
+    def ancestors(self, k: int) -> np.ndarray:
+        out = np.zeros(self.n, dtype=np.uint32)
+        _abi.check(self.lib.cssm_fleet_get_ancestors(self._h, int(k), _p(out, C.POINTER(C.c_uint32))))
+        return out
+
+    def last_ms(self) -> Tuple[float, float]:
+        """Device time (HIP events) of the last ll_filter / init / step call and of the last summary, ms; < 0: none yet."""
+        ms = np.zeros(2)
+        _abi.check(self.lib.cssm_fleet_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1])
+
+
 class _PfView(NativePf):
     """A chain of a batch seen as a NativePf: the batch owns the handle, closing the view destroys nothing."""
 
@@ -672,6 +804,109 @@ class FilterInterpolate(_FilterBase):
         obs = [None] + [d.observation for d in data]
         return ll, [PfOut(times[k], obs[k], float(em[k]), CredibleInterval(float(el[k]), float(eu[k])), m[k].copy(),
                           [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k], hi[k])]) for k in range(len(times))]
+
+
+@dataclass(frozen=True)
+class FleetState:
+    """``PfState`` of one series of a ``FilterFleet`` (ParticleFilter.scala:32-37); ``particles`` is fetched on demand and only for
+    the fleet's current state."""
+    t: float
+    observation: Optional[float]
+    ll: float
+    ess: int
+    series: int = 0
+    _owner: Optional[NativePfFleet] = field(default=None, repr=False, compare=False)
+    _generation: int = field(default=-1, repr=False, compare=False)
+
+    @property
+    def particles(self) -> np.ndarray:
+        if self._owner is None or self._owner.generation != self._generation:
+            raise RuntimeError("this state is not the fleet's current one; its cloud was advanced on the device")
+        return self._owner.particles(self.series)
+
+
+class FilterFleet:
+    """The reference's streaming filter per sensor (``filterStream``, ParticleFilter.scala:163-166) for many sensors at once:
+    ``Filter(mods[k], resample)`` for every k, advanced by one device call.  ``mods`` share one structure; series k's default key is
+    ``cssm_pf_run_key(seed, k)``.  Only ``Resampling.systematicResampling`` is served: any other ``resample`` raises with the
+    C layer's message (``Filter`` / ``NativePfBatch`` serve the others)."""
+
+    def __init__(self, mods: Sequence[Model], resample, n_particles: int, seed: int = 20260101, device: int = 0):
+        if not callable(resample):
+            raise TypeError("resample must be a Resample[A]: (samples, weights) -> samples")
+        kinds = {Resampling.systematicResampling: 0, Resampling.stratifiedResampling: 1, Resampling.multinomialResampling: 2}
+        self.mods = list(mods)
+        self.S = len(self.mods)
+        self.seed = seed
+        self._fleet = NativePfFleet(self.mods[0], n_particles, self.S, device)
+        try:
+            self._fleet.set_option(2, kinds.get(resample, 3))      # CSSM_OPT_RESAMPLER: refused unless systematic
+            self._fleet.set_params(self.mods)
+            self._fleet.reseed(self.keys(seed, self.S))
+        except Exception:
+            self._fleet.close()
+            raise
+        self._states: List[FleetState] = []
+
+    @staticmethod
+    def keys(seed: int, series: int) -> List[int]:
+        """Series k runs under ``cssm_pf_run_key(seed, k)`` -- never ``seed + k`` (include/cssm_pf.h, cssm_pf_run_key)."""
+        lib = _abi.load_library()
+        return [int(lib.cssm_pf_run_key(int(seed) & (2**64 - 1), k)) for k in range(int(series))]
+
+    def close(self):
+        self._fleet.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _wrap(self, t, obs, ll, ess) -> List[FleetState]:
+        g = self._fleet.generation
+        self._states = [FleetState(float(t[k]), obs[k], float(ll[k]), int(ess[k]), k, self._fleet, g) for k in range(self.S)]
+        return self._states
+
+    def initialiseState(self, t0s) -> List[FleetState]:
+        t0 = np.broadcast_to(np.asarray(t0s, dtype=np.float64), (self.S,))
+        self._fleet.init(t0)
+        return self._wrap(t0, [None] * self.S, np.zeros(self.S), [self._fleet.n] * self.S)
+
+    def stepFilter(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]]) -> List[FleetState]:
+        """``ys[k]`` None = sensor k has nothing new (its state is returned as it is); a TimedObservation whose ``observation`` is None
+        is the reference's ``None`` branch (propagate only)."""
+        if len(states) != self.S or len(ys) != self.S:
+            raise ValueError("one state and one (optional) observation per series")
+        if any(s._owner is not self._fleet or s._generation != self._fleet.generation for s in states):
+            raise RuntimeError("stepFilter needs the fleet's current states (the clouds live on the device)")
+        act = np.array([0 if o is None else 1 for o in ys], dtype=np.uint8)
+        t = np.array([states[k].t if o is None else o.t for k, o in enumerate(ys)], dtype=np.float64)
+        has = np.array([0 if (o is None or o.observation is None) else 1 for o in ys], dtype=np.uint8)
+        y = np.array([o.observation if h else 0.0 for o, h in zip(ys, has)], dtype=np.float64)
+        ll, ess, rc = self._fleet.step(t, y, has, act)
+        for k in range(self.S):
+            if rc[k]:
+                raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable (or it has no cloud)")
+        keep = [s if not a else None for s, a in zip(states, act)]
+        return self._wrap(t, [s.observation if s is not None else (float(y[k]) if has[k] else None) for k, s in enumerate(keep)],
+                          [s.ll if s is not None else ll[k] for k, s in enumerate(keep)],
+                          [s.ess if s is not None else ess[k] for k, s in enumerate(keep)])
+
+    def llFilter(self, datas: Sequence[Sequence[TimedObservation]]) -> np.ndarray:
+        ll, _, _, rc = self._fleet.ll_filter([split_data(d) for d in datas])
+        for k in range(self.S):
+            if rc[k]:
+                raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable")
+        self._states = []
+        return ll
+
+    def getIntervals(self) -> List[PfOut]:
+        """``ParticleFilter.getIntervals`` (:415-424) of every series' current state."""
+        m, lo, hi, em, el, eu = self._fleet.summary(0.975)
+        st = self._states if self._states and self._states[0]._generation == self._fleet.generation else None
+        return [PfOut(st[k].t if st else float("nan"), st[k].observation if st else None, float(em[k]), CredibleInterval(float(el[k]), float(eu[k])),
+                      m[k], [CredibleInterval(a, b) for a, b in zip(lo[k], hi[k])]) for k in range(self.S)]
 
 
 class ParticleFilter:

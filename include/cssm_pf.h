@@ -745,6 +745,82 @@ int cssm_desc_flatten(const cssm_model_desc* desc, double* theta, size_t cap, si
  * whose words are listed in csrc/cssm_prop.hip (KnownStructures) run kernels that hold them at compile time. */
 int cssm_model_structure(const cssm_model_desc* desc, uint32_t* words_out, int32_t* d_out);
 
+/* ---- fleet of independent series ------------------------------------------------------------
+ * The reference's everyday shape: a streaming filter per sensor (filterStream, model/ParticleFilter.scala:163-166) over many
+ * sensors, N = 100 ... 2000 particles each (examples/Filtering.scala:24, examples/DetermineParameters.scala, the pilot run of
+ * model/Streaming.scala:19-40).  A cssm_fleet holds S series of ONE model structure (the cssm_model_structure words, d, obs_kind,
+ * obs_df of the descriptor it is created with), N particles each; parameters, Philox key, data and clock are every series' own.
+ * One launch advances all of them, ONE WORKGROUP PER SERIES: a cloud of at most CSSM_FLEET_MAX_N particles keeps its weights, its
+ * scan and its ancestors in the workgroup's LDS, so nothing of a series crosses a block ("Fleet").
+ *
+ * Per series k every result has the bits of a handle of its own -- cssm_pf_create(descs[k], N, seeds[k]) driven through the same
+ * calls -- and so of the oracle: ll, ll_t, ess_t, cloud, ancestors, observation index, the paired Philox streams.
+ *
+ * Served: every observation model except LGCP, every transition and composition, d = 1 .. CSSM_MAX_DIM, systematic resampling,
+ * 1 <= N <= CSSM_FLEET_MAX_N.  Everything else is refused at cssm_fleet_create / _set_params / _set_option with CSSM_EINVAL_ARG /
+ * CSSM_EINVAL_DESC and a message naming the reason and the entry points that do serve it (cssm_pf_*, cssm_pfb_*); a fleet call
+ * never degenerates into S single-handle runs.  Thread-affinity and device rules as for every entry point: each call selects the
+ * fleet's device; the fleet owns a non-blocking stream; a fleet is not re-entrant.
+ * Not here: forecasts and `filter`'s sampled path from a fleet, sharded fleets, other resamplers. */
+typedef struct cssm_fleet cssm_fleet;
+/* 12 bytes of LDS per particle (weight 8, ancestor 4) + 7.3 KB per block: 55.3 KB at 4096, two blocks per CU of 160 KiB; the summary
+ * kernel sorts a row of at most 4096 keys (32 KiB) in LDS. */
+#define CSSM_FLEET_MAX_N 4096
+
+/* Errors: CSSM_EINVAL_ARG (N outside [1, CSSM_FLEET_MAX_N], S = 0, device out of range), CSSM_EINVAL_DESC (invalid descriptor,
+ * LGCP), CSSM_EHIP (no device), CSSM_ENOMEM (16 d N bytes of state per series). */
+int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out);
+void cssm_fleet_destroy(cssm_fleet* f);
+uint32_t cssm_fleet_num_series(const cssm_fleet* f);
+uint64_t cssm_fleet_num_particles(const cssm_fleet* f);
+/* descs[k] = the parameters of series k (pointers may repeat); every descriptor must have the fleet's structure, else
+ * CSSM_EINVAL_DESC naming the series, and the fleet keeps the parameters it had.  Until the first call every series has the
+ * parameters of the creating descriptor. */
+int cssm_fleet_set_params(cssm_fleet* f, const cssm_model_desc* const* descs);
+/* seeds[k] = the Philox key of series k (default 0).  Derive the keys of one user seed with cssm_pf_run_key(seed, k). */
+int cssm_fleet_reseed(cssm_fleet* f, const uint64_t* seeds);
+/* CSSM_OPT_RESAMPLER only, and only CSSM_RESAMPLE_SYSTEMATIC: any other resampler is CSSM_EINVAL_ARG with the reason (the
+ * `Resample[A]` a FilterFleet is constructed with goes through here). */
+int cssm_fleet_set_option(cssm_fleet* f, int option, int value);
+
+/* llFilter (model/ParticleFilter.scala:137-140) of every series, ragged: series k owns the records off[k] .. off[k+1]-1 of
+ * t / y / has_obs (off[0] = 0, non-decreasing, S + 1 entries; has_obs may be NULL = all 1); its cloud is drawn afresh at the
+ * slice's smallest time (data.minBy(_.t)).  ll_out[S]; ll_t / ess_t (optional) laid out like t; rc_out[S] = the series' OWN status:
+ * CSSM_OK; CSSM_EINVAL_ARG for a series with no records (the reference's minBy throws; the series is left as it was);
+ * CSSM_ENONFINITE when its weights were unusable at some observation -- its cloud is then undefined until it is initialised again
+ * (the rule of cssm_pf_step), its later records are skipped (their ll_t / ess_t read NaN / -1, ll_out[k] NaN), and every other
+ * series is bit for bit what it is without it.  The call returns non-zero only for errors that are not one series' own
+ * (CSSM_EINVAL_ARG: null arguments, off[0] != 0 or off decreasing; HIP failures).  A fleet continues with cssm_fleet_step
+ * afterwards as a handle does after cssm_pf_ll_filter. */
+int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                         double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out);
+
+/* initialiseState + stepFilter (:105-132).  cssm_fleet_init draws every series' cloud at its own t0[k].  cssm_fleet_step advances
+ * the series with active[k] != 0 (active NULL = every series) by one observation (t[k], y[k], has_obs[k]; has_obs NULL = all 1): the
+ * bits of cssm_pf_step.  Inactive series are untouched (their t / y / has_obs entries are not read, their ll_out / ess_out entries
+ * not written, rc_out[k] = CSSM_OK).  rc_out[k] = CSSM_ENONFINITE as above; CSSM_ESTATE for an active series without a cloud
+ * (never initialised, or failed since).  The call returns CSSM_ESTATE when no series of the fleet has a cloud. */
+int cssm_fleet_init(cssm_fleet* f, const double* t0);
+int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                    double* ll_out, int32_t* ess_out, int* rc_out);
+
+/* cssm_pf_summary (getIntervals, model/ParticleFilter.scala:415-424) of every series at its own time: state_* [S * d], eta_* [S];
+ * any may be NULL.  Order statistics exact, ranks and clamping as documented there, means plain fp64 sums.  A series without a
+ * cloud reads NaN. */
+int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_mean, double* state_lower, double* state_upper,
+                       double* eta_of_mean, double* eta_lower, double* eta_upper);
+/* the cloud (SoA, d x N, as cssm_pf_get_particles) and the ancestors of series k; CSSM_ESTATE without a cloud */
+int cssm_fleet_get_particles(cssm_fleet* f, uint32_t k, double* out_dN);
+int cssm_fleet_get_ancestors(cssm_fleet* f, uint32_t k, uint32_t* out_N);
+/* ms2[0] = device time of the last ll_filter / init / step call (upload, launch, read-back), ms2[1] = of the last summary; HIP
+ * events on the fleet's stream, < 0 while there was none. */
+int cssm_fleet_last_ms(cssm_fleet* f, double* ms2);
+/* Diagnostic, no device: the compact per-observation record the fleet uploads for (t_prev, t, y, has_obs, step) under `desc`,
+ * a cloud of n_particles and Philox key `seed` -- 80 + 40 d bytes: y, c[4], cdf, u, dt, ref (doubles), has_obs (i32), step (u32),
+ * then d x 4 transition coefficients and d f coefficients, each the value cssm_pf_step's record holds. */
+int cssm_fleet_pack_record(const cssm_model_desc* desc, uint64_t n_particles, uint64_t seed, double t_prev, double t, double y,
+                           int has_obs, uint32_t step, unsigned char* out, size_t cap, size_t* bytes);
+
 /* ---- errors / build info ------------------------------------------------------------------ */
 const char* cssm_last_error(void);
 const char* cssm_version(void);
