@@ -172,10 +172,8 @@ extern "C" int cssm_pfb_create(const cssm_model_desc* desc, uint64_t n_particles
   if (!out) return fail(CSSM_EINVAL_ARG, "out is null");
   *out = nullptr;
   if (n_chains < 1 || n_chains > 64) return fail(CSSM_EINVAL_ARG, "1 .. 64 chains per batch");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range (%d devices)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  const int rc_dev = cssm_use_device(device);
+  if (rc_dev) return rc_dev;
   cssm_pfb* b = new cssm_pfb();
   b->B = n_chains; b->device = device;
   auto bail = [&](int rc) { const std::string keep = cssm_last_error(); cssm_pfb_destroy(b); return fail(rc, "%s", keep.c_str()); };

@@ -300,11 +300,10 @@ __device__ __forceinline__ void draw_normals(uint64_t seed, uint64_t gid, uint32
   for (int k = 0; k < D; ++k) z[k] = odd ? E[k + S] : E[k];
 }
 
-// One transition of component k (model/Sde.scala:86-95,114-123,139-150; :30-43 for Euler); components are independent.
-template <int D>
-__device__ __forceinline__ void transition_one(const ModelK& mk, const StepRec* __restrict__ rec, double dt, int k, double& xk, double zk) {
-  const double p0 = rec->coef[k][0], p1 = rec->coef[k][1], p2 = rec->coef[k][2], p3 = rec->coef[k][3];
-  const int kind = mk.kind(k);
+// One transition of a component on its coefficients p0 .. p3 (model/Sde.scala:86-95,114-123,139-150; :30-43 for Euler); components
+// are independent.  The only statement of this arithmetic: a record's coefficients (transition_one) and a particle's own
+// (cssm_forecast.hip) both come here, so equal coefficients give equal bits.
+__device__ __forceinline__ void transition_step(int kind, double p0, double p1, double p2, double p3, double dt, double& xk, double zk) {
   if (kind == CSSM_SDE_BROWNIAN) {
     xk = p3 * zk + xk;
   } else if (kind == CSSM_SDE_GEN_BROWNIAN) {
@@ -319,6 +318,12 @@ __device__ __forceinline__ void transition_one(const ModelK& mk, const StepRec* 
     double b = p2 * dW;
     xk = (xk + a) + b;
   }
+}
+// ... of component k under the record's coefficients
+template <int D>
+__device__ __forceinline__ void transition_one(const ModelK& mk, const StepRec* __restrict__ rec, double dt, int k, double& xk, double zk) {
+  const double p0 = rec->coef[k][0], p1 = rec->coef[k][1], p2 = rec->coef[k][2], p3 = rec->coef[k][3];
+  transition_step(mk.kind(k), p0, p1, p2, p3, dt, xk, zk);
 }
 template <int D>
 __device__ __forceinline__ void transition(const ModelK& mk, const StepRec* __restrict__ rec, double dt,

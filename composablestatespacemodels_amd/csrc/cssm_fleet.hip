@@ -138,22 +138,6 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_summary(const double* __re
   }
 }
 
-// link(f(mean, t)) on the host (cssm_eta_of_mean of cssm_pf.hip takes a handle; the same statements on the model alone)
-static double fleet_eta_of_mean(const HostModel& m, const double* fco, const double* mean) {
-  double g = 0.0, acc = 0.0;
-  for (int k = 0; k < m.d; ++k) {
-    const int fm = m.mk.fmode(k);
-    if (fm == FM_START) acc = fco[k] * mean[k]; else if (fm == FM_ADD) acc = acc + fco[k] * mean[k];
-    if (m.mk.leaf_end(k)) g = m.mk.first_leaf(k) ? acc : g + acc;
-  }
-  switch (m.obs_kind) {
-    case CSSM_OBS_POISSON: case CSSM_OBS_NEGBIN: case CSSM_OBS_ZIP: return cssm_exp(g);
-    case CSSM_OBS_BERNOULLI: return (g > 6.0) ? 1.0 : ((g < -6.0) ? 0.0 : 1.0 / (1.0 + cssm_exp(-g)));
-    case CSSM_OBS_BETA: return cssm_exp(-g);
-    default: return g;
-  }
-}
-
 extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
@@ -178,10 +162,8 @@ extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particl
   if (rc) return rc;
   if (base.obs_kind == CSSM_OBS_LGCP)
     return fail(CSSM_EINVAL_DESC, "the fleet filter does not serve the LGCP observation model (sub-stepped events); " FLEET_SERVED);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range (%d devices)", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  rc = cssm_use_device(device);
+  if (rc) return rc;
   cssm_fleet* f = new cssm_fleet();
   f->device = device; f->n = (uint32_t)n_particles; f->S = n_series; f->d = base.d;
   base.n_global = n_particles; base.seed = 0;
@@ -453,9 +435,9 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
       hcur[k] = f->live[k] ? (f->step[k] & 1u) : 0xffffffffu;
     }
   });
-  // ranks, 0-based ascending (cssm_pf_summary): states (N - index - 1, index - 1), eta (N - index, index), index = floor(interval N)
-  const long long idxr = (long long)std::floor(interval * (double)n);
-  auto clampr = [&](long long r) { return (uint32_t)std::min<long long>(std::max<long long>(r, 0), (long long)n - 1); };
+  SelState rs, re;   // the ranks of a state row and of the eta row, as cssm_pf_summary takes them
+  sel_ranks(rs, n, interval, true);
+  sel_ranks(re, n, interval, false);
   uint32_t np2 = 2u;
   while (np2 < n) np2 <<= 1;
   double* d_fco = f->d_sm; double* d_out = f->d_sm + n_fco;
@@ -463,7 +445,7 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
   HIP_TRY(hipEventRecord(f->ev[2], f->stream));
   HIP_TRY(hipMemcpyAsync(f->d_sm, hbuf.data(), need * 8, hipMemcpyHostToDevice, f->stream));
   DISPATCH_D(d, hipLaunchKernelGGL(k_fleet_summary<D>, dim3(S, rows), dim3(CSSM_BLOCK), (size_t)np2 * 8u, f->stream, f->state, f->anc, d_cur, d_fco, n, np2,
-                                   f->base.mk, clampr((long long)n - idxr - 1), clampr(idxr - 1), clampr((long long)n - idxr), clampr(idxr), d_out));
+                                   f->base.mk, (uint32_t)rs.rank[0], (uint32_t)rs.rank[1], (uint32_t)re.rank[0], (uint32_t)re.rank[1], d_out));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(hbuf.data() + n_fco, d_out, n_out * 8, hipMemcpyDeviceToHost, f->stream));
   HIP_TRY(hipEventRecord(f->ev[3], f->stream));
@@ -482,7 +464,7 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
     const double* oe = ho + ((size_t)k * rows + d) * 3;
     if (eta_lower) eta_lower[k] = oe[1];
     if (eta_upper) eta_upper[k] = oe[2];
-    if (eta_of_mean) eta_of_mean[k] = f->live[k] ? fleet_eta_of_mean(f->models[k], hbuf.data() + (size_t)k * d, mean) : cssm_nan();   // :420
+    if (eta_of_mean) eta_of_mean[k] = f->live[k] ? cssm_eta_of_mean(f->models[k], hbuf.data() + (size_t)k * d, mean) : cssm_nan();   // :420
   }
   return CSSM_OK;
 }

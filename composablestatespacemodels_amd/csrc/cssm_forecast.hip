@@ -2,12 +2,18 @@
 // 368-409) and the scan of SimulateData.forecast + summariseForecast over future times (model/Data.scala:196-231), and the stateless
 // observation draw on given etas (cssm_obs_draw).  See include/cssm_pf.h for the contract, include/cssm_obs_draws.h for the draws.
 //
-// One call = chunks of horizons.  Per chunk: k_forecast<D> (one thread per particle PAIR, so that every Philox block of the
-// transition serves both particles, as in k_propagate) gathers the pair once -- from the handle's current cloud through the same
-// indirection k_summary_fill reads, or from the carry buffer of the chunk before -- and runs the chunk's horizons with the state in
-// registers: transition (CSSM_STREAM_STEP under `key` at step h), gamma and eta at t[h], one observation draw (CSSM_STREAM_OBS), the
-// d + 2 order keys and the block's fp64 partial sums per horizon.  Then one radix selection (k_sel_hist / k_sel_pick, grid.y = the
-// chunk's rows) and k_forecast_finish (means and the order statistics per row).  The filter's own buffers are only read.
+// One call = chunks of horizons.  Per chunk: the forecast kernel (one thread per particle PAIR, so that every Philox block of the
+// transition serves both particles, as in k_propagate) gathers the pair once -- from its source, or from the carry buffer of the
+// chunk before -- and runs the chunk's horizons with the state in registers: transition (CSSM_STREAM_STEP under `key` at step h),
+// gamma and eta at t[h], one observation draw (CSSM_STREAM_OBS), the d + 2 order keys and the block's fp64 partial sums per horizon.
+// Then one radix selection (k_sel_hist / k_sel_pick, grid.y = the chunk's rows) and k_forecast_finish (means and the order
+// statistics per row).  The filter's own buffers are only read.
+//
+// All of that is forecast_body<D, Src>, written once.  The two kernels are entry points that fill a source and call it:
+// k_forecast<D> with CloudSrc (the handle's current cloud through the indirection k_summary_fill reads, moved under the handle's
+// records) and k_forecast_post<D> with PostSrc (a pair of a posterior sample per particle: its state, its own parameters).  A source
+// says where a particle starts, what moves a pair one step and which observation parameters each particle draws with; both step
+// whole pairs through pair_normals_feed and a component through transition_step (cssm_device.hip.h).
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
 #include "cssm_sde_coef.h"
@@ -15,14 +21,38 @@
 
 #include <cmath>
 
-template <int D>
-__global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restrict__ src, size_t src_stride, const uint32_t* __restrict__ anc,
-                                                         const double* __restrict__ src2, size_t src2_stride, uint32_t n_split,
-                                                         double* __restrict__ carry, int from_carry, int to_carry, uint64_t n,
-                                                         const StepRec* __restrict__ recs, uint32_t h0, uint32_t hc, ModelK mk, uint64_t key,
-                                                         cssm_obs_params op, const double* __restrict__ logtab,
-                                                         unsigned long long* __restrict__ keys, double* __restrict__ partial,
-                                                         double* __restrict__ samples) {
+// The 2 D normals of the pair (2m, 2m+1) as propagate_pair (cssm_device.hip.h) draws them: its ceil(D / 2) Philox blocks in order, each
+// normal handed to feed(b, k, e) as soon as it exists -- normal q goes to particle b = q / D of the pair, component k = q % D.  Both
+// sources below step whole pairs through this loop.  MUST CHANGE TOGETHER WITH propagate_pair, which keeps its own statement of the
+// loop: k_propagate's code changes when its loop goes through a callable (profiles/forecast_body_pair_loop_asm.md), and that kernel
+// is not to move.  tests/test_gpu_forecast.py holds k_forecast to the oracle's propagate bit for bit.
+template <int D, class Feed>
+__device__ __forceinline__ void pair_normals_feed(uint64_t seed, uint64_t gid_even, uint32_t step, const double* tab, Feed&& feed) {
+  const uint64_t stream = cssm_pair_stream(gid_even);
+  auto give = [&](int q, double e) {            // (q is a compile-time constant wherever this is called)
+    if (q < 2 * D) feed(q / D, q % D, e);
+  };
+#pragma unroll
+  for (int B = 0; B < (D + 1) / 2; ++B) {
+    const cssm_u32x4 blk = cssm_philox_draw(seed, stream, step, CSSM_STREAM_STEP, (uint32_t)B);
+    double e0, e1;
+    cssm_normal_pair64(blk.v[0], blk.v[1], tab, &e0, &e1);
+    give(4 * B, e0); give(4 * B + 1, e1);
+    if (2 * B + 1 < D) {
+      cssm_normal_pair64(blk.v[2], blk.v[3], tab, &e0, &e1);
+      give(4 * B + 2, e0); give(4 * B + 3, e1);
+    }
+  }
+}
+
+// What the two forecasts share -- everything but where a particle starts and what moves it.  One thread per particle PAIR; a source
+// `s` answers: begin (what it needs of the pair before the first load), x0 (component k of particle i, the pair's particle b, before
+// the first chunk), step (one transition of the pair, or of its first particle alone) and obs (the observation parameters b draws with).
+template <int D, class Src>
+__device__ __forceinline__ void forecast_body(Src& s, double* __restrict__ carry, int from_carry, int to_carry, uint64_t n,
+                                              const StepRec* __restrict__ recs, uint32_t h0, uint32_t hc, const ModelK& mk, uint64_t key,
+                                              const double* __restrict__ logtab, unsigned long long* __restrict__ keys,
+                                              double* __restrict__ partial, double* __restrict__ samples) {
   constexpr int R = D + 2;   // rows per horizon: the D state components, eta, the observation
   __shared__ double s_p[CSSM_BLOCK / 64][R];
   const double* tab = stage_log_table(logtab);
@@ -32,30 +62,23 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restric
   const uint64_t ia = 2 * p, ib = ia + 1;
   const bool hasb = live && ib < n;
   const size_t rows = (size_t)hc * R;
+  s.begin(live, hasb, ia, ib, key, from_carry);
   double xa[D], xb[D];
-  auto load = [&](uint64_t i, int k) -> double {
-    if (from_carry) return carry[(size_t)k * n + i];
-    const size_t j = anc ? (size_t)anc[i] : (size_t)i;
-    return (src2 && j >= n_split)
-        ? (src2_stride == 0 ? ld_sys_f64(src2 + (size_t)(j - n_split) * (size_t)(D + 1) + k) : ld_sys_f64(src2 + (size_t)k * src2_stride + (j - n_split)))
-        : src[(size_t)k * src_stride + j];
-  };
 #pragma unroll
   for (int k = 0; k < D; ++k) {
-    xa[k] = live ? load(ia, k) : 0.0;
-    xb[k] = hasb ? load(ib, k) : 0.0;
+    xa[k] = live ? (from_carry ? carry[(size_t)k * n + ia] : s.x0(0, ia, k)) : 0.0;
+    xb[k] = hasb ? (from_carry ? carry[(size_t)k * n + ib] : s.x0(1, ib, k)) : 0.0;
   }
   for (uint32_t j = 0; j < hc; ++j) {
     const StepRec* rec = recs + j;
     const uint32_t h = h0 + j;
     double ga = 0.0, gb = 0.0, ea = 0.0, eb = 0.0, oa = 0.0, ob = 0.0;
     if (live) {
-      if (hasb) propagate_pair<D>(mk, rec, rec->dt, key, ia, h, tab, xa, xb);
-      else propagate_one<D>(mk, rec, rec->dt, key, ia, h, tab, xa);
+      s.step(hasb, mk, rec, key, ia, h, tab, xa, xb);
       ga = gamma_of<D>(mk, rec, xa);
       ea = link_of(mk.obs_kind, ga);
       cssm_obs_stream sa = cssm_obs_stream_at(key, ia, h);
-      oa = cssm_obs_draw_one(&op, ea, &sa, tab);
+      oa = cssm_obs_draw_one(&s.obs(0), ea, &sa, tab);
       unsigned long long* kr = keys + (size_t)j * R * n;
 #pragma unroll
       for (int k = 0; k < D; ++k) kr[(size_t)k * n + ia] = cssm_order_key(xa[k]);
@@ -65,7 +88,7 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restric
         gb = gamma_of<D>(mk, rec, xb);
         eb = link_of(mk.obs_kind, gb);
         cssm_obs_stream sb = cssm_obs_stream_at(key, ib, h);
-        ob = cssm_obs_draw_one(&op, eb, &sb, tab);
+        ob = cssm_obs_draw_one(&s.obs(1), eb, &sb, tab);
 #pragma unroll
         for (int k = 0; k < D; ++k) kr[(size_t)k * n + ib] = cssm_order_key(xb[k]);
         kr[(size_t)D * n + ib] = cssm_order_key(eb);
@@ -108,6 +131,42 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restric
   }
 }
 
+// Source 1: the handle's cloud under the handle's records.  A particle is gathered through the indirection k_summary_fill reads and
+// moves by transition_one on the record (the unpaired last particle of an odd cloud: propagate_one); both particles draw with the
+// model's one set of observation parameters.
+template <int D>
+struct CloudSrc {
+  const double* __restrict__ src; size_t src_stride; const uint32_t* __restrict__ anc; const double* __restrict__ src2; size_t src2_stride;
+  uint32_t n_split;
+  cssm_obs_params op;
+  __device__ __forceinline__ void begin(bool, bool, uint64_t, uint64_t, uint64_t, int) {}
+  __device__ __forceinline__ double x0(int, uint64_t i, int k) const {
+    const size_t j = anc ? (size_t)anc[i] : (size_t)i;
+    return (src2 && j >= n_split)
+        ? (src2_stride == 0 ? ld_sys_f64(src2 + (size_t)(j - n_split) * (size_t)(D + 1) + k) : ld_sys_f64(src2 + (size_t)k * src2_stride + (j - n_split)))
+        : src[(size_t)k * src_stride + j];
+  }
+  __device__ __forceinline__ void step(bool hasb, const ModelK& mk, const StepRec* __restrict__ rec, uint64_t key, uint64_t ia, uint32_t h,
+                                       const double* tab, double (&xa)[D], double (&xb)[D]) const {
+    const double dt = rec->dt;
+    if (hasb) pair_normals_feed<D>(key, ia, h, tab, [&](int b, int k, double e) { transition_one<D>(mk, rec, dt, k, b ? xb[k] : xa[k], e); });
+    else propagate_one<D>(mk, rec, dt, key, ia, h, tab, xa);
+  }
+  __device__ __forceinline__ const cssm_obs_params& obs(int) const { return op; }
+};
+
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restrict__ src, size_t src_stride, const uint32_t* __restrict__ anc,
+                                                         const double* __restrict__ src2, size_t src2_stride, uint32_t n_split,
+                                                         double* __restrict__ carry, int from_carry, int to_carry, uint64_t n,
+                                                         const StepRec* __restrict__ recs, uint32_t h0, uint32_t hc, ModelK mk, uint64_t key,
+                                                         cssm_obs_params op, const double* __restrict__ logtab,
+                                                         unsigned long long* __restrict__ keys, double* __restrict__ partial,
+                                                         double* __restrict__ samples) {
+  CloudSrc<D> s{src, src_stride, anc, src2, src2_stride, n_split, op};
+  forecast_body<D>(s, carry, from_carry, to_carry, n, recs, h0, hc, mk, key, logtab, keys, partial, samples);
+}
+
 // ---- forecasts from a joint posterior sample (cssm_pf_forecast_posterior): particle i starts from the state of pair pick_i and
 // moves under that pair's parameter set.  A particle's set is the 3 D constrained values (mu, phi, sigma) of its posterior row, held in
 // registers up to D = 8 and read from the row (L2-resident: M x (3 D + 1) doubles) above, where two particles' sets would spill.
@@ -131,65 +190,52 @@ struct PostParams<D, false> {
   __device__ __forceinline__ double sigma(int k) const { return row[3 * k + 2]; }
 };
 
-// transition_one (cssm_device.hip.h) with the component's coefficients evaluated from the particle's own parameters
-// (cssm_sde_coef: what cssm_build_rec puts into a record for them) -- the same arithmetic, so equal parameters give equal bits
-template <class P>
-__device__ __forceinline__ void transition_post(int kind, const P& prm, int k, double dt, double& xk, double zk) {
-  double c[4];
-  cssm_sde_coef(kind, prm.mu(k), prm.phi(k), prm.sigma(k), dt, c);
-  const double p0 = c[0], p1 = c[1], p2 = c[2], p3 = c[3];
-  if (kind == CSSM_SDE_BROWNIAN) {
-    xk = p3 * zk + xk;
-  } else if (kind == CSSM_SDE_GEN_BROWNIAN) {
-    double mean = xk + p0;
-    xk = p3 * zk + mean;
-  } else if (kind == CSSM_SDE_OU) {
-    double mean = p0 + (xk - p0) * p1;
-    xk = p3 * zk + mean;
-  } else {
-    double dW = p3 * zk;
-    double a = (p0 + p1 * xk) * dt;
-    double b = p2 * dW;
-    xk = (xk + a) + b;
+// Source 2: a pair of the posterior sample per particle.  The first chunk gathers x0[pick_i] (M x D), every chunk loads row pick_i
+// of `rows` (M x (3 D + 1): the parameter set, then the observation constant p0).  pick_i = pick[i], or the draw
+// cssm_posterior_pick(key, i, M) when pick is null; pick_out (optional) receives it in the first chunk.  A component moves by
+// transition_step on the coefficients cssm_sde_coef gives for the particle's own parameters (what cssm_build_rec puts into a record
+// for them): the same arithmetic, so equal parameters give equal bits.  Philox streams and f are those of the handle's records.
+template <int D>
+struct PostSrc {
+  static constexpr size_t S = 3 * D + 1;
+  const double* __restrict__ x; const double* __restrict__ rows; uint64_t M; const uint32_t* __restrict__ pick; uint32_t* __restrict__ pick_out;
+  cssm_obs_params opa, opb;   // (kind and df: the model's; p0: the particle's row)
+  uint64_t ma, mb;
+  PostParams<D> pa, pb;
+  __device__ __forceinline__ void begin(bool live, bool hasb, uint64_t ia, uint64_t ib, uint64_t key, int from_carry) {
+    auto pick_of = [&](uint64_t i) -> uint64_t { return pick ? (uint64_t)pick[i] : (uint64_t)cssm_posterior_pick(key, i, M); };
+    ma = live ? pick_of(ia) : 0; mb = hasb ? pick_of(ib) : 0;
+    if (pick_out && !from_carry) {
+      if (live) pick_out[ia] = (uint32_t)ma;
+      if (hasb) pick_out[ib] = (uint32_t)mb;
+    }
+    pa.load(rows + ma * S);
+    pb.load(rows + mb * S);
+    opa.p0 = rows[ma * S + 3 * D];
+    opb.p0 = rows[mb * S + 3 * D];
   }
-}
-
-// propagate_pair with a parameter set per particle: the pair's Philox blocks in the same order, normal q -> particle q / D,
-// component q % D
-template <int D, class P>
-__device__ __forceinline__ void propagate_pair_post(const ModelK& mk, double dt, uint64_t seed, uint64_t gid_even, uint32_t step,
-                                                    const double* tab, const P& pa, const P& pb, double (&xa)[D], double (&xb)[D]) {
-  const uint64_t stream = cssm_pair_stream(gid_even);
-  auto feed = [&](int q, double e) {            // (q is a compile-time constant wherever this is called)
-    if (q < D) transition_post(mk.kind(q % D), pa, q % D, dt, xa[q % D], e);
-    else if (q < 2 * D) transition_post(mk.kind((q - D + D) % D), pb, (q - D + D) % D, dt, xb[(q - D + D) % D], e);
-  };
+  __device__ __forceinline__ double x0(int b, uint64_t, int k) const { return x[(b ? mb : ma) * D + k]; }
+  static __device__ __forceinline__ void move(int kind, const PostParams<D>& prm, int k, double dt, double& xk, double zk) {
+    double c[4];
+    cssm_sde_coef(kind, prm.mu(k), prm.phi(k), prm.sigma(k), dt, c);
+    transition_step(kind, c[0], c[1], c[2], c[3], dt, xk, zk);
+  }
+  // (the unpaired last particle of an odd cloud is keyed as propagate_one keys it)
+  __device__ __forceinline__ void step(bool hasb, const ModelK& mk, const StepRec* __restrict__ rec, uint64_t key, uint64_t ia, uint32_t h,
+                                       const double* tab, double (&xa)[D], double (&xb)[D]) const {
+    const double dt = rec->dt;
+    if (hasb) {
+      pair_normals_feed<D>(key, ia, h, tab, [&](int b, int k, double e) { move(mk.kind(k), b ? pb : pa, k, dt, b ? xb[k] : xa[k], e); });
+    } else {
+      double z[D];
+      draw_normals<D>(key, ia, h, CSSM_STREAM_STEP, tab, z);
 #pragma unroll
-  for (int B = 0; B < (D + 1) / 2; ++B) {
-    const cssm_u32x4 blk = cssm_philox_draw(seed, stream, step, CSSM_STREAM_STEP, (uint32_t)B);
-    double e0, e1;
-    cssm_normal_pair64(blk.v[0], blk.v[1], tab, &e0, &e1);
-    feed(4 * B, e0); feed(4 * B + 1, e1);
-    if (2 * B + 1 < D) {
-      cssm_normal_pair64(blk.v[2], blk.v[3], tab, &e0, &e1);
-      feed(4 * B + 2, e0); feed(4 * B + 3, e1);
+      for (int k = 0; k < D; ++k) move(mk.kind(k), pa, k, dt, xa[k], z[k]);
     }
   }
-}
-// ... and for one particle of either parity (the last, unpaired particle of an odd cloud), keyed as propagate_one
-template <int D, class P>
-__device__ __forceinline__ void propagate_one_post(const ModelK& mk, double dt, uint64_t seed, uint64_t gid, uint32_t step,
-                                                   const double* tab, const P& pa, double (&x)[D]) {
-  double z[D];
-  draw_normals<D>(seed, gid, step, CSSM_STREAM_STEP, tab, z);
-#pragma unroll
-  for (int k = 0; k < D; ++k) transition_post(mk.kind(k), pa, k, dt, x[k], z[k]);
-}
+  __device__ __forceinline__ const cssm_obs_params& obs(int b) const { return b ? opb : opa; }
+};
 
-// k_forecast with the particle's pair: the first chunk gathers x0[pick_i] (M x D), every chunk loads row pick_i of `rows`
-// (M x (3 D + 1): the parameter set, then the observation constant p0).  pick_i = pick[i], or the draw cssm_posterior_pick(key, i, M)
-// when pick is null; pick_out (optional) receives it in the first chunk.  Everything else -- Philox streams, f from the handle's
-// records, the order keys, partial sums, samples and the carry -- is k_forecast's.
 template <int D>
 __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast_post(const double* __restrict__ x0, const double* __restrict__ rows, uint64_t M,
                                                               const uint32_t* __restrict__ pick, uint32_t* __restrict__ pick_out,
@@ -198,96 +244,9 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast_post(const double* __re
                                                               int obs_df, const double* __restrict__ logtab,
                                                               unsigned long long* __restrict__ keys, double* __restrict__ partial,
                                                               double* __restrict__ samples) {
-  constexpr int R = D + 2;   // rows per horizon: the D state components, eta, the observation
-  constexpr size_t S = 3 * D + 1;
-  __shared__ double s_p[CSSM_BLOCK / 64][R];
-  const double* tab = stage_log_table(logtab);
-  const uint64_t npairs = (n + 1) / 2;
-  const uint64_t p = (uint64_t)blockIdx.x * CSSM_BLOCK + threadIdx.x;
-  const bool live = p < npairs;
-  const uint64_t ia = 2 * p, ib = ia + 1;
-  const bool hasb = live && ib < n;
-  const size_t rows_c = (size_t)hc * R;
-  auto pick_of = [&](uint64_t i) -> uint64_t { return pick ? (uint64_t)pick[i] : (uint64_t)cssm_posterior_pick(key, i, M); };
-  const uint64_t ma = live ? pick_of(ia) : 0, mb = hasb ? pick_of(ib) : 0;
-  if (pick_out && !from_carry) {
-    if (live) pick_out[ia] = (uint32_t)ma;
-    if (hasb) pick_out[ib] = (uint32_t)mb;
-  }
-  PostParams<D> pa, pb;
-  pa.load(rows + ma * S);
-  pb.load(rows + mb * S);
-  cssm_obs_params opa, opb;
-  opa.kind = opb.kind = mk.obs_kind; opa.df = opb.df = obs_df;
-  opa.p0 = rows[ma * S + 3 * D];
-  opb.p0 = rows[mb * S + 3 * D];
-  double xa[D], xb[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    xa[k] = live ? (from_carry ? carry[(size_t)k * n + ia] : x0[ma * D + k]) : 0.0;
-    xb[k] = hasb ? (from_carry ? carry[(size_t)k * n + ib] : x0[mb * D + k]) : 0.0;
-  }
-  for (uint32_t j = 0; j < hc; ++j) {
-    const StepRec* rec = recs + j;
-    const uint32_t h = h0 + j;
-    double ga = 0.0, gb = 0.0, ea = 0.0, eb = 0.0, oa = 0.0, ob = 0.0;
-    if (live) {
-      if (hasb) propagate_pair_post<D>(mk, rec->dt, key, ia, h, tab, pa, pb, xa, xb);
-      else propagate_one_post<D>(mk, rec->dt, key, ia, h, tab, pa, xa);
-      ga = gamma_of<D>(mk, rec, xa);
-      ea = link_of(mk.obs_kind, ga);
-      cssm_obs_stream sa = cssm_obs_stream_at(key, ia, h);
-      oa = cssm_obs_draw_one(&opa, ea, &sa, tab);
-      unsigned long long* kr = keys + (size_t)j * R * n;
-#pragma unroll
-      for (int k = 0; k < D; ++k) kr[(size_t)k * n + ia] = cssm_order_key(xa[k]);
-      kr[(size_t)D * n + ia] = cssm_order_key(ea);
-      kr[(size_t)(D + 1) * n + ia] = cssm_order_key(oa);
-      if (hasb) {
-        gb = gamma_of<D>(mk, rec, xb);
-        eb = link_of(mk.obs_kind, gb);
-        cssm_obs_stream sb = cssm_obs_stream_at(key, ib, h);
-        ob = cssm_obs_draw_one(&opb, eb, &sb, tab);
-#pragma unroll
-        for (int k = 0; k < D; ++k) kr[(size_t)k * n + ib] = cssm_order_key(xb[k]);
-        kr[(size_t)D * n + ib] = cssm_order_key(eb);
-        kr[(size_t)(D + 1) * n + ib] = cssm_order_key(ob);
-      }
-      if (samples) {   // rows of horizon j: state..., gamma, eta, obs
-        double* sr = samples + (size_t)j * (D + 3) * n;
-#pragma unroll
-        for (int k = 0; k < D; ++k) sr[(size_t)k * n + ia] = xa[k];
-        sr[(size_t)D * n + ia] = ga; sr[(size_t)(D + 1) * n + ia] = ea; sr[(size_t)(D + 2) * n + ia] = oa;
-        if (hasb) {
-#pragma unroll
-          for (int k = 0; k < D; ++k) sr[(size_t)k * n + ib] = xb[k];
-          sr[(size_t)D * n + ib] = gb; sr[(size_t)(D + 1) * n + ib] = eb; sr[(size_t)(D + 2) * n + ib] = ob;
-        }
-      }
-    }
-    // the block's partial sums of the horizon's R rows, summed as k_forecast sums them
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      double v = (k < D) ? xa[k % D] + xb[k % D] : (k == D ? ea + eb : oa + ob);
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < R) {
-      double v = 0.0;
-      for (int w = 0; w < CSSM_BLOCK / 64; ++w) v += s_p[w][threadIdx.x];
-      partial[(size_t)blockIdx.x * rows_c + (size_t)j * R + threadIdx.x] = v;
-    }
-    __syncthreads();
-  }
-  if (to_carry && live) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      carry[(size_t)k * n + ia] = xa[k];
-      if (hasb) carry[(size_t)k * n + ib] = xb[k];
-    }
-  }
+  PostSrc<D> s{x0, rows, M, pick, pick_out};
+  s.opa.kind = s.opb.kind = mk.obs_kind; s.opa.df = s.opb.df = obs_df;
+  forecast_body<D>(s, carry, from_carry, to_carry, n, recs, h0, hc, mk, key, logtab, keys, partial, samples);
 }
 
 // per row of the chunk: out[3 row] = mean (block partials / n), out[3 row + 1 / + 2] = the two selected order statistics
@@ -349,25 +308,17 @@ extern "C" int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_
   cssm_obs_params op;
   int rc = obs_params(obs_kind, has_scale, scale, df, &op);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range", device);
-  HIP_TRY(hipSetDevice(device));
+  rc = cssm_use_device(device);
+  if (rc) return rc;
+  CssmTemps tmp;
   double *de = nullptr, *dout = nullptr, *dtab = nullptr;
-  if (hipMalloc(&de, n * 8) != hipSuccess || hipMalloc(&dout, n * 8) != hipSuccess || hipMalloc(&dtab, sizeof(CSSM_TAB)) != hipSuccess)
-    rc = fail(CSSM_ENOMEM, "hipMalloc");
-  if (!rc && (hipMemcpy(de, eta, n * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dtab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice) != hipSuccess))
-    rc = fail(CSSM_EHIP, "upload");
-  if (!rc) {
-    hipLaunchKernelGGL(k_obs_draw, dim3(grid_for(n, CSSM_BLOCK, kGridCap)), dim3(CSSM_BLOCK), 0, 0, op, de, (uint64_t)n, key, step, dtab, dout);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(CSSM_EHIP, "cssm_obs_draw: %s", hipGetErrorString(e));
-  }
-  if (de) (void)hipFree(de);
-  if (dout) (void)hipFree(dout);
-  if (dtab) (void)hipFree(dtab);
-  return rc;
+  HIP_ALLOC(tmp, de, n * 8); HIP_ALLOC(tmp, dout, n * 8); HIP_ALLOC(tmp, dtab, sizeof(CSSM_TAB));
+  HIP_TRY(hipMemcpy(de, eta, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dtab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_obs_draw, dim3(grid_for(n, CSSM_BLOCK, kGridCap)), dim3(CSSM_BLOCK), 0, 0, op, de, (uint64_t)n, key, step, dtab, dout);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
+  return CSSM_OK;
 }
 
 // Horizon times after t_start: finite and non-decreasing (`start` names t_start in the message)
@@ -390,7 +341,6 @@ template <class Launch>
 static int forecast_chunks(cssm_pf* pf, double t_start, const double* t, size_t H, double interval, double* state_mean, double* state_lower,
                            double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
                            double* obs_upper, double* samples, Launch&& launch) {
-  int rc = CSSM_OK;
   HIP_TRY(hipSetDevice(pf->device));
   const int d = pf->d, R = d + 2;
   const uint64_t n = pf->n;
@@ -402,43 +352,35 @@ static int forecast_chunks(cssm_pf* pf, double t_start, const double* t, size_t 
   const uint64_t npairs = (n + 1) / 2;
   const int nb_f = (int)((npairs + CSSM_BLOCK - 1) / CSSM_BLOCK);
   const int nb_s = grid_for(n, CSSM_BLOCK, 1024);
-  const long long idxr = (long long)std::floor(interval * (double)n);   // ranks as summary_impl forms them
-  auto clampr = [&](long long r) { return (unsigned long long)std::min<long long>(std::max<long long>(r, 0), (long long)n - 1); };
   std::vector<StepRec> hrec(H);
   for (size_t h = 0; h < H; ++h) cssm_build_rec(pf, h ? t[h - 1] : t_start, t[h], 0.0, 0, (uint32_t)h, &hrec[h]);
   std::vector<SelState> hst(rows_max);
   std::vector<double> hout(3 * rows_max);
+  CssmTemps tmp;
   StepRec* drec = nullptr; double* carry = nullptr; unsigned long long* keys = nullptr; double* partial = nullptr; SelState* st = nullptr;
   uint32_t* hist = nullptr; double* out = nullptr; double* dsamp = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   double ms_kernel = 0.0, ms_select = 0.0;
   const bool chunked = hc < H;
-#define FC_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(CSSM_EHIP, "%s: %s", #expr, hipGetErrorString(e__)); goto done; } } while (0)
-#define FC_ALLOC(p, bytes) do { if (hipMalloc(&(p), (bytes)) != hipSuccess) { rc = fail(CSSM_ENOMEM, "hipMalloc(%zu) for the forecast", (size_t)(bytes)); goto done; } } while (0)
-  FC_ALLOC(drec, H * sizeof(StepRec));
-  FC_ALLOC(keys, rows_max * n * 8);
-  FC_ALLOC(partial, (size_t)nb_f * rows_max * 8);
-  FC_ALLOC(st, rows_max * sizeof(SelState));
-  FC_ALLOC(hist, rows_max * 512 * 4);
-  FC_ALLOC(out, 3 * rows_max * 8);
-  if (chunked) FC_ALLOC(carry, (size_t)d * n * 8);
-  if (samples) FC_ALLOC(dsamp, hc * (size_t)(d + 3) * n * 8);
-  for (int i = 0; i < 3; ++i) FC_TRY(hipEventCreate(&ev[i]));
-  FC_TRY(hipMemcpyAsync(drec, hrec.data(), H * sizeof(StepRec), hipMemcpyHostToDevice, pf->stream));
+  HIP_ALLOC(tmp, drec, H * sizeof(StepRec));
+  HIP_ALLOC(tmp, keys, rows_max * n * 8);
+  HIP_ALLOC(tmp, partial, (size_t)nb_f * rows_max * 8);
+  HIP_ALLOC(tmp, st, rows_max * sizeof(SelState));
+  HIP_ALLOC(tmp, hist, rows_max * 512 * 4);
+  HIP_ALLOC(tmp, out, 3 * rows_max * 8);
+  if (chunked) HIP_ALLOC(tmp, carry, (size_t)d * n * 8);
+  if (samples) HIP_ALLOC(tmp, dsamp, hc * (size_t)(d + 3) * n * 8);
+  for (int i = 0; i < 3; ++i) HIP_TRY(tmp.event(ev[i]));
+  HIP_TRY(hipMemcpyAsync(drec, hrec.data(), H * sizeof(StepRec), hipMemcpyHostToDevice, pf->stream));
   for (size_t h0 = 0; h0 < H; h0 += hc) {
     const size_t hn = std::min(hc, H - h0), rows = hn * (size_t)R;
-    for (size_t r = 0; r < rows; ++r) {
-      const bool state_row = (int)(r % R) < d;   // getCredibleInterval (:496-501) vs getOrderStatistic (:455-460)
-      hst[r].prefix[0] = hst[r].prefix[1] = 0;
-      hst[r].rank[0] = clampr(state_row ? (long long)n - idxr - 1 : (long long)n - idxr);
-      hst[r].rank[1] = clampr(state_row ? idxr - 1 : idxr);
-    }
-    FC_TRY(hipMemcpyAsync(st, hst.data(), rows * sizeof(SelState), hipMemcpyHostToDevice, pf->stream));
-    FC_TRY(hipMemsetAsync(hist, 0, rows * 512 * 4, pf->stream));
-    FC_TRY(hipEventRecord(ev[0], pf->stream));
+    for (size_t r = 0; r < rows; ++r) sel_ranks(hst[r], n, interval, (int)(r % R) < d);
+    HIP_TRY(hipMemcpyAsync(st, hst.data(), rows * sizeof(SelState), hipMemcpyHostToDevice, pf->stream));
+    HIP_TRY(hipMemsetAsync(hist, 0, rows * 512 * 4, pf->stream));
+    HIP_TRY(hipEventRecord(ev[0], pf->stream));
     launch(h0, hn, (const StepRec*)(drec + h0), carry, (int)(h0 > 0), (int)(chunked && h0 + hn < H), keys, partial, dsamp, nb_f);
-    FC_TRY(hipGetLastError());
-    FC_TRY(hipEventRecord(ev[1], pf->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1], pf->stream));
     for (int shift = 56; shift >= 0; shift -= 8) {
       hipLaunchKernelGGL(k_sel_hist, dim3(nb_s, (unsigned)rows), dim3(CSSM_BLOCK), 0, pf->stream, (const unsigned long long*)keys, (size_t)n, n,
                          (const SelState*)st, shift, hist);
@@ -446,15 +388,15 @@ static int forecast_chunks(cssm_pf* pf, double t_start, const double* t, size_t 
     }
     hipLaunchKernelGGL(k_forecast_finish, dim3((unsigned)rows), dim3(CSSM_BLOCK), 0, pf->stream, (const SelState*)st, (const double*)partial, nb_f,
                        (int)rows, n, out);
-    FC_TRY(hipGetLastError());
-    FC_TRY(hipEventRecord(ev[2], pf->stream));
-    FC_TRY(hipMemcpyAsync(hout.data(), out, 3 * rows * 8, hipMemcpyDeviceToHost, pf->stream));
-    if (samples) FC_TRY(hipMemcpyAsync(samples + h0 * (size_t)(d + 3) * n, dsamp, hn * (size_t)(d + 3) * n * 8, hipMemcpyDeviceToHost, pf->stream));
-    FC_TRY(hipStreamSynchronize(pf->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[2], pf->stream));
+    HIP_TRY(hipMemcpyAsync(hout.data(), out, 3 * rows * 8, hipMemcpyDeviceToHost, pf->stream));
+    if (samples) HIP_TRY(hipMemcpyAsync(samples + h0 * (size_t)(d + 3) * n, dsamp, hn * (size_t)(d + 3) * n * 8, hipMemcpyDeviceToHost, pf->stream));
+    HIP_TRY(hipStreamSynchronize(pf->stream));
     {
       float a = 0.f, b = 0.f;
-      FC_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-      FC_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+      HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+      HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
       ms_kernel += a; ms_select += b;
     }
     for (size_t j = 0; j < hn; ++j) {
@@ -475,12 +417,7 @@ static int forecast_chunks(cssm_pf* pf, double t_start, const double* t, size_t 
   }
   pf->forecast_ms[0] = ms_kernel;
   pf->forecast_ms[1] = ms_select;
-done:
-#undef FC_TRY
-#undef FC_ALLOC
-  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  { void* ptrs[] = {drec, carry, keys, partial, st, hist, out, dsamp}; for (void* q : ptrs) if (q) (void)hipFree(q); }
-  return rc;
+  return CSSM_OK;
 }
 
 extern "C" int cssm_pf_forecast(cssm_pf* pf, const double* t, size_t H, uint64_t key, double interval, double* state_mean, double* state_lower,
@@ -547,17 +484,16 @@ extern "C" int cssm_pf_forecast_posterior(cssm_pf* pf, const cssm_model_desc* de
     return CSSM_OK;
   }
   HIP_TRY(hipSetDevice(pf->device));
+  CssmTemps tmp;
   double *dx = nullptr, *drows = nullptr;
   uint32_t *dpick = nullptr, *dpick_out = nullptr;
-#define FP_ALLOC(p, bytes) do { if (hipMalloc(&(p), (bytes)) != hipSuccess) { rc = fail(CSSM_ENOMEM, "hipMalloc(%zu) for the forecast", (size_t)(bytes)); goto done; } } while (0)
-#define FP_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(CSSM_EHIP, "%s: %s", #expr, hipGetErrorString(e__)); goto done; } } while (0)
-  FP_ALLOC(dx, M * (size_t)d * 8);
-  FP_ALLOC(drows, rows.size() * 8);
-  if (pick) FP_ALLOC(dpick, n * 4);
-  if (pick_out) FP_ALLOC(dpick_out, n * 4);
-  FP_TRY(hipMemcpy(dx, x, M * (size_t)d * 8, hipMemcpyHostToDevice));
-  FP_TRY(hipMemcpy(drows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
-  if (pick) FP_TRY(hipMemcpy(dpick, pick, n * 4, hipMemcpyHostToDevice));
+  HIP_ALLOC(tmp, dx, M * (size_t)d * 8);
+  HIP_ALLOC(tmp, drows, rows.size() * 8);
+  if (pick) HIP_ALLOC(tmp, dpick, n * 4);
+  if (pick_out) HIP_ALLOC(tmp, dpick_out, n * 4);
+  HIP_TRY(hipMemcpy(dx, x, M * (size_t)d * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(drows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+  if (pick) HIP_TRY(hipMemcpy(dpick, pick, n * 4, hipMemcpyHostToDevice));
   rc = forecast_chunks(pf, t0, t, H, interval, state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower,
                        obs_upper, samples,
                        [&](size_t h0, size_t hn, const StepRec* recs, double* carry, int from_carry, int to_carry, unsigned long long* keys,
@@ -567,11 +503,7 @@ extern "C" int cssm_pf_forecast_posterior(cssm_pf* pf, const cssm_model_desc* de
                                                           to_carry, n, recs, (uint32_t)h0, (uint32_t)hn, pf->mk, key, pf->obs_df,
                                                           (const double*)pf->d_logtab, keys, partial, dsamp));
                        });
-  if (!rc && pick_out) FP_TRY(hipMemcpy(pick_out, dpick_out, n * 4, hipMemcpyDeviceToHost));
-done:
-#undef FP_ALLOC
-#undef FP_TRY
-  { void* ptrs[] = {dx, drows, dpick, dpick_out}; for (void* q : ptrs) if (q) (void)hipFree(q); }
+  if (!rc && pick_out) HIP_TRY(hipMemcpy(pick_out, dpick_out, n * 4, hipMemcpyDeviceToHost));
   return rc;
 }
 

@@ -18,6 +18,45 @@
     if (e__ != hipSuccess) return fail(CSSM_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
   } while (0)
 
+
+// What one call borrows from the device -- memory, events, a stream: made through this owner, released when it goes out of scope,
+// on every path out of the function.  (The handles' long-lived buffers are not its business.)
+struct CssmTemps {
+  std::vector<void*> mem;
+  std::vector<hipEvent_t> events;
+  hipStream_t own_stream = nullptr;
+  CssmTemps() = default;
+  CssmTemps(const CssmTemps&) = delete;
+  CssmTemps& operator=(const CssmTemps&) = delete;
+  ~CssmTemps() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (void* p : mem) (void)hipFree(p);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
+  template <class T>
+  hipError_t alloc(T*& p, size_t bytes) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e == hipSuccess) { mem.push_back(q); p = static_cast<T*>(q); }
+    return e;
+  }
+  hipError_t event(hipEvent_t& ev) {
+    const hipError_t e = hipEventCreate(&ev);
+    if (e == hipSuccess) events.push_back(ev);
+    return e;
+  }
+  hipError_t stream(hipStream_t& st) {
+    const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) own_stream = st;
+    return e;
+  }
+};
+// a failed allocation through the owner `tmp`: CSSM_ENOMEM (every other HIP error: HIP_TRY)
+#define HIP_ALLOC(tmp, p, bytes)                                                                                   \
+  do {                                                                                                             \
+    if ((tmp).alloc(p, (bytes)) != hipSuccess) return fail(CSSM_ENOMEM, "hipMalloc(%zu) for " #p " (%s:%d)", (size_t)(bytes), __FILE__, __LINE__); \
+  } while (0)
+
 #define CSSM_NKERNELS CSSM_PROFILE_NKERNELS
 
 
@@ -221,5 +260,6 @@ void cssm_batch_fresh(cssm_pf* pf, double t0);   // host-side state of a freshly
 int cssm_batch_ok(const cssm_pf* pf);            // the batched launches serve this handle's configuration
 int cssm_check_device_err(cssm_pf* pf, const Scalars& h);
 int cssm_prop_items(int d);   // PropItems<D>
-double cssm_eta_of_mean(const cssm_pf* pf, const StepRec& rec, const double* mean);
-void cssm_peer_free(cssm_pf* pf);   // cssm_shard.hip: the peer-written exchange's windows, mappings and device table   // link(f(stateMean, t)), ParticleFilter.scala:420
+int cssm_use_device(int device);   // the device exists and is current, or the error
+double cssm_eta_of_mean(const HostModel& m, const double* fco, const double* mean);   // link(f(stateMean, t)), ParticleFilter.scala:420
+void cssm_peer_free(cssm_pf* pf);   // cssm_shard.hip: the peer-written exchange's windows, mappings and device table

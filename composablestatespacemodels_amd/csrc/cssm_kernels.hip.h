@@ -3,6 +3,9 @@
 // header is included by cssm_pf.hip and cssm_shard.hip.
 #pragma once
 
+#include <algorithm>
+#include <cmath>
+
 #include "cssm_device.hip.h"
 
 // ------------------------------------------------------------------------------------ init
@@ -334,6 +337,16 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_summary_fill(const double* __res
 
 // Radix select, most significant byte first, two targets (lower / upper order statistic) per row.
 struct SelState { unsigned long long prefix[2]; unsigned long long rank[2]; };
+// The two ranks of a row, 0-based in ascending order of a cloud of n: getCredibleInterval (model/ParticleFilter.scala:488-502) takes
+// (n - index - 1, index - 1) for a state row, getOrderStatistic (:455-460) takes (n - index, index) for eta and the observation, with
+// index = floor(interval n); clamped into the cloud.
+static inline void sel_ranks(SelState& s, uint64_t n, double interval, bool state_row) {
+  const long long idx = (long long)std::floor(interval * (double)n);
+  auto clamp = [&](long long r) { return (unsigned long long)std::min<long long>(std::max<long long>(r, 0), (long long)n - 1); };
+  s.prefix[0] = s.prefix[1] = 0;
+  s.rank[0] = clamp(state_row ? (long long)n - idx - 1 : (long long)n - idx);
+  s.rank[1] = clamp(state_row ? idx - 1 : idx);
+}
 
 static __global__ __launch_bounds__(CSSM_BLOCK) void k_sel_hist(const unsigned long long* __restrict__ keys, size_t kstride, uint64_t n,
                                                          const SelState* __restrict__ st, int shift, uint32_t* __restrict__ hist) {

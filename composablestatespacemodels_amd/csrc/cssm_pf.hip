@@ -164,6 +164,14 @@ static int alloc_handle(cssm_pf* pf) {
   return upload_init_params(pf);
 }
 
+int cssm_use_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range (%d devices)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  return CSSM_OK;
+}
+
 static int create_common(const cssm_model_desc* desc, uint64_t n_global, uint64_t first, uint64_t n_local,
                          uint64_t seed, int device, void* stream, bool sharded, cssm_pf** out) {
   if (!out) return fail(CSSM_EINVAL_ARG, "out is null");
@@ -171,16 +179,15 @@ static int create_common(const cssm_model_desc* desc, uint64_t n_global, uint64_
   if (n_global < 1 || n_global > 0xffff0000ull) return fail(CSSM_EINVAL_ARG, "n_particles must be in [1, 2^32 - 2^16]");
   if (n_local < 1 || first + n_local > n_global) return fail(CSSM_ESHARD, "shard [%llu, +%llu) outside [0, %llu)",
                                                               (unsigned long long)first, (unsigned long long)n_local, (unsigned long long)n_global);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range (%d devices)", device, ndev);
+  int rc = cssm_use_device(device);
+  if (rc) return rc;
   cssm_pf* pf = new cssm_pf();
   pf->device = device;
   pf->n_global = n_global; pf->first = first; pf->n = n_local; pf->seed = seed; pf->sharded = sharded;
   if (sharded || stream != nullptr) { pf->stream = (hipStream_t)stream; pf->own_stream = false; }
   pf->opt_fused = 1;   // two launches per observation at every size (measured with the slim single-GPU kernels: 18.7 vs 20.0 us at
                             // N = 100 000, 34.0 vs 35.4 at 2^20, 336 vs 356 at 2^24); an outlying observation is redone in place
-  int rc = cssm_build_model(pf, desc, false);
+  rc = cssm_build_model(pf, desc, false);
   if (rc == CSSM_OK) { pf->obs_has_scale = desc->leaves[0].has_scale; pf->obs_scale = desc->leaves[0].scale; }
   if (rc == CSSM_OK) rc = alloc_handle(pf);
   if (rc != CSSM_OK) { const std::string keep = cssm_last_error(); cssm_pf_destroy(pf); return fail(rc, "%s", keep.c_str()); }
@@ -973,10 +980,8 @@ __global__ void k_contract_normals(uint64_t seed, uint64_t first, uint32_t step,
 
 extern "C" int cssm_contract_eval(int device, int fn, const double* x, size_t n, double* out, size_t n_out) {
   if (!x || !out || n < 1) return fail(CSSM_EINVAL_ARG, "null argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range", device);
-  HIP_TRY(hipSetDevice(device));
+  int rc = cssm_use_device(device);
+  if (rc) return rc;
   size_t need = n, d = 0, np = 0;
   if (fn == CSSM_FN_SINCOS2PI || fn == CSSM_FN_FIX || fn == CSSM_FN_SINCOS_U24) need = 2 * n;
   else if (fn == CSSM_FN_PAIRED_NORMALS) {
@@ -987,27 +992,22 @@ extern "C" int cssm_contract_eval(int device, int fn, const double* x, size_t n,
     if (np < 1) return fail(CSSM_EINVAL_ARG, "out is too small");
   } else if ((fn < CSSM_FN_EXP || fn > CSSM_FN_FIX) && fn != CSSM_FN_SINCOS_U24 && fn != CSSM_FN_SQRT_RADIUS) return fail(CSSM_EINVAL_ARG, "unknown contract function %d", fn);
   if (n_out < need) return fail(CSSM_EINVAL_ARG, "out holds %zu doubles, %zu needed", n_out, need);
+  CssmTemps tmp;
   double *dx = nullptr, *dout = nullptr, *dtab = nullptr;
-  int rc = CSSM_OK;
-  if (hipMalloc(&dx, n * 8) != hipSuccess || hipMalloc(&dout, need * 8) != hipSuccess || hipMalloc(&dtab, sizeof(CSSM_TAB)) != hipSuccess)
-    rc = fail(CSSM_ENOMEM, "hipMalloc");
-  if (!rc && (hipMemcpy(dx, x, n * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dtab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice) != hipSuccess))
-    rc = fail(CSSM_EHIP, "upload");
-  if (!rc) {
-    if (fn == CSSM_FN_PAIRED_NORMALS) {
-      const uint64_t seed = (uint64_t)x[0], first = (uint64_t)x[1];
-      const uint32_t step = (uint32_t)x[2], tag = (uint32_t)x[3];
-      DISPATCH_D((int)d, k_contract_normals<D><<<dim3(grid_for(np, 256, 1024)), dim3(256)>>>(seed, first, step, tag, np, dout, dtab));
-    } else {
-      hipLaunchKernelGGL(k_contract_eval, dim3(grid_for(n, 256, 1024)), dim3(256), 0, 0, fn, dx, n, dout, dtab);
-    }
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = fail(CSSM_EHIP, "contract kernel");
+  HIP_ALLOC(tmp, dx, n * 8); HIP_ALLOC(tmp, dout, need * 8); HIP_ALLOC(tmp, dtab, sizeof(CSSM_TAB));
+  HIP_TRY(hipMemcpy(dx, x, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dtab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice));
+  if (fn == CSSM_FN_PAIRED_NORMALS) {
+    const uint64_t seed = (uint64_t)x[0], first = (uint64_t)x[1];
+    const uint32_t step = (uint32_t)x[2], tag = (uint32_t)x[3];
+    DISPATCH_D((int)d, k_contract_normals<D><<<dim3(grid_for(np, 256, 1024)), dim3(256)>>>(seed, first, step, tag, np, dout, dtab));
+  } else {
+    hipLaunchKernelGGL(k_contract_eval, dim3(grid_for(n, 256, 1024)), dim3(256), 0, 0, fn, dx, n, dout, dtab);
   }
-  if (!rc && hipMemcpy(out, dout, need * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(CSSM_EHIP, "download");
-  if (dx) (void)hipFree(dx);
-  if (dout) (void)hipFree(dout);
-  if (dtab) (void)hipFree(dtab);
-  return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, dout, need * 8, hipMemcpyDeviceToHost));
+  return CSSM_OK;
 }
 
 // ---- on-box streaming ceiling (bench.py: roofline.copy_ceiling) ---------------------------------------------------
@@ -1018,31 +1018,26 @@ __global__ __launch_bounds__(256) void k_diag_copy(const uint4* __restrict__ src
 }
 extern "C" int cssm_diag_copy_ceiling(int device, size_t bytes, int reps, double* gbps_out) {
   if (!gbps_out || bytes < (1u << 20) || reps < 1) return fail(CSSM_EINVAL_ARG, "bytes >= 1 MiB, reps >= 1 and an output pointer are required");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(CSSM_EINVAL_ARG, "device %d out of range", device);
-  HIP_TRY(hipSetDevice(device));
+  int rc = cssm_use_device(device);
+  if (rc) return rc;
   const size_t n16 = bytes / 16;
+  CssmTemps tmp;
   uint4 *a = nullptr, *b = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = CSSM_OK;
-  if (hipMalloc(&a, n16 * 16) != hipSuccess || hipMalloc(&b, n16 * 16) != hipSuccess) rc = fail(CSSM_ENOMEM, "hipMalloc of 2 x %zu bytes", n16 * 16);
-  if (!rc && (hipMemset(a, 1, n16 * 16) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = fail(CSSM_EHIP, "setup");
-  if (!rc) {
-    const int grid = 65536;      // many short blocks: measured best for a plain copy (tools/copy_bench.hip: 5.4 TB/s at 1 GiB, 4.7 with 4096 blocks)
-    hipLaunchKernelGGL(k_diag_copy, dim3(grid), dim3(256), 0, 0, a, b, n16);
-    (void)hipEventRecord(e0, 0);
-    for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_diag_copy, dim3(grid), dim3(256), 0, 0, (r & 1) ? b : a, (r & 1) ? a : b, n16);
-    (void)hipEventRecord(e1, 0);
-    float ms = 0.f;
-    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || hipGetLastError() != hipSuccess) rc = fail(CSSM_EHIP, "copy kernel");
-    else *gbps_out = 2.0 * (double)(n16 * 16) * reps / ((double)ms * 1e-3) / 1e9;
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (a) (void)hipFree(a);
-  if (b) (void)hipFree(b);
-  return rc;
+  HIP_ALLOC(tmp, a, n16 * 16); HIP_ALLOC(tmp, b, n16 * 16);
+  HIP_TRY(hipMemset(a, 1, n16 * 16));
+  HIP_TRY(tmp.event(e0)); HIP_TRY(tmp.event(e1));
+  const int grid = 65536;      // many short blocks: measured best for a plain copy (tools/copy_bench.hip: 5.4 TB/s at 1 GiB, 4.7 with 4096 blocks)
+  hipLaunchKernelGGL(k_diag_copy, dim3(grid), dim3(256), 0, 0, a, b, n16);
+  HIP_TRY(hipEventRecord(e0, 0));
+  for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_diag_copy, dim3(grid), dim3(256), 0, 0, (r & 1) ? b : a, (r & 1) ? a : b, n16);
+  HIP_TRY(hipEventRecord(e1, 0));
+  float ms = 0.f;
+  HIP_TRY(hipEventSynchronize(e1));
+  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+  HIP_TRY(hipGetLastError());
+  *gbps_out = 2.0 * (double)(n16 * 16) * reps / ((double)ms * 1e-3) / 1e9;
+  return CSSM_OK;
 }
 
 extern "C" int cssm_pf_last_loop_ms(cssm_pf* pf, float* ms_out) {
@@ -1187,14 +1182,14 @@ static double host_link(int obs_kind, double g) {
   }
 }
 
-double cssm_eta_of_mean(const cssm_pf* pf, const StepRec& rec, const double* mean) {
+double cssm_eta_of_mean(const HostModel& m, const double* fco, const double* mean) {
   double g = 0.0, acc = 0.0;
-  for (int k = 0; k < pf->d; ++k) {
-    const int fm = pf->mk.fmode(k);
-    if (fm == FM_START) acc = rec.fco[k] * mean[k]; else if (fm == FM_ADD) acc = acc + rec.fco[k] * mean[k];
-    if (pf->mk.leaf_end(k)) g = pf->mk.first_leaf(k) ? acc : g + acc;
+  for (int k = 0; k < m.d; ++k) {
+    const int fm = m.mk.fmode(k);
+    if (fm == FM_START) acc = fco[k] * mean[k]; else if (fm == FM_ADD) acc = acc + fco[k] * mean[k];
+    if (m.mk.leaf_end(k)) g = m.mk.first_leaf(k) ? acc : g + acc;
   }
-  return host_link(pf->obs_kind, g);
+  return host_link(m.obs_kind, g);
 }
 
 // Summary of the cloud { src[:, idx[i]] : i < n } at time `time` (idx == nullptr: identity); see cssm_pf_summary.
@@ -1209,24 +1204,15 @@ static int summary_impl(cssm_pf* pf, const double* src, size_t src_stride, const
   std::vector<SelState> hst(rows);
   std::vector<double> hout(3 * rows);
   StepRec hrec;
-  int rc = CSSM_OK;
-  // ranks, 0-based in ascending order: getCredibleInterval (:488-502) uses (N - index - 1, index - 1) with
-  // index = floor(interval * N); getOrderStatistic (:455-460) uses (N - index, index) -- both reproduced
-  const long long idxr = (long long)std::floor(interval * (double)n);
-  auto clampr = [&](long long r) { return (unsigned long long)std::min<long long>(std::max<long long>(r, 0), (long long)n - 1); };
-  for (int k = 0; k < rows; ++k) {
-    hst[k].prefix[0] = hst[k].prefix[1] = 0;
-    hst[k].rank[0] = clampr(k < d ? (long long)n - idxr - 1 : (long long)n - idxr);
-    hst[k].rank[1] = clampr(k < d ? idxr - 1 : idxr);
-  }
+  CssmTemps tmp;   // (after the host buffers: released, and the device idle, before they go)
+  for (int k = 0; k < rows; ++k) sel_ranks(hst[k], n, interval, k < d);
   cssm_build_rec(pf, time, time, 0.0, 0, pf->step, &hrec);   // F(t) of the requested time for f(x, t)
-#define SM_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(CSSM_EHIP, "%s: %s", #expr, hipGetErrorString(e__)); goto done; } } while (0)
-  SM_TRY(hipMalloc(&keys, (size_t)rows * n * 8)); SM_TRY(hipMalloc(&partial, (size_t)nblocks * d * 8));
-  SM_TRY(hipMalloc(&st, rows * sizeof(SelState))); SM_TRY(hipMalloc(&hist, (size_t)rows * 512 * 4)); SM_TRY(hipMalloc(&out, 3 * rows * 8));
-  SM_TRY(hipMalloc(&drec, sizeof(StepRec)));
-  SM_TRY(hipMemcpyAsync(st, hst.data(), rows * sizeof(SelState), hipMemcpyHostToDevice, pf->stream));
-  SM_TRY(hipMemcpyAsync(drec, &hrec, sizeof hrec, hipMemcpyHostToDevice, pf->stream));
-  SM_TRY(hipMemsetAsync(hist, 0, (size_t)rows * 512 * 4, pf->stream));
+  HIP_ALLOC(tmp, keys, (size_t)rows * n * 8); HIP_ALLOC(tmp, partial, (size_t)nblocks * d * 8);
+  HIP_ALLOC(tmp, st, rows * sizeof(SelState)); HIP_ALLOC(tmp, hist, (size_t)rows * 512 * 4); HIP_ALLOC(tmp, out, 3 * rows * 8);
+  HIP_ALLOC(tmp, drec, sizeof(StepRec));
+  HIP_TRY(hipMemcpyAsync(st, hst.data(), rows * sizeof(SelState), hipMemcpyHostToDevice, pf->stream));
+  HIP_TRY(hipMemcpyAsync(drec, &hrec, sizeof hrec, hipMemcpyHostToDevice, pf->stream));
+  HIP_TRY(hipMemsetAsync(hist, 0, (size_t)rows * 512 * 4, pf->stream));
   {
     DISPATCH_D(d, k_summary_fill<D><<<dim3(nblocks), dim3(CSSM_BLOCK), 0, pf->stream>>>(
                       src, src_stride, idx, idx ? src2 : nullptr, src2_stride, n_split, n, drec, pf->mk, keys, (size_t)n, partial));
@@ -1236,9 +1222,9 @@ static int summary_impl(cssm_pf* pf, const double* src, size_t src_stride, const
     }
     hipLaunchKernelGGL(k_summary_finish, dim3(1), dim3(64), 0, pf->stream, st, partial, nblocks, d, n, out);
   }
-  SM_TRY(hipGetLastError());
-  SM_TRY(hipMemcpyAsync(hout.data(), out, 3 * rows * 8, hipMemcpyDeviceToHost, pf->stream));
-  SM_TRY(hipStreamSynchronize(pf->stream));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(hout.data(), out, 3 * rows * 8, hipMemcpyDeviceToHost, pf->stream));
+  HIP_TRY(hipStreamSynchronize(pf->stream));
   for (int k = 0; k < d; ++k) {
     if (state_mean) state_mean[k] = hout[k];
     if (state_lower) state_lower[k] = hout[rows + k];
@@ -1246,11 +1232,8 @@ static int summary_impl(cssm_pf* pf, const double* src, size_t src_stride, const
   }
   if (eta_lower) *eta_lower = hout[rows + d];
   if (eta_upper) *eta_upper = hout[2 * rows + d];
-  if (eta_of_mean) *eta_of_mean = cssm_eta_of_mean(pf, hrec, hout.data());   // meanEta = link(f(stateMean, t)), :420
-done:
-#undef SM_TRY
-  { void* ptrs[] = {keys, partial, st, hist, out, drec}; for (void* q : ptrs) if (q) (void)hipFree(q); }
-  return rc;
+  if (eta_of_mean) *eta_of_mean = cssm_eta_of_mean(*pf, hrec.fco, hout.data());   // meanEta = link(f(stateMean, t)), :420
+  return CSSM_OK;
 }
 
 extern "C" int cssm_pf_summary(cssm_pf* pf, double interval, double* state_mean, double* state_lower, double* state_upper,
@@ -1370,27 +1353,25 @@ extern "C" int cssm_resample(int kind, const double* w, size_t n, double u, uint
   if (kind < CSSM_RESAMPLE_SYSTEMATIC || kind > CSSM_RESAMPLE_MULTINOMIAL) return fail(CSSM_EINVAL_ARG, "unknown resampler %d", kind);
   if (kind != CSSM_RESAMPLE_SYSTEMATIC) u = 0.0;
   if (!(u >= 0.0 && u < 1.0)) return fail(CSSM_EINVAL_ARG, "u must be in [0, 1)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  HIP_TRY(hipSetDevice(device));
+  int rc = cssm_use_device(device);
+  if (rc) return rc;
   const uint32_t ntiles = (uint32_t)((n + CSSM_TILE - 1) / CSSM_TILE);
   const uint32_t sup = (ntiles + 1023u) / 1024u, nunits = (ntiles + sup - 1) / sup;
   const size_t stride = (size_t)ntiles * CSSM_TILE;
   double* d_w = nullptr; uint32_t *d_end = nullptr, *d_anc = nullptr; cssm_u128 *tS = nullptr, *tS2 = nullptr, *tP = nullptr;
   Scalars* sc = nullptr; StepRec* d_rec = nullptr; double* d_tab = nullptr; double* d_cum = nullptr;
   hipStream_t st = nullptr;
-  int rc = CSSM_OK;
   StepRec hrec; memset(&hrec, 0, sizeof hrec); hrec.u = u; hrec.step = step;
   Scalars hs;
   std::vector<double> wscaled;
-#define RS_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(CSSM_EHIP, "%s: %s", #expr, hipGetErrorString(e__)); goto done; } } while (0)
-  RS_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  RS_TRY(hipMalloc(&d_w, stride * 8)); RS_TRY(hipMalloc(&d_end, stride * 4)); RS_TRY(hipMalloc(&d_anc, stride * 4));
-  RS_TRY(hipMalloc(&tS, ntiles * sizeof(cssm_u128))); RS_TRY(hipMalloc(&tS2, ntiles * sizeof(cssm_u128))); RS_TRY(hipMalloc(&tP, ntiles * sizeof(cssm_u128)));
-  RS_TRY(hipMalloc(&sc, sizeof(Scalars))); RS_TRY(hipMalloc(&d_rec, sizeof(StepRec))); RS_TRY(hipMalloc(&d_tab, sizeof(CSSM_TAB)));
-  if (kind == CSSM_RESAMPLE_MULTINOMIAL) RS_TRY(hipMalloc(&d_cum, stride * 8));
-  RS_TRY(hipMemcpyAsync(d_tab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+  CssmTemps tmp;
+  HIP_TRY(tmp.stream(st));
+  HIP_ALLOC(tmp, d_w, stride * 8); HIP_ALLOC(tmp, d_end, stride * 4); HIP_ALLOC(tmp, d_anc, stride * 4);
+  HIP_ALLOC(tmp, tS, ntiles * sizeof(cssm_u128)); HIP_ALLOC(tmp, tS2, ntiles * sizeof(cssm_u128)); HIP_ALLOC(tmp, tP, ntiles * sizeof(cssm_u128));
+  HIP_ALLOC(tmp, sc, sizeof(Scalars)); HIP_ALLOC(tmp, d_rec, sizeof(StepRec)); HIP_ALLOC(tmp, d_tab, sizeof(CSSM_TAB));
+  if (kind == CSSM_RESAMPLE_MULTINOMIAL) HIP_ALLOC(tmp, d_cum, stride * 8);
+  HIP_TRY(hipMemcpyAsync(d_tab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
   {
     // Weights of ANY scale: the reference normalises w / sum(w) (Resampling.scala:21-24) and its own property is stated over every
     // non-empty vector in [0, 1] (SamplingTest.scala:12-22), but the contract's sums live on a 2^-96 grid -- a vector whose largest
@@ -1406,8 +1387,8 @@ extern "C" int cssm_resample(int kind, const double* w, size_t n, double u, uint
       w = wscaled.data();
     }
   }
-  RS_TRY(hipMemcpyAsync(d_w, w, n * 8, hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemcpyAsync(d_rec, &hrec, sizeof hrec, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_w, w, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_rec, &hrec, sizeof hrec, hipMemcpyHostToDevice, st));
   {
     const int tgrid = (int)nunits;
     hipLaunchKernelGGL(k_tile_sums, dim3(tgrid), dim3(CSSM_BLOCK), 0, st, d_w, (uint64_t)n, sc, tS, tS2, ntiles, sup, nunits, 1, -1, (const double*)nullptr, d_tab,
@@ -1427,17 +1408,12 @@ extern "C" int cssm_resample(int kind, const double* w, size_t n, double u, uint
     if (kind == CSSM_RESAMPLE_MULTINOMIAL)
       hipLaunchKernelGGL(k_multinomial, dim3(grid_for(n, 256, kGridCap)), dim3(256), 0, st, d_cum, (uint64_t)n, seed, step, d_anc);
   }
-  RS_TRY(hipGetLastError());
-  RS_TRY(hipMemcpyAsync(CSSM_SC_TAIL_ARGS(&hs, sc), hipMemcpyDeviceToHost, st));
-  RS_TRY(hipMemcpyAsync(anc, d_anc, n * 4, hipMemcpyDeviceToHost, st));
-  RS_TRY(hipStreamSynchronize(st));
-  if (hs.S_tot.lo == 0 && hs.S_tot.hi == 0) rc = fail(CSSM_ENONFINITE, "all weights are zero (the reference divides by a zero total)");
-done:
-#undef RS_TRY
-  void* ptrs[] = {d_w, d_end, d_anc, tS, tS2, tP, sc, d_rec, d_tab, d_cum};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(CSSM_SC_TAIL_ARGS(&hs, sc), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(anc, d_anc, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (hs.S_tot.lo == 0 && hs.S_tot.hi == 0) return fail(CSSM_ENONFINITE, "all weights are zero (the reference divides by a zero total)");
+  return CSSM_OK;
 }
 
 #ifdef CSSM_OFF_STAMPS

@@ -95,9 +95,8 @@ static __global__ void k_residual_draws(const double* __restrict__ cum, uint64_t
 extern "C" int cssm_resample_residual(const double* w, size_t n, uint64_t seed, uint32_t step, uint32_t* anc, int device) {
   if (!w || !anc) return fail(CSSM_EINVAL_ARG, "null argument");
   if (n < 1 || n >= 0xffffffffull) return fail(CSSM_EINVAL_ARG, "n out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(CSSM_EHIP, "no HIP device available (this library has no CPU path)");
-  HIP_TRY(hipSetDevice(device));
+  const int rc_dev = cssm_use_device(device);
+  if (rc_dev) return rc_dev;
   const uint32_t ntiles = (uint32_t)((n + CSSM_TILE - 1) / CSSM_TILE);
   const uint32_t sup = (ntiles + 1023u) / 1024u, nunits = (ntiles + sup - 1) / sup;
   const size_t stride = (size_t)ntiles * CSSM_TILE;
@@ -105,20 +104,19 @@ extern "C" int cssm_resample_residual(const double* w, size_t n, uint64_t seed, 
   double *d_w = nullptr, *d_r = nullptr, *d_cum = nullptr, *d_tab = nullptr; uint32_t *d_k = nullptr, *d_bk = nullptr, *d_anc = nullptr, *d_end = nullptr;
   cssm_u128 *tS = nullptr, *tS2 = nullptr, *tP = nullptr; Scalars* sc = nullptr; StepRec* d_rec = nullptr; unsigned long long* d_total = nullptr;
   hipStream_t st = nullptr;
-  int rc = CSSM_OK;
   StepRec hrec; memset(&hrec, 0, sizeof hrec); hrec.step = step;
   Scalars hs;
   unsigned long long K = 0;
   std::vector<double> wscaled;
-#define RS_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(CSSM_EHIP, "%s: %s", #expr, hipGetErrorString(e__)); goto done; } } while (0)
-  RS_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  RS_TRY(hipMalloc(&d_w, stride * 8)); RS_TRY(hipMalloc(&d_r, stride * 8)); RS_TRY(hipMalloc(&d_cum, stride * 8));
-  RS_TRY(hipMalloc(&d_k, stride * 4)); RS_TRY(hipMalloc(&d_bk, (size_t)nblocks * 4)); RS_TRY(hipMalloc(&d_anc, stride * 4)); RS_TRY(hipMalloc(&d_end, stride * 4));
-  RS_TRY(hipMalloc(&tS, ntiles * sizeof(cssm_u128))); RS_TRY(hipMalloc(&tS2, ntiles * sizeof(cssm_u128))); RS_TRY(hipMalloc(&tP, ntiles * sizeof(cssm_u128)));
-  RS_TRY(hipMalloc(&sc, sizeof(Scalars))); RS_TRY(hipMalloc(&d_rec, sizeof(StepRec))); RS_TRY(hipMalloc(&d_tab, sizeof(CSSM_TAB))); RS_TRY(hipMalloc(&d_total, 8));
-  RS_TRY(hipMemcpyAsync(d_tab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
-  RS_TRY(hipMemsetAsync(d_r, 0, stride * 8, st));
+  CssmTemps tmp;
+  HIP_TRY(tmp.stream(st));
+  HIP_ALLOC(tmp, d_w, stride * 8); HIP_ALLOC(tmp, d_r, stride * 8); HIP_ALLOC(tmp, d_cum, stride * 8);
+  HIP_ALLOC(tmp, d_k, stride * 4); HIP_ALLOC(tmp, d_bk, (size_t)nblocks * 4); HIP_ALLOC(tmp, d_anc, stride * 4); HIP_ALLOC(tmp, d_end, stride * 4);
+  HIP_ALLOC(tmp, tS, ntiles * sizeof(cssm_u128)); HIP_ALLOC(tmp, tS2, ntiles * sizeof(cssm_u128)); HIP_ALLOC(tmp, tP, ntiles * sizeof(cssm_u128));
+  HIP_ALLOC(tmp, sc, sizeof(Scalars)); HIP_ALLOC(tmp, d_rec, sizeof(StepRec)); HIP_ALLOC(tmp, d_tab, sizeof(CSSM_TAB)); HIP_ALLOC(tmp, d_total, 8);
+  HIP_TRY(hipMemcpyAsync(d_tab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+  HIP_TRY(hipMemsetAsync(d_r, 0, stride * 8, st));
   {   // (weights of any scale: brought up by an exact power of two as cssm_resample does -- the sums live on a 2^-96 grid)
     double wmax = 0.0;
     for (size_t i = 0; i < n; ++i) if (w[i] > wmax) wmax = w[i];
@@ -130,8 +128,8 @@ extern "C" int cssm_resample_residual(const double* w, size_t n, uint64_t seed, 
       w = wscaled.data();
     }
   }
-  RS_TRY(hipMemcpyAsync(d_w, w, n * 8, hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemcpyAsync(d_rec, &hrec, sizeof hrec, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_w, w, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_rec, &hrec, sizeof hrec, hipMemcpyHostToDevice, st));
   // S = sum F_i
   hipLaunchKernelGGL(k_tile_sums, dim3((int)nunits), dim3(CSSM_BLOCK), 0, st, d_w, (uint64_t)n, sc, tS, tS2, ntiles, sup, nunits, 1, -1, (const double*)nullptr, d_tab,
                      (const StepRec*)d_rec, 0u);
@@ -141,17 +139,17 @@ extern "C" int cssm_resample_residual(const double* w, size_t n, uint64_t seed, 
   hipLaunchKernelGGL(k_residual_split, dim3(nblocks), dim3(CSSM_BLOCK), 0, st, (const double*)d_w, (uint64_t)n, (const Scalars*)sc, d_k, d_r, d_bk);
   hipLaunchKernelGGL(k_residual_scan_blocks, dim3(1), dim3(1024), 0, st, d_bk, nblocks, d_total);
   hipLaunchKernelGGL(k_residual_prefix, dim3(nblocks), dim3(CSSM_BLOCK), 0, st, d_k, (uint64_t)n, (const uint32_t*)d_bk);
-  RS_TRY(hipGetLastError());
-  RS_TRY(hipMemcpyAsync(CSSM_SC_TAIL_ARGS(&hs, sc), hipMemcpyDeviceToHost, st));
-  RS_TRY(hipMemcpyAsync(&K, d_total, 8, hipMemcpyDeviceToHost, st));
-  RS_TRY(hipStreamSynchronize(st));
-  if (hs.S_tot.lo == 0 && hs.S_tot.hi == 0) { rc = fail(CSSM_ENONFINITE, "all weights are zero (the reference divides by a zero total)"); goto done; }
-  if (K > (unsigned long long)n) { rc = fail(CSSM_ESTATE, "residual resampling: %llu deterministic copies for %zu slots", K, n); goto done; }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(CSSM_SC_TAIL_ARGS(&hs, sc), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&K, d_total, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (hs.S_tot.lo == 0 && hs.S_tot.hi == 0) return fail(CSSM_ENONFINITE, "all weights are zero (the reference divides by a zero total)");
+  if (K > (unsigned long long)n) return fail(CSSM_ESTATE, "residual resampling: %llu deterministic copies for %zu slots", K, n);
   if (K > 0) hipLaunchKernelGGL(k_residual_fill, dim3(grid_for(K, 256, kGridCap)), dim3(256), 0, st, (const uint32_t*)d_k, (uint64_t)n, (uint64_t)K, d_anc);
   if (K < (unsigned long long)n) {
     // the residual weights' cumulative distribution (the multinomial resampler's: contract sums of r), then m draws
     const uint64_t m = (uint64_t)n - K;
-    RS_TRY(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+    HIP_TRY(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
     hipLaunchKernelGGL(k_tile_sums, dim3((int)nunits), dim3(CSSM_BLOCK), 0, st, d_r, (uint64_t)n, sc, tS, tS2, ntiles, sup, nunits, 1, -1, (const double*)nullptr, d_tab,
                        (const StepRec*)d_rec, 0u);
     hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, st, tS, tS2, tP, nunits, sc, (uint64_t)n, 1, (double*)nullptr, (int32_t*)nullptr, 0u,
@@ -160,19 +158,14 @@ extern "C" int cssm_resample_residual(const double* w, size_t n, uint64_t seed, 
                        d_r, (uint64_t)n, sc, (const cssm_u128*)tP, (const cssm_u128*)tS2, d_rec, (uint64_t)n, d_end, d_end /* (unused: no runs are written) */, ntiles, sup, nunits, 1, 0,
                        (double*)nullptr, (int32_t*)nullptr, 0u, 0, (const unsigned long long*)nullptr, 0, 1, 1, seed, d_cum, d_tab, 0,
                        (unsigned long long*)nullptr, 0u, (uint32_t)n, 5u);
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipMemcpyAsync(CSSM_SC_TAIL_ARGS(&hs, sc), hipMemcpyDeviceToHost, st));
-    RS_TRY(hipStreamSynchronize(st));
-    if (hs.S_tot.lo == 0 && hs.S_tot.hi == 0) { rc = fail(CSSM_ENONFINITE, "residual resampling: %llu slots are left and every residual weight is zero", (unsigned long long)m); goto done; }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(CSSM_SC_TAIL_ARGS(&hs, sc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hs.S_tot.lo == 0 && hs.S_tot.hi == 0) return fail(CSSM_ENONFINITE, "residual resampling: %llu slots are left and every residual weight is zero", (unsigned long long)m);
     hipLaunchKernelGGL(k_residual_draws, dim3(grid_for(m, 256, kGridCap)), dim3(256), 0, st, (const double*)d_cum, (uint64_t)n, seed, step, (uint64_t)K, m, d_anc);
   }
-  RS_TRY(hipGetLastError());
-  RS_TRY(hipMemcpyAsync(anc, d_anc, n * 4, hipMemcpyDeviceToHost, st));
-  RS_TRY(hipStreamSynchronize(st));
-done:
-#undef RS_TRY
-  void* ptrs[] = {d_w, d_r, d_cum, d_tab, d_k, d_bk, d_anc, d_end, tS, tS2, tP, sc, d_rec, d_total};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(anc, d_anc, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CSSM_OK;
 }

@@ -1188,16 +1188,8 @@ extern "C" int cssm_pf_shard_summary_begin(cssm_pf* pf, double interval, double*
     pf->sm_cap = (size_t)n;
   }
   pf->sm_blocks = nblocks; pf->sm_time = pf->t;
-  // ranks, 0-based in ascending order, of the GLOBAL cloud: getCredibleInterval (:488-502) uses (N - index - 1, index - 1) with
-  // index = floor(interval * N); getOrderStatistic (:455-460) uses (N - index, index)
-  std::vector<SelState> hst(rows);
-  const long long idxr = (long long)std::floor(interval * (double)ng);
-  auto clampr = [&](long long r) { return (unsigned long long)std::min<long long>(std::max<long long>(r, 0), (long long)ng - 1); };
-  for (int k = 0; k < rows; ++k) {
-    hst[k].prefix[0] = hst[k].prefix[1] = 0;
-    hst[k].rank[0] = clampr(k < d ? (long long)ng - idxr - 1 : (long long)ng - idxr);
-    hst[k].rank[1] = clampr(k < d ? idxr - 1 : idxr);
-  }
+  std::vector<SelState> hst(rows);   // (ranks of the GLOBAL cloud)
+  for (int k = 0; k < rows; ++k) sel_ranks(hst[k], ng, interval, k < d);
   StepRec hrec;
   cssm_build_rec(pf, pf->t, pf->t, 0.0, 0, pf->step, &hrec);   // F(t) of the cloud's time for f(x, t)
   HIP_TRY(hipMemcpyAsync(pf->sm_st, hst.data(), rows * sizeof(SelState), hipMemcpyHostToDevice, pf->stream));
@@ -1252,7 +1244,7 @@ extern "C" int cssm_pf_shard_summary_finish(cssm_pf* pf, const double* sums_glob
   if (eta_of_mean) {
     StepRec hrec;
     cssm_build_rec(pf, pf->sm_time, pf->sm_time, 0.0, 0, pf->step, &hrec);
-    *eta_of_mean = cssm_eta_of_mean(pf, hrec, mean.data());
+    *eta_of_mean = cssm_eta_of_mean(*pf, hrec.fco, mean.data());
   }
   return CSSM_OK;
 }
