@@ -18,13 +18,14 @@
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
 #include "cssm_fleet.hip.h"
+#include "cssm_fleet_forecast.hip.h"
 
 static_assert(CSSM_FLEET_MAX_N <= 4096, "k_fleet_summary sorts at most 4096 keys in LDS; k_fleet_series holds 12 bytes per particle there");
 
 struct cssm_fleet {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // filter / step call, summary
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // filter / step call, summary, forecast
   uint32_t n = 0, S = 0;
   int d = 0, threads = 64;
   size_t lds = 0;
@@ -33,6 +34,8 @@ struct cssm_fleet {
   std::vector<double> t;                // per series: its clock
   std::vector<uint32_t> step;           // ... its observation index (Philox counter word; parity = the buffer that holds its cloud)
   std::vector<uint8_t> live;            // ... a cloud exists (initialised and not failed since)
+  std::vector<int> obs_has_scale;       // ... the leftmost leaf's scale as stored (forecasts: cssm_obs_params_make)
+  std::vector<double> obs_scale;
   bool par_dirty = true;
   // device
   double* state = nullptr; uint32_t* anc = nullptr; FleetSeries* ser = nullptr; FleetPar* par = nullptr; double* logtab = nullptr;
@@ -43,7 +46,15 @@ struct cssm_fleet {
   // host staging (pinned)
   unsigned char* h_stage = nullptr; size_t h_stage_cap = 0;
   std::vector<FleetSeries> h_ser;
-  float ms_call = -1.f, ms_summary = -1.f;
+  float ms_call = -1.f, ms_summary = -1.f, ms_forecast = -1.f;
+  // forecasts (cssm_fleet_forecast), grow-only: [off | keys | obs params | buffer numbers | records | results] and its pinned mirror,
+  // eta / obs staging of every series, the samples of one chunk of series (at most fc_samp_max bytes: CSSM_OPT_FORECAST_CAP)
+  unsigned char* d_fc = nullptr; size_t fc_cap = 0;
+  unsigned char* h_fc = nullptr; size_t h_fc_cap = 0;
+  double* d_fc_stage = nullptr;
+  double* d_fc_samp = nullptr; size_t fc_samp_cap = 0;
+  size_t fc_samp_max = (size_t)1 << 30;
+  int fc_select = 0;                    // CSSM_OPT_FLEET_SELECT: 0 = by N (CSSM_FLEET_SELECT_MIN_N), 1 = bitonic sort, 2 = radix select
 };
 
 #define FLEET_SERVED "cssm_pf_* (one handle per series) and cssm_pfb_* (batch of chains) serve it"
@@ -142,9 +153,10 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_sm};
+  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
+  if (f->h_fc) (void)hipHostFree(f->h_fc);
   for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;
@@ -171,6 +183,7 @@ extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particl
   const uint32_t S = n_series, n = f->n;
   f->models.assign(S, base);
   f->t.assign(S, 0.0); f->step.assign(S, 0u); f->live.assign(S, 0); f->h_ser.resize(S);
+  f->obs_has_scale.assign(S, desc->leaves[0].has_scale); f->obs_scale.assign(S, desc->leaves[0].scale);
   // block size: about four particles per thread, whole waves, at most CSSM_FLEET_MAX_THREADS (results do not depend on it)
   f->threads = (int)std::min<uint32_t>(CSSM_FLEET_MAX_THREADS, std::max<uint32_t>(64u, ((n + 3u) / 4u + 63u) & ~63u));
   f->lds = (size_t)((n + 1u) & ~1u) * 8u + (size_t)n * 4u;
@@ -195,6 +208,16 @@ extern "C" uint64_t cssm_fleet_num_particles(const cssm_fleet* f) { return f ? f
 
 extern "C" int cssm_fleet_set_option(cssm_fleet* f, int option, int value) {
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  if (option == CSSM_OPT_FORECAST_CAP) {   // KiB of samples one chunk of series holds on the device; 0 = 1 GiB
+    if (value < 0) return fail(CSSM_EINVAL_ARG, "CSSM_OPT_FORECAST_CAP must not be negative (got %d)", value);
+    f->fc_samp_max = value ? (size_t)value << 10 : (size_t)1 << 30;
+    return CSSM_OK;
+  }
+  if (option == CSSM_OPT_FLEET_SELECT) {
+    if (value < 0 || value > 2) return fail(CSSM_EINVAL_ARG, "CSSM_OPT_FLEET_SELECT is 0 (by N), 1 (sort) or 2 (radix select), not %d", value);
+    f->fc_select = value;
+    return CSSM_OK;
+  }
   if (option != CSSM_OPT_RESAMPLER) return fail(CSSM_EINVAL_ARG, "a fleet has no option %d", option);
   if (value != CSSM_RESAMPLE_SYSTEMATIC)
     return fail(CSSM_EINVAL_ARG, "the fleet filter resamples systematically only (resampler %d asked for); " FLEET_SERVED, value);
@@ -213,7 +236,10 @@ extern "C" int cssm_fleet_set_params(cssm_fleet* f, const cssm_model_desc* const
     if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "series %u: %s", k, keep.c_str()); }
     last = descs[k];
   }
-  for (uint32_t k = 0; k < f->S; ++k) { next[k].seed = f->models[k].seed; next[k].n_global = f->n; }
+  for (uint32_t k = 0; k < f->S; ++k) {
+    next[k].seed = f->models[k].seed; next[k].n_global = f->n;
+    f->obs_has_scale[k] = descs[k]->leaves[0].has_scale; f->obs_scale[k] = descs[k]->leaves[0].scale;
+  }
   f->models.swap(next);
   f->par_dirty = true;
   return CSSM_OK;
@@ -469,6 +495,171 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
   return CSSM_OK;
 }
 
+// SimulateData.forecast + summariseForecast (model/Data.scala:196-231) of every series from its current cloud: one upload (offsets,
+// keys, observation parameters, buffer numbers, records), one launch whose blocks are the series (k_fleet_forecast), one read-back.
+// A call that returns samples runs the fleet in chunks of series whose samples fit fc_samp_max -- never chunks of horizons: a series
+// is one block's work.  What a series' own arguments spoil is the series' own: its status, NaN in its outputs, no block for it.
+static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
+extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const double* t, const uint64_t* keys, double interval,
+                                   double* state_mean, double* state_lower, double* state_upper, double* eta_mean, double* eta_lower,
+                                   double* eta_upper, double* obs_mean, double* obs_lower, double* obs_upper, double* samples, int* rc_out) {
+  if (!f || !off || !t || !keys || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  const uint32_t S = f->S, n = f->n;
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  for (uint32_t k = 0; k < S; ++k)
+    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
+                                         k + 1, (unsigned long long)off[k + 1]);
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  const size_t R = (size_t)off[S];
+  for (uint32_t k = 0; k < S; ++k)
+    if (off[k + 1] - off[k] > 0xffffffffull) return fail(CSSM_EINVAL_ARG, "series %u: too many horizons", k);
+  if (R == 0) { for (uint32_t k = 0; k < S; ++k) rc_out[k] = CSSM_OK; return CSSM_OK; }
+  bool any_live = false;
+  for (uint32_t k = 0; k < S; ++k) any_live = any_live || f->live[k];
+  if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
+  HIP_TRY(hipSetDevice(f->device));
+  const int d = f->d, rows = d + 2;
+  const size_t RB = CSSM_FLEET_REC_BYTES(d);
+  const size_t o_keys = ((size_t)S + 1u) * 8u, o_op = o_keys + (size_t)S * 8u, o_cur = o_op + (size_t)S * sizeof(cssm_obs_params);
+  const size_t o_rec = o_cur + (((size_t)S * 4u + 7u) & ~(size_t)7u), o_out = o_rec + R * RB, n_out = R * (size_t)rows * 3u;
+  const size_t need = o_out + n_out * 8u;
+  if (need > f->h_fc_cap) {
+    if (f->h_fc) (void)hipHostFree(f->h_fc);
+    f->h_fc = nullptr; f->h_fc_cap = 0;
+    if (hipHostMalloc((void**)&f->h_fc, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of pinned staging", need);
+    f->h_fc_cap = need + need / 4;
+  }
+  if (need > f->fc_cap) {
+    if (f->d_fc) (void)hipFree(f->d_fc);
+    f->d_fc = nullptr; f->fc_cap = 0;
+    if (hipMalloc(&f->d_fc, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of records and results", need);
+    f->fc_cap = need + need / 4;
+  }
+  if (!f->d_fc_stage && hipMalloc(&f->d_fc_stage, (size_t)S * 2u * n * 8u) != hipSuccess) {
+    f->d_fc_stage = nullptr;
+    return fail(CSSM_ENOMEM, "fleet forecast: 16 N bytes of staging per series");
+  }
+  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_fc);
+  unsigned long long* h_keys = reinterpret_cast<unsigned long long*>(f->h_fc + o_keys);
+  cssm_obs_params* h_op = reinterpret_cast<cssm_obs_params*>(f->h_fc + o_op);
+  uint32_t* h_cur = reinterpret_cast<uint32_t*>(f->h_fc + o_cur);
+  unsigned char* h_recs = f->h_fc + o_rec;
+  const double* h_out = reinterpret_cast<const double*>(f->h_fc + o_out);
+  // the series' own statuses: no cloud, a model without the scale its observation needs, times that are not a forecast's
+  std::string scale_msg;
+  size_t n_run = 0;
+  for (uint32_t k = 0; k <= S; ++k) h_off[k] = off[k];
+  for (uint32_t k = 0; k < S; ++k) {
+    const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+    h_keys[k] = keys[k]; h_cur[k] = 0xffffffffu; rc_out[k] = CSSM_OK;
+    memset(&h_op[k], 0, sizeof(cssm_obs_params));
+    if (b == a) continue;
+    if (!f->live[k]) { rc_out[k] = CSSM_ESTATE; continue; }
+    if (cssm_obs_params_or_fail(f->base.obs_kind, f->obs_has_scale[k], f->obs_scale[k], f->base.obs_df, &h_op[k])) {
+      if (scale_msg.empty()) scale_msg = "series " + std::to_string(k) + ": " + cssm_last_error();
+      rc_out[k] = CSSM_EINVAL_ARG;
+      continue;
+    }
+    double prev = f->t[k];
+    for (size_t s = a; s < b; ++s) {
+      if (!std::isfinite(t[s]) || !(t[s] >= prev)) { rc_out[k] = CSSM_EINVAL_ARG; break; }
+      prev = t[s];
+    }
+    if (rc_out[k]) continue;
+    h_cur[k] = f->step[k] & 1u;
+    n_run += b - a;
+  }
+  fleet_parallel(S, n_run, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      if (h_cur[k] > 1u) continue;
+      double tp = f->t[k];
+      for (size_t s = (size_t)off[k]; s < (size_t)off[k + 1]; ++s) {
+        fleet_pack_rec(f->models[k], tp, t[s], 0.0, 0, (uint32_t)(s - (size_t)off[k]), h_recs + s * RB);
+        tp = t[s];
+      }
+    }
+  });
+  if (n_run) {
+    // chunks of series: all of them, or (samples) as many as fit the cap -- one series at least
+    const size_t samp_row = (size_t)(d + 3) * n * 8u;
+    std::vector<uint32_t> cut{0u};
+    if (samples) {
+      const size_t cap_rows = std::max<size_t>(1, f->fc_samp_max / samp_row);
+      size_t most = 0;
+      for (uint32_t k = 0; k < S; ++k)
+        if ((size_t)(off[k + 1] - off[cut.back()]) > cap_rows && k > cut.back()) cut.push_back(k);
+      cut.push_back(S);
+      for (size_t c = 0; c + 1 < cut.size(); ++c) most = std::max<size_t>(most, (size_t)(off[cut[c + 1]] - off[cut[c]]));
+      if (most * samp_row > f->fc_samp_cap) {
+        if (f->d_fc_samp) (void)hipFree(f->d_fc_samp);
+        f->d_fc_samp = nullptr; f->fc_samp_cap = 0;
+        if (hipMalloc(&f->d_fc_samp, most * samp_row) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of samples", most * samp_row);
+        f->fc_samp_cap = most * samp_row;
+      }
+    } else {
+      cut.push_back(S);
+    }
+    SelState rs, re;
+    sel_ranks(rs, n, interval, true);
+    sel_ranks(re, n, interval, false);
+    FleetFcLaunch l;
+    l.args.n = n; l.args.np2 = 2u;
+    while (l.args.np2 < n) l.args.np2 <<= 1;
+    l.args.select = f->fc_select ? (uint32_t)(f->fc_select == 2) : (uint32_t)(n >= CSSM_FLEET_SELECT_MIN_N);
+    l.args.state = f->state; l.args.anc = f->anc;
+    l.args.off = reinterpret_cast<const unsigned long long*>(f->d_fc);
+    l.args.keys = reinterpret_cast<const unsigned long long*>(f->d_fc + o_keys);
+    l.args.op = reinterpret_cast<const cssm_obs_params*>(f->d_fc + o_op);
+    l.args.cur = reinterpret_cast<const uint32_t*>(f->d_fc + o_cur);
+    l.args.recs = f->d_fc + o_rec;
+    l.args.stage = f->d_fc_stage;
+    l.args.out = reinterpret_cast<double*>(f->d_fc + o_out);
+    l.args.logtab = f->logtab; l.args.mk = f->base.mk;
+    l.args.lo_state = (uint32_t)rs.rank[0]; l.args.hi_state = (uint32_t)rs.rank[1];
+    l.args.lo_eta = (uint32_t)re.rank[0]; l.args.hi_eta = (uint32_t)re.rank[1];
+    l.d = d; l.threads = f->threads; l.stream = f->stream;
+    HIP_TRY(hipEventRecord(f->ev[4], f->stream));
+    HIP_TRY(hipMemcpyAsync(f->d_fc, f->h_fc, o_out, hipMemcpyHostToDevice, f->stream));
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+      const size_t ra = (size_t)off[cut[c]], rb = (size_t)off[cut[c + 1]];
+      if (rb == ra) continue;
+      l.args.k0 = cut[c]; l.n_series = cut[c + 1] - cut[c];
+      l.args.samples = samples ? f->d_fc_samp : nullptr; l.args.samp_r0 = ra;
+      const int hrc = cssm_fleet_forecast_launch(l);
+      if (hrc) return fail(CSSM_EHIP, "k_fleet_forecast: %s", hipGetErrorString((hipError_t)hrc));
+      if (samples) HIP_TRY(hipMemcpyAsync(samples + ra * (size_t)(d + 3) * n, f->d_fc_samp, (rb - ra) * samp_row, hipMemcpyDeviceToHost, f->stream));
+      if (samples && c + 2 < cut.size()) HIP_TRY(hipStreamSynchronize(f->stream));   // (the next chunk writes the same buffer)
+    }
+    HIP_TRY(hipMemcpyAsync(f->h_fc + o_out, f->d_fc + o_out, n_out * 8u, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipEventRecord(f->ev[5], f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    if (hipEventElapsedTime(&f->ms_forecast, f->ev[4], f->ev[5]) != hipSuccess) f->ms_forecast = -1.f;
+  }
+  for (uint32_t k = 0; k < S; ++k) {
+    const bool ok = rc_out[k] == CSSM_OK;
+    for (size_t r = (size_t)off[k]; r < (size_t)off[k + 1]; ++r) {
+      const double* o = h_out + r * (size_t)rows * 3u;
+      auto at = [&](int row, int q) { return ok ? o[3 * row + q] : cssm_nan(); };
+      for (int c = 0; c < d; ++c) {
+        if (state_mean) state_mean[r * d + c] = at(c, 0);
+        if (state_lower) state_lower[r * d + c] = at(c, 1);
+        if (state_upper) state_upper[r * d + c] = at(c, 2);
+      }
+      if (eta_mean) eta_mean[r] = at(d, 0);
+      if (eta_lower) eta_lower[r] = at(d, 1);
+      if (eta_upper) eta_upper[r] = at(d, 2);
+      if (obs_mean) obs_mean[r] = at(d + 1, 0);
+      if (obs_lower) obs_lower[r] = at(d + 1, 1);
+      if (obs_upper) obs_upper[r] = at(d + 1, 2);
+      if (samples && !ok) std::fill(samples + r * (size_t)(d + 3) * n, samples + (r + 1) * (size_t)(d + 3) * n, cssm_nan());
+    }
+  }
+  if (!scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", scale_msg.c_str());   // (the call succeeds; the message names the first such series)
+  return CSSM_OK;
+}
+
+extern "C" uint64_t cssm_fleet_observation_index(const cssm_fleet* f, uint32_t k) { return (f && k < f->S) ? f->step[k] : 0; }
+
 extern "C" int cssm_fleet_get_particles(cssm_fleet* f, uint32_t k, double* out_dN) {
   if (!f || !out_dN) return fail(CSSM_EINVAL_ARG, "null argument");
   if (k >= f->S) return fail(CSSM_EINVAL_ARG, "series %u of %u", k, f->S);
@@ -496,7 +687,7 @@ extern "C" int cssm_fleet_get_ancestors(cssm_fleet* f, uint32_t k, uint32_t* out
 
 extern "C" int cssm_fleet_last_ms(cssm_fleet* f, double* ms2) {
   if (!f || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
-  ms2[0] = (double)f->ms_call; ms2[1] = (double)f->ms_summary;
+  ms2[0] = (double)f->ms_call; ms2[1] = (double)f->ms_summary; ms2[2] = (double)f->ms_forecast;
   return CSSM_OK;
 }
 

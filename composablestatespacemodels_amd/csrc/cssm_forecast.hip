@@ -300,6 +300,8 @@ static int obs_params(int kind, int has_scale, double scale, int df, cssm_obs_pa
                                  "(the reference's LogGaussianCox.observation is ???: scala.NotImplementedError)");
   return fail(CSSM_EINVAL_ARG, "unknown obs_kind %d", kind);
 }
+// (the fleet's forecasts refuse a series with the same words: cssm_fleet_forecast.hip.h)
+int cssm_obs_params_or_fail(int kind, int has_scale, double scale, int df, cssm_obs_params* op) { return obs_params(kind, has_scale, scale, df, op); }
 
 extern "C" int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_scale, double scale, int df, uint64_t key, uint32_t step,
                              double* out, int device) {

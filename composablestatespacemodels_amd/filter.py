@@ -379,6 +379,7 @@ class NativePfFleet:
         _abi.check(self.lib.cssm_model_structure(self._desc.ptr(), words, C.byref(d)))
         self.d = int(d.value)
         self.generation = 0
+        self.seeds = [0] * self.S          # the keys given to reseed (cssm_fleet_reseed's default: 0)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -406,6 +407,7 @@ class NativePfFleet:
             raise ValueError("one seed per series")
         sd = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
         _abi.check(self.lib.cssm_fleet_reseed(self._h, _p(sd, C.POINTER(C.c_uint64))))
+        self.seeds = [int(x) for x in sd]
 
     def set_option(self, option: int, value: int):
         _abi.check(self.lib.cssm_fleet_set_option(self._h, int(option), int(value)))
@@ -488,11 +490,68 @@ class NativePfFleet:
         _abi.check(self.lib.cssm_fleet_get_ancestors(self._h, int(k), _p(out, C.POINTER(C.c_uint32))))
         return out
 
-    def last_ms(self) -> Tuple[float, float]:
-        """Device time (HIP events) of the last ll_filter / init / step call and of the last summary, ms; < 0: none yet."""
-        ms = np.zeros(2)
+    def last_ms(self) -> Tuple[float, float, float]:
+        """Device time (HIP events) of the last ll_filter / init / step call, of the last summary and of the last forecast, ms;
+        < 0: none yet."""
+        ms = np.zeros(3)
         _abi.check(self.lib.cssm_fleet_last_ms(self._h, _p(ms)))
-        return float(ms[0]), float(ms[1])
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def observation_index(self, k: int) -> int:
+        """Observations series k's current cloud has seen (cssm_fleet_observation_index)."""
+        return int(self.lib.cssm_fleet_observation_index(self._h, int(k)))
+
+    def forecast_key(self, k: int) -> int:
+        """The default Philox key of a forecast of series k's current cloud: cssm_pf_run_key(seed_k, 2^63 | observation index), the
+        rule of ``NativePf.forecast_key``."""
+        return int(self.lib.cssm_pf_run_key(self.seeds[k], (1 << 63) | self.observation_index(k)))
+
+    def pack_times(self, times):
+        """The ragged arrays of ``cssm_fleet_forecast`` from a sequence of S arrays of future times (None or empty: no horizons for
+        that series): ``(off uint64[S + 1], t float64)``, C-contiguous.  A wrong number of series is refused here."""
+        if len(times) != self.S:
+            raise ValueError("one array of times per series (None or empty: none)")
+        ts = [np.zeros(0) if v is None else np.asarray(v, dtype=np.float64).ravel() for v in times]
+        off = np.zeros(self.S + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(v) for v in ts], dtype=np.uint64)
+        t = np.ascontiguousarray(np.concatenate(ts) if ts else np.zeros(0), dtype=np.float64)
+        return off, t
+
+    def forecast(self, times, keys=None, interval: float = 0.975, want_samples: bool = False):
+        """cssm_fleet_forecast: every series' horizons in one launch.  ``times``: S arrays (None / empty: none for that series);
+        ``keys``: S Philox keys (None: ``forecast_key(k)``).  A list of S dicts with the keys of ``NativePf.forecast`` and shapes
+        [H_k, ...], plus ``rc``, the series' own status (its arrays read NaN when it is not zero).  The fleet is not touched."""
+        off, t = self.pack_times(times)
+        if keys is None:
+            keys = [self.forecast_key(k) for k in range(self.S)]
+        if len(keys) != self.S:
+            raise ValueError("one key per series")
+        ky = np.ascontiguousarray([int(x) & (2**64 - 1) for x in keys], dtype=np.uint64)
+        arr, samples, rc = self.forecast_packed(off, t, ky, interval, want_samples)
+        o = [int(v) for v in off]
+        outs = []
+        for k in range(self.S):
+            r = {name: v[o[k]:o[k + 1]] for name, v in arr.items()}
+            r["samples"] = samples[o[k]:o[k + 1]] if want_samples else None
+            r["key"] = int(ky[k]); r["rc"] = int(rc[k])
+            outs.append(r)
+        return outs
+
+    def forecast_packed(self, off, t, keys, interval: float = 0.975, want_samples: bool = False):
+        """``forecast`` on the arrays ``pack_times`` made and a uint64 array of keys (a caller that forecasts the same fleet repeatedly
+        packs once): ``(dict of arrays laid out like t, samples or None, rc[S])``."""
+        R = int(off[-1])
+        tt = t if R else np.zeros(1)
+        arr = {k: np.zeros((R, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
+        arr.update({k: np.zeros(R) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        samples = np.zeros((R, self.d + 3, self.n)) if want_samples else None
+        rc = np.zeros(self.S, dtype=np.int32)
+        u64 = C.POINTER(C.c_uint64)
+        _abi.check(self.lib.cssm_fleet_forecast(self._h, _p(off, u64), _p(tt), _p(keys, u64), float(interval), _p(arr["state_mean"]),
+                                                _p(arr["state_lower"]), _p(arr["state_upper"]), _p(arr["eta_mean"]), _p(arr["eta_lower"]),
+                                                _p(arr["eta_upper"]), _p(arr["obs_mean"]), _p(arr["obs_lower"]), _p(arr["obs_upper"]),
+                                                _p(samples) if want_samples else None, _p(rc, C.POINTER(C.c_int))))
+        return arr, samples, rc
 
 
 class _PfView(NativePf):
@@ -900,6 +959,22 @@ class FilterFleet:
                 raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable")
         self._states = []
         return ll
+
+    def forecast(self, times, interval: float = 0.975, seed: Optional[int] = None) -> List[List[ForecastOut]]:
+        """``ParticleFilter.forecast`` of every series from its current state, all of them in one device call: ``times[k]`` = series k's
+        future times (None / empty: none; the list for it is empty).  seed = the Philox key of every series' draws; None: each
+        series' default key (``NativePfFleet.forecast_key``)."""
+        ts = [[] if v is None else [float(x) for x in v] for v in times]
+        rs = self._fleet.forecast(ts, None if seed is None else [int(seed)] * self.S, float(interval))
+        for k, r in enumerate(rs):
+            if r["rc"]:
+                raise _abi.CssmError(r["rc"], f"series {k}: its forecast was refused (no cloud, times before its clock or decreasing, "
+                                              f"or a model without the scale its observation needs)")
+        return [_forecast_outs(ts[k], rs[k]) for k in range(self.S)]
+
+    def getMeanForecast(self, ts, interval: float, seed: Optional[int] = None) -> List[ForecastOut]:
+        """``ParticleFilter.getMeanForecast`` (:389-409) of every series: one horizon each, ``ts[k]`` its time."""
+        return [o[0] for o in self.forecast([[float(v)] for v in ts], interval, seed)]
 
     def getIntervals(self) -> List[PfOut]:
         """``ParticleFilter.getIntervals`` (:415-424) of every series' current state."""

@@ -309,6 +309,10 @@ int cssm_pf_stream_idle(cssm_pf* pf);
  * ((d + 2) x N x 8 bytes per horizon) fit in this many KiB (at least one horizon per chunk).  Results do not depend on it (tests
  * lower it to run the chunked path at small N). */
 #define CSSM_OPT_FORECAST_CAP 11
+/* CSSM_OPT_FLEET_SELECT (fleets only; default 0): how cssm_fleet_forecast takes the two order statistics of a row inside the series'
+ * workgroup -- 0: chosen by N (today: the sort at every N), 1: a bitonic sort of the row's keys in LDS, 2: a radix select over them in LDS.  Both are exact: the
+ * results do not depend on it (tests/test_gpu_fleet_forecast.py); it exists for measurements. */
+#define CSSM_OPT_FLEET_SELECT 12
 int cssm_pf_set_option(cssm_pf* pf, int option, int value);
 /* Counters of the run-time specialisation in this process: out4 = {kernels compiled, kernels loaded from the disk cache, launches of
  * run-time-compiled kernels, failures (each reported once on stderr)}. */
@@ -761,7 +765,8 @@ int cssm_model_structure(const cssm_model_desc* desc, uint32_t* words_out, int32
  * CSSM_EINVAL_DESC and a message naming the reason and the entry points that do serve it (cssm_pf_*, cssm_pfb_*); a fleet call
  * never degenerates into S single-handle runs.  Thread-affinity and device rules as for every entry point: each call selects the
  * fleet's device; the fleet owns a non-blocking stream; a fleet is not re-entrant.
- * Not here: forecasts and `filter`'s sampled path from a fleet, sharded fleets, other resamplers. */
+ * Not here: `filter`'s sampled path and posterior-predictive forecasts from a fleet, sharded fleets, other resamplers
+ * (INTEGRATION.md). */
 typedef struct cssm_fleet cssm_fleet;
 /* 12 bytes of LDS per particle (weight 8, ancestor 4) + 7.3 KB per block: 55.3 KB at 4096, two blocks per CU of 160 KiB; the summary
  * kernel sorts a row of at most 4096 keys (32 KiB) in LDS. */
@@ -779,8 +784,9 @@ uint64_t cssm_fleet_num_particles(const cssm_fleet* f);
 int cssm_fleet_set_params(cssm_fleet* f, const cssm_model_desc* const* descs);
 /* seeds[k] = the Philox key of series k (default 0).  Derive the keys of one user seed with cssm_pf_run_key(seed, k). */
 int cssm_fleet_reseed(cssm_fleet* f, const uint64_t* seeds);
-/* CSSM_OPT_RESAMPLER only, and only CSSM_RESAMPLE_SYSTEMATIC: any other resampler is CSSM_EINVAL_ARG with the reason (the
- * `Resample[A]` a FilterFleet is constructed with goes through here). */
+/* CSSM_OPT_RESAMPLER, and only CSSM_RESAMPLE_SYSTEMATIC: any other resampler is CSSM_EINVAL_ARG with the reason (the
+ * `Resample[A]` a FilterFleet is constructed with goes through here); CSSM_OPT_FORECAST_CAP (KiB, 0 = 1 GiB, negative refused): the
+ * samples cssm_fleet_forecast holds on the device at a time; CSSM_OPT_FLEET_SELECT.  Every other option is CSSM_EINVAL_ARG. */
 int cssm_fleet_set_option(cssm_fleet* f, int option, int value);
 
 /* llFilter (model/ParticleFilter.scala:137-140) of every series, ragged: series k owns the records off[k] .. off[k+1]-1 of
@@ -812,9 +818,42 @@ int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_mean, doubl
 /* the cloud (SoA, d x N, as cssm_pf_get_particles) and the ancestors of series k; CSSM_ESTATE without a cloud */
 int cssm_fleet_get_particles(cssm_fleet* f, uint32_t k, double* out_dN);
 int cssm_fleet_get_ancestors(cssm_fleet* f, uint32_t k, uint32_t* out_N);
-/* ms2[0] = device time of the last ll_filter / init / step call (upload, launch, read-back), ms2[1] = of the last summary; HIP
- * events on the fleet's stream, < 0 while there was none. */
-int cssm_fleet_last_ms(cssm_fleet* f, double* ms2);
+/* Forecasts of every series from its current cloud, all horizons of all series in ONE launch (one workgroup per series): the scan of
+ * SimulateData.forecast + summariseForecast (model/Data.scala:196-231, model/ParticleFilter.scala:368-409).  Ragged as
+ * cssm_fleet_ll_filter: series k owns the future times t[off[k] .. off[k+1]) (off[0] = 0, non-decreasing, S + 1 entries); a series
+ * with no horizons is left alone (nothing is written for it, rc_out[k] = CSSM_OK).  keys[k] = the Philox key of series k's forecast
+ * (the rule of thumb of cssm_pf_forecast: cssm_pf_run_key(seed_k, 2^63 | cssm_fleet_observation_index(f, k))).  Outputs are laid out
+ * like t; with R = off[S]: state_* [R][d], eta_* / obs_* [R], the optional samples [R][d + 3][N] (rows: the d states, gamma, eta, obs);
+ * any output may be NULL.
+ *
+ * Per series k the result is what cssm_pf_forecast(handle_k, t_k, H_k, keys[k], interval, ...) returns for a handle of its own --
+ * cssm_pf_create(descs[k], N, seeds[k]) driven through the same calls: the source is the series' current cloud (what
+ * cssm_fleet_summary reads), horizon h starts from horizon h - 1, the transition is the one an unweighted step with key keys[k] and
+ * observation index h draws (CSSM_STREAM_STEP, paired streams, dt = 0 allowed), gamma and eta are taken at the series' own t[h] under
+ * its own parameters, one observation draw on CSSM_STREAM_OBS with its own scale, ranks and clamping as documented at
+ * cssm_pf_forecast.  Order statistics and samples are those bits; means are plain fp64 sums, so their order of summation may differ.
+ *
+ * The fleet is not touched: clouds, ancestors, clocks, observation indices, ll, ESS and keys stay as they were, and a following
+ * cssm_fleet_step / cssm_fleet_summary returns what it would have without the forecast.
+ *
+ * rc_out[S] = the series' OWN status: CSSM_ESTATE for a series that has horizons but no cloud; CSSM_EINVAL_ARG for a series whose
+ * times are not finite, start before its clock or decrease, and for a series whose model lacks the scale its observation needs
+ * (cssm_last_error then carries the reference's exception for the first such series, although the call succeeds).  Such a series'
+ * outputs read NaN, and every other series is bit for bit what it is without it.  The call itself fails only for errors that are not
+ * one series' own: CSSM_EINVAL_ARG (null f / off / t / keys / rc_out, off[0] != 0 or off decreasing, interval outside (0, 1]),
+ * CSSM_ESTATE when no series of the fleet has a cloud and R > 0, CSSM_ENOMEM, HIP failures.  With samples, the fleet runs in chunks
+ * of series whose samples fit CSSM_OPT_FORECAST_CAP on the device (a series is never split). */
+int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const double* t, const uint64_t* keys, double interval,
+                        double* state_mean, double* state_lower, double* state_upper,
+                        double* eta_mean, double* eta_lower, double* eta_upper,
+                        double* obs_mean, double* obs_lower, double* obs_upper,
+                        double* samples, int* rc_out);
+/* Observations series k's current cloud has seen (the Philox counter word of its next step); 0 for a null fleet or k >= S, the
+ * convention of cssm_pf_observation_index. */
+uint64_t cssm_fleet_observation_index(const cssm_fleet* f, uint32_t k);
+/* ms3[0] = device time of the last ll_filter / init / step call (upload, launch, read-back), ms3[1] = of the last summary, ms3[2] =
+ * of the last forecast; HIP events on the fleet's stream, < 0 while there was none.  The array holds THREE doubles. */
+int cssm_fleet_last_ms(cssm_fleet* f, double* ms3);
 /* Diagnostic, no device: the compact per-observation record the fleet uploads for (t_prev, t, y, has_obs, step) under `desc`,
  * a cloud of n_particles and Philox key `seed` -- 80 + 40 d bytes: y, c[4], cdf, u, dt, ref (doubles), has_obs (i32), step (u32),
  * then d x 4 transition coefficients and d f coefficients, each the value cssm_pf_step's record holds. */
