@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +26,8 @@ static_assert(CSSM_FLEET_MAX_N <= 4096, "k_fleet_summary sorts at most 4096 keys
 struct cssm_fleet {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // filter / step call, summary, forecast
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // filter / step call, summary, forecast,
+                                                                                                 // [6], [7]: a path launch's upload | kernel | read-back
   uint32_t n = 0, S = 0;
   int d = 0, threads = 64;
   size_t lds = 0;
@@ -42,6 +44,10 @@ struct cssm_fleet {
   unsigned char* d_stage = nullptr; size_t stage_cap = 0;
   double* d_ll_t = nullptr; int32_t* d_ess_t = nullptr; size_t res_cap = 0;
   double* d_tmp = nullptr;              // d x n: cssm_fleet_get_particles
+  double* d_path = nullptr; size_t path_cap = 0;   // cssm_fleet_filter, grow-only: [S][d] last rows, then (asked for) the R + S rows of the paths
+  float ms_upload = -1.f, ms_kernel = -1.f;        // ... of its last launch
+  double ms_build = 0.0;                           // ... host time of its records
+  double pm_split[6] = {0, 0, 0, 0, 0, 0};         // cssm_fleet_pmmh_run: see cssm_fleet_pmmh_last_split
   double* d_sm = nullptr; size_t sm_cap = 0;   // summary: [S][d] f coefficients, [S][d + 1][3] results, [S] buffer numbers
   // host staging (pinned)
   unsigned char* h_stage = nullptr; size_t h_stage_cap = 0;
@@ -73,9 +79,10 @@ static void fleet_parallel(size_t count, size_t work, F f) {
   for (auto& x : th) x.join();
 }
 
-static void fleet_pack_rec(const HostModel& m, double t_prev, double t, double y, int has, uint32_t step, unsigned char* dst) {
+static void fleet_pack_rec(const HostModel& m, double t_prev, double t, double y, int has, uint32_t step, unsigned char* dst, uint32_t* pick = nullptr) {
   StepRec r;
   cssm_build_rec(&m, t_prev, t, y, has, step, &r);
+  if (pick) *pick = r.pick;
   FleetRecHead h;
   h.y = r.y; h.c[0] = r.c[0]; h.c[1] = r.c[1]; h.c[2] = r.c[2]; h.c[3] = r.c[3]; h.cdf = r.cdf; h.u = r.u; h.dt = r.dt; h.ref = r.ref;
   h.has_obs = r.has_obs; h.step = r.step;
@@ -153,7 +160,7 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp};
+  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
   if (f->h_fc) (void)hipHostFree(f->h_fc);
@@ -270,8 +277,9 @@ static int fleet_upload_par(cssm_fleet* f) {
 // staging layout of a launch: [S + 1 offsets (u64)] [S control words (u32), padded to 8 bytes] [R compact records]
 static size_t fleet_stage_head(const cssm_fleet* f) { return ((size_t)f->S + 1u) * 8u + (((size_t)f->S * 4u + 7u) & ~(size_t)7u); }
 
-static int fleet_ensure(cssm_fleet* f, size_t R) {
-  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d);
+// (picks: the launch also carries R sampleOne slots, uint32 each, behind the records)
+static int fleet_ensure(cssm_fleet* f, size_t R, bool picks = false) {
+  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d) + (picks ? R * 4u : 0u);
   if (need > f->h_stage_cap) {
     if (f->h_stage) (void)hipHostFree(f->h_stage);
     f->h_stage = nullptr; f->h_stage_cap = 0;
@@ -296,16 +304,28 @@ static int fleet_ensure(cssm_fleet* f, size_t R) {
   return CSSM_OK;
 }
 
-// upload the staged launch, run it, bring the series' scalars (and, asked for, the per-observation results) back; synchronises
-static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t) {
+// upload the staged launch, run it, bring the series' scalars (and, asked for, the per-observation results) back; synchronises.
+// want_path: the staged launch carries its picks and runs k_fleet_series<D, true>; path_out (may be null) / last_out receive the rows.
+static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, bool want_path = false, double* path_out = nullptr, double* last_out = nullptr) {
   int rc = fleet_upload_par(f);
   if (rc) return rc;
-  const size_t head = fleet_stage_head(f), bytes = head + R * CSSM_FLEET_REC_BYTES(f->d);
+  const size_t head = fleet_stage_head(f), recs = R * CSSM_FLEET_REC_BYTES(f->d), bytes = head + recs + (want_path ? R * 4u : 0u);
+  const size_t n_last = (size_t)f->S * f->d, n_rows = n_last + (path_out ? (R + f->S) * (size_t)f->d : 0u);
+  if (want_path && n_rows > f->path_cap) {
+    if (f->d_path) (void)hipFree(f->d_path);
+    f->d_path = nullptr; f->path_cap = 0;
+    if (hipMalloc(&f->d_path, (n_rows + n_rows / 4) * 8) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of sampled paths", n_rows * 8);
+    f->path_cap = n_rows + n_rows / 4;
+  }
   HIP_TRY(hipEventRecord(f->ev[0], f->stream));
   HIP_TRY(hipMemcpyAsync(f->d_stage, f->h_stage, bytes, hipMemcpyHostToDevice, f->stream));
   if (R) {   // records a failed series never reaches read as NaN / -1
     HIP_TRY(hipMemsetAsync(f->d_ll_t, 0xff, R * 8, f->stream));
     HIP_TRY(hipMemsetAsync(f->d_ess_t, 0xff, R * 4, f->stream));
+  }
+  if (want_path) {   // ... and the rows it never records as NaN
+    HIP_TRY(hipMemsetAsync(f->d_path, 0xff, n_rows * 8, f->stream));
+    HIP_TRY(hipEventRecord(f->ev[6], f->stream));
   }
   FleetLaunch l;
   l.args.n = f->n; l.args.state = f->state; l.args.anc = f->anc; l.args.ser = f->ser; l.args.par = f->par;
@@ -313,7 +333,10 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t) {
   l.args.ctl = reinterpret_cast<const uint32_t*>(f->d_stage + ((size_t)f->S + 1u) * 8u);
   l.args.recs = f->d_stage + head;
   l.args.ll_t = f->d_ll_t; l.args.ess_t = f->d_ess_t; l.args.logtab = f->logtab; l.args.mk = f->base.mk;
-  l.n_series = f->S; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+  l.args.picks = want_path ? reinterpret_cast<const uint32_t*>(f->d_stage + head + recs) : nullptr;
+  l.args.path = (want_path && path_out) ? f->d_path + n_last : nullptr;
+  l.args.last = want_path ? f->d_path : nullptr;
+  l.n_series = f->S; l.path = want_path; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
   int hrc = 0;
   switch (f->d) {
 #define FLEET_CASE(D) case D: hrc = cssm_fleet_launch_d##D(l); break;
@@ -323,18 +346,26 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t) {
     default: return fail(CSSM_EINVAL_DESC, "latent dimension %d", f->d);
   }
   if (hrc) return fail(CSSM_EHIP, "k_fleet_series: %s", hipGetErrorString((hipError_t)hrc));
+  if (want_path) HIP_TRY(hipEventRecord(f->ev[7], f->stream));
   HIP_TRY(hipMemcpyAsync(f->h_ser.data(), f->ser, (size_t)f->S * sizeof(FleetSeries), hipMemcpyDeviceToHost, f->stream));
+  if (want_path && path_out) HIP_TRY(hipMemcpyAsync(path_out, f->d_path + n_last, (n_rows - n_last) * 8, hipMemcpyDeviceToHost, f->stream));
+  if (want_path && last_out) HIP_TRY(hipMemcpyAsync(last_out, f->d_path, n_last * 8, hipMemcpyDeviceToHost, f->stream));
   if (R && ll_t) HIP_TRY(hipMemcpyAsync(ll_t, f->d_ll_t, R * 8, hipMemcpyDeviceToHost, f->stream));
   if (R && ess_t) HIP_TRY(hipMemcpyAsync(ess_t, f->d_ess_t, R * 4, hipMemcpyDeviceToHost, f->stream));
   HIP_TRY(hipEventRecord(f->ev[1], f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
   if (hipEventElapsedTime(&f->ms_call, f->ev[0], f->ev[1]) != hipSuccess) f->ms_call = -1.f;
+  if (want_path) {
+    if (hipEventElapsedTime(&f->ms_upload, f->ev[0], f->ev[6]) != hipSuccess) f->ms_upload = -1.f;
+    if (hipEventElapsedTime(&f->ms_kernel, f->ev[6], f->ev[7]) != hipSuccess) f->ms_kernel = -1.f;
+  }
   return CSSM_OK;
 }
 
-extern "C" int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
-                                    double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out) {
-  if (!f || !off || !ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+// llFilter / filter of every series: the records of all of them built (threaded above 8192), ONE upload, ONE launch, ONE read-back.
+// want_path: `filter` -- the sampleOne slots travel behind the records, path_out (may be null) and last_out (may be null) are written.
+static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double* ll_out, double* ll_t,
+                            int32_t* ess_t, bool want_path, double* path_out, double* last_out, int* rc_out) {
   const uint32_t S = f->S;
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
   for (uint32_t k = 0; k < S; ++k)
@@ -343,12 +374,14 @@ extern "C" int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const do
   const size_t R = (size_t)off[S];
   if (R && (!t || !y)) return fail(CSSM_EINVAL_ARG, "null data");
   HIP_TRY(hipSetDevice(f->device));
-  int rc = fleet_ensure(f, R);
+  const auto tb0 = std::chrono::steady_clock::now();
+  int rc = fleet_ensure(f, R, want_path);
   if (rc) return rc;
   unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
   uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
   unsigned char* h_recs = f->h_stage + fleet_stage_head(f);
   const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
+  uint32_t* h_picks = want_path ? reinterpret_cast<uint32_t*>(h_recs + R * RB) : nullptr;
   for (uint32_t k = 0; k <= S; ++k) h_off[k] = off[k];
   std::vector<double> t0(S, 0.0);
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
@@ -361,12 +394,13 @@ extern "C" int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const do
       t0[k] = m;
       double tp = m;
       for (size_t s = a; s < b; ++s) {
-        fleet_pack_rec(f->models[k], tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), h_recs + s * RB);
+        fleet_pack_rec(f->models[k], tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), h_recs + s * RB, h_picks ? h_picks + s : nullptr);
         tp = t[s];
       }
     }
   });
-  rc = fleet_launch(f, R, ll_t, ess_t);
+  if (want_path) f->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
+  rc = fleet_launch(f, R, ll_t, ess_t, want_path, path_out, last_out);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
     const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
@@ -378,6 +412,99 @@ extern "C" int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const do
       rc_out[k] = CSSM_OK; ll_out[k] = s.ll; f->live[k] = 1; f->t[k] = t[b - 1]; f->step[k] = (uint32_t)(b - a);
     }
   }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                    double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out) {
+  if (!f || !off || !ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, false, nullptr, nullptr, rc_out);
+}
+
+// filter (model/ParticleFilter.scala:152-158) of every series: cssm_fleet_ll_filter, and one particle of the initial cloud and of the
+// cloud after every record (Resampling.sampleOne).  What needs no fleet is refused first, so that it is refused on any host.
+extern "C" int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double* ll_out,
+                                 double* ll_t, int32_t* ess_t, double* path_out, double* last_out, int* rc_out) {
+  if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
+  if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
+  if (!path_out && !last_out)
+    return fail(CSSM_EINVAL_ARG, "neither path_out nor last_out is given: cssm_fleet_ll_filter is the call that records no path");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, true, path_out, last_out, rc_out);
+}
+
+// ParticleMetropolisHastings (model/PMMH.scala:68-81,114-123) for S chains in lockstep, a chain per series: chain k is cssm_pmmh_run
+// with theta0[k], seeds[k] and series k's slice of the data -- proposals, filter keys and decisions are cssm_pmmh_chain_*'s, as in
+// every PMMH driver -- and an iteration's S filters are ONE fleet launch that brings back S x d doubles of sampled states.
+#define FLEET_PMMH_SERVED "cssm_pmmh_run_batched (a batch of chains, each spread over the GPU) serves it"
+extern "C" int cssm_fleet_pmmh_run(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, size_t n_theta, double delta, const uint64_t* off,
+                                   const double* t, const double* y, const uint8_t* has_obs, const uint64_t* seeds, size_t n_iters, double* ll,
+                                   double* theta, int32_t* accepted, double* last_state) {
+  if (!desc || !theta0 || !off || !t || !y || !seeds) return fail(CSSM_EINVAL_ARG, "null argument (desc, theta0, off, t, y, seeds)");
+  if (n_iters && (!ll || !theta || !accepted || !last_state)) return fail(CSSM_EINVAL_ARG, "null output");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  HostModel probe;
+  int rc = cssm_build_model(&probe, desc, false);
+  if (rc) return rc;
+  if (probe.obs_kind == CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_DESC, "the fleet does not serve the LGCP observation model (sub-stepped events); " FLEET_PMMH_SERVED);
+  size_t flat = 0;
+  rc = cssm_desc_flatten(desc, nullptr, 0, &flat);
+  if (rc) return rc;
+  if (flat != n_theta) return fail(CSSM_EINVAL_ARG, "theta0 has %zu entries per chain, the descriptor flattens to %zu", n_theta, flat);
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const uint32_t S = f->S;
+  const int d = f->d;
+  for (uint32_t k = 0; k < S; ++k) {
+    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
+                                         k + 1, (unsigned long long)off[k + 1]);
+    if (off[k + 1] == off[k]) return fail(CSSM_EINVAL_ARG, "chain %u has an empty slice of the data (the reference's minBy throws on an empty Vector)", k);
+  }
+  {   // the structure must be the fleet's: said here, once, not per series of the first iteration
+    HostModel same = f->base;
+    rc = cssm_build_model(&same, desc, true);
+    if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "desc is not of the fleet's model structure (%s); " FLEET_PMMH_SERVED, keep.c_str()); }
+  }
+  std::vector<cssm_pmmh_chain*> chains(S, nullptr);
+  std::vector<const cssm_model_desc*> descs(S);
+  std::vector<uint64_t> keys(S);
+  std::vector<double> pll(S), last((size_t)S * d);
+  std::vector<int> rcs(S);
+  for (uint32_t k = 0; k < S && !rc; ++k) rc = cssm_pmmh_chain_create(desc, theta0 + (size_t)k * n_theta, n_theta, delta, seeds[k], d, &chains[k]);
+  double split[6] = {0, 0, 0, 0, 0, 0};
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+  for (size_t it = 0; it < n_iters && !rc; ++it) {
+    const auto ta = clk::now();
+    for (uint32_t k = 0; k < S; ++k) descs[k] = cssm_pmmh_chain_propose(chains[k], it, &keys[k]);
+    rc = cssm_fleet_set_params(f, descs.data());
+    if (rc) break;
+    rc = cssm_fleet_reseed(f, keys.data());
+    if (rc) break;
+    split[0] += ms_since(ta);
+    rc = cssm_fleet_filter(f, off, t, y, has_obs, pll.data(), nullptr, nullptr, nullptr, last.data(), rcs.data());
+    if (rc) break;
+    split[1] += f->ms_build; split[2] += f->ms_upload; split[3] += f->ms_kernel;
+    const auto tc = clk::now();
+    for (uint32_t k = 0; k < S; ++k) {
+      if (rcs[k] == CSSM_ENONFINITE) pll[k] = -cssm_inf();                    // a proposal the filter cannot weigh is rejected
+      else if (rcs[k]) { rc = fail(rcs[k], "chain %u: the fleet's filter returned status %d", k, rcs[k]); break; }
+      const size_t o = (size_t)k * n_iters + it;
+      cssm_pmmh_chain_decide(chains[k], it, pll[k], last.data() + (size_t)k * d, &ll[o], theta + o * n_theta, &accepted[o], last_state + o * (size_t)d);
+    }
+    split[4] += ms_since(tc);
+    split[5] += 1.0;
+  }
+  for (cssm_pmmh_chain* c : chains) if (c) cssm_pmmh_chain_destroy(c);
+  for (int q = 0; q < 6; ++q) f->pm_split[q] = split[q];
+  return rc;
+}
+
+extern "C" int cssm_fleet_pmmh_last_split(cssm_fleet* f, double* ms6) {
+  if (!f || !ms6) return fail(CSSM_EINVAL_ARG, "null argument");
+  for (int q = 0; q < 6; ++q) ms6[q] = f->pm_split[q];
   return CSSM_OK;
 }
 

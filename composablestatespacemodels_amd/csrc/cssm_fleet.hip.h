@@ -53,6 +53,11 @@ struct FleetArgs {
   int32_t* ess_t;
   const double* logtab;
   ModelK mk;
+  // `filter`'s sampled path (k_fleet_series<D, true> only; model/ParticleFilter.scala:152-158, Resampling.sampleOne).  Behind every
+  // field the other instantiation reads: its kernel arguments stay where they were.
+  const uint32_t* picks;             // per record of the launch: StepRec::pick, the slot sampleOne takes after that observation
+  double* path;                      // may be null; series k owns rows off[k] + k .. off[k + 1] + k (T_k + 1 rows of d), preset to NaN
+  double* last;                      // [S][d], preset to NaN: row T_k of series k's path
 };
 
 // a - b mod 2^128 (integers: exact)
@@ -70,9 +75,19 @@ __device__ __forceinline__ uint32_t fleet_end_slot(cssm_u128 run, double totd, d
   return (c > n) ? n : c;
 }
 
+// Row `row` of the series' sampled path: component tid of the particle in slot `pick` of the cloud in `buf`, through the ancestors
+// (the identity behind the initial draw and behind an unweighted record).  The caller stands behind a barrier that completed both.
+template <int D>
+__device__ __forceinline__ void fleet_path_row(const double* buf, const uint32_t* s_anc, uint32_t n, uint32_t pick, double* row, uint32_t tid) {
+  if (tid < (uint32_t)D) row[tid] = buf[(size_t)tid * n + s_anc[pick]];
+}
+
 // llFilter / stepFilter of series blockIdx.x over its records of this launch (model/ParticleFilter.scala:105-140).
 // Dynamic LDS: n_even doubles (log-weights, then the weights in their place) + n ancestors.
-template <int D>
+// PATH: `filter` (:152-158) -- a launch that draws the initial cloud also records one particle of it and one of the cloud after every
+// record (FleetArgs::picks / path / last).  A template flag: the instantiation cssm_fleet_ll_filter and cssm_fleet_step run holds no
+// trace of it (the resource table).
+template <int D, bool PATH>
 __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_series(const FleetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   __shared__ StepRec s_rec;
@@ -112,8 +127,19 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   const uint32_t j0 = tid * it;
   const uint32_t j1 = (j0 + it < n) ? j0 + it : n;             // (j0 >= n: an empty range)
   constexpr uint32_t RB = (uint32_t)CSSM_FLEET_REC_BYTES(D);
+  uint32_t cur = 0u;                                           // (PATH) the buffer that holds the cloud: 0 behind the initial draw
   for (unsigned long long r = r0; r < r1; ++r) {               // bounded by the series' length
     __syncthreads();                                            // the cloud / ancestors of the record before; s_rec is free
+    if (PATH && a.path) {                                       // (uniform) row r - r0: the initial cloud's pick, or the record before's
+      uint32_t pick;
+      if (r == r0) {
+        const int32_t pr = (int32_t)cssm_philox_draw(seed, 0, 0, CSSM_STREAM_PICK, 0).v[0];
+        pick = (uint32_t)((uint64_t)(pr < 0 ? (uint32_t)0 - (uint32_t)pr : (uint32_t)pr) % n);
+      } else {
+        pick = a.picks[r - 1];
+      }
+      fleet_path_row<D>(st + (size_t)cur * D * n, s_anc, n, pick, a.path + (size_t)(r + k) * D, tid);
+    }
     {
       const unsigned char* g = a.recs + (size_t)r * RB;
       const FleetRecHead* h = reinterpret_cast<const FleetRecHead*>(g);
@@ -131,6 +157,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     const bool weighted = rec->has_obs != 0;
     const double* src = st + (size_t)(step & 1u) * D * n;
     double* dst = st + (size_t)((step & 1u) ^ 1u) * D * n;
+    if (PATH) cur = (step & 1u) ^ 1u;
     // 1. gather through the previous ancestors, transition, f, log-density (:118, :123)
     double tmax = -cssm_inf();
     bool bad = false;
@@ -225,6 +252,11 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     if (tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
   }
   __syncthreads();
+  if (PATH && !err && r1 > r0) {                               // (uniform) the last row: no record follows to write it
+    const uint32_t pick = a.picks[r1 - 1];
+    if (a.path) fleet_path_row<D>(st + (size_t)cur * D * n, s_anc, n, pick, a.path + (size_t)(r1 + k) * D, tid);
+    fleet_path_row<D>(st + (size_t)cur * D * n, s_anc, n, pick, a.last + (size_t)k * D, tid);
+  }
   for (uint32_t i = tid; i < n; i += bs) ganc[i] = s_anc[i];
   if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.ser[k] = o; }
 }
@@ -232,6 +264,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
 struct FleetLaunch {
   FleetArgs args;
   uint32_t n_series;
+  bool path;            // k_fleet_series<D, true>
   int threads;
   size_t lds;
   hipStream_t stream;

@@ -452,6 +452,50 @@ class NativePfFleet:
         o = [int(v) for v in off]
         return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], rc
 
+    def _check_packed(self, off, t, y, has):
+        """What ``filter_packed`` refuses before any device call: a ragged layout that is not S series of t / y / has."""
+        off = np.asarray(off)
+        if off.dtype != np.uint64 or off.ndim != 1 or len(off) != self.S + 1:
+            raise ValueError(f"off must hold S + 1 = {self.S + 1} uint64 offsets")
+        if int(off[0]) != 0 or any(int(off[k + 1]) < int(off[k]) for k in range(self.S)):
+            raise ValueError("off[0] must be 0 and off must be non-decreasing")
+        R = int(off[-1])
+        for name, a, ty in (("t", t, np.float64), ("y", y, np.float64), ("has", has, np.uint8)):
+            if a is None or a.dtype != ty or len(a) != R or not a.flags.c_contiguous:
+                raise ValueError(f"{name} must be a C-contiguous {np.dtype(ty).name} array of off[-1] = {R} entries")
+        return R
+
+    def filter(self, datas, want_path: bool = True):
+        """``filter`` of every series (cssm_fleet_filter): ``(ll[S], [ll_t of series k], [ess_t of series k], paths, last[S, d], rc[S])``.
+        ``paths``: a list of ``[T_k + 1, d]`` arrays -- row 0 the sampled particle of the initial cloud, row s + 1 the one after
+        observation s -- or None without ``want_path`` (the device then keeps and returns the last rows only).  A series whose rc is
+        not zero reads NaN from the failing observation on and in its ``last`` row."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        return self.filter_packed(*self.pack(datas), want_path=want_path)
+
+    def filter_packed(self, off, t, y, has, want_path: bool = True):
+        """``filter`` on arrays ``pack`` made (a caller that filters the same fleet repeatedly packs once)."""
+        R = self._check_packed(off, t, y, has)
+        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
+        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
+        last = np.zeros((self.S, self.d))
+        path = np.zeros((R + self.S, self.d)) if want_path else None
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_filter(self._h, _p(off, C.POINTER(C.c_uint64)), _p(t), _p(y), _p(has, C.POINTER(C.c_uint8)), _p(ll),
+                                              _p(ll_t), _p(ess_t, C.POINTER(C.c_int32)), _p(path) if want_path else None, _p(last),
+                                              _p(rc, C.POINTER(C.c_int))))
+        o = [int(v) for v in off]
+        paths = [path[o[k] + k:o[k + 1] + k + 1] for k in range(self.S)] if want_path else None
+        return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], paths, last, rc
+
+    def pmmh_last_split(self):
+        """cssm_fleet_pmmh_last_split: milliseconds of the last ``cssm_fleet_pmmh_run`` on this fleet, summed over its iterations --
+        (propose + set_params + reseed, record building, upload, kernel, decide) and the iterations counted."""
+        ms = np.zeros(6)
+        _abi.check(self.lib.cssm_fleet_pmmh_last_split(self._h, _p(ms)))
+        return tuple(float(v) for v in ms[:5]), int(ms[5])
+
     def init(self, t0):
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (self.S,)), dtype=np.float64)
         self.generation += 1
@@ -959,6 +1003,21 @@ class FilterFleet:
                 raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable")
         self._states = []
         return ll
+
+    def filter(self, datas: Sequence[Sequence[TimedObservation]]) -> List[Tuple[float, List[StateSpace]]]:
+        """``Filter.filter`` (ParticleFilter.scala:152-158) of every series in one device call: per series ``(ll, [StateSpace(t, state)])``
+        of length T_k + 1, the first entry at the slice's smallest time."""
+        split = [split_data(d) for d in datas]
+        ll, _, _, paths, _, rc = self._fleet.filter(split)
+        for k in range(self.S):
+            if rc[k]:
+                raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable")
+        self._states = []
+        out = []
+        for k, (t, _, _) in enumerate(split):
+            times = [float(np.min(t))] + [float(v) for v in t]
+            out.append((float(ll[k]), [StateSpace(tt, paths[k][i].copy()) for i, tt in enumerate(times)]))
+        return out
 
     def forecast(self, times, interval: float = 0.975, seed: Optional[int] = None) -> List[List[ForecastOut]]:
         """``ParticleFilter.forecast`` of every series from its current state, all of them in one device call: ``times[k]`` = series k's

@@ -21,7 +21,7 @@ from typing import Callable, Iterator, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .filter import NativePf, Resampling
+from .filter import NativePf, NativePfFleet, Resampling
 from .model import Parameters, UnparamModel, split_data
 
 
@@ -187,6 +187,68 @@ def pmmh_native_batched(unparam: UnparamModel, inits: Sequence[Parameters], data
                                              ll.ctypes.data_as(dp), th.ctypes.data_as(dp), acc.ctypes.data_as(C.POINTER(C.c_int32)), last.ctypes.data_as(dp)))
     finally:
         lib.cssm_pfb_destroy(hb)
+    return ll, th, acc, last
+
+
+def pmmh_fleet_pack(datas, chains: int):
+    """The ragged arrays of ``cssm_fleet_pmmh_run`` for ``chains`` chains: ``datas`` is ONE data set (a sequence of TimedObservation: every
+    chain sees it) or a sequence of ``chains`` data sets.  Refuses an empty data set here, before any device call."""
+    datas = list(datas)
+    shared = len(datas) == 0 or hasattr(datas[0], "observation")
+    if shared:
+        datas = [datas] * chains
+    if len(datas) != chains:
+        raise ValueError(f"one data set, or one per chain ({chains}), not {len(datas)}")
+    cache = {}
+    split = []
+    for k, d in enumerate(datas):
+        if len(d) == 0:
+            raise ValueError(f"chain {k} has an empty data set (the reference's minBy throws on an empty Vector)")
+        split.append(cache.setdefault(id(d), split_data(d)))
+    return NativePfFleet.pack(split)
+
+
+def pmmh_native_fleet(unparam: UnparamModel, inits: Sequence[Parameters], datas, n: int, delta: float, iters: int,
+                      seeds: Sequence[int], device: int = 0, fleet: Optional[NativePfFleet] = None):
+    """``len(inits)`` chains in lockstep on a fleet (``cssm_fleet_pmmh_run``), a chain per series and ONE launch per iteration: chain k is
+    ``pmmh_native(unparam, inits[k], data_k, n, delta, iters, seed=seeds[k])`` bit for bit.  ``datas``: one data set (every chain sees it)
+    or a sequence of S data sets (a chain per sensor).  For the reference's everyday cloud sizes (n <= ``_abi.FLEET_MAX_N``, no LGCP,
+    systematic resampling); ``pmmh_native_batched`` serves the rest.  ``fleet``: a NativePfFleet of S series and n particles to reuse.
+    Returns (ll[S, iters], theta[S, iters, n_theta], accepted[S, iters], last_state[S, iters, d]); each chain's rows go through
+    ``posterior_rows`` unchanged."""
+    S = len(inits)
+    if S < 1 or len(seeds) != S:
+        raise ValueError("one seed per chain")
+    theta0 = [np.asarray(p.flattenParams(), dtype=np.float64) for p in inits]
+    if any(th.shape != theta0[0].shape for th in theta0):
+        raise ValueError("every chain's initial parameters must flatten to the same length")
+    theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+    off, t, y, has = pmmh_fleet_pack(datas, S)
+    model = unparam.run(inits[0])
+    desc = model.descriptor()
+    own = fleet is None
+    if own:
+        try:
+            fleet = NativePfFleet(model, n, S, device)
+        except _abi.CssmError as e:
+            if e.code in (_abi.CSSM_EINVAL_ARG, _abi.CSSM_EINVAL_DESC):
+                raise _abi.CssmError(e.code, f"{e.args[0]}; cssm_pmmh_run_batched (pmmh_native_batched) serves the chains a fleet does not") from None
+            raise
+    elif fleet.S != S or fleet.n != int(n):
+        raise ValueError(f"the fleet holds {fleet.S} series of {fleet.n} particles, the run needs {S} of {n}")
+    try:
+        nt = theta0.shape[1]
+        ll = np.zeros((S, iters)); th = np.zeros((S, iters, nt)); acc = np.zeros((S, iters), dtype=np.int32); last = np.zeros((S, iters, fleet.d))
+        sd = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
+        dp, u64 = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        fleet.generation += 1
+        _abi.check(fleet.lib.cssm_fleet_pmmh_run(fleet._h, desc.ptr(), theta0.ctypes.data_as(dp), nt, float(delta), off.ctypes.data_as(u64),
+                                                 t.ctypes.data_as(dp), y.ctypes.data_as(dp), has.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 sd.ctypes.data_as(u64), int(iters), ll.ctypes.data_as(dp), th.ctypes.data_as(dp),
+                                                 acc.ctypes.data_as(C.POINTER(C.c_int32)), last.ctypes.data_as(dp)))
+    finally:
+        if own:
+            fleet.close()
     return ll, th, acc, last
 
 

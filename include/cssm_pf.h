@@ -765,8 +765,7 @@ int cssm_model_structure(const cssm_model_desc* desc, uint32_t* words_out, int32
  * CSSM_EINVAL_DESC and a message naming the reason and the entry points that do serve it (cssm_pf_*, cssm_pfb_*); a fleet call
  * never degenerates into S single-handle runs.  Thread-affinity and device rules as for every entry point: each call selects the
  * fleet's device; the fleet owns a non-blocking stream; a fleet is not re-entrant.
- * Not here: `filter`'s sampled path and posterior-predictive forecasts from a fleet, sharded fleets, other resamplers
- * (INTEGRATION.md). */
+ * Not here: posterior-predictive forecasts from a fleet, sharded fleets, other resamplers. */
 typedef struct cssm_fleet cssm_fleet;
 /* 12 bytes of LDS per particle (weight 8, ancestor 4) + 7.3 KB per block: 55.3 KB at 4096, two blocks per CU of 160 KiB; the summary
  * kernel sorts a row of at most 4096 keys (32 KiB) in LDS. */
@@ -800,6 +799,42 @@ int cssm_fleet_set_option(cssm_fleet* f, int option, int value);
  * afterwards as a handle does after cssm_pf_ll_filter. */
 int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
                          double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out);
+
+/* filter (model/ParticleFilter.scala:152-158) of every series: cssm_fleet_ll_filter -- the same arguments, the same ll_out / ll_t /
+ * ess_t / rc_out, the same cloud, ancestors, clock and observation index left behind (the fleet continues with cssm_fleet_step) -- and
+ * the sampled path (Resampling.sampleOne, model/Resampling.scala:151-154), recorded by the series' own workgroup inside the one launch.
+ *   path_out (may be NULL): series k owns rows off[k] + k .. off[k+1] + k, T_k + 1 rows of d doubles (off[S] + S rows in all).  Row 0
+ *     is the initial cloud's particle at slot abs((int32)Philox(seed_k, 0, 0, CSSM_STREAM_PICK, 0).v[0]) % N, row s + 1 the resampled
+ *     particle at the record's pick after observation s (identity ancestors behind an observation without a datum).
+ *   last_out (may be NULL): [S][d], row T_k of series k's path -- what a Metropolis chain keeps.  With last_out alone the device keeps
+ *     and the host reads S x d doubles, not the paths.
+ * Per series every result is bit for bit cssm_pf_reseed + cssm_pf_filter on a handle of its own.  At least one of path_out and last_out
+ * must be given: with neither the call is CSSM_EINVAL_ARG and names cssm_fleet_ll_filter.  Errors as cssm_fleet_ll_filter; a series that
+ * fails with CSSM_ENONFINITE keeps the rows recorded before the failing observation (rows 0 .. s for a failure at observation s), its
+ * later rows and its last_out row read NaN; a series with no records (CSSM_EINVAL_ARG) has NaN in its single row; no other series
+ * notices either.  Null off / ll_out / rc_out / data, both outputs NULL and off[0] != 0 are refused before the fleet is looked at. */
+int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                      double* ll_out, double* ll_t, int32_t* ess_t, double* path_out, double* last_out, int* rc_out);
+
+/* ParticleMetropolisHastings (model/PMMH.scala:68-81,114-123; examples/DetermineParameters.scala) for S chains in lockstep, a chain
+ * per series, ONE launch per iteration: chain k starts at theta0[k * n_theta ..], runs under seeds[k] and sees series k's slice of the
+ * data (off / t / y / has_obs as cssm_fleet_ll_filter; the slices may repeat one data set or differ per sensor).  Per iteration:
+ * cssm_pmmh_run's proposal and filter key for every chain, cssm_fleet_set_params, cssm_fleet_reseed, one cssm_fleet_filter with
+ * last_out only, cssm_pmmh_run's decision for every chain; a chain whose filter is CSSM_ENONFINITE is rejected (ll' = -inf), any other
+ * status ends the run with it.  Outputs chain-major as cssm_pmmh_run_batched: ll[k * n_iters + it], theta[(k * n_iters + it) * n_theta
+ * + j], accepted[...], last_state[(k * n_iters + it) * d + j].  Chain k is bit for bit cssm_pmmh_run(handle of N particles, theta0[k],
+ * its slice, seeds[k]).  The fleet's parameters and keys are those of the last iteration afterwards.
+ * Refused: null arguments, off[0] != 0, an LGCP descriptor (CSSM_EINVAL_DESC), n_theta that is not the descriptor's -- all before the
+ * fleet is looked at --, off decreasing, an empty slice (CSSM_EINVAL_ARG, before the first iteration), a descriptor of another
+ * structure than the fleet's (CSSM_EINVAL_DESC).  What a fleet does not hold (LGCP, other resamplers, N > CSSM_FLEET_MAX_N) is refused
+ * at cssm_fleet_create / _set_option as ever; cssm_pmmh_run_batched serves those. */
+int cssm_fleet_pmmh_run(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, size_t n_theta, double delta,
+                        const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                        const uint64_t* seeds, size_t n_iters,
+                        double* ll, double* theta, int32_t* accepted, double* last_state);
+/* Where the last cssm_fleet_pmmh_run spent its time, milliseconds summed over its iterations: ms6[0] proposals + set_params + reseed
+ * (host), [1] record building (host), [2] upload and [3] kernel (HIP events), [4] decisions (host); ms6[5] = the iterations counted. */
+int cssm_fleet_pmmh_last_split(cssm_fleet* f, double* ms6);
 
 /* initialiseState + stepFilter (:105-132).  cssm_fleet_init draws every series' cloud at its own t0[k].  cssm_fleet_step advances
  * the series with active[k] != 0 (active NULL = every series) by one observation (t[k], y[k], has_obs[k]; has_obs NULL = all 1): the
@@ -851,7 +886,7 @@ int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const double* t, con
 /* Observations series k's current cloud has seen (the Philox counter word of its next step); 0 for a null fleet or k >= S, the
  * convention of cssm_pf_observation_index. */
 uint64_t cssm_fleet_observation_index(const cssm_fleet* f, uint32_t k);
-/* ms3[0] = device time of the last ll_filter / init / step call (upload, launch, read-back), ms3[1] = of the last summary, ms3[2] =
+/* ms3[0] = device time of the last ll_filter / filter / init / step call (upload, launch, read-back), ms3[1] = of the last summary, ms3[2] =
  * of the last forecast; HIP events on the fleet's stream, < 0 while there was none.  The array holds THREE doubles. */
 int cssm_fleet_last_ms(cssm_fleet* f, double* ms3);
 /* Diagnostic, no device: the compact per-observation record the fleet uploads for (t_prev, t, y, has_obs, step) under `desc`,
