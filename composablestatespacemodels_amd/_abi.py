@@ -184,6 +184,8 @@ SYMBOLS = [
     ("cssm_fleet_get_ancestors", C.c_int, [_h, C.c_uint32, _u32p]),
     ("cssm_fleet_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_forecast", C.c_int, [_h, _u64p, _dp, _u64p, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    ("cssm_fleet_forecast_posterior", C.c_int, [_h, _descp, _u64p, _dp, C.c_size_t, _dp, _dp, _u64p, _dp, _u32p, _u64p, C.c_double,
+                                                _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p, C.POINTER(C.c_int)]),
     ("cssm_fleet_observation_index", C.c_uint64, [_h, C.c_uint32]),
     ("cssm_fleet_pack_record", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32,
                                          _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -627,11 +627,124 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
 // A call that returns samples runs the fleet in chunks of series whose samples fit fc_samp_max -- never chunks of horizons: a series
 // is one block's work.  What a series' own arguments spoil is the series' own: its status, NaN in its outputs, no block for it.
 static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
+
+// the grow-only buffers of both forecasts: `need` bytes of d_fc and of its pinned mirror, 16 N bytes of eta / obs staging per series
+static int fleet_fc_ensure(cssm_fleet* f, size_t need) {
+  if (need > f->h_fc_cap) {
+    if (f->h_fc) (void)hipHostFree(f->h_fc);
+    f->h_fc = nullptr; f->h_fc_cap = 0;
+    if (hipHostMalloc((void**)&f->h_fc, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of pinned staging", need);
+    f->h_fc_cap = need + need / 4;
+  }
+  if (need > f->fc_cap) {
+    if (f->d_fc) (void)hipFree(f->d_fc);
+    f->d_fc = nullptr; f->fc_cap = 0;
+    if (hipMalloc(&f->d_fc, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of records and results", need);
+    f->fc_cap = need + need / 4;
+  }
+  if (!f->d_fc_stage && hipMalloc(&f->d_fc_stage, (size_t)f->S * 2u * f->n * 8u) != hipSuccess) {
+    f->d_fc_stage = nullptr;
+    return fail(CSSM_ENOMEM, "fleet forecast: 16 N bytes of staging per series");
+  }
+  return CSSM_OK;
+}
+
+// chunks of series [cut[c], cut[c + 1]): all of them, or (samples) as many as fit the cap -- one series at least; the device buffer
+// of one chunk's samples
+static int fleet_fc_cuts(cssm_fleet* f, const uint64_t* off, bool samples, std::vector<uint32_t>& cut) {
+  const uint32_t S = f->S;
+  const size_t samp_row = (size_t)(f->d + 3) * f->n * 8u;
+  cut.assign(1, 0u);
+  if (!samples) { cut.push_back(S); return CSSM_OK; }
+  const size_t cap_rows = std::max<size_t>(1, f->fc_samp_max / samp_row);
+  size_t most = 0;
+  for (uint32_t k = 0; k < S; ++k)
+    if ((size_t)(off[k + 1] - off[cut.back()]) > cap_rows && k > cut.back()) cut.push_back(k);
+  cut.push_back(S);
+  for (size_t c = 0; c + 1 < cut.size(); ++c) most = std::max<size_t>(most, (size_t)(off[cut[c + 1]] - off[cut[c]]));
+  if (most * samp_row > f->fc_samp_cap) {
+    if (f->d_fc_samp) (void)hipFree(f->d_fc_samp);
+    f->d_fc_samp = nullptr; f->fc_samp_cap = 0;
+    if (hipMalloc(&f->d_fc_samp, most * samp_row) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of samples", most * samp_row);
+    f->fc_samp_cap = most * samp_row;
+  }
+  return CSSM_OK;
+}
+
+// what every launch of either forecast kernel shares: sizes, ranks, the way to a row's order statistics, the fleet's buffers
+static void fleet_fc_args(const cssm_fleet* f, double interval, FleetFcLaunch& l) {
+  const uint32_t n = f->n;
+  SelState rs, re;
+  sel_ranks(rs, n, interval, true);
+  sel_ranks(re, n, interval, false);
+  l.args.n = n; l.args.np2 = 2u;
+  while (l.args.np2 < n) l.args.np2 <<= 1;
+  l.args.select = f->fc_select ? (uint32_t)(f->fc_select == 2) : (uint32_t)(n >= CSSM_FLEET_SELECT_MIN_N);
+  l.args.state = f->state; l.args.anc = f->anc;
+  l.args.stage = f->d_fc_stage;
+  l.args.logtab = f->logtab; l.args.mk = f->base.mk;
+  l.args.lo_state = (uint32_t)rs.rank[0]; l.args.hi_state = (uint32_t)rs.rank[1];
+  l.args.lo_eta = (uint32_t)re.rank[0]; l.args.hi_eta = (uint32_t)re.rank[1];
+  l.d = f->d; l.threads = f->threads; l.stream = f->stream;
+}
+
+// the results [R][d + 2][3] into the caller's arrays; a series whose status is not zero reads NaN
+static void fleet_fc_scatter(const cssm_fleet* f, const uint64_t* off, const double* h_out, const int* rc_out, double* state_mean, double* state_lower,
+                             double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
+                             double* obs_upper, double* samples) {
+  const uint32_t n = f->n;
+  const int d = f->d, rows = d + 2;
+  for (uint32_t k = 0; k < f->S; ++k) {
+    const bool ok = rc_out[k] == CSSM_OK;
+    for (size_t r = (size_t)off[k]; r < (size_t)off[k + 1]; ++r) {
+      const double* o = h_out + r * (size_t)rows * 3u;
+      auto at = [&](int row, int q) { return ok ? o[3 * row + q] : cssm_nan(); };
+      for (int c = 0; c < d; ++c) {
+        if (state_mean) state_mean[r * d + c] = at(c, 0);
+        if (state_lower) state_lower[r * d + c] = at(c, 1);
+        if (state_upper) state_upper[r * d + c] = at(c, 2);
+      }
+      if (eta_mean) eta_mean[r] = at(d, 0);
+      if (eta_lower) eta_lower[r] = at(d, 1);
+      if (eta_upper) eta_upper[r] = at(d, 2);
+      if (obs_mean) obs_mean[r] = at(d + 1, 0);
+      if (obs_lower) obs_lower[r] = at(d + 1, 1);
+      if (obs_upper) obs_upper[r] = at(d + 1, 2);
+      if (samples && !ok) std::fill(samples + r * (size_t)(d + 3) * n, samples + (r + 1) * (size_t)(d + 3) * n, cssm_nan());
+    }
+  }
+}
+
+// upload `up` bytes of the staged call, run it in the chunks of series `cut` (launch(l) starts one chunk's kernel), bring the samples of
+// every chunk and the bytes [back, back + back_bytes) of d_fc home; the device time lands in ms_forecast
+template <class Launch>
+static int fleet_fc_run(cssm_fleet* f, const uint64_t* off, const std::vector<uint32_t>& cut, FleetFcLaunch& l, size_t up, size_t back, size_t back_bytes,
+                        double* samples, const char* kernel, Launch&& launch) {
+  const size_t samp_row = (size_t)(f->d + 3) * f->n * 8u;
+  HIP_TRY(hipEventRecord(f->ev[4], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->d_fc, f->h_fc, up, hipMemcpyHostToDevice, f->stream));
+  for (size_t c = 0; c + 1 < cut.size(); ++c) {
+    const size_t ra = (size_t)off[cut[c]], rb = (size_t)off[cut[c + 1]];
+    if (rb == ra) continue;
+    l.args.k0 = cut[c]; l.n_series = cut[c + 1] - cut[c];
+    l.args.samples = samples ? f->d_fc_samp : nullptr; l.args.samp_r0 = ra;
+    const int hrc = launch(l);
+    if (hrc) return fail(CSSM_EHIP, "%s: %s", kernel, hipGetErrorString((hipError_t)hrc));
+    if (samples) HIP_TRY(hipMemcpyAsync(samples + ra * (size_t)(f->d + 3) * f->n, f->d_fc_samp, (rb - ra) * samp_row, hipMemcpyDeviceToHost, f->stream));
+    if (samples && c + 2 < cut.size()) HIP_TRY(hipStreamSynchronize(f->stream));   // (the next chunk writes the same buffer)
+  }
+  HIP_TRY(hipMemcpyAsync(f->h_fc + back, f->d_fc + back, back_bytes, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipEventRecord(f->ev[5], f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  if (hipEventElapsedTime(&f->ms_forecast, f->ev[4], f->ev[5]) != hipSuccess) f->ms_forecast = -1.f;
+  return CSSM_OK;
+}
+
 extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const double* t, const uint64_t* keys, double interval,
                                    double* state_mean, double* state_lower, double* state_upper, double* eta_mean, double* eta_lower,
                                    double* eta_upper, double* obs_mean, double* obs_lower, double* obs_upper, double* samples, int* rc_out) {
   if (!f || !off || !t || !keys || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
-  const uint32_t S = f->S, n = f->n;
+  const uint32_t S = f->S;
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
   for (uint32_t k = 0; k < S; ++k)
     if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
@@ -650,21 +763,9 @@ extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const dou
   const size_t o_keys = ((size_t)S + 1u) * 8u, o_op = o_keys + (size_t)S * 8u, o_cur = o_op + (size_t)S * sizeof(cssm_obs_params);
   const size_t o_rec = o_cur + (((size_t)S * 4u + 7u) & ~(size_t)7u), o_out = o_rec + R * RB, n_out = R * (size_t)rows * 3u;
   const size_t need = o_out + n_out * 8u;
-  if (need > f->h_fc_cap) {
-    if (f->h_fc) (void)hipHostFree(f->h_fc);
-    f->h_fc = nullptr; f->h_fc_cap = 0;
-    if (hipHostMalloc((void**)&f->h_fc, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of pinned staging", need);
-    f->h_fc_cap = need + need / 4;
-  }
-  if (need > f->fc_cap) {
-    if (f->d_fc) (void)hipFree(f->d_fc);
-    f->d_fc = nullptr; f->fc_cap = 0;
-    if (hipMalloc(&f->d_fc, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of records and results", need);
-    f->fc_cap = need + need / 4;
-  }
-  if (!f->d_fc_stage && hipMalloc(&f->d_fc_stage, (size_t)S * 2u * n * 8u) != hipSuccess) {
-    f->d_fc_stage = nullptr;
-    return fail(CSSM_ENOMEM, "fleet forecast: 16 N bytes of staging per series");
+  {
+    const int erc = fleet_fc_ensure(f, need);
+    if (erc) return erc;
   }
   unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_fc);
   unsigned long long* h_keys = reinterpret_cast<unsigned long long*>(f->h_fc + o_keys);
@@ -707,81 +808,161 @@ extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const dou
     }
   });
   if (n_run) {
-    // chunks of series: all of them, or (samples) as many as fit the cap -- one series at least
-    const size_t samp_row = (size_t)(d + 3) * n * 8u;
-    std::vector<uint32_t> cut{0u};
-    if (samples) {
-      const size_t cap_rows = std::max<size_t>(1, f->fc_samp_max / samp_row);
-      size_t most = 0;
-      for (uint32_t k = 0; k < S; ++k)
-        if ((size_t)(off[k + 1] - off[cut.back()]) > cap_rows && k > cut.back()) cut.push_back(k);
-      cut.push_back(S);
-      for (size_t c = 0; c + 1 < cut.size(); ++c) most = std::max<size_t>(most, (size_t)(off[cut[c + 1]] - off[cut[c]]));
-      if (most * samp_row > f->fc_samp_cap) {
-        if (f->d_fc_samp) (void)hipFree(f->d_fc_samp);
-        f->d_fc_samp = nullptr; f->fc_samp_cap = 0;
-        if (hipMalloc(&f->d_fc_samp, most * samp_row) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of samples", most * samp_row);
-        f->fc_samp_cap = most * samp_row;
-      }
-    } else {
-      cut.push_back(S);
-    }
-    SelState rs, re;
-    sel_ranks(rs, n, interval, true);
-    sel_ranks(re, n, interval, false);
+    std::vector<uint32_t> cut;
+    int rc = fleet_fc_cuts(f, off, samples != nullptr, cut);
+    if (rc) return rc;
     FleetFcLaunch l;
-    l.args.n = n; l.args.np2 = 2u;
-    while (l.args.np2 < n) l.args.np2 <<= 1;
-    l.args.select = f->fc_select ? (uint32_t)(f->fc_select == 2) : (uint32_t)(n >= CSSM_FLEET_SELECT_MIN_N);
-    l.args.state = f->state; l.args.anc = f->anc;
+    fleet_fc_args(f, interval, l);
     l.args.off = reinterpret_cast<const unsigned long long*>(f->d_fc);
     l.args.keys = reinterpret_cast<const unsigned long long*>(f->d_fc + o_keys);
     l.args.op = reinterpret_cast<const cssm_obs_params*>(f->d_fc + o_op);
     l.args.cur = reinterpret_cast<const uint32_t*>(f->d_fc + o_cur);
     l.args.recs = f->d_fc + o_rec;
-    l.args.stage = f->d_fc_stage;
     l.args.out = reinterpret_cast<double*>(f->d_fc + o_out);
-    l.args.logtab = f->logtab; l.args.mk = f->base.mk;
-    l.args.lo_state = (uint32_t)rs.rank[0]; l.args.hi_state = (uint32_t)rs.rank[1];
-    l.args.lo_eta = (uint32_t)re.rank[0]; l.args.hi_eta = (uint32_t)re.rank[1];
-    l.d = d; l.threads = f->threads; l.stream = f->stream;
-    HIP_TRY(hipEventRecord(f->ev[4], f->stream));
-    HIP_TRY(hipMemcpyAsync(f->d_fc, f->h_fc, o_out, hipMemcpyHostToDevice, f->stream));
-    for (size_t c = 0; c + 1 < cut.size(); ++c) {
-      const size_t ra = (size_t)off[cut[c]], rb = (size_t)off[cut[c + 1]];
-      if (rb == ra) continue;
-      l.args.k0 = cut[c]; l.n_series = cut[c + 1] - cut[c];
-      l.args.samples = samples ? f->d_fc_samp : nullptr; l.args.samp_r0 = ra;
-      const int hrc = cssm_fleet_forecast_launch(l);
-      if (hrc) return fail(CSSM_EHIP, "k_fleet_forecast: %s", hipGetErrorString((hipError_t)hrc));
-      if (samples) HIP_TRY(hipMemcpyAsync(samples + ra * (size_t)(d + 3) * n, f->d_fc_samp, (rb - ra) * samp_row, hipMemcpyDeviceToHost, f->stream));
-      if (samples && c + 2 < cut.size()) HIP_TRY(hipStreamSynchronize(f->stream));   // (the next chunk writes the same buffer)
-    }
-    HIP_TRY(hipMemcpyAsync(f->h_fc + o_out, f->d_fc + o_out, n_out * 8u, hipMemcpyDeviceToHost, f->stream));
-    HIP_TRY(hipEventRecord(f->ev[5], f->stream));
-    HIP_TRY(hipStreamSynchronize(f->stream));
-    if (hipEventElapsedTime(&f->ms_forecast, f->ev[4], f->ev[5]) != hipSuccess) f->ms_forecast = -1.f;
+    rc = fleet_fc_run(f, off, cut, l, o_out, o_out, n_out * 8u, samples, "k_fleet_forecast", [](const FleetFcLaunch& q) { return cssm_fleet_forecast_launch(q); });
+    if (rc) return rc;
   }
-  for (uint32_t k = 0; k < S; ++k) {
-    const bool ok = rc_out[k] == CSSM_OK;
-    for (size_t r = (size_t)off[k]; r < (size_t)off[k + 1]; ++r) {
-      const double* o = h_out + r * (size_t)rows * 3u;
-      auto at = [&](int row, int q) { return ok ? o[3 * row + q] : cssm_nan(); };
-      for (int c = 0; c < d; ++c) {
-        if (state_mean) state_mean[r * d + c] = at(c, 0);
-        if (state_lower) state_lower[r * d + c] = at(c, 1);
-        if (state_upper) state_upper[r * d + c] = at(c, 2);
-      }
-      if (eta_mean) eta_mean[r] = at(d, 0);
-      if (eta_lower) eta_lower[r] = at(d, 1);
-      if (eta_upper) eta_upper[r] = at(d, 2);
-      if (obs_mean) obs_mean[r] = at(d + 1, 0);
-      if (obs_lower) obs_lower[r] = at(d + 1, 1);
-      if (obs_upper) obs_upper[r] = at(d + 1, 2);
-      if (samples && !ok) std::fill(samples + r * (size_t)(d + 3) * n, samples + (r + 1) * (size_t)(d + 3) * n, cssm_nan());
-    }
-  }
+  fleet_fc_scatter(f, off, h_out, rc_out, state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, samples);
   if (!scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", scale_msg.c_str());   // (the call succeeds; the message names the first such series)
+  return CSSM_OK;
+}
+
+// SimulateData.forecast(unparamModel, t, n)(posterior) + summariseForecast of every series under its OWN joint posterior sample
+// (cssm_pf_forecast_posterior per series): the rows of every series validated and constraint-transformed by cssm_posterior_rows on a
+// few host threads, then one upload (offsets, keys, buffer numbers, records, states, rows, the caller's picks), one launch per chunk
+// of series (k_fleet_forecast_post), one read-back (the picks, the results).  The fleet lends its device, stream, contract table, N,
+// structure and scratch -- the state buffer of a series that does not hold its cloud among it; nothing it keeps per series changes.
+extern "C" int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_desc* desc, const uint64_t* moff, const double* theta, size_t n_theta,
+                                             const double* x, const double* t0, const uint64_t* off, const double* t, const uint32_t* pick,
+                                             const uint64_t* keys, double interval, double* state_mean, double* state_lower, double* state_upper,
+                                             double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
+                                             double* obs_upper, double* samples, uint32_t* pick_out, int* rc_out) {
+  if (!f || !desc || !moff || !theta || !x || !t0 || !off || !t || !keys || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  const uint32_t S = f->S, n = f->n;
+  if (moff[0] != 0) return fail(CSSM_EINVAL_ARG, "moff[0] must be 0");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  for (uint32_t k = 0; k < S; ++k) {
+    if (moff[k + 1] < moff[k]) return fail(CSSM_EINVAL_ARG, "moff must be non-decreasing (moff[%u] = %llu > moff[%u] = %llu)", k,
+                                           (unsigned long long)moff[k], k + 1, (unsigned long long)moff[k + 1]);
+    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
+                                         k + 1, (unsigned long long)off[k + 1]);
+  }
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (!desc->leaves || desc->n_leaves < 1) return fail(CSSM_EINVAL_DESC, "null model descriptor");
+  {   // the structure (an LGCP descriptor is never a fleet's) and the length of a row: no rows looked at
+    const int rc = cssm_posterior_rows_into(&f->base, desc, theta, n_theta, 0, nullptr);
+    if (rc) return rc;
+  }
+  const size_t R = (size_t)off[S], Mtot = (size_t)moff[S];
+  const int d = f->d, rows = d + 2;
+  const size_t RS = 3 * (size_t)d + 1, RB = CSSM_FLEET_REC_BYTES(d);
+  HIP_TRY(hipSetDevice(f->device));
+  // layout: [off | keys | moff | buffer numbers | records | x | rows | picks | results]; the caller's picks are uploaded, the drawn
+  // ones only read back
+  const size_t o_keys = ((size_t)S + 1u) * 8u, o_moff = o_keys + (size_t)S * 8u, o_cur = o_moff + ((size_t)S + 1u) * 8u;
+  const size_t o_rec = o_cur + (((size_t)S * 4u + 7u) & ~(size_t)7u), o_x = o_rec + R * RB, o_rows = o_x + Mtot * (size_t)d * 8u;
+  const size_t o_pick = o_rows + Mtot * RS * 8u, o_out = o_pick + (((size_t)S * n * 4u + 7u) & ~(size_t)7u), n_out = R * (size_t)rows * 3u;
+  const size_t need = o_out + n_out * 8u;
+  int rc = fleet_fc_ensure(f, need);
+  if (rc) return rc;
+  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_fc);
+  unsigned long long* h_keys = reinterpret_cast<unsigned long long*>(f->h_fc + o_keys);
+  unsigned long long* h_moff = reinterpret_cast<unsigned long long*>(f->h_fc + o_moff);
+  uint32_t* h_cur = reinterpret_cast<uint32_t*>(f->h_fc + o_cur);
+  unsigned char* h_recs = f->h_fc + o_rec;
+  double* h_x = reinterpret_cast<double*>(f->h_fc + o_x);                  // (a series' states are copied here once they are known finite)
+  double* h_rows = reinterpret_cast<double*>(f->h_fc + o_rows);
+  uint32_t* h_pick = reinterpret_cast<uint32_t*>(f->h_fc + o_pick);
+  const double* h_out = reinterpret_cast<const double*>(f->h_fc + o_out);
+  for (uint32_t k = 0; k <= S; ++k) { h_off[k] = off[k]; h_moff[k] = moff[k]; }
+  if (pick) memcpy(h_pick, pick, (size_t)S * n * 4u);
+  // the series' own statuses (what cssm_pf_forecast_posterior refuses, in its order); the message of each as its thread left it
+  cssm_obs_params op;
+  std::string scale_msg;
+  const bool no_scale = cssm_obs_params_or_fail(f->base.obs_kind, desc->leaves[0].has_scale, desc->leaves[0].scale, f->base.obs_df, &op) != 0;
+  if (no_scale) scale_msg = cssm_last_error();
+  std::vector<std::string> msg(S);
+  fleet_parallel(S, Mtot + R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t ha = (size_t)off[k], hb = (size_t)off[k + 1], ma = (size_t)moff[k], M = (size_t)moff[k + 1] - ma;
+      h_keys[k] = keys[k]; h_cur[k] = 0xffffffffu; rc_out[k] = CSSM_OK;
+      auto refuse = [&](const std::string& why) { rc_out[k] = CSSM_EINVAL_ARG; msg[k] = why; };
+      if (M == 0) {
+        if (hb > ha) refuse("the posterior sample is empty (M = 0)");
+        continue;
+      }
+      if (M > 0xffffffffull) { refuse("the posterior sample has more than 2^32 - 1 rows"); continue; }
+      if (hb - ha > 0xffffffffull) { refuse("too many horizons"); continue; }
+      if (!std::isfinite(t0[k])) { refuse("t0 is not finite"); continue; }
+      if (no_scale) { refuse(scale_msg); continue; }             // (with or without horizons, as the single handle)
+      if (cssm_posterior_rows_into(&f->base, desc, theta + ma * n_theta, n_theta, M, h_rows + ma * RS)) { refuse(cssm_last_error()); continue; }
+      const double* xs = x + ma * (size_t)d;
+      for (size_t m = 0; m < M && !rc_out[k]; ++m)
+        for (int c = 0; c < d; ++c)
+          if (!std::isfinite(xs[m * d + c])) { refuse("x row " + std::to_string(m) + ": component " + std::to_string(c) + " is not finite"); break; }
+      if (rc_out[k]) continue;
+      memcpy(h_x + ma * (size_t)d, xs, M * (size_t)d * 8u);
+      if (pick)
+        for (uint32_t i = 0; i < n; ++i)
+          if (pick[(size_t)k * n + i] >= M) {
+            refuse("pick[" + std::to_string(i) + "] = " + std::to_string(pick[(size_t)k * n + i]) + " is not below M = " + std::to_string(M));
+            break;
+          }
+      if (rc_out[k]) continue;
+      double prev = t0[k];
+      for (size_t s = ha; s < hb; ++s) {
+        if (!std::isfinite(t[s])) { refuse("t[" + std::to_string(s - ha) + "] is not finite"); break; }
+        if (!(t[s] >= prev)) { refuse(s > ha ? "t must be non-decreasing" : "t[0] is before t0"); break; }
+        prev = t[s];
+      }
+      if (rc_out[k] || hb == ha) continue;
+      h_cur[k] = f->live[k] ? (f->step[k] & 1u) : 0u;          // the cloud's buffer is only named to be avoided; without a cloud both are free
+      double tp = t0[k];
+      for (size_t s = ha; s < hb; ++s) {
+        fleet_pack_rec(f->models[k], tp, t[s], 0.0, 0, (uint32_t)(s - ha), h_recs + s * RB);
+        tp = t[s];
+      }
+    }
+  });
+  size_t n_run = 0;
+  for (uint32_t k = 0; k < S; ++k)
+    if (h_cur[k] <= 1u) n_run += (size_t)(off[k + 1] - off[k]);
+  if (n_run) {
+    std::vector<uint32_t> cut;
+    rc = fleet_fc_cuts(f, off, samples != nullptr, cut);
+    if (rc) return rc;
+    FleetFcLaunch l;
+    fleet_fc_args(f, interval, l);
+    l.args.off = reinterpret_cast<const unsigned long long*>(f->d_fc);
+    l.args.keys = reinterpret_cast<const unsigned long long*>(f->d_fc + o_keys);
+    l.args.op = nullptr;
+    l.args.cur = reinterpret_cast<const uint32_t*>(f->d_fc + o_cur);
+    l.args.recs = f->d_fc + o_rec;
+    l.args.out = reinterpret_cast<double*>(f->d_fc + o_out);
+    FleetFcPost q;
+    q.moff = reinterpret_cast<const unsigned long long*>(f->d_fc + o_moff);
+    q.x = reinterpret_cast<const double*>(f->d_fc + o_x);
+    q.rows = reinterpret_cast<const double*>(f->d_fc + o_rows);
+    q.picks = reinterpret_cast<uint32_t*>(f->d_fc + o_pick);
+    q.draw = pick ? 0u : 1u;
+    q.obs_df = f->base.obs_df;
+    const size_t back = pick_out && !pick ? o_pick : o_out;
+    rc = fleet_fc_run(f, off, cut, l, pick ? o_out : o_pick, back, need - back, samples, "k_fleet_forecast_post",
+                      [&](const FleetFcLaunch& ll) { return cssm_fleet_forecast_post_launch(ll, q); });
+    if (rc) return rc;
+  }
+  fleet_fc_scatter(f, off, h_out, rc_out, state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, samples);
+  if (pick_out)   // a series that ran: what its block used; one without horizons: the same picks, formed here; a refused or empty one: zeros
+    for (uint32_t k = 0; k < S; ++k) {
+      uint32_t* po = pick_out + (size_t)k * n;
+      const uint64_t M = moff[k + 1] - moff[k];
+      if (rc_out[k] || M == 0) { std::fill(po, po + n, 0u); continue; }
+      if (pick) { memcpy(po, pick + (size_t)k * n, (size_t)n * 4u); continue; }
+      if (h_cur[k] <= 1u) { memcpy(po, h_pick + (size_t)k * n, (size_t)n * 4u); continue; }
+      for (uint32_t i = 0; i < n; ++i) po[i] = cssm_posterior_pick(keys[k], i, M);
+    }
+  for (uint32_t k = 0; k < S; ++k)   // (the call succeeds; the message names the first refused series)
+    if (rc_out[k]) { (void)fail(CSSM_EINVAL_ARG, "series %u: %s", k, msg[k].c_str()); break; }
   return CSSM_OK;
 }
 

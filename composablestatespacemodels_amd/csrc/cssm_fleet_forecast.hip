@@ -1,27 +1,41 @@
-// cssm_fleet_forecast.hip -- forecasts of every series of a fleet in ONE launch (include/cssm_pf.h: cssm_fleet_forecast): the scan of
-// SimulateData.forecast + summariseForecast (model/Data.scala:196-231, model/ParticleFilter.scala:368-409) per series, ONE WORKGROUP PER
-// SERIES as k_fleet_series.  A block runs the whole chain of its series' horizons: nothing of a series crosses a block -- no atomics on
-// global memory, no flag another block reads, no cooperative launch; every loop is bounded by N or by the series' horizons.
+// cssm_fleet_forecast.hip -- forecasts of every series of a fleet in ONE launch (include/cssm_pf.h: cssm_fleet_forecast,
+// cssm_fleet_forecast_posterior): the scan of SimulateData.forecast + summariseForecast (model/Data.scala:196-231,
+// model/ParticleFilter.scala:368-409) per series, ONE WORKGROUP PER SERIES as k_fleet_series.  A block runs the whole chain of its
+// series' horizons: nothing of a series crosses a block -- no atomics on global memory, no flag another block reads, no cooperative
+// launch; every loop is bounded by N or by the series' horizons.
 //
-// Every arithmetic statement is the existing device function, so a series has the bits of cssm_pf_forecast on a handle of its own:
-// propagate_pair / propagate_one (the paired CSSM_STREAM_STEP streams under the forecast's key at step h), gamma_of, link_of,
-// cssm_obs_draw_one on cssm_obs_stream_at (CSSM_STREAM_OBS), cssm_order_key; the ranks are sel_ranks' (the host passes them).  The order
-// statistics of a row are exact either way: k_fleet_summary's bitonic network over the row's keys in LDS, or (FleetFcArgs::select) a
-// radix select over them in LDS, the single handle's k_sel_hist / k_sel_pick in one block; the means are plain fp64 sums.
+// All of that is fleet_forecast_body<D, Src>, written once.  The two kernels are entry points that fill a source and call it:
+// k_fleet_forecast<D> with FleetCloudSrc (the series' cloud through its ancestors, moved under the series' records) and
+// k_fleet_forecast_post<D> with FleetPostSrc (a pair of the series' posterior sample per particle: its state, its own parameters).
+// A source says where a pair starts, what moves it one step and which observation parameters each particle draws with -- the split
+// of forecast_body<D, Src> (cssm_forecast.hip) for the single handle.
 //
-// Where the operands live.  Horizon 0 gathers the series' cloud (buffer step & 1 through its ancestors); the states between horizons
-// live in the series' OTHER state buffer, which is free between calls -- the next record of k_fleet_series overwrites all of it before
-// anything reads it.  A thread always owns the same particle pairs, so it updates them in place without a barrier.  eta and the
-// observation draw of a horizon are staged in 2 N doubles of per-series scratch (written and read by the same block), so the block's
-// LDS holds one row of keys only and as many blocks fit a CU as k_fleet_summary's.
+// Every arithmetic statement is the existing device function, so a series has the bits of cssm_pf_forecast /
+// cssm_pf_forecast_posterior on a handle of its own: propagate_pair / propagate_one, or post_step (cssm_posterior_move.hip.h) -- the
+// paired CSSM_STREAM_STEP streams under the forecast's key at step h --, gamma_of, link_of, cssm_obs_draw_one on cssm_obs_stream_at
+// (CSSM_STREAM_OBS), cssm_order_key; the ranks are sel_ranks' (the host passes them).  The order statistics of a row are exact either
+// way: k_fleet_summary's bitonic network over the row's keys in LDS, or (FleetFcArgs::select) a radix select over them in LDS, the
+// single handle's k_sel_hist / k_sel_pick in one block; the means are plain fp64 sums.
+//
+// Where the operands live.  Horizon 0 gathers from the source (the series' cloud in buffer step & 1 through its ancestors, or the
+// posterior states x[pick_i]); the states between horizons live in the series' OTHER state buffer, which is free between calls -- the
+// next record of k_fleet_series overwrites all of it before anything reads it (a series without a cloud lends buffer 1).  A thread
+// always owns the same particle pairs, so it updates them in place without a barrier.  eta and the observation draw of a horizon are
+// staged in 2 N doubles of per-series scratch (written and read by the same block), so the block's LDS holds one row of keys only and
+// as many blocks fit a CU as k_fleet_summary's.
 #include <hip/hip_runtime.h>
 
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
+#include "cssm_posterior_move.hip.h"
 #include "cssm_fleet_forecast.hip.h"
 
-template <int D>
-__global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_forecast(const FleetFcArgs a) {
+// What the two fleet forecasts share -- everything but where a pair starts and what moves it.  A source `s` answers: series (what it
+// needs of series k before the first horizon), pair (what it needs of the pair (ia, ib) at a horizon, before any load), x0 (the pair's
+// states before the first horizon), step (one transition of the pair, or of its first particle alone) and obs (the observation
+// parameters particle b of the pair draws with).
+template <int D, class Src>
+__device__ __forceinline__ void fleet_forecast_body(const FleetFcArgs& a, Src& s) {
   extern __shared__ unsigned long long s_keys[];
   __shared__ StepRec s_rec;
   __shared__ double s_p[CSSM_FLEET_MAX_THREADS / 64];
@@ -34,11 +48,9 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   if (r0 >= r1 || cur > 1u) return;                            // (uniform) no horizons, or the host refused the series: untouched
   const double* tab = stage_log_table(a.logtab);
   const uint64_t key = a.keys[k];
-  const cssm_obs_params op = a.op[k];
   double* st = a.state + (size_t)k * 2u * D * n;
-  const double* src = st + (size_t)cur * D * n;                // the cloud: only read
   double* wrk = st + (size_t)(cur ^ 1u) * D * n;               // the states between horizons
-  const uint32_t* ganc = a.anc + (size_t)k * n;
+  s.series(a, k, st + (size_t)cur * D * n);
   double* stage = a.stage + (size_t)k * 2u * n;                // eta[n], obs[n] of the horizon at hand
   const uint32_t npairs = (n + 1u) / 2u, nw = bs >> 6;
   constexpr uint32_t RB = (uint32_t)CSSM_FLEET_REC_BYTES(D);
@@ -65,21 +77,19 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
       const uint32_t ia = 2u * p, ib = ia + 1u;
       const bool hasb = ib < n;
       double xa[D], xb[D];
+      s.pair(first, hasb, ia, ib, key);
       if (first) {
-        const uint32_t ja = ganc[ia], jb = hasb ? ganc[ib] : 0u;
-#pragma unroll
-        for (int c = 0; c < D; ++c) { xa[c] = src[(size_t)c * n + ja]; xb[c] = hasb ? src[(size_t)c * n + jb] : 0.0; }
+        s.x0(hasb, ia, ib, n, xa, xb);
       } else {
 #pragma unroll
         for (int c = 0; c < D; ++c) { xa[c] = wrk[(size_t)c * n + ia]; xb[c] = hasb ? wrk[(size_t)c * n + ib] : 0.0; }
       }
-      if (hasb) propagate_pair<D>(a.mk, rec, rec->dt, key, (uint64_t)ia, h, tab, xa, xb);
-      else propagate_one<D>(a.mk, rec, rec->dt, key, (uint64_t)ia, h, tab, xa);      // (the unpaired last particle of an odd cloud)
+      s.step(hasb, a.mk, rec, key, (uint64_t)ia, h, tab, xa, xb);
       {
         const double ga = gamma_of<D>(a.mk, rec, xa);
         const double ea = link_of(a.mk.obs_kind, ga);
         cssm_obs_stream sa = cssm_obs_stream_at(key, (uint64_t)ia, h);
-        const double oa = cssm_obs_draw_one(&op, ea, &sa, tab);
+        const double oa = cssm_obs_draw_one(&s.obs(0), ea, &sa, tab);
 #pragma unroll
         for (int c = 0; c < D; ++c) wrk[(size_t)c * n + ia] = xa[c];
         stage[ia] = ea; stage[n + ia] = oa;
@@ -93,7 +103,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
         const double gb = gamma_of<D>(a.mk, rec, xb);
         const double eb = link_of(a.mk.obs_kind, gb);
         cssm_obs_stream sb = cssm_obs_stream_at(key, (uint64_t)ib, h);
-        const double ob = cssm_obs_draw_one(&op, eb, &sb, tab);
+        const double ob = cssm_obs_draw_one(&s.obs(1), eb, &sb, tab);
 #pragma unroll
         for (int c = 0; c < D; ++c) wrk[(size_t)c * n + ib] = xb[c];
         stage[ib] = eb; stage[n + ib] = ob;
@@ -188,7 +198,92 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   }
 }
 
+// Source 1: the series' cloud under the series' records.  A pair is gathered through the ancestors and moves by propagate_pair (the
+// unpaired last particle of an odd cloud: propagate_one); both particles draw with the series' one set of observation parameters.
+template <int D>
+struct FleetCloudSrc {
+  const double* src; const uint32_t* ganc;
+  cssm_obs_params op;
+  __device__ __forceinline__ void series(const FleetFcArgs& a, uint32_t k, const double* cloud) {
+    op = a.op[k]; src = cloud; ganc = a.anc + (size_t)k * a.n;
+  }
+  __device__ __forceinline__ void pair(bool, bool, uint32_t, uint32_t, uint64_t) {}
+  __device__ __forceinline__ void x0(bool hasb, uint32_t ia, uint32_t ib, uint32_t n, double (&xa)[D], double (&xb)[D]) const {
+    const uint32_t ja = ganc[ia], jb = hasb ? ganc[ib] : 0u;
+#pragma unroll
+    for (int c = 0; c < D; ++c) { xa[c] = src[(size_t)c * n + ja]; xb[c] = hasb ? src[(size_t)c * n + jb] : 0.0; }
+  }
+  __device__ __forceinline__ void step(bool hasb, const ModelK& mk, const StepRec* rec, uint64_t key, uint64_t ia, uint32_t h, const double* tab,
+                                       double (&xa)[D], double (&xb)[D]) const {
+    if (hasb) propagate_pair<D>(mk, rec, rec->dt, key, ia, h, tab, xa, xb);
+    else propagate_one<D>(mk, rec, rec->dt, key, ia, h, tab, xa);      // (the unpaired last particle of an odd cloud)
+  }
+  __device__ __forceinline__ const cssm_obs_params& obs(int) const { return op; }
+};
+
+template <int D>
+__global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_forecast(const FleetFcArgs a) {
+  FleetCloudSrc<D> s;
+  fleet_forecast_body<D>(a, s);
+}
+
+// Source 2: a pair of the series' posterior sample per particle (PostSrc of cssm_forecast.hip, per series).  Series k owns the pairs
+// moff[k] .. moff[k + 1] - 1 of x (M x D) and rows (M x (3 D + 1): the parameter set, then the observation constant p0).  Particle i
+// sits on pair pick_i of its series: picks[k][i] as the host uploaded it, or (draw) cssm_posterior_pick(keys[k], i, M_k), which the
+// first horizon writes there -- the later horizons and the host read it back (a thread always owns the same pairs: no barrier).  A
+// thread serves several pairs per horizon, so a pair's parameters are loaded at every horizon; of a record only dt and the f
+// coefficients are used.
+template <int D>
+struct FleetPostSrc {
+  static constexpr size_t S = 3 * D + 1;
+  const FleetFcPost q;
+  const double* x; const double* rows; uint32_t* picks; uint32_t M;
+  cssm_obs_params opa, opb;   // (kind and df: the model's; p0: the particle's row)
+  uint32_t ma, mb;
+  PostParams<D, (D <= CSSM_FLEET_POST_REG_MAX_D)> pa, pb;
+  __device__ __forceinline__ explicit FleetPostSrc(const FleetFcPost& q_) : q(q_) {}
+  __device__ __forceinline__ void series(const FleetFcArgs& a, uint32_t k, const double*) {
+    const unsigned long long m0 = q.moff[k];
+    M = (uint32_t)(q.moff[k + 1] - m0);
+    x = q.x + (size_t)m0 * D; rows = q.rows + (size_t)m0 * S; picks = q.picks + (size_t)k * a.n;
+    opa.kind = opb.kind = a.mk.obs_kind; opa.df = opb.df = q.obs_df;
+  }
+  __device__ __forceinline__ void pair(bool first, bool hasb, uint32_t ia, uint32_t ib, uint64_t key) {
+    if (first && q.draw) {
+      ma = cssm_posterior_pick(key, (uint64_t)ia, (uint64_t)M); mb = hasb ? cssm_posterior_pick(key, (uint64_t)ib, (uint64_t)M) : 0u;
+      picks[ia] = ma;
+      if (hasb) picks[ib] = mb;
+    } else {
+      ma = picks[ia]; mb = hasb ? picks[ib] : 0u;
+    }
+    pa.load(rows + (size_t)ma * S);
+    pb.load(rows + (size_t)mb * S);
+    opa.p0 = rows[(size_t)ma * S + 3 * D];
+    opb.p0 = rows[(size_t)mb * S + 3 * D];
+  }
+  __device__ __forceinline__ void x0(bool hasb, uint32_t, uint32_t, uint32_t, double (&xa)[D], double (&xb)[D]) const {
+#pragma unroll
+    for (int c = 0; c < D; ++c) { xa[c] = x[(size_t)ma * D + c]; xb[c] = hasb ? x[(size_t)mb * D + c] : 0.0; }
+  }
+  __device__ __forceinline__ void step(bool hasb, const ModelK& mk, const StepRec* rec, uint64_t key, uint64_t ia, uint32_t h, const double* tab,
+                                       double (&xa)[D], double (&xb)[D]) const {
+    post_step<D>(hasb, mk, rec->dt, key, ia, h, tab, pa, pb, xa, xb);
+  }
+  __device__ __forceinline__ const cssm_obs_params& obs(int b) const { return b ? opb : opa; }
+};
+
+template <int D>
+__global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_forecast_post(const FleetFcArgs a, const FleetFcPost q) {
+  FleetPostSrc<D> s(q);
+  fleet_forecast_body<D>(a, s);
+}
+
 int cssm_fleet_forecast_launch(const FleetFcLaunch& l) {
   DISPATCH_D(l.d, hipLaunchKernelGGL(k_fleet_forecast<D>, dim3(l.n_series), dim3(l.threads), (size_t)l.args.np2 * 8u, l.stream, l.args));
+  return (int)hipGetLastError();
+}
+
+int cssm_fleet_forecast_post_launch(const FleetFcLaunch& l, const FleetFcPost& q) {
+  DISPATCH_D(l.d, hipLaunchKernelGGL(k_fleet_forecast_post<D>, dim3(l.n_series), dim3(l.threads), (size_t)l.args.np2 * 8u, l.stream, l.args, q));
   return (int)hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // cssm_fleet_forecast.hip.h -- what the fleet's host side (cssm_fleet.hip) hands to the forecast kernel's translation unit
-// (cssm_fleet_forecast.hip: k_fleet_forecast, one workgroup per series, the whole chain of a series' horizons in one launch).
+// (cssm_fleet_forecast.hip: k_fleet_forecast and k_fleet_forecast_post, one workgroup per series, the whole chain of a series' horizons
+// in one launch).
 #pragma once
 
 #include "cssm_fleet.hip.h"
@@ -38,6 +39,24 @@ struct FleetFcLaunch {
   hipStream_t stream;
 };
 int cssm_fleet_forecast_launch(const FleetFcLaunch& l);
+
+// k_fleet_forecast_post keeps the parameter sets of a pair (6 D doubles) in registers up to this latent dimension and reads them from
+// the posterior rows above it (PostParams<D, REG>, cssm_posterior_move.hip.h).  0 = from the rows at every d: a thread serves several
+// pairs per horizon, so a set is loaded per pair and horizon and used once either way, and held in registers it cost d = 6 .. 8 their
+// 28 - 180 bytes of scratch and d <= 4 another 30 - 170 (the resource table).
+#define CSSM_FLEET_POST_REG_MAX_D 0
+
+// What cssm_fleet_forecast_posterior adds to FleetFcArgs (of which k_fleet_forecast_post does not read anc and op; cur[k] only says
+// which buffer of a series is free: the other one)
+struct FleetFcPost {
+  const unsigned long long* moff;    // [S + 1]: series k owns the posterior pairs moff[k] .. moff[k + 1] - 1
+  const double* x;                   // [M][d]: the state of every pair at its series' t0
+  const double* rows;                // [M][3 d + 1]: cssm_posterior_rows (mu, phi, sigma per component, then the observation constant)
+  uint32_t* picks;                   // [S][n]: the pair of every particle, within its series
+  uint32_t draw;                     // 0: picks holds the caller's; 1: the first horizon draws them (cssm_posterior_pick) and writes them there
+  int obs_df;
+};
+int cssm_fleet_forecast_post_launch(const FleetFcLaunch& l, const FleetFcPost& q);
 
 // cssm_forecast.hip: the observation parameters of a draw, or the reference's exception for a model without the scale its
 // observation needs, as the message of cssm_last_error

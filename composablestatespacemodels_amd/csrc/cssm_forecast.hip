@@ -13,37 +13,13 @@
 // k_forecast<D> with CloudSrc (the handle's current cloud through the indirection k_summary_fill reads, moved under the handle's
 // records) and k_forecast_post<D> with PostSrc (a pair of a posterior sample per particle: its state, its own parameters).  A source
 // says where a particle starts, what moves a pair one step and which observation parameters each particle draws with; both step
-// whole pairs through pair_normals_feed and a component through transition_step (cssm_device.hip.h).
+// whole pairs through pair_normals_feed and a component through transition_step (cssm_posterior_move.hip.h, cssm_device.hip.h).
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
-#include "cssm_sde_coef.h"
+#include "cssm_posterior_move.hip.h"
 #include "../../include/cssm_obs_draws.h"
 
 #include <cmath>
-
-// The 2 D normals of the pair (2m, 2m+1) as propagate_pair (cssm_device.hip.h) draws them: its ceil(D / 2) Philox blocks in order, each
-// normal handed to feed(b, k, e) as soon as it exists -- normal q goes to particle b = q / D of the pair, component k = q % D.  Both
-// sources below step whole pairs through this loop.  MUST CHANGE TOGETHER WITH propagate_pair, which keeps its own statement of the
-// loop: k_propagate's code changes when its loop goes through a callable (profiles/forecast_body_pair_loop_asm.md), and that kernel
-// is not to move.  tests/test_gpu_forecast.py holds k_forecast to the oracle's propagate bit for bit.
-template <int D, class Feed>
-__device__ __forceinline__ void pair_normals_feed(uint64_t seed, uint64_t gid_even, uint32_t step, const double* tab, Feed&& feed) {
-  const uint64_t stream = cssm_pair_stream(gid_even);
-  auto give = [&](int q, double e) {            // (q is a compile-time constant wherever this is called)
-    if (q < 2 * D) feed(q / D, q % D, e);
-  };
-#pragma unroll
-  for (int B = 0; B < (D + 1) / 2; ++B) {
-    const cssm_u32x4 blk = cssm_philox_draw(seed, stream, step, CSSM_STREAM_STEP, (uint32_t)B);
-    double e0, e1;
-    cssm_normal_pair64(blk.v[0], blk.v[1], tab, &e0, &e1);
-    give(4 * B, e0); give(4 * B + 1, e1);
-    if (2 * B + 1 < D) {
-      cssm_normal_pair64(blk.v[2], blk.v[3], tab, &e0, &e1);
-      give(4 * B + 2, e0); give(4 * B + 3, e1);
-    }
-  }
-}
 
 // What the two forecasts share -- everything but where a particle starts and what moves it.  One thread per particle PAIR; a source
 // `s` answers: begin (what it needs of the pair before the first load), x0 (component k of particle i, the pair's particle b, before
@@ -169,26 +145,8 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restric
 
 // ---- forecasts from a joint posterior sample (cssm_pf_forecast_posterior): particle i starts from the state of pair pick_i and
 // moves under that pair's parameter set.  A particle's set is the 3 D constrained values (mu, phi, sigma) of its posterior row, held in
-// registers up to D = 8 and read from the row (L2-resident: M x (3 D + 1) doubles) above, where two particles' sets would spill.
-template <int D, bool REG = (D <= 8)>
-struct PostParams {
-  double v[3 * D];
-  __device__ __forceinline__ void load(const double* __restrict__ row) {
-#pragma unroll
-    for (int k = 0; k < 3 * D; ++k) v[k] = row[k];
-  }
-  __device__ __forceinline__ double mu(int k) const { return v[3 * k]; }
-  __device__ __forceinline__ double phi(int k) const { return v[3 * k + 1]; }
-  __device__ __forceinline__ double sigma(int k) const { return v[3 * k + 2]; }
-};
-template <int D>
-struct PostParams<D, false> {
-  const double* row;
-  __device__ __forceinline__ void load(const double* __restrict__ r) { row = r; }
-  __device__ __forceinline__ double mu(int k) const { return row[3 * k]; }
-  __device__ __forceinline__ double phi(int k) const { return row[3 * k + 1]; }
-  __device__ __forceinline__ double sigma(int k) const { return row[3 * k + 2]; }
-};
+// registers up to D = 8 and read from the row (L2-resident: M x (3 D + 1) doubles) above, where two particles' sets would spill
+// (PostParams, cssm_posterior_move.hip.h).
 
 // Source 2: a pair of the posterior sample per particle.  The first chunk gathers x0[pick_i] (M x D), every chunk loads row pick_i
 // of `rows` (M x (3 D + 1): the parameter set, then the observation constant p0).  pick_i = pick[i], or the draw
@@ -215,23 +173,9 @@ struct PostSrc {
     opb.p0 = rows[mb * S + 3 * D];
   }
   __device__ __forceinline__ double x0(int b, uint64_t, int k) const { return x[(b ? mb : ma) * D + k]; }
-  static __device__ __forceinline__ void move(int kind, const PostParams<D>& prm, int k, double dt, double& xk, double zk) {
-    double c[4];
-    cssm_sde_coef(kind, prm.mu(k), prm.phi(k), prm.sigma(k), dt, c);
-    transition_step(kind, c[0], c[1], c[2], c[3], dt, xk, zk);
-  }
-  // (the unpaired last particle of an odd cloud is keyed as propagate_one keys it)
   __device__ __forceinline__ void step(bool hasb, const ModelK& mk, const StepRec* __restrict__ rec, uint64_t key, uint64_t ia, uint32_t h,
                                        const double* tab, double (&xa)[D], double (&xb)[D]) const {
-    const double dt = rec->dt;
-    if (hasb) {
-      pair_normals_feed<D>(key, ia, h, tab, [&](int b, int k, double e) { move(mk.kind(k), b ? pb : pa, k, dt, b ? xb[k] : xa[k], e); });
-    } else {
-      double z[D];
-      draw_normals<D>(key, ia, h, CSSM_STREAM_STEP, tab, z);
-#pragma unroll
-      for (int k = 0; k < D; ++k) move(mk.kind(k), pa, k, dt, xa[k], z[k]);
-    }
+    post_step<D>(hasb, mk, rec->dt, key, ia, h, tab, pa, pb, xa, xb);
   }
   __device__ __forceinline__ const cssm_obs_params& obs(int b) const { return b ? opb : opa; }
 };

@@ -363,6 +363,10 @@ void cssm_pmmh_chain_decide(cssm_pmmh_chain* c, size_t it, double pll, const dou
 // of every component, then the observation constant p0 (cssm_obs_params_make).  The structure must be the handle's.
 int cssm_posterior_rows(const HostModel* pf, const cssm_model_desc* desc, const double* theta, size_t n_theta, size_t M,
                         std::vector<double>& rows) {
+  rows.assign(M * (3 * (size_t)pf->d + 1), 0.0);
+  return cssm_posterior_rows_into(pf, desc, theta, n_theta, M, rows.data());
+}
+int cssm_posterior_rows_into(const HostModel* pf, const cssm_model_desc* desc, const double* theta, size_t n_theta, size_t M, double* rows) {
   OwnedDesc o;
   int rc = own_desc(desc, &o);
   if (rc) return rc;
@@ -375,7 +379,6 @@ int cssm_posterior_rows(const HostModel* pf, const cssm_model_desc* desc, const 
   if (n_theta != o.slots.size()) return fail(CSSM_EINVAL_ARG, "n_theta = %zu, the descriptor flattens to %zu", n_theta, o.slots.size());
   const int d = tmp.d;
   const size_t S = 3 * (size_t)d + 1;
-  rows.assign(M * S, 0.0);
   for (size_t m = 0; m < M; ++m) {
     const double* th = theta + m * n_theta;
     for (size_t j = 0; j < n_theta; ++j) {
@@ -384,7 +387,8 @@ int cssm_posterior_rows(const HostModel* pf, const cssm_model_desc* desc, const 
     }
     rc = build_model_into(&tmp, &o.desc);
     if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "theta row %zu: %s", m, keep.c_str()); }
-    double* r = rows.data() + m * S;
+    double* r = rows + m * S;
+    r[3 * d] = 0.0;
     for (int k = 0; k < d; ++k) {
       const Comp& c = tmp.comp[k];
       r[3 * k] = c.mu; r[3 * k + 1] = c.phi; r[3 * k + 2] = c.sigma;

@@ -102,6 +102,8 @@ void cssm_build_rec(const HostModel* m, double t_prev, double t, double y, int h
 #if !defined(__HIPCC_RTC__)
 // The parameter rows of cssm_pf_forecast_posterior: (mu, phi, sigma) per component and the observation constant, 3 d + 1 per row.
 int cssm_posterior_rows(const HostModel* m, const cssm_model_desc* desc, const double* theta, size_t n_theta, size_t M, std::vector<double>& rows);
+// ... the same rows written into the caller's M x (3 d + 1) doubles (the fleet's pinned staging); on a refusal what they hold is undefined
+int cssm_posterior_rows_into(const HostModel* m, const cssm_model_desc* desc, const double* theta, size_t n_theta, size_t M, double* rows);
 #endif
 // LGCP with a time-dependent f (FilterLgcp.calcWeight evaluates f at every simulated time, model/ParticleFilter.scala:193-205):
 // append the n_sub x d coefficient rows of records recs[first .. first + count) to `table` and set their fsub_off;

@@ -378,6 +378,9 @@ class NativePfFleet:
         d = C.c_int32()
         _abi.check(self.lib.cssm_model_structure(self._desc.ptr(), words, C.byref(d)))
         self.d = int(d.value)
+        nt = C.c_size_t()
+        _abi.check(self.lib.cssm_desc_flatten(self._desc.ptr(), None, 0, C.byref(nt)))
+        self.n_theta = int(nt.value)       # the length of a parameter row in flatten order
         self.generation = 0
         self.seeds = [0] * self.S          # the keys given to reseed (cssm_fleet_reseed's default: 0)
 
@@ -596,6 +599,96 @@ class NativePfFleet:
                                                 _p(arr["eta_upper"]), _p(arr["obs_mean"]), _p(arr["obs_lower"]), _p(arr["obs_upper"]),
                                                 _p(samples) if want_samples else None, _p(rc, C.POINTER(C.c_int))))
         return arr, samples, rc
+
+    def posterior_key(self, k: int) -> int:
+        """The default Philox key of series k's posterior forecast: cssm_pf_run_key(seed_k, 2^63) -- ``forecast_key()`` of a fresh
+        ``NativePf`` with that seed, the handle ``ParticleFilter.forecastPosterior`` makes."""
+        return int(self.lib.cssm_pf_run_key(self.seeds[k], 1 << 63))
+
+    def pack_posteriors(self, posteriors, n_theta: Optional[int] = None):
+        """The ragged posteriors of ``cssm_fleet_forecast_posterior`` from a sequence of S ``(theta[M_k, n_theta], x[M_k, d])`` pairs
+        (None or empty arrays: M_k = 0): ``(moff uint64[S + 1], theta float64[M, n_theta], x float64[M, d])``, C-contiguous.  A wrong
+        number of series, rows of differing length and states of another dimension are refused here.  ``n_theta``: the length of a
+        row; None: the descriptor's (``self.n_theta``), or what the first row tells where the fleet has no descriptor."""
+        if len(posteriors) != self.S:
+            raise ValueError("one (theta, x) posterior per series (None or empty: none)")
+        if n_theta is None:
+            n_theta = getattr(self, "n_theta", None)
+        ths, xs = [], []
+        for k, p in enumerate(posteriors):
+            th = None if p is None else np.asarray(p[0], dtype=np.float64)
+            if th is None or th.size == 0:
+                ths.append(None); xs.append(None)
+                continue
+            th = np.atleast_2d(th)
+            x = np.asarray(p[1], dtype=np.float64).reshape(th.shape[0], -1)
+            if th.ndim != 2 or x.shape != (th.shape[0], self.d):
+                raise ValueError(f"series {k}: theta must be M x n_theta and x M x d = {th.shape[0]} x {self.d} (got {th.shape}, {x.shape})")
+            if n_theta is None:
+                n_theta = th.shape[1]
+            if th.shape[1] != n_theta:
+                raise ValueError(f"series {k}: its rows hold {th.shape[1]} parameters, the others {n_theta}")
+            ths.append(th); xs.append(x)
+        nt = int(n_theta or 0)
+        moff = np.zeros(self.S + 1, dtype=np.uint64)
+        moff[1:] = np.cumsum([0 if v is None else len(v) for v in ths], dtype=np.uint64)
+        theta = np.ascontiguousarray(np.concatenate([np.zeros((0, nt))] + [v for v in ths if v is not None]), dtype=np.float64)
+        x = np.ascontiguousarray(np.concatenate([np.zeros((0, self.d))] + [v for v in xs if v is not None]), dtype=np.float64)
+        return moff, theta, x
+
+    def forecast_posterior(self, posteriors, t0s, times, keys=None, interval: float = 0.975, picks=None, want_samples: bool = False):
+        """cssm_fleet_forecast_posterior: every series' posterior-predictive forecast in one launch.  ``posteriors[k]`` =
+        ``(theta[M_k, n_theta], x[M_k, d])``, series k's joint posterior sample, its states at ``t0s[k]`` (a scalar serves every
+        series); ``times``: S arrays (None / empty: none for that series); ``keys``: S Philox keys (None: ``posterior_key(k)``);
+        ``picks``: None (drawn under the keys) or [S, N] indices, series k's below M_k.  A list of S dicts with the keys of
+        ``forecast`` plus ``pick`` (uint32[N]): per series what ``NativePf.forecast_posterior`` returns on a handle of N particles.
+        The fleet lends its structure and scratch only: no series needs a cloud, none is touched."""
+        moff, theta, x = self.pack_posteriors(posteriors)
+        t0 = np.asarray(t0s, dtype=np.float64)
+        if t0.ndim != 0 and t0.shape != (self.S,):
+            raise ValueError("one t0 per series (or one for all)")
+        t0 = np.ascontiguousarray(np.broadcast_to(t0, (self.S,)), dtype=np.float64)
+        off, t = self.pack_times(times)
+        if keys is not None and len(keys) != self.S:
+            raise ValueError("one key per series")
+        pk = None
+        if picks is not None:
+            pa = np.asarray(picks)
+            if pa.shape != (self.S, self.n) or (pa < 0).any():
+                raise ValueError(f"picks must hold S x N = {self.S} x {self.n} non-negative indices")
+            pk = np.ascontiguousarray(pa, dtype=np.uint32)
+        if keys is None:
+            keys = [self.posterior_key(k) for k in range(self.S)]
+        ky = np.ascontiguousarray([int(v) & (2**64 - 1) for v in keys], dtype=np.uint64)
+        arr, samples, pick_out, rc = self.forecast_posterior_packed(moff, theta, x, t0, off, t, ky, interval, pk, want_samples)
+        o = [int(v) for v in off]
+        outs = []
+        for k in range(self.S):
+            r = {name: v[o[k]:o[k + 1]] for name, v in arr.items()}
+            r["samples"] = samples[o[k]:o[k + 1]] if want_samples else None
+            r["key"] = int(ky[k]); r["rc"] = int(rc[k]); r["pick"] = pick_out[k]
+            outs.append(r)
+        return outs
+
+    def forecast_posterior_packed(self, moff, theta, x, t0, off, t, keys, interval: float = 0.975, picks=None, want_samples: bool = False):
+        """``forecast_posterior`` on the arrays ``pack_posteriors`` and ``pack_times`` made, float64 t0[S], uint64 keys[S] and (optional)
+        uint32 picks[S, N]: ``(dict of arrays laid out like t, samples or None, pick uint32[S, N], rc[S])``."""
+        R, M = int(off[-1]), int(moff[-1])
+        tt = t if R else np.zeros(1)
+        th = theta if M else np.zeros((1, max(1, theta.shape[1])))
+        xx = x if M else np.zeros((1, self.d))
+        arr = {k: np.zeros((R, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
+        arr.update({k: np.zeros(R) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        samples = np.zeros((R, self.d + 3, self.n)) if want_samples else None
+        pick_out = np.zeros((self.S, self.n), dtype=np.uint32)
+        rc = np.zeros(self.S, dtype=np.int32)
+        u64, u32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        _abi.check(self.lib.cssm_fleet_forecast_posterior(
+            self._h, self._desc.ptr(), _p(moff, u64), _p(th), int(theta.shape[1]), _p(xx), _p(t0), _p(off, u64), _p(tt),
+            _p(picks, u32) if picks is not None else None, _p(keys, u64), float(interval), _p(arr["state_mean"]), _p(arr["state_lower"]),
+            _p(arr["state_upper"]), _p(arr["eta_mean"]), _p(arr["eta_lower"]), _p(arr["eta_upper"]), _p(arr["obs_mean"]), _p(arr["obs_lower"]),
+            _p(arr["obs_upper"]), _p(samples) if want_samples else None, _p(pick_out, u32), _p(rc, C.POINTER(C.c_int))))
+        return arr, samples, pick_out, rc
 
 
 class _PfView(NativePf):
@@ -1029,6 +1122,26 @@ class FilterFleet:
             if r["rc"]:
                 raise _abi.CssmError(r["rc"], f"series {k}: its forecast was refused (no cloud, times before its clock or decreasing, "
                                               f"or a model without the scale its observation needs)")
+        return [_forecast_outs(ts[k], rs[k]) for k in range(self.S)]
+
+    def forecastPosterior(self, posteriors, t0s, times, interval: float = 0.975, seed: Optional[int] = None,
+                          params: Optional[Parameters] = None) -> List[List[ForecastOut]]:
+        """``ParticleFilter.forecastPosterior`` of every series under its own joint posterior sample -- e.g. the chains of
+        ``pmmh.pmmh_native_fleet`` through ``pmmh.fleet_posterior_rows`` --, all of them in one device call: ``posteriors[k]`` is what
+        ``ParticleFilter.forecastPosterior`` accepts (MetropStates, or the arrays (theta[M, n_theta], last_state[M, d]) with ``params``,
+        the parameter tree the rows flatten), its states at ``t0s[k]``; n = the fleet's particles.  seed = the Philox key of every
+        series' draws; None: each series' default key (``NativePfFleet.posterior_key``).  No series needs a filtered state."""
+        if len(posteriors) != self.S or len(times) != self.S:
+            raise ValueError("one posterior and one array of times per series")
+        t0 = np.asarray(t0s, dtype=np.float64)
+        if t0.ndim != 0 and t0.shape != (self.S,):
+            raise ValueError("one t0 per series (or one for all)")
+        ts = [[] if v is None else [float(x) for x in v] for v in times]
+        post = [_posterior_arrays(p, params)[:2] for p in posteriors]
+        rs = self._fleet.forecast_posterior(post, t0, ts, None if seed is None else [int(seed)] * self.S, float(interval))
+        for k, r in enumerate(rs):
+            if r["rc"]:
+                raise _abi.CssmError(r["rc"], self._fleet.lib.cssm_last_error().decode() or f"series {k}: its posterior forecast was refused")
         return [_forecast_outs(ts[k], rs[k]) for k in range(self.S)]
 
     def getMeanForecast(self, ts, interval: float, seed: Optional[int] = None) -> List[ForecastOut]:

@@ -287,3 +287,14 @@ def posterior_rows(theta, last_state, burn_in: int = 0, thin: int = 1):
     last_state = np.asarray(last_state, dtype=np.float64).reshape(theta.shape[0], -1)
     keep = np.arange(burn_in, theta.shape[0], thin)
     return theta[keep], last_state[keep]
+
+
+def fleet_posterior_rows(theta, last_state, burn_in: int = 0, thin: int = 1):
+    """``posterior_rows`` of every chain of ``pmmh_native_fleet``'s output (theta[S, iters, n_theta], last_state[S, iters, d]): a list of
+    S ``(theta_k, last_state_k)`` pairs, what ``NativePfFleet.forecast_posterior`` and ``FilterFleet.forecastPosterior`` (with
+    ``params``) take as their posteriors."""
+    theta = np.asarray(theta, dtype=np.float64)
+    last_state = np.asarray(last_state, dtype=np.float64)
+    if theta.ndim != 3 or last_state.ndim != 3 or last_state.shape[:2] != theta.shape[:2]:
+        raise ValueError("theta[S, iters, n_theta] and last_state[S, iters, d] of pmmh_native_fleet")
+    return [posterior_rows(theta[k], last_state[k], burn_in, thin) for k in range(theta.shape[0])]

@@ -765,7 +765,7 @@ int cssm_model_structure(const cssm_model_desc* desc, uint32_t* words_out, int32
  * CSSM_EINVAL_DESC and a message naming the reason and the entry points that do serve it (cssm_pf_*, cssm_pfb_*); a fleet call
  * never degenerates into S single-handle runs.  Thread-affinity and device rules as for every entry point: each call selects the
  * fleet's device; the fleet owns a non-blocking stream; a fleet is not re-entrant.
- * Not here: posterior-predictive forecasts from a fleet, sharded fleets, other resamplers. */
+ * Not here: sharded fleets, other resamplers. */
 typedef struct cssm_fleet cssm_fleet;
 /* 12 bytes of LDS per particle (weight 8, ancestor 4) + 7.3 KB per block: 55.3 KB at 4096, two blocks per CU of 160 KiB; the summary
  * kernel sorts a row of at most 4096 keys (32 KiB) in LDS. */
@@ -785,7 +785,8 @@ int cssm_fleet_set_params(cssm_fleet* f, const cssm_model_desc* const* descs);
 int cssm_fleet_reseed(cssm_fleet* f, const uint64_t* seeds);
 /* CSSM_OPT_RESAMPLER, and only CSSM_RESAMPLE_SYSTEMATIC: any other resampler is CSSM_EINVAL_ARG with the reason (the
  * `Resample[A]` a FilterFleet is constructed with goes through here); CSSM_OPT_FORECAST_CAP (KiB, 0 = 1 GiB, negative refused): the
- * samples cssm_fleet_forecast holds on the device at a time; CSSM_OPT_FLEET_SELECT.  Every other option is CSSM_EINVAL_ARG. */
+ * samples cssm_fleet_forecast / cssm_fleet_forecast_posterior hold on the device at a time; CSSM_OPT_FLEET_SELECT.  Every other option
+ * is CSSM_EINVAL_ARG. */
 int cssm_fleet_set_option(cssm_fleet* f, int option, int value);
 
 /* llFilter (model/ParticleFilter.scala:137-140) of every series, ragged: series k owns the records off[k] .. off[k+1]-1 of
@@ -883,11 +884,42 @@ int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const double* t, con
                         double* eta_mean, double* eta_lower, double* eta_upper,
                         double* obs_mean, double* obs_lower, double* obs_upper,
                         double* samples, int* rc_out);
+/* Posterior-predictive forecasts of every series in one launch: SimulateData.forecast(unparamModel, t, n)(posterior) + summariseForecast
+ * (model/Data.scala:196-231) per series, each under its OWN joint posterior sample -- what S chains of cssm_fleet_pmmh_run leave.
+ * Ragged posteriors: series k owns the pairs moff[k] .. moff[k+1]-1 (moff[0] = 0, non-decreasing, S + 1 entries; M_k = their number);
+ * pair m is theta[m * n_theta ..] in flatten order and x[m * d ..], its state at t0[k].  off, t, keys, interval and the layout of every
+ * output are cssm_fleet_forecast's.  pick (optional): [S][N] host indices, series k's each below M_k; pick_out (optional): [S][N].
+ *
+ * Per series k the result is bit for bit what cssm_pf_forecast_posterior(handle of N particles, desc, theta_k, n_theta, x_k, M_k, t0[k],
+ * t_k, H_k, pick_k or NULL, keys[k], interval, ...) returns -- order statistics, samples and picks; means are plain fp64 sums, so their
+ * order of summation may differ.  f(x, t) is that of series k's model (f has no parameters).  A series without horizons still gets its
+ * pick_out row when M_k > 0; the pick_out row of a refused series, or of one with M_k = 0, reads 0.
+ *
+ * The fleet lends its device, stream, contract table, N, structure and scratch, as a handle does to cssm_pf_forecast_posterior: clouds,
+ * ancestors, clocks, observation indices, ll, ESS, keys and parameters of every series stay as they were, and no series needs a cloud
+ * (a fleet that was never initialised serves the call).
+ *
+ * rc_out[S] = the series' OWN status, CSSM_EINVAL_ARG for: horizons with M_k = 0; a theta row the model rejects or a non-finite theta
+ * or x entry; pick >= M_k; a t0 or times that are not finite, times before t0[k] or decreasing; a descriptor without the scale its
+ * observation needs (every series with M_k > 0, with or without horizons, as the single handle refuses it for any H).  Such a series' outputs read NaN, every other series is bit for bit what it is without it, the call succeeds and
+ * cssm_last_error names the first such series and its row ("series k: theta row m: ...").  The call itself fails, before the fleet is
+ * looked at, for: a null f / desc / moff / theta / x / t0 / off / t / keys / rc_out, moff[0] or off[0] != 0 or either decreasing, interval
+ * outside (0, 1], n_theta not the descriptor's (CSSM_EINVAL_ARG); a descriptor of another structure than the fleet's, LGCP among them
+ * (CSSM_EINVAL_DESC).  With samples, the fleet runs in chunks of series whose samples fit CSSM_OPT_FORECAST_CAP (a series is never
+ * split); CSSM_OPT_FLEET_SELECT applies; the device time is cssm_fleet_last_ms()[2]. */
+int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_desc* desc,
+                                  const uint64_t* moff, const double* theta, size_t n_theta, const double* x,
+                                  const double* t0, const uint64_t* off, const double* t,
+                                  const uint32_t* pick, const uint64_t* keys, double interval,
+                                  double* state_mean, double* state_lower, double* state_upper,
+                                  double* eta_mean, double* eta_lower, double* eta_upper,
+                                  double* obs_mean, double* obs_lower, double* obs_upper,
+                                  double* samples, uint32_t* pick_out, int* rc_out);
 /* Observations series k's current cloud has seen (the Philox counter word of its next step); 0 for a null fleet or k >= S, the
  * convention of cssm_pf_observation_index. */
 uint64_t cssm_fleet_observation_index(const cssm_fleet* f, uint32_t k);
 /* ms3[0] = device time of the last ll_filter / filter / init / step call (upload, launch, read-back), ms3[1] = of the last summary, ms3[2] =
- * of the last forecast; HIP events on the fleet's stream, < 0 while there was none.  The array holds THREE doubles. */
+ * of the last forecast (cssm_fleet_forecast or cssm_fleet_forecast_posterior); HIP events on the fleet's stream, < 0 while there was none.  The array holds THREE doubles. */
 int cssm_fleet_last_ms(cssm_fleet* f, double* ms3);
 /* Diagnostic, no device: the compact per-observation record the fleet uploads for (t_prev, t, y, has_obs, step) under `desc`,
  * a cloud of n_particles and Philox key `seed` -- 80 + 40 d bytes: y, c[4], cdf, u, dt, ref (doubles), has_obs (i32), step (u32),
