@@ -29,6 +29,8 @@ OBS_NEGBIN, OBS_ZIP, OBS_BERNOULLI, OBS_STUDENT_T, OBS_BETA = 3, 4, 5, 6, 7
 MAX_DIM = 16
 MAX_LEAVES = 16
 FLEET_MAX_N = 4096   # CSSM_FLEET_MAX_N
+CSSM_OPT_INTERP_CAP = 13
+CSSM_INTERP_REFERENCE_PAIRING = 1
 
 _dp = C.POINTER(C.c_double)
 
@@ -186,6 +188,8 @@ SYMBOLS = [
     ("cssm_fleet_forecast", C.c_int, [_h, _u64p, _dp, _u64p, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_fleet_forecast_posterior", C.c_int, [_h, _descp, _u64p, _dp, C.c_size_t, _dp, _dp, _u64p, _dp, _u32p, _u64p, C.c_double,
                                                 _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_interpolate", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    ("cssm_fleet_interpolate_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_observation_index", C.c_uint64, [_h, C.c_uint32]),
     ("cssm_fleet_pack_record", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32,
                                          _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),

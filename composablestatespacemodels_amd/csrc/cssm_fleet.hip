@@ -20,6 +20,7 @@
 #include "cssm_kernels.hip.h"
 #include "cssm_fleet.hip.h"
 #include "cssm_fleet_forecast.hip.h"
+#include "cssm_fleet_interp.hip.h"
 
 static_assert(CSSM_FLEET_MAX_N <= 4096, "k_fleet_summary sorts at most 4096 keys in LDS; k_fleet_series holds 12 bytes per particle there");
 
@@ -61,6 +62,15 @@ struct cssm_fleet {
   double* d_fc_samp = nullptr; size_t fc_samp_cap = 0;
   size_t fc_samp_max = (size_t)1 << 30;
   int fc_select = 0;                    // CSSM_OPT_FLEET_SELECT: 0 = by N (CSSM_FLEET_SELECT_MIN_N), 1 = bitonic sort, 2 = radix select
+  // interpolation (cssm_fleet_interpolate), grow-only: one chunk's [off | records | f coefficients | series scalars | results] and its
+  // pinned mirror; one chunk's lineage history (clouds, then ancestors: at most ip_hist_max bytes, CSSM_OPT_INTERP_CAP)
+  unsigned char* d_ip = nullptr; size_t ip_cap = 0;
+  unsigned char* h_ip = nullptr; size_t h_ip_cap = 0;
+  unsigned char* d_ip_hist = nullptr; size_t ip_hist_cap = 0;
+  size_t ip_hist_max = (size_t)1 << 30;
+  hipEvent_t ev_ip[3] = {nullptr, nullptr, nullptr};   // before the forward launch | between the two | behind the lineage launch
+  double ms_ip[2] = {-1.0, -1.0};                      // ... of the last interpolation, summed over its chunks
+  bool ip_ran = false;
 };
 
 #define FLEET_SERVED "cssm_pf_* (one handle per series) and cssm_pfb_* (batch of chains) serve it"
@@ -160,11 +170,13 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp};
+  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp, f->d_ip, f->d_ip_hist};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
   if (f->h_fc) (void)hipHostFree(f->h_fc);
+  if (f->h_ip) (void)hipHostFree(f->h_ip);
   for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : f->ev_ip) if (e) (void)hipEventDestroy(e);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;
 }
@@ -197,6 +209,7 @@ extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particl
   auto bail = [&](int code, const char* what) { cssm_fleet_destroy(f); return fail(code, "fleet of %u series x %u particles: %s", S, n, what); };
   if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) return bail(CSSM_EHIP, "hipStreamCreate");
   for (hipEvent_t& e : f->ev) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
+  for (hipEvent_t& e : f->ev_ip) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   const size_t rows = (size_t)S * 2u * f->d * n;
   if (hipMalloc(&f->state, rows * 8) != hipSuccess || hipMalloc(&f->anc, (size_t)S * n * 4) != hipSuccess ||
       hipMalloc(&f->ser, (size_t)S * sizeof(FleetSeries)) != hipSuccess || hipMalloc(&f->par, (size_t)S * sizeof(FleetPar)) != hipSuccess ||
@@ -218,6 +231,11 @@ extern "C" int cssm_fleet_set_option(cssm_fleet* f, int option, int value) {
   if (option == CSSM_OPT_FORECAST_CAP) {   // KiB of samples one chunk of series holds on the device; 0 = 1 GiB
     if (value < 0) return fail(CSSM_EINVAL_ARG, "CSSM_OPT_FORECAST_CAP must not be negative (got %d)", value);
     f->fc_samp_max = value ? (size_t)value << 10 : (size_t)1 << 30;
+    return CSSM_OK;
+  }
+  if (option == CSSM_OPT_INTERP_CAP) {   // KiB of lineage history one chunk of series holds on the device; 0 = 1 GiB
+    if (value < 0) return fail(CSSM_EINVAL_ARG, "CSSM_OPT_INTERP_CAP must not be negative (got %d)", value);
+    f->ip_hist_max = value ? (size_t)value << 10 : (size_t)1 << 30;
     return CSSM_OK;
   }
   if (option == CSSM_OPT_FLEET_SELECT) {
@@ -304,6 +322,20 @@ static int fleet_ensure(cssm_fleet* f, size_t R, bool picks = false) {
   return CSSM_OK;
 }
 
+// k_fleet_series of the fleet's latent dimension (one object per dimension: cssm_fleet_d.hip)
+static int fleet_series_launch(int d, const FleetLaunch& l) {
+  int hrc = 0;
+  switch (d) {
+#define FLEET_CASE(D) case D: hrc = cssm_fleet_launch_d##D(l); break;
+    FLEET_CASE(1) FLEET_CASE(2) FLEET_CASE(3) FLEET_CASE(4) FLEET_CASE(5) FLEET_CASE(6) FLEET_CASE(7) FLEET_CASE(8)
+    FLEET_CASE(9) FLEET_CASE(10) FLEET_CASE(11) FLEET_CASE(12) FLEET_CASE(13) FLEET_CASE(14) FLEET_CASE(15) FLEET_CASE(16)
+#undef FLEET_CASE
+    default: return fail(CSSM_EINVAL_DESC, "latent dimension %d", d);
+  }
+  if (hrc) return fail(CSSM_EHIP, "k_fleet_series: %s", hipGetErrorString((hipError_t)hrc));
+  return CSSM_OK;
+}
+
 // upload the staged launch, run it, bring the series' scalars (and, asked for, the per-observation results) back; synchronises.
 // want_path: the staged launch carries its picks and runs k_fleet_series<D, true>; path_out (may be null) / last_out receive the rows.
 static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, bool want_path = false, double* path_out = nullptr, double* last_out = nullptr) {
@@ -336,16 +368,10 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
   l.args.picks = want_path ? reinterpret_cast<const uint32_t*>(f->d_stage + head + recs) : nullptr;
   l.args.path = (want_path && path_out) ? f->d_path + n_last : nullptr;
   l.args.last = want_path ? f->d_path : nullptr;
+  l.args.hist = nullptr; l.args.hanc = nullptr; l.args.hser = nullptr; l.args.k0 = 0u;
   l.n_series = f->S; l.path = want_path; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
-  int hrc = 0;
-  switch (f->d) {
-#define FLEET_CASE(D) case D: hrc = cssm_fleet_launch_d##D(l); break;
-    FLEET_CASE(1) FLEET_CASE(2) FLEET_CASE(3) FLEET_CASE(4) FLEET_CASE(5) FLEET_CASE(6) FLEET_CASE(7) FLEET_CASE(8)
-    FLEET_CASE(9) FLEET_CASE(10) FLEET_CASE(11) FLEET_CASE(12) FLEET_CASE(13) FLEET_CASE(14) FLEET_CASE(15) FLEET_CASE(16)
-#undef FLEET_CASE
-    default: return fail(CSSM_EINVAL_DESC, "latent dimension %d", f->d);
-  }
-  if (hrc) return fail(CSSM_EHIP, "k_fleet_series: %s", hipGetErrorString((hipError_t)hrc));
+  rc = fleet_series_launch(f->d, l);
+  if (rc) return rc;
   if (want_path) HIP_TRY(hipEventRecord(f->ev[7], f->stream));
   HIP_TRY(hipMemcpyAsync(f->h_ser.data(), f->ser, (size_t)f->S * sizeof(FleetSeries), hipMemcpyDeviceToHost, f->stream));
   if (want_path && path_out) HIP_TRY(hipMemcpyAsync(path_out, f->d_path + n_last, (n_rows - n_last) * 8, hipMemcpyDeviceToHost, f->stream));
@@ -963,6 +989,185 @@ extern "C" int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_des
     }
   for (uint32_t k = 0; k < S; ++k)   // (the call succeeds; the message names the first refused series)
     if (rc_out[k]) { (void)fail(CSSM_EINVAL_ARG, "series %u: %s", k, msg[k].c_str()); break; }
+  return CSSM_OK;
+}
+
+// FilterInterpolate (model/ParticleFilter.scala:273-311, examples/Interpolate.scala:31-44) of every series: cssm_pf_interpolate per
+// series in TWO launches per chunk of series -- the forward pass keeps every cloud and every weighted record's ancestors of a series
+// in a slab of its own (k_fleet_series<D, false, true>), the backward pass composes the surviving lineages and summarises every time
+// index (k_fleet_lineage, cssm_fleet_interp.hip).  The fleet lends its device, stream, contract table, N, structure, parameters and
+// keys; nothing it keeps per series changes.  Chunks: as many series as fit ip_hist_max bytes of history, one at least -- never a
+// part of a series.  Per chunk one upload (offsets, records, the f coefficients of every output row), the two launches, one read-back.
+extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval,
+                                      int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
+                                      double* eta_lower, double* eta_upper, int* rc_out) {
+  if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
+  if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (flags & ~CSSM_INTERP_REFERENCE_PAIRING) return fail(CSSM_EINVAL_ARG, "unknown flag bits 0x%x (CSSM_INTERP_REFERENCE_PAIRING is the only flag)",
+                                                          (unsigned)(flags & ~CSSM_INTERP_REFERENCE_PAIRING));
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const uint32_t S = f->S, n = f->n;
+  const int d = f->d, rows = d + 1;
+  for (uint32_t k = 0; k < S; ++k) {
+    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
+                                         k + 1, (unsigned long long)off[k + 1]);
+    if (off[k + 1] - off[k] > 0xfffffffeull) return fail(CSSM_EINVAL_ARG, "series %u: too many records", k);
+  }
+  HIP_TRY(hipSetDevice(f->device));
+  int rc = fleet_upload_par(f);
+  if (rc) return rc;
+  // chunks of series [cut[c], cut[c + 1]) whose history fits the cap; the buffers of the largest one
+  const size_t RB = CSSM_FLEET_REC_BYTES(d), slice = (size_t)n * (8u * (size_t)d + 4u);
+  auto stage_o = [&](uint32_t k0, uint32_t k1, size_t* o) {   // byte offsets of [off | recs | fco | ser | out | end] of a chunk
+    const size_t Sc = k1 - k0, Rc = (size_t)(off[k1] - off[k0]), Qc = Rc + Sc;
+    o[0] = 0; o[1] = (Sc + 1u) * 8u; o[2] = o[1] + Rc * RB; o[3] = o[2] + Qc * (size_t)d * 8u; o[4] = o[3] + Sc * sizeof(FleetSeries);
+    o[5] = o[4] + Qc * (size_t)rows * 24u;
+  };
+  std::vector<uint32_t> cut(1, 0u);
+  size_t held = 0, need = 0, need_hist = 0;
+  uint32_t widest = 0;
+  for (uint32_t k = 0; k < S; ++k) {
+    const size_t b = ((size_t)(off[k + 1] - off[k]) + 1u) * slice;
+    if (k > cut.back() && held + b > f->ip_hist_max) { cut.push_back(k); held = 0; }
+    held += b;
+    if (held > need_hist) { need_hist = held; widest = cut.back(); }
+  }
+  cut.push_back(S);
+  for (size_t c = 0; c + 1 < cut.size(); ++c) {
+    size_t o[6];
+    stage_o(cut[c], cut[c + 1], o);
+    need = std::max(need, o[5]);
+  }
+  if (need > f->h_ip_cap) {
+    if (f->h_ip) (void)hipHostFree(f->h_ip);
+    f->h_ip = nullptr; f->h_ip_cap = 0;
+    if (hipHostMalloc((void**)&f->h_ip, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of pinned staging", need);
+    f->h_ip_cap = need + need / 4;
+  }
+  if (need > f->ip_cap) {
+    if (f->d_ip) (void)hipFree(f->d_ip);
+    f->d_ip = nullptr; f->ip_cap = 0;
+    if (hipMalloc(&f->d_ip, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of records and results", need);
+    f->ip_cap = need + need / 4;
+  }
+  if (need_hist > f->ip_hist_cap) {
+    if (f->d_ip_hist) (void)hipFree(f->d_ip_hist);
+    f->d_ip_hist = nullptr; f->ip_hist_cap = 0;
+    if (hipMalloc(&f->d_ip_hist, need_hist) != hipSuccess) {
+      f->d_ip_hist = nullptr;
+      if (need_hist > f->ip_hist_max)   // a series longer than the cap runs alone
+        return fail(CSSM_ENOMEM, "fleet interpolation: series %u alone needs %zu bytes of lineage history ((T + 1) N (8 d + 4))", widest, need_hist);
+      return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of lineage history (CSSM_OPT_INTERP_CAP lowers it)", need_hist);
+    }
+    f->ip_hist_cap = need_hist;
+  }
+  SelState rs, re;
+  sel_ranks(rs, n, interval, true);
+  sel_ranks(re, n, interval, false);
+  uint32_t np2 = 2u;
+  while (np2 < n) np2 <<= 1;
+  const bool pairing = (flags & CSSM_INTERP_REFERENCE_PAIRING) != 0;
+  double ms[2] = {0.0, 0.0};
+  for (size_t c = 0; c + 1 < cut.size(); ++c) {
+    const uint32_t k0 = cut[c], k1 = cut[c + 1], Sc = k1 - k0;
+    const size_t R0 = (size_t)off[k0], Rc = (size_t)off[k1] - R0, Qc = Rc + Sc;
+    size_t o[6];
+    stage_o(k0, k1, o);
+    unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_ip);
+    unsigned char* h_recs = f->h_ip + o[1];
+    double* h_fco = reinterpret_cast<double*>(f->h_ip + o[2]);
+    const FleetSeries* h_ser = reinterpret_cast<const FleetSeries*>(f->h_ip + o[3]);
+    const double* h_out = reinterpret_cast<const double*>(f->h_ip + o[4]);
+    for (uint32_t k = k0; k <= k1; ++k) h_off[k - k0] = off[k] - R0;
+    fleet_parallel(Sc, 2 * Rc, [&](size_t lo, size_t hi) {
+      for (size_t kl = lo; kl < hi; ++kl) {
+        const size_t k = k0 + kl, a = (size_t)off[k], b = (size_t)off[k + 1];
+        double* fco = h_fco + (a - R0 + kl) * (size_t)d;      // the series' first output row
+        if (b == a) { std::fill(fco, fco + d, 0.0); continue; }
+        double m = t[a];
+        for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;      // data.minBy(_.t).t
+        double tp = m;
+        for (size_t s = a; s < b; ++s) {
+          fleet_pack_rec(f->models[k], tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), h_recs + (s - R0) * RB);
+          tp = t[s];
+        }
+        for (size_t q = 0; q <= b - a; ++q) {                  // F(time of output row q), as cssm_pf_interpolate's summaries build it
+          const double time = q ? t[a + q - 1] : m;
+          StepRec r;
+          cssm_build_rec(&f->models[k], time, time, 0.0, 0, 0u, &r);
+          for (int cc = 0; cc < d; ++cc) fco[q * (size_t)d + cc] = r.fco[cc];
+        }
+      }
+    });
+    if (Rc) {
+      double* d_hist = reinterpret_cast<double*>(f->d_ip_hist);
+      uint32_t* d_hanc = reinterpret_cast<uint32_t*>(f->d_ip_hist + Qc * (size_t)d * n * 8u);
+      HIP_TRY(hipMemcpyAsync(f->d_ip, f->h_ip, o[3], hipMemcpyHostToDevice, f->stream));
+      HIP_TRY(hipEventRecord(f->ev_ip[0], f->stream));
+      FleetLaunch l;
+      l.args.n = n; l.args.state = f->state; l.args.anc = f->anc; l.args.ser = f->ser; l.args.par = f->par;
+      l.args.off = reinterpret_cast<const unsigned long long*>(f->d_ip);
+      l.args.ctl = nullptr; l.args.recs = f->d_ip + o[1];
+      l.args.ll_t = nullptr; l.args.ess_t = nullptr; l.args.logtab = f->logtab; l.args.mk = f->base.mk;
+      l.args.picks = nullptr; l.args.path = nullptr; l.args.last = nullptr;
+      l.args.hist = d_hist; l.args.hanc = d_hanc; l.args.hser = reinterpret_cast<FleetSeries*>(f->d_ip + o[3]); l.args.k0 = k0;
+      l.n_series = Sc; l.path = false; l.hist = true; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+      rc = fleet_series_launch(d, l);
+      if (rc) return rc;
+      HIP_TRY(hipEventRecord(f->ev_ip[1], f->stream));
+      FleetLinLaunch q;
+      q.args.n = n; q.args.np2 = np2; q.args.pairing = pairing ? 1u : 0u;
+      q.args.hist = d_hist; q.args.hanc = d_hanc;
+      q.args.off = l.args.off; q.args.ser = l.args.hser; q.args.recs = l.args.recs;
+      q.args.fco = reinterpret_cast<const double*>(f->d_ip + o[2]);
+      q.args.out = reinterpret_cast<double*>(f->d_ip + o[4]);
+      q.args.mk = f->base.mk;
+      q.args.lo_state = (uint32_t)rs.rank[0]; q.args.hi_state = (uint32_t)rs.rank[1];
+      q.args.lo_eta = (uint32_t)re.rank[0]; q.args.hi_eta = (uint32_t)re.rank[1];
+      q.d = d; q.n_series = Sc; q.stream = f->stream;
+      const int hrc = cssm_fleet_lineage_launch(q);
+      if (hrc) return fail(CSSM_EHIP, "k_fleet_lineage: %s", hipGetErrorString((hipError_t)hrc));
+      HIP_TRY(hipEventRecord(f->ev_ip[2], f->stream));
+      HIP_TRY(hipMemcpyAsync(f->h_ip + o[3], f->d_ip + o[3], o[5] - o[3], hipMemcpyDeviceToHost, f->stream));
+      HIP_TRY(hipStreamSynchronize(f->stream));
+      float m0 = 0.f, m1 = 0.f;
+      if (hipEventElapsedTime(&m0, f->ev_ip[0], f->ev_ip[1]) == hipSuccess && hipEventElapsedTime(&m1, f->ev_ip[1], f->ev_ip[2]) == hipSuccess) {
+        ms[0] += (double)m0; ms[1] += (double)m1;
+      }
+    }
+    for (uint32_t kl = 0; kl < Sc; ++kl) {
+      const uint32_t k = k0 + kl;
+      const size_t a = (size_t)off[k], T = (size_t)off[k + 1] - a, lrow = a - R0 + kl, grow = a + k;
+      if (T == 0) rc_out[k] = CSSM_EINVAL_ARG;                 // (the reference's minBy throws on an empty Vector)
+      else rc_out[k] = h_ser[kl].err ? CSSM_ENONFINITE : CSSM_OK;
+      const bool ok = rc_out[k] == CSSM_OK;
+      ll_out[k] = ok ? h_ser[kl].ll : cssm_nan();
+      for (size_t q = 0; q <= T; ++q) {
+        const double* ho = h_out + (lrow + q) * (size_t)rows * 3u;
+        double mean[CSSM_MAX_DIM];
+        for (int cc = 0; cc < d; ++cc) {
+          mean[cc] = ok ? ho[3 * cc] : cssm_nan();
+          if (state_mean) state_mean[(grow + q) * d + cc] = mean[cc];
+          if (state_lower) state_lower[(grow + q) * d + cc] = ok ? ho[3 * cc + 1] : cssm_nan();
+          if (state_upper) state_upper[(grow + q) * d + cc] = ok ? ho[3 * cc + 2] : cssm_nan();
+        }
+        if (eta_lower) eta_lower[grow + q] = ok ? ho[3 * d + 1] : cssm_nan();
+        if (eta_upper) eta_upper[grow + q] = ok ? ho[3 * d + 2] : cssm_nan();
+        if (eta_of_mean) eta_of_mean[grow + q] = ok ? cssm_eta_of_mean(f->models[k], h_fco + (lrow + q) * (size_t)d, mean) : cssm_nan();   // :420
+      }
+    }
+  }
+  f->ms_ip[0] = ms[0]; f->ms_ip[1] = ms[1]; f->ip_ran = true;
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_interpolate_last_ms(cssm_fleet* f, double* ms2) {
+  if (!f || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (!f->ip_ran) return fail(CSSM_ESTATE, "no interpolation has run on this fleet (cssm_fleet_interpolate first)");
+  ms2[0] = f->ms_ip[0]; ms2[1] = f->ms_ip[1];
   return CSSM_OK;
 }
 

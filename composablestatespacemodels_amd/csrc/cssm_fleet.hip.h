@@ -58,6 +58,15 @@ struct FleetArgs {
   const uint32_t* picks;             // per record of the launch: StepRec::pick, the slot sampleOne takes after that observation
   double* path;                      // may be null; series k owns rows off[k] + k .. off[k + 1] + k (T_k + 1 rows of d), preset to NaN
   double* last;                      // [S][d], preset to NaN: row T_k of series k's path
+  // cssm_fleet_interpolate's forward pass (k_fleet_series<D, false, true> only), again behind every field the other instantiations read.
+  // The launch's blocks are a CHUNK of series: off / recs / hser are the chunk's own (block b owns the records off[b] .. off[b + 1] - 1),
+  // par is the fleet's (series k0 + b).  Block b keeps every cloud and every ancestor array of its series: slices off[b] + b .. off[b + 1]
+  // + b of `hist` ([d][n] doubles each) and of `hanc` ([n] each) -- slice 0 the initial cloud, slice s + 1 the cloud record s wrote and
+  // (behind a weighted record) the ancestors that resampled it.  state / anc / ser / ctl / ll_t / ess_t are not touched.
+  double* hist;
+  uint32_t* hanc;
+  FleetSeries* hser;                 // [series of the chunk]: ll, err, fail_rec of the forward pass
+  uint32_t k0;
 };
 
 // a - b mod 2^128 (integers: exact)
@@ -87,7 +96,10 @@ __device__ __forceinline__ void fleet_path_row(const double* buf, const uint32_t
 // PATH: `filter` (:152-158) -- a launch that draws the initial cloud also records one particle of it and one of the cloud after every
 // record (FleetArgs::picks / path / last).  A template flag: the instantiation cssm_fleet_ll_filter and cssm_fleet_step run holds no
 // trace of it (the resource table).
-template <int D, bool PATH>
+// HIST: the forward pass of cssm_fleet_interpolate (FilterInterpolate, model/ParticleFilter.scala:273-311) -- the same statements, but
+// every cloud and every weighted record's ancestors are kept (FleetArgs::hist / hanc) instead of ping-ponging two buffers, and nothing
+// the fleet holds per series is written.  A template flag as PATH is: the other two instantiations hold no trace of it either.
+template <int D, bool PATH, bool HIST = false>
 __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_series(const FleetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   __shared__ StepRec s_rec;
@@ -99,15 +111,15 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   double* s_lw = reinterpret_cast<double*>(s_dyn);
   uint32_t* s_anc = reinterpret_cast<uint32_t*>(s_dyn + (size_t)((n + 1u) & ~1u) * 8u);
   const unsigned long long r0 = a.off[k], r1 = a.off[k + 1];
-  const uint32_t ctl = a.ctl[k];
-  if (!(ctl & CSSM_FLEET_CTL_INIT) && r0 >= r1) return;      // (uniform) nothing for this series in this launch: untouched
+  const uint32_t ctl = HIST ? CSSM_FLEET_CTL_INIT : a.ctl[k];   // (HIST: a series is always run from its initial cloud)
+  if ((HIST || !(ctl & CSSM_FLEET_CTL_INIT)) && r0 >= r1) return;   // (uniform) nothing for this series in this launch: untouched
   const double* tab = stage_log_table(a.logtab);
-  const FleetPar* par = a.par + k;
+  const FleetPar* par = a.par + (HIST ? a.k0 + k : k);
   const uint64_t seed = par->seed;
-  double* st = a.state + (size_t)k * 2u * D * n;
-  uint32_t* ganc = a.anc + (size_t)k * n;
+  double* st = HIST ? a.hist + (size_t)(r0 + k) * D * n : a.state + (size_t)k * 2u * D * n;   // (HIST: slice 0 of the series)
+  uint32_t* ganc = HIST ? a.hanc + (size_t)(r0 + k) * n : a.anc + (size_t)k * n;              // (HIST: ancestor slice 0, never written)
   double ll; int32_t ess; uint32_t err = 0u, fail_rec = 0u;
-  if (ctl & CSSM_FLEET_CTL_INIT) {
+  if (HIST || (ctl & CSSM_FLEET_CTL_INIT)) {
     // initialiseState (:105-108): x0 = sqrt(c0) z + m0 into buffer 0, identity ancestors, ll = 0, ess = N
     for (uint32_t i = tid; i < n; i += bs) {
       double z[D];
@@ -155,8 +167,8 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     const StepRec* rec = &s_rec;
     const uint32_t step = rec->step;
     const bool weighted = rec->has_obs != 0;
-    const double* src = st + (size_t)(step & 1u) * D * n;
-    double* dst = st + (size_t)((step & 1u) ^ 1u) * D * n;
+    const double* src = st + (size_t)(HIST ? (uint32_t)(r - r0) : (step & 1u)) * D * n;
+    double* dst = st + (size_t)(HIST ? (uint32_t)(r - r0) + 1u : ((step & 1u) ^ 1u)) * D * n;
     if (PATH) cur = (step & 1u) ^ 1u;
     // 1. gather through the previous ancestors, transition, f, log-density (:118, :123)
     double tmax = -cssm_inf();
@@ -179,7 +191,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     if (!weighted) {                                            // (uniform) the None branch (:121): the cloud moves, nothing else
       __syncthreads();
       for (uint32_t i = tid; i < n; i += bs) s_anc[i] = i;
-      if (tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
+      if (!HIST && tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
       continue;
     }
     // 2. the block's own max is at hand before any weight is formed: the level is chosen in place
@@ -243,13 +255,19 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
       if (lane == 63u) s_wm[wid] = incl;
       __syncthreads();
       for (uint32_t w = 0; w < wid; ++w) carry = (s_wm[w] > carry) ? s_wm[w] : carry;
+      uint32_t* hslice = HIST ? ganc + (size_t)((uint32_t)(r - r0) + 1u) * n : nullptr;   // (HIST) the ancestors that resampled slice s + 1
       for (uint32_t s = j0; s < j1; ++s) {
         const uint32_t v = s_anc[s];
         carry = (v > carry) ? v : carry;
         s_anc[s] = carry;
+        if (HIST) hslice[s] = carry;
       }
     }
-    if (tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
+    if (!HIST && tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
+  }
+  if (HIST) {                                                   // the fleet's ancestors and scalars stay as they were
+    if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.hser[k] = o; }
+    return;
   }
   __syncthreads();
   if (PATH && !err && r1 > r0) {                               // (uniform) the last row: no record follows to write it
@@ -265,6 +283,7 @@ struct FleetLaunch {
   FleetArgs args;
   uint32_t n_series;
   bool path;            // k_fleet_series<D, true>
+  bool hist = false;    // k_fleet_series<D, false, true>: n_series blocks, the series args.k0 .. args.k0 + n_series - 1
   int threads;
   size_t lds;
   hipStream_t stream;

@@ -416,17 +416,18 @@ class NativePfFleet:
         _abi.check(self.lib.cssm_fleet_set_option(self._h, int(option), int(value)))
 
     @staticmethod
-    def pack(datas):
+    def pack(datas, allow_empty: bool = False):
         """The ragged arrays of ``cssm_fleet_ll_filter`` from a sequence of ``(t, y, has)`` triples (``has`` may be None = all
         observed): ``(off uint64[S + 1], t, y, has uint8)``, C-contiguous.  An empty series is refused here, before any device call
-        (the reference's ``minBy`` throws on an empty Vector)."""
+        (the reference's ``minBy`` throws on an empty Vector) -- unless ``allow_empty`` (``interpolate``: the series' own status says
+        so, the others run)."""
         off = np.zeros(len(datas) + 1, dtype=np.uint64)
         ts, ys, hs = [], [], []
         for k, tr in enumerate(datas):
             t, y = np.asarray(tr[0], dtype=np.float64).ravel(), np.asarray(tr[1], dtype=np.float64).ravel()
             h = tr[2] if len(tr) > 2 else None
             h = np.ones(len(t), dtype=np.uint8) if h is None else np.asarray(h, dtype=np.uint8).ravel()
-            if len(t) == 0:
+            if len(t) == 0 and not allow_empty:
                 raise ValueError(f"series {k} has no records (the reference's minBy throws on an empty Vector)")
             if len(y) != len(t) or len(h) != len(t):
                 raise ValueError(f"series {k}: t, y and has differ in length")
@@ -491,6 +492,39 @@ class NativePfFleet:
         o = [int(v) for v in off]
         paths = [path[o[k] + k:o[k + 1] + k + 1] for k in range(self.S)] if want_path else None
         return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], paths, last, rc
+
+    def interpolate(self, datas, interval: float = 0.975, reference_pairing: bool = False):
+        """cssm_fleet_interpolate: ``NativePf.interpolate`` of every series in two launches.  ``(ll[S], per-series list of (mean[T_k + 1,
+        d], lower, upper, eta_of_mean[T_k + 1], eta_lower, eta_upper), rc[S])``; rc[k] != 0 is series k's own status (-6: no records,
+        -5: its weights were unusable) and its arrays and ll read NaN.  The fleet's clouds and clocks are not touched."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        return self.interpolate_packed(*self.pack(datas, allow_empty=True), interval=interval, reference_pairing=reference_pairing)
+
+    def interpolate_packed(self, off, t, y, has, interval: float = 0.975, reference_pairing: bool = False):
+        """``interpolate`` on arrays ``pack`` made (a caller that interpolates the same fleet repeatedly packs once)."""
+        R = self._check_packed(off, t, y, has)
+        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
+        m, lo, hi = (np.zeros((R + self.S, self.d)) for _ in range(3))
+        em, el, eu = (np.zeros(R + self.S) for _ in range(3))
+        tt, yy, hh = (t, y, has) if R else (np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.uint8))
+        _abi.check(self.lib.cssm_fleet_interpolate(self._h, _p(off, C.POINTER(C.c_uint64)), _p(tt), _p(yy), _p(hh, C.POINTER(C.c_uint8)),
+                                                   float(interval), _abi.CSSM_INTERP_REFERENCE_PAIRING if reference_pairing else 0, _p(ll),
+                                                   _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu), _p(rc, C.POINTER(C.c_int))))
+        return ll, self.interpolate_rows(off, (m, lo, hi, em, el, eu)), rc
+
+    @staticmethod
+    def interpolate_rows(off, arrays):
+        """Series k's rows of ``cssm_fleet_interpolate``'s outputs: ``off[k] + k .. off[k + 1] + k`` (T_k + 1 rows, row 0 the initial
+        cloud) of every array, per series."""
+        o = [int(v) for v in off]
+        return [tuple(a[o[k] + k:o[k + 1] + k + 1] for a in arrays) for k in range(len(o) - 1)]
+
+    def interpolate_last_ms(self) -> Tuple[float, float]:
+        """Device time (HIP events) of the last interpolation's forward launch and lineage launch, ms, summed over its chunks."""
+        ms = np.zeros(2)
+        _abi.check(self.lib.cssm_fleet_interpolate_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1])
 
     def pmmh_last_split(self):
         """cssm_fleet_pmmh_last_split: milliseconds of the last ``cssm_fleet_pmmh_run`` on this fleet, summed over its iterations --
@@ -995,11 +1029,8 @@ class FilterInterpolate(_FilterBase):
     def interpolate(self, data: Sequence[TimedObservation], particles: int, interval: float = 0.975,
                     reference_pairing: bool = False) -> Tuple[float, List[PfOut]]:
         t, y, h = split_data(data)
-        ll, m, lo, hi, em, el, eu = self._ensure(particles).interpolate(t, y, h, interval, reference_pairing)
-        times = [float(np.min(t))] + [float(v) for v in t]
-        obs = [None] + [d.observation for d in data]
-        return ll, [PfOut(times[k], obs[k], float(em[k]), CredibleInterval(float(el[k]), float(eu[k])), m[k].copy(),
-                          [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k], hi[k])]) for k in range(len(times))]
+        ll, *arrays = self._ensure(particles).interpolate(t, y, h, interval, reference_pairing)
+        return ll, _interpolate_outs(data, t, arrays)
 
 
 @dataclass(frozen=True)
@@ -1111,6 +1142,20 @@ class FilterFleet:
             times = [float(np.min(t))] + [float(v) for v in t]
             out.append((float(ll[k]), [StateSpace(tt, paths[k][i].copy()) for i, tt in enumerate(times)]))
         return out
+
+    def interpolate(self, datas: Sequence[Sequence[TimedObservation]], interval: float = 0.975,
+                    reference_pairing: bool = False) -> List[Tuple[float, List[PfOut]]]:
+        """``FilterInterpolate(mods[k], resample).interpolate(datas[k], n)`` of every series in one device call (two launches): per series
+        ``(ll, [PfOut])`` of length T_k + 1.  The fleet's current states stay valid: the clouds are not touched."""
+        split = [split_data(d) for d in datas]
+        ll, rows, rc = self._fleet.interpolate(split, float(interval), reference_pairing)
+        for k in range(self.S):
+            if rc[k]:
+                raise _abi.CssmError(int(rc[k]), f"series {k}: " + ("it has no records" if rc[k] == _abi.CSSM_EINVAL_ARG else "its weights were unusable"))
+        return [(float(ll[k]), _interpolate_outs(datas[k], split[k][0], rows[k])) for k in range(self.S)]
+
+    def interpolate_last_ms(self) -> Tuple[float, float]:
+        return self._fleet.interpolate_last_ms()
 
     def forecast(self, times, interval: float = 0.975, seed: Optional[int] = None) -> List[List[ForecastOut]]:
         """``ParticleFilter.forecast`` of every series from its current state, all of them in one device call: ``times[k]`` = series k's
@@ -1273,6 +1318,16 @@ class ParticleFilter:
     @staticmethod
     def mean(s: Sequence[float]) -> float:  # :522-524
         return float(np.sum(s)) / len(s)
+
+
+def _interpolate_outs(data: Sequence[TimedObservation], t, arrays) -> List[PfOut]:
+    """The ``PfOut`` list of one interpolated series (examples/Interpolate.scala:42-44) from ``(mean[T + 1, d], lower, upper,
+    eta_of_mean[T + 1], eta_lower, eta_upper)``: entry 0 at the smallest time without an observation, entry s + 1 datum s."""
+    m, lo, hi, em, el, eu = arrays
+    times = [float(np.min(t))] + [float(v) for v in t]
+    obs = [None] + [d.observation for d in data]
+    return [PfOut(times[k], obs[k], float(em[k]), CredibleInterval(float(el[k]), float(eu[k])), m[k].copy(),
+                  [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k], hi[k])]) for k in range(len(times))]
 
 
 def _forecast_outs(times: Sequence[float], r) -> List[ForecastOut]:

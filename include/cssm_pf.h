@@ -313,6 +313,10 @@ int cssm_pf_stream_idle(cssm_pf* pf);
  * workgroup -- 0: chosen by N (today: the sort at every N), 1: a bitonic sort of the row's keys in LDS, 2: a radix select over them in LDS.  Both are exact: the
  * results do not depend on it (tests/test_gpu_fleet_forecast.py); it exists for measurements. */
 #define CSSM_OPT_FLEET_SELECT 12
+/* CSSM_OPT_INTERP_CAP (fleets only, cssm_fleet_set_option; value in KiB; default 0 = 1 GiB, negative refused): cssm_fleet_interpolate runs the
+ * fleet in chunks of series whose lineage history ((T_k + 1) x N x (8 d + 4) bytes per series) fits in this many KiB -- one series at
+ * least per chunk, never a part of one.  Results do not depend on it (tests lower it to run the chunked path on a small fleet). */
+#define CSSM_OPT_INTERP_CAP 13
 int cssm_pf_set_option(cssm_pf* pf, int option, int value);
 /* Counters of the run-time specialisation in this process: out4 = {kernels compiled, kernels loaded from the disk cache, launches of
  * run-time-compiled kernels, failures (each reported once on stderr)}. */
@@ -785,7 +789,8 @@ int cssm_fleet_set_params(cssm_fleet* f, const cssm_model_desc* const* descs);
 int cssm_fleet_reseed(cssm_fleet* f, const uint64_t* seeds);
 /* CSSM_OPT_RESAMPLER, and only CSSM_RESAMPLE_SYSTEMATIC: any other resampler is CSSM_EINVAL_ARG with the reason (the
  * `Resample[A]` a FilterFleet is constructed with goes through here); CSSM_OPT_FORECAST_CAP (KiB, 0 = 1 GiB, negative refused): the
- * samples cssm_fleet_forecast / cssm_fleet_forecast_posterior hold on the device at a time; CSSM_OPT_FLEET_SELECT.  Every other option
+ * samples cssm_fleet_forecast / cssm_fleet_forecast_posterior hold on the device at a time; CSSM_OPT_FLEET_SELECT; CSSM_OPT_INTERP_CAP
+ * (KiB, 0 = 1 GiB, negative refused): the lineage history cssm_fleet_interpolate holds on the device at a time.  Every other option
  * is CSSM_EINVAL_ARG. */
 int cssm_fleet_set_option(cssm_fleet* f, int option, int value);
 
@@ -915,6 +920,36 @@ int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_desc* desc,
                                   double* eta_mean, double* eta_lower, double* eta_upper,
                                   double* obs_mean, double* obs_lower, double* obs_upper,
                                   double* samples, uint32_t* pick_out, int* rc_out);
+/* FilterInterpolate (model/ParticleFilter.scala:273-311, examples/Interpolate.scala:31-44) of every series: cssm_pf_interpolate on a
+ * handle of its own, cssm_pf_create(descs[k], N, seeds[k]), per series -- in two launches for the whole fleet: a forward pass that keeps
+ * every cloud and every weighted record's ancestors of a series ((T_k + 1) x N x (8 d + 4) bytes, the single handle's figure), one
+ * workgroup per series, and a backward pass that composes the lineages surviving to the end of the series and summarises them per time
+ * index, one workgroup per (series, row).  off / t / y / has_obs are ragged as for cssm_fleet_ll_filter (series k owns the records
+ * off[k] .. off[k + 1] - 1, its t0 is its slice's smallest time); the outputs are laid out like cssm_fleet_filter's path_out: series k owns
+ * the rows off[k] + k .. off[k + 1] + k (T_k + 1 rows, row 0 the initial cloud), state_* = [off[S] + S][d], eta_* = [off[S] + S]; any of
+ * them may be null, ll_out[S] and rc_out[S] may not.  flags: 0 or CSSM_INTERP_REFERENCE_PAIRING, as for cssm_pf_interpolate.
+ * ll_out[k] and every order statistic (state_lower / upper, eta_lower / upper) have the single handle's bits; the means are plain fp64
+ * sums whose order of summation may differ, eta_of_mean = link(f(mean, time)) is formed on the host from the mean as there.
+ *
+ * The fleet is only LENT: its device, stream, contract table, N, structure, parameters and keys.  The clouds, ancestors, clocks,
+ * observation indices and statuses of its series stay as they were -- a following cssm_fleet_step / _summary / _forecast returns what it
+ * would have returned without this call, and a fleet that was never initialised serves it.  (The single handle borrows its own buffers
+ * and must be re-initialised; the fleet's history lives in a slab of its own.)
+ *
+ * rc_out[S] = the series' OWN status: CSSM_EINVAL_ARG for a series without records (its single row and ll_out[k] read NaN),
+ * CSSM_ENONFINITE when its weights were unusable at some observation (all its rows and ll_out[k] read NaN: the single handle returns no
+ * summaries then either); every other series is bit for bit what it is without that one.  The call itself fails, before the fleet is
+ * looked at, for a null off / ll_out / rc_out / t / y / f, off[0] != 0, interval outside (0, 1] or unknown flag bits, and for a
+ * decreasing off (CSSM_EINVAL_ARG); CSSM_ENOMEM and HIP failures fail it too.  The fleet runs in chunks of series whose history fits
+ * CSSM_OPT_INTERP_CAP (a series is never split; one larger than the cap runs alone, and CSSM_ENOMEM names it if it does not fit the
+ * device): per chunk one upload, the two launches, one read-back. */
+int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                           double interval, int flags, double* ll_out,
+                           double* state_mean, double* state_lower, double* state_upper,
+                           double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out);
+/* ms2[0] = device time of the forward launch, ms2[1] = of the lineage launch of the last cssm_fleet_interpolate, each summed over its
+ * chunks (HIP events on the fleet's stream).  CSSM_ESTATE before the first interpolation.  The array holds TWO doubles. */
+int cssm_fleet_interpolate_last_ms(cssm_fleet* f, double* ms2);
 /* Observations series k's current cloud has seen (the Philox counter word of its next step); 0 for a null fleet or k >= S, the
  * convention of cssm_pf_observation_index. */
 uint64_t cssm_fleet_observation_index(const cssm_fleet* f, uint32_t k);
