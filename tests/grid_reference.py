@@ -30,6 +30,10 @@ exactly from the Gaussian tails and reported.
 
 The error bound: the same computation with every spacing divided by 1.5; the bound is the absolute difference of the two
 (likelihood, means, quantiles), and the finer result is the one returned.
+
+The smoothers: the fixed-interval smoothing distributions p(x_s | y_1..T) that the rows of interpolate converge to (row 0 the initial
+state at min(t), row s+1 the state at t[s]) -- `rts` in closed form for the Gaussian-observation models, `grid_smoother` /
+`smoother_reference` by a backward pass over the grids and matrices the forward pass built, with the same error-bound conventions.
 """
 from __future__ import annotations
 
@@ -253,7 +257,10 @@ def _quantiles(a, f, qs, up=64):
     return [float(np.interp(q, c, x)) for q in qs]
 
 
-def grid_filter(spec: Spec, t, y, has, lgcp_precision=0, refine=1.0, budget=POINT_BUDGET) -> GridResult:
+def grid_filter(spec: Spec, t, y, has, lgcp_precision=0, refine=1.0, budget=POINT_BUDGET, keep=None) -> GridResult:
+    """`keep`: a list that receives what a backward pass needs (grid_smoother) -- first (axes, density) of the initial state, then
+    per datum (axes, post-observation density, per-axis matrices of the move or None, potential or None).  The filter's own
+    arithmetic does not depend on it."""
     t = np.asarray(t, dtype=np.float64); y = np.asarray(y, dtype=np.float64)
     has = np.ones(len(t), dtype=bool) if has is None else np.asarray(has).astype(bool)
     d, lgcp = spec.d, spec.obs == "lgcp"
@@ -282,7 +289,7 @@ def grid_filter(spec: Spec, t, y, has, lgcp_precision=0, refine=1.0, budget=POIN
         pm, pv = A * m + b, A * A * v + q
         hn = _spacing(np.sqrt(pv), h_rule, budget)
         hos = max(hos, float(np.max(hn / np.sqrt(q))))
-        new_axes, p, out = [], G.p, 0.0
+        new_axes, p, out, Ks = [], G.p, 0.0, []
         for k in range(d):
             ax = _axis(pm[k], math.sqrt(pv[k]), hn[k])
             src = G.axes[k]
@@ -294,10 +301,11 @@ def grid_filter(spec: Spec, t, y, has, lgcp_precision=0, refine=1.0, budget=POIN
             tail = ndtr((ax[0] - 0.5 * hn[k] - mu) / s) + ndtr((mu - ax[-1] - 0.5 * hn[k]) / s)
             out += float((G.marginal(k) * (src[1] - src[0]) * tail).sum())
             new_axes.append(ax)
+            Ks.append(K)
         lost = max(lost, out)
         Gn = _Grid(new_axes, p)
         points = max(points, p.size)
-        return Gn
+        return Gn, Ks
 
     def normalise(G):
         z = float(G.p.sum()) * G.vol
@@ -307,14 +315,19 @@ def grid_filter(spec: Spec, t, y, has, lgcp_precision=0, refine=1.0, budget=POIN
     T = len(t)
     ll, now = 0.0, float(t.min())
     ll_t, mean, lo, hi = np.zeros(T), np.zeros((T, d)), np.zeros((T, d)), np.zeros((T, d))
+    if keep is not None:
+        if lgcp:
+            raise ValueError("no backward pass for the LGCP: interpolate refuses it")
+        keep.append((G.axes, G.p))
     for s in range(T):
+        Ks, pot = None, None
         dt = float(t[s]) - now
         if lgcp:
             if dt != 0:
                 nsub = int(math.ceil(dt / delta))
                 tau = float(t[s])
                 for _ in range(nsub):
-                    G = move(G, delta)
+                    G = move(G, delta)[0]
                     tau = tau + delta
                     G.p *= np.exp(-np.exp(G.gamma(spec.H(tau))) * delta)
                     ll += normalise(G)
@@ -322,17 +335,20 @@ def grid_filter(spec: Spec, t, y, has, lgcp_precision=0, refine=1.0, budget=POIN
                 ll += normalise(G)
         else:
             if dt != 0:
-                G = move(G, dt)
+                G, Ks = move(G, dt)
             if has[s]:
                 lg = log_potential(spec.obs, spec.scale, spec.df, G.gamma(spec.H(float(t[s]))), float(y[s]))
                 mx = float(np.max(lg))
-                G.p = G.p * np.exp(lg - mx)
+                pot = np.exp(lg - mx)
+                G.p = G.p * pot
                 ll += mx + normalise(G)
         now = float(t[s])
         ll_t[s] = ll
         mean[s] = G.moments()[0]
         for k in range(d):
             lo[s, k], hi[s, k] = _quantiles(G.axes[k], G.marginal(k), QUANTILES)
+        if keep is not None:                                       # (no kept array is written in place afterwards)
+            keep.append((G.axes, G.p, Ks, pot))
     return GridResult(ll_t, mean, lo, hi, lost, points, hos)
 
 
@@ -394,3 +410,126 @@ def kalman(spec: Spec, t, y, has=None):
         now = float(t[s])
         ll_t[s], means[s], vars_[s] = ll, m, np.diag(P)
     return ll_t, means, vars_
+
+
+def _gaussian_forward(spec: Spec, t, y, has):
+    """The forward pass of `kalman` with what a backward pass needs kept: filtering means [T+1, d] and full covariances
+    [T+1, d, d] (row 0 the initial state at min(t), row s+1 after datum s) and each step's (A, b, q)."""
+    if spec.obs not in ("linear", "seasonal"):
+        raise ValueError("Kalman needs a Gaussian observation")
+    t = np.asarray(t, dtype=np.float64)
+    has = np.ones(len(t), dtype=bool) if has is None else np.asarray(has).astype(bool)
+    r = math.exp(spec.scale) ** 2
+    d, T = spec.d, len(t)
+    m, P = spec.m0.copy(), np.diag(spec.c0)
+    now = float(t.min())
+    means, covs, steps = np.zeros((T + 1, d)), np.zeros((T + 1, d, d)), []
+    means[0], covs[0] = m, P
+    for s in range(T):
+        dt = float(t[s]) - now
+        A, b, q = spec.transition(dt) if dt != 0 else (np.ones(d), np.zeros(d), np.zeros(d))   # dt = 0 is the identity
+        m = A * m + b
+        P = A[:, None] * P * A[None, :] + np.diag(q)
+        if has[s]:
+            H = spec.H(float(t[s]))
+            S = float(H @ P @ H) + r
+            K = P @ H / S
+            m = m + K * (float(y[s]) - float(H @ m))
+            P = P - np.outer(K, H @ P)
+            P = 0.5 * (P + P.T)
+        now = float(t[s])
+        means[s + 1], covs[s + 1] = m, P
+        steps.append((A, b, q))
+    return means, covs, steps
+
+
+def rts(spec: Spec, t, y, has=None):
+    """The Rauch-Tung-Striebel fixed-interval smoother of a Gaussian-observation model: smoothed means [T+1, d] and full
+    covariances [T+1, d, d] of p(x_s | y_1..T); row 0 is the initial state at min(t), row s+1 the state at t[s]."""
+    mf, Pf, steps = _gaussian_forward(spec, t, y, has)
+    ms, Ps = mf.copy(), Pf.copy()
+    for s in range(len(steps) - 1, -1, -1):
+        A, b, q = steps[s]
+        mp = A * mf[s] + b
+        Pp = A[:, None] * Pf[s] * A[None, :] + np.diag(q)
+        G = np.linalg.solve(Pp, A[:, None] * Pf[s]).T              # P_f A' Pp^-1 (both symmetric)
+        ms[s] = mf[s] + G @ (ms[s + 1] - mp)
+        Ps[s] = Pf[s] + G @ (Ps[s + 1] - Pp) @ G.T
+        Ps[s] = 0.5 * (Ps[s] + Ps[s].T)
+    return ms, Ps
+
+
+def gamma_moments(spec: Spec, mean, cov, time):
+    """Mean and sd of gamma = H(time) . x for x ~ N(mean, cov)."""
+    H = spec.H(float(time))
+    return float(H @ mean), math.sqrt(float(H @ cov @ H))
+
+
+# ------------------------------------------------------------------------------------------------ the grid smoother
+@dataclass
+class SmoothResult:
+    mean: np.ndarray                 # [T+1, d] smoothed means; row 0 the initial state at min(t), row s+1 the state at t[s]
+    lo: np.ndarray                   # [T+1, d] 2.5 % marginal quantiles
+    hi: np.ndarray                   # [T+1, d] 97.5 % marginal quantiles
+    filter: GridResult               # the forward pass: exactly what grid_filter returns
+    mean_err: np.ndarray = field(default=None)    # refinement bounds (filled by `smoother_reference`)
+    lo_err: np.ndarray = field(default=None)
+    hi_err: np.ndarray = field(default=None)
+
+
+def grid_smoother(spec: Spec, t, y, has, refine=1.0, budget=POINT_BUDGET) -> SmoothResult:
+    """The fixed-interval smoothing distributions p(x_s | y_1..T) on the grids of grid_filter: its forward pass, then
+    beta_T = 1, beta_s(x) = sum_i N(x'_i; A x + b, q) h'_i g_s(x'_i) beta_{s+1}(x'_i) per axis (the forward matrices
+    transposed, with the new grid's spacing in place of the old one's), renormalised by its maximum;
+    smoothed_s = filtered_s beta_s."""
+    if spec.obs == "lgcp":
+        raise ValueError("no smoother for the LGCP: interpolate refuses it")
+    keep = []
+    f = grid_filter(spec, t, y, has, 0, refine, budget, keep=keep)
+    T, d = len(keep) - 1, spec.d
+    mean, lo, hi = np.zeros((T + 1, d)), np.zeros((T + 1, d)), np.zeros((T + 1, d))
+
+    def summarise(row, axes, p):
+        G = _Grid(axes, p)
+        mean[row] = G.moments()[0]
+        for k in range(d):
+            lo[row, k], hi[row, k] = _quantiles(axes[k], G.marginal(k), QUANTILES)
+
+    beta = np.ones_like(keep[T][1])
+    summarise(T, keep[T][0], keep[T][1])
+    for s in range(T - 1, -1, -1):                                  # the step from row s to row s + 1 is datum s
+        axes_new, _, Ks, pot = keep[s + 1]
+        axes_old, p_old = keep[s][0], keep[s][1]
+        keep[s + 1] = None
+        if pot is not None:
+            beta = beta * pot
+        if Ks is not None:
+            for k in range(d):
+                B = Ks[k].T * ((axes_new[k][1] - axes_new[k][0]) / (axes_old[k][1] - axes_old[k][0]))
+                beta = np.moveaxis(np.tensordot(B, beta, axes=([1], [k])), 0, k)
+        beta = beta / float(np.max(beta))
+        summarise(s, axes_old, p_old * beta)
+    return SmoothResult(mean, lo, hi, f)
+
+
+_SMOOTH_CACHE: Dict[tuple, SmoothResult] = {}
+
+
+def smoother_reference(model, t, y, has=None, budget=POINT_BUDGET) -> SmoothResult:
+    """The grid smoother at spacing h and h / 1.5; returns the finer result with error bounds by `reference`'s conventions
+    (means: the absolute difference; quantiles: three times the difference + 1e-5), its `filter` with `reference`'s bounds.
+    Cached per (model, series)."""
+    key = _key(model, t, y, has, 0) + (budget,)
+    if key not in _SMOOTH_CACHE:
+        spec = spec_of(model)
+        a = grid_smoother(spec, t, y, has, 1.0, budget)
+        b = grid_smoother(spec, t, y, has, REFINE, budget=budget * REFINE ** spec.d)
+        b.mean_err = np.abs(b.mean - a.mean)
+        b.lo_err, b.hi_err = 3.0 * np.abs(b.lo - a.lo) + 1e-5, 3.0 * np.abs(b.hi - a.hi) + 1e-5
+        fa, fb = a.filter, b.filter
+        fb.ll_err = np.abs(fb.ll_t - fa.ll_t)
+        fb.mean_err = np.abs(fb.mean - fa.mean)
+        fb.lo_err, fb.hi_err = 3.0 * np.abs(fb.lo - fa.lo) + 1e-5, 3.0 * np.abs(fb.hi - fa.hi) + 1e-5
+        fb.lost = max(fa.lost, fb.lost)
+        _SMOOTH_CACHE[key] = b
+    return _SMOOTH_CACHE[key]

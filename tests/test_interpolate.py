@@ -3,7 +3,11 @@
 CPU: the oracle's literal restatement (particles ARE paths; a weighted step copies whole paths) against an
 independent reconstruction from the per-step ancestor arrays of the plain filter.
 GPU: cssm_pf_interpolate (ancestor history on the device, genealogy composed backwards) against the oracle --
-order statistics bit-exact, means within 1e-12 (the device sums in a different order)."""
+order statistics bit-exact, means within 1e-12 (the device sums in a different order).
+
+Both sides here share one statement of which cloud a row summarises and of how the ancestors compose.  That statement itself is
+held to an exact fixed-interval smoother (RTS, a grid smoother) in tests/test_grid_smoother.py (the oracle) and
+tests/test_gpu_grid_smoother.py (the handle, with the stratified and the multinomial resampler too)."""
 import numpy as np
 import pytest
 
