@@ -410,6 +410,16 @@ __device__ __forceinline__ double gamma_of(const ModelK& mk, const StepRec* __re
   return gamma_coef<D>(mk, rec->fco, x);
 }
 
+// link of the observing leaf (model/Model.scala:24,183,269,296,318-326,345)
+__device__ __forceinline__ double link_of(int obs_kind, double g) {
+  switch (obs_kind) {
+    case CSSM_OBS_POISSON: case CSSM_OBS_NEGBIN: case CSSM_OBS_ZIP: return cssm_exp(g);
+    case CSSM_OBS_BERNOULLI: return (g > 6.0) ? 1.0 : ((g < -6.0) ? 0.0 : 1.0 / (1.0 + cssm_exp(-g)));
+    case CSSM_OBS_BETA: return cssm_exp(-g);
+    default: return g;
+  }
+}
+
 // dataLikelihood(gamma, y) of the leftmost leaf; the branch is wave-uniform (mk is a kernel argument).
 // Constants c[] per observation kind are listed in build_rec (cssm_pf.hip); the oracle states the same
 // expressions with the reference's line numbers (oracle/cssm_oracle.c, logdens).

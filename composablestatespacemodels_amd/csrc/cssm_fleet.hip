@@ -45,6 +45,7 @@ struct cssm_fleet {
   unsigned char* d_stage = nullptr; size_t stage_cap = 0;
   double* d_ll_t = nullptr; int32_t* d_ess_t = nullptr; size_t res_cap = 0;
   double* d_tmp = nullptr;              // d x n: cssm_fleet_get_particles
+  double* d_iv = nullptr; size_t iv_cap = 0;       // cssm_fleet_filter_intervals / _step_intervals, grow-only: rows of [d + 1][3] (mean, lower, upper)
   double* d_path = nullptr; size_t path_cap = 0;   // cssm_fleet_filter, grow-only: [S][d] last rows, then (asked for) the R + S rows of the paths
   float ms_upload = -1.f, ms_kernel = -1.f;        // ... of its last launch
   double ms_build = 0.0;                           // ... host time of its records
@@ -170,7 +171,7 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp, f->d_ip, f->d_ip_hist};
+  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_iv, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp, f->d_ip, f->d_ip_hist};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
   if (f->h_fc) (void)hipHostFree(f->h_fc);
@@ -295,9 +296,17 @@ static int fleet_upload_par(cssm_fleet* f) {
 // staging layout of a launch: [S + 1 offsets (u64)] [S control words (u32), padded to 8 bytes] [R compact records]
 static size_t fleet_stage_head(const cssm_fleet* f) { return ((size_t)f->S + 1u) * 8u + (((size_t)f->S * 4u + 7u) & ~(size_t)7u); }
 
-// (picks: the launch also carries R sampleOne slots, uint32 each, behind the records)
-static int fleet_ensure(cssm_fleet* f, size_t R, bool picks = false) {
-  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d) + (picks ? R * 4u : 0u);
+// What a launch that also writes getIntervals of its clouds carries and brings back (k_fleet_series<D, false, false, true>).
+struct FleetIv {
+  double interval;
+  bool step;                  // one row per series (cssm_fleet_step_intervals), not T_k + 1 rows per series
+  size_t rows = 0;            // of [d + 1][3] doubles: S, or R + S
+  std::vector<double> out;    // the rows as the device left them; NaN where no block wrote
+};
+
+// (picks: the launch also carries R sampleOne slots, uint32 each, behind the records; iv: S x d f coefficients, F at every series' t0)
+static int fleet_ensure(cssm_fleet* f, size_t R, bool picks = false, bool iv = false) {
+  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d) + (picks ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u);
   if (need > f->h_stage_cap) {
     if (f->h_stage) (void)hipHostFree(f->h_stage);
     f->h_stage = nullptr; f->h_stage_cap = 0;
@@ -338,10 +347,20 @@ static int fleet_series_launch(int d, const FleetLaunch& l) {
 
 // upload the staged launch, run it, bring the series' scalars (and, asked for, the per-observation results) back; synchronises.
 // want_path: the staged launch carries its picks and runs k_fleet_series<D, true>; path_out (may be null) / last_out receive the rows.
-static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, bool want_path = false, double* path_out = nullptr, double* last_out = nullptr) {
+// iv: the staged launch carries the f coefficients of every series' t0 behind its records and runs k_fleet_series<D, false, false, true>.
+static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, bool want_path = false, double* path_out = nullptr, double* last_out = nullptr,
+                        FleetIv* iv = nullptr) {
   int rc = fleet_upload_par(f);
   if (rc) return rc;
-  const size_t head = fleet_stage_head(f), recs = R * CSSM_FLEET_REC_BYTES(f->d), bytes = head + recs + (want_path ? R * 4u : 0u);
+  const size_t head = fleet_stage_head(f), recs = R * CSSM_FLEET_REC_BYTES(f->d),
+               bytes = head + recs + (want_path ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u);
+  const size_t n_iv = iv ? iv->rows * (size_t)(f->d + 1) * 3u : 0u;
+  if (n_iv > f->iv_cap) {
+    if (f->d_iv) (void)hipFree(f->d_iv);
+    f->d_iv = nullptr; f->iv_cap = 0;
+    if (hipMalloc(&f->d_iv, (n_iv + n_iv / 4) * 8) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of filtered intervals", n_iv * 8);
+    f->iv_cap = n_iv + n_iv / 4;
+  }
   const size_t n_last = (size_t)f->S * f->d, n_rows = n_last + (path_out ? (R + f->S) * (size_t)f->d : 0u);
   if (want_path && n_rows > f->path_cap) {
     if (f->d_path) (void)hipFree(f->d_path);
@@ -359,6 +378,7 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
     HIP_TRY(hipMemsetAsync(f->d_path, 0xff, n_rows * 8, f->stream));
     HIP_TRY(hipEventRecord(f->ev[6], f->stream));
   }
+  if (iv) HIP_TRY(hipMemsetAsync(f->d_iv, 0xff, n_iv * 8, f->stream));   // ... and the rows it never summarises
   FleetLaunch l;
   l.args.n = f->n; l.args.state = f->state; l.args.anc = f->anc; l.args.ser = f->ser; l.args.par = f->par;
   l.args.off = reinterpret_cast<const unsigned long long*>(f->d_stage);
@@ -369,7 +389,20 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
   l.args.path = (want_path && path_out) ? f->d_path + n_last : nullptr;
   l.args.last = want_path ? f->d_path : nullptr;
   l.args.hist = nullptr; l.args.hanc = nullptr; l.args.hser = nullptr; l.args.k0 = 0u;
+  l.args.iv_fco0 = nullptr; l.args.iv_out = nullptr; l.args.iv_rows = 0u; l.args.iv_np2 = 0u; l.args.iv_rk = FleetRowRanks{0u, 0u, 0u, 0u};
   l.n_series = f->S; l.path = want_path; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+  if (iv) {
+    SelState rs, re;   // the ranks of a state row and of the eta row, as cssm_fleet_summary takes them
+    sel_ranks(rs, f->n, iv->interval, true);
+    sel_ranks(re, f->n, iv->interval, false);
+    uint32_t np2 = 2u;
+    while (np2 < f->n) np2 <<= 1;
+    l.args.iv_fco0 = reinterpret_cast<const double*>(f->d_stage + head + recs);
+    l.args.iv_out = f->d_iv; l.args.iv_rows = iv->step ? 1u : 0u; l.args.iv_np2 = np2;
+    l.args.iv_rk = FleetRowRanks{(uint32_t)rs.rank[0], (uint32_t)rs.rank[1], (uint32_t)re.rank[0], (uint32_t)re.rank[1]};
+    l.ival = true; l.lds = (size_t)np2 * 8u + (size_t)f->n * 4u;   // the keys of a row's sort take the weights' place
+    iv->out.resize(n_iv);
+  }
   rc = fleet_series_launch(f->d, l);
   if (rc) return rc;
   if (want_path) HIP_TRY(hipEventRecord(f->ev[7], f->stream));
@@ -378,6 +411,7 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
   if (want_path && last_out) HIP_TRY(hipMemcpyAsync(last_out, f->d_path, n_last * 8, hipMemcpyDeviceToHost, f->stream));
   if (R && ll_t) HIP_TRY(hipMemcpyAsync(ll_t, f->d_ll_t, R * 8, hipMemcpyDeviceToHost, f->stream));
   if (R && ess_t) HIP_TRY(hipMemcpyAsync(ess_t, f->d_ess_t, R * 4, hipMemcpyDeviceToHost, f->stream));
+  if (n_iv) HIP_TRY(hipMemcpyAsync(iv->out.data(), f->d_iv, n_iv * 8, hipMemcpyDeviceToHost, f->stream));
   HIP_TRY(hipEventRecord(f->ev[1], f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
   if (hipEventElapsedTime(&f->ms_call, f->ev[0], f->ev[1]) != hipSuccess) f->ms_call = -1.f;
@@ -391,7 +425,7 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
 // llFilter / filter of every series: the records of all of them built (threaded above 8192), ONE upload, ONE launch, ONE read-back.
 // want_path: `filter` -- the sampleOne slots travel behind the records, path_out (may be null) and last_out (may be null) are written.
 static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double* ll_out, double* ll_t,
-                            int32_t* ess_t, bool want_path, double* path_out, double* last_out, int* rc_out) {
+                            int32_t* ess_t, bool want_path, double* path_out, double* last_out, int* rc_out, FleetIv* iv = nullptr) {
   const uint32_t S = f->S;
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
   for (uint32_t k = 0; k < S; ++k)
@@ -401,23 +435,30 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
   if (R && (!t || !y)) return fail(CSSM_EINVAL_ARG, "null data");
   HIP_TRY(hipSetDevice(f->device));
   const auto tb0 = std::chrono::steady_clock::now();
-  int rc = fleet_ensure(f, R, want_path);
+  int rc = fleet_ensure(f, R, want_path, iv != nullptr);
   if (rc) return rc;
   unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
   uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
   unsigned char* h_recs = f->h_stage + fleet_stage_head(f);
   const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
   uint32_t* h_picks = want_path ? reinterpret_cast<uint32_t*>(h_recs + R * RB) : nullptr;
+  double* h_fco0 = iv ? reinterpret_cast<double*>(h_recs + R * RB) : nullptr;   // (a launch carries picks or these, never both)
   for (uint32_t k = 0; k <= S; ++k) h_off[k] = off[k];
   std::vector<double> t0(S, 0.0);
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
       h_ctl[k] = (b > a) ? CSSM_FLEET_CTL_INIT : 0u;
+      if (h_fco0) for (int c = 0; c < f->d; ++c) h_fco0[k * f->d + c] = 0.0;
       if (b == a) continue;
       double m = t[a];
       for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;      // data.minBy(_.t).t
       t0[k] = m;
+      if (h_fco0) {                                                      // F(t0): t0 need not be the first record's time
+        StepRec r0;
+        cssm_build_rec(&f->models[k], m, m, 0.0, 0, 0u, &r0);
+        for (int c = 0; c < f->d; ++c) h_fco0[k * f->d + c] = r0.fco[c];
+      }
       double tp = m;
       for (size_t s = a; s < b; ++s) {
         fleet_pack_rec(f->models[k], tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), h_recs + s * RB, h_picks ? h_picks + s : nullptr);
@@ -426,7 +467,8 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
     }
   });
   if (want_path) f->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-  rc = fleet_launch(f, R, ll_t, ess_t, want_path, path_out, last_out);
+  if (iv) { iv->step = false; iv->rows = R + S; }
+  rc = fleet_launch(f, R, ll_t, ess_t, want_path, path_out, last_out, iv);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
     const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
@@ -459,6 +501,64 @@ extern "C" int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const doubl
   if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
   return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, true, path_out, last_out, rc_out);
+}
+
+// One row of a FleetIv launch into the caller's arrays: the d state rows and the eta row as the block left them, eta of the mean formed
+// here as cssm_fleet_summary forms it (:420) from the row's own f coefficients.
+struct FleetIvOut {
+  double *state_mean, *state_lower, *state_upper, *eta_of_mean, *eta_lower, *eta_upper;
+};
+static void fleet_iv_row(const cssm_fleet* f, uint32_t k, const double* src, const double* fco, const FleetIvOut& o, size_t row) {
+  const int d = f->d;
+  double mean[CSSM_MAX_DIM];
+  for (int c = 0; c < d; ++c) {
+    mean[c] = src[c * 3];
+    if (o.state_mean) o.state_mean[row * d + c] = src[c * 3];
+    if (o.state_lower) o.state_lower[row * d + c] = src[c * 3 + 1];
+    if (o.state_upper) o.state_upper[row * d + c] = src[c * 3 + 2];
+  }
+  if (o.eta_lower) o.eta_lower[row] = src[d * 3 + 1];
+  if (o.eta_upper) o.eta_upper[row] = src[d * 3 + 2];
+  if (o.eta_of_mean) o.eta_of_mean[row] = cssm_eta_of_mean(f->models[k], fco, mean);
+}
+
+// examples/Filtering.scala:24-31 of every series: cssm_fleet_ll_filter, and getIntervals (model/ParticleFilter.scala:415-424) of the initial
+// cloud and of the cloud after every record, written by the series' own workgroup inside the one launch.  What needs no fleet is refused
+// first, so that it is refused on any host.
+extern "C" int cssm_fleet_filter_intervals(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval,
+                                           double* ll_out, double* ll_t, int32_t* ess_t, double* state_mean, double* state_lower, double* state_upper,
+                                           double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out) {
+  if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
+  if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  FleetIv iv;
+  iv.interval = interval;
+  int rc = fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, false, nullptr, nullptr, rc_out, &iv);
+  if (rc) return rc;
+  const uint32_t S = f->S;
+  const int d = f->d;
+  const size_t R = (size_t)off[S], RB = CSSM_FLEET_REC_BYTES(d), rowsz = (size_t)(d + 1) * 3u;
+  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  for (double* p : {state_mean, state_lower, state_upper}) if (p) std::fill(p, p + (R + S) * (size_t)d, cssm_nan());
+  for (double* p : {eta_of_mean, eta_lower, eta_upper}) if (p) std::fill(p, p + (R + S), cssm_nan());
+  const unsigned char* h_recs = f->h_stage + fleet_stage_head(f);   // (the staged launch is still there: the records' f coefficients)
+  const double* h_fco0 = reinterpret_cast<const double*>(h_recs + R * RB);
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+      if (b == a) continue;                                         // no records: NaN in its single row
+      const FleetSeries& s = f->h_ser[k];
+      const size_t nrows = s.err ? (size_t)s.fail_rec + 1u : b - a + 1u;   // a failure at observation s keeps rows 0 .. s
+      for (size_t i = 0; i < nrows; ++i) {
+        const double* fco = i ? reinterpret_cast<const double*>(h_recs + (a + i - 1) * RB + sizeof(FleetRecHead)) + 4 * d : h_fco0 + k * d;
+        fleet_iv_row(f, (uint32_t)k, iv.out.data() + (a + k + i) * rowsz, fco, o, a + k + i);
+      }
+    }
+  });
+  return CSSM_OK;
 }
 
 // ParticleMetropolisHastings (model/PMMH.scala:68-81,114-123) for S chains in lockstep, a chain per series: chain k is cssm_pmmh_run
@@ -550,15 +650,15 @@ extern "C" int cssm_fleet_init(cssm_fleet* f, const double* t0) {
   return CSSM_OK;
 }
 
-extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
-                               double* ll_out, int32_t* ess_out, int* rc_out) {
-  if (!f || !t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+// stepFilter of the active series; iv (cssm_fleet_step_intervals): the same launch also writes getIntervals of every cloud it moved
+static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                          double* ll_out, int32_t* ess_out, int* rc_out, FleetIv* iv, const FleetIvOut* ivo) {
   const uint32_t S = f->S;
   bool any_live = false;
   for (uint32_t k = 0; k < S; ++k) any_live = any_live || f->live[k];
   if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
   HIP_TRY(hipSetDevice(f->device));
-  int rc = fleet_ensure(f, S);
+  int rc = fleet_ensure(f, S, false, iv != nullptr);
   if (rc) return rc;
   unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
   uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
@@ -575,7 +675,11 @@ extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const doubl
       if (h_off[k + 1] > h_off[k])
         fleet_pack_rec(f->models[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1, f->step[k], h_recs + (size_t)h_off[k] * RB);
   });
-  rc = fleet_launch(f, R, nullptr, nullptr);
+  if (iv) {   // (no launch of a step draws a cloud: the f coefficients of a t0 are not read)
+    iv->step = true; iv->rows = S;
+    memset(h_recs + R * RB, 0, (size_t)S * f->d * 8u);
+  }
+  rc = fleet_launch(f, R, nullptr, nullptr, false, nullptr, nullptr, iv);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
     if (active && !active[k]) { rc_out[k] = CSSM_OK; continue; }            // untouched
@@ -585,8 +689,31 @@ extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const doubl
     rc_out[k] = CSSM_OK; f->t[k] = t[k]; f->step[k] += 1u;
     if (ll_out) ll_out[k] = s.ll;
     if (ess_out) ess_out[k] = s.ess;
+    if (iv)
+      fleet_iv_row(f, k, iv->out.data() + (size_t)k * (f->d + 1) * 3u,
+                   reinterpret_cast<const double*>(h_recs + (size_t)h_off[k] * RB + sizeof(FleetRecHead)) + 4 * f->d, *ivo, k);
   }
   return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                               double* ll_out, int32_t* ess_out, int* rc_out) {
+  if (!f || !t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, nullptr, nullptr);
+}
+
+// filterStream + getIntervals (examples/Filtering.scala:24-31, one observation per sensor per call): cssm_fleet_step, and the summaries of
+// every cloud it moved from the same launch.  The entries of a series that is inactive, has no cloud or fails are not written.
+extern "C" int cssm_fleet_step_intervals(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs, double interval,
+                                         double* ll_out, int32_t* ess_out, double* state_mean, double* state_lower, double* state_upper,
+                                         double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out) {
+  if (!t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  FleetIv iv;
+  iv.interval = interval;
+  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, &iv, &o);
 }
 
 extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_mean, double* state_lower, double* state_upper,

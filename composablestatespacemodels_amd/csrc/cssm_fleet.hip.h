@@ -14,6 +14,8 @@
 #define CSSM_FLEET_MAX_THREADS 512   /* 8 waves: two per SIMD, so every instantiation may use 256 vector registers */
 #define CSSM_FLEET_WAVES(D) ((D) <= 4 ? 4 : 2)   /* waves per SIMD the register allocation aims at (the table and the A/B) */
 
+#include "cssm_fleet_intervals.hip.h"
+
 // What the host uploads per (series, observation): the fields of cssm_build_rec's StepRec the kernels of a non-LGCP model read, with
 // exactly the d components in use -- 80 + 40 d bytes (120 at d = 1, 200 at d = 3, 720 at d = 16) instead of sizeof(StepRec).  The
 // block expands it into a StepRec in LDS, so the device functions above read it through the pointer they always took.
@@ -67,6 +69,15 @@ struct FleetArgs {
   uint32_t* hanc;
   FleetSeries* hser;                 // [series of the chunk]: ll, err, fail_rec of the forward pass
   uint32_t k0;
+  // getIntervals of the cloud behind the initial draw and behind every record (k_fleet_series<D, false, false, true> only:
+  // cssm_fleet_filter_intervals / cssm_fleet_step_intervals; model/ParticleFilter.scala:415-424, examples/Filtering.scala:24-31), once
+  // more behind every field the other instantiations read.
+  const double* iv_fco0;             // [S][d]: F at series k's t0, the f coefficients of its row 0 (read by a launch that draws the cloud)
+  double* iv_out;                    // rows of [d + 1][3] (mean, lower, upper), preset to NaN; iv_rows == 0: series k owns rows off[k] + k ..
+                                     // off[k + 1] + k, row 0 the initial cloud; iv_rows == 1 (step): row k is the cloud behind series k's record
+  uint32_t iv_rows;
+  uint32_t iv_np2;                   // the power of two >= max(n, 2): the keys a row's sort holds where the weights were
+  FleetRowRanks iv_rk;
 };
 
 // a - b mod 2^128 (integers: exact)
@@ -99,7 +110,11 @@ __device__ __forceinline__ void fleet_path_row(const double* buf, const uint32_t
 // HIST: the forward pass of cssm_fleet_interpolate (FilterInterpolate, model/ParticleFilter.scala:273-311) -- the same statements, but
 // every cloud and every weighted record's ancestors are kept (FleetArgs::hist / hanc) instead of ping-ponging two buffers, and nothing
 // the fleet holds per series is written.  A template flag as PATH is: the other two instantiations hold no trace of it either.
-template <int D, bool PATH, bool HIST = false>
+// IVAL: llFilter that also writes getIntervals of every cloud it passes through (FleetArgs::iv_*) -- fleet_cloud_intervals behind the
+// barrier that completes the initial draw and behind the one that completes a record's cloud and ancestors, with the record's own f
+// coefficients (s_rec.fco is F at the record's time).  The keys of a row's sort live where the weights were (dead once the resampling
+// has read them), so the dynamic LDS is 8 np2 + 4 n bytes.  A template flag again: the other three instantiations hold no trace of it.
+template <int D, bool PATH, bool HIST = false, bool IVAL = false>
 __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_series(const FleetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   __shared__ StepRec s_rec;
@@ -109,7 +124,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   const uint32_t n = a.n, k = blockIdx.x, tid = threadIdx.x, bs = blockDim.x;
   const uint32_t lane = tid & 63u, wid = tid >> 6, nw = bs >> 6;
   double* s_lw = reinterpret_cast<double*>(s_dyn);
-  uint32_t* s_anc = reinterpret_cast<uint32_t*>(s_dyn + (size_t)((n + 1u) & ~1u) * 8u);
+  uint32_t* s_anc = reinterpret_cast<uint32_t*>(s_dyn + (size_t)(IVAL ? a.iv_np2 : ((n + 1u) & ~1u)) * 8u);
   const unsigned long long r0 = a.off[k], r1 = a.off[k + 1];
   const uint32_t ctl = HIST ? CSSM_FLEET_CTL_INIT : a.ctl[k];   // (HIST: a series is always run from its initial cloud)
   if ((HIST || !(ctl & CSSM_FLEET_CTL_INIT)) && r0 >= r1) return;   // (uniform) nothing for this series in this launch: untouched
@@ -152,6 +167,9 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
       }
       fleet_path_row<D>(st + (size_t)cur * D * n, s_anc, n, pick, a.path + (size_t)(r + k) * D, tid);
     }
+    if (IVAL && r == r0 && (ctl & CSSM_FLEET_CTL_INIT))         // (uniform) row 0: the initial cloud, F at the series' t0
+      fleet_cloud_intervals<D>(st, s_anc, n, a.iv_np2, a.mk, a.iv_fco0 + (size_t)k * D, a.iv_rk, reinterpret_cast<unsigned long long*>(s_lw),
+                               a.iv_out + (size_t)(r0 + k) * (D + 1) * 3u);
     {
       const unsigned char* g = a.recs + (size_t)r * RB;
       const FleetRecHead* h = reinterpret_cast<const FleetRecHead*>(g);
@@ -192,6 +210,11 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
       __syncthreads();
       for (uint32_t i = tid; i < n; i += bs) s_anc[i] = i;
       if (!HIST && tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
+      if (IVAL) {                                               // the cloud this record moved, through identity ancestors
+        __syncthreads();
+        fleet_cloud_intervals<D>(dst, s_anc, n, a.iv_np2, a.mk, s_rec.fco, a.iv_rk, reinterpret_cast<unsigned long long*>(s_lw),
+                                 a.iv_out + (size_t)(a.iv_rows ? k : r + k + 1u) * (D + 1) * 3u);
+      }
       continue;
     }
     // 2. the block's own max is at hand before any weight is formed: the level is chosen in place
@@ -264,6 +287,11 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
       }
     }
     if (!HIST && tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
+    if (IVAL) {                                                 // the cloud this record wrote, through the ancestors that resampled it
+      __syncthreads();
+      fleet_cloud_intervals<D>(dst, s_anc, n, a.iv_np2, a.mk, s_rec.fco, a.iv_rk, reinterpret_cast<unsigned long long*>(s_lw),
+                               a.iv_out + (size_t)(a.iv_rows ? k : r + k + 1u) * (D + 1) * 3u);
+    }
   }
   if (HIST) {                                                   // the fleet's ancestors and scalars stay as they were
     if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.hser[k] = o; }
@@ -284,6 +312,7 @@ struct FleetLaunch {
   uint32_t n_series;
   bool path;            // k_fleet_series<D, true>
   bool hist = false;    // k_fleet_series<D, false, true>: n_series blocks, the series args.k0 .. args.k0 + n_series - 1
+  bool ival = false;    // k_fleet_series<D, false, false, true>: lds = 8 args.iv_np2 + 4 n bytes
   int threads;
   size_t lds;
   hipStream_t stream;

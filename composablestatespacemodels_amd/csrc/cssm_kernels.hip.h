@@ -285,16 +285,6 @@ static __global__ void k_record(const Scalars* __restrict__ sc, double* __restri
 // getIntervals (model/ParticleFilter.scala:415-424): meanState (:465-479), getallCredibleIntervals
 // (:488-512) and getOrderStatistic (:455-460) of the CURRENT (resampled) cloud, on the device.
 
-// link of the observing leaf (model/Model.scala:24,183,269,296,318-326,345)
-__device__ __forceinline__ double link_of(int obs_kind, double g) {
-  switch (obs_kind) {
-    case CSSM_OBS_POISSON: case CSSM_OBS_NEGBIN: case CSSM_OBS_ZIP: return cssm_exp(g);
-    case CSSM_OBS_BERNOULLI: return (g > 6.0) ? 1.0 : ((g < -6.0) ? 0.0 : 1.0 / (1.0 + cssm_exp(-g)));
-    case CSSM_OBS_BETA: return cssm_exp(-g);
-    default: return g;
-  }
-}
-
 // rows 0..d-1: the resampled state components, row d: eta = link(f(x, t)); stored as order-preserving keys
 template <int D>
 __global__ __launch_bounds__(CSSM_BLOCK) void k_summary_fill(const double* __restrict__ src, size_t src_stride,

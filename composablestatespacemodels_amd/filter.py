@@ -493,6 +493,31 @@ class NativePfFleet:
         paths = [path[o[k] + k:o[k + 1] + k + 1] for k in range(self.S)] if want_path else None
         return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], paths, last, rc
 
+    def filter_intervals(self, datas, interval: float = 0.975):
+        """cssm_fleet_filter_intervals: ``ll_filter`` and, from the same launch, ``summary`` of the initial cloud and of the cloud after
+        every record.  ``(ll[S], [ll_t of series k], [ess_t of series k], per-series list of (mean[T_k + 1, d], lower, upper,
+        eta_of_mean[T_k + 1], eta_lower, eta_upper), rc[S])``; rc[k] != 0 is series k's own status (-6: no records, its single row reads
+        NaN; -5: its weights were unusable at observation s, its rows read NaN from s + 1 on).  The fleet continues with ``step``."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        return self.filter_intervals_packed(*self.pack(datas, allow_empty=True), interval=interval)
+
+    def filter_intervals_packed(self, off, t, y, has, interval: float = 0.975):
+        """``filter_intervals`` on arrays ``pack`` made (a caller that filters the same fleet repeatedly packs once)."""
+        R = self._check_packed(off, t, y, has)
+        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
+        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
+        m, lo, hi = (np.zeros((R + self.S, self.d)) for _ in range(3))
+        em, el, eu = (np.zeros(R + self.S) for _ in range(3))
+        tt, yy, hh = (t, y, has) if R else (np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.uint8))
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_filter_intervals(self._h, _p(off, C.POINTER(C.c_uint64)), _p(tt), _p(yy), _p(hh, C.POINTER(C.c_uint8)),
+                                                        float(interval), _p(ll), _p(ll_t), _p(ess_t, C.POINTER(C.c_int32)),
+                                                        _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu), _p(rc, C.POINTER(C.c_int))))
+        o = [int(v) for v in off]
+        return (ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)],
+                self.interpolate_rows(off, (m, lo, hi, em, el, eu)), rc)
+
     def interpolate(self, datas, interval: float = 0.975, reference_pairing: bool = False):
         """cssm_fleet_interpolate: ``NativePf.interpolate`` of every series in two launches.  ``(ll[S], per-series list of (mean[T_k + 1,
         d], lower, upper, eta_of_mean[T_k + 1], eta_lower, eta_upper), rc[S])``; rc[k] != 0 is series k's own status (-6: no records,
@@ -553,6 +578,26 @@ class NativePfFleet:
         self.generation += 1
         _abi.check(self.lib.cssm_fleet_step(self._h, ap, _p(t), _p(y), hp, _p(ll), _p(ess, C.POINTER(C.c_int32)), _p(rc, C.POINTER(C.c_int))))
         return ll, ess, rc
+
+    def step_intervals(self, t, y, has=None, active=None, interval: float = 0.975):
+        """cssm_fleet_step_intervals: ``step`` and, from the same launch, ``summary`` of every cloud it moved: ``(ll[S], ess[S], (state_mean[S,
+        d], state_lower, state_upper, eta_of_mean[S], eta_lower, eta_upper), rc[S])``; entries of series that are inactive, have no cloud
+        or fail are NaN / -1."""
+        t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+        if len(t) != self.S or len(y) != self.S:
+            raise ValueError("one (t, y) per series")
+        hp = ap = None
+        if has is not None:
+            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
+        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32); rc = np.zeros(self.S, dtype=np.int32)
+        m, lo, hi = (np.full((self.S, self.d), np.nan) for _ in range(3))
+        em, el, eu = (np.full(self.S, np.nan) for _ in range(3))
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_step_intervals(self._h, ap, _p(t), _p(y), hp, float(interval), _p(ll), _p(ess, C.POINTER(C.c_int32)),
+                                                      _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu), _p(rc, C.POINTER(C.c_int))))
+        return ll, ess, (m, lo, hi, em, el, eu), rc
 
     def summary(self, interval: float = 0.975):
         """(state_mean[S, d], state_lower[S, d], state_upper[S, d], eta_of_mean[S], eta_lower[S], eta_upper[S])."""
@@ -1103,6 +1148,15 @@ class FilterFleet:
     def stepFilter(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]]) -> List[FleetState]:
         """``ys[k]`` None = sensor k has nothing new (its state is returned as it is); a TimedObservation whose ``observation`` is None
         is the reference's ``None`` branch (propagate only)."""
+        return self._step(states, ys, None)[0]
+
+    def stepIntervals(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]],
+                      interval: float = 0.975) -> Tuple[List[FleetState], List[Optional[PfOut]]]:
+        """``stepFilter`` and ``getIntervals`` of every state it advanced, from one device call (``filterStream`` mapped through
+        ``getIntervals``, examples/Filtering.scala:24-31): the new states, and per series its ``PfOut`` -- None where ``ys[k]`` is None."""
+        return self._step(states, ys, float(interval))
+
+    def _step(self, states, ys, interval: Optional[float]):
         if len(states) != self.S or len(ys) != self.S:
             raise ValueError("one state and one (optional) observation per series")
         if any(s._owner is not self._fleet or s._generation != self._fleet.generation for s in states):
@@ -1111,14 +1165,22 @@ class FilterFleet:
         t = np.array([states[k].t if o is None else o.t for k, o in enumerate(ys)], dtype=np.float64)
         has = np.array([0 if (o is None or o.observation is None) else 1 for o in ys], dtype=np.uint8)
         y = np.array([o.observation if h else 0.0 for o, h in zip(ys, has)], dtype=np.float64)
-        ll, ess, rc = self._fleet.step(t, y, has, act)
+        if interval is None:
+            ll, ess, rc = self._fleet.step(t, y, has, act)
+        else:
+            ll, ess, rows, rc = self._fleet.step_intervals(t, y, has, act, interval)
         for k in range(self.S):
             if rc[k]:
                 raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable (or it has no cloud)")
         keep = [s if not a else None for s, a in zip(states, act)]
-        return self._wrap(t, [s.observation if s is not None else (float(y[k]) if has[k] else None) for k, s in enumerate(keep)],
-                          [s.ll if s is not None else ll[k] for k, s in enumerate(keep)],
-                          [s.ess if s is not None else ess[k] for k, s in enumerate(keep)])
+        new = self._wrap(t, [s.observation if s is not None else (float(y[k]) if has[k] else None) for k, s in enumerate(keep)],
+                         [s.ll if s is not None else ll[k] for k, s in enumerate(keep)],
+                         [s.ess if s is not None else ess[k] for k, s in enumerate(keep)])
+        if interval is None:
+            return new, None
+        m, lo, hi, em, el, eu = rows
+        return new, [PfOut(new[k].t, new[k].observation, float(em[k]), CredibleInterval(float(el[k]), float(eu[k])), m[k].copy(),
+                           [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k], hi[k])]) if act[k] else None for k in range(self.S)]
 
     def llFilter(self, datas: Sequence[Sequence[TimedObservation]]) -> np.ndarray:
         ll, _, _, rc = self._fleet.ll_filter([split_data(d) for d in datas])
@@ -1142,6 +1204,18 @@ class FilterFleet:
             times = [float(np.min(t))] + [float(v) for v in t]
             out.append((float(ll[k]), [StateSpace(tt, paths[k][i].copy()) for i, tt in enumerate(times)]))
         return out
+
+    def filterIntervals(self, datas: Sequence[Sequence[TimedObservation]], interval: float = 0.975) -> List[List[PfOut]]:
+        """examples/Filtering.scala:24-31 of every series in one device call (one launch): ``filter`` mapped through ``getIntervals`` --
+        per series T_k + 1 ``PfOut``, the first without an observation at the slice's smallest time (``Flow.scan`` emits the initial
+        state), entry s + 1 after datum s.  ``formats.pfout_csv`` writes the reference's ``Filtered.csv`` lines from them."""
+        split = [split_data(d) for d in datas]
+        _, _, _, rows, rc = self._fleet.filter_intervals(split, float(interval))
+        for k in range(self.S):
+            if rc[k]:
+                raise _abi.CssmError(int(rc[k]), f"series {k}: " + ("it has no records" if rc[k] == _abi.CSSM_EINVAL_ARG else "its weights were unusable"))
+        self._states = []
+        return [_interpolate_outs(datas[k], split[k][0], rows[k]) for k in range(self.S)]
 
     def interpolate(self, datas: Sequence[Sequence[TimedObservation]], interval: float = 0.975,
                     reference_pairing: bool = False) -> List[Tuple[float, List[PfOut]]]:

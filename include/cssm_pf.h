@@ -822,6 +822,26 @@ int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const double* t, co
 int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
                       double* ll_out, double* ll_t, int32_t* ess_t, double* path_out, double* last_out, int* rc_out);
 
+/* The reference's everyday program (examples/Filtering.scala:24-31: filter, then getIntervals of every emitted PfState,
+ * model/ParticleFilter.scala:415-424) of every series: cssm_fleet_ll_filter -- off / t / y / has_obs / ll_out / ll_t / ess_t / rc_out are
+ * its arguments bit for bit, and the cloud, ancestors, clock and observation index left behind are the ones it leaves (the fleet
+ * continues with cssm_fleet_step) -- and cssm_fleet_summary of the initial cloud and of the cloud after every record, written by the
+ * series' own workgroup inside the ONE launch: no history, no second launch, no device memory beyond the outputs.
+ *   Rows are laid out like cssm_fleet_filter's path_out: series k owns rows off[k] + k .. off[k+1] + k (T_k + 1 rows, off[S] + S in
+ *   all); row 0 is the initial cloud at the slice's smallest time, row s + 1 the cloud after observation s (identity ancestors behind an
+ *   observation without a datum), eta with F at the row's own time.  state_mean / state_lower / state_upper: [off[S] + S][d];
+ *   eta_of_mean / eta_lower / eta_upper: [off[S] + S]; any of the six may be NULL.
+ * Order statistics exact, ranks and clamping as cssm_pf_summary documents them (a state row and the eta row take different rank pairs),
+ * means plain fp64 sums, eta_of_mean = link(f(mean, t)) formed on the host.  Every row is preset to NaN: a series with no records
+ * (CSSM_EINVAL_ARG) has NaN in its single row; a series that fails with CSSM_ENONFINITE at observation s keeps rows 0 .. s and reads NaN
+ * from row s + 1 on; no other series notices either.  Null off / ll_out / rc_out / t / y, off[0] != 0, an interval outside (0, 1] and
+ * a null fleet are refused with CSSM_EINVAL_ARG before the fleet is looked at; a decreasing off as by cssm_fleet_ll_filter.  The device
+ * time is cssm_fleet_last_ms()[0]. */
+int cssm_fleet_filter_intervals(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                double interval, double* ll_out, double* ll_t, int32_t* ess_t,
+                                double* state_mean, double* state_lower, double* state_upper,
+                                double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out);
+
 /* ParticleMetropolisHastings (model/PMMH.scala:68-81,114-123; examples/DetermineParameters.scala) for S chains in lockstep, a chain
  * per series, ONE launch per iteration: chain k starts at theta0[k * n_theta ..], runs under seeds[k] and sees series k's slice of the
  * data (off / t / y / has_obs as cssm_fleet_ll_filter; the slices may repeat one data set or differ per sensor).  Per iteration:
@@ -850,6 +870,16 @@ int cssm_fleet_pmmh_last_split(cssm_fleet* f, double* ms6);
 int cssm_fleet_init(cssm_fleet* f, const double* t0);
 int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
                     double* ll_out, int32_t* ess_out, int* rc_out);
+
+/* The streaming shape of cssm_fleet_filter_intervals (filterStream, then getIntervals of every state; one observation per sensor per
+ * call): cssm_fleet_step -- the same arguments, bits and statuses -- and cssm_fleet_summary of every cloud the call moved, from the same
+ * launch.  state_* [S][d], eta_* [S], any may be NULL; the entries of a series that is inactive, has no cloud (CSSM_ESTATE) or fails
+ * (CSSM_ENONFINITE) are not written, as its ll_out / ess_out entries are not.  Null t / y / rc_out, an interval outside (0, 1] and a null
+ * fleet are refused with CSSM_EINVAL_ARG before the fleet is looked at.  The device time is cssm_fleet_last_ms()[0]. */
+int cssm_fleet_step_intervals(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                              double interval, double* ll_out, int32_t* ess_out,
+                              double* state_mean, double* state_lower, double* state_upper,
+                              double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out);
 
 /* cssm_pf_summary (getIntervals, model/ParticleFilter.scala:415-424) of every series at its own time: state_* [S * d], eta_* [S];
  * any may be NULL.  Order statistics exact, ranks and clamping as documented there, means plain fp64 sums.  A series without a
