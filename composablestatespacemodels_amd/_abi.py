@@ -179,6 +179,10 @@ SYMBOLS = [
     ("cssm_fleet_filter", C.c_int, [_h, _u64p, _dp, _dp, _u8p, _dp, _dp, _i32p, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_fleet_filter_intervals", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_double, _dp, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_fleet_step_intervals", C.c_int, [_h, _u8p, _dp, _dp, _u8p, C.c_double, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    ("cssm_fleet_filter_forecasts", C.c_int, [_h, _u64p, _dp, _dp, _u8p, _u64p, C.c_double, _dp, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                              _i32p, _i32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("cssm_fleet_step_forecast", C.c_int, [_h, _u8p, _dp, _dp, _u8p, _u64p, C.c_double, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                           _i32p, _i32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("cssm_fleet_pmmh_run", C.c_int, [_h, _descp, _dp, C.c_size_t, C.c_double, _u64p, _dp, _dp, _u8p, _u64p, C.c_size_t, _dp, _dp, _i32p, _dp]),
     ("cssm_fleet_pmmh_last_split", C.c_int, [_h, _dp]),
     ("cssm_fleet_init", C.c_int, [_h, _dp]),

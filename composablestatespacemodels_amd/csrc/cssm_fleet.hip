@@ -45,6 +45,7 @@ struct cssm_fleet {
   unsigned char* d_stage = nullptr; size_t stage_cap = 0;
   double* d_ll_t = nullptr; int32_t* d_ess_t = nullptr; size_t res_cap = 0;
   double* d_tmp = nullptr;              // d x n: cssm_fleet_get_particles
+  unsigned char* d_fcr = nullptr; size_t fcr_cap = 0;   // cssm_fleet_filter_forecasts / _step_forecast, grow-only: rows of [d + 2][3] doubles, then rows of 2 PIT counts
   double* d_iv = nullptr; size_t iv_cap = 0;       // cssm_fleet_filter_intervals / _step_intervals, grow-only: rows of [d + 1][3] (mean, lower, upper)
   double* d_path = nullptr; size_t path_cap = 0;   // cssm_fleet_filter, grow-only: [S][d] last rows, then (asked for) the R + S rows of the paths
   float ms_upload = -1.f, ms_kernel = -1.f;        // ... of its last launch
@@ -171,7 +172,7 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_iv, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp, f->d_ip, f->d_ip_hist};
+  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_iv, f->d_fcr, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp, f->d_ip, f->d_ip_hist};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (f->h_stage) (void)hipHostFree(f->h_stage);
   if (f->h_fc) (void)hipHostFree(f->h_fc);
@@ -304,9 +305,26 @@ struct FleetIv {
   std::vector<double> out;    // the rows as the device left them; NaN where no block wrote
 };
 
-// (picks: the launch also carries R sampleOne slots, uint32 each, behind the records; iv: S x d f coefficients, F at every series' t0)
-static int fleet_ensure(cssm_fleet* f, size_t R, bool picks = false, bool iv = false) {
-  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d) + (picks ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u);
+// What a launch that also forecasts every record before it is stepped carries and brings back (k_fleet_series<D, false, false, false, true>).
+struct FleetFc {
+  double interval;
+  const uint64_t* keys;       // the caller's, one per record of the call as the caller counts them ([off[S]], or [S] for a step), or null
+  bool step = false;          // one row per series (cssm_fleet_step_forecast), not one per record
+  size_t rows = 0;            // of [d + 2][3] doubles and of 2 counts: S, or R
+  std::vector<double> out;    // the rows as the device left them; NaN where no block wrote
+  std::vector<int32_t> pit;   // ... -1 where no block wrote
+  std::vector<int> fc_rc;     // [S]: the forecast's own status of every series
+  std::string scale_msg;      // the reference's exception for the first series without the scale its observation needs
+};
+// behind the R records of such a launch: [R keys (u64)] [R data (f64)] [S observation parameters] [R flags (u32)]
+static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
+static size_t fleet_fc_bytes(const cssm_fleet* f, size_t R) { return R * 16u + (size_t)f->S * sizeof(cssm_obs_params) + ((R * 4u + 7u) & ~(size_t)7u); }
+
+// (picks: the launch also carries R sampleOne slots, uint32 each, behind the records; iv: S x d f coefficients, F at every series' t0;
+// fc: fleet_fc_bytes -- a launch carries one of the three at most)
+static int fleet_ensure(cssm_fleet* f, size_t R, bool picks = false, bool iv = false, bool fc = false) {
+  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d) + (picks ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u) +
+                      (fc ? fleet_fc_bytes(f, R) : 0u);
   if (need > f->h_stage_cap) {
     if (f->h_stage) (void)hipHostFree(f->h_stage);
     f->h_stage = nullptr; f->h_stage_cap = 0;
@@ -348,12 +366,24 @@ static int fleet_series_launch(int d, const FleetLaunch& l) {
 // upload the staged launch, run it, bring the series' scalars (and, asked for, the per-observation results) back; synchronises.
 // want_path: the staged launch carries its picks and runs k_fleet_series<D, true>; path_out (may be null) / last_out receive the rows.
 // iv: the staged launch carries the f coefficients of every series' t0 behind its records and runs k_fleet_series<D, false, false, true>.
+// fc: the staged launch carries fleet_fc_bytes behind its records and runs k_fleet_series<D, false, false, false, true>.
 static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, bool want_path = false, double* path_out = nullptr, double* last_out = nullptr,
-                        FleetIv* iv = nullptr) {
+                        FleetIv* iv = nullptr, FleetFc* fc = nullptr) {
   int rc = fleet_upload_par(f);
   if (rc) return rc;
   const size_t head = fleet_stage_head(f), recs = R * CSSM_FLEET_REC_BYTES(f->d),
-               bytes = head + recs + (want_path ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u);
+               bytes = head + recs + (want_path ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u) + (fc ? fleet_fc_bytes(f, R) : 0u);
+  const size_t n_fco = fc ? fc->rows * (size_t)(f->d + 2) * 3u : 0u, n_fcr = n_fco * 8u + (fc ? fc->rows * 8u : 0u);   // (bytes: doubles, then counts)
+  if (n_fcr > f->fcr_cap) {
+    if (f->d_fcr) (void)hipFree(f->d_fcr);
+    f->d_fcr = nullptr; f->fcr_cap = 0;
+    if (hipMalloc(&f->d_fcr, n_fcr + n_fcr / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of one-step-ahead forecasts", n_fcr);
+    f->fcr_cap = n_fcr + n_fcr / 4;
+  }
+  if (fc && !f->d_fc_stage && hipMalloc(&f->d_fc_stage, (size_t)f->S * 2u * f->n * 8u) != hipSuccess) {
+    f->d_fc_stage = nullptr;
+    return fail(CSSM_ENOMEM, "fleet forecast: 16 N bytes of staging per series");
+  }
   const size_t n_iv = iv ? iv->rows * (size_t)(f->d + 1) * 3u : 0u;
   if (n_iv > f->iv_cap) {
     if (f->d_iv) (void)hipFree(f->d_iv);
@@ -379,6 +409,7 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
     HIP_TRY(hipEventRecord(f->ev[6], f->stream));
   }
   if (iv) HIP_TRY(hipMemsetAsync(f->d_iv, 0xff, n_iv * 8, f->stream));   // ... and the rows it never summarises
+  if (n_fcr) HIP_TRY(hipMemsetAsync(f->d_fcr, 0xff, n_fcr, f->stream));  // ... or never forecasts (NaN; -1 in the counts)
   FleetLaunch l;
   l.args.n = f->n; l.args.state = f->state; l.args.anc = f->anc; l.args.ser = f->ser; l.args.par = f->par;
   l.args.off = reinterpret_cast<const unsigned long long*>(f->d_stage);
@@ -390,7 +421,27 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
   l.args.last = want_path ? f->d_path : nullptr;
   l.args.hist = nullptr; l.args.hanc = nullptr; l.args.hser = nullptr; l.args.k0 = 0u;
   l.args.iv_fco0 = nullptr; l.args.iv_out = nullptr; l.args.iv_rows = 0u; l.args.iv_np2 = 0u; l.args.iv_rk = FleetRowRanks{0u, 0u, 0u, 0u};
+  l.args.fc = FleetOneStep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   l.n_series = f->S; l.path = want_path; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+  if (fc) {
+    SelState rs, re;   // the ranks of a state row and of the eta / obs rows, as cssm_fleet_forecast takes them
+    sel_ranks(rs, f->n, fc->interval, true);
+    sel_ranks(re, f->n, fc->interval, false);
+    uint32_t np2 = 2u;
+    while (np2 < f->n) np2 <<= 1;
+    const unsigned char* x = f->d_stage + head + recs;
+    l.args.fc.keys = reinterpret_cast<const unsigned long long*>(x);
+    l.args.fc.y = reinterpret_cast<const double*>(x + R * 8u);
+    l.args.fc.op = reinterpret_cast<const cssm_obs_params*>(x + R * 16u);
+    l.args.fc.flags = reinterpret_cast<const uint32_t*>(x + R * 16u + (size_t)f->S * sizeof(cssm_obs_params));
+    l.args.fc.stage = f->d_fc_stage;
+    l.args.fc.out = reinterpret_cast<double*>(f->d_fcr);
+    l.args.fc.pit = reinterpret_cast<int32_t*>(f->d_fcr + n_fco * 8u);
+    l.args.iv_rows = fc->step ? 1u : 0u; l.args.iv_np2 = np2;
+    l.args.iv_rk = FleetRowRanks{(uint32_t)rs.rank[0], (uint32_t)rs.rank[1], (uint32_t)re.rank[0], (uint32_t)re.rank[1]};
+    l.fcst = true; l.lds = (size_t)np2 * 8u + (size_t)f->n * 4u;   // the keys of a row's sort take the weights' place
+    fc->out.resize(n_fco); fc->pit.resize(fc->rows * 2u);
+  }
   if (iv) {
     SelState rs, re;   // the ranks of a state row and of the eta row, as cssm_fleet_summary takes them
     sel_ranks(rs, f->n, iv->interval, true);
@@ -412,6 +463,10 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
   if (R && ll_t) HIP_TRY(hipMemcpyAsync(ll_t, f->d_ll_t, R * 8, hipMemcpyDeviceToHost, f->stream));
   if (R && ess_t) HIP_TRY(hipMemcpyAsync(ess_t, f->d_ess_t, R * 4, hipMemcpyDeviceToHost, f->stream));
   if (n_iv) HIP_TRY(hipMemcpyAsync(iv->out.data(), f->d_iv, n_iv * 8, hipMemcpyDeviceToHost, f->stream));
+  if (n_fcr) {
+    HIP_TRY(hipMemcpyAsync(fc->out.data(), f->d_fcr, n_fco * 8u, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(fc->pit.data(), f->d_fcr + n_fco * 8u, fc->rows * 8u, hipMemcpyDeviceToHost, f->stream));
+  }
   HIP_TRY(hipEventRecord(f->ev[1], f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
   if (hipEventElapsedTime(&f->ms_call, f->ev[0], f->ev[1]) != hipSuccess) f->ms_call = -1.f;
@@ -422,10 +477,53 @@ static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, b
   return CSSM_OK;
 }
 
+// the staged arrays of a FleetFc launch of R records (fleet_fc_bytes) in the pinned staging
+struct FleetFcStage {
+  unsigned long long* keys; double* y; cssm_obs_params* op; uint32_t* flags;
+};
+static FleetFcStage fleet_fc_stage(const cssm_fleet* f, size_t R) {
+  unsigned char* x = f->h_stage + fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d);
+  return FleetFcStage{reinterpret_cast<unsigned long long*>(x), reinterpret_cast<double*>(x + R * 8u), reinterpret_cast<cssm_obs_params*>(x + R * 16u),
+                      reinterpret_cast<uint32_t*>(x + R * 16u + (size_t)f->S * sizeof(cssm_obs_params))};
+}
+// the observation parameters of series k's draws and the forecast's own status of the series (runs: the call has a record for it)
+static void fleet_fc_series(const cssm_fleet* f, uint32_t k, bool runs, FleetFc* fc, cssm_obs_params* op) {
+  memset(op, 0, sizeof *op);
+  fc->fc_rc[k] = CSSM_OK;
+  if (!runs) return;
+  if (cssm_obs_params_or_fail(f->base.obs_kind, f->obs_has_scale[k], f->obs_scale[k], f->base.obs_df, op)) {
+    if (fc->scale_msg.empty()) fc->scale_msg = "series " + std::to_string(k) + ": " + cssm_last_error();
+    fc->fc_rc[k] = CSSM_EINVAL_ARG;
+  }
+}
+// One row of a FleetFc launch into the caller's arrays; a row without a forecast (ok == false) reads NaN and -1
+struct FleetFcOut {
+  double *state_mean, *state_lower, *state_upper, *eta_mean, *eta_lower, *eta_upper, *obs_mean, *obs_lower, *obs_upper;
+  int32_t *obs_below, *obs_equal;
+};
+static void fleet_fc_row(const cssm_fleet* f, const FleetFc& fc, size_t src_row, bool ok, const FleetFcOut& o, size_t row) {
+  const int d = f->d;
+  const double* v = fc.out.data() + src_row * (size_t)(d + 2) * 3u;
+  auto at = [&](int r, int q) { return ok ? v[3 * r + q] : cssm_nan(); };
+  for (int c = 0; c < d; ++c) {
+    if (o.state_mean) o.state_mean[row * d + c] = at(c, 0);
+    if (o.state_lower) o.state_lower[row * d + c] = at(c, 1);
+    if (o.state_upper) o.state_upper[row * d + c] = at(c, 2);
+  }
+  if (o.eta_mean) o.eta_mean[row] = at(d, 0);
+  if (o.eta_lower) o.eta_lower[row] = at(d, 1);
+  if (o.eta_upper) o.eta_upper[row] = at(d, 2);
+  if (o.obs_mean) o.obs_mean[row] = at(d + 1, 0);
+  if (o.obs_lower) o.obs_lower[row] = at(d + 1, 1);
+  if (o.obs_upper) o.obs_upper[row] = at(d + 1, 2);
+  if (o.obs_below) o.obs_below[row] = ok ? fc.pit[2 * src_row] : -1;
+  if (o.obs_equal) o.obs_equal[row] = ok ? fc.pit[2 * src_row + 1] : -1;
+}
+
 // llFilter / filter of every series: the records of all of them built (threaded above 8192), ONE upload, ONE launch, ONE read-back.
 // want_path: `filter` -- the sampleOne slots travel behind the records, path_out (may be null) and last_out (may be null) are written.
 static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double* ll_out, double* ll_t,
-                            int32_t* ess_t, bool want_path, double* path_out, double* last_out, int* rc_out, FleetIv* iv = nullptr) {
+                            int32_t* ess_t, bool want_path, double* path_out, double* last_out, int* rc_out, FleetIv* iv = nullptr, FleetFc* fc = nullptr) {
   const uint32_t S = f->S;
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
   for (uint32_t k = 0; k < S; ++k)
@@ -435,12 +533,19 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
   if (R && (!t || !y)) return fail(CSSM_EINVAL_ARG, "null data");
   HIP_TRY(hipSetDevice(f->device));
   const auto tb0 = std::chrono::steady_clock::now();
-  int rc = fleet_ensure(f, R, want_path, iv != nullptr);
+  int rc = fleet_ensure(f, R, want_path, iv != nullptr, fc != nullptr);
   if (rc) return rc;
   unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
   uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
   unsigned char* h_recs = f->h_stage + fleet_stage_head(f);
   const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
+  FleetFcStage fs{nullptr, nullptr, nullptr, nullptr};
+  if (fc) {                                                              // (the reference's exception is one message: formed in order)
+    fs = fleet_fc_stage(f, R);
+    fc->fc_rc.assign(S, CSSM_OK);
+    for (uint32_t k = 0; k < S; ++k) fleet_fc_series(f, k, off[k + 1] > off[k], fc, &fs.op[k]);
+    if (R & 1u) fs.flags[R] = 0u;                                        // (the padding travels too)
+  }
   uint32_t* h_picks = want_path ? reinterpret_cast<uint32_t*>(h_recs + R * RB) : nullptr;
   double* h_fco0 = iv ? reinterpret_cast<double*>(h_recs + R * RB) : nullptr;   // (a launch carries picks or these, never both)
   for (uint32_t k = 0; k <= S; ++k) h_off[k] = off[k];
@@ -462,13 +567,20 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
       double tp = m;
       for (size_t s = a; s < b; ++s) {
         fleet_pack_rec(f->models[k], tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), h_recs + s * RB, h_picks ? h_picks + s : nullptr);
+        if (fc) {   // the forecast of record s: cssm_fleet_forecast's own refusals of a time, the key, the datum as given
+          const bool on = fc->fc_rc[k] == CSSM_OK && std::isfinite(t[s]) && t[s] >= tp;
+          fs.flags[s] = on ? (CSSM_FLEET_FC_ON | ((has_obs ? has_obs[s] : 1) ? CSSM_FLEET_FC_HAS : 0u)) : 0u;
+          fs.keys[s] = fc->keys ? fc->keys[s] : cssm_pf_run_key(f->models[k].seed, (1ull << 63) | (uint64_t)(s - a));
+          fs.y[s] = y[s];
+        }
         tp = t[s];
       }
     }
   });
   if (want_path) f->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
   if (iv) { iv->step = false; iv->rows = R + S; }
-  rc = fleet_launch(f, R, ll_t, ess_t, want_path, path_out, last_out, iv);
+  if (fc) { fc->step = false; fc->rows = R; }
+  rc = fleet_launch(f, R, ll_t, ess_t, want_path, path_out, last_out, iv, fc);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
     const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
@@ -558,6 +670,41 @@ extern "C" int cssm_fleet_filter_intervals(cssm_fleet* f, const uint64_t* off, c
       }
     }
   });
+  return CSSM_OK;
+}
+
+// ParticleFilter.getMeanForecast mapped over the filter stream (model/ParticleFilter.scala:368-409) of every series: cssm_fleet_ll_filter,
+// and before every record is stepped the forecast of its time from the cloud before it -- cssm_fleet_forecast with that single horizon --
+// by the series' own workgroup inside the ONE launch.  What needs no fleet is refused first, so that it is refused on any host.
+extern "C" int cssm_fleet_filter_forecasts(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                           const uint64_t* keys, double interval, double* ll_out, double* ll_t, int32_t* ess_t, double* state_mean,
+                                           double* state_lower, double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper,
+                                           double* obs_mean, double* obs_lower, double* obs_upper, int32_t* obs_below, int32_t* obs_equal,
+                                           int* rc_out, int* fc_rc_out) {
+  if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
+  if (!ll_out || !rc_out || !fc_rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out / fc_rc_out is null");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  FleetFc fc;
+  fc.interval = interval; fc.keys = keys;
+  int rc = fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, false, nullptr, nullptr, rc_out, nullptr, &fc);
+  if (rc) return rc;
+  const uint32_t S = f->S;
+  const size_t R = (size_t)off[S];
+  const FleetFcOut o{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal};
+  const FleetFcStage fs = fleet_fc_stage(f, R);                         // (the staged launch is still there: the records' flags)
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+      fc_rc_out[k] = fc.fc_rc[k];
+      const FleetSeries& s = f->h_ser[k];
+      const size_t nrows = (b > a && s.err) ? (size_t)s.fail_rec + 1u : b - a;   // a failure at observation s keeps rows 0 .. s
+      for (size_t i = 0; i < b - a; ++i) fleet_fc_row(f, fc, a + i, i < nrows && (fs.flags[a + i] & CSSM_FLEET_FC_ON), o, a + i);
+    }
+  });
+  if (!fc.scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", fc.scale_msg.c_str());   // (the call succeeds; the message names the first such series)
   return CSSM_OK;
 }
 
@@ -652,13 +799,14 @@ extern "C" int cssm_fleet_init(cssm_fleet* f, const double* t0) {
 
 // stepFilter of the active series; iv (cssm_fleet_step_intervals): the same launch also writes getIntervals of every cloud it moved
 static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
-                          double* ll_out, int32_t* ess_out, int* rc_out, FleetIv* iv, const FleetIvOut* ivo) {
+                          double* ll_out, int32_t* ess_out, int* rc_out, FleetIv* iv, const FleetIvOut* ivo, FleetFc* fc = nullptr,
+                          const FleetFcOut* fco = nullptr, int* fc_rc_out = nullptr) {
   const uint32_t S = f->S;
   bool any_live = false;
   for (uint32_t k = 0; k < S; ++k) any_live = any_live || f->live[k];
   if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
   HIP_TRY(hipSetDevice(f->device));
-  int rc = fleet_ensure(f, S, false, iv != nullptr);
+  int rc = fleet_ensure(f, S, false, iv != nullptr, fc != nullptr);
   if (rc) return rc;
   unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
   uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
@@ -675,13 +823,31 @@ static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t,
       if (h_off[k + 1] > h_off[k])
         fleet_pack_rec(f->models[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1, f->step[k], h_recs + (size_t)h_off[k] * RB);
   });
+  FleetFcStage fs{nullptr, nullptr, nullptr, nullptr};
+  if (fc) {   // the forecast of every active series' record: cssm_fleet_forecast's own refusals of a time, the key, the datum as given
+    fs = fleet_fc_stage(f, R);
+    fc->step = true; fc->rows = S;
+    fc->fc_rc.assign(S, CSSM_OK);
+    if (R & 1u) fs.flags[R] = 0u;
+    for (uint32_t k = 0; k < S; ++k) {
+      const bool runs = h_off[k + 1] > h_off[k];
+      fleet_fc_series(f, k, runs, fc, &fs.op[k]);
+      if (!runs) continue;
+      const size_t r = (size_t)h_off[k];
+      const bool on = fc->fc_rc[k] == CSSM_OK && std::isfinite(t[k]) && t[k] >= f->t[k];
+      fs.flags[r] = on ? (CSSM_FLEET_FC_ON | ((has_obs ? has_obs[k] : 1) ? CSSM_FLEET_FC_HAS : 0u)) : 0u;
+      fs.keys[r] = fc->keys ? fc->keys[k] : cssm_pf_run_key(f->models[k].seed, (1ull << 63) | (uint64_t)f->step[k]);
+      fs.y[r] = y[k];
+    }
+  }
   if (iv) {   // (no launch of a step draws a cloud: the f coefficients of a t0 are not read)
     iv->step = true; iv->rows = S;
     memset(h_recs + R * RB, 0, (size_t)S * f->d * 8u);
   }
-  rc = fleet_launch(f, R, nullptr, nullptr, false, nullptr, nullptr, iv);
+  rc = fleet_launch(f, R, nullptr, nullptr, false, nullptr, nullptr, iv, fc);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
+    if (fc_rc_out) fc_rc_out[k] = fc->fc_rc[k];
     if (active && !active[k]) { rc_out[k] = CSSM_OK; continue; }            // untouched
     if (!f->live[k]) { rc_out[k] = CSSM_ESTATE; continue; }                 // no cloud: never initialised, or failed since
     const FleetSeries& s = f->h_ser[k];
@@ -692,7 +858,9 @@ static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t,
     if (iv)
       fleet_iv_row(f, k, iv->out.data() + (size_t)k * (f->d + 1) * 3u,
                    reinterpret_cast<const double*>(h_recs + (size_t)h_off[k] * RB + sizeof(FleetRecHead)) + 4 * f->d, *ivo, k);
+    if (fc) fleet_fc_row(f, *fc, k, (fs.flags[(size_t)h_off[k]] & CSSM_FLEET_FC_ON) != 0u, *fco, k);
   }
+  if (fc && !fc->scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", fc->scale_msg.c_str());   // (the call succeeds)
   return CSSM_OK;
 }
 
@@ -714,6 +882,23 @@ extern "C" int cssm_fleet_step_intervals(cssm_fleet* f, const uint8_t* active, c
   iv.interval = interval;
   const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
   return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, &iv, &o);
+}
+
+// getMeanForecast over a filterStream, one observation per sensor per call: cssm_fleet_step -- the same arguments, bits and statuses -- and
+// before the record is stepped cssm_fleet_forecast of its time, from the same launch.  The entries of a series that is inactive, has no
+// cloud or fails are not written.
+extern "C" int cssm_fleet_step_forecast(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                                        const uint64_t* keys, double interval, double* ll_out, int32_t* ess_out, double* state_mean,
+                                        double* state_lower, double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper,
+                                        double* obs_mean, double* obs_lower, double* obs_upper, int32_t* obs_below, int32_t* obs_equal,
+                                        int* rc_out, int* fc_rc_out) {
+  if (!t || !y || !rc_out || !fc_rc_out) return fail(CSSM_EINVAL_ARG, "null argument (t, y, rc_out, fc_rc_out)");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  FleetFc fc;
+  fc.interval = interval; fc.keys = keys;
+  const FleetFcOut o{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal};
+  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, nullptr, nullptr, &fc, &o, fc_rc_out);
 }
 
 extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_mean, double* state_lower, double* state_upper,
@@ -779,8 +964,6 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
 // keys, observation parameters, buffer numbers, records), one launch whose blocks are the series (k_fleet_forecast), one read-back.
 // A call that returns samples runs the fleet in chunks of series whose samples fit fc_samp_max -- never chunks of horizons: a series
 // is one block's work.  What a series' own arguments spoil is the series' own: its status, NaN in its outputs, no block for it.
-static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
-
 // the grow-only buffers of both forecasts: `need` bytes of d_fc and of its pinned mirror, 16 N bytes of eta / obs staging per series
 static int fleet_fc_ensure(cssm_fleet* f, size_t need) {
   if (need > f->h_fc_cap) {
@@ -1240,6 +1423,7 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
       l.args.ctl = nullptr; l.args.recs = f->d_ip + o[1];
       l.args.ll_t = nullptr; l.args.ess_t = nullptr; l.args.logtab = f->logtab; l.args.mk = f->base.mk;
       l.args.picks = nullptr; l.args.path = nullptr; l.args.last = nullptr;
+      l.args.fc = FleetOneStep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
       l.args.hist = d_hist; l.args.hanc = d_hanc; l.args.hser = reinterpret_cast<FleetSeries*>(f->d_ip + o[3]); l.args.k0 = k0;
       l.n_series = Sc; l.path = false; l.hist = true; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
       rc = fleet_series_launch(d, l);

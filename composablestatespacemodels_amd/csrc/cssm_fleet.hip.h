@@ -15,6 +15,7 @@
 #define CSSM_FLEET_WAVES(D) ((D) <= 4 ? 4 : 2)   /* waves per SIMD the register allocation aims at (the table and the A/B) */
 
 #include "cssm_fleet_intervals.hip.h"
+#include "cssm_fleet_onestep.hip.h"
 
 // What the host uploads per (series, observation): the fields of cssm_build_rec's StepRec the kernels of a non-LGCP model read, with
 // exactly the d components in use -- 80 + 40 d bytes (120 at d = 1, 200 at d = 3, 720 at d = 16) instead of sizeof(StepRec).  The
@@ -78,6 +79,10 @@ struct FleetArgs {
   uint32_t iv_rows;
   uint32_t iv_np2;                   // the power of two >= max(n, 2): the keys a row's sort holds where the weights were
   FleetRowRanks iv_rk;
+  // the one-step-ahead forecast of every record before it is stepped (k_fleet_series<D, false, false, false, true> only:
+  // cssm_fleet_filter_forecasts / cssm_fleet_step_forecast; model/ParticleFilter.scala:368-409 over a filter stream), behind every field
+  // the other instantiations read.  It takes iv_np2, iv_rk and iv_rows (1: the row of a record is its series' number) as IVAL does.
+  FleetOneStep fc;
 };
 
 // a - b mod 2^128 (integers: exact)
@@ -114,7 +119,12 @@ __device__ __forceinline__ void fleet_path_row(const double* buf, const uint32_t
 // barrier that completes the initial draw and behind the one that completes a record's cloud and ancestors, with the record's own f
 // coefficients (s_rec.fco is F at the record's time).  The keys of a row's sort live where the weights were (dead once the resampling
 // has read them), so the dynamic LDS is 8 np2 + 4 n bytes.  A template flag again: the other three instantiations hold no trace of it.
-template <int D, bool PATH, bool HIST = false, bool IVAL = false>
+// FCST: llFilter that also forecasts every record just before it is stepped (FleetArgs::fc, cssm_fleet_onestep.hip.h) -- behind the
+// barrier that completes the record in LDS: the cloud before the record through s_anc, one transition over the record's own dt and
+// coefficients under the record's forecast key, into the record's destination buffer, which step 1 overwrites afterwards.  The keys of a
+// row live where the weights were, as under IVAL (dead between a record's resampling and the next record's weighing).  A template flag
+// once more: the other four instantiations hold no trace of it.
+template <int D, bool PATH, bool HIST = false, bool IVAL = false, bool FCST = false>
 __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_series(const FleetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   __shared__ StepRec s_rec;
@@ -124,7 +134,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   const uint32_t n = a.n, k = blockIdx.x, tid = threadIdx.x, bs = blockDim.x;
   const uint32_t lane = tid & 63u, wid = tid >> 6, nw = bs >> 6;
   double* s_lw = reinterpret_cast<double*>(s_dyn);
-  uint32_t* s_anc = reinterpret_cast<uint32_t*>(s_dyn + (size_t)(IVAL ? a.iv_np2 : ((n + 1u) & ~1u)) * 8u);
+  uint32_t* s_anc = reinterpret_cast<uint32_t*>(s_dyn + (size_t)((IVAL || FCST) ? a.iv_np2 : ((n + 1u) & ~1u)) * 8u);
   const unsigned long long r0 = a.off[k], r1 = a.off[k + 1];
   const uint32_t ctl = HIST ? CSSM_FLEET_CTL_INIT : a.ctl[k];   // (HIST: a series is always run from its initial cloud)
   if ((HIST || !(ctl & CSSM_FLEET_CTL_INIT)) && r0 >= r1) return;   // (uniform) nothing for this series in this launch: untouched
@@ -188,6 +198,17 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     const double* src = st + (size_t)(HIST ? (uint32_t)(r - r0) : (step & 1u)) * D * n;
     double* dst = st + (size_t)(HIST ? (uint32_t)(r - r0) + 1u : ((step & 1u) ^ 1u)) * D * n;
     if (PATH) cur = (step & 1u) ^ 1u;
+    if constexpr (FCST) {                                       // (uniform) the forecast of this record from the cloud before it
+      __shared__ double s_fcp[CSSM_FLEET_MAX_THREADS / 64];     // the waves' partial sums of a row's mean ...
+      __shared__ uint32_t s_fcc[2 * (CSSM_FLEET_MAX_THREADS / 64)];   // ... and their PIT counts
+      const uint32_t fl = a.fc.flags[r];
+      if (fl & CSSM_FLEET_FC_ON) {
+        const size_t row = a.iv_rows ? (size_t)k : (size_t)r;
+        fleet_onestep_forecast<D>(a.mk, rec, src, dst, s_anc, n, a.iv_np2, a.fc.keys[r], a.fc.op[k], a.fc.stage + (size_t)k * 2u * n, tab, a.iv_rk,
+                                  reinterpret_cast<unsigned long long*>(s_lw), s_fcp, s_fcc, a.fc.y[r], (fl & CSSM_FLEET_FC_HAS) != 0u,
+                                  a.fc.out + row * (D + 2) * 3u, a.fc.pit + row * 2u);
+      }
+    }
     // 1. gather through the previous ancestors, transition, f, log-density (:118, :123)
     double tmax = -cssm_inf();
     bool bad = false;
@@ -313,6 +334,7 @@ struct FleetLaunch {
   bool path;            // k_fleet_series<D, true>
   bool hist = false;    // k_fleet_series<D, false, true>: n_series blocks, the series args.k0 .. args.k0 + n_series - 1
   bool ival = false;    // k_fleet_series<D, false, false, true>: lds = 8 args.iv_np2 + 4 n bytes
+  bool fcst = false;    // k_fleet_series<D, false, false, false, true>: the same lds
   int threads;
   size_t lds;
   hipStream_t stream;

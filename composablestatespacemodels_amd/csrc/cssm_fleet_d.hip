@@ -12,7 +12,8 @@
 #define CSSM_FLEET_NAME(d) CSSM_FLEET_NAME2(d)
 
 int CSSM_FLEET_NAME(CSSM_FLEET_D)(const FleetLaunch& l) {
-  if (l.ival) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false, false, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
+  if (l.fcst) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false, false, false, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
+  else if (l.ival) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false, false, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
   else if (l.hist) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
   else if (l.path) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
   else hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);

@@ -118,15 +118,7 @@ __device__ __forceinline__ void fleet_forecast_body(const FleetFcArgs& a, Src& s
     for (uint32_t row = 0; row < (uint32_t)D + 2u; ++row) {
       __syncthreads();                                          // the horizon's values are written; the row before is read
       const double* v = (row < (uint32_t)D) ? wrk + (size_t)row * n : stage + (size_t)(row - (uint32_t)D) * n;
-      double acc = 0.0;
-      for (uint32_t i = tid; i < np2; i += bs) {
-        unsigned long long kk = ~0ull;
-        if (i < n) { const double x = v[i]; acc += x; kk = cssm_order_key(x); }
-        s_keys[i] = kk;
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-      if ((tid & 63u) == 0u) s_p[tid >> 6] = acc;
+      fleet_row_keys(v, n, np2, s_keys, s_p);
       const uint32_t lo = row < (uint32_t)D ? a.lo_state : a.lo_eta, hi = row < (uint32_t)D ? a.hi_state : a.hi_eta;
       unsigned long long klo, khi;
       if (a.select) {                                           // (uniform)
@@ -170,19 +162,7 @@ __device__ __forceinline__ void fleet_forecast_body(const FleetFcArgs& a, Src& s
         __syncthreads();
         klo = s_pre[0]; khi = s_pre[1];
       } else {
-        for (uint32_t k2 = 2u; k2 <= np2; k2 <<= 1) {
-          for (uint32_t j = k2 >> 1; j > 0u; j >>= 1) {
-            __syncthreads();
-            for (uint32_t i = tid; i < np2; i += bs) {
-              const uint32_t q = i ^ j;
-              if (q > i) {
-                const unsigned long long x = s_keys[i], y = s_keys[q];
-                const bool up = (i & k2) == 0u;
-                if ((x > y) == up) { s_keys[i] = y; s_keys[q] = x; }
-              }
-            }
-          }
-        }
+        fleet_sort_keys(s_keys, np2, tid, bs);
         __syncthreads();
         klo = s_keys[lo]; khi = s_keys[hi];
       }

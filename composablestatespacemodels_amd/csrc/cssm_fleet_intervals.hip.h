@@ -12,6 +12,44 @@ struct FleetRowRanks {
   uint32_t lo_state, hi_state, lo_eta, hi_eta;
 };
 
+// What the row summaries of a forecast share (fleet_forecast_body of cssm_fleet_forecast.hip, fleet_onestep_forecast of
+// cssm_fleet_onestep.hip.h), written once.  fleet_cloud_intervals below keeps its own statement of the network: it adds a row in another
+// order (k_fleet_summary's), and called from there the shared function moved the registers of k_fleet_series<6, false, false, true>
+// (211 -> 168 VGPRs), which no change to another instantiation may do.
+// fleet_sort_keys: k_fleet_summary's bitonic network over the np2 keys of a row in LDS, ascending; every stage opens with a barrier (so
+// the keys may have been written just before the call), the caller closes with one before it reads a rank.
+__device__ __forceinline__ void fleet_sort_keys(unsigned long long* s_keys, uint32_t np2, uint32_t tid, uint32_t bs) {
+  for (uint32_t k2 = 2u; k2 <= np2; k2 <<= 1) {
+    for (uint32_t j = k2 >> 1; j > 0u; j >>= 1) {
+      __syncthreads();
+      for (uint32_t i = tid; i < np2; i += bs) {
+        const uint32_t p = i ^ j;
+        if (p > i) {
+          const unsigned long long x = s_keys[i], y = s_keys[p];
+          const bool up = (i & k2) == 0u;
+          if ((x > y) == up) { s_keys[i] = y; s_keys[p] = x; }
+        }
+      }
+    }
+  }
+}
+// fleet_row_keys: the n values of a row (`v`, written by this block behind a barrier) as order-preserving keys, padded to np2 with the
+// largest key, and the row's sum in a forecast's order of additions -- thread tid adds v[tid], v[tid + blockDim], ..., a butterfly over
+// each wave, the waves' sums in s_p for the thread that adds them left to right.  Both forecasts of a fleet run blocks of the fleet's
+// one size, so a row's mean has the same bits from either.
+__device__ __forceinline__ void fleet_row_keys(const double* v, uint32_t n, uint32_t np2, unsigned long long* s_keys, double* s_p) {
+  const uint32_t tid = threadIdx.x, bs = blockDim.x;
+  double acc = 0.0;
+  for (uint32_t i = tid; i < np2; i += bs) {
+    unsigned long long kk = ~0ull;
+    if (i < n) { const double x = v[i]; acc += x; kk = cssm_order_key(x); }
+    s_keys[i] = kk;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((tid & 63u) == 0u) s_p[tid >> 6] = acc;
+}
+
 // The cloud is `buf` ([D][n], SoA) read through `s_anc` (LDS, n entries); `s_keys` holds np2 keys of LDS nothing else uses meanwhile,
 // np2 the power of two >= max(n, 2); `fco` the D f coefficients at the cloud's time (any address space); `out` = [D + 1][3]: mean, lower,
 // upper.  Every thread of the block calls it, behind a barrier that completed buf and s_anc; it ends behind a barrier of its own, so

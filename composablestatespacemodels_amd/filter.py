@@ -518,6 +518,84 @@ class NativePfFleet:
         return (ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)],
                 self.interpolate_rows(off, (m, lo, hi, em, el, eu)), rc)
 
+    FORECAST_NAMES = ("state_mean", "state_lower", "state_upper", "eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")
+
+    def _forecast_arrays(self, rows: int):
+        """The nine statistics of ``forecast`` and the two PIT counts for ``rows`` rows, preset to NaN / -1, and their pointers in the
+        C call's order."""
+        arr = {k: np.full((rows, self.d), np.nan) for k in self.FORECAST_NAMES[:3]}
+        arr.update({k: np.full(rows, np.nan) for k in self.FORECAST_NAMES[3:]})
+        arr.update({k: np.full(rows, -1, dtype=np.int32) for k in ("obs_below", "obs_equal")})
+        ptrs = [_p(arr[k]) for k in self.FORECAST_NAMES] + [_p(arr[k], C.POINTER(C.c_int32)) for k in ("obs_below", "obs_equal")]
+        return arr, ptrs
+
+    def filter_forecasts(self, datas, interval: float = 0.975, keys=None):
+        """cssm_fleet_filter_forecasts: ``ll_filter`` and, from the same launch, before every record is stepped, ``forecast`` of the
+        record's time from the cloud before it (``ParticleFilter.getMeanForecast`` mapped over the filter stream).  ``keys``: per series
+        an array of T_k Philox keys (None: the rule of ``forecast_key`` for every record).  ``(ll[S], [ll_t of series k], [ess_t of
+        series k], fc, rc[S], fc_rc[S])``; ``fc`` is a list of S dicts with the nine statistic names of ``forecast`` plus ``obs_below``
+        / ``obs_equal`` (the PIT counts: draws strictly below / equal to the datum; -1 without one), shapes [T_k, ...].  A row reads
+        NaN behind the record at which the series failed, for a record whose time ``forecast`` refuses, and throughout a series whose
+        ``fc_rc`` is not zero (a model without the scale its observation draw needs).  The fleet continues with ``step``."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        if keys is not None and len(keys) != self.S:
+            raise ValueError("one array of keys per series")
+        off, t, y, has = self.pack(datas, allow_empty=True)
+        ky = None
+        if keys is not None:
+            o = [int(v) for v in off]
+            per = [np.asarray([int(x) & (2**64 - 1) for x in np.asarray(v, dtype=object).ravel()], dtype=np.uint64) for v in keys]
+            for k in range(self.S):
+                if len(per[k]) != o[k + 1] - o[k]:
+                    raise ValueError(f"series {k}: one key per record ({o[k + 1] - o[k]}), not {len(per[k])}")
+            ky = np.ascontiguousarray(np.concatenate(per) if per else np.zeros(0), dtype=np.uint64)
+        return self.filter_forecasts_packed(off, t, y, has, interval, ky)
+
+    def filter_forecasts_packed(self, off, t, y, has, interval: float = 0.975, keys=None):
+        """``filter_forecasts`` on arrays ``pack`` made and (optional) a uint64 array of off[-1] keys."""
+        R = self._check_packed(off, t, y, has)
+        if keys is not None and (keys.dtype != np.uint64 or len(keys) != R or not keys.flags.c_contiguous):
+            raise ValueError(f"keys must be a C-contiguous uint64 array of off[-1] = {R} entries")
+        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32); fc_rc = np.zeros(self.S, dtype=np.int32)
+        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
+        arr, ptrs = self._forecast_arrays(R)
+        tt, yy, hh = (t, y, has) if R else (np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.uint8))
+        u64 = C.POINTER(C.c_uint64)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_filter_forecasts(self._h, _p(off, u64), _p(tt), _p(yy), _p(hh, C.POINTER(C.c_uint8)),
+                                                        _p(keys, u64) if keys is not None and R else None, float(interval), _p(ll), _p(ll_t),
+                                                        _p(ess_t, C.POINTER(C.c_int32)), *ptrs, _p(rc, C.POINTER(C.c_int)),
+                                                        _p(fc_rc, C.POINTER(C.c_int))))
+        o = [int(v) for v in off]
+        fc = [{name: v[o[k]:o[k + 1]] for name, v in arr.items()} for k in range(self.S)]
+        return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], fc, rc, fc_rc
+
+    def step_forecast(self, t, y, has=None, active=None, keys=None, interval: float = 0.975):
+        """cssm_fleet_step_forecast: ``step`` and, from the same launch, before the record is stepped, ``forecast`` of its time:
+        ``(ll[S], ess[S], fc, rc[S], fc_rc[S])``; ``fc`` a dict of the nine statistics ([S, d] / [S]) and the PIT counts
+        ``obs_below`` / ``obs_equal``; entries of series that are inactive, have no cloud or fail are NaN / -1.  ``keys``: S Philox
+        keys (None: ``forecast_key(k)``)."""
+        t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+        if len(t) != self.S or len(y) != self.S:
+            raise ValueError("one (t, y) per series")
+        if keys is not None and len(keys) != self.S:
+            raise ValueError("one key per series")
+        hp = ap = kp = None
+        if has is not None:
+            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
+        if keys is not None:
+            keys = np.ascontiguousarray([int(x) & (2**64 - 1) for x in keys], dtype=np.uint64); kp = _p(keys, C.POINTER(C.c_uint64))
+        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32)
+        rc = np.zeros(self.S, dtype=np.int32); fc_rc = np.zeros(self.S, dtype=np.int32)
+        arr, ptrs = self._forecast_arrays(self.S)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_step_forecast(self._h, ap, _p(t), _p(y), hp, kp, float(interval), _p(ll), _p(ess, C.POINTER(C.c_int32)),
+                                                     *ptrs, _p(rc, C.POINTER(C.c_int)), _p(fc_rc, C.POINTER(C.c_int))))
+        return ll, ess, arr, rc, fc_rc
+
     def interpolate(self, datas, interval: float = 0.975, reference_pairing: bool = False):
         """cssm_fleet_interpolate: ``NativePf.interpolate`` of every series in two launches.  ``(ll[S], per-series list of (mean[T_k + 1,
         d], lower, upper, eta_of_mean[T_k + 1], eta_lower, eta_upper), rc[S])``; rc[k] != 0 is series k's own status (-6: no records,
@@ -1156,7 +1234,14 @@ class FilterFleet:
         ``getIntervals``, examples/Filtering.scala:24-31): the new states, and per series its ``PfOut`` -- None where ``ys[k]`` is None."""
         return self._step(states, ys, float(interval))
 
-    def _step(self, states, ys, interval: Optional[float]):
+    def stepForecast(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]],
+                     interval: float = 0.975) -> Tuple[List[FleetState], List[Optional[ForecastOut]]]:
+        """``getMeanForecast`` of every datum's time from the state before it, then ``stepFilter``, from one device call
+        (``ParticleFilter.getMeanForecast`` mapped over a ``filterStream``, :368-409): the new states, and per series the
+        ``ForecastOut`` at its datum's time under the series' default key -- None where ``ys[k]`` is None."""
+        return self._step(states, ys, float(interval), forecast=True)
+
+    def _step(self, states, ys, interval: Optional[float], forecast: bool = False):
         if len(states) != self.S or len(ys) != self.S:
             raise ValueError("one state and one (optional) observation per series")
         if any(s._owner is not self._fleet or s._generation != self._fleet.generation for s in states):
@@ -1167,6 +1252,11 @@ class FilterFleet:
         y = np.array([o.observation if h else 0.0 for o, h in zip(ys, has)], dtype=np.float64)
         if interval is None:
             ll, ess, rc = self._fleet.step(t, y, has, act)
+        elif forecast:
+            ll, ess, rows, rc, fc_rc = self._fleet.step_forecast(t, y, has, act, None, interval)
+            for k in range(self.S):
+                if fc_rc[k]:
+                    raise _abi.CssmError(int(fc_rc[k]), self._fleet.lib.cssm_last_error().decode() or f"series {k}: its forecast was refused")
         else:
             ll, ess, rows, rc = self._fleet.step_intervals(t, y, has, act, interval)
         for k in range(self.S):
@@ -1178,6 +1268,8 @@ class FilterFleet:
                          [s.ess if s is not None else ess[k] for k, s in enumerate(keep)])
         if interval is None:
             return new, None
+        if forecast:
+            return new, [_forecast_outs([new[k].t], {name: v[k:k + 1] for name, v in rows.items()})[0] if act[k] else None for k in range(self.S)]
         m, lo, hi, em, el, eu = rows
         return new, [PfOut(new[k].t, new[k].observation, float(em[k]), CredibleInterval(float(el[k]), float(eu[k])), m[k].copy(),
                            [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k], hi[k])]) if act[k] else None for k in range(self.S)]
@@ -1216,6 +1308,20 @@ class FilterFleet:
                 raise _abi.CssmError(int(rc[k]), f"series {k}: " + ("it has no records" if rc[k] == _abi.CSSM_EINVAL_ARG else "its weights were unusable"))
         self._states = []
         return [_interpolate_outs(datas[k], split[k][0], rows[k]) for k in range(self.S)]
+
+    def filterForecasts(self, datas: Sequence[Sequence[TimedObservation]], interval: float = 0.975) -> List[List[ForecastOut]]:
+        """``ParticleFilter.getMeanForecast`` (:368-409) mapped over the filter stream of every series in one device call (one launch):
+        per series one ``ForecastOut`` per datum, at the datum's time, from the state before the datum and under the key
+        ``getMeanForecast`` takes there by default.  ``formats.forecast_out_csv`` writes the reference's lines from them."""
+        split = [split_data(d) for d in datas]
+        _, _, _, fc, rc, fc_rc = self._fleet.filter_forecasts(split, float(interval))
+        for k in range(self.S):
+            if rc[k]:
+                raise _abi.CssmError(int(rc[k]), f"series {k}: " + ("it has no records" if rc[k] == _abi.CSSM_EINVAL_ARG else "its weights were unusable"))
+            if fc_rc[k]:
+                raise _abi.CssmError(int(fc_rc[k]), self._fleet.lib.cssm_last_error().decode() or f"series {k}: its forecasts were refused")
+        self._states = []
+        return [_forecast_outs([float(v) for v in split[k][0]], fc[k]) for k in range(self.S)]
 
     def interpolate(self, datas: Sequence[Sequence[TimedObservation]], interval: float = 0.975,
                     reference_pairing: bool = False) -> List[Tuple[float, List[PfOut]]]:

@@ -881,6 +881,51 @@ int cssm_fleet_step_intervals(cssm_fleet* f, const uint8_t* active, const double
                               double* state_mean, double* state_lower, double* state_upper,
                               double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out);
 
+/* One-step-ahead forecasts inside the filtering launch: ParticleFilter.getMeanForecast mapped over a filter stream
+ * (model/ParticleFilter.scala:368-409) -- from every PfState the forecast of the time of the NEXT observation, before that observation
+ * is weighed: the prequential check of a filtered sensor -- of every series, in ONE launch.
+ *   The filter part.  off / t / y / has_obs / ll_out / ll_t / ess_t / rc_out are cssm_fleet_ll_filter's arguments bit for bit, and the
+ *   cloud, ancestors, clock, observation index and statuses left behind are the ones it leaves.
+ *   The forecast of record r.  Outputs are laid out like t: R = off[S] rows, state_* [R][d], eta_* / obs_* / obs_below / obs_equal [R]; any
+ *   of them may be NULL.  Row r is bit for bit what cssm_fleet_forecast returns for that series with the single horizon t[r] under key
+ *   keys[r], issued just before the record is stepped: the source is the series' cloud before record r through its ancestors (the
+ *   initial cloud at the slice's smallest time for the first record); one transition over t[r] - clock on the paired CSSM_STREAM_STEP
+ *   streams under keys[r], horizon index 0 (dt = 0 allowed); gamma and eta at t[r] under the series' own parameters; one observation draw
+ *   on CSSM_STREAM_OBS with the series' own scale; ranks and clamping as documented at cssm_pf_forecast, order statistics exact, means
+ *   plain fp64 sums in cssm_fleet_forecast's order.  The record's own y plays no part in its row; a record without a datum gets a row
+ *   like any other.  keys == NULL: keys[r] = cssm_pf_run_key(seed_k, 2^63 | observation index of the cloud before the record), the rule of
+ *   thumb of cssm_fleet_forecast.
+ *   EXTENSION (the reference has none): obs_below[r] / obs_equal[r] = how many of the N drawn observations are strictly below / equal to
+ *   y[r] -- the counts of the probability integral transform; both read -1 for a record without a datum and for a NaN row.
+ *   Statuses.  Every row is preset to NaN.  A series that fails with CSSM_ENONFINITE at record s keeps rows 0 .. s (row s is formed before
+ *   the weighing) and reads NaN from row s + 1 on.  A record whose time is not finite or lies before the series' clock has a NaN row --
+ *   cssm_fleet_forecast refuses such a time --, and the filter treats the record as cssm_fleet_ll_filter does.  fc_rc_out[S] (required) is
+ *   the forecast's own status: CSSM_OK, or CSSM_EINVAL_ARG for a series whose model lacks the scale its observation draw needs: every
+ *   forecast row of that series is NaN, its filter results are untouched, and cssm_last_error carries the reference's exception for the
+ *   first such series although the call succeeds.  No other series notices any of this.
+ * Samples are not offered here: at fleet scale they are R (d + 3) N doubles, and cssm_fleet_forecast serves a caller who wants them for
+ * one state.  Null off / t / y / ll_out / rc_out / fc_rc_out, off[0] != 0, an interval outside (0, 1] and a null fleet are refused with
+ * CSSM_EINVAL_ARG before the fleet is looked at; a decreasing off as by cssm_fleet_ll_filter.  The device time is cssm_fleet_last_ms()[0]. */
+int cssm_fleet_filter_forecasts(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                const uint64_t* keys, double interval, double* ll_out, double* ll_t, int32_t* ess_t,
+                                double* state_mean, double* state_lower, double* state_upper,
+                                double* eta_mean, double* eta_lower, double* eta_upper,
+                                double* obs_mean, double* obs_lower, double* obs_upper,
+                                int32_t* obs_below, int32_t* obs_equal, int* rc_out, int* fc_rc_out);
+/* The streaming shape of cssm_fleet_filter_forecasts (one observation per sensor per call): cssm_fleet_step -- active / t / y / has_obs /
+ * ll_out / ess_out / rc_out are its arguments, bits and statuses -- and, before the record is stepped, cssm_fleet_forecast of the single
+ * horizon t[k] under keys[k] ([S]; NULL: the rule above with the series' current observation index), from the same launch.  state_*
+ * [S][d], the others [S], any may be NULL; the entries of a series that is inactive, has no cloud (CSSM_ESTATE) or fails
+ * (CSSM_ENONFINITE) are not written, as its ll_out / ess_out entries are not; an active series whose time is refused, or whose model
+ * lacks its scale (fc_rc_out[k] = CSSM_EINVAL_ARG), reads NaN and -1.  Null t / y / rc_out / fc_rc_out, an interval outside (0, 1] and a
+ * null fleet are refused with CSSM_EINVAL_ARG before the fleet is looked at.  The device time is cssm_fleet_last_ms()[0]. */
+int cssm_fleet_step_forecast(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                             const uint64_t* keys, double interval, double* ll_out, int32_t* ess_out,
+                             double* state_mean, double* state_lower, double* state_upper,
+                             double* eta_mean, double* eta_lower, double* eta_upper,
+                             double* obs_mean, double* obs_lower, double* obs_upper,
+                             int32_t* obs_below, int32_t* obs_equal, int* rc_out, int* fc_rc_out);
+
 /* cssm_pf_summary (getIntervals, model/ParticleFilter.scala:415-424) of every series at its own time: state_* [S * d], eta_* [S];
  * any may be NULL.  Order statistics exact, ranks and clamping as documented there, means plain fp64 sums.  A series without a
  * cloud reads NaN. */
