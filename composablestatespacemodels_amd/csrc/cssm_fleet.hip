@@ -24,11 +24,47 @@
 
 static_assert(CSSM_FLEET_MAX_N <= 4096, "k_fleet_summary sorts at most 4096 keys in LDS; k_fleet_series holds 12 bytes per particle there");
 
+// A grow-only allocation of the fleet, on the device or pinned on the host.  It frees itself with the fleet: cssm_fleet_destroy keeps no
+// list of them.
+struct FleetBuf {
+  void* p = nullptr;
+  size_t cap = 0;   // bytes
+  const bool pinned;
+  explicit FleetBuf(bool pinned_ = false) : pinned(pinned_) {}
+  FleetBuf(const FleetBuf&) = delete;
+  FleetBuf& operator=(const FleetBuf&) = delete;
+  ~FleetBuf() { release(); }
+  void release() {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr; cap = 0;
+  }
+  // room for `bytes` -- and (slack) a quarter more, for what grows a little from call to call; false: no memory, the buffer is empty
+  bool reserve(size_t bytes, bool slack) {
+    if (bytes <= cap) return true;
+    release();
+    const size_t want = slack ? bytes + bytes / 4 : bytes;
+    if ((pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) { p = nullptr; return false; }
+    cap = want;
+    return true;
+  }
+  template <class T> T* at(size_t byte = 0) const { return reinterpret_cast<T*>(static_cast<unsigned char*>(p) + byte); }
+};
+// ... the same view of any staged bytes (a layout struct names the offsets once; its host and device views are taken with this)
+template <class T> static T* fleet_at(void* base, size_t byte) { return reinterpret_cast<T*>(static_cast<unsigned char*>(base) + byte); }
+static size_t fleet_pad8(size_t bytes) { return (bytes + 7u) & ~(size_t)7u; }
+
+enum FleetEvent {
+  EV_CALL_BEGIN, EV_CALL_END,             // a series launch: init / filter / step call
+  EV_SUMMARY_BEGIN, EV_SUMMARY_END,
+  EV_FORECAST_BEGIN, EV_FORECAST_END,
+  EV_PATH_UPLOADED, EV_PATH_KERNEL_END,   // a path launch's upload | kernel | read-back
+  EV_COUNT
+};
+
 struct cssm_fleet {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // filter / step call, summary, forecast,
-                                                                                                 // [6], [7]: a path launch's upload | kernel | read-back
+  hipEvent_t ev[EV_COUNT] = {};
   uint32_t n = 0, S = 0;
   int d = 0, threads = 64;
   size_t lds = 0;
@@ -40,35 +76,26 @@ struct cssm_fleet {
   std::vector<int> obs_has_scale;       // ... the leftmost leaf's scale as stored (forecasts: cssm_obs_params_make)
   std::vector<double> obs_scale;
   bool par_dirty = true;
-  // device
-  double* state = nullptr; uint32_t* anc = nullptr; FleetSeries* ser = nullptr; FleetPar* par = nullptr; double* logtab = nullptr;
-  unsigned char* d_stage = nullptr; size_t stage_cap = 0;
-  double* d_ll_t = nullptr; int32_t* d_ess_t = nullptr; size_t res_cap = 0;
-  double* d_tmp = nullptr;              // d x n: cssm_fleet_get_particles
-  unsigned char* d_fcr = nullptr; size_t fcr_cap = 0;   // cssm_fleet_filter_forecasts / _step_forecast, grow-only: rows of [d + 2][3] doubles, then rows of 2 PIT counts
-  double* d_iv = nullptr; size_t iv_cap = 0;       // cssm_fleet_filter_intervals / _step_intervals, grow-only: rows of [d + 1][3] (mean, lower, upper)
-  double* d_path = nullptr; size_t path_cap = 0;   // cssm_fleet_filter, grow-only: [S][d] last rows, then (asked for) the R + S rows of the paths
-  float ms_upload = -1.f, ms_kernel = -1.f;        // ... of its last launch
-  double ms_build = 0.0;                           // ... host time of its records
-  double pm_split[6] = {0, 0, 0, 0, 0, 0};         // cssm_fleet_pmmh_run: see cssm_fleet_pmmh_last_split
-  double* d_sm = nullptr; size_t sm_cap = 0;   // summary: [S][d] f coefficients, [S][d + 1][3] results, [S] buffer numbers
-  // host staging (pinned)
-  unsigned char* h_stage = nullptr; size_t h_stage_cap = 0;
+  // device, sized by cssm_fleet_create: double [S][2][d][n] | uint32 [S][n] | FleetSeries [S] | FleetPar [S] | the contract's table |
+  // d x n doubles (cssm_fleet_get_particles)
+  FleetBuf state, anc, ser, par, logtab, d_tmp;
+  // grow-only, device and pinned host
+  FleetBuf d_stage, h_stage{true};      // a series launch as staged (FleetStage) and its pinned mirror
+  FleetBuf d_ll_t, d_ess_t;             // ... its per-observation results
+  FleetBuf d_rows;                      // ... what its rider writes: sampled paths, filtered intervals or one-step-ahead forecasts (FleetStage)
+  FleetBuf d_sm;                        // cssm_fleet_summary as staged (FleetSmStage)
+  FleetBuf d_fc, h_fc{true};            // cssm_fleet_forecast / _forecast_posterior as staged (FleetFcStage) and its pinned mirror
+  FleetBuf d_fc_scratch;                // [S][2][n]: eta and the observation draw of every forecast kernel (fleet_fc_scratch)
+  FleetBuf d_fc_samp;                   // the samples of one chunk of series (at most fc_samp_max bytes: CSSM_OPT_FORECAST_CAP)
+  FleetBuf d_ip, h_ip{true};            // one chunk of cssm_fleet_interpolate as staged (FleetIpStage) and its pinned mirror
+  FleetBuf d_ip_hist;                   // ... its lineage history (clouds, then ancestors: at most ip_hist_max bytes, CSSM_OPT_INTERP_CAP)
   std::vector<FleetSeries> h_ser;
   float ms_call = -1.f, ms_summary = -1.f, ms_forecast = -1.f;
-  // forecasts (cssm_fleet_forecast), grow-only: [off | keys | obs params | buffer numbers | records | results] and its pinned mirror,
-  // eta / obs staging of every series, the samples of one chunk of series (at most fc_samp_max bytes: CSSM_OPT_FORECAST_CAP)
-  unsigned char* d_fc = nullptr; size_t fc_cap = 0;
-  unsigned char* h_fc = nullptr; size_t h_fc_cap = 0;
-  double* d_fc_stage = nullptr;
-  double* d_fc_samp = nullptr; size_t fc_samp_cap = 0;
+  float ms_upload = -1.f, ms_kernel = -1.f;        // cssm_fleet_filter: ... of its last launch
+  double ms_build = 0.0;                           // ... host time of its records
+  double pm_split[6] = {0, 0, 0, 0, 0, 0};         // cssm_fleet_pmmh_run: see cssm_fleet_pmmh_last_split
   size_t fc_samp_max = (size_t)1 << 30;
   int fc_select = 0;                    // CSSM_OPT_FLEET_SELECT: 0 = by N (CSSM_FLEET_SELECT_MIN_N), 1 = bitonic sort, 2 = radix select
-  // interpolation (cssm_fleet_interpolate), grow-only: one chunk's [off | records | f coefficients | series scalars | results] and its
-  // pinned mirror; one chunk's lineage history (clouds, then ancestors: at most ip_hist_max bytes, CSSM_OPT_INTERP_CAP)
-  unsigned char* d_ip = nullptr; size_t ip_cap = 0;
-  unsigned char* h_ip = nullptr; size_t h_ip_cap = 0;
-  unsigned char* d_ip_hist = nullptr; size_t ip_hist_cap = 0;
   size_t ip_hist_max = (size_t)1 << 30;
   hipEvent_t ev_ip[3] = {nullptr, nullptr, nullptr};   // before the forward launch | between the two | behind the lineage launch
   double ms_ip[2] = {-1.0, -1.0};                      // ... of the last interpolation, summed over its chunks
@@ -172,15 +199,10 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  void* ptrs[] = {f->state, f->anc, f->ser, f->par, f->logtab, f->d_stage, f->d_ll_t, f->d_ess_t, f->d_tmp, f->d_path, f->d_iv, f->d_fcr, f->d_sm, f->d_fc, f->d_fc_stage, f->d_fc_samp, f->d_ip, f->d_ip_hist};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (f->h_stage) (void)hipHostFree(f->h_stage);
-  if (f->h_fc) (void)hipHostFree(f->h_fc);
-  if (f->h_ip) (void)hipHostFree(f->h_ip);
   for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : f->ev_ip) if (e) (void)hipEventDestroy(e);
   if (f->stream) (void)hipStreamDestroy(f->stream);
-  delete f;
+  delete f;   // (every FleetBuf frees itself)
 }
 
 extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out) {
@@ -213,12 +235,11 @@ extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particl
   for (hipEvent_t& e : f->ev) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   for (hipEvent_t& e : f->ev_ip) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   const size_t rows = (size_t)S * 2u * f->d * n;
-  if (hipMalloc(&f->state, rows * 8) != hipSuccess || hipMalloc(&f->anc, (size_t)S * n * 4) != hipSuccess ||
-      hipMalloc(&f->ser, (size_t)S * sizeof(FleetSeries)) != hipSuccess || hipMalloc(&f->par, (size_t)S * sizeof(FleetPar)) != hipSuccess ||
-      hipMalloc(&f->logtab, sizeof(CSSM_TAB)) != hipSuccess || hipMalloc(&f->d_tmp, (size_t)f->d * n * 8) != hipSuccess)
+  if (!f->state.reserve(rows * 8, false) || !f->anc.reserve((size_t)S * n * 4, false) || !f->ser.reserve((size_t)S * sizeof(FleetSeries), false) ||
+      !f->par.reserve((size_t)S * sizeof(FleetPar), false) || !f->logtab.reserve(sizeof(CSSM_TAB), false) || !f->d_tmp.reserve((size_t)f->d * n * 8, false))
     return bail(CSSM_ENOMEM, "device memory (16 d N bytes of state per series)");
-  if (hipMemcpyAsync(f->logtab, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice, f->stream) != hipSuccess ||
-      hipMemsetAsync(f->ser, 0, (size_t)S * sizeof(FleetSeries), f->stream) != hipSuccess ||
+  if (hipMemcpyAsync(f->logtab.p, CSSM_TAB, sizeof(CSSM_TAB), hipMemcpyHostToDevice, f->stream) != hipSuccess ||
+      hipMemsetAsync(f->ser.p, 0, (size_t)S * sizeof(FleetSeries), f->stream) != hipSuccess ||
       hipStreamSynchronize(f->stream) != hipSuccess)
     return bail(CSSM_EHIP, "uploading the contract's table");
   *out = f;
@@ -288,65 +309,186 @@ static int fleet_upload_par(cssm_fleet* f) {
     hp[k].seed = m.seed;
     for (int c = 0; c < m.d; ++c) { hp[k].m0[c] = m.comp[c].m0; hp[k].sd0[c] = std::sqrt(m.comp[c].c0); }
   }
-  HIP_TRY(hipMemcpyAsync(f->par, hp.data(), (size_t)f->S * sizeof(FleetPar), hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipMemcpyAsync(f->par.p, hp.data(), (size_t)f->S * sizeof(FleetPar), hipMemcpyHostToDevice, f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));   // (hp is pageable and dies here)
   f->par_dirty = false;
   return CSSM_OK;
 }
 
-// staging layout of a launch: [S + 1 offsets (u64)] [S control words (u32), padded to 8 bytes] [R compact records]
-static size_t fleet_stage_head(const cssm_fleet* f) { return ((size_t)f->S + 1u) * 8u + (((size_t)f->S * 4u + 7u) & ~(size_t)7u); }
-
-// What a launch that also writes getIntervals of its clouds carries and brings back (k_fleet_series<D, false, false, true>).
-struct FleetIv {
-  double interval;
-  bool step;                  // one row per series (cssm_fleet_step_intervals), not T_k + 1 rows per series
-  size_t rows = 0;            // of [d + 1][3] doubles: S, or R + S
-  std::vector<double> out;    // the rows as the device left them; NaN where no block wrote
+// The interval ranks of a cloud of n (a state row; the eta / observation rows, as cssm_pf_summary takes them) and the power of two
+// >= max(n, 2) a row's sort in LDS pads to: what every kernel that summarises rows takes.
+struct FleetRanks {
+  FleetRowRanks rk;
+  uint32_t np2;
 };
+static FleetRanks fleet_ranks(uint32_t n, double interval) {
+  SelState rs, re;
+  sel_ranks(rs, n, interval, true);
+  sel_ranks(re, n, interval, false);
+  FleetRanks r{FleetRowRanks{(uint32_t)rs.rank[0], (uint32_t)rs.rank[1], (uint32_t)re.rank[0], (uint32_t)re.rank[1]}, 2u};
+  while (r.np2 < n) r.np2 <<= 1;
+  return r;
+}
 
-// What a launch that also forecasts every record before it is stepped carries and brings back (k_fleet_series<D, false, false, false, true>).
-struct FleetFc {
-  double interval;
-  const uint64_t* keys;       // the caller's, one per record of the call as the caller counts them ([off[S]], or [S] for a step), or null
-  bool step = false;          // one row per series (cssm_fleet_step_forecast), not one per record
-  size_t rows = 0;            // of [d + 2][3] doubles and of 2 counts: S, or R
-  std::vector<double> out;    // the rows as the device left them; NaN where no block wrote
-  std::vector<int32_t> pit;   // ... -1 where no block wrote
-  std::vector<int> fc_rc;     // [S]: the forecast's own status of every series
-  std::string scale_msg;      // the reference's exception for the first series without the scale its observation needs
-};
-// behind the R records of such a launch: [R keys (u64)] [R data (f64)] [S observation parameters] [R flags (u32)]
-static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
-static size_t fleet_fc_bytes(const cssm_fleet* f, size_t R) { return R * 16u + (size_t)f->S * sizeof(cssm_obs_params) + ((R * 4u + 7u) & ~(size_t)7u); }
-
-// (picks: the launch also carries R sampleOne slots, uint32 each, behind the records; iv: S x d f coefficients, F at every series' t0;
-// fc: fleet_fc_bytes -- a launch carries one of the three at most)
-static int fleet_ensure(cssm_fleet* f, size_t R, bool picks = false, bool iv = false, bool fc = false) {
-  const size_t need = fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d) + (picks ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u) +
-                      (fc ? fleet_fc_bytes(f, R) : 0u);
-  if (need > f->h_stage_cap) {
-    if (f->h_stage) (void)hipHostFree(f->h_stage);
-    f->h_stage = nullptr; f->h_stage_cap = 0;
-    if (hipHostMalloc((void**)&f->h_stage, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of pinned staging", need);
-    f->h_stage_cap = need + need / 4;
-  }
-  if (need > f->stage_cap) {
-    if (f->d_stage) (void)hipFree(f->d_stage);
-    f->d_stage = nullptr; f->stage_cap = 0;
-    if (hipMalloc(&f->d_stage, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of records", need);
-    f->stage_cap = need + need / 4;
-  }
-  const size_t rr = std::max<size_t>(R, 1);
-  if (rr > f->res_cap) {
-    if (f->d_ll_t) (void)hipFree(f->d_ll_t);
-    if (f->d_ess_t) (void)hipFree(f->d_ess_t);
-    f->d_ll_t = nullptr; f->d_ess_t = nullptr; f->res_cap = 0;
-    if (hipMalloc(&f->d_ll_t, (rr + rr / 4) * 8) != hipSuccess || hipMalloc(&f->d_ess_t, (rr + rr / 4) * 4) != hipSuccess)
-      return fail(CSSM_ENOMEM, "fleet: per-observation results");
-    f->res_cap = rr + rr / 4;
-  }
+// off[k + 1] >= off[k] of a ragged layout, refused in the words every entry point uses ...
+static int fleet_off_step(const char* name, const uint64_t* off, uint32_t k) {
+  if (off[k + 1] >= off[k]) return CSSM_OK;
+  return fail(CSSM_EINVAL_ARG, "%s must be non-decreasing (%s[%u] = %llu > %s[%u] = %llu)", name, name, k, (unsigned long long)off[k], name, k + 1,
+              (unsigned long long)off[k + 1]);
+}
+// ... and a whole layout of S series
+static int fleet_off_check(const uint64_t* off, uint32_t S) {
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  for (uint32_t k = 0; k < S; ++k)
+    if (const int rc = fleet_off_step("off", off, k)) return rc;
   return CSSM_OK;
+}
+
+// The caller's arrays of a call that returns getIntervals (cssm_fleet_summary, _interpolate, _filter_intervals, _step_intervals), and
+// row `row` of them from a block's [d + 1][3] (mean, lower, upper of the d states and of eta).  Eta of the mean is formed here
+// (model/ParticleFilter.scala:420) from the row's own f coefficients.  ok == false: the row reads NaN.
+struct FleetIvOut {
+  double *state_mean, *state_lower, *state_upper, *eta_of_mean, *eta_lower, *eta_upper;
+};
+static void fleet_iv_row(const cssm_fleet* f, uint32_t k, const double* src, const double* fco, bool ok, const FleetIvOut& o, size_t row) {
+  const int d = f->d;
+  auto at = [&](int r, int q) { return ok ? src[3 * r + q] : cssm_nan(); };
+  double mean[CSSM_MAX_DIM];
+  for (int c = 0; c < d; ++c) {
+    mean[c] = at(c, 0);
+    if (o.state_mean) o.state_mean[row * d + c] = mean[c];
+    if (o.state_lower) o.state_lower[row * d + c] = at(c, 1);
+    if (o.state_upper) o.state_upper[row * d + c] = at(c, 2);
+  }
+  if (o.eta_lower) o.eta_lower[row] = at(d, 1);
+  if (o.eta_upper) o.eta_upper[row] = at(d, 2);
+  if (o.eta_of_mean) o.eta_of_mean[row] = ok ? cssm_eta_of_mean(f->models[k], fco, mean) : cssm_nan();
+}
+
+// The caller's arrays of a call that returns forecasts (cssm_fleet_forecast, _forecast_posterior, _filter_forecasts, _step_forecast),
+// and row `row` of them from a block's [d + 2][3] (mean, lower, upper of the d states, of eta and of the observation) and, where the
+// call has them, its 2 PIT counts.  ok == false: the row reads NaN and -1.
+struct FleetFcOut {
+  double *state_mean, *state_lower, *state_upper, *eta_mean, *eta_lower, *eta_upper, *obs_mean, *obs_lower, *obs_upper;
+  int32_t *obs_below, *obs_equal;
+};
+static void fleet_fc_row(int d, const double* src, const int32_t* pit, bool ok, const FleetFcOut& o, size_t row) {
+  auto at = [&](int r, int q) { return ok ? src[3 * r + q] : cssm_nan(); };
+  for (int c = 0; c < d; ++c) {
+    if (o.state_mean) o.state_mean[row * d + c] = at(c, 0);
+    if (o.state_lower) o.state_lower[row * d + c] = at(c, 1);
+    if (o.state_upper) o.state_upper[row * d + c] = at(c, 2);
+  }
+  if (o.eta_mean) o.eta_mean[row] = at(d, 0);
+  if (o.eta_lower) o.eta_lower[row] = at(d, 1);
+  if (o.eta_upper) o.eta_upper[row] = at(d, 2);
+  if (o.obs_mean) o.obs_mean[row] = at(d + 1, 0);
+  if (o.obs_lower) o.obs_lower[row] = at(d + 1, 1);
+  if (o.obs_upper) o.obs_upper[row] = at(d + 1, 2);
+  if (o.obs_below) o.obs_below[row] = ok ? pit[0] : -1;
+  if (o.obs_equal) o.obs_equal[row] = ok ? pit[1] : -1;
+}
+
+// The layout of a series launch of R records, computed once per launch (fleet_ensure): every size and pointer of the launch, and what
+// an entry point reads in the staging after the launch, derives from it.
+// Staged, one upload: [S + 1 offsets (u64)] [S control words (u32), padded to 8 bytes] [R compact records] [the rider's:
+//   path: R sampleOne slots (u32) | ival: [S][d] f coefficients, F at every series' t0 | fcst: R keys (u64), R data (f64), S observation
+//   parameters, R flags (u32) padded to 8 bytes] -- a launch carries one rider at most.
+// Written by the rider into d_rows, preset to 0xff bytes (NaN; -1 in the counts) for what no block writes:
+//   path: [S][d] last rows, then (asked for) the R + S rows of the paths | ival: `rows` of [d + 1][3] | fcst: `rows` of [d + 2][3], then
+//   `rows` of 2 PIT counts (i32).
+static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
+struct FleetStage {
+  FleetKind kind = FleetKind::plain;
+  size_t R = 0, rec_bytes = 0;
+  size_t ctl = 0, recs = 0, ride = 0, fc_y = 0, fc_op = 0, fc_flags = 0, bytes = 0;   // byte offsets into the staging, and its size
+  size_t rows = 0, out_doubles = 0, rows_bytes = 0;   // d_rows: the rows of ival / fcst and their doubles; the bytes of any rider
+};
+struct FleetStageView {   // the staging on the host or on the device; the pointers of another rider are null
+  unsigned long long* off; uint32_t* ctl; unsigned char* recs;
+  uint32_t* picks;
+  double* fco0;
+  unsigned long long* keys; double* y; cssm_obs_params* op; uint32_t* flags;
+};
+static FleetStageView fleet_view(const FleetStage& st, const FleetBuf& b) {
+  FleetStageView v{};
+  v.off = b.at<unsigned long long>(); v.ctl = b.at<uint32_t>(st.ctl); v.recs = b.at<unsigned char>(st.recs);
+  if (st.kind == FleetKind::path) v.picks = b.at<uint32_t>(st.ride);
+  if (st.kind == FleetKind::ival) v.fco0 = b.at<double>(st.ride);
+  if (st.kind == FleetKind::fcst) {
+    v.keys = b.at<unsigned long long>(st.ride); v.y = b.at<double>(st.fc_y);
+    v.op = b.at<cssm_obs_params>(st.fc_op); v.flags = b.at<uint32_t>(st.fc_flags);
+  }
+  return v;
+}
+// the f coefficients of staged record r
+static const double* fleet_rec_fco(const FleetStageView& v, int d, size_t r) {
+  return reinterpret_cast<const double*>(v.recs + r * CSSM_FLEET_REC_BYTES(d) + sizeof(FleetRecHead)) + 4 * d;
+}
+
+// What rides behind the records of a series launch -- nothing (plain), `filter`'s sampled path, getIntervals of every cloud (ival), the
+// forecast of every record before it is stepped (fcst) -- with that rider's inputs and what it brings back.  (hist is
+// cssm_fleet_interpolate's own launch: it stages chunk by chunk, FleetIpStage.)
+struct FleetRide {
+  FleetKind kind = FleetKind::plain;
+  bool step = false;                 // ival / fcst: one row per series (cssm_fleet_step_*), not T_k + 1 / T_k rows per series
+  double interval = 0.0;             // ival / fcst
+  double *path_out = nullptr, *last_out = nullptr;   // path: receive the rows; either may be null
+  const uint64_t* keys = nullptr;    // fcst: the caller's, one per record as the caller counts them ([off[S]], or [S] for a step), or null
+  FleetIvOut ivo{};                  // ival, step: the caller's arrays (the entries of a series that is inactive, has no cloud or fails are not written)
+  FleetFcOut fco{};                  // fcst, step: ...
+  int* fc_rc_out = nullptr;
+  FleetStage st;                     // the launch's layout (fleet_ensure)
+  std::vector<double> out;           // ival / fcst: the rows as the device left them; NaN where no block wrote
+  std::vector<int32_t> pit;          // fcst: ... -1 where no block wrote
+  std::vector<int> fc_rc;            // fcst, [S]: the forecast's own status of every series
+  std::string scale_msg;             // fcst: the reference's exception for the first series without the scale its observation needs
+};
+
+// lay a launch of R records with this rider out (ride.st) and make room for it: the staging, its pinned mirror, the per-observation results
+static int fleet_ensure(cssm_fleet* f, size_t R, FleetRide& ride) {
+  const size_t S = f->S, d = (size_t)f->d;
+  FleetStage& st = ride.st;
+  st = FleetStage();
+  st.kind = ride.kind; st.R = R; st.rec_bytes = CSSM_FLEET_REC_BYTES(f->d);
+  st.ctl = (S + 1u) * 8u;
+  st.recs = st.ctl + fleet_pad8(S * 4u);
+  st.ride = st.recs + R * st.rec_bytes;
+  st.bytes = st.ride;
+  if (st.kind == FleetKind::path) {
+    st.bytes += R * 4u;
+    st.rows_bytes = (S * d + (ride.path_out ? (R + S) * d : 0u)) * 8u;
+  } else if (st.kind == FleetKind::ival) {
+    st.bytes += S * d * 8u;
+    st.rows = ride.step ? S : R + S;
+    st.out_doubles = st.rows * (d + 1) * 3u;
+    st.rows_bytes = st.out_doubles * 8u;
+  } else if (st.kind == FleetKind::fcst) {
+    st.fc_y = st.ride + R * 8u; st.fc_op = st.fc_y + R * 8u; st.fc_flags = st.fc_op + S * sizeof(cssm_obs_params);
+    st.bytes = st.fc_flags + fleet_pad8(R * 4u);
+    st.rows = ride.step ? S : R;
+    st.out_doubles = st.rows * (d + 2) * 3u;
+    st.rows_bytes = st.out_doubles * 8u + st.rows * 8u;
+  }
+  if (!f->h_stage.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet: %zu bytes of pinned staging", st.bytes);
+  if (!f->d_stage.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet: %zu bytes of records", st.bytes);
+  const size_t rr = std::max<size_t>(R, 1);
+  if (!f->d_ll_t.reserve(rr * 8, true) || !f->d_ess_t.reserve(rr * 4, true)) return fail(CSSM_ENOMEM, "fleet: per-observation results");
+  return CSSM_OK;
+}
+
+// 16 N bytes of eta / obs staging per series: the scratch of every kernel that forecasts, allocated once
+static int fleet_fc_scratch(cssm_fleet* f) {
+  if (!f->d_fc_scratch.reserve((size_t)f->S * 2u * f->n * 8u, false)) return fail(CSSM_ENOMEM, "fleet forecast: 16 N bytes of staging per series");
+  return CSSM_OK;
+}
+
+// what every launch of k_fleet_series takes from the fleet
+static void fleet_series_args(const cssm_fleet* f, FleetLaunch& l) {
+  l.args.n = f->n; l.args.state = f->state.at<double>(); l.args.anc = f->anc.at<uint32_t>();
+  l.args.ser = f->ser.at<FleetSeries>(); l.args.par = f->par.at<FleetPar>();
+  l.args.logtab = f->logtab.at<double>(); l.args.mk = f->base.mk;
+  l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
 }
 
 // k_fleet_series of the fleet's latent dimension (one object per dimension: cssm_fleet_d.hip)
@@ -363,224 +505,138 @@ static int fleet_series_launch(int d, const FleetLaunch& l) {
   return CSSM_OK;
 }
 
-// upload the staged launch, run it, bring the series' scalars (and, asked for, the per-observation results) back; synchronises.
-// want_path: the staged launch carries its picks and runs k_fleet_series<D, true>; path_out (may be null) / last_out receive the rows.
-// iv: the staged launch carries the f coefficients of every series' t0 behind its records and runs k_fleet_series<D, false, false, true>.
-// fc: the staged launch carries fleet_fc_bytes behind its records and runs k_fleet_series<D, false, false, false, true>.
-static int fleet_launch(cssm_fleet* f, size_t R, double* ll_t, int32_t* ess_t, bool want_path = false, double* path_out = nullptr, double* last_out = nullptr,
-                        FleetIv* iv = nullptr, FleetFc* fc = nullptr) {
+// upload the staged launch (fleet_ensure laid it out, the caller filled it), run it with its rider, bring the series' scalars, the
+// rider's rows and (asked for) the per-observation results back; synchronises.
+static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* ess_t) {
   int rc = fleet_upload_par(f);
   if (rc) return rc;
-  const size_t head = fleet_stage_head(f), recs = R * CSSM_FLEET_REC_BYTES(f->d),
-               bytes = head + recs + (want_path ? R * 4u : 0u) + (iv ? (size_t)f->S * f->d * 8u : 0u) + (fc ? fleet_fc_bytes(f, R) : 0u);
-  const size_t n_fco = fc ? fc->rows * (size_t)(f->d + 2) * 3u : 0u, n_fcr = n_fco * 8u + (fc ? fc->rows * 8u : 0u);   // (bytes: doubles, then counts)
-  if (n_fcr > f->fcr_cap) {
-    if (f->d_fcr) (void)hipFree(f->d_fcr);
-    f->d_fcr = nullptr; f->fcr_cap = 0;
-    if (hipMalloc(&f->d_fcr, n_fcr + n_fcr / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of one-step-ahead forecasts", n_fcr);
-    f->fcr_cap = n_fcr + n_fcr / 4;
-  }
-  if (fc && !f->d_fc_stage && hipMalloc(&f->d_fc_stage, (size_t)f->S * 2u * f->n * 8u) != hipSuccess) {
-    f->d_fc_stage = nullptr;
-    return fail(CSSM_ENOMEM, "fleet forecast: 16 N bytes of staging per series");
-  }
-  const size_t n_iv = iv ? iv->rows * (size_t)(f->d + 1) * 3u : 0u;
-  if (n_iv > f->iv_cap) {
-    if (f->d_iv) (void)hipFree(f->d_iv);
-    f->d_iv = nullptr; f->iv_cap = 0;
-    if (hipMalloc(&f->d_iv, (n_iv + n_iv / 4) * 8) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of filtered intervals", n_iv * 8);
-    f->iv_cap = n_iv + n_iv / 4;
-  }
-  const size_t n_last = (size_t)f->S * f->d, n_rows = n_last + (path_out ? (R + f->S) * (size_t)f->d : 0u);
-  if (want_path && n_rows > f->path_cap) {
-    if (f->d_path) (void)hipFree(f->d_path);
-    f->d_path = nullptr; f->path_cap = 0;
-    if (hipMalloc(&f->d_path, (n_rows + n_rows / 4) * 8) != hipSuccess) return fail(CSSM_ENOMEM, "fleet: %zu bytes of sampled paths", n_rows * 8);
-    f->path_cap = n_rows + n_rows / 4;
-  }
-  HIP_TRY(hipEventRecord(f->ev[0], f->stream));
-  HIP_TRY(hipMemcpyAsync(f->d_stage, f->h_stage, bytes, hipMemcpyHostToDevice, f->stream));
+  const FleetStage& st = ride.st;
+  const size_t R = st.R, n_last = (size_t)f->S * f->d;
+  const bool path = st.kind == FleetKind::path, ival = st.kind == FleetKind::ival, fcst = st.kind == FleetKind::fcst;
+  if (!f->d_rows.reserve(st.rows_bytes, true))
+    return fail(CSSM_ENOMEM, "fleet: %zu bytes of %s", st.rows_bytes, path ? "sampled paths" : ival ? "filtered intervals" : "one-step-ahead forecasts");
+  if (fcst && (rc = fleet_fc_scratch(f))) return rc;
+  HIP_TRY(hipEventRecord(f->ev[EV_CALL_BEGIN], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->d_stage.p, f->h_stage.p, st.bytes, hipMemcpyHostToDevice, f->stream));
   if (R) {   // records a failed series never reaches read as NaN / -1
-    HIP_TRY(hipMemsetAsync(f->d_ll_t, 0xff, R * 8, f->stream));
-    HIP_TRY(hipMemsetAsync(f->d_ess_t, 0xff, R * 4, f->stream));
+    HIP_TRY(hipMemsetAsync(f->d_ll_t.p, 0xff, R * 8, f->stream));
+    HIP_TRY(hipMemsetAsync(f->d_ess_t.p, 0xff, R * 4, f->stream));
   }
-  if (want_path) {   // ... and the rows it never records as NaN
-    HIP_TRY(hipMemsetAsync(f->d_path, 0xff, n_rows * 8, f->stream));
-    HIP_TRY(hipEventRecord(f->ev[6], f->stream));
+  if (st.rows_bytes) HIP_TRY(hipMemsetAsync(f->d_rows.p, 0xff, st.rows_bytes, f->stream));   // ... and the rows it never records, summarises or forecasts
+  if (path) HIP_TRY(hipEventRecord(f->ev[EV_PATH_UPLOADED], f->stream));
+  const FleetStageView dv = fleet_view(st, f->d_stage);
+  double* rows = f->d_rows.at<double>();
+  FleetLaunch l{};
+  fleet_series_args(f, l);
+  l.args.off = dv.off; l.args.ctl = dv.ctl; l.args.recs = dv.recs;
+  l.args.ll_t = f->d_ll_t.at<double>(); l.args.ess_t = f->d_ess_t.at<int32_t>();
+  l.n_series = f->S; l.kind = st.kind;
+  if (path) {
+    l.args.picks = dv.picks; l.args.last = rows;
+    if (ride.path_out) l.args.path = rows + n_last;
   }
-  if (iv) HIP_TRY(hipMemsetAsync(f->d_iv, 0xff, n_iv * 8, f->stream));   // ... and the rows it never summarises
-  if (n_fcr) HIP_TRY(hipMemsetAsync(f->d_fcr, 0xff, n_fcr, f->stream));  // ... or never forecasts (NaN; -1 in the counts)
-  FleetLaunch l;
-  l.args.n = f->n; l.args.state = f->state; l.args.anc = f->anc; l.args.ser = f->ser; l.args.par = f->par;
-  l.args.off = reinterpret_cast<const unsigned long long*>(f->d_stage);
-  l.args.ctl = reinterpret_cast<const uint32_t*>(f->d_stage + ((size_t)f->S + 1u) * 8u);
-  l.args.recs = f->d_stage + head;
-  l.args.ll_t = f->d_ll_t; l.args.ess_t = f->d_ess_t; l.args.logtab = f->logtab; l.args.mk = f->base.mk;
-  l.args.picks = want_path ? reinterpret_cast<const uint32_t*>(f->d_stage + head + recs) : nullptr;
-  l.args.path = (want_path && path_out) ? f->d_path + n_last : nullptr;
-  l.args.last = want_path ? f->d_path : nullptr;
-  l.args.hist = nullptr; l.args.hanc = nullptr; l.args.hser = nullptr; l.args.k0 = 0u;
-  l.args.iv_fco0 = nullptr; l.args.iv_out = nullptr; l.args.iv_rows = 0u; l.args.iv_np2 = 0u; l.args.iv_rk = FleetRowRanks{0u, 0u, 0u, 0u};
-  l.args.fc = FleetOneStep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  l.n_series = f->S; l.path = want_path; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
-  if (fc) {
-    SelState rs, re;   // the ranks of a state row and of the eta / obs rows, as cssm_fleet_forecast takes them
-    sel_ranks(rs, f->n, fc->interval, true);
-    sel_ranks(re, f->n, fc->interval, false);
-    uint32_t np2 = 2u;
-    while (np2 < f->n) np2 <<= 1;
-    const unsigned char* x = f->d_stage + head + recs;
-    l.args.fc.keys = reinterpret_cast<const unsigned long long*>(x);
-    l.args.fc.y = reinterpret_cast<const double*>(x + R * 8u);
-    l.args.fc.op = reinterpret_cast<const cssm_obs_params*>(x + R * 16u);
-    l.args.fc.flags = reinterpret_cast<const uint32_t*>(x + R * 16u + (size_t)f->S * sizeof(cssm_obs_params));
-    l.args.fc.stage = f->d_fc_stage;
-    l.args.fc.out = reinterpret_cast<double*>(f->d_fcr);
-    l.args.fc.pit = reinterpret_cast<int32_t*>(f->d_fcr + n_fco * 8u);
-    l.args.iv_rows = fc->step ? 1u : 0u; l.args.iv_np2 = np2;
-    l.args.iv_rk = FleetRowRanks{(uint32_t)rs.rank[0], (uint32_t)rs.rank[1], (uint32_t)re.rank[0], (uint32_t)re.rank[1]};
-    l.fcst = true; l.lds = (size_t)np2 * 8u + (size_t)f->n * 4u;   // the keys of a row's sort take the weights' place
-    fc->out.resize(n_fco); fc->pit.resize(fc->rows * 2u);
+  if (ival || fcst) {
+    const FleetRanks r = fleet_ranks(f->n, ride.interval);
+    l.args.iv_rows = ride.step ? 1u : 0u; l.args.iv_np2 = r.np2; l.args.iv_rk = r.rk;
+    l.lds = (size_t)r.np2 * 8u + (size_t)f->n * 4u;   // the keys of a row's sort take the weights' place
+    ride.out.resize(st.out_doubles);
   }
-  if (iv) {
-    SelState rs, re;   // the ranks of a state row and of the eta row, as cssm_fleet_summary takes them
-    sel_ranks(rs, f->n, iv->interval, true);
-    sel_ranks(re, f->n, iv->interval, false);
-    uint32_t np2 = 2u;
-    while (np2 < f->n) np2 <<= 1;
-    l.args.iv_fco0 = reinterpret_cast<const double*>(f->d_stage + head + recs);
-    l.args.iv_out = f->d_iv; l.args.iv_rows = iv->step ? 1u : 0u; l.args.iv_np2 = np2;
-    l.args.iv_rk = FleetRowRanks{(uint32_t)rs.rank[0], (uint32_t)rs.rank[1], (uint32_t)re.rank[0], (uint32_t)re.rank[1]};
-    l.ival = true; l.lds = (size_t)np2 * 8u + (size_t)f->n * 4u;   // the keys of a row's sort take the weights' place
-    iv->out.resize(n_iv);
+  if (ival) { l.args.iv_fco0 = dv.fco0; l.args.iv_out = rows; }
+  if (fcst) {
+    l.args.fc.keys = dv.keys; l.args.fc.y = dv.y; l.args.fc.op = dv.op; l.args.fc.flags = dv.flags;
+    l.args.fc.stage = f->d_fc_scratch.at<double>();
+    l.args.fc.out = rows; l.args.fc.pit = f->d_rows.at<int32_t>(st.out_doubles * 8u);
+    ride.pit.resize(st.rows * 2u);
   }
   rc = fleet_series_launch(f->d, l);
   if (rc) return rc;
-  if (want_path) HIP_TRY(hipEventRecord(f->ev[7], f->stream));
-  HIP_TRY(hipMemcpyAsync(f->h_ser.data(), f->ser, (size_t)f->S * sizeof(FleetSeries), hipMemcpyDeviceToHost, f->stream));
-  if (want_path && path_out) HIP_TRY(hipMemcpyAsync(path_out, f->d_path + n_last, (n_rows - n_last) * 8, hipMemcpyDeviceToHost, f->stream));
-  if (want_path && last_out) HIP_TRY(hipMemcpyAsync(last_out, f->d_path, n_last * 8, hipMemcpyDeviceToHost, f->stream));
-  if (R && ll_t) HIP_TRY(hipMemcpyAsync(ll_t, f->d_ll_t, R * 8, hipMemcpyDeviceToHost, f->stream));
-  if (R && ess_t) HIP_TRY(hipMemcpyAsync(ess_t, f->d_ess_t, R * 4, hipMemcpyDeviceToHost, f->stream));
-  if (n_iv) HIP_TRY(hipMemcpyAsync(iv->out.data(), f->d_iv, n_iv * 8, hipMemcpyDeviceToHost, f->stream));
-  if (n_fcr) {
-    HIP_TRY(hipMemcpyAsync(fc->out.data(), f->d_fcr, n_fco * 8u, hipMemcpyDeviceToHost, f->stream));
-    HIP_TRY(hipMemcpyAsync(fc->pit.data(), f->d_fcr + n_fco * 8u, fc->rows * 8u, hipMemcpyDeviceToHost, f->stream));
-  }
-  HIP_TRY(hipEventRecord(f->ev[1], f->stream));
+  if (path) HIP_TRY(hipEventRecord(f->ev[EV_PATH_KERNEL_END], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->h_ser.data(), f->ser.p, (size_t)f->S * sizeof(FleetSeries), hipMemcpyDeviceToHost, f->stream));
+  if (path && ride.path_out) HIP_TRY(hipMemcpyAsync(ride.path_out, rows + n_last, st.rows_bytes - n_last * 8, hipMemcpyDeviceToHost, f->stream));
+  if (path && ride.last_out) HIP_TRY(hipMemcpyAsync(ride.last_out, rows, n_last * 8, hipMemcpyDeviceToHost, f->stream));
+  if (R && ll_t) HIP_TRY(hipMemcpyAsync(ll_t, f->d_ll_t.p, R * 8, hipMemcpyDeviceToHost, f->stream));
+  if (R && ess_t) HIP_TRY(hipMemcpyAsync(ess_t, f->d_ess_t.p, R * 4, hipMemcpyDeviceToHost, f->stream));
+  if (st.out_doubles) HIP_TRY(hipMemcpyAsync(ride.out.data(), rows, st.out_doubles * 8u, hipMemcpyDeviceToHost, f->stream));
+  if (fcst && st.rows) HIP_TRY(hipMemcpyAsync(ride.pit.data(), l.args.fc.pit, st.rows * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipEventRecord(f->ev[EV_CALL_END], f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
-  if (hipEventElapsedTime(&f->ms_call, f->ev[0], f->ev[1]) != hipSuccess) f->ms_call = -1.f;
-  if (want_path) {
-    if (hipEventElapsedTime(&f->ms_upload, f->ev[0], f->ev[6]) != hipSuccess) f->ms_upload = -1.f;
-    if (hipEventElapsedTime(&f->ms_kernel, f->ev[6], f->ev[7]) != hipSuccess) f->ms_kernel = -1.f;
+  if (hipEventElapsedTime(&f->ms_call, f->ev[EV_CALL_BEGIN], f->ev[EV_CALL_END]) != hipSuccess) f->ms_call = -1.f;
+  if (path) {
+    if (hipEventElapsedTime(&f->ms_upload, f->ev[EV_CALL_BEGIN], f->ev[EV_PATH_UPLOADED]) != hipSuccess) f->ms_upload = -1.f;
+    if (hipEventElapsedTime(&f->ms_kernel, f->ev[EV_PATH_UPLOADED], f->ev[EV_PATH_KERNEL_END]) != hipSuccess) f->ms_kernel = -1.f;
   }
   return CSSM_OK;
 }
 
-// the staged arrays of a FleetFc launch of R records (fleet_fc_bytes) in the pinned staging
-struct FleetFcStage {
-  unsigned long long* keys; double* y; cssm_obs_params* op; uint32_t* flags;
-};
-static FleetFcStage fleet_fc_stage(const cssm_fleet* f, size_t R) {
-  unsigned char* x = f->h_stage + fleet_stage_head(f) + R * CSSM_FLEET_REC_BYTES(f->d);
-  return FleetFcStage{reinterpret_cast<unsigned long long*>(x), reinterpret_cast<double*>(x + R * 8u), reinterpret_cast<cssm_obs_params*>(x + R * 16u),
-                      reinterpret_cast<uint32_t*>(x + R * 16u + (size_t)f->S * sizeof(cssm_obs_params))};
-}
-// the observation parameters of series k's draws and the forecast's own status of the series (runs: the call has a record for it)
-static void fleet_fc_series(const cssm_fleet* f, uint32_t k, bool runs, FleetFc* fc, cssm_obs_params* op) {
-  memset(op, 0, sizeof *op);
-  fc->fc_rc[k] = CSSM_OK;
-  if (!runs) return;
-  if (cssm_obs_params_or_fail(f->base.obs_kind, f->obs_has_scale[k], f->obs_scale[k], f->base.obs_df, op)) {
-    if (fc->scale_msg.empty()) fc->scale_msg = "series " + std::to_string(k) + ": " + cssm_last_error();
-    fc->fc_rc[k] = CSSM_EINVAL_ARG;
+// fcst: the forecast's own status and the observation parameters of every series (runs(k): the launch has a record of series k).  The
+// reference's exception is one message: formed in order.
+template <class Runs>
+static void fleet_fc_series(const cssm_fleet* f, FleetRide& ride, const FleetStageView& h, Runs runs) {
+  ride.fc_rc.assign(f->S, CSSM_OK);
+  for (uint32_t k = 0; k < f->S; ++k) {
+    memset(&h.op[k], 0, sizeof(cssm_obs_params));
+    if (runs(k) && cssm_obs_params_or_fail(f->base.obs_kind, f->obs_has_scale[k], f->obs_scale[k], f->base.obs_df, &h.op[k])) {
+      if (ride.scale_msg.empty()) ride.scale_msg = "series " + std::to_string(k) + ": " + cssm_last_error();
+      ride.fc_rc[k] = CSSM_EINVAL_ARG;
+    }
   }
+  if (ride.st.R & 1u) h.flags[ride.st.R] = 0u;   // (the padding travels too)
 }
-// One row of a FleetFc launch into the caller's arrays; a row without a forecast (ok == false) reads NaN and -1
-struct FleetFcOut {
-  double *state_mean, *state_lower, *state_upper, *eta_mean, *eta_lower, *eta_upper, *obs_mean, *obs_lower, *obs_upper;
-  int32_t *obs_below, *obs_equal;
-};
-static void fleet_fc_row(const cssm_fleet* f, const FleetFc& fc, size_t src_row, bool ok, const FleetFcOut& o, size_t row) {
-  const int d = f->d;
-  const double* v = fc.out.data() + src_row * (size_t)(d + 2) * 3u;
-  auto at = [&](int r, int q) { return ok ? v[3 * r + q] : cssm_nan(); };
-  for (int c = 0; c < d; ++c) {
-    if (o.state_mean) o.state_mean[row * d + c] = at(c, 0);
-    if (o.state_lower) o.state_lower[row * d + c] = at(c, 1);
-    if (o.state_upper) o.state_upper[row * d + c] = at(c, 2);
-  }
-  if (o.eta_mean) o.eta_mean[row] = at(d, 0);
-  if (o.eta_lower) o.eta_lower[row] = at(d, 1);
-  if (o.eta_upper) o.eta_upper[row] = at(d, 2);
-  if (o.obs_mean) o.obs_mean[row] = at(d + 1, 0);
-  if (o.obs_lower) o.obs_lower[row] = at(d + 1, 1);
-  if (o.obs_upper) o.obs_upper[row] = at(d + 1, 2);
-  if (o.obs_below) o.obs_below[row] = ok ? fc.pit[2 * src_row] : -1;
-  if (o.obs_equal) o.obs_equal[row] = ok ? fc.pit[2 * src_row + 1] : -1;
+// fcst: the forecast of staged record r -- series k's observation `idx`, the caller's `slot` -- before it is stepped from t_prev to t:
+// cssm_fleet_forecast's own refusals of a time, the key, the datum as given
+static void fleet_fc_record(const cssm_fleet* f, const FleetRide& ride, const FleetStageView& h, uint32_t k, size_t r, size_t slot, uint32_t idx,
+                            double t_prev, double t, double y, int has) {
+  const bool on = ride.fc_rc[k] == CSSM_OK && std::isfinite(t) && t >= t_prev;
+  h.flags[r] = on ? (CSSM_FLEET_FC_ON | (has ? CSSM_FLEET_FC_HAS : 0u)) : 0u;
+  h.keys[r] = ride.keys ? ride.keys[slot] : cssm_pf_run_key(f->models[k].seed, (1ull << 63) | (uint64_t)idx);
+  h.y[r] = y;
 }
 
-// llFilter / filter of every series: the records of all of them built (threaded above 8192), ONE upload, ONE launch, ONE read-back.
-// want_path: `filter` -- the sampleOne slots travel behind the records, path_out (may be null) and last_out (may be null) are written.
+// llFilter / filter of every series: the records of all of them built (threaded above 8192), ONE upload, ONE launch with the call's
+// rider, ONE read-back.
 static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double* ll_out, double* ll_t,
-                            int32_t* ess_t, bool want_path, double* path_out, double* last_out, int* rc_out, FleetIv* iv = nullptr, FleetFc* fc = nullptr) {
+                            int32_t* ess_t, int* rc_out, FleetRide& ride) {
   const uint32_t S = f->S;
-  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
-  for (uint32_t k = 0; k < S; ++k)
-    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
-                                         k + 1, (unsigned long long)off[k + 1]);
+  int rc = fleet_off_check(off, S);
+  if (rc) return rc;
   const size_t R = (size_t)off[S];
   if (R && (!t || !y)) return fail(CSSM_EINVAL_ARG, "null data");
   HIP_TRY(hipSetDevice(f->device));
   const auto tb0 = std::chrono::steady_clock::now();
-  int rc = fleet_ensure(f, R, want_path, iv != nullptr, fc != nullptr);
+  ride.step = false;
+  rc = fleet_ensure(f, R, ride);
   if (rc) return rc;
-  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
-  uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
-  unsigned char* h_recs = f->h_stage + fleet_stage_head(f);
-  const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
-  FleetFcStage fs{nullptr, nullptr, nullptr, nullptr};
-  if (fc) {                                                              // (the reference's exception is one message: formed in order)
-    fs = fleet_fc_stage(f, R);
-    fc->fc_rc.assign(S, CSSM_OK);
-    for (uint32_t k = 0; k < S; ++k) fleet_fc_series(f, k, off[k + 1] > off[k], fc, &fs.op[k]);
-    if (R & 1u) fs.flags[R] = 0u;                                        // (the padding travels too)
-  }
-  uint32_t* h_picks = want_path ? reinterpret_cast<uint32_t*>(h_recs + R * RB) : nullptr;
-  double* h_fco0 = iv ? reinterpret_cast<double*>(h_recs + R * RB) : nullptr;   // (a launch carries picks or these, never both)
-  for (uint32_t k = 0; k <= S; ++k) h_off[k] = off[k];
+  const FleetStageView h = fleet_view(ride.st, f->h_stage);
+  const size_t RB = ride.st.rec_bytes;
+  const bool fcst = ride.kind == FleetKind::fcst;
+  if (fcst) fleet_fc_series(f, ride, h, [&](uint32_t k) { return off[k + 1] > off[k]; });
+  for (uint32_t k = 0; k <= S; ++k) h.off[k] = off[k];
   std::vector<double> t0(S, 0.0);
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
-      h_ctl[k] = (b > a) ? CSSM_FLEET_CTL_INIT : 0u;
-      if (h_fco0) for (int c = 0; c < f->d; ++c) h_fco0[k * f->d + c] = 0.0;
+      h.ctl[k] = (b > a) ? CSSM_FLEET_CTL_INIT : 0u;
+      if (h.fco0) for (int c = 0; c < f->d; ++c) h.fco0[k * f->d + c] = 0.0;
       if (b == a) continue;
       double m = t[a];
       for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;      // data.minBy(_.t).t
       t0[k] = m;
-      if (h_fco0) {                                                      // F(t0): t0 need not be the first record's time
+      if (h.fco0) {                                                      // F(t0): t0 need not be the first record's time
         StepRec r0;
         cssm_build_rec(&f->models[k], m, m, 0.0, 0, 0u, &r0);
-        for (int c = 0; c < f->d; ++c) h_fco0[k * f->d + c] = r0.fco[c];
+        for (int c = 0; c < f->d; ++c) h.fco0[k * f->d + c] = r0.fco[c];
       }
       double tp = m;
       for (size_t s = a; s < b; ++s) {
-        fleet_pack_rec(f->models[k], tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), h_recs + s * RB, h_picks ? h_picks + s : nullptr);
-        if (fc) {   // the forecast of record s: cssm_fleet_forecast's own refusals of a time, the key, the datum as given
-          const bool on = fc->fc_rc[k] == CSSM_OK && std::isfinite(t[s]) && t[s] >= tp;
-          fs.flags[s] = on ? (CSSM_FLEET_FC_ON | ((has_obs ? has_obs[s] : 1) ? CSSM_FLEET_FC_HAS : 0u)) : 0u;
-          fs.keys[s] = fc->keys ? fc->keys[s] : cssm_pf_run_key(f->models[k].seed, (1ull << 63) | (uint64_t)(s - a));
-          fs.y[s] = y[s];
-        }
+        const int has = has_obs ? (int)has_obs[s] : 1;
+        fleet_pack_rec(f->models[k], tp, t[s], y[s], has, (uint32_t)(s - a), h.recs + s * RB, h.picks ? h.picks + s : nullptr);
+        if (fcst) fleet_fc_record(f, ride, h, (uint32_t)k, s, s, (uint32_t)(s - a), tp, t[s], y[s], has);
         tp = t[s];
       }
     }
   });
-  if (want_path) f->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-  if (iv) { iv->step = false; iv->rows = R + S; }
-  if (fc) { fc->step = false; fc->rows = R; }
-  rc = fleet_launch(f, R, ll_t, ess_t, want_path, path_out, last_out, iv, fc);
+  if (ride.kind == FleetKind::path) f->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
+  rc = fleet_launch(f, ride, ll_t, ess_t);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
     const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
@@ -598,11 +654,13 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
 extern "C" int cssm_fleet_ll_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
                                     double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out) {
   if (!f || !off || !ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
-  return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, false, nullptr, nullptr, rc_out);
+  FleetRide ride;
+  return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, rc_out, ride);
 }
 
 // filter (model/ParticleFilter.scala:152-158) of every series: cssm_fleet_ll_filter, and one particle of the initial cloud and of the
-// cloud after every record (Resampling.sampleOne).  What needs no fleet is refused first, so that it is refused on any host.
+// cloud after every record (Resampling.sampleOne): the sampleOne slots travel behind the records.  What needs no fleet is refused first,
+// so that it is refused on any host.
 extern "C" int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double* ll_out,
                                  double* ll_t, int32_t* ess_t, double* path_out, double* last_out, int* rc_out) {
   if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
@@ -612,26 +670,9 @@ extern "C" int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const doubl
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
   if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
-  return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, true, path_out, last_out, rc_out);
-}
-
-// One row of a FleetIv launch into the caller's arrays: the d state rows and the eta row as the block left them, eta of the mean formed
-// here as cssm_fleet_summary forms it (:420) from the row's own f coefficients.
-struct FleetIvOut {
-  double *state_mean, *state_lower, *state_upper, *eta_of_mean, *eta_lower, *eta_upper;
-};
-static void fleet_iv_row(const cssm_fleet* f, uint32_t k, const double* src, const double* fco, const FleetIvOut& o, size_t row) {
-  const int d = f->d;
-  double mean[CSSM_MAX_DIM];
-  for (int c = 0; c < d; ++c) {
-    mean[c] = src[c * 3];
-    if (o.state_mean) o.state_mean[row * d + c] = src[c * 3];
-    if (o.state_lower) o.state_lower[row * d + c] = src[c * 3 + 1];
-    if (o.state_upper) o.state_upper[row * d + c] = src[c * 3 + 2];
-  }
-  if (o.eta_lower) o.eta_lower[row] = src[d * 3 + 1];
-  if (o.eta_upper) o.eta_upper[row] = src[d * 3 + 2];
-  if (o.eta_of_mean) o.eta_of_mean[row] = cssm_eta_of_mean(f->models[k], fco, mean);
+  FleetRide ride;
+  ride.kind = FleetKind::path; ride.path_out = path_out; ride.last_out = last_out;
+  return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, rc_out, ride);
 }
 
 // examples/Filtering.scala:24-31 of every series: cssm_fleet_ll_filter, and getIntervals (model/ParticleFilter.scala:415-424) of the initial
@@ -646,28 +687,25 @@ extern "C" int cssm_fleet_filter_intervals(cssm_fleet* f, const uint64_t* off, c
   if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
-  FleetIv iv;
-  iv.interval = interval;
-  int rc = fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, false, nullptr, nullptr, rc_out, &iv);
+  FleetRide ride;
+  ride.kind = FleetKind::ival; ride.interval = interval;
+  int rc = fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, rc_out, ride);
   if (rc) return rc;
   const uint32_t S = f->S;
   const int d = f->d;
-  const size_t R = (size_t)off[S], RB = CSSM_FLEET_REC_BYTES(d), rowsz = (size_t)(d + 1) * 3u;
+  const size_t R = ride.st.R, rowsz = (size_t)(d + 1) * 3u;
   const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
   for (double* p : {state_mean, state_lower, state_upper}) if (p) std::fill(p, p + (R + S) * (size_t)d, cssm_nan());
   for (double* p : {eta_of_mean, eta_lower, eta_upper}) if (p) std::fill(p, p + (R + S), cssm_nan());
-  const unsigned char* h_recs = f->h_stage + fleet_stage_head(f);   // (the staged launch is still there: the records' f coefficients)
-  const double* h_fco0 = reinterpret_cast<const double*>(h_recs + R * RB);
+  const FleetStageView h = fleet_view(ride.st, f->h_stage);   // (the staged launch is still there: the f coefficients of every row)
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
       if (b == a) continue;                                         // no records: NaN in its single row
       const FleetSeries& s = f->h_ser[k];
       const size_t nrows = s.err ? (size_t)s.fail_rec + 1u : b - a + 1u;   // a failure at observation s keeps rows 0 .. s
-      for (size_t i = 0; i < nrows; ++i) {
-        const double* fco = i ? reinterpret_cast<const double*>(h_recs + (a + i - 1) * RB + sizeof(FleetRecHead)) + 4 * d : h_fco0 + k * d;
-        fleet_iv_row(f, (uint32_t)k, iv.out.data() + (a + k + i) * rowsz, fco, o, a + k + i);
-      }
+      for (size_t i = 0; i < nrows; ++i)
+        fleet_iv_row(f, (uint32_t)k, ride.out.data() + (a + k + i) * rowsz, i ? fleet_rec_fco(h, d, a + i - 1) : h.fco0 + k * d, true, o, a + k + i);
     }
   });
   return CSSM_OK;
@@ -687,24 +725,25 @@ extern "C" int cssm_fleet_filter_forecasts(cssm_fleet* f, const uint64_t* off, c
   if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
-  FleetFc fc;
-  fc.interval = interval; fc.keys = keys;
-  int rc = fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, false, nullptr, nullptr, rc_out, nullptr, &fc);
+  FleetRide ride;
+  ride.kind = FleetKind::fcst; ride.interval = interval; ride.keys = keys;
+  int rc = fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, rc_out, ride);
   if (rc) return rc;
   const uint32_t S = f->S;
-  const size_t R = (size_t)off[S];
+  const size_t rowsz = (size_t)(f->d + 2) * 3u;
   const FleetFcOut o{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal};
-  const FleetFcStage fs = fleet_fc_stage(f, R);                         // (the staged launch is still there: the records' flags)
-  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+  const FleetStageView h = fleet_view(ride.st, f->h_stage);   // (the staged launch is still there: the records' flags)
+  fleet_parallel(S, ride.st.R, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
-      fc_rc_out[k] = fc.fc_rc[k];
+      fc_rc_out[k] = ride.fc_rc[k];
       const FleetSeries& s = f->h_ser[k];
       const size_t nrows = (b > a && s.err) ? (size_t)s.fail_rec + 1u : b - a;   // a failure at observation s keeps rows 0 .. s
-      for (size_t i = 0; i < b - a; ++i) fleet_fc_row(f, fc, a + i, i < nrows && (fs.flags[a + i] & CSSM_FLEET_FC_ON), o, a + i);
+      for (size_t r = a; r < b; ++r)
+        fleet_fc_row(f->d, ride.out.data() + r * rowsz, ride.pit.data() + 2 * r, r - a < nrows && (h.flags[r] & CSSM_FLEET_FC_ON), o, r);
     }
   });
-  if (!fc.scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", fc.scale_msg.c_str());   // (the call succeeds; the message names the first such series)
+  if (!ride.scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", ride.scale_msg.c_str());   // (the call succeeds; the message names the first such series)
   return CSSM_OK;
 }
 
@@ -731,8 +770,7 @@ extern "C" int cssm_fleet_pmmh_run(cssm_fleet* f, const cssm_model_desc* desc, c
   const uint32_t S = f->S;
   const int d = f->d;
   for (uint32_t k = 0; k < S; ++k) {
-    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
-                                         k + 1, (unsigned long long)off[k + 1]);
+    if ((rc = fleet_off_step("off", off, k))) return rc;
     if (off[k + 1] == off[k]) return fail(CSSM_EINVAL_ARG, "chain %u has an empty slice of the data (the reference's minBy throws on an empty Vector)", k);
   }
   {   // the structure must be the fleet's: said here, once, not per series of the first iteration
@@ -784,70 +822,54 @@ extern "C" int cssm_fleet_pmmh_last_split(cssm_fleet* f, double* ms6) {
 extern "C" int cssm_fleet_init(cssm_fleet* f, const double* t0) {
   if (!f || !t0) return fail(CSSM_EINVAL_ARG, "null argument");
   HIP_TRY(hipSetDevice(f->device));
-  int rc = fleet_ensure(f, 0);
+  FleetRide ride;
+  int rc = fleet_ensure(f, 0, ride);
   if (rc) return rc;
   const uint32_t S = f->S;
-  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
-  uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
-  for (uint32_t k = 0; k <= S; ++k) h_off[k] = 0;
-  for (uint32_t k = 0; k < S; ++k) h_ctl[k] = CSSM_FLEET_CTL_INIT;
-  rc = fleet_launch(f, 0, nullptr, nullptr);
+  const FleetStageView h = fleet_view(ride.st, f->h_stage);
+  for (uint32_t k = 0; k <= S; ++k) h.off[k] = 0;
+  for (uint32_t k = 0; k < S; ++k) h.ctl[k] = CSSM_FLEET_CTL_INIT;
+  rc = fleet_launch(f, ride, nullptr, nullptr);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) { f->live[k] = 1; f->t[k] = t0[k]; f->step[k] = 0u; }
   return CSSM_OK;
 }
 
-// stepFilter of the active series; iv (cssm_fleet_step_intervals): the same launch also writes getIntervals of every cloud it moved
+// stepFilter of the active series, one record each, with the call's rider: ival (cssm_fleet_step_intervals) -- the same launch also
+// writes getIntervals of every cloud it moved; fcst (cssm_fleet_step_forecast) -- and forecasts every record before it is stepped
 static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
-                          double* ll_out, int32_t* ess_out, int* rc_out, FleetIv* iv, const FleetIvOut* ivo, FleetFc* fc = nullptr,
-                          const FleetFcOut* fco = nullptr, int* fc_rc_out = nullptr) {
+                          double* ll_out, int32_t* ess_out, int* rc_out, FleetRide& ride) {
   const uint32_t S = f->S;
+  const int d = f->d;
   bool any_live = false;
   for (uint32_t k = 0; k < S; ++k) any_live = any_live || f->live[k];
   if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
   HIP_TRY(hipSetDevice(f->device));
-  int rc = fleet_ensure(f, S, false, iv != nullptr, fc != nullptr);
-  if (rc) return rc;
-  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_stage);
-  uint32_t* h_ctl = reinterpret_cast<uint32_t*>(f->h_stage + ((size_t)S + 1u) * 8u);
-  unsigned char* h_recs = f->h_stage + fleet_stage_head(f);
-  const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
+  auto runs = [&](uint32_t k) { return (!active || active[k]) && f->live[k]; };
   size_t R = 0;
-  for (uint32_t k = 0; k < S; ++k) {
-    h_off[k] = R; h_ctl[k] = 0u;
-    if ((!active || active[k]) && f->live[k]) ++R;
-  }
-  h_off[S] = R;
+  for (uint32_t k = 0; k < S; ++k) R += runs(k) ? 1u : 0u;
+  ride.step = true;
+  int rc = fleet_ensure(f, R, ride);
+  if (rc) return rc;
+  const FleetStageView h = fleet_view(ride.st, f->h_stage);
+  const bool ival = ride.kind == FleetKind::ival, fcst = ride.kind == FleetKind::fcst;
+  h.off[0] = 0;
+  for (uint32_t k = 0; k < S; ++k) { h.ctl[k] = 0u; h.off[k + 1] = h.off[k] + (runs(k) ? 1u : 0u); }
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k)
-      if (h_off[k + 1] > h_off[k])
-        fleet_pack_rec(f->models[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1, f->step[k], h_recs + (size_t)h_off[k] * RB);
+      if (h.off[k + 1] > h.off[k])
+        fleet_pack_rec(f->models[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1, f->step[k], h.recs + (size_t)h.off[k] * ride.st.rec_bytes);
   });
-  FleetFcStage fs{nullptr, nullptr, nullptr, nullptr};
-  if (fc) {   // the forecast of every active series' record: cssm_fleet_forecast's own refusals of a time, the key, the datum as given
-    fs = fleet_fc_stage(f, R);
-    fc->step = true; fc->rows = S;
-    fc->fc_rc.assign(S, CSSM_OK);
-    if (R & 1u) fs.flags[R] = 0u;
-    for (uint32_t k = 0; k < S; ++k) {
-      const bool runs = h_off[k + 1] > h_off[k];
-      fleet_fc_series(f, k, runs, fc, &fs.op[k]);
-      if (!runs) continue;
-      const size_t r = (size_t)h_off[k];
-      const bool on = fc->fc_rc[k] == CSSM_OK && std::isfinite(t[k]) && t[k] >= f->t[k];
-      fs.flags[r] = on ? (CSSM_FLEET_FC_ON | ((has_obs ? has_obs[k] : 1) ? CSSM_FLEET_FC_HAS : 0u)) : 0u;
-      fs.keys[r] = fc->keys ? fc->keys[k] : cssm_pf_run_key(f->models[k].seed, (1ull << 63) | (uint64_t)f->step[k]);
-      fs.y[r] = y[k];
-    }
+  if (fcst) {
+    fleet_fc_series(f, ride, h, runs);
+    for (uint32_t k = 0; k < S; ++k)
+      if (runs(k)) fleet_fc_record(f, ride, h, k, (size_t)h.off[k], k, f->step[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1);
   }
-  if (iv) {   // (no launch of a step draws a cloud: the f coefficients of a t0 are not read)
-    iv->step = true; iv->rows = S;
-    memset(h_recs + R * RB, 0, (size_t)S * f->d * 8u);
-  }
-  rc = fleet_launch(f, R, nullptr, nullptr, false, nullptr, nullptr, iv, fc);
+  if (ival) memset(h.fco0, 0, (size_t)S * d * 8u);   // (no launch of a step draws a cloud: the f coefficients of a t0 are not read)
+  rc = fleet_launch(f, ride, nullptr, nullptr);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
-    if (fc_rc_out) fc_rc_out[k] = fc->fc_rc[k];
+    if (ride.fc_rc_out) ride.fc_rc_out[k] = ride.fc_rc[k];
     if (active && !active[k]) { rc_out[k] = CSSM_OK; continue; }            // untouched
     if (!f->live[k]) { rc_out[k] = CSSM_ESTATE; continue; }                 // no cloud: never initialised, or failed since
     const FleetSeries& s = f->h_ser[k];
@@ -855,19 +877,19 @@ static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t,
     rc_out[k] = CSSM_OK; f->t[k] = t[k]; f->step[k] += 1u;
     if (ll_out) ll_out[k] = s.ll;
     if (ess_out) ess_out[k] = s.ess;
-    if (iv)
-      fleet_iv_row(f, k, iv->out.data() + (size_t)k * (f->d + 1) * 3u,
-                   reinterpret_cast<const double*>(h_recs + (size_t)h_off[k] * RB + sizeof(FleetRecHead)) + 4 * f->d, *ivo, k);
-    if (fc) fleet_fc_row(f, *fc, k, (fs.flags[(size_t)h_off[k]] & CSSM_FLEET_FC_ON) != 0u, *fco, k);
+    const size_t r = (size_t)h.off[k];
+    if (ival) fleet_iv_row(f, k, ride.out.data() + (size_t)k * (d + 1) * 3u, fleet_rec_fco(h, d, r), true, ride.ivo, k);
+    if (fcst) fleet_fc_row(d, ride.out.data() + (size_t)k * (d + 2) * 3u, ride.pit.data() + 2 * (size_t)k, (h.flags[r] & CSSM_FLEET_FC_ON) != 0u, ride.fco, k);
   }
-  if (fc && !fc->scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", fc->scale_msg.c_str());   // (the call succeeds)
+  if (!ride.scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", ride.scale_msg.c_str());   // (the call succeeds)
   return CSSM_OK;
 }
 
 extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
                                double* ll_out, int32_t* ess_out, int* rc_out) {
   if (!f || !t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
-  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, nullptr, nullptr);
+  FleetRide ride;
+  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, ride);
 }
 
 // filterStream + getIntervals (examples/Filtering.scala:24-31, one observation per sensor per call): cssm_fleet_step, and the summaries of
@@ -878,10 +900,10 @@ extern "C" int cssm_fleet_step_intervals(cssm_fleet* f, const uint8_t* active, c
   if (!t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
-  FleetIv iv;
-  iv.interval = interval;
-  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
-  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, &iv, &o);
+  FleetRide ride;
+  ride.kind = FleetKind::ival; ride.interval = interval;
+  ride.ivo = FleetIvOut{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, ride);
 }
 
 // getMeanForecast over a filterStream, one observation per sensor per call: cssm_fleet_step -- the same arguments, bits and statuses -- and
@@ -895,11 +917,16 @@ extern "C" int cssm_fleet_step_forecast(cssm_fleet* f, const uint8_t* active, co
   if (!t || !y || !rc_out || !fc_rc_out) return fail(CSSM_EINVAL_ARG, "null argument (t, y, rc_out, fc_rc_out)");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
-  FleetFc fc;
-  fc.interval = interval; fc.keys = keys;
-  const FleetFcOut o{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal};
-  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, nullptr, nullptr, &fc, &o, fc_rc_out);
+  FleetRide ride;
+  ride.kind = FleetKind::fcst; ride.interval = interval; ride.keys = keys; ride.fc_rc_out = fc_rc_out;
+  ride.fco = FleetFcOut{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal};
+  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, ride);
 }
+
+// cssm_fleet_summary as staged in d_sm: [S][d] f coefficients | [S][d + 1][3] results | [S] buffer numbers (u32, padded to 8 bytes)
+struct FleetSmStage {
+  size_t out, out_bytes, cur, bytes;
+};
 
 extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_mean, double* state_lower, double* state_upper,
                                   double* eta_of_mean, double* eta_lower, double* eta_upper) {
@@ -908,55 +935,35 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
   HIP_TRY(hipSetDevice(f->device));
   const uint32_t S = f->S, n = f->n;
   const int d = f->d, rows = d + 1;
-  // layout of d_sm (doubles): [S][d] f coefficients | [S][rows][3] results | [S] buffer numbers (u32, two per double)
-  const size_t n_fco = (size_t)S * d, n_out = (size_t)S * rows * 3, n_cur = ((size_t)S + 1) / 2, need = n_fco + n_out + n_cur;
-  if (need > f->sm_cap) {
-    if (f->d_sm) (void)hipFree(f->d_sm);
-    f->d_sm = nullptr; f->sm_cap = 0;
-    if (hipMalloc(&f->d_sm, need * 8) != hipSuccess) return fail(CSSM_ENOMEM, "fleet summary buffers");
-    f->sm_cap = need;
-  }
-  std::vector<double> hbuf(need, 0.0);
-  uint32_t* hcur = reinterpret_cast<uint32_t*>(hbuf.data() + n_fco + n_out);
+  FleetSmStage st;
+  st.out = (size_t)S * d * 8u; st.out_bytes = (size_t)S * rows * 24u; st.cur = st.out + st.out_bytes; st.bytes = st.cur + fleet_pad8((size_t)S * 4u);
+  if (!f->d_sm.reserve(st.bytes, false)) return fail(CSSM_ENOMEM, "fleet summary buffers");
+  std::vector<double> hbuf(st.bytes / 8u, 0.0);
+  double* h_fco = hbuf.data();
+  const double* h_out = fleet_at<double>(hbuf.data(), st.out);
+  uint32_t* h_cur = fleet_at<uint32_t>(hbuf.data(), st.cur);
   fleet_parallel(S, (size_t)S * 4, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       StepRec r;
       cssm_build_rec(&f->models[k], f->t[k], f->t[k], 0.0, 0, f->step[k], &r);   // F(t) of the series' own time
-      for (int c = 0; c < d; ++c) hbuf[k * d + c] = r.fco[c];
-      hcur[k] = f->live[k] ? (f->step[k] & 1u) : 0xffffffffu;
+      for (int c = 0; c < d; ++c) h_fco[k * d + c] = r.fco[c];
+      h_cur[k] = f->live[k] ? (f->step[k] & 1u) : 0xffffffffu;
     }
   });
-  SelState rs, re;   // the ranks of a state row and of the eta row, as cssm_pf_summary takes them
-  sel_ranks(rs, n, interval, true);
-  sel_ranks(re, n, interval, false);
-  uint32_t np2 = 2u;
-  while (np2 < n) np2 <<= 1;
-  double* d_fco = f->d_sm; double* d_out = f->d_sm + n_fco;
-  const uint32_t* d_cur = reinterpret_cast<const uint32_t*>(f->d_sm + n_fco + n_out);
-  HIP_TRY(hipEventRecord(f->ev[2], f->stream));
-  HIP_TRY(hipMemcpyAsync(f->d_sm, hbuf.data(), need * 8, hipMemcpyHostToDevice, f->stream));
-  DISPATCH_D(d, hipLaunchKernelGGL(k_fleet_summary<D>, dim3(S, rows), dim3(CSSM_BLOCK), (size_t)np2 * 8u, f->stream, f->state, f->anc, d_cur, d_fco, n, np2,
-                                   f->base.mk, (uint32_t)rs.rank[0], (uint32_t)rs.rank[1], (uint32_t)re.rank[0], (uint32_t)re.rank[1], d_out));
+  const FleetRanks r = fleet_ranks(n, interval);
+  HIP_TRY(hipEventRecord(f->ev[EV_SUMMARY_BEGIN], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->d_sm.p, hbuf.data(), st.bytes, hipMemcpyHostToDevice, f->stream));
+  DISPATCH_D(d, hipLaunchKernelGGL(k_fleet_summary<D>, dim3(S, rows), dim3(CSSM_BLOCK), (size_t)r.np2 * 8u, f->stream, f->state.at<double>(),
+                                   f->anc.at<uint32_t>(), f->d_sm.at<const uint32_t>(st.cur), f->d_sm.at<const double>(), n, r.np2, f->base.mk,
+                                   r.rk.lo_state, r.rk.hi_state, r.rk.lo_eta, r.rk.hi_eta, f->d_sm.at<double>(st.out)));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(hbuf.data() + n_fco, d_out, n_out * 8, hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipEventRecord(f->ev[3], f->stream));
+  HIP_TRY(hipMemcpyAsync(fleet_at<double>(hbuf.data(), st.out), f->d_sm.at<double>(st.out), st.out_bytes, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipEventRecord(f->ev[EV_SUMMARY_END], f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
-  if (hipEventElapsedTime(&f->ms_summary, f->ev[2], f->ev[3]) != hipSuccess) f->ms_summary = -1.f;
-  const double* ho = hbuf.data() + n_fco;
-  for (uint32_t k = 0; k < S; ++k) {
-    double mean[CSSM_MAX_DIM];
-    for (int c = 0; c < d; ++c) {
-      const double* o = ho + ((size_t)k * rows + c) * 3;
-      mean[c] = o[0];
-      if (state_mean) state_mean[(size_t)k * d + c] = o[0];
-      if (state_lower) state_lower[(size_t)k * d + c] = o[1];
-      if (state_upper) state_upper[(size_t)k * d + c] = o[2];
-    }
-    const double* oe = ho + ((size_t)k * rows + d) * 3;
-    if (eta_lower) eta_lower[k] = oe[1];
-    if (eta_upper) eta_upper[k] = oe[2];
-    if (eta_of_mean) eta_of_mean[k] = f->live[k] ? cssm_eta_of_mean(f->models[k], hbuf.data() + (size_t)k * d, mean) : cssm_nan();   // :420
-  }
+  if (hipEventElapsedTime(&f->ms_summary, f->ev[EV_SUMMARY_BEGIN], f->ev[EV_SUMMARY_END]) != hipSuccess) f->ms_summary = -1.f;
+  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  for (uint32_t k = 0; k < S; ++k)   // (a series without a cloud: its block wrote NaN)
+    fleet_iv_row(f, k, h_out + (size_t)k * rows * 3u, h_fco + (size_t)k * d, f->live[k] != 0, o, k);
   return CSSM_OK;
 }
 
@@ -964,25 +971,36 @@ extern "C" int cssm_fleet_summary(cssm_fleet* f, double interval, double* state_
 // keys, observation parameters, buffer numbers, records), one launch whose blocks are the series (k_fleet_forecast), one read-back.
 // A call that returns samples runs the fleet in chunks of series whose samples fit fc_samp_max -- never chunks of horizons: a series
 // is one block's work.  What a series' own arguments spoil is the series' own: its status, NaN in its outputs, no block for it.
-// the grow-only buffers of both forecasts: `need` bytes of d_fc and of its pinned mirror, 16 N bytes of eta / obs staging per series
+//
+// Either forecast as staged in h_fc / d_fc (byte offsets; off is at 0):
+//   cssm_fleet_forecast:            [off | keys | observation parameters | buffer numbers | records | results]
+//   cssm_fleet_forecast_posterior:  [off | keys | moff | buffer numbers | records | x | rows | picks | results]
+// off, moff: S + 1 u64; keys: S u64; buffer numbers: S u32, padded to 8 bytes; records: R compact ones; x: M x d states; rows: M x
+// (3 d + 1) constraint-transformed parameters; picks: S x N u32, padded; results: R x [d + 2][3].
+struct FleetFcStage {
+  size_t keys, op, moff, cur, recs, x, rows, pick, out, out_bytes, bytes;
+};
+static FleetFcStage fleet_fc_stage(const cssm_fleet* f, size_t R, bool posterior = false, size_t M = 0) {
+  const size_t S = f->S, d = (size_t)f->d;
+  FleetFcStage st;
+  st.keys = (S + 1u) * 8u;
+  st.op = st.moff = st.keys + S * 8u;
+  st.cur = posterior ? st.moff + (S + 1u) * 8u : st.op + S * sizeof(cssm_obs_params);
+  st.recs = st.cur + fleet_pad8(S * 4u);
+  st.x = st.recs + R * CSSM_FLEET_REC_BYTES(f->d);
+  st.rows = st.x + M * d * 8u;
+  st.pick = st.rows + M * (3u * d + 1u) * 8u;
+  st.out = st.pick + (posterior ? fleet_pad8(S * f->n * 4u) : 0u);
+  st.out_bytes = R * (d + 2u) * 24u;
+  st.bytes = st.out + st.out_bytes;
+  return st;
+}
+
+// the grow-only buffers of both forecasts: `need` bytes of d_fc and of its pinned mirror, the kernels' scratch
 static int fleet_fc_ensure(cssm_fleet* f, size_t need) {
-  if (need > f->h_fc_cap) {
-    if (f->h_fc) (void)hipHostFree(f->h_fc);
-    f->h_fc = nullptr; f->h_fc_cap = 0;
-    if (hipHostMalloc((void**)&f->h_fc, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of pinned staging", need);
-    f->h_fc_cap = need + need / 4;
-  }
-  if (need > f->fc_cap) {
-    if (f->d_fc) (void)hipFree(f->d_fc);
-    f->d_fc = nullptr; f->fc_cap = 0;
-    if (hipMalloc(&f->d_fc, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of records and results", need);
-    f->fc_cap = need + need / 4;
-  }
-  if (!f->d_fc_stage && hipMalloc(&f->d_fc_stage, (size_t)f->S * 2u * f->n * 8u) != hipSuccess) {
-    f->d_fc_stage = nullptr;
-    return fail(CSSM_ENOMEM, "fleet forecast: 16 N bytes of staging per series");
-  }
-  return CSSM_OK;
+  if (!f->h_fc.reserve(need, true)) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of pinned staging", need);
+  if (!f->d_fc.reserve(need, true)) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of records and results", need);
+  return fleet_fc_scratch(f);
 }
 
 // chunks of series [cut[c], cut[c + 1]): all of them, or (samples) as many as fit the cap -- one series at least; the device buffer
@@ -998,55 +1016,38 @@ static int fleet_fc_cuts(cssm_fleet* f, const uint64_t* off, bool samples, std::
     if ((size_t)(off[k + 1] - off[cut.back()]) > cap_rows && k > cut.back()) cut.push_back(k);
   cut.push_back(S);
   for (size_t c = 0; c + 1 < cut.size(); ++c) most = std::max<size_t>(most, (size_t)(off[cut[c + 1]] - off[cut[c]]));
-  if (most * samp_row > f->fc_samp_cap) {
-    if (f->d_fc_samp) (void)hipFree(f->d_fc_samp);
-    f->d_fc_samp = nullptr; f->fc_samp_cap = 0;
-    if (hipMalloc(&f->d_fc_samp, most * samp_row) != hipSuccess) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of samples", most * samp_row);
-    f->fc_samp_cap = most * samp_row;
-  }
+  if (!f->d_fc_samp.reserve(most * samp_row, false)) return fail(CSSM_ENOMEM, "fleet forecast: %zu bytes of samples", most * samp_row);
   return CSSM_OK;
 }
 
-// what every launch of either forecast kernel shares: sizes, ranks, the way to a row's order statistics, the fleet's buffers
-static void fleet_fc_args(const cssm_fleet* f, double interval, FleetFcLaunch& l) {
+// what every launch of either forecast kernel shares: sizes, ranks, the way to a row's order statistics, the fleet's buffers, the
+// staged call on the device
+static void fleet_fc_args(const cssm_fleet* f, double interval, const FleetFcStage& st, FleetFcLaunch& l) {
   const uint32_t n = f->n;
-  SelState rs, re;
-  sel_ranks(rs, n, interval, true);
-  sel_ranks(re, n, interval, false);
-  l.args.n = n; l.args.np2 = 2u;
-  while (l.args.np2 < n) l.args.np2 <<= 1;
+  const FleetRanks r = fleet_ranks(n, interval);
+  l.args.n = n; l.args.np2 = r.np2;
   l.args.select = f->fc_select ? (uint32_t)(f->fc_select == 2) : (uint32_t)(n >= CSSM_FLEET_SELECT_MIN_N);
-  l.args.state = f->state; l.args.anc = f->anc;
-  l.args.stage = f->d_fc_stage;
-  l.args.logtab = f->logtab; l.args.mk = f->base.mk;
-  l.args.lo_state = (uint32_t)rs.rank[0]; l.args.hi_state = (uint32_t)rs.rank[1];
-  l.args.lo_eta = (uint32_t)re.rank[0]; l.args.hi_eta = (uint32_t)re.rank[1];
+  l.args.state = f->state.at<double>(); l.args.anc = f->anc.at<uint32_t>();
+  l.args.stage = f->d_fc_scratch.at<double>();
+  l.args.logtab = f->logtab.at<double>(); l.args.mk = f->base.mk;
+  l.args.lo_state = r.rk.lo_state; l.args.hi_state = r.rk.hi_state;
+  l.args.lo_eta = r.rk.lo_eta; l.args.hi_eta = r.rk.hi_eta;
+  l.args.off = f->d_fc.at<const unsigned long long>();
+  l.args.keys = f->d_fc.at<const unsigned long long>(st.keys);
+  l.args.cur = f->d_fc.at<const uint32_t>(st.cur);
+  l.args.recs = f->d_fc.at<const unsigned char>(st.recs);
+  l.args.out = f->d_fc.at<double>(st.out);
   l.d = f->d; l.threads = f->threads; l.stream = f->stream;
 }
 
 // the results [R][d + 2][3] into the caller's arrays; a series whose status is not zero reads NaN
-static void fleet_fc_scatter(const cssm_fleet* f, const uint64_t* off, const double* h_out, const int* rc_out, double* state_mean, double* state_lower,
-                             double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
-                             double* obs_upper, double* samples) {
-  const uint32_t n = f->n;
-  const int d = f->d, rows = d + 2;
+static void fleet_fc_scatter(const cssm_fleet* f, const uint64_t* off, const double* h_out, const int* rc_out, const FleetFcOut& o, double* samples) {
+  const size_t rowsz = (size_t)(f->d + 2) * 3u, samp = (size_t)(f->d + 3) * f->n;
   for (uint32_t k = 0; k < f->S; ++k) {
     const bool ok = rc_out[k] == CSSM_OK;
     for (size_t r = (size_t)off[k]; r < (size_t)off[k + 1]; ++r) {
-      const double* o = h_out + r * (size_t)rows * 3u;
-      auto at = [&](int row, int q) { return ok ? o[3 * row + q] : cssm_nan(); };
-      for (int c = 0; c < d; ++c) {
-        if (state_mean) state_mean[r * d + c] = at(c, 0);
-        if (state_lower) state_lower[r * d + c] = at(c, 1);
-        if (state_upper) state_upper[r * d + c] = at(c, 2);
-      }
-      if (eta_mean) eta_mean[r] = at(d, 0);
-      if (eta_lower) eta_lower[r] = at(d, 1);
-      if (eta_upper) eta_upper[r] = at(d, 2);
-      if (obs_mean) obs_mean[r] = at(d + 1, 0);
-      if (obs_lower) obs_lower[r] = at(d + 1, 1);
-      if (obs_upper) obs_upper[r] = at(d + 1, 2);
-      if (samples && !ok) std::fill(samples + r * (size_t)(d + 3) * n, samples + (r + 1) * (size_t)(d + 3) * n, cssm_nan());
+      fleet_fc_row(f->d, h_out + r * rowsz, nullptr, ok, o, r);
+      if (samples && !ok) std::fill(samples + r * samp, samples + (r + 1) * samp, cssm_nan());
     }
   }
 }
@@ -1057,22 +1058,22 @@ template <class Launch>
 static int fleet_fc_run(cssm_fleet* f, const uint64_t* off, const std::vector<uint32_t>& cut, FleetFcLaunch& l, size_t up, size_t back, size_t back_bytes,
                         double* samples, const char* kernel, Launch&& launch) {
   const size_t samp_row = (size_t)(f->d + 3) * f->n * 8u;
-  HIP_TRY(hipEventRecord(f->ev[4], f->stream));
-  HIP_TRY(hipMemcpyAsync(f->d_fc, f->h_fc, up, hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipEventRecord(f->ev[EV_FORECAST_BEGIN], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->d_fc.p, f->h_fc.p, up, hipMemcpyHostToDevice, f->stream));
   for (size_t c = 0; c + 1 < cut.size(); ++c) {
     const size_t ra = (size_t)off[cut[c]], rb = (size_t)off[cut[c + 1]];
     if (rb == ra) continue;
     l.args.k0 = cut[c]; l.n_series = cut[c + 1] - cut[c];
-    l.args.samples = samples ? f->d_fc_samp : nullptr; l.args.samp_r0 = ra;
+    l.args.samples = samples ? f->d_fc_samp.at<double>() : nullptr; l.args.samp_r0 = ra;
     const int hrc = launch(l);
     if (hrc) return fail(CSSM_EHIP, "%s: %s", kernel, hipGetErrorString((hipError_t)hrc));
-    if (samples) HIP_TRY(hipMemcpyAsync(samples + ra * (size_t)(f->d + 3) * f->n, f->d_fc_samp, (rb - ra) * samp_row, hipMemcpyDeviceToHost, f->stream));
+    if (samples) HIP_TRY(hipMemcpyAsync(samples + ra * (size_t)(f->d + 3) * f->n, f->d_fc_samp.p, (rb - ra) * samp_row, hipMemcpyDeviceToHost, f->stream));
     if (samples && c + 2 < cut.size()) HIP_TRY(hipStreamSynchronize(f->stream));   // (the next chunk writes the same buffer)
   }
-  HIP_TRY(hipMemcpyAsync(f->h_fc + back, f->d_fc + back, back_bytes, hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipEventRecord(f->ev[5], f->stream));
+  HIP_TRY(hipMemcpyAsync(f->h_fc.at<unsigned char>(back), f->d_fc.at<unsigned char>(back), back_bytes, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipEventRecord(f->ev[EV_FORECAST_END], f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
-  if (hipEventElapsedTime(&f->ms_forecast, f->ev[4], f->ev[5]) != hipSuccess) f->ms_forecast = -1.f;
+  if (hipEventElapsedTime(&f->ms_forecast, f->ev[EV_FORECAST_BEGIN], f->ev[EV_FORECAST_END]) != hipSuccess) f->ms_forecast = -1.f;
   return CSSM_OK;
 }
 
@@ -1081,10 +1082,8 @@ extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const dou
                                    double* eta_upper, double* obs_mean, double* obs_lower, double* obs_upper, double* samples, int* rc_out) {
   if (!f || !off || !t || !keys || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
   const uint32_t S = f->S;
-  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
-  for (uint32_t k = 0; k < S; ++k)
-    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
-                                         k + 1, (unsigned long long)off[k + 1]);
+  int rc = fleet_off_check(off, S);
+  if (rc) return rc;
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   const size_t R = (size_t)off[S];
   for (uint32_t k = 0; k < S; ++k)
@@ -1094,21 +1093,15 @@ extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const dou
   for (uint32_t k = 0; k < S; ++k) any_live = any_live || f->live[k];
   if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
   HIP_TRY(hipSetDevice(f->device));
-  const int d = f->d, rows = d + 2;
-  const size_t RB = CSSM_FLEET_REC_BYTES(d);
-  const size_t o_keys = ((size_t)S + 1u) * 8u, o_op = o_keys + (size_t)S * 8u, o_cur = o_op + (size_t)S * sizeof(cssm_obs_params);
-  const size_t o_rec = o_cur + (((size_t)S * 4u + 7u) & ~(size_t)7u), o_out = o_rec + R * RB, n_out = R * (size_t)rows * 3u;
-  const size_t need = o_out + n_out * 8u;
-  {
-    const int erc = fleet_fc_ensure(f, need);
-    if (erc) return erc;
-  }
-  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_fc);
-  unsigned long long* h_keys = reinterpret_cast<unsigned long long*>(f->h_fc + o_keys);
-  cssm_obs_params* h_op = reinterpret_cast<cssm_obs_params*>(f->h_fc + o_op);
-  uint32_t* h_cur = reinterpret_cast<uint32_t*>(f->h_fc + o_cur);
-  unsigned char* h_recs = f->h_fc + o_rec;
-  const double* h_out = reinterpret_cast<const double*>(f->h_fc + o_out);
+  const size_t RB = CSSM_FLEET_REC_BYTES(f->d);
+  const FleetFcStage st = fleet_fc_stage(f, R);
+  rc = fleet_fc_ensure(f, st.bytes);
+  if (rc) return rc;
+  unsigned long long* h_off = f->h_fc.at<unsigned long long>();
+  unsigned long long* h_keys = f->h_fc.at<unsigned long long>(st.keys);
+  cssm_obs_params* h_op = f->h_fc.at<cssm_obs_params>(st.op);
+  uint32_t* h_cur = f->h_fc.at<uint32_t>(st.cur);
+  unsigned char* h_recs = f->h_fc.at<unsigned char>(st.recs);
   // the series' own statuses: no cloud, a model without the scale its observation needs, times that are not a forecast's
   std::string scale_msg;
   size_t n_run = 0;
@@ -1145,20 +1138,16 @@ extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const dou
   });
   if (n_run) {
     std::vector<uint32_t> cut;
-    int rc = fleet_fc_cuts(f, off, samples != nullptr, cut);
+    rc = fleet_fc_cuts(f, off, samples != nullptr, cut);
     if (rc) return rc;
     FleetFcLaunch l;
-    fleet_fc_args(f, interval, l);
-    l.args.off = reinterpret_cast<const unsigned long long*>(f->d_fc);
-    l.args.keys = reinterpret_cast<const unsigned long long*>(f->d_fc + o_keys);
-    l.args.op = reinterpret_cast<const cssm_obs_params*>(f->d_fc + o_op);
-    l.args.cur = reinterpret_cast<const uint32_t*>(f->d_fc + o_cur);
-    l.args.recs = f->d_fc + o_rec;
-    l.args.out = reinterpret_cast<double*>(f->d_fc + o_out);
-    rc = fleet_fc_run(f, off, cut, l, o_out, o_out, n_out * 8u, samples, "k_fleet_forecast", [](const FleetFcLaunch& q) { return cssm_fleet_forecast_launch(q); });
+    fleet_fc_args(f, interval, st, l);
+    l.args.op = f->d_fc.at<const cssm_obs_params>(st.op);
+    rc = fleet_fc_run(f, off, cut, l, st.out, st.out, st.out_bytes, samples, "k_fleet_forecast", [](const FleetFcLaunch& q) { return cssm_fleet_forecast_launch(q); });
     if (rc) return rc;
   }
-  fleet_fc_scatter(f, off, h_out, rc_out, state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, samples);
+  const FleetFcOut o{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, nullptr, nullptr};
+  fleet_fc_scatter(f, off, f->h_fc.at<const double>(st.out), rc_out, o, samples);
   if (!scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", scale_msg.c_str());   // (the call succeeds; the message names the first such series)
   return CSSM_OK;
 }
@@ -1177,39 +1166,31 @@ extern "C" int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_des
   const uint32_t S = f->S, n = f->n;
   if (moff[0] != 0) return fail(CSSM_EINVAL_ARG, "moff[0] must be 0");
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  int rc = CSSM_OK;
   for (uint32_t k = 0; k < S; ++k) {
-    if (moff[k + 1] < moff[k]) return fail(CSSM_EINVAL_ARG, "moff must be non-decreasing (moff[%u] = %llu > moff[%u] = %llu)", k,
-                                           (unsigned long long)moff[k], k + 1, (unsigned long long)moff[k + 1]);
-    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
-                                         k + 1, (unsigned long long)off[k + 1]);
+    if ((rc = fleet_off_step("moff", moff, k))) return rc;
+    if ((rc = fleet_off_step("off", off, k))) return rc;
   }
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (!desc->leaves || desc->n_leaves < 1) return fail(CSSM_EINVAL_DESC, "null model descriptor");
-  {   // the structure (an LGCP descriptor is never a fleet's) and the length of a row: no rows looked at
-    const int rc = cssm_posterior_rows_into(&f->base, desc, theta, n_theta, 0, nullptr);
-    if (rc) return rc;
-  }
+  // the structure (an LGCP descriptor is never a fleet's) and the length of a row: no rows looked at
+  rc = cssm_posterior_rows_into(&f->base, desc, theta, n_theta, 0, nullptr);
+  if (rc) return rc;
   const size_t R = (size_t)off[S], Mtot = (size_t)moff[S];
-  const int d = f->d, rows = d + 2;
+  const int d = f->d;
   const size_t RS = 3 * (size_t)d + 1, RB = CSSM_FLEET_REC_BYTES(d);
   HIP_TRY(hipSetDevice(f->device));
-  // layout: [off | keys | moff | buffer numbers | records | x | rows | picks | results]; the caller's picks are uploaded, the drawn
-  // ones only read back
-  const size_t o_keys = ((size_t)S + 1u) * 8u, o_moff = o_keys + (size_t)S * 8u, o_cur = o_moff + ((size_t)S + 1u) * 8u;
-  const size_t o_rec = o_cur + (((size_t)S * 4u + 7u) & ~(size_t)7u), o_x = o_rec + R * RB, o_rows = o_x + Mtot * (size_t)d * 8u;
-  const size_t o_pick = o_rows + Mtot * RS * 8u, o_out = o_pick + (((size_t)S * n * 4u + 7u) & ~(size_t)7u), n_out = R * (size_t)rows * 3u;
-  const size_t need = o_out + n_out * 8u;
-  int rc = fleet_fc_ensure(f, need);
+  const FleetFcStage st = fleet_fc_stage(f, R, true, Mtot);   // (the caller's picks are uploaded, the drawn ones only read back)
+  rc = fleet_fc_ensure(f, st.bytes);
   if (rc) return rc;
-  unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_fc);
-  unsigned long long* h_keys = reinterpret_cast<unsigned long long*>(f->h_fc + o_keys);
-  unsigned long long* h_moff = reinterpret_cast<unsigned long long*>(f->h_fc + o_moff);
-  uint32_t* h_cur = reinterpret_cast<uint32_t*>(f->h_fc + o_cur);
-  unsigned char* h_recs = f->h_fc + o_rec;
-  double* h_x = reinterpret_cast<double*>(f->h_fc + o_x);                  // (a series' states are copied here once they are known finite)
-  double* h_rows = reinterpret_cast<double*>(f->h_fc + o_rows);
-  uint32_t* h_pick = reinterpret_cast<uint32_t*>(f->h_fc + o_pick);
-  const double* h_out = reinterpret_cast<const double*>(f->h_fc + o_out);
+  unsigned long long* h_off = f->h_fc.at<unsigned long long>();
+  unsigned long long* h_keys = f->h_fc.at<unsigned long long>(st.keys);
+  unsigned long long* h_moff = f->h_fc.at<unsigned long long>(st.moff);
+  uint32_t* h_cur = f->h_fc.at<uint32_t>(st.cur);
+  unsigned char* h_recs = f->h_fc.at<unsigned char>(st.recs);
+  double* h_x = f->h_fc.at<double>(st.x);                  // (a series' states are copied here once they are known finite)
+  double* h_rows = f->h_fc.at<double>(st.rows);
+  uint32_t* h_pick = f->h_fc.at<uint32_t>(st.pick);
   for (uint32_t k = 0; k <= S; ++k) { h_off[k] = off[k]; h_moff[k] = moff[k]; }
   if (pick) memcpy(h_pick, pick, (size_t)S * n * 4u);
   // the series' own statuses (what cssm_pf_forecast_posterior refuses, in its order); the message of each as its thread left it
@@ -1268,26 +1249,22 @@ extern "C" int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_des
     rc = fleet_fc_cuts(f, off, samples != nullptr, cut);
     if (rc) return rc;
     FleetFcLaunch l;
-    fleet_fc_args(f, interval, l);
-    l.args.off = reinterpret_cast<const unsigned long long*>(f->d_fc);
-    l.args.keys = reinterpret_cast<const unsigned long long*>(f->d_fc + o_keys);
+    fleet_fc_args(f, interval, st, l);
     l.args.op = nullptr;
-    l.args.cur = reinterpret_cast<const uint32_t*>(f->d_fc + o_cur);
-    l.args.recs = f->d_fc + o_rec;
-    l.args.out = reinterpret_cast<double*>(f->d_fc + o_out);
     FleetFcPost q;
-    q.moff = reinterpret_cast<const unsigned long long*>(f->d_fc + o_moff);
-    q.x = reinterpret_cast<const double*>(f->d_fc + o_x);
-    q.rows = reinterpret_cast<const double*>(f->d_fc + o_rows);
-    q.picks = reinterpret_cast<uint32_t*>(f->d_fc + o_pick);
+    q.moff = f->d_fc.at<const unsigned long long>(st.moff);
+    q.x = f->d_fc.at<const double>(st.x);
+    q.rows = f->d_fc.at<const double>(st.rows);
+    q.picks = f->d_fc.at<uint32_t>(st.pick);
     q.draw = pick ? 0u : 1u;
     q.obs_df = f->base.obs_df;
-    const size_t back = pick_out && !pick ? o_pick : o_out;
-    rc = fleet_fc_run(f, off, cut, l, pick ? o_out : o_pick, back, need - back, samples, "k_fleet_forecast_post",
+    const size_t back = pick_out && !pick ? st.pick : st.out;
+    rc = fleet_fc_run(f, off, cut, l, pick ? st.out : st.pick, back, st.bytes - back, samples, "k_fleet_forecast_post",
                       [&](const FleetFcLaunch& ll) { return cssm_fleet_forecast_post_launch(ll, q); });
     if (rc) return rc;
   }
-  fleet_fc_scatter(f, off, h_out, rc_out, state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, samples);
+  const FleetFcOut o{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, nullptr, nullptr};
+  fleet_fc_scatter(f, off, f->h_fc.at<const double>(st.out), rc_out, o, samples);
   if (pick_out)   // a series that ran: what its block used; one without horizons: the same picks, formed here; a refused or empty one: zeros
     for (uint32_t k = 0; k < S; ++k) {
       uint32_t* po = pick_out + (size_t)k * n;
@@ -1300,6 +1277,23 @@ extern "C" int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_des
   for (uint32_t k = 0; k < S; ++k)   // (the call succeeds; the message names the first refused series)
     if (rc_out[k]) { (void)fail(CSSM_EINVAL_ARG, "series %u: %s", k, msg[k].c_str()); break; }
   return CSSM_OK;
+}
+
+// One chunk of cssm_fleet_interpolate -- the series k0 .. k1 - 1, Rc records, Rc + Sc output rows -- as staged in h_ip / d_ip (byte
+// offsets; the chunk's own offsets are at 0): [off | records | the f coefficients of every output row | series scalars | results].  The
+// first three are uploaded, the last two read back.
+struct FleetIpStage {
+  size_t recs, fco, ser, out, bytes;
+};
+static FleetIpStage fleet_ip_stage(const cssm_fleet* f, const uint64_t* off, uint32_t k0, uint32_t k1) {
+  const size_t d = (size_t)f->d, Sc = k1 - k0, Rc = (size_t)(off[k1] - off[k0]), Qc = Rc + Sc;
+  FleetIpStage st;
+  st.recs = (Sc + 1u) * 8u;
+  st.fco = st.recs + Rc * CSSM_FLEET_REC_BYTES(f->d);
+  st.ser = st.fco + Qc * d * 8u;
+  st.out = st.ser + Sc * sizeof(FleetSeries);
+  st.bytes = st.out + Qc * (d + 1u) * 24u;
+  return st;
 }
 
 // FilterInterpolate (model/ParticleFilter.scala:273-311, examples/Interpolate.scala:31-44) of every series: cssm_pf_interpolate per
@@ -1321,21 +1315,16 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
   const uint32_t S = f->S, n = f->n;
   const int d = f->d, rows = d + 1;
+  int rc = CSSM_OK;
   for (uint32_t k = 0; k < S; ++k) {
-    if (off[k + 1] < off[k]) return fail(CSSM_EINVAL_ARG, "off must be non-decreasing (off[%u] = %llu > off[%u] = %llu)", k, (unsigned long long)off[k],
-                                         k + 1, (unsigned long long)off[k + 1]);
+    if ((rc = fleet_off_step("off", off, k))) return rc;
     if (off[k + 1] - off[k] > 0xfffffffeull) return fail(CSSM_EINVAL_ARG, "series %u: too many records", k);
   }
   HIP_TRY(hipSetDevice(f->device));
-  int rc = fleet_upload_par(f);
+  rc = fleet_upload_par(f);
   if (rc) return rc;
   // chunks of series [cut[c], cut[c + 1]) whose history fits the cap; the buffers of the largest one
   const size_t RB = CSSM_FLEET_REC_BYTES(d), slice = (size_t)n * (8u * (size_t)d + 4u);
-  auto stage_o = [&](uint32_t k0, uint32_t k1, size_t* o) {   // byte offsets of [off | recs | fco | ser | out | end] of a chunk
-    const size_t Sc = k1 - k0, Rc = (size_t)(off[k1] - off[k0]), Qc = Rc + Sc;
-    o[0] = 0; o[1] = (Sc + 1u) * 8u; o[2] = o[1] + Rc * RB; o[3] = o[2] + Qc * (size_t)d * 8u; o[4] = o[3] + Sc * sizeof(FleetSeries);
-    o[5] = o[4] + Qc * (size_t)rows * 24u;
-  };
   std::vector<uint32_t> cut(1, 0u);
   size_t held = 0, need = 0, need_hist = 0;
   uint32_t widest = 0;
@@ -1346,51 +1335,27 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
     if (held > need_hist) { need_hist = held; widest = cut.back(); }
   }
   cut.push_back(S);
-  for (size_t c = 0; c + 1 < cut.size(); ++c) {
-    size_t o[6];
-    stage_o(cut[c], cut[c + 1], o);
-    need = std::max(need, o[5]);
+  for (size_t c = 0; c + 1 < cut.size(); ++c) need = std::max(need, fleet_ip_stage(f, off, cut[c], cut[c + 1]).bytes);
+  if (!f->h_ip.reserve(need, true)) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of pinned staging", need);
+  if (!f->d_ip.reserve(need, true)) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of records and results", need);
+  if (!f->d_ip_hist.reserve(need_hist, false)) {
+    if (need_hist > f->ip_hist_max)   // a series longer than the cap runs alone
+      return fail(CSSM_ENOMEM, "fleet interpolation: series %u alone needs %zu bytes of lineage history ((T + 1) N (8 d + 4))", widest, need_hist);
+    return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of lineage history (CSSM_OPT_INTERP_CAP lowers it)", need_hist);
   }
-  if (need > f->h_ip_cap) {
-    if (f->h_ip) (void)hipHostFree(f->h_ip);
-    f->h_ip = nullptr; f->h_ip_cap = 0;
-    if (hipHostMalloc((void**)&f->h_ip, need + need / 4, hipHostMallocDefault) != hipSuccess) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of pinned staging", need);
-    f->h_ip_cap = need + need / 4;
-  }
-  if (need > f->ip_cap) {
-    if (f->d_ip) (void)hipFree(f->d_ip);
-    f->d_ip = nullptr; f->ip_cap = 0;
-    if (hipMalloc(&f->d_ip, need + need / 4) != hipSuccess) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of records and results", need);
-    f->ip_cap = need + need / 4;
-  }
-  if (need_hist > f->ip_hist_cap) {
-    if (f->d_ip_hist) (void)hipFree(f->d_ip_hist);
-    f->d_ip_hist = nullptr; f->ip_hist_cap = 0;
-    if (hipMalloc(&f->d_ip_hist, need_hist) != hipSuccess) {
-      f->d_ip_hist = nullptr;
-      if (need_hist > f->ip_hist_max)   // a series longer than the cap runs alone
-        return fail(CSSM_ENOMEM, "fleet interpolation: series %u alone needs %zu bytes of lineage history ((T + 1) N (8 d + 4))", widest, need_hist);
-      return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of lineage history (CSSM_OPT_INTERP_CAP lowers it)", need_hist);
-    }
-    f->ip_hist_cap = need_hist;
-  }
-  SelState rs, re;
-  sel_ranks(rs, n, interval, true);
-  sel_ranks(re, n, interval, false);
-  uint32_t np2 = 2u;
-  while (np2 < n) np2 <<= 1;
+  const FleetRanks r = fleet_ranks(n, interval);
   const bool pairing = (flags & CSSM_INTERP_REFERENCE_PAIRING) != 0;
+  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
   double ms[2] = {0.0, 0.0};
   for (size_t c = 0; c + 1 < cut.size(); ++c) {
     const uint32_t k0 = cut[c], k1 = cut[c + 1], Sc = k1 - k0;
     const size_t R0 = (size_t)off[k0], Rc = (size_t)off[k1] - R0, Qc = Rc + Sc;
-    size_t o[6];
-    stage_o(k0, k1, o);
-    unsigned long long* h_off = reinterpret_cast<unsigned long long*>(f->h_ip);
-    unsigned char* h_recs = f->h_ip + o[1];
-    double* h_fco = reinterpret_cast<double*>(f->h_ip + o[2]);
-    const FleetSeries* h_ser = reinterpret_cast<const FleetSeries*>(f->h_ip + o[3]);
-    const double* h_out = reinterpret_cast<const double*>(f->h_ip + o[4]);
+    const FleetIpStage st = fleet_ip_stage(f, off, k0, k1);
+    unsigned long long* h_off = f->h_ip.at<unsigned long long>();
+    unsigned char* h_recs = f->h_ip.at<unsigned char>(st.recs);
+    double* h_fco = f->h_ip.at<double>(st.fco);
+    const FleetSeries* h_ser = f->h_ip.at<const FleetSeries>(st.ser);
+    const double* h_out = f->h_ip.at<const double>(st.out);
     for (uint32_t k = k0; k <= k1; ++k) h_off[k - k0] = off[k] - R0;
     fleet_parallel(Sc, 2 * Rc, [&](size_t lo, size_t hi) {
       for (size_t kl = lo; kl < hi; ++kl) {
@@ -1406,43 +1371,38 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
         }
         for (size_t q = 0; q <= b - a; ++q) {                  // F(time of output row q), as cssm_pf_interpolate's summaries build it
           const double time = q ? t[a + q - 1] : m;
-          StepRec r;
-          cssm_build_rec(&f->models[k], time, time, 0.0, 0, 0u, &r);
-          for (int cc = 0; cc < d; ++cc) fco[q * (size_t)d + cc] = r.fco[cc];
+          StepRec rec;
+          cssm_build_rec(&f->models[k], time, time, 0.0, 0, 0u, &rec);
+          for (int cc = 0; cc < d; ++cc) fco[q * (size_t)d + cc] = rec.fco[cc];
         }
       }
     });
     if (Rc) {
-      double* d_hist = reinterpret_cast<double*>(f->d_ip_hist);
-      uint32_t* d_hanc = reinterpret_cast<uint32_t*>(f->d_ip_hist + Qc * (size_t)d * n * 8u);
-      HIP_TRY(hipMemcpyAsync(f->d_ip, f->h_ip, o[3], hipMemcpyHostToDevice, f->stream));
+      HIP_TRY(hipMemcpyAsync(f->d_ip.p, f->h_ip.p, st.ser, hipMemcpyHostToDevice, f->stream));
       HIP_TRY(hipEventRecord(f->ev_ip[0], f->stream));
-      FleetLaunch l;
-      l.args.n = n; l.args.state = f->state; l.args.anc = f->anc; l.args.ser = f->ser; l.args.par = f->par;
-      l.args.off = reinterpret_cast<const unsigned long long*>(f->d_ip);
-      l.args.ctl = nullptr; l.args.recs = f->d_ip + o[1];
-      l.args.ll_t = nullptr; l.args.ess_t = nullptr; l.args.logtab = f->logtab; l.args.mk = f->base.mk;
-      l.args.picks = nullptr; l.args.path = nullptr; l.args.last = nullptr;
-      l.args.fc = FleetOneStep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      l.args.hist = d_hist; l.args.hanc = d_hanc; l.args.hser = reinterpret_cast<FleetSeries*>(f->d_ip + o[3]); l.args.k0 = k0;
-      l.n_series = Sc; l.path = false; l.hist = true; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+      FleetLaunch l{};
+      fleet_series_args(f, l);
+      l.args.off = f->d_ip.at<const unsigned long long>(); l.args.recs = f->d_ip.at<const unsigned char>(st.recs);
+      l.args.hist = f->d_ip_hist.at<double>(); l.args.hanc = f->d_ip_hist.at<uint32_t>(Qc * (size_t)d * n * 8u);
+      l.args.hser = f->d_ip.at<FleetSeries>(st.ser); l.args.k0 = k0;
+      l.n_series = Sc; l.kind = FleetKind::hist;
       rc = fleet_series_launch(d, l);
       if (rc) return rc;
       HIP_TRY(hipEventRecord(f->ev_ip[1], f->stream));
       FleetLinLaunch q;
-      q.args.n = n; q.args.np2 = np2; q.args.pairing = pairing ? 1u : 0u;
-      q.args.hist = d_hist; q.args.hanc = d_hanc;
+      q.args.n = n; q.args.np2 = r.np2; q.args.pairing = pairing ? 1u : 0u;
+      q.args.hist = l.args.hist; q.args.hanc = l.args.hanc;
       q.args.off = l.args.off; q.args.ser = l.args.hser; q.args.recs = l.args.recs;
-      q.args.fco = reinterpret_cast<const double*>(f->d_ip + o[2]);
-      q.args.out = reinterpret_cast<double*>(f->d_ip + o[4]);
+      q.args.fco = f->d_ip.at<const double>(st.fco);
+      q.args.out = f->d_ip.at<double>(st.out);
       q.args.mk = f->base.mk;
-      q.args.lo_state = (uint32_t)rs.rank[0]; q.args.hi_state = (uint32_t)rs.rank[1];
-      q.args.lo_eta = (uint32_t)re.rank[0]; q.args.hi_eta = (uint32_t)re.rank[1];
+      q.args.lo_state = r.rk.lo_state; q.args.hi_state = r.rk.hi_state;
+      q.args.lo_eta = r.rk.lo_eta; q.args.hi_eta = r.rk.hi_eta;
       q.d = d; q.n_series = Sc; q.stream = f->stream;
       const int hrc = cssm_fleet_lineage_launch(q);
       if (hrc) return fail(CSSM_EHIP, "k_fleet_lineage: %s", hipGetErrorString((hipError_t)hrc));
       HIP_TRY(hipEventRecord(f->ev_ip[2], f->stream));
-      HIP_TRY(hipMemcpyAsync(f->h_ip + o[3], f->d_ip + o[3], o[5] - o[3], hipMemcpyDeviceToHost, f->stream));
+      HIP_TRY(hipMemcpyAsync(f->h_ip.at<unsigned char>(st.ser), f->d_ip.at<unsigned char>(st.ser), st.bytes - st.ser, hipMemcpyDeviceToHost, f->stream));
       HIP_TRY(hipStreamSynchronize(f->stream));
       float m0 = 0.f, m1 = 0.f;
       if (hipEventElapsedTime(&m0, f->ev_ip[0], f->ev_ip[1]) == hipSuccess && hipEventElapsedTime(&m1, f->ev_ip[1], f->ev_ip[2]) == hipSuccess) {
@@ -1456,19 +1416,8 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
       else rc_out[k] = h_ser[kl].err ? CSSM_ENONFINITE : CSSM_OK;
       const bool ok = rc_out[k] == CSSM_OK;
       ll_out[k] = ok ? h_ser[kl].ll : cssm_nan();
-      for (size_t q = 0; q <= T; ++q) {
-        const double* ho = h_out + (lrow + q) * (size_t)rows * 3u;
-        double mean[CSSM_MAX_DIM];
-        for (int cc = 0; cc < d; ++cc) {
-          mean[cc] = ok ? ho[3 * cc] : cssm_nan();
-          if (state_mean) state_mean[(grow + q) * d + cc] = mean[cc];
-          if (state_lower) state_lower[(grow + q) * d + cc] = ok ? ho[3 * cc + 1] : cssm_nan();
-          if (state_upper) state_upper[(grow + q) * d + cc] = ok ? ho[3 * cc + 2] : cssm_nan();
-        }
-        if (eta_lower) eta_lower[grow + q] = ok ? ho[3 * d + 1] : cssm_nan();
-        if (eta_upper) eta_upper[grow + q] = ok ? ho[3 * d + 2] : cssm_nan();
-        if (eta_of_mean) eta_of_mean[grow + q] = ok ? cssm_eta_of_mean(f->models[k], h_fco + (lrow + q) * (size_t)d, mean) : cssm_nan();   // :420
-      }
+      for (size_t q = 0; q <= T; ++q)
+        fleet_iv_row(f, k, h_out + (lrow + q) * (size_t)rows * 3u, h_fco + (lrow + q) * (size_t)d, ok, o, grow + q);
     }
   }
   f->ms_ip[0] = ms[0]; f->ms_ip[1] = ms[1]; f->ip_ran = true;
@@ -1490,11 +1439,11 @@ extern "C" int cssm_fleet_get_particles(cssm_fleet* f, uint32_t k, double* out_d
   if (!f->live[k]) return fail(CSSM_ESTATE, "series %u has no cloud (not initialised, or its weights were unusable)", k);
   HIP_TRY(hipSetDevice(f->device));
   const uint32_t n = f->n;
-  const double* src = f->state + ((size_t)k * 2u + (f->step[k] & 1u)) * f->d * n;
-  hipLaunchKernelGGL(k_gather, dim3(grid_for(n, 256, 64)), dim3(256), 0, f->stream, src, (size_t)n, f->anc + (size_t)k * n, f->d_tmp, (size_t)n, (uint64_t)n,
+  const double* src = f->state.at<double>() + ((size_t)k * 2u + (f->step[k] & 1u)) * f->d * n;
+  hipLaunchKernelGGL(k_gather, dim3(grid_for(n, 256, 64)), dim3(256), 0, f->stream, src, (size_t)n, f->anc.at<uint32_t>() + (size_t)k * n, f->d_tmp.at<double>(), (size_t)n, (uint64_t)n,
                      f->d, (const double*)nullptr, (size_t)0, 0u);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_dN, f->d_tmp, (size_t)f->d * n * 8, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(out_dN, f->d_tmp.p, (size_t)f->d * n * 8, hipMemcpyDeviceToHost, f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
   return CSSM_OK;
 }
@@ -1504,7 +1453,7 @@ extern "C" int cssm_fleet_get_ancestors(cssm_fleet* f, uint32_t k, uint32_t* out
   if (k >= f->S) return fail(CSSM_EINVAL_ARG, "series %u of %u", k, f->S);
   if (!f->live[k]) return fail(CSSM_ESTATE, "series %u has no cloud (not initialised, or its weights were unusable)", k);
   HIP_TRY(hipSetDevice(f->device));
-  HIP_TRY(hipMemcpyAsync(out_N, f->anc + (size_t)k * f->n, (size_t)f->n * 4, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(out_N, f->anc.at<uint32_t>() + (size_t)k * f->n, (size_t)f->n * 4, hipMemcpyDeviceToHost, f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
   return CSSM_OK;
 }

@@ -328,15 +328,14 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.ser[k] = o; }
 }
 
+// which k_fleet_series a launch runs: <D, false> | <D, true> | <D, false, true> | <D, false, false, true> | <D, false, false, false, true>
+enum class FleetKind : int { plain, path, hist, ival, fcst };
 struct FleetLaunch {
   FleetArgs args;
-  uint32_t n_series;
-  bool path;            // k_fleet_series<D, true>
-  bool hist = false;    // k_fleet_series<D, false, true>: n_series blocks, the series args.k0 .. args.k0 + n_series - 1
-  bool ival = false;    // k_fleet_series<D, false, false, true>: lds = 8 args.iv_np2 + 4 n bytes
-  bool fcst = false;    // k_fleet_series<D, false, false, false, true>: the same lds
+  uint32_t n_series;    // blocks; hist: the series args.k0 .. args.k0 + n_series - 1
+  FleetKind kind;
   int threads;
-  size_t lds;
+  size_t lds;           // ival, fcst: 8 args.iv_np2 + 4 n bytes
   hipStream_t stream;
 };
 // one per latent dimension, defined in cssm_fleet_d.hip

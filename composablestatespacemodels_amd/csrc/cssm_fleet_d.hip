@@ -12,10 +12,14 @@
 #define CSSM_FLEET_NAME(d) CSSM_FLEET_NAME2(d)
 
 int CSSM_FLEET_NAME(CSSM_FLEET_D)(const FleetLaunch& l) {
-  if (l.fcst) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false, false, false, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
-  else if (l.ival) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false, false, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
-  else if (l.hist) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
-  else if (l.path) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, true>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
-  else hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, false>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args);
+#define CSSM_FLEET_RUN(...) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, __VA_ARGS__>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args)
+  switch (l.kind) {   // (the object holds the kernels in the order they are named here: reordering the cases reorders its code)
+    case FleetKind::fcst: CSSM_FLEET_RUN(false, false, false, true); break;
+    case FleetKind::ival: CSSM_FLEET_RUN(false, false, true); break;
+    case FleetKind::hist: CSSM_FLEET_RUN(false, true); break;
+    case FleetKind::path: CSSM_FLEET_RUN(true); break;
+    case FleetKind::plain: CSSM_FLEET_RUN(false); break;
+  }
+#undef CSSM_FLEET_RUN
   return (int)hipGetLastError();
 }
