@@ -31,6 +31,7 @@ MAX_LEAVES = 16
 FLEET_MAX_N = 4096   # CSSM_FLEET_MAX_N
 CSSM_OPT_INTERP_CAP = 13
 CSSM_INTERP_REFERENCE_PAIRING = 1
+CSSM_FLEET_NO_ROWS = 0xFFFFFFFF
 
 _dp = C.POINTER(C.c_double)
 
@@ -196,6 +197,11 @@ SYMBOLS = [
                                                 _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p, C.POINTER(C.c_int)]),
     ("cssm_fleet_interpolate", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_fleet_interpolate_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_fleet_window", C.c_int, [_h, C.c_uint32]),
+    ("cssm_fleet_window_depth", C.c_uint32, [_h, C.c_uint32]),
+    ("cssm_fleet_step_interpolate", C.c_int, [_h, _u8p, _dp, _dp, _u8p, _u32p, C.c_uint32, C.c_double, _dp, _i32p, _u32p, _dp, _dp, _dp, _dp, _dp, _dp,
+                                              C.POINTER(C.c_int)]),
+    ("cssm_fleet_step_interpolate_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_observation_index", C.c_uint64, [_h, C.c_uint32]),
     ("cssm_fleet_pack_record", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32,
                                          _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),

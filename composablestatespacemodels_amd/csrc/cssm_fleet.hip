@@ -100,7 +100,26 @@ struct cssm_fleet {
   hipEvent_t ev_ip[3] = {nullptr, nullptr, nullptr};   // before the forward launch | between the two | behind the lineage launch
   double ms_ip[2] = {-1.0, -1.0};                      // ... of the last interpolation, summed over its chunks
   bool ip_ran = false;
+  // the window of cssm_fleet_step_interpolate: per series a ring of win_slices slots, each a cloud and the ancestors that resampled it
+  // ([S][slices][d][n] doubles, then [S][slices][n] uint32).  Per series on the host: whether the window is continuous (the cloud the
+  // fleet holds is the one its newest slot holds), the newest slot, the records remembered behind the base slice; per slot F at its time
+  // and whether a weighted record wrote it.
+  FleetBuf win;
+  uint32_t win_slices = 0;
+  std::vector<uint8_t> win_on, win_res;
+  std::vector<uint32_t> win_head, win_depth;
+  std::vector<double> win_fco;
+  hipEvent_t ev_win[3] = {nullptr, nullptr, nullptr};   // before the forward launch | between the two | behind the lineage launch
+  double ms_win[2] = {-1.0, -1.0};
+  bool win_ran = false;
 };
+// series k's cloud, key or parameters are about to be written by another call than cssm_fleet_step_interpolate: its window restarts
+static void fleet_win_drop(cssm_fleet* f, uint32_t k) {
+  if (f->win_slices) { f->win_on[k] = 0; f->win_depth[k] = 0u; }
+}
+static void fleet_win_drop_all(cssm_fleet* f) {
+  for (uint32_t k = 0; k < f->S && f->win_slices; ++k) fleet_win_drop(f, k);
+}
 
 #define FLEET_SERVED "cssm_pf_* (one handle per series) and cssm_pfb_* (batch of chains) serve it"
 
@@ -201,6 +220,7 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (f->stream) (void)hipStreamSynchronize(f->stream);
   for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : f->ev_ip) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : f->ev_win) if (e) (void)hipEventDestroy(e);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;   // (every FleetBuf frees itself)
 }
@@ -234,6 +254,7 @@ extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particl
   if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) return bail(CSSM_EHIP, "hipStreamCreate");
   for (hipEvent_t& e : f->ev) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   for (hipEvent_t& e : f->ev_ip) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
+  for (hipEvent_t& e : f->ev_win) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   const size_t rows = (size_t)S * 2u * f->d * n;
   if (!f->state.reserve(rows * 8, false) || !f->anc.reserve((size_t)S * n * 4, false) || !f->ser.reserve((size_t)S * sizeof(FleetSeries), false) ||
       !f->par.reserve((size_t)S * sizeof(FleetPar), false) || !f->logtab.reserve(sizeof(CSSM_TAB), false) || !f->d_tmp.reserve((size_t)f->d * n * 8, false))
@@ -290,6 +311,7 @@ extern "C" int cssm_fleet_set_params(cssm_fleet* f, const cssm_model_desc* const
   }
   f->models.swap(next);
   f->par_dirty = true;
+  fleet_win_drop_all(f);
   return CSSM_OK;
 }
 
@@ -297,6 +319,7 @@ extern "C" int cssm_fleet_reseed(cssm_fleet* f, const uint64_t* seeds) {
   if (!f || !seeds) return fail(CSSM_EINVAL_ARG, "null argument");
   for (uint32_t k = 0; k < f->S; ++k) f->models[k].seed = seeds[k];
   f->par_dirty = true;
+  fleet_win_drop_all(f);
   return CSSM_OK;
 }
 
@@ -393,15 +416,17 @@ static void fleet_fc_row(int d, const double* src, const int32_t* pit, bool ok, 
 // an entry point reads in the staging after the launch, derives from it.
 // Staged, one upload: [S + 1 offsets (u64)] [S control words (u32), padded to 8 bytes] [R compact records] [the rider's:
 //   path: R sampleOne slots (u32) | ival: [S][d] f coefficients, F at every series' t0 | fcst: R keys (u64), R data (f64), S observation
-//   parameters, R flags (u32) padded to 8 bytes] -- a launch carries one rider at most.
+//   parameters, R flags (u32) padded to 8 bytes | ring: R slots (u32) and S base slots (u32), each padded to 8 bytes, then the lineage
+//   launch's Q requests (FleetWinReq), Q x L slot words (u32, padded), Q x L x d f coefficients] -- a launch carries one rider at most.
 // Written by the rider into d_rows, preset to 0xff bytes (NaN; -1 in the counts) for what no block writes:
 //   path: [S][d] last rows, then (asked for) the R + S rows of the paths | ival: `rows` of [d + 1][3] | fcst: `rows` of [d + 2][3], then
-//   `rows` of 2 PIT counts (i32).
+//   `rows` of 2 PIT counts (i32) | ring: Q x L rows of [d + 1][3], written by the lineage launch.
 static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
 struct FleetStage {
   FleetKind kind = FleetKind::plain;
   size_t R = 0, rec_bytes = 0;
   size_t ctl = 0, recs = 0, ride = 0, fc_y = 0, fc_op = 0, fc_flags = 0, bytes = 0;   // byte offsets into the staging, and its size
+  size_t w_base = 0, w_req = 0, w_words = 0, w_fco = 0;                                // ... of the ring rider
   size_t rows = 0, out_doubles = 0, rows_bytes = 0;   // d_rows: the rows of ival / fcst and their doubles; the bytes of any rider
 };
 struct FleetStageView {   // the staging on the host or on the device; the pointers of another rider are null
@@ -409,6 +434,7 @@ struct FleetStageView {   // the staging on the host or on the device; the point
   uint32_t* picks;
   double* fco0;
   unsigned long long* keys; double* y; cssm_obs_params* op; uint32_t* flags;
+  uint32_t *w_slot, *w_base; FleetWinReq* w_req; uint32_t* w_words; double* w_fco;
 };
 static FleetStageView fleet_view(const FleetStage& st, const FleetBuf& b) {
   FleetStageView v{};
@@ -419,6 +445,10 @@ static FleetStageView fleet_view(const FleetStage& st, const FleetBuf& b) {
     v.keys = b.at<unsigned long long>(st.ride); v.y = b.at<double>(st.fc_y);
     v.op = b.at<cssm_obs_params>(st.fc_op); v.flags = b.at<uint32_t>(st.fc_flags);
   }
+  if (st.kind == FleetKind::ring) {
+    v.w_slot = b.at<uint32_t>(st.ride); v.w_base = b.at<uint32_t>(st.w_base); v.w_req = b.at<FleetWinReq>(st.w_req);
+    v.w_words = b.at<uint32_t>(st.w_words); v.w_fco = b.at<double>(st.w_fco);
+  }
   return v;
 }
 // the f coefficients of staged record r
@@ -427,8 +457,9 @@ static const double* fleet_rec_fco(const FleetStageView& v, int d, size_t r) {
 }
 
 // What rides behind the records of a series launch -- nothing (plain), `filter`'s sampled path, getIntervals of every cloud (ival), the
-// forecast of every record before it is stepped (fcst) -- with that rider's inputs and what it brings back.  (hist is
-// cssm_fleet_interpolate's own launch: it stages chunk by chunk, FleetIpStage.)
+// forecast of every record before it is stepped (fcst), the window every record is remembered in and the lineage launch behind it
+// (ring) -- with that rider's inputs and what it brings back.  (hist is cssm_fleet_interpolate's own launch: it stages chunk by chunk,
+// FleetIpStage.)
 struct FleetRide {
   FleetKind kind = FleetKind::plain;
   bool step = false;                 // ival / fcst: one row per series (cssm_fleet_step_*), not T_k + 1 / T_k rows per series
@@ -438,6 +469,10 @@ struct FleetRide {
   FleetIvOut ivo{};                  // ival, step: the caller's arrays (the entries of a series that is inactive, has no cloud or fails are not written)
   FleetFcOut fco{};                  // fcst, step: ...
   int* fc_rc_out = nullptr;
+  const uint32_t* lag = nullptr;     // ring: the caller's [S], or null = max_lag for every series
+  uint32_t max_lag = 0;
+  uint32_t* rows_out = nullptr;
+  size_t win_Q = 0, win_L = 0;       // ring: the series that ask for rows; the rows a request holds on the device (min(max_lag + 1, slices))
   FleetStage st;                     // the launch's layout (fleet_ensure)
   std::vector<double> out;           // ival / fcst: the rows as the device left them; NaN where no block wrote
   std::vector<int32_t> pit;          // fcst: ... -1 where no block wrote
@@ -469,6 +504,13 @@ static int fleet_ensure(cssm_fleet* f, size_t R, FleetRide& ride) {
     st.rows = ride.step ? S : R;
     st.out_doubles = st.rows * (d + 2) * 3u;
     st.rows_bytes = st.out_doubles * 8u + st.rows * 8u;
+  } else if (st.kind == FleetKind::ring) {
+    st.w_base = st.ride + fleet_pad8(R * 4u); st.w_req = st.w_base + fleet_pad8(S * 4u);
+    st.w_words = st.w_req + ride.win_Q * sizeof(FleetWinReq); st.w_fco = st.w_words + fleet_pad8(ride.win_Q * ride.win_L * 4u);
+    st.bytes = st.w_fco + ride.win_Q * ride.win_L * d * 8u;
+    st.rows = ride.win_Q * ride.win_L;
+    st.out_doubles = st.rows * (d + 1) * 3u;
+    st.rows_bytes = st.out_doubles * 8u;
   }
   if (!f->h_stage.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet: %zu bytes of pinned staging", st.bytes);
   if (!f->d_stage.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet: %zu bytes of records", st.bytes);
@@ -512,9 +554,15 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
   if (rc) return rc;
   const FleetStage& st = ride.st;
   const size_t R = st.R, n_last = (size_t)f->S * f->d;
-  const bool path = st.kind == FleetKind::path, ival = st.kind == FleetKind::ival, fcst = st.kind == FleetKind::fcst;
+  const bool path = st.kind == FleetKind::path, ival = st.kind == FleetKind::ival, fcst = st.kind == FleetKind::fcst, ring = st.kind == FleetKind::ring;
   if (!f->d_rows.reserve(st.rows_bytes, true))
-    return fail(CSSM_ENOMEM, "fleet: %zu bytes of %s", st.rows_bytes, path ? "sampled paths" : ival ? "filtered intervals" : "one-step-ahead forecasts");
+    return fail(CSSM_ENOMEM, "fleet: %zu bytes of %s", st.rows_bytes,
+                path ? "sampled paths" : ival ? "filtered intervals" : ring ? "fixed-lag rows" : "one-step-ahead forecasts");
+  if (!ring) {   // the cloud of every series this launch runs is written outside its window
+    const FleetStageView hv = fleet_view(st, f->h_stage);
+    for (uint32_t k = 0; k < f->S; ++k)
+      if (hv.off[k + 1] > hv.off[k] || (hv.ctl[k] & CSSM_FLEET_CTL_INIT)) fleet_win_drop(f, k);
+  }
   if (fcst && (rc = fleet_fc_scratch(f))) return rc;
   HIP_TRY(hipEventRecord(f->ev[EV_CALL_BEGIN], f->stream));
   HIP_TRY(hipMemcpyAsync(f->d_stage.p, f->h_stage.p, st.bytes, hipMemcpyHostToDevice, f->stream));
@@ -548,8 +596,30 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
     l.args.fc.out = rows; l.args.fc.pit = f->d_rows.at<int32_t>(st.out_doubles * 8u);
     ride.pit.resize(st.rows * 2u);
   }
+  if (ring) {
+    l.args.ring.x = f->win.at<double>(); l.args.ring.a = f->win.at<uint32_t>((size_t)f->S * f->win_slices * f->d * f->n * 8u);
+    l.args.ring.slot = dv.w_slot; l.args.ring.base = dv.w_base; l.args.ring.slices = f->win_slices;
+    ride.out.resize(st.out_doubles);
+    HIP_TRY(hipEventRecord(f->ev_win[0], f->stream));
+  }
   rc = fleet_series_launch(f->d, l);
   if (rc) return rc;
+  if (ring) {   // the lineage launch: every block reads only what the forward launch finished
+    HIP_TRY(hipEventRecord(f->ev_win[1], f->stream));
+    if (ride.win_Q) {
+      const FleetRanks r = fleet_ranks(f->n, ride.interval);
+      FleetWinLaunch q;
+      q.args.n = f->n; q.args.np2 = r.np2; q.args.slices = f->win_slices; q.args.L = (uint32_t)ride.win_L;
+      q.args.ring_x = l.args.ring.x; q.args.ring_a = l.args.ring.a;
+      q.args.req = dv.w_req; q.args.words = dv.w_words; q.args.ser = l.args.ser; q.args.fco = dv.w_fco; q.args.out = rows;
+      q.args.mk = f->base.mk;
+      q.args.lo_state = r.rk.lo_state; q.args.hi_state = r.rk.hi_state; q.args.lo_eta = r.rk.lo_eta; q.args.hi_eta = r.rk.hi_eta;
+      q.d = f->d; q.n_req = (uint32_t)ride.win_Q; q.stream = f->stream;
+      const int hrc = cssm_fleet_window_launch(q);
+      if (hrc) return fail(CSSM_EHIP, "k_fleet_window: %s", hipGetErrorString((hipError_t)hrc));
+      HIP_TRY(hipEventRecord(f->ev_win[2], f->stream));
+    }
+  }
   if (path) HIP_TRY(hipEventRecord(f->ev[EV_PATH_KERNEL_END], f->stream));
   HIP_TRY(hipMemcpyAsync(f->h_ser.data(), f->ser.p, (size_t)f->S * sizeof(FleetSeries), hipMemcpyDeviceToHost, f->stream));
   if (path && ride.path_out) HIP_TRY(hipMemcpyAsync(ride.path_out, rows + n_last, st.rows_bytes - n_last * 8, hipMemcpyDeviceToHost, f->stream));
@@ -564,6 +634,12 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
   if (path) {
     if (hipEventElapsedTime(&f->ms_upload, f->ev[EV_CALL_BEGIN], f->ev[EV_PATH_UPLOADED]) != hipSuccess) f->ms_upload = -1.f;
     if (hipEventElapsedTime(&f->ms_kernel, f->ev[EV_PATH_UPLOADED], f->ev[EV_PATH_KERNEL_END]) != hipSuccess) f->ms_kernel = -1.f;
+  }
+  if (ring) {
+    float m0 = -1.f, m1 = 0.f;
+    if (hipEventElapsedTime(&m0, f->ev_win[0], f->ev_win[1]) != hipSuccess) m0 = -1.f;
+    if (ride.win_Q && hipEventElapsedTime(&m1, f->ev_win[1], f->ev_win[2]) != hipSuccess) m1 = -1.f;
+    f->ms_win[0] = (double)m0; f->ms_win[1] = (double)m1; f->win_ran = true;
   }
   return CSSM_OK;
 }
@@ -836,7 +912,9 @@ extern "C" int cssm_fleet_init(cssm_fleet* f, const double* t0) {
 }
 
 // stepFilter of the active series, one record each, with the call's rider: ival (cssm_fleet_step_intervals) -- the same launch also
-// writes getIntervals of every cloud it moved; fcst (cssm_fleet_step_forecast) -- and forecasts every record before it is stepped
+// writes getIntervals of every cloud it moved; fcst (cssm_fleet_step_forecast) -- and forecasts every record before it is stepped; ring
+// (cssm_fleet_step_interpolate) -- remembers every cloud it moved in the series' window, and a second launch summarises the last rows of
+// the series that ask through the lineages that survive to that cloud
 static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
                           double* ll_out, int32_t* ess_out, int* rc_out, FleetRide& ride) {
   const uint32_t S = f->S;
@@ -846,13 +924,19 @@ static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t,
   if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
   HIP_TRY(hipSetDevice(f->device));
   auto runs = [&](uint32_t k) { return (!active || active[k]) && f->live[k]; };
+  const bool ival = ride.kind == FleetKind::ival, fcst = ride.kind == FleetKind::fcst, ring = ride.kind == FleetKind::ring;
+  const uint32_t W = f->win_slices;
+  auto lag_of = [&](uint32_t k) { return ride.lag ? ride.lag[k] : ride.max_lag; };
   size_t R = 0;
-  for (uint32_t k = 0; k < S; ++k) R += runs(k) ? 1u : 0u;
+  for (uint32_t k = 0; k < S; ++k) {
+    R += runs(k) ? 1u : 0u;
+    if (ring && runs(k) && lag_of(k) != CSSM_FLEET_NO_ROWS) ride.win_Q += 1u;
+  }
+  if (ring) ride.win_L = std::min<size_t>((size_t)ride.max_lag + 1u, W);   // (a window never returns more rows than it has slots)
   ride.step = true;
   int rc = fleet_ensure(f, R, ride);
   if (rc) return rc;
   const FleetStageView h = fleet_view(ride.st, f->h_stage);
-  const bool ival = ride.kind == FleetKind::ival, fcst = ride.kind == FleetKind::fcst;
   h.off[0] = 0;
   for (uint32_t k = 0; k < S; ++k) { h.ctl[k] = 0u; h.off[k + 1] = h.off[k] + (runs(k) ? 1u : 0u); }
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
@@ -866,20 +950,81 @@ static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t,
       if (runs(k)) fleet_fc_record(f, ride, h, k, (size_t)h.off[k], k, f->step[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1);
   }
   if (ival) memset(h.fco0, 0, (size_t)S * d * 8u);   // (no launch of a step draws a cloud: the f coefficients of a t0 are not read)
+  std::vector<uint32_t> w_req_of;                    // ring: series k's request, or none
+  if (ring) {
+    // the ring arithmetic, here and nowhere else: a window that is not continuous restarts at slot 0 with the cloud the series holds now
+    // as its base slice (F at the series' clock, no ancestors); the record's slot is the one behind the newest, modulo the slices.  What
+    // is noted per slot is noted now (a series that fails loses its window anyway); head / depth move once the launch has succeeded.
+    w_req_of.assign(S, CSSM_FLEET_NO_ROWS);
+    const size_t L = ride.win_L;
+    size_t q = 0;
+    for (uint32_t k = 0; k < S; ++k) {
+      h.w_base[k] = 0u;
+      if (!runs(k)) continue;
+      const size_t r = (size_t)h.off[k], w0 = (size_t)k * W;
+      const bool restart = !f->win_on[k];
+      const uint32_t head = restart ? 0u : f->win_head[k], depth = restart ? 0u : f->win_depth[k];
+      const uint32_t slot = (head + 1u) % W, depth1 = std::min(depth + 1u, W - 1u);
+      if (restart) {
+        h.ctl[k] |= CSSM_FLEET_CTL_BASE;
+        StepRec r0;
+        cssm_build_rec(&f->models[k], f->t[k], f->t[k], 0.0, 0, 0u, &r0);   // F at the base slice's time
+        for (int c = 0; c < d; ++c) f->win_fco[w0 * d + c] = r0.fco[c];
+        f->win_res[w0] = 0;
+      }
+      h.w_slot[r] = slot;
+      const double* fco = fleet_rec_fco(h, d, r);
+      for (int c = 0; c < d; ++c) f->win_fco[(w0 + slot) * d + c] = fco[c];
+      f->win_res[w0 + slot] = (has_obs ? has_obs[k] : 1) ? 1 : 0;
+      const uint32_t lg = lag_of(k);
+      if (lg == CSSM_FLEET_NO_ROWS) continue;
+      const uint32_t nrows = std::min(lg, depth1) + 1u;       // <= slices: L holds them
+      w_req_of[k] = (uint32_t)q;
+      h.w_req[q] = FleetWinReq{k, nrows};
+      for (uint32_t j = 0; j < (uint32_t)L; ++j) {
+        const uint32_t sj = (slot + W - (j % W)) % W;           // (rows beyond nrows are not walked: their words only travel)
+        h.w_words[q * L + j] = j < nrows ? (sj | (f->win_res[w0 + sj] ? CSSM_FLEET_WIN_RESAMPLED : 0u)) : 0u;
+        for (int c = 0; c < d; ++c) h.w_fco[(q * L + j) * d + c] = j < nrows ? f->win_fco[(w0 + sj) * d + c] : 0.0;
+      }
+      ++q;
+    }
+    if (R & 1u) h.w_slot[R] = 0u;                              // (the padding travels too)
+    if (S & 1u) h.w_base[S] = 0u;
+    if ((ride.win_Q * L) & 1u) h.w_words[ride.win_Q * L] = 0u;
+  }
   rc = fleet_launch(f, ride, nullptr, nullptr);
-  if (rc) return rc;
+  if (rc) {
+    if (ring) for (uint32_t k = 0; k < S; ++k) if (runs(k)) fleet_win_drop(f, k);
+    return rc;
+  }
   for (uint32_t k = 0; k < S; ++k) {
     if (ride.fc_rc_out) ride.fc_rc_out[k] = ride.fc_rc[k];
     if (active && !active[k]) { rc_out[k] = CSSM_OK; continue; }            // untouched
     if (!f->live[k]) { rc_out[k] = CSSM_ESTATE; continue; }                 // no cloud: never initialised, or failed since
     const FleetSeries& s = f->h_ser[k];
-    if (s.err) { rc_out[k] = CSSM_ENONFINITE; f->live[k] = 0; continue; }
+    if (s.err) { rc_out[k] = CSSM_ENONFINITE; f->live[k] = 0; fleet_win_drop(f, k); continue; }
     rc_out[k] = CSSM_OK; f->t[k] = t[k]; f->step[k] += 1u;
     if (ll_out) ll_out[k] = s.ll;
     if (ess_out) ess_out[k] = s.ess;
     const size_t r = (size_t)h.off[k];
     if (ival) fleet_iv_row(f, k, ride.out.data() + (size_t)k * (d + 1) * 3u, fleet_rec_fco(h, d, r), true, ride.ivo, k);
     if (fcst) fleet_fc_row(d, ride.out.data() + (size_t)k * (d + 2) * 3u, ride.pit.data() + 2 * (size_t)k, (h.flags[r] & CSSM_FLEET_FC_ON) != 0u, ride.fco, k);
+    if (ring) {
+      const bool restart = !f->win_on[k];
+      f->win_head[k] = ((restart ? 0u : f->win_head[k]) + 1u) % W;
+      f->win_depth[k] = std::min((restart ? 0u : f->win_depth[k]) + 1u, W - 1u);
+      f->win_on[k] = 1;
+      const uint32_t q = w_req_of[k];
+      const uint32_t nrows = q == CSSM_FLEET_NO_ROWS ? 0u : h.w_req[q].rows;
+      if (ride.rows_out) ride.rows_out[k] = nrows;
+      if (q == CSSM_FLEET_NO_ROWS) continue;                   // stepped and remembered, not summarised: nothing of its rows is written
+      const size_t L = ride.win_L, Lc = (size_t)ride.max_lag + 1u;
+      for (size_t j = 0; j < Lc; ++j) {
+        const bool ok = j < nrows;
+        const size_t at = q * L + (ok ? j : 0u);
+        fleet_iv_row(f, k, ride.out.data() + at * (size_t)(d + 1) * 3u, h.w_fco + at * d, ok, ride.ivo, (size_t)k * Lc + j);
+      }
+    }
   }
   if (!ride.scale_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", ride.scale_msg.c_str());   // (the call succeeds)
   return CSSM_OK;
@@ -921,6 +1066,64 @@ extern "C" int cssm_fleet_step_forecast(cssm_fleet* f, const uint8_t* active, co
   ride.kind = FleetKind::fcst; ride.interval = interval; ride.keys = keys; ride.fc_rc_out = fc_rc_out;
   ride.fco = FleetFcOut{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal};
   return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, ride);
+}
+
+// The window cssm_fleet_step_interpolate remembers in: `slices` slots per series, a cloud and its ancestors each -- S x slices x N x
+// (8 d + 4) bytes.  Every window restarts.
+extern "C" int cssm_fleet_window(cssm_fleet* f, uint32_t slices) {
+  if (slices == 1u) return fail(CSSM_EINVAL_ARG, "a window of 1 slice remembers no record behind its base slice: slices is 0 (no window) or at least 2");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  HIP_TRY(hipSetDevice(f->device));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  f->win.release();
+  f->win_slices = 0;
+  f->win_on.clear(); f->win_res.clear(); f->win_head.clear(); f->win_depth.clear(); f->win_fco.clear();
+  if (slices == 0u) return CSSM_OK;
+  const size_t per = (size_t)f->S * f->n * (8u * (size_t)f->d + 4u);
+  if (slices > 0x7fffffffu || (size_t)slices > (~(size_t)0) / per)
+    return fail(CSSM_ENOMEM, "fleet window: %u slices of %zu bytes each do not fit any memory", slices, per);
+  const size_t bytes = per * slices;
+  if (!f->win.reserve(bytes, false)) {
+    (void)hipGetLastError();   // (the fleet goes on without a window)
+    return fail(CSSM_ENOMEM, "fleet window: %zu bytes of history (S x slices x N x (8 d + 4) = %u x %u x %u x %d) do not fit the device", bytes, f->S,
+                slices, f->n, 8 * f->d + 4);
+  }
+  const size_t slots = (size_t)f->S * slices;
+  f->win_on.assign(f->S, 0); f->win_head.assign(f->S, 0u); f->win_depth.assign(f->S, 0u);
+  f->win_res.assign(slots, 0); f->win_fco.assign(slots * (size_t)f->d, 0.0);
+  f->win_slices = slices;
+  return CSSM_OK;
+}
+
+extern "C" uint32_t cssm_fleet_window_depth(const cssm_fleet* f, uint32_t k) { return (f && k < f->S && f->win_slices) ? f->win_depth[k] : 0u; }
+
+// FilterInterpolate as the stream it is (ParticleFilter.interpolate, model/ParticleFilter.scala:281-310; one stepInterpolate per
+// observation): cssm_fleet_step -- the same arguments, bits and statuses -- which also remembers every cloud it moved and its ancestors in
+// the series' window, and a second launch that summarises, for the series that ask, the last lag + 1 time indices through the lineages
+// that survive to the cloud just written.  What needs no fleet is refused first, so that it is refused on any host.
+extern "C" int cssm_fleet_step_interpolate(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                                           const uint32_t* lag, uint32_t max_lag, double interval, double* ll_out, int32_t* ess_out,
+                                           uint32_t* rows_out, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
+                                           double* eta_lower, double* eta_upper, int* rc_out) {
+  if (!t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument (t, y, rc_out)");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (max_lag == CSSM_FLEET_NO_ROWS) return fail(CSSM_EINVAL_ARG, "max_lag = %u is CSSM_FLEET_NO_ROWS, not a lag", max_lag);
+  for (uint32_t k = 0; lag && k < (f ? f->S : 1u); ++k)   // (a fleet has one series at least: lag[0] can be looked at without one)
+    if (lag[k] > max_lag && lag[k] != CSSM_FLEET_NO_ROWS)
+      return fail(CSSM_EINVAL_ARG, "lag[%u] = %u is above max_lag = %u (CSSM_FLEET_NO_ROWS asks for no rows)", k, lag[k], max_lag);
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  if (!f->win_slices) return fail(CSSM_ESTATE, "the fleet has no window to remember in (cssm_fleet_window first)");
+  FleetRide ride;
+  ride.kind = FleetKind::ring; ride.interval = interval; ride.lag = lag; ride.max_lag = max_lag; ride.rows_out = rows_out;
+  ride.ivo = FleetIvOut{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, ride);
+}
+
+extern "C" int cssm_fleet_step_interpolate_last_ms(cssm_fleet* f, double* ms2) {
+  if (!f || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (!f->win_ran) return fail(CSSM_ESTATE, "no streaming interpolation has run on this fleet (cssm_fleet_step_interpolate first)");
+  ms2[0] = f->ms_win[0]; ms2[1] = f->ms_win[1];
+  return CSSM_OK;
 }
 
 // cssm_fleet_summary as staged in d_sm: [S][d] f coefficients | [S][d + 1][3] results | [S] buffer numbers (u32, padded to 8 bytes)

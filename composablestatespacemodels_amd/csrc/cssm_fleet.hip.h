@@ -42,6 +42,18 @@ struct FleetSeries {
 };
 
 #define CSSM_FLEET_CTL_INIT 1u   /* draw the initial cloud before the series' first record of this launch */
+#define CSSM_FLEET_CTL_BASE 2u   /* (RING) the series' window restarts: its first record of this launch also keeps the cloud it gathers */
+
+// The window of cssm_fleet_step_interpolate (k_fleet_series<D, false, false, false, false, true> writes it, k_fleet_window reads it):
+// per series `slices` clouds ([d][n] doubles each) and as many ancestor arrays ([n] each).  The host does the ring arithmetic: a kernel
+// only ever sees slot numbers below `slices`.
+struct FleetRing {
+  double* x;                         // [S][slices][d][n]
+  uint32_t* a;                       // [S][slices][n]
+  const uint32_t* slot;              // per record of the launch: the slot that keeps the cloud the record writes and its ancestors
+  const uint32_t* base;              // [S]: (CSSM_FLEET_CTL_BASE) the slot that keeps the cloud before the series' first record
+  uint32_t slices;
+};
 
 struct FleetArgs {
   uint32_t n;                        // particles per series
@@ -83,6 +95,9 @@ struct FleetArgs {
   // cssm_fleet_filter_forecasts / cssm_fleet_step_forecast; model/ParticleFilter.scala:368-409 over a filter stream), behind every field
   // the other instantiations read.  It takes iv_np2, iv_rk and iv_rows (1: the row of a record is its series' number) as IVAL does.
   FleetOneStep fc;
+  // the window of cssm_fleet_step_interpolate (k_fleet_series<D, false, false, false, false, true> only), behind every field the other
+  // instantiations read
+  FleetRing ring;
 };
 
 // a - b mod 2^128 (integers: exact)
@@ -124,7 +139,13 @@ __device__ __forceinline__ void fleet_path_row(const double* buf, const uint32_t
 // coefficients under the record's forecast key, into the record's destination buffer, which step 1 overwrites afterwards.  The keys of a
 // row live where the weights were, as under IVAL (dead between a record's resampling and the next record's weighing).  A template flag
 // once more: the other four instantiations hold no trace of it.
-template <int D, bool PATH, bool HIST = false, bool IVAL = false, bool FCST = false>
+// RING: stepFilter that also remembers (FleetArgs::ring, cssm_fleet_step_interpolate) -- the cloud a record writes goes to the record's
+// slot of the series' window as well as to its destination buffer, and behind the resampling (behind the None branch: with the
+// identity) the ancestors go to the slot's ancestor slice; a series whose window restarts (CSSM_FLEET_CTL_BASE) keeps the cloud its first
+// record gathers, not yet propagated, in its base slot.  The two cloud copies are loops of their own around step 1, which stays the
+// plain launch's statement for statement.  state / anc / ser ping-pong as in the plain launch.  A template flag as the
+// others: the other five instantiations hold no trace of it.
+template <int D, bool PATH, bool HIST = false, bool IVAL = false, bool FCST = false, bool RING = false>
 __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_series(const FleetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   __shared__ StepRec s_rec;
@@ -209,6 +230,20 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
                                   a.fc.out + row * (D + 2) * 3u, a.fc.pit + row * 2u);
       }
     }
+    // (RING) the record's slot of the series' window, and the base slot of a window that restarts at this record
+    double* ring_x = nullptr; uint32_t* ring_a = nullptr; double* ring_b = nullptr;
+    if constexpr (RING) {
+      const size_t w0 = (size_t)k * a.ring.slices, sl = w0 + a.ring.slot[r];
+      ring_x = a.ring.x + sl * D * n; ring_a = a.ring.a + sl * n;
+      if (r == r0 && (ctl & CSSM_FLEET_CTL_BASE)) ring_b = a.ring.x + (w0 + a.ring.base[k]) * D * n;
+      if (ring_b) {                                             // (uniform) X[anc[i]], not yet propagated: what cssm_fleet_get_particles returns
+        for (uint32_t i = tid; i < n; i += bs) {
+          const uint32_t j = s_anc[i];
+#pragma unroll
+          for (int c = 0; c < D; ++c) ring_b[(size_t)c * n + i] = src[(size_t)c * n + j];
+        }
+      }
+    }
     // 1. gather through the previous ancestors, transition, f, log-density (:118, :123)
     double tmax = -cssm_inf();
     bool bad = false;
@@ -227,9 +262,18 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
         s_lw[i] = lw;
       }
     }
+    if constexpr (RING) {                                       // the cloud this record wrote, into its slot: a thread copies the particles it wrote itself
+      for (uint32_t i = tid; i < n; i += bs) {
+#pragma unroll
+        for (int c = 0; c < D; ++c) ring_x[(size_t)c * n + i] = dst[(size_t)c * n + i];
+      }
+    }
     if (!weighted) {                                            // (uniform) the None branch (:121): the cloud moves, nothing else
       __syncthreads();
-      for (uint32_t i = tid; i < n; i += bs) s_anc[i] = i;
+      for (uint32_t i = tid; i < n; i += bs) {
+        s_anc[i] = i;
+        if constexpr (RING) ring_a[i] = i;
+      }
       if (!HIST && tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
       if (IVAL) {                                               // the cloud this record moved, through identity ancestors
         __syncthreads();
@@ -305,6 +349,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
         carry = (v > carry) ? v : carry;
         s_anc[s] = carry;
         if (HIST) hslice[s] = carry;
+        if constexpr (RING) ring_a[s] = carry;
       }
     }
     if (!HIST && tid == 0) { a.ll_t[r] = ll; a.ess_t[r] = ess; }
@@ -328,8 +373,9 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.ser[k] = o; }
 }
 
-// which k_fleet_series a launch runs: <D, false> | <D, true> | <D, false, true> | <D, false, false, true> | <D, false, false, false, true>
-enum class FleetKind : int { plain, path, hist, ival, fcst };
+// which k_fleet_series a launch runs: <D, false> | <D, true> | <D, false, true> | <D, false, false, true> | <D, false, false, false, true> |
+// <D, false, false, false, false, true>
+enum class FleetKind : int { plain, path, hist, ival, fcst, ring };
 struct FleetLaunch {
   FleetArgs args;
   uint32_t n_series;    // blocks; hist: the series args.k0 .. args.k0 + n_series - 1

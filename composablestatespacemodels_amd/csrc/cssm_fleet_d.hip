@@ -19,6 +19,7 @@ int CSSM_FLEET_NAME(CSSM_FLEET_D)(const FleetLaunch& l) {
     case FleetKind::hist: CSSM_FLEET_RUN(false, true); break;
     case FleetKind::path: CSSM_FLEET_RUN(true); break;
     case FleetKind::plain: CSSM_FLEET_RUN(false); break;
+    case FleetKind::ring: CSSM_FLEET_RUN(false, false, false, false, true); break;
   }
 #undef CSSM_FLEET_RUN
   return (int)hipGetLastError();

@@ -8,7 +8,8 @@
 // One block per (series, row), 256 threads.  Each of the d + 1 blocks of a series composes b itself (N loads of ancestors per time
 // index), so no block reads what another one wrote: no atomics on global memory, no flag, every loop bounded by N or by T_k.  A
 // thread owns the same slots i = tid, tid + 256, ... of b in every phase, so the composition and the gather need no barrier of their
-// own.  The row summary is k_fleet_summary's statement: the values as order-preserving keys, a bitonic network over the next power
+// own.  cssm_fleet_step_interpolate's k_fleet_window walks the slots of a series' window with the same body (fleet_lineage_body: the two
+// differ in where their slices lie).  The row summary is k_fleet_summary's statement: the values as order-preserving keys, a bitonic network over the next power
 // of two in LDS (padded with the largest key), the mean a plain fp64 sum.  It is stated here a third time (k_fleet_summary,
 // fleet_forecast_body): one __device__ function for the three is held back until the resource report of the two existing kernels can
 // be compared with it in place.
@@ -20,29 +21,52 @@
 #include "cssm_kernels.hip.h"
 #include "cssm_fleet_interp.hip.h"
 
+// Where the slices a block walks lie -- newest first -- and where each one's row goes: the whole history of a series
+// (cssm_fleet_interpolate) or the window of one (cssm_fleet_step_interpolate).  Step j of `steps`: cloud(j) / anc(j) the slice,
+// resampled(j) whether its ancestors exist (the slice was written by a weighted record), fco(j) F at its time, out(j) its [d + 1][3].
 template <int D>
-__global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_lineage(const FleetLinArgs a) {
-  extern __shared__ unsigned long long s_keys[];
-  __shared__ double s_p[CSSM_BLOCK / 64];
-  const uint32_t n = a.n, np2 = a.np2, k = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
-  uint32_t* s_b = reinterpret_cast<uint32_t*>(s_keys + np2);
-  const unsigned long long r0 = a.off[k], r1 = a.off[k + 1];
-  const uint32_t T = (uint32_t)(r1 - r0);
-  const size_t base = (size_t)r0 + k;                           // the series' first slice and first output row
-  if (T == 0u || a.ser[k].err != 0u) {                          // (uniform) no records, or unusable weights: every row reads NaN
-    for (uint32_t o = 0; o <= T; ++o)
-      if (tid < 3u) a.out[((base + o) * (D + 1) + row) * 3u + tid] = cssm_nan();
-    return;
+struct FleetLinHist {                                           // slices base .. base + T of hist / hanc, output row o = s or T - s
+  const FleetLinArgs& a;
+  size_t base; unsigned long long r0; uint32_t T;
+  __device__ __forceinline__ uint32_t slice(uint32_t j) const { return T - j; }
+  __device__ __forceinline__ uint32_t row(uint32_t j) const { return a.pairing ? j : T - j; }
+  __device__ __forceinline__ bool resampled(uint32_t j) const {
+    const uint32_t s = slice(j);
+    return s >= 1u && reinterpret_cast<const FleetRecHead*>(a.recs + ((size_t)r0 + s - 1u) * (uint32_t)CSSM_FLEET_REC_BYTES(D))->has_obs != 0;
   }
-  constexpr uint32_t RB = (uint32_t)CSSM_FLEET_REC_BYTES(D);
+  __device__ __forceinline__ const uint32_t* anc(uint32_t j) const { return a.hanc + (base + slice(j)) * a.n; }
+  __device__ __forceinline__ const double* cloud(uint32_t j) const { return a.hist + (base + slice(j)) * D * a.n; }
+  __device__ __forceinline__ const double* fco(uint32_t j) const { return a.fco + (base + row(j)) * D; }
+  __device__ __forceinline__ double* out(uint32_t j) const { return a.out + (base + row(j)) * (D + 1) * 3u; }
+};
+template <int D>
+struct FleetLinWindow {                                         // request q: the slots words[j] of series k's window, output row q L + j
+  const FleetWinArgs& a;
+  uint32_t k, q;
+  __device__ __forceinline__ uint32_t word(uint32_t j) const { return a.words[(size_t)q * a.L + j]; }
+  __device__ __forceinline__ size_t slot(uint32_t j) const { return (size_t)k * a.slices + (word(j) & ~CSSM_FLEET_WIN_RESAMPLED); }
+  __device__ __forceinline__ bool resampled(uint32_t j) const { return (word(j) & CSSM_FLEET_WIN_RESAMPLED) != 0u; }
+  __device__ __forceinline__ const uint32_t* anc(uint32_t j) const { return a.ring_a + slot(j) * a.n; }
+  __device__ __forceinline__ const double* cloud(uint32_t j) const { return a.ring_x + slot(j) * D * a.n; }
+  __device__ __forceinline__ const double* fco(uint32_t j) const { return a.fco + ((size_t)q * a.L + j) * D; }
+  __device__ __forceinline__ double* out(uint32_t j) const { return a.out + ((size_t)q * a.L + j) * (D + 1) * 3u; }
+};
+
+// The lineages that survive to the newest slice, summarised slice by slice going back: b = the identity; per slice b = anc[b] where the
+// slice resampled, then row `row` of the slice's cloud through b -- keys, bitonic sort over np2, the mean (slots tid + 256 q per
+// thread, the xor-shuffle tree, the wave partials added in wave order).
+template <int D, class Src>
+__device__ __forceinline__ void fleet_lineage_body(const Src& src_of, uint32_t steps, uint32_t n, uint32_t np2, uint32_t row, const ModelK& mk,
+                                                   uint32_t lo_state, uint32_t hi_state, uint32_t lo_eta, uint32_t hi_eta,
+                                                   unsigned long long* s_keys, uint32_t* s_b, double* s_p) {
+  const uint32_t tid = threadIdx.x;
   for (uint32_t i = tid; i < n; i += CSSM_BLOCK) s_b[i] = i;
-  for (uint32_t s = T + 1u; s-- > 0u;) {                        // bounded by the series' length
+  for (uint32_t st = 0; st < steps; ++st) {                     // bounded by the series' length / the window's
     __syncthreads();                                            // the row sorted last is read; s_p is free
-    const bool resampled = s >= 1u && reinterpret_cast<const FleetRecHead*>(a.recs + ((size_t)r0 + s - 1u) * RB)->has_obs != 0;
-    const uint32_t* ga = a.hanc + (base + s) * n;
-    const double* src = a.hist + (base + s) * D * n;
-    const uint32_t o = a.pairing ? T - s : s;
-    const double* fco = a.fco + (base + o) * D;
+    const bool resampled = src_of.resampled(st);
+    const uint32_t* ga = src_of.anc(st);
+    const double* src = src_of.cloud(st);
+    const double* fco = src_of.fco(st);
     double acc = 0.0;
     for (uint32_t i = tid; i < np2; i += CSSM_BLOCK) {
       unsigned long long key = ~0ull;
@@ -56,7 +80,7 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_lineage(const FleetLinArgs
           double x[D];
 #pragma unroll
           for (int q = 0; q < D; ++q) x[q] = src[(size_t)q * n + j];
-          v = link_of(a.mk.obs_kind, gamma_coef<D>(a.mk, fco, x));
+          v = link_of(mk.obs_kind, gamma_coef<D>(mk, fco, x));
         }
         acc += v;
         key = cssm_order_key(v);
@@ -83,16 +107,52 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_lineage(const FleetLinArgs
     if (tid == 0) {
       double sum = 0.0;
       for (int w = 0; w < CSSM_BLOCK / 64; ++w) sum += s_p[w];
-      double* out = a.out + ((base + o) * (D + 1) + row) * 3u;
+      double* out = src_of.out(st) + (size_t)row * 3u;
       out[0] = sum / (double)n;
-      out[1] = cssm_order_unkey(s_keys[row < (uint32_t)D ? a.lo_state : a.lo_eta]);
-      out[2] = cssm_order_unkey(s_keys[row < (uint32_t)D ? a.hi_state : a.hi_eta]);
+      out[1] = cssm_order_unkey(s_keys[row < (uint32_t)D ? lo_state : lo_eta]);
+      out[2] = cssm_order_unkey(s_keys[row < (uint32_t)D ? hi_state : hi_eta]);
     }
   }
+}
+
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_lineage(const FleetLinArgs a) {
+  extern __shared__ unsigned long long s_keys[];
+  __shared__ double s_p[CSSM_BLOCK / 64];
+  const uint32_t n = a.n, np2 = a.np2, k = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
+  uint32_t* s_b = reinterpret_cast<uint32_t*>(s_keys + np2);
+  const unsigned long long r0 = a.off[k], r1 = a.off[k + 1];
+  const uint32_t T = (uint32_t)(r1 - r0);
+  const size_t base = (size_t)r0 + k;                           // the series' first slice and first output row
+  if (T == 0u || a.ser[k].err != 0u) {                          // (uniform) no records, or unusable weights: every row reads NaN
+    for (uint32_t o = 0; o <= T; ++o)
+      if (tid < 3u) a.out[((base + o) * (D + 1) + row) * 3u + tid] = cssm_nan();
+    return;
+  }
+  fleet_lineage_body<D>(FleetLinHist<D>{a, base, r0, T}, T + 1u, n, np2, row, a.mk, a.lo_state, a.hi_state, a.lo_eta, a.hi_eta, s_keys, s_b, s_p);
+}
+
+// cssm_fleet_step_interpolate's second launch: one block per (series that asked for rows, row), over the slots of the series' window
+// the host named, newest first.  A series the forward launch gave up leaves its rows as they were preset (NaN).
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_window(const FleetWinArgs a) {
+  extern __shared__ unsigned long long s_keys[];
+  __shared__ double s_p[CSSM_BLOCK / 64];
+  const uint32_t q = blockIdx.x, row = blockIdx.y;
+  const FleetWinReq rq = a.req[q];
+  if (a.ser[rq.k].err != 0u) return;                            // (uniform)
+  uint32_t* s_b = reinterpret_cast<uint32_t*>(s_keys + a.np2);
+  fleet_lineage_body<D>(FleetLinWindow<D>{a, rq.k, q}, rq.rows, a.n, a.np2, row, a.mk, a.lo_state, a.hi_state, a.lo_eta, a.hi_eta, s_keys, s_b, s_p);
 }
 
 int cssm_fleet_lineage_launch(const FleetLinLaunch& l) {
   const size_t lds = (size_t)l.args.np2 * 8u + (size_t)l.args.n * 4u;
   DISPATCH_D(l.d, hipLaunchKernelGGL(k_fleet_lineage<D>, dim3(l.n_series, D + 1), dim3(CSSM_BLOCK), lds, l.stream, l.args));
+  return (int)hipGetLastError();
+}
+
+int cssm_fleet_window_launch(const FleetWinLaunch& l) {
+  const size_t lds = (size_t)l.args.np2 * 8u + (size_t)l.args.n * 4u;
+  DISPATCH_D(l.d, hipLaunchKernelGGL(k_fleet_window<D>, dim3(l.n_req, D + 1), dim3(CSSM_BLOCK), lds, l.stream, l.args));
   return (int)hipGetLastError();
 }

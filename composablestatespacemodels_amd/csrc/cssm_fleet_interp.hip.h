@@ -27,3 +27,32 @@ struct FleetLinLaunch {
   hipStream_t stream;
 };
 int cssm_fleet_lineage_launch(const FleetLinLaunch& l);
+
+// cssm_fleet_step_interpolate's lineage launch (k_fleet_window): blocks (q, row), request q of the call -- series req[q].k asked for
+// req[q].rows rows.  words[q][j], j < rows: the slot of the series' window that holds time index (newest - j), CSSM_FLEET_WIN_RESAMPLED set
+// where a weighted record wrote it (its ancestor slice is composed; the base slice and the slices of unweighted records are walked with
+// the identity).  fco[q][j][d]: F at that index's time.  out[q][j][d + 1][3], preset to NaN.
+#define CSSM_FLEET_WIN_RESAMPLED 0x80000000u
+struct FleetWinReq {
+  uint32_t k, rows;
+};
+struct FleetWinArgs {
+  uint32_t n, np2;
+  uint32_t slices, L;                // slots per series; rows per request in words / fco / out (max_lag + 1)
+  const double* ring_x;              // FleetRing::x / a as the forward launch left them
+  const uint32_t* ring_a;
+  const FleetWinReq* req;
+  const uint32_t* words;
+  const FleetSeries* ser;            // the fleet's [S]: err != 0 -- the forward launch gave the series up
+  const double* fco;
+  double* out;
+  ModelK mk;
+  uint32_t lo_state, hi_state, lo_eta, hi_eta;
+};
+struct FleetWinLaunch {
+  FleetWinArgs args;
+  int d;
+  uint32_t n_req;
+  hipStream_t stream;
+};
+int cssm_fleet_window_launch(const FleetWinLaunch& l);

@@ -677,6 +677,69 @@ class NativePfFleet:
                                                       _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu), _p(rc, C.POINTER(C.c_int))))
         return ll, ess, (m, lo, hi, em, el, eu), rc
 
+    def window(self, slices: int):
+        """cssm_fleet_window: remember, per series, the ``slices`` most recent clouds and ancestor arrays on the device (S x slices x N
+        x (8 d + 4) bytes) for ``step_interpolate``; 0 frees them.  Every window restarts."""
+        if int(slices) < 0:
+            raise ValueError("slices must not be negative")
+        _abi.check(self.lib.cssm_fleet_window(self._h, int(slices)))
+
+    def window_depth(self, k: int) -> int:
+        """The records remembered behind series k's base slice (cssm_fleet_window_depth): 0 .. slices - 1."""
+        return int(self.lib.cssm_fleet_window_depth(self._h, int(k)))
+
+    def _lags(self, lag, max_lag: int):
+        """``step_interpolate``'s ``lag`` as the C call takes it: None (every series max_lag), or uint32[S] with CSSM_FLEET_NO_ROWS where
+        an entry is None (a C-contiguous uint32 array is taken as it is).  Refused here, before any device call: a negative max_lag, a sequence of another length than S, a negative
+        entry."""
+        if int(max_lag) < 0 or int(max_lag) >= _abi.CSSM_FLEET_NO_ROWS:
+            raise ValueError("max_lag must be in 0 .. 2^32 - 2")
+        if lag is None:
+            return None
+        if np.ndim(lag) == 0:
+            lag = [lag] * self.S
+        if len(lag) != self.S:
+            raise ValueError(f"one lag per series ({self.S}), not {len(lag)}")
+        if isinstance(lag, np.ndarray) and lag.dtype == np.uint32 and lag.flags.c_contiguous:
+            return lag                                  # (as the C call takes it: a caller that streams builds it once)
+        if any(v is not None and int(v) < 0 for v in lag):
+            raise ValueError("a lag must not be negative (None asks for no rows)")
+        return np.ascontiguousarray([_abi.CSSM_FLEET_NO_ROWS if v is None else int(v) for v in lag], dtype=np.uint32)
+
+    def step_interpolate(self, t, y, has=None, active=None, lag=None, max_lag: int = 0, interval: float = 0.975):
+        """cssm_fleet_step_interpolate: ``step``, which also remembers every cloud it moved in the series' window, and (a second launch)
+        the fixed-lag interpolation of the series that ask: ``(ll[S], ess[S], rows_out[S], (state_mean[S, max_lag + 1, d], state_lower,
+        state_upper, eta_of_mean[S, max_lag + 1], eta_lower, eta_upper), rc[S])``.  Row j of series k summarises time index (newest - j)
+        through the lineages that survive to the cloud just written; ``rows_out[k]`` = min(lag_k, window_depth(k)) + 1 rows are filled,
+        the others read NaN.  ``lag``: None (max_lag for every series), an int, or one entry per series with None for "no rows"."""
+        t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+        if len(t) != self.S or len(y) != self.S:
+            raise ValueError("one (t, y) per series")
+        lg = self._lags(lag, max_lag)
+        hp = ap = None
+        if has is not None:
+            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
+        L = int(max_lag) + 1
+        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32); rc = np.zeros(self.S, dtype=np.int32)
+        rows = np.zeros(self.S, dtype=np.uint32)
+        m, lo, hi = (np.full((self.S, L, self.d), np.nan) for _ in range(3))
+        em, el, eu = (np.full((self.S, L), np.nan) for _ in range(3))
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_step_interpolate(self._h, ap, _p(t), _p(y), hp, None if lg is None else _p(lg, C.POINTER(C.c_uint32)),
+                                                        int(max_lag), float(interval), _p(ll), _p(ess, C.POINTER(C.c_int32)),
+                                                        _p(rows, C.POINTER(C.c_uint32)), _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu),
+                                                        _p(rc, C.POINTER(C.c_int))))
+        return ll, ess, rows, (m, lo, hi, em, el, eu), rc
+
+    def step_interpolate_last_ms(self) -> Tuple[float, float]:
+        """Device time (HIP events) of the last ``step_interpolate``'s forward launch and lineage launch, ms (the latter 0 when no
+        series asked for rows)."""
+        ms = np.zeros(2)
+        _abi.check(self.lib.cssm_fleet_step_interpolate_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1])
+
     def summary(self, interval: float = 0.975):
         """(state_mean[S, d], state_lower[S, d], state_upper[S, d], eta_of_mean[S], eta_lower[S], eta_upper[S])."""
         m, lo, hi = np.zeros((self.S, self.d)), np.zeros((self.S, self.d)), np.zeros((self.S, self.d))
@@ -1241,7 +1304,25 @@ class FilterFleet:
         ``ForecastOut`` at its datum's time under the series' default key -- None where ``ys[k]`` is None."""
         return self._step(states, ys, float(interval), forecast=True)
 
-    def _step(self, states, ys, interval: Optional[float], forecast: bool = False):
+    def window(self, slices: int):
+        """``NativePfFleet.window``: the device memory ``stepInterpolate`` remembers in (0 frees it)."""
+        self._fleet.window(slices)
+        self._win_hist = [[] for _ in range(self.S)]
+
+    def stepInterpolate(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]], lag,
+                        interval: float = 0.975) -> Tuple[List[FleetState], List[List[PfOut]]]:
+        """``FilterInterpolate``'s stream (``ParticleFilter.interpolate``, ParticleFilter.scala:281-310) per sensor: ``stepFilter``, and per
+        series the ``PfOut`` of its last ``lag + 1`` time indices through the paths that survive to this datum, oldest first as
+        ``interpolate`` returns them (fewer while the window holds fewer; an empty list where ``ys[k]`` is None).  ``lag``: an int, or
+        one entry per series with None for "no rows".  ``window(slices)`` first."""
+        if np.ndim(lag) == 0:
+            lag = [lag] * self.S
+        if len(lag) != self.S:
+            raise ValueError(f"one lag per series ({self.S}), not {len(lag)}")
+        max_lag = max([int(v) for v in lag if v is not None], default=0)
+        return self._step(states, ys, float(interval), lags=(list(lag), max_lag))
+
+    def _step(self, states, ys, interval: Optional[float], forecast: bool = False, lags=None):
         if len(states) != self.S or len(ys) != self.S:
             raise ValueError("one state and one (optional) observation per series")
         if any(s._owner is not self._fleet or s._generation != self._fleet.generation for s in states):
@@ -1250,7 +1331,13 @@ class FilterFleet:
         t = np.array([states[k].t if o is None else o.t for k, o in enumerate(ys)], dtype=np.float64)
         has = np.array([0 if (o is None or o.observation is None) else 1 for o in ys], dtype=np.uint8)
         y = np.array([o.observation if h else 0.0 for o, h in zip(ys, has)], dtype=np.float64)
-        if interval is None:
+        if lags is not None:
+            hist = getattr(self, "_win_hist", None) or [[] for _ in range(self.S)]
+            for k in range(self.S):                    # a window that restarts takes the state before this datum as its base slice
+                if act[k] and self._fleet.window_depth(k) == 0:
+                    hist[k] = [(states[k].t, states[k].observation)]
+            ll, ess, nrows, rows, rc = self._fleet.step_interpolate(t, y, has, act, lags[0], lags[1], interval)
+        elif interval is None:
             ll, ess, rc = self._fleet.step(t, y, has, act)
         elif forecast:
             ll, ess, rows, rc, fc_rc = self._fleet.step_forecast(t, y, has, act, None, interval)
@@ -1266,6 +1353,19 @@ class FilterFleet:
         new = self._wrap(t, [s.observation if s is not None else (float(y[k]) if has[k] else None) for k, s in enumerate(keep)],
                          [s.ll if s is not None else ll[k] for k, s in enumerate(keep)],
                          [s.ess if s is not None else ess[k] for k, s in enumerate(keep)])
+        if lags is not None:
+            m, lo, hi, em, el, eu = rows
+            outs = []
+            for k in range(self.S):
+                if not act[k]:
+                    outs.append([]); continue
+                hist[k] = (hist[k] + [(new[k].t, new[k].observation)])[-(self._fleet.window_depth(k) + 1):]
+                r = int(nrows[k])
+                outs.append([PfOut(hist[k][-1 - j][0], hist[k][-1 - j][1], float(em[k, j]), CredibleInterval(float(el[k, j]), float(eu[k, j])),
+                                   m[k, j].copy(), [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k, j], hi[k, j])])
+                             for j in range(r - 1, -1, -1)])
+            self._win_hist = hist
+            return new, outs
         if interval is None:
             return new, None
         if forecast:

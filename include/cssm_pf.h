@@ -1025,6 +1025,56 @@ int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const double* t, 
 /* ms2[0] = device time of the forward launch, ms2[1] = of the lineage launch of the last cssm_fleet_interpolate, each summed over its
  * chunks (HIP events on the fleet's stream).  CSSM_ESTATE before the first interpolation.  The array holds TWO doubles. */
 int cssm_fleet_interpolate_last_ms(cssm_fleet* f, double* ms2);
+/* ---- fixed-lag interpolation of a live fleet (FilterInterpolate as the stream it is: ParticleFilter.interpolate, model/
+ * ParticleFilter.scala:281-310 -- one stepInterpolate per observation, every element carrying the paths that survive to that moment;
+ * examples/Interpolate.scala: once data resumes behind a gap, the surviving lineages fill it).
+ *
+ * cssm_fleet_window(f, slices): the fleet remembers, per series, its `slices` most recent clouds and ancestor arrays on the device --
+ * S x slices x N x (8 d + 4) bytes (459 MB at S = 1024, N = 1000, d = 3, slices = 16).  slices >= 2 allocates and sets every series'
+ * depth to 0 (re-opening, with the same size or another, restarts every window); 0 frees; 1 is CSSM_EINVAL_ARG.  An allocation that
+ * does not fit is CSSM_ENOMEM naming the bytes, and the fleet goes on without a window.
+ * cssm_fleet_window_depth(f, k): the records remembered behind series k's base slice, 0 .. slices - 1 (the base slice is not counted; a
+ * full ring overwrites its oldest slice and the depth stays slices - 1); 0 for a null fleet, k >= S or no window.
+ *
+ * cssm_fleet_step_interpolate: cssm_fleet_step -- active / t / y / has_obs / ll_out / ess_out / rc_out are its arguments, bits and
+ * statuses, and the cloud, ancestors, clock and observation index it leaves are the ones cssm_fleet_step leaves -- which also writes
+ * every cloud it moved and the ancestors that resampled it into the series' window (one launch), and, for the series that ask, a second
+ * launch: the summaries of the last lag + 1 time indices through the lineages that survive to the cloud just written, one workgroup per
+ * (series, row).
+ *   lag: [S], or NULL = max_lag for every series.  CSSM_FLEET_NO_ROWS: the series is stepped and remembered but not summarised --
+ *   rows_out[k] = 0, nothing of its rows is written, no block of the second launch runs for it (a call in which no series asks is one
+ *   launch).  Any other lag[k] above max_lag fails the call (CSSM_EINVAL_ARG naming k).
+ *   Outputs: state_* = [S][max_lag + 1][d], eta_* = [S][max_lag + 1], rows_out = [S]; any may be NULL.  For a series stepped through
+ *   records 0 .. m by this call only, its window open since before record 0, row j (0 <= j <= min(lag_k, depth_k)) is bit for bit row
+ *   m + 1 - j of cssm_fleet_interpolate over its records 0 .. m (flags 0, the same t0, parameters and key): j = 0 is the cloud just
+ *   written through the ancestors that resampled it, the order statistics are exact, the means are k_fleet_lineage's sums in its order,
+ *   eta_of_mean is formed on the host from the mean.  Rows min(lag_k, depth_k) < j <= max_lag read NaN; rows_out[k] = min(lag_k,
+ *   depth_k) + 1.  The bounded window changes no row it still returns: the lineages are only ever composed from the newest index back.
+ *   For a series that is inactive, has no cloud (CSSM_ESTATE) or fails (CSSM_ENONFINITE) no entry is written, as for ll / ess; a failed
+ *   series loses its window.
+ *   Continuity: a series' window is continuous only across consecutive cssm_fleet_step_interpolate calls that stepped it.  Every other
+ *   call that writes its cloud, key or parameters (cssm_fleet_init, _step, _step_intervals, _step_forecast, _ll_filter, _filter,
+ *   _filter_intervals, _filter_forecasts, _pmmh_run, _reseed, _set_params) sets its depth to 0, and the next cssm_fleet_step_interpolate
+ *   first records the cloud the series holds then (what cssm_fleet_get_particles returns, identity ancestors) as the base slice at the
+ *   series' clock: the rows never reach behind it, and from it on they are the prefix interpolation's.  Calls that only read
+ *   (cssm_fleet_summary, the forecasts, cssm_fleet_interpolate, cssm_fleet_get_*) leave the windows alone, and cssm_fleet_interpolate
+ *   does not touch them.
+ *   CSSM_INTERP_REFERENCE_PAIRING is not offered: it pairs output row k with time index T - k, which has no meaning in a window whose
+ *   T moves with every call.
+ *   Errors: null t / y / rc_out, an interval outside (0, 1], a bad lag and a null fleet are refused with CSSM_EINVAL_ARG before the fleet
+ *   is looked at; a fleet without a window is CSSM_ESTATE naming cssm_fleet_window; then as cssm_fleet_step.  The device time of the
+ *   whole call is cssm_fleet_last_ms()[0].
+ * cssm_fleet_step_interpolate_last_ms: ms2[0] = device time of the forward launch, ms2[1] = of the lineage launch (0 when no series
+ * asked for rows) of the last cssm_fleet_step_interpolate; CSSM_ESTATE before the first.  The array holds TWO doubles. */
+#define CSSM_FLEET_NO_ROWS 0xffffffffu
+int cssm_fleet_window(cssm_fleet* f, uint32_t slices);
+uint32_t cssm_fleet_window_depth(const cssm_fleet* f, uint32_t k);
+int cssm_fleet_step_interpolate(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
+                                const uint32_t* lag, uint32_t max_lag, double interval,
+                                double* ll_out, int32_t* ess_out, uint32_t* rows_out,
+                                double* state_mean, double* state_lower, double* state_upper,
+                                double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out);
+int cssm_fleet_step_interpolate_last_ms(cssm_fleet* f, double* ms2);
 /* Observations series k's current cloud has seen (the Philox counter word of its next step); 0 for a null fleet or k >= S, the
  * convention of cssm_pf_observation_index. */
 uint64_t cssm_fleet_observation_index(const cssm_fleet* f, uint32_t k);
