@@ -59,6 +59,18 @@ def assert_series_equal_oracle(fl, k, model, n, seed, data, ll, ll_t, ess_t, nat
     return o
 
 
+def assert_summary_equal_oracle(got, k, o, interval):
+    """series k of a `summary(interval)` (six arrays over the series) against the oracle's summary of the same cloud: test_summaries'
+    rules -- order statistics bit for bit, the means (plain fp64 sums in another order) within rtol 1e-12, atol 0"""
+    m, lo, hi, em, el, eu = got
+    om, olo, ohi, oem, oel, oeu = o.summary(interval)
+    np.testing.assert_array_equal(lo[k], olo)
+    np.testing.assert_array_equal(hi[k], ohi)
+    assert el[k] == oel and eu[k] == oeu
+    np.testing.assert_allclose(m[k], om, rtol=1e-12, atol=0)      # plain fp64 sums in another order
+    np.testing.assert_allclose(em[k], oem, rtol=1e-12, atol=0)
+
+
 # 1 ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 2, 63, 100, 1000, _abi.FLEET_MAX_N])
 def test_ragged_fleet_equals_the_oracle_and_handles_of_its_own(n):
@@ -238,14 +250,9 @@ def test_summaries(n):
         for k in range(S):
             o = oracle.OraclePf(models[k].descriptor(), n, seeds[k]); o.filter(*datas[k]); orc.append(o)
         for interval in (0.975, 0.5):
-            m, lo, hi, em, el, eu = fl.summary(interval)
+            got = fl.summary(interval)
             for k in range(S):
-                om, olo, ohi, oem, oel, oeu = orc[k].summary(interval)
-                np.testing.assert_array_equal(lo[k], olo)
-                np.testing.assert_array_equal(hi[k], ohi)
-                assert el[k] == oel and eu[k] == oeu
-                np.testing.assert_allclose(m[k], om, rtol=1e-12, atol=0)      # plain fp64 sums in another order
-                np.testing.assert_allclose(em[k], oem, rtol=1e-12, atol=0)
+                assert_summary_equal_oracle(got, k, orc[k], interval)
 
 
 # 7 ------------------------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ from composablestatespacemodels_amd.filter import FilterFleet, NativePfFleet, Re
 from composablestatespacemodels_amd.formats import forecast_out_csv
 from test_forecast_draws import build_twin
 from test_gpu_fleet import run_key
+from test_gpu_fleet_interpolate import with_gap
 from test_gpu_fleet_intervals import _MODELS, ragged
 from test_gpu_forecast import check_forecast, expected
 
@@ -154,6 +155,71 @@ def test_every_row_of_a_ragged_fleet_equals_the_loop(name, n, twin):
                     assert (fc[k]["obs_below"][r], fc[k]["obs_equal"][r]) == (int((exp[2][0] < y).sum()), int((exp[2][0] == y).sum()))
             if ky is keys and interval == 0.975:
                 assert sorted(clouds) == sorted(e for e in ends if e != (3, 3)), "every first and last row but the dead series' last"
+
+
+def assert_whole_fleet_equals_the_loop(fl, ref, models, datas, keys, interval, rows, twin):
+    """`filter_forecasts(datas, interval, keys)` on `fl` of a fleet no series of which fails, against loop() on `ref` (the same models and
+    seeds): every row of every series, ll_t, ess_t, ll and the clouds both fleets hold afterwards; and rows[k] (record indices) of series
+    k against the oracle chain + twin draws from the cloud before the record, PIT counts included -- k_fleet_forecast, which the loop
+    runs, is one body with the kernel under test."""
+    S, n = fl.S, fl.n
+    T = [len(d[0]) for d in datas]
+    asked = [(k, r) for k in range(S) for r in rows[k]]
+    ll, ll_t, ess_t, fc, rc, fc_rc = fl.filter_forecasts(datas, interval, keys)
+    want, wll_t, wess_t, failed, clouds = loop(ref, datas, keys, interval, asked)
+    assert not rc.any() and not fc_rc.any() and failed == [None] * S, (rc, fc_rc, failed)
+    for k in range(S):
+        assert all(len(fc[k][nm]) == T[k] for nm in STAT + PIT)
+        assert_same_forecasts(fc[k], want[k], (n, interval, k))
+        assert nan_rows(fc[k]) == []
+        np.testing.assert_array_equal(ll_t[k], wll_t[k]); np.testing.assert_array_equal(ess_t[k], wess_t[k])
+        has = np.asarray(datas[k][2], dtype=bool)
+        assert np.all((fc[k]["obs_below"] >= 0) == has) and np.all((fc[k]["obs_equal"] >= 0) == has), (n, k)
+        assert ll[k] == wll_t[k][-1]
+        np.testing.assert_array_equal(fl.particles(k), ref.particles(k))
+        np.testing.assert_array_equal(fl.ancestors(k), ref.ancestors(k))
+        assert fl.observation_index(k) == ref.observation_index(k) == T[k]
+    assert sorted(clouds) == sorted(asked)
+    for (k, r), (cloud, clock) in clouds.items():
+        exp = expected(models[k], cloud, clock, np.array([datas[k][0][r]]), keys[k][r], twin)
+        row = {nm: fc[k][nm][r:r + 1] for nm in STAT}
+        row["samples"] = None
+        check_forecast(row, *exp, interval=interval)
+        y = datas[k][1][r]
+        pit = (int((exp[2][0] < y).sum()), int((exp[2][0] == y).sum())) if datas[k][2][r] else (-1, -1)
+        assert (fc[k]["obs_below"][r], fc[k]["obs_equal"][r]) == pit, (n, k, r)
+
+
+@pytest.mark.parametrize("d", list(range(1, 17)))
+def test_every_latent_dimension(d, twin):
+    """k_fleet_series<d, FCST> from both entry points on the per-dimension fixture of the sibling files: every row against the loop; rows
+    0, 4 (the first record behind the gap: the cloud before it is read through identity ancestors) and 5 (the last) against the oracle
+    chain; then one streamed record (one series without a datum) against forecast + step."""
+    model = cases.dim_model(d)
+    S, n = 3, 257
+    seeds = [SEED + 17 * k for k in range(S)]
+    datas = [with_gap(cases.poisson_counts(6, seed=SEED + k), 2, 4) for k in range(S)]
+    keys = record_keys(datas)
+    with NativePfFleet(model, n, S) as fl, NativePfFleet(model, n, S) as ref:
+        assert fl.d == ref.d == d
+        fl.reseed(seeds); ref.reseed(seeds)
+        assert_whole_fleet_equals_the_loop(fl, ref, [model] * S, datas, keys, 0.975, [(0, 4, 5)] * S, twin)
+        t = np.array([float(dd[0][-1]) + 0.75 for dd in datas]); y = np.array([1.0, 3.0, 0.0])
+        has = np.array([1, 0, 1], dtype=np.uint8); active = np.ones(S, dtype=np.uint8)
+        ky = np.array([run_key(KEY + 99, k) for k in range(S)], dtype=np.uint64)
+        ll, ess, arr, rc, fc_rc = _raw_step_forecast(fl, t, y, has, active, ky, 0.5, 7.5)
+        rs = ref.forecast([[v] for v in t], [int(v) for v in ky], 0.5, want_samples=True)
+        lb, eb, rb = ref.step(t, y, has, active)
+        assert not rc.any() and not rb.any() and not fc_rc.any(), (rc, rb, fc_rc)
+        for k in range(S):
+            assert ll[k] == lb[k] and ess[k] == eb[k] and rs[k]["rc"] == 0, (d, k)
+            for nm in STAT:
+                np.testing.assert_array_equal(arr[nm][k], rs[k][nm][0], err_msg=f"d {d} series {k} {nm}")
+            obs = rs[k]["samples"][0, d + 2]
+            pit = (int((obs < y[k]).sum()), int((obs == y[k]).sum())) if has[k] else (-1, -1)
+            assert (arr["obs_below"][k], arr["obs_equal"][k]) == pit, (d, k)
+            np.testing.assert_array_equal(fl.particles(k), ref.particles(k))
+            np.testing.assert_array_equal(fl.ancestors(k), ref.ancestors(k))
 
 
 # 2 ------------------------------------------------------------------------------------------------------------------------------

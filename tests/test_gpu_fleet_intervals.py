@@ -23,6 +23,8 @@ from composablestatespacemodels_amd import Data, _abi
 from composablestatespacemodels_amd.filter import FilterFleet, NativePfFleet, Resampling
 from composablestatespacemodels_amd.formats import pfout_csv
 from oracle import oracle
+from test_gpu_fleet import assert_summary_equal_oracle
+from test_gpu_fleet_interpolate import with_gap
 
 pytestmark = pytest.mark.gpu
 
@@ -99,7 +101,7 @@ def assert_nan_rows(got, first, tag):
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 2, 100, 1000, _abi.FLEET_MAX_N])
+@pytest.mark.parametrize("n", [1, 2, 63, 100, 1000, _abi.FLEET_MAX_N])
 @pytest.mark.parametrize("name", list(_MODELS))
 def test_every_row_of_a_ragged_fleet_equals_the_oracle(name, n):
     make, gen, link = _MODELS[name]
@@ -136,6 +138,77 @@ def test_every_row_of_a_ragged_fleet_equals_the_oracle(name, n):
                 else:
                     assert np.isnan(ll[k]) and np.isnan(ll_t[k][seen:]).all() and (ess_t[k][seen:] == -1).all()
                     assert_nan_rows(rows[k], seen + 1, (name, n, iv, k))
+
+
+def assert_whole_series_equals_the_oracle(fl, k, res, want, iv, n, link, tag):
+    """series k of a `filter_intervals(datas, iv)` that the oracle ran to its end (want: its oracle_rows): every row, ll_t, ess_t, ll and
+    the cloud the fleet holds afterwards"""
+    ll, ll_t, ess_t, rows, rc = res
+    wrows, absx, oll_t, oess_t, failed, o = want
+    assert rc[k] == 0 and failed is None, (tag, rc[k], failed)
+    assert all(len(a) == len(oll_t) + 1 for a in rows[k]) and len(wrows[iv]) == len(oll_t) + 1
+    np.testing.assert_array_equal(ll_t[k], oll_t)
+    np.testing.assert_array_equal(ess_t[k], oess_t)
+    assert_rows(rows[k], wrows[iv], absx, n, link, tag)
+    assert ll[k] == oll_t[-1]
+    np.testing.assert_array_equal(fl.particles(k), o.particles())
+    np.testing.assert_array_equal(fl.ancestors(k), o.ancestors())
+
+
+@pytest.mark.parametrize("d", list(range(1, 17)))
+def test_every_latent_dimension(d):
+    """k_fleet_series<d, IVAL> from both entry points and k_fleet_summary<d>: the per-dimension fixture of the sibling files (two
+    unweighted records: the None branch has an IVAL call site of its own), every row against the oracle; then two streamed records in
+    which the three series are weighted, unweighted and inactive in turn, against the oracle's step + summary and, bit for bit, a twin
+    fleet's step + summary -- whose summaries are held to the oracle by test_summaries' rules as well."""
+    model = cases.dim_model(d)
+    S, n = 3, 257
+    seeds = [SEED + 17 * k for k in range(S)]
+    datas = [with_gap(cases.poisson_counts(6, seed=SEED + k), 2, 4) for k in range(S)]
+    intervals = (0.975, 0.5, 1.0)
+    want = [oracle_rows(model, n, seeds[k], datas[k], intervals) for k in range(S)]
+    orc = [w[5] for w in want]
+    with NativePfFleet(model, n, S) as fl, NativePfFleet(model, n, S) as tw:
+        assert fl.d == tw.d == d
+        fl.reseed(seeds); tw.reseed(seeds)
+        for iv in intervals:
+            res = fl.filter_intervals(datas, iv)
+            assert not res[4].any(), res[4]
+            for k in range(S):
+                assert_whole_series_equals_the_oracle(fl, k, res, want[k], iv, n, "exp", (d, iv, k))
+        _, _, _, rc = tw.ll_filter(datas)
+        assert not rc.any(), rc
+        sm = tw.summary(1.0)
+        for k in range(S):
+            assert_summary_equal_oracle(sm, k, orc[k], 1.0)
+            for a, b in zip(res[3][k], sm):                      # the call's last row is the summary of the cloud it leaves
+                np.testing.assert_array_equal(a[-1], b[k])
+        clock = np.array([float(dd[0][-1]) for dd in datas])
+        for r, interval in enumerate((0.975, 0.5)):
+            role = [(k + r) % 3 for k in range(S)]               # 0: weighted, 1: unweighted, 2: inactive
+            active = np.array([q != 2 for q in role], dtype=np.uint8)
+            has = np.array([q == 0 for q in role], dtype=np.uint8)
+            clock = clock + np.where(active != 0, 0.5 + 0.25 * r, 0.0)
+            y = np.array([2.0, 0.0, 4.0])
+            ll, ess, rows, rc = _raw_step_intervals(fl, clock, y, has, active, interval, 7.5)
+            lb, eb, rb = tw.step(clock, y, has, active)
+            sb = tw.summary(interval)
+            assert not rc.any() and not rb.any(), (r, rc, rb)
+            for k in range(S):
+                if not active[k]:                                # untouched: the sentinels stand
+                    assert ll[k] == 7.5 and ess[k] == -77 and all(np.all(a[k] == 7.5) for a in rows), (r, k)
+                    continue
+                assert (ll[k], ess[k]) == (lb[k], eb[k]) == orc[k].step(clock[k], y[k], bool(has[k])), (d, r, k)
+                for a, b in zip(rows, sb):
+                    np.testing.assert_array_equal(a[k], b[k], err_msg=f"d {d} round {r} series {k}")
+                got = tuple(np.asarray(a[k])[None] for a in rows)
+                assert_rows(got, [orc[k].summary(interval)], [np.abs(orc[k].particles()).mean(axis=1)], n, "exp", (d, r, k))
+                assert_summary_equal_oracle(sb, k, orc[k], interval)
+        for k in range(S):
+            for f in (fl, tw):
+                np.testing.assert_array_equal(f.particles(k), orc[k].particles())
+                np.testing.assert_array_equal(f.ancestors(k), orc[k].ancestors())
+            assert fl.observation_index(k) == tw.observation_index(k)
 
 
 # 2 ------------------------------------------------------------------------------------------------------------------------------
