@@ -27,11 +27,43 @@ import numpy as np
 from . import _abi
 from .model import Data, Model, Parameters, TimedObservation, UnparamModel, split_data
 
-_dp = C.POINTER(C.c_double)
+# the pointer an array is handed to the library as, by its dtype (an int32 array is a status or a count: `int*` / `int32_t*`, one type)
+_PTR = {np.dtype(ty): C.POINTER(c) for ty, c in ((np.float64, C.c_double), (np.uint8, C.c_uint8), (np.int32, C.c_int), (np.uint32, C.c_uint32),
+                                                 (np.uint64, C.c_uint64))}
+_dp = _PTR[np.dtype(np.float64)]
+
+FORECAST_NAMES = ("state_mean", "state_lower", "state_upper", "eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")
 
 
-def _p(a, ty=_dp):
-    return a.ctypes.data_as(ty)
+def _p(a, ty=None):
+    """The array's address as the pointer its dtype names; None (an optional argument that is not given) stays None."""
+    return None if a is None else a.ctypes.data_as(ty or _PTR[a.dtype])
+
+
+def _u8(a):
+    """An optional array of flags as the library takes it."""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _filled(shape, fill):
+    return np.zeros(shape) if fill == 0 else np.full(shape, fill)
+
+
+def _interval_arrays(prefix, d, fill=0.0):
+    """The six outputs of a summary in the C calls' order, preset to ``fill``: ``(state_mean, state_lower, state_upper)`` of shape
+    ``[*prefix, d]`` and ``(eta_of_mean, eta_lower, eta_upper)`` of shape ``prefix``."""
+    wide = (*prefix, d)
+    return _filled(wide, fill), _filled(wide, fill), _filled(wide, fill), _filled(prefix, fill), _filled(prefix, fill), _filled(prefix, fill)
+
+
+def _forecast_arrays(d, rows, fill=np.nan, pit=True):
+    """The nine statistics of a forecast for ``rows`` rows, preset to ``fill`` -- with ``pit`` also the two PIT counts, preset to -1 -- by
+    name, and their pointers in the C calls' order."""
+    arr = {k: _filled((rows, d), fill) for k in FORECAST_NAMES[:3]}
+    arr.update({k: _filled(rows, fill) for k in FORECAST_NAMES[3:]})
+    if pit:
+        arr.update({k: np.full(rows, -1, dtype=np.int32) for k in ("obs_below", "obs_equal")})
+    return arr, [_p(v) for v in arr.values()]
 
 
 class NativePf:
@@ -48,7 +80,7 @@ class NativePf:
         self.model = model
         self.seed = int(seed) & (2**64 - 1)
         # the same entry point bound once more with untyped pointers: run_more hands it raw array addresses
-        self._ll_filter_more_raw = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double),
+        self._ll_filter_more_raw = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _dp,
                                                C.c_void_p, C.c_void_p)(("cssm_pf_ll_filter_more", self.lib))
 
     def close(self):
@@ -113,21 +145,16 @@ class NativePf:
         t = np.ascontiguousarray(t, dtype=np.float64)
         y = np.ascontiguousarray(y, dtype=np.float64)
         T = len(t)
-        hp = None
-        if has is not None:
-            has = np.ascontiguousarray(has, dtype=np.uint8)
-            hp = _p(has, C.POINTER(C.c_uint8))
+        has = _u8(has)
         ll = C.c_double()
         ll_t = np.zeros(T)
         ess_t = np.zeros(T, dtype=np.int32)
         path = None
         if want_path:
             path = np.zeros((T + 1, self.d))
-            rc = self.lib.cssm_pf_filter(self._h, _p(t), _p(y), hp, T, C.byref(ll), _p(ll_t),
-                                         _p(ess_t, C.POINTER(C.c_int32)), _p(path))
+            rc = self.lib.cssm_pf_filter(self._h, _p(t), _p(y), _p(has), T, C.byref(ll), _p(ll_t), _p(ess_t), _p(path))
         else:
-            rc = self.lib.cssm_pf_ll_filter(self._h, _p(t), _p(y), hp, T, C.byref(ll), _p(ll_t),
-                                            _p(ess_t, C.POINTER(C.c_int32)))
+            rc = self.lib.cssm_pf_ll_filter(self._h, _p(t), _p(y), _p(has), T, C.byref(ll), _p(ll_t), _p(ess_t))
         self.generation += 1
         _abi.check(rc)
         return ll.value, ll_t, ess_t, path
@@ -187,7 +214,7 @@ class NativePf:
         """{kernel: (total_ms, launches)} accumulated since profile(True)."""
         ms = np.zeros(len(self.KERNELS))
         cnt = np.zeros(len(self.KERNELS), dtype=np.uint64)
-        _abi.check(self.lib.cssm_pf_profile_read(self._h, _p(ms), _p(cnt, C.POINTER(C.c_uint64))))
+        _abi.check(self.lib.cssm_pf_profile_read(self._h, _p(ms), _p(cnt)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(self.KERNELS)}
 
     def summary(self, interval: float = 0.975):
@@ -213,13 +240,9 @@ class NativePf:
         t = np.ascontiguousarray(np.atleast_1d(np.asarray(t, dtype=np.float64)))
         H = len(t)
         key = self.forecast_key() if key is None else int(key) & (2**64 - 1)
-        out = {k: np.zeros((H, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
-        out.update({k: np.zeros(H) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        out, ptrs = _forecast_arrays(self.d, H, 0.0, pit=False)
         samples = np.zeros((H, self.d + 3, self.n)) if want_samples else None
-        _abi.check(self.lib.cssm_pf_forecast(self._h, _p(t), H, key, float(interval), _p(out["state_mean"]), _p(out["state_lower"]),
-                                             _p(out["state_upper"]), _p(out["eta_mean"]), _p(out["eta_lower"]), _p(out["eta_upper"]),
-                                             _p(out["obs_mean"]), _p(out["obs_lower"]), _p(out["obs_upper"]),
-                                             _p(samples) if want_samples else None))
+        _abi.check(self.lib.cssm_pf_forecast(self._h, _p(t), H, key, float(interval), *ptrs, _p(samples)))
         out["samples"] = samples
         out["key"] = key
         return out
@@ -244,17 +267,11 @@ class NativePf:
             if p.shape != (self.n,) or (p < 0).any():
                 raise ValueError(f"pick must hold N = {self.n} non-negative indices")
             pk = np.ascontiguousarray(p, dtype=np.uint32)
-        out = {k: np.zeros((H, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
-        out.update({k: np.zeros(H) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        out, ptrs = _forecast_arrays(self.d, H, 0.0, pit=False)
         samples = np.zeros((H, self.d + 3, self.n)) if want_samples else None
         pick_out = np.zeros(self.n, dtype=np.uint32)
-        u32 = C.POINTER(C.c_uint32)
-        _abi.check(self.lib.cssm_pf_forecast_posterior(self._h, self._desc.ptr(), _p(theta), nt, _p(x), M, float(t0), _p(t), H,
-                                                       _p(pk, u32) if pk is not None else None, key, float(interval),
-                                                       _p(out["state_mean"]), _p(out["state_lower"]), _p(out["state_upper"]),
-                                                       _p(out["eta_mean"]), _p(out["eta_lower"]), _p(out["eta_upper"]), _p(out["obs_mean"]),
-                                                       _p(out["obs_lower"]), _p(out["obs_upper"]), _p(samples) if want_samples else None,
-                                                       _p(pick_out, u32)))
+        _abi.check(self.lib.cssm_pf_forecast_posterior(self._h, self._desc.ptr(), _p(theta), nt, _p(x), M, float(t0), _p(t), H, _p(pk), key,
+                                                       float(interval), *ptrs, _p(samples), _p(pick_out)))
         out["samples"] = samples
         out["key"] = key
         out["pick"] = pick_out
@@ -271,18 +288,14 @@ class NativePf:
         t = np.ascontiguousarray(t, dtype=np.float64)
         y = np.ascontiguousarray(y, dtype=np.float64)
         T = len(t)
-        hp = None
-        if has is not None:
-            has = np.ascontiguousarray(has, dtype=np.uint8)
-            hp = _p(has, C.POINTER(C.c_uint8))
-        m, lo, hi = (np.zeros((T + 1, self.d)) for _ in range(3))
-        em, el, eu = (np.zeros(T + 1) for _ in range(3))
+        has = _u8(has)
+        rows = _interval_arrays((T + 1,), self.d)
         ll = C.c_double()
-        rc = self.lib.cssm_pf_interpolate(self._h, _p(t), _p(y), hp, T, float(interval), 1 if reference_pairing else 0,
-                                          C.byref(ll), _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu))
+        rc = self.lib.cssm_pf_interpolate(self._h, _p(t), _p(y), _p(has), T, float(interval), 1 if reference_pairing else 0,
+                                          C.byref(ll), *map(_p, rows))
         self.generation += 1
         _abi.check(rc)
-        return ll.value, m, lo, hi, em, el, eu
+        return (ll.value,) + rows
 
     def particles(self) -> np.ndarray:
         out = np.zeros((self.d, self.n))
@@ -312,7 +325,7 @@ class NativePf:
 
     def ancestors(self) -> np.ndarray:
         out = np.zeros(self.n, dtype=np.uint32)
-        _abi.check(self.lib.cssm_pf_get_ancestors(self._h, _p(out, C.POINTER(C.c_uint32))))
+        _abi.check(self.lib.cssm_pf_get_ancestors(self._h, _p(out)))
         return out
 
 
@@ -343,16 +356,13 @@ class NativePfBatch:
             raise ValueError("one model and one seed per chain")
         t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
         T = len(t)
-        hp = None
-        if has is not None:
-            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
+        has = _u8(has)
         descs = [m.descriptor() for m in models]
-        arr = (C.POINTER(_abi.ModelDesc) * self.B)(*[C.pointer(d.desc) for d in descs])
+        arr = (_abi._descp * self.B)(*[C.pointer(d.desc) for d in descs])
         sd = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
         ll = np.zeros(self.B); rc = np.zeros(self.B, dtype=np.int32)
         path = np.zeros((self.B, T + 1, self.d)) if want_path else None
-        _abi.check(self.lib.cssm_pfb_filter(self._h, arr, _p(sd, C.POINTER(C.c_uint64)), _p(t), _p(y), hp, T, _p(ll), _p(path) if want_path else None,
-                                            _p(rc, C.POINTER(C.c_int))))
+        _abi.check(self.lib.cssm_pfb_filter(self._h, arr, _p(sd), _p(t), _p(y), _p(has), T, _p(ll), _p(path), _p(rc)))
         return ll, path, rc
 
     def chain(self, k: int) -> "NativePf":
@@ -402,14 +412,14 @@ class NativePfFleet:
             raise ValueError("one model per series")
         cache = {}
         descs = [cache.setdefault(id(m), m.descriptor()) for m in models]   # (pointers may repeat)
-        arr = (C.POINTER(_abi.ModelDesc) * self.S)(*[C.pointer(d.desc) for d in descs])
+        arr = (_abi._descp * self.S)(*[C.pointer(d.desc) for d in descs])
         _abi.check(self.lib.cssm_fleet_set_params(self._h, arr))
 
     def reseed(self, seeds: Sequence[int]):
         if len(seeds) != self.S:
             raise ValueError("one seed per series")
         sd = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
-        _abi.check(self.lib.cssm_fleet_reseed(self._h, _p(sd, C.POINTER(C.c_uint64))))
+        _abi.check(self.lib.cssm_fleet_reseed(self._h, _p(sd)))
         self.seeds = [int(x) for x in sd]
 
     def set_option(self, option: int, value: int):
@@ -447,27 +457,47 @@ class NativePfFleet:
 
     def ll_filter_packed(self, off, t, y, has):
         """``ll_filter`` on arrays ``pack`` made (a caller that filters the same fleet repeatedly packs once)."""
-        R = int(off[-1])
-        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
-        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        ll, rc, ll_t, ess_t = self._record_outputs(R)
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_ll_filter(self._h, _p(off, C.POINTER(C.c_uint64)), _p(t), _p(y), _p(has, C.POINTER(C.c_uint8)), _p(ll),
-                                                 _p(ll_t), _p(ess_t, C.POINTER(C.c_int32)), _p(rc, C.POINTER(C.c_int))))
-        o = [int(v) for v in off]
-        return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], rc
+        _abi.check(self.lib.cssm_fleet_ll_filter(self._h, _p(off), _p(t), _p(y), _p(has), _p(ll), _p(ll_t), _p(ess_t), _p(rc)))
+        return ll, self._split(off, ll_t), self._split(off, ess_t), rc
 
     def _check_packed(self, off, t, y, has):
-        """What ``filter_packed`` refuses before any device call: a ragged layout that is not S series of t / y / has."""
+        """What every packed call refuses before any device call: a ragged layout that is not S series of t / y / has."""
         off = np.asarray(off)
         if off.dtype != np.uint64 or off.ndim != 1 or len(off) != self.S + 1:
             raise ValueError(f"off must hold S + 1 = {self.S + 1} uint64 offsets")
-        if int(off[0]) != 0 or any(int(off[k + 1]) < int(off[k]) for k in range(self.S)):
+        if int(off[0]) != 0 or (off[1:] < off[:-1]).any():
             raise ValueError("off[0] must be 0 and off must be non-decreasing")
         R = int(off[-1])
         for name, a, ty in (("t", t, np.float64), ("y", y, np.float64), ("has", has, np.uint8)):
             if a is None or a.dtype != ty or len(a) != R or not a.flags.c_contiguous:
                 raise ValueError(f"{name} must be a C-contiguous {np.dtype(ty).name} array of off[-1] = {R} entries")
         return R
+
+    def _record_inputs(self, off, t, y, has):
+        """What every packed record call starts with: ``_check_packed``, then ``(R, t, y, has)`` as the C call takes them -- it refuses null
+        data, so a fleet without a single record hands over one-entry placeholders, which are never read."""
+        R = self._check_packed(off, t, y, has)
+        return (R, t, y, has) if R else (0, np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.uint8))
+
+    def _record_outputs(self, R):
+        """``(ll[S], rc[S], ll_t[R], ess_t[R])`` of a record call."""
+        return np.zeros(self.S), np.zeros(self.S, dtype=np.int32), np.zeros(R), np.zeros(R, dtype=np.int32)
+
+    @staticmethod
+    def _split(off, a, extra=0):
+        """Series k's rows of ``a``, per series: ``off[k] + extra k .. off[k + 1] + extra (k + 1)`` -- ``extra`` = 0 for an array laid out
+        like the records, 1 for one laid out like the paths (T_k + 1 rows per series, row 0 the initial cloud)."""
+        first = [v + extra * k for k, v in enumerate(np.asarray(off).tolist())]
+        return [a[i:j] for i, j in zip(first, first[1:])]
+
+    @classmethod
+    def _split_named(cls, off, arr):
+        """``_split`` of every array of a dict: per series a dict of its rows under the same names."""
+        per = {name: cls._split(off, v) for name, v in arr.items()}
+        return [{name: rows[k] for name, rows in per.items()} for k in range(len(off) - 1)]
 
     def filter(self, datas, want_path: bool = True):
         """``filter`` of every series (cssm_fleet_filter): ``(ll[S], [ll_t of series k], [ess_t of series k], paths, last[S, d], rc[S])``.
@@ -480,18 +510,13 @@ class NativePfFleet:
 
     def filter_packed(self, off, t, y, has, want_path: bool = True):
         """``filter`` on arrays ``pack`` made (a caller that filters the same fleet repeatedly packs once)."""
-        R = self._check_packed(off, t, y, has)
-        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
-        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        ll, rc, ll_t, ess_t = self._record_outputs(R)
         last = np.zeros((self.S, self.d))
         path = np.zeros((R + self.S, self.d)) if want_path else None
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_filter(self._h, _p(off, C.POINTER(C.c_uint64)), _p(t), _p(y), _p(has, C.POINTER(C.c_uint8)), _p(ll),
-                                              _p(ll_t), _p(ess_t, C.POINTER(C.c_int32)), _p(path) if want_path else None, _p(last),
-                                              _p(rc, C.POINTER(C.c_int))))
-        o = [int(v) for v in off]
-        paths = [path[o[k] + k:o[k + 1] + k + 1] for k in range(self.S)] if want_path else None
-        return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], paths, last, rc
+        _abi.check(self.lib.cssm_fleet_filter(self._h, _p(off), _p(t), _p(y), _p(has), _p(ll), _p(ll_t), _p(ess_t), _p(path), _p(last), _p(rc)))
+        return ll, self._split(off, ll_t), self._split(off, ess_t), self._split(off, path, 1) if want_path else None, last, rc
 
     def filter_intervals(self, datas, interval: float = 0.975):
         """cssm_fleet_filter_intervals: ``ll_filter`` and, from the same launch, ``summary`` of the initial cloud and of the cloud after
@@ -504,30 +529,20 @@ class NativePfFleet:
 
     def filter_intervals_packed(self, off, t, y, has, interval: float = 0.975):
         """``filter_intervals`` on arrays ``pack`` made (a caller that filters the same fleet repeatedly packs once)."""
-        R = self._check_packed(off, t, y, has)
-        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
-        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
-        m, lo, hi = (np.zeros((R + self.S, self.d)) for _ in range(3))
-        em, el, eu = (np.zeros(R + self.S) for _ in range(3))
-        tt, yy, hh = (t, y, has) if R else (np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.uint8))
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        ll, rc, ll_t, ess_t = self._record_outputs(R)
+        rows = _interval_arrays((R + self.S,), self.d)
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_filter_intervals(self._h, _p(off, C.POINTER(C.c_uint64)), _p(tt), _p(yy), _p(hh, C.POINTER(C.c_uint8)),
-                                                        float(interval), _p(ll), _p(ll_t), _p(ess_t, C.POINTER(C.c_int32)),
-                                                        _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu), _p(rc, C.POINTER(C.c_int))))
-        o = [int(v) for v in off]
-        return (ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)],
-                self.interpolate_rows(off, (m, lo, hi, em, el, eu)), rc)
+        _abi.check(self.lib.cssm_fleet_filter_intervals(self._h, _p(off), _p(t), _p(y), _p(has), float(interval), _p(ll), _p(ll_t), _p(ess_t),
+                                                        *map(_p, rows), _p(rc)))
+        return ll, self._split(off, ll_t), self._split(off, ess_t), self.interpolate_rows(off, rows), rc
 
-    FORECAST_NAMES = ("state_mean", "state_lower", "state_upper", "eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")
+    FORECAST_NAMES = FORECAST_NAMES
 
-    def _forecast_arrays(self, rows: int):
-        """The nine statistics of ``forecast`` and the two PIT counts for ``rows`` rows, preset to NaN / -1, and their pointers in the
-        C call's order."""
-        arr = {k: np.full((rows, self.d), np.nan) for k in self.FORECAST_NAMES[:3]}
-        arr.update({k: np.full(rows, np.nan) for k in self.FORECAST_NAMES[3:]})
-        arr.update({k: np.full(rows, -1, dtype=np.int32) for k in ("obs_below", "obs_equal")})
-        ptrs = [_p(arr[k]) for k in self.FORECAST_NAMES] + [_p(arr[k], C.POINTER(C.c_int32)) for k in ("obs_below", "obs_equal")]
-        return arr, ptrs
+    def _forecast_arrays(self, rows: int, fill=np.nan, pit: bool = True):
+        """The nine statistics of ``forecast`` for ``rows`` rows, preset to ``fill`` -- with ``pit`` also the two PIT counts, preset to -1 --
+        and their pointers in the C calls' order: the one builder of every forecast's outputs."""
+        return _forecast_arrays(self.d, rows, fill, pit)
 
     def filter_forecasts(self, datas, interval: float = 0.975, keys=None):
         """cssm_fleet_filter_forecasts: ``ll_filter`` and, from the same launch, before every record is stepped, ``forecast`` of the
@@ -554,46 +569,33 @@ class NativePfFleet:
 
     def filter_forecasts_packed(self, off, t, y, has, interval: float = 0.975, keys=None):
         """``filter_forecasts`` on arrays ``pack`` made and (optional) a uint64 array of off[-1] keys."""
-        R = self._check_packed(off, t, y, has)
+        R, t, y, has = self._record_inputs(off, t, y, has)
         if keys is not None and (keys.dtype != np.uint64 or len(keys) != R or not keys.flags.c_contiguous):
             raise ValueError(f"keys must be a C-contiguous uint64 array of off[-1] = {R} entries")
-        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32); fc_rc = np.zeros(self.S, dtype=np.int32)
-        ll_t = np.zeros(R); ess_t = np.zeros(R, dtype=np.int32)
+        ll, rc, ll_t, ess_t = self._record_outputs(R)
+        fc_rc = np.zeros(self.S, dtype=np.int32)
         arr, ptrs = self._forecast_arrays(R)
-        tt, yy, hh = (t, y, has) if R else (np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.uint8))
-        u64 = C.POINTER(C.c_uint64)
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_filter_forecasts(self._h, _p(off, u64), _p(tt), _p(yy), _p(hh, C.POINTER(C.c_uint8)),
-                                                        _p(keys, u64) if keys is not None and R else None, float(interval), _p(ll), _p(ll_t),
-                                                        _p(ess_t, C.POINTER(C.c_int32)), *ptrs, _p(rc, C.POINTER(C.c_int)),
-                                                        _p(fc_rc, C.POINTER(C.c_int))))
-        o = [int(v) for v in off]
-        fc = [{name: v[o[k]:o[k + 1]] for name, v in arr.items()} for k in range(self.S)]
-        return ll, [ll_t[o[k]:o[k + 1]] for k in range(self.S)], [ess_t[o[k]:o[k + 1]] for k in range(self.S)], fc, rc, fc_rc
+        _abi.check(self.lib.cssm_fleet_filter_forecasts(self._h, _p(off), _p(t), _p(y), _p(has), _p(keys if R else None), float(interval), _p(ll),
+                                                        _p(ll_t), _p(ess_t), *ptrs, _p(rc), _p(fc_rc)))
+        return ll, self._split(off, ll_t), self._split(off, ess_t), self._split_named(off, arr), rc, fc_rc
 
     def step_forecast(self, t, y, has=None, active=None, keys=None, interval: float = 0.975):
         """cssm_fleet_step_forecast: ``step`` and, from the same launch, before the record is stepped, ``forecast`` of its time:
         ``(ll[S], ess[S], fc, rc[S], fc_rc[S])``; ``fc`` a dict of the nine statistics ([S, d] / [S]) and the PIT counts
         ``obs_below`` / ``obs_equal``; entries of series that are inactive, have no cloud or fail are NaN / -1.  ``keys``: S Philox
         keys (None: ``forecast_key(k)``)."""
-        t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
-        if len(t) != self.S or len(y) != self.S:
-            raise ValueError("one (t, y) per series")
-        if keys is not None and len(keys) != self.S:
-            raise ValueError("one key per series")
-        hp = ap = kp = None
-        if has is not None:
-            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
+        t, y, has, active = self._step_inputs(t, y, has, active)
         if keys is not None:
-            keys = np.ascontiguousarray([int(x) & (2**64 - 1) for x in keys], dtype=np.uint64); kp = _p(keys, C.POINTER(C.c_uint64))
-        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32)
-        rc = np.zeros(self.S, dtype=np.int32); fc_rc = np.zeros(self.S, dtype=np.int32)
+            if len(keys) != self.S:
+                raise ValueError("one key per series")
+            keys = np.ascontiguousarray([int(x) & (2**64 - 1) for x in keys], dtype=np.uint64)
+        ll, ess, rc = self._step_outputs()
+        fc_rc = np.zeros(self.S, dtype=np.int32)
         arr, ptrs = self._forecast_arrays(self.S)
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_step_forecast(self._h, ap, _p(t), _p(y), hp, kp, float(interval), _p(ll), _p(ess, C.POINTER(C.c_int32)),
-                                                     *ptrs, _p(rc, C.POINTER(C.c_int)), _p(fc_rc, C.POINTER(C.c_int))))
+        _abi.check(self.lib.cssm_fleet_step_forecast(self._h, _p(active), _p(t), _p(y), _p(has), _p(keys), float(interval), _p(ll), _p(ess), *ptrs,
+                                                     _p(rc), _p(fc_rc)))
         return ll, ess, arr, rc, fc_rc
 
     def interpolate(self, datas, interval: float = 0.975, reference_pairing: bool = False):
@@ -606,76 +608,86 @@ class NativePfFleet:
 
     def interpolate_packed(self, off, t, y, has, interval: float = 0.975, reference_pairing: bool = False):
         """``interpolate`` on arrays ``pack`` made (a caller that interpolates the same fleet repeatedly packs once)."""
-        R = self._check_packed(off, t, y, has)
-        ll = np.zeros(self.S); rc = np.zeros(self.S, dtype=np.int32)
-        m, lo, hi = (np.zeros((R + self.S, self.d)) for _ in range(3))
-        em, el, eu = (np.zeros(R + self.S) for _ in range(3))
-        tt, yy, hh = (t, y, has) if R else (np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.uint8))
-        _abi.check(self.lib.cssm_fleet_interpolate(self._h, _p(off, C.POINTER(C.c_uint64)), _p(tt), _p(yy), _p(hh, C.POINTER(C.c_uint8)),
-                                                   float(interval), _abi.CSSM_INTERP_REFERENCE_PAIRING if reference_pairing else 0, _p(ll),
-                                                   _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu), _p(rc, C.POINTER(C.c_int))))
-        return ll, self.interpolate_rows(off, (m, lo, hi, em, el, eu)), rc
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        ll, rc = np.zeros(self.S), np.zeros(self.S, dtype=np.int32)
+        rows = _interval_arrays((R + self.S,), self.d)
+        _abi.check(self.lib.cssm_fleet_interpolate(self._h, _p(off), _p(t), _p(y), _p(has), float(interval),
+                                                   _abi.CSSM_INTERP_REFERENCE_PAIRING if reference_pairing else 0, _p(ll), *map(_p, rows), _p(rc)))
+        return ll, self.interpolate_rows(off, rows), rc
 
     @staticmethod
     def interpolate_rows(off, arrays):
         """Series k's rows of ``cssm_fleet_interpolate``'s outputs: ``off[k] + k .. off[k + 1] + k`` (T_k + 1 rows, row 0 the initial
-        cloud) of every array, per series."""
-        o = [int(v) for v in off]
-        return [tuple(a[o[k] + k:o[k + 1] + k + 1] for a in arrays) for k in range(len(o) - 1)]
+        cloud) of every array, per series (``_split`` with a row more per series)."""
+        per = [NativePfFleet._split(off, a, 1) for a in arrays]
+        return [tuple(rows[k] for rows in per) for k in range(len(off) - 1)]
+
+    def _ms(self, fn, count):
+        """The ``count`` milliseconds one of the library's timing getters writes."""
+        ms = np.zeros(count)
+        _abi.check(fn(self._h, _p(ms)))
+        return tuple(float(v) for v in ms)
 
     def interpolate_last_ms(self) -> Tuple[float, float]:
         """Device time (HIP events) of the last interpolation's forward launch and lineage launch, ms, summed over its chunks."""
-        ms = np.zeros(2)
-        _abi.check(self.lib.cssm_fleet_interpolate_last_ms(self._h, _p(ms)))
-        return float(ms[0]), float(ms[1])
+        return self._ms(self.lib.cssm_fleet_interpolate_last_ms, 2)
 
     def pmmh_last_split(self):
         """cssm_fleet_pmmh_last_split: milliseconds of the last ``cssm_fleet_pmmh_run`` on this fleet, summed over its iterations --
         (propose + set_params + reseed, record building, upload, kernel, decide) and the iterations counted."""
-        ms = np.zeros(6)
-        _abi.check(self.lib.cssm_fleet_pmmh_last_split(self._h, _p(ms)))
-        return tuple(float(v) for v in ms[:5]), int(ms[5])
+        ms = self._ms(self.lib.cssm_fleet_pmmh_last_split, 6)
+        return ms[:5], int(ms[5])
+
+    def pmmh_run(self, desc, theta0, delta, off, t, y, has, seeds, iters):
+        """cssm_fleet_pmmh_run: a Metropolis chain per series from the rows of ``theta0[S, n_theta]`` under ``seeds``, ``desc`` the
+        descriptor the rows flatten, on the arrays ``pack`` made: ``(ll[S, iters], theta[S, iters, n_theta], accepted[S, iters],
+        last_state[S, iters, d])`` (``pmmh.pmmh_native_fleet`` is the caller's entry point)."""
+        nt = theta0.shape[1]
+        ll, th, last = np.zeros((self.S, iters)), np.zeros((self.S, iters, nt)), np.zeros((self.S, iters, self.d))
+        acc = np.zeros((self.S, iters), dtype=np.int32)
+        sd = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_pmmh_run(self._h, desc.ptr(), _p(theta0), nt, float(delta), _p(off), _p(t), _p(y), _p(has), _p(sd), int(iters),
+                                                _p(ll), _p(th), _p(acc), _p(last)))
+        return ll, th, acc, last
 
     def init(self, t0):
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (self.S,)), dtype=np.float64)
         self.generation += 1
         _abi.check(self.lib.cssm_fleet_init(self._h, _p(t0)))
 
-    def step(self, t, y, has=None, active=None):
-        """One observation for the active series (``active`` None = all): ``(ll[S], ess[S], rc[S])``; entries of inactive series are
-        NaN / -1 / 0."""
+    def _step_inputs(self, t, y, has, active):
+        """What every step call starts with: ``(t, y, has, active)`` as the C call takes them (None stays None), one ``(t, y)`` per
+        series or a refusal.  The caller holds them across its C call."""
         t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
         if len(t) != self.S or len(y) != self.S:
             raise ValueError("one (t, y) per series")
-        hp = ap = None
-        if has is not None:
-            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
-        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32); rc = np.zeros(self.S, dtype=np.int32)
+        return t, y, _u8(has), _u8(active)
+
+    def _step_outputs(self):
+        """``(ll[S], ess[S], rc[S])`` of a step call, preset to NaN / -1 / 0: what the entries of a series it does not move read."""
+        return np.full(self.S, np.nan), np.full(self.S, -1, dtype=np.int32), np.zeros(self.S, dtype=np.int32)
+
+    def step(self, t, y, has=None, active=None):
+        """One observation for the active series (``active`` None = all): ``(ll[S], ess[S], rc[S])``; entries of inactive series are
+        NaN / -1 / 0."""
+        t, y, has, active = self._step_inputs(t, y, has, active)
+        ll, ess, rc = self._step_outputs()
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_step(self._h, ap, _p(t), _p(y), hp, _p(ll), _p(ess, C.POINTER(C.c_int32)), _p(rc, C.POINTER(C.c_int))))
+        _abi.check(self.lib.cssm_fleet_step(self._h, _p(active), _p(t), _p(y), _p(has), _p(ll), _p(ess), _p(rc)))
         return ll, ess, rc
 
     def step_intervals(self, t, y, has=None, active=None, interval: float = 0.975):
         """cssm_fleet_step_intervals: ``step`` and, from the same launch, ``summary`` of every cloud it moved: ``(ll[S], ess[S], (state_mean[S,
         d], state_lower, state_upper, eta_of_mean[S], eta_lower, eta_upper), rc[S])``; entries of series that are inactive, have no cloud
         or fail are NaN / -1."""
-        t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
-        if len(t) != self.S or len(y) != self.S:
-            raise ValueError("one (t, y) per series")
-        hp = ap = None
-        if has is not None:
-            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
-        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32); rc = np.zeros(self.S, dtype=np.int32)
-        m, lo, hi = (np.full((self.S, self.d), np.nan) for _ in range(3))
-        em, el, eu = (np.full(self.S, np.nan) for _ in range(3))
+        t, y, has, active = self._step_inputs(t, y, has, active)
+        ll, ess, rc = self._step_outputs()
+        rows = _interval_arrays((self.S,), self.d, np.nan)
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_step_intervals(self._h, ap, _p(t), _p(y), hp, float(interval), _p(ll), _p(ess, C.POINTER(C.c_int32)),
-                                                      _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu), _p(rc, C.POINTER(C.c_int))))
-        return ll, ess, (m, lo, hi, em, el, eu), rc
+        _abi.check(self.lib.cssm_fleet_step_intervals(self._h, _p(active), _p(t), _p(y), _p(has), float(interval), _p(ll), _p(ess), *map(_p, rows),
+                                                      _p(rc)))
+        return ll, ess, rows, rc
 
     def window(self, slices: int):
         """cssm_fleet_window: remember, per series, the ``slices`` most recent clouds and ancestor arrays on the device (S x slices x N
@@ -712,40 +724,26 @@ class NativePfFleet:
         state_upper, eta_of_mean[S, max_lag + 1], eta_lower, eta_upper), rc[S])``.  Row j of series k summarises time index (newest - j)
         through the lineages that survive to the cloud just written; ``rows_out[k]`` = min(lag_k, window_depth(k)) + 1 rows are filled,
         the others read NaN.  ``lag``: None (max_lag for every series), an int, or one entry per series with None for "no rows"."""
-        t = np.ascontiguousarray(t, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
-        if len(t) != self.S or len(y) != self.S:
-            raise ValueError("one (t, y) per series")
-        lg = self._lags(lag, max_lag)
-        hp = ap = None
-        if has is not None:
-            has = np.ascontiguousarray(has, dtype=np.uint8); hp = _p(has, C.POINTER(C.c_uint8))
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.uint8); ap = _p(active, C.POINTER(C.c_uint8))
-        L = int(max_lag) + 1
-        ll = np.full(self.S, np.nan); ess = np.full(self.S, -1, dtype=np.int32); rc = np.zeros(self.S, dtype=np.int32)
-        rows = np.zeros(self.S, dtype=np.uint32)
-        m, lo, hi = (np.full((self.S, L, self.d), np.nan) for _ in range(3))
-        em, el, eu = (np.full((self.S, L), np.nan) for _ in range(3))
+        t, y, has, active = self._step_inputs(t, y, has, active)
+        lag = self._lags(lag, max_lag)
+        ll, ess, rc = self._step_outputs()
+        nrows = np.zeros(self.S, dtype=np.uint32)
+        rows = _interval_arrays((self.S, int(max_lag) + 1), self.d, np.nan)
         self.generation += 1
-        _abi.check(self.lib.cssm_fleet_step_interpolate(self._h, ap, _p(t), _p(y), hp, None if lg is None else _p(lg, C.POINTER(C.c_uint32)),
-                                                        int(max_lag), float(interval), _p(ll), _p(ess, C.POINTER(C.c_int32)),
-                                                        _p(rows, C.POINTER(C.c_uint32)), _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu),
-                                                        _p(rc, C.POINTER(C.c_int))))
-        return ll, ess, rows, (m, lo, hi, em, el, eu), rc
+        _abi.check(self.lib.cssm_fleet_step_interpolate(self._h, _p(active), _p(t), _p(y), _p(has), _p(lag), int(max_lag), float(interval), _p(ll),
+                                                        _p(ess), _p(nrows), *map(_p, rows), _p(rc)))
+        return ll, ess, nrows, rows, rc
 
     def step_interpolate_last_ms(self) -> Tuple[float, float]:
         """Device time (HIP events) of the last ``step_interpolate``'s forward launch and lineage launch, ms (the latter 0 when no
         series asked for rows)."""
-        ms = np.zeros(2)
-        _abi.check(self.lib.cssm_fleet_step_interpolate_last_ms(self._h, _p(ms)))
-        return float(ms[0]), float(ms[1])
+        return self._ms(self.lib.cssm_fleet_step_interpolate_last_ms, 2)
 
     def summary(self, interval: float = 0.975):
         """(state_mean[S, d], state_lower[S, d], state_upper[S, d], eta_of_mean[S], eta_lower[S], eta_upper[S])."""
-        m, lo, hi = np.zeros((self.S, self.d)), np.zeros((self.S, self.d)), np.zeros((self.S, self.d))
-        em, el, eu = np.zeros(self.S), np.zeros(self.S), np.zeros(self.S)
-        _abi.check(self.lib.cssm_fleet_summary(self._h, float(interval), _p(m), _p(lo), _p(hi), _p(em), _p(el), _p(eu)))
-        return m, lo, hi, em, el, eu
+        rows = _interval_arrays((self.S,), self.d)
+        _abi.check(self.lib.cssm_fleet_summary(self._h, float(interval), *map(_p, rows)))
+        return rows
 
     def particles(self, k: int) -> np.ndarray:
         out = np.zeros((self.d, self.n))
@@ -754,15 +752,13 @@ class NativePfFleet:
 
     def ancestors(self, k: int) -> np.ndarray:
         out = np.zeros(self.n, dtype=np.uint32)
-        _abi.check(self.lib.cssm_fleet_get_ancestors(self._h, int(k), _p(out, C.POINTER(C.c_uint32))))
+        _abi.check(self.lib.cssm_fleet_get_ancestors(self._h, int(k), _p(out)))
         return out
 
     def last_ms(self) -> Tuple[float, float, float]:
         """Device time (HIP events) of the last ll_filter / init / step call, of the last summary and of the last forecast, ms;
         < 0: none yet."""
-        ms = np.zeros(3)
-        _abi.check(self.lib.cssm_fleet_last_ms(self._h, _p(ms)))
-        return float(ms[0]), float(ms[1]), float(ms[2])
+        return self._ms(self.lib.cssm_fleet_last_ms, 3)
 
     def observation_index(self, k: int) -> int:
         """Observations series k's current cloud has seen (cssm_fleet_observation_index)."""
@@ -795,13 +791,15 @@ class NativePfFleet:
             raise ValueError("one key per series")
         ky = np.ascontiguousarray([int(x) & (2**64 - 1) for x in keys], dtype=np.uint64)
         arr, samples, rc = self.forecast_packed(off, t, ky, interval, want_samples)
-        o = [int(v) for v in off]
-        outs = []
-        for k in range(self.S):
-            r = {name: v[o[k]:o[k + 1]] for name, v in arr.items()}
-            r["samples"] = samples[o[k]:o[k + 1]] if want_samples else None
-            r["key"] = int(ky[k]); r["rc"] = int(rc[k])
-            outs.append(r)
+        return self._forecast_dicts(off, arr, samples, ky, rc)
+
+    def _forecast_dicts(self, off, arr, samples, keys, rc):
+        """Per series what a forecast returns: its rows of the nine statistics and of the samples (None without them), its key and its
+        status."""
+        outs = self._split_named(off, arr)
+        per = [None] * self.S if samples is None else self._split(off, samples)
+        for k, r in enumerate(outs):
+            r["samples"] = per[k]; r["key"] = int(keys[k]); r["rc"] = int(rc[k])
         return outs
 
     def forecast_packed(self, off, t, keys, interval: float = 0.975, want_samples: bool = False):
@@ -809,15 +807,10 @@ class NativePfFleet:
         packs once): ``(dict of arrays laid out like t, samples or None, rc[S])``."""
         R = int(off[-1])
         tt = t if R else np.zeros(1)
-        arr = {k: np.zeros((R, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
-        arr.update({k: np.zeros(R) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        arr, ptrs = self._forecast_arrays(R, 0.0, pit=False)
         samples = np.zeros((R, self.d + 3, self.n)) if want_samples else None
         rc = np.zeros(self.S, dtype=np.int32)
-        u64 = C.POINTER(C.c_uint64)
-        _abi.check(self.lib.cssm_fleet_forecast(self._h, _p(off, u64), _p(tt), _p(keys, u64), float(interval), _p(arr["state_mean"]),
-                                                _p(arr["state_lower"]), _p(arr["state_upper"]), _p(arr["eta_mean"]), _p(arr["eta_lower"]),
-                                                _p(arr["eta_upper"]), _p(arr["obs_mean"]), _p(arr["obs_lower"]), _p(arr["obs_upper"]),
-                                                _p(samples) if want_samples else None, _p(rc, C.POINTER(C.c_int))))
+        _abi.check(self.lib.cssm_fleet_forecast(self._h, _p(off), _p(tt), _p(keys), float(interval), *ptrs, _p(samples), _p(rc)))
         return arr, samples, rc
 
     def posterior_key(self, k: int) -> int:
@@ -881,13 +874,9 @@ class NativePfFleet:
             keys = [self.posterior_key(k) for k in range(self.S)]
         ky = np.ascontiguousarray([int(v) & (2**64 - 1) for v in keys], dtype=np.uint64)
         arr, samples, pick_out, rc = self.forecast_posterior_packed(moff, theta, x, t0, off, t, ky, interval, pk, want_samples)
-        o = [int(v) for v in off]
-        outs = []
-        for k in range(self.S):
-            r = {name: v[o[k]:o[k + 1]] for name, v in arr.items()}
-            r["samples"] = samples[o[k]:o[k + 1]] if want_samples else None
-            r["key"] = int(ky[k]); r["rc"] = int(rc[k]); r["pick"] = pick_out[k]
-            outs.append(r)
+        outs = self._forecast_dicts(off, arr, samples, ky, rc)
+        for k, r in enumerate(outs):
+            r["pick"] = pick_out[k]
         return outs
 
     def forecast_posterior_packed(self, moff, theta, x, t0, off, t, keys, interval: float = 0.975, picks=None, want_samples: bool = False):
@@ -897,17 +886,12 @@ class NativePfFleet:
         tt = t if R else np.zeros(1)
         th = theta if M else np.zeros((1, max(1, theta.shape[1])))
         xx = x if M else np.zeros((1, self.d))
-        arr = {k: np.zeros((R, self.d)) for k in ("state_mean", "state_lower", "state_upper")}
-        arr.update({k: np.zeros(R) for k in ("eta_mean", "eta_lower", "eta_upper", "obs_mean", "obs_lower", "obs_upper")})
+        arr, ptrs = self._forecast_arrays(R, 0.0, pit=False)
         samples = np.zeros((R, self.d + 3, self.n)) if want_samples else None
         pick_out = np.zeros((self.S, self.n), dtype=np.uint32)
         rc = np.zeros(self.S, dtype=np.int32)
-        u64, u32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
-        _abi.check(self.lib.cssm_fleet_forecast_posterior(
-            self._h, self._desc.ptr(), _p(moff, u64), _p(th), int(theta.shape[1]), _p(xx), _p(t0), _p(off, u64), _p(tt),
-            _p(picks, u32) if picks is not None else None, _p(keys, u64), float(interval), _p(arr["state_mean"]), _p(arr["state_lower"]),
-            _p(arr["state_upper"]), _p(arr["eta_mean"]), _p(arr["eta_lower"]), _p(arr["eta_upper"]), _p(arr["obs_mean"]), _p(arr["obs_lower"]),
-            _p(arr["obs_upper"]), _p(samples) if want_samples else None, _p(pick_out, u32), _p(rc, C.POINTER(C.c_int))))
+        _abi.check(self.lib.cssm_fleet_forecast_posterior(self._h, self._desc.ptr(), _p(moff), _p(th), int(theta.shape[1]), _p(xx), _p(t0), _p(off),
+                                                          _p(tt), _p(picks), _p(keys), float(interval), *ptrs, _p(samples), _p(pick_out), _p(rc)))
         return arr, samples, pick_out, rc
 
 
@@ -938,7 +922,7 @@ class Resampling:
     def systematicAncestors(weights: Sequence[float], u: float, device: int = 0) -> np.ndarray:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         anc = np.zeros(len(w), dtype=np.uint32)
-        _abi.check(_abi.load_library().cssm_resample_systematic(_p(w), len(w), float(u), _p(anc, C.POINTER(C.c_uint32)), device))
+        _abi.check(_abi.load_library().cssm_resample_systematic(_p(w), len(w), float(u), _p(anc), device))
         return anc
 
     @staticmethod
@@ -947,7 +931,7 @@ class Resampling:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         anc = np.zeros(len(w), dtype=np.uint32)
         _abi.check(_abi.load_library().cssm_resample(int(kind), _p(w), len(w), float(u), int(seed), int(step),
-                                                     _p(anc, C.POINTER(C.c_uint32)), device))
+                                                     _p(anc), device))
         return anc
 
     @staticmethod
@@ -973,7 +957,7 @@ class Resampling:
         """cssm_resample_residual (an EXTENSION, see ``residualResampling``): the particle every slot takes."""
         w = np.ascontiguousarray(weights, dtype=np.float64)
         anc = np.zeros(len(w), dtype=np.uint32)
-        _abi.check(_abi.load_library().cssm_resample_residual(_p(w), len(w), int(seed), int(step), _p(anc, C.POINTER(C.c_uint32)), device))
+        _abi.check(_abi.load_library().cssm_resample_residual(_p(w), len(w), int(seed), int(step), _p(anc), device))
         return anc
 
     @staticmethod
@@ -1289,20 +1273,29 @@ class FilterFleet:
     def stepFilter(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]]) -> List[FleetState]:
         """``ys[k]`` None = sensor k has nothing new (its state is returned as it is); a TimedObservation whose ``observation`` is None
         is the reference's ``None`` branch (propagate only)."""
-        return self._step(states, ys, None)[0]
+        return self._advance(states, ys, lambda t, y, has, act: self._fleet.step(t, y, has, act) + (None,))[0]
 
     def stepIntervals(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]],
                       interval: float = 0.975) -> Tuple[List[FleetState], List[Optional[PfOut]]]:
         """``stepFilter`` and ``getIntervals`` of every state it advanced, from one device call (``filterStream`` mapped through
         ``getIntervals``, examples/Filtering.scala:24-31): the new states, and per series its ``PfOut`` -- None where ``ys[k]`` is None."""
-        return self._step(states, ys, float(interval))
+        def call(t, y, has, act):
+            ll, ess, rows, rc = self._fleet.step_intervals(t, y, has, act, float(interval))
+            return ll, ess, rc, rows
+        new, act, rows = self._advance(states, ys, call)
+        return new, [_pfout(new[k].t, new[k].observation, rows, k) if act[k] else None for k in range(self.S)]
 
     def stepForecast(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]],
                      interval: float = 0.975) -> Tuple[List[FleetState], List[Optional[ForecastOut]]]:
         """``getMeanForecast`` of every datum's time from the state before it, then ``stepFilter``, from one device call
         (``ParticleFilter.getMeanForecast`` mapped over a ``filterStream``, :368-409): the new states, and per series the
         ``ForecastOut`` at its datum's time under the series' default key -- None where ``ys[k]`` is None."""
-        return self._step(states, ys, float(interval), forecast=True)
+        def call(t, y, has, act):
+            ll, ess, fc, rc, fc_rc = self._fleet.step_forecast(t, y, has, act, None, float(interval))
+            self._raise_series(None, fc_rc=fc_rc, stepping=True)
+            return ll, ess, rc, fc
+        new, act, fc = self._advance(states, ys, call)
+        return new, [_forecast_outs([new[k].t], {name: v[k:k + 1] for name, v in fc.items()})[0] if act[k] else None for k in range(self.S)]
 
     def window(self, slices: int):
         """``NativePfFleet.window``: the device memory ``stepInterpolate`` remembers in (0 frees it)."""
@@ -1320,9 +1313,28 @@ class FilterFleet:
         if len(lag) != self.S:
             raise ValueError(f"one lag per series ({self.S}), not {len(lag)}")
         max_lag = max([int(v) for v in lag if v is not None], default=0)
-        return self._step(states, ys, float(interval), lags=(list(lag), max_lag))
+        hist = getattr(self, "_win_hist", None) or [[] for _ in range(self.S)]   # per series the (t, observation) of its window's slices
 
-    def _step(self, states, ys, interval: Optional[float], forecast: bool = False, lags=None):
+        def call(t, y, has, act):
+            for k in range(self.S):                    # a window that restarts takes the state before this datum as its base slice
+                if act[k] and self._fleet.window_depth(k) == 0:
+                    hist[k] = [(states[k].t, states[k].observation)]
+            ll, ess, nrows, rows, rc = self._fleet.step_interpolate(t, y, has, act, list(lag), max_lag, float(interval))
+            return ll, ess, rc, (nrows, rows)
+        new, act, (nrows, rows) = self._advance(states, ys, call)
+        outs = []
+        for k in range(self.S):
+            if not act[k]:
+                outs.append([]); continue
+            hist[k] = (hist[k] + [(new[k].t, new[k].observation)])[-(self._fleet.window_depth(k) + 1):]
+            outs.append([_pfout(*hist[k][-1 - j], rows, (k, j)) for j in range(int(nrows[k]) - 1, -1, -1)])
+        self._win_hist = hist
+        return new, outs
+
+    def _advance(self, states, ys, call):
+        """What every step method does around its device call: the fleet's current states and one (optional) observation per series or
+        a refusal; ``call(t, y, has, act)`` -> ``(ll, ess, rc, rest)``; a series' own status raised; the new states (an inactive
+        series keeps the fields of its old one).  Returns ``(new_states, act, rest)``."""
         if len(states) != self.S or len(ys) != self.S:
             raise ValueError("one state and one (optional) observation per series")
         if any(s._owner is not self._fleet or s._generation != self._fleet.generation for s in states):
@@ -1331,54 +1343,30 @@ class FilterFleet:
         t = np.array([states[k].t if o is None else o.t for k, o in enumerate(ys)], dtype=np.float64)
         has = np.array([0 if (o is None or o.observation is None) else 1 for o in ys], dtype=np.uint8)
         y = np.array([o.observation if h else 0.0 for o, h in zip(ys, has)], dtype=np.float64)
-        if lags is not None:
-            hist = getattr(self, "_win_hist", None) or [[] for _ in range(self.S)]
-            for k in range(self.S):                    # a window that restarts takes the state before this datum as its base slice
-                if act[k] and self._fleet.window_depth(k) == 0:
-                    hist[k] = [(states[k].t, states[k].observation)]
-            ll, ess, nrows, rows, rc = self._fleet.step_interpolate(t, y, has, act, lags[0], lags[1], interval)
-        elif interval is None:
-            ll, ess, rc = self._fleet.step(t, y, has, act)
-        elif forecast:
-            ll, ess, rows, rc, fc_rc = self._fleet.step_forecast(t, y, has, act, None, interval)
-            for k in range(self.S):
-                if fc_rc[k]:
-                    raise _abi.CssmError(int(fc_rc[k]), self._fleet.lib.cssm_last_error().decode() or f"series {k}: its forecast was refused")
-        else:
-            ll, ess, rows, rc = self._fleet.step_intervals(t, y, has, act, interval)
-        for k in range(self.S):
-            if rc[k]:
-                raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable (or it has no cloud)")
+        ll, ess, rc, rest = call(t, y, has, act)
+        self._raise_series(rc, stepping=True)
         keep = [s if not a else None for s, a in zip(states, act)]
         new = self._wrap(t, [s.observation if s is not None else (float(y[k]) if has[k] else None) for k, s in enumerate(keep)],
                          [s.ll if s is not None else ll[k] for k, s in enumerate(keep)],
                          [s.ess if s is not None else ess[k] for k, s in enumerate(keep)])
-        if lags is not None:
-            m, lo, hi, em, el, eu = rows
-            outs = []
-            for k in range(self.S):
-                if not act[k]:
-                    outs.append([]); continue
-                hist[k] = (hist[k] + [(new[k].t, new[k].observation)])[-(self._fleet.window_depth(k) + 1):]
-                r = int(nrows[k])
-                outs.append([PfOut(hist[k][-1 - j][0], hist[k][-1 - j][1], float(em[k, j]), CredibleInterval(float(el[k, j]), float(eu[k, j])),
-                                   m[k, j].copy(), [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k, j], hi[k, j])])
-                             for j in range(r - 1, -1, -1)])
-            self._win_hist = hist
-            return new, outs
-        if interval is None:
-            return new, None
-        if forecast:
-            return new, [_forecast_outs([new[k].t], {name: v[k:k + 1] for name, v in rows.items()})[0] if act[k] else None for k in range(self.S)]
-        m, lo, hi, em, el, eu = rows
-        return new, [PfOut(new[k].t, new[k].observation, float(em[k]), CredibleInterval(float(el[k]), float(eu[k])), m[k].copy(),
-                           [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k], hi[k])]) if act[k] else None for k in range(self.S)]
+        return new, act, rest
+
+    def _raise_series(self, rc, empty_ok=False, fc_rc=None, stepping=False):
+        """Raise the first series' own status, as the reference throws from its filter: ``rc[k]`` -- "it has no records" for
+        CSSM_EINVAL_ARG where the call runs a fleet with an empty series (``empty_ok``), else "its weights were unusable" (a step may
+        also have met a series without a cloud) --, then ``fc_rc[k]``, a refused forecast, with the library's own text."""
+        for k in range(self.S):
+            if rc is not None and rc[k]:
+                why = ("it has no records" if empty_ok and rc[k] == _abi.CSSM_EINVAL_ARG else
+                       "its weights were unusable" + (" (or it has no cloud)" if stepping else ""))
+                raise _abi.CssmError(int(rc[k]), f"series {k}: {why}")
+            if fc_rc is not None and fc_rc[k]:
+                raise _abi.CssmError(int(fc_rc[k]), self._fleet.lib.cssm_last_error().decode()
+                                     or f"series {k}: its forecast{' was' if stepping else 's were'} refused")
 
     def llFilter(self, datas: Sequence[Sequence[TimedObservation]]) -> np.ndarray:
         ll, _, _, rc = self._fleet.ll_filter([split_data(d) for d in datas])
-        for k in range(self.S):
-            if rc[k]:
-                raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable")
+        self._raise_series(rc)
         self._states = []
         return ll
 
@@ -1387,9 +1375,7 @@ class FilterFleet:
         of length T_k + 1, the first entry at the slice's smallest time."""
         split = [split_data(d) for d in datas]
         ll, _, _, paths, _, rc = self._fleet.filter(split)
-        for k in range(self.S):
-            if rc[k]:
-                raise _abi.CssmError(int(rc[k]), f"series {k}: its weights were unusable")
+        self._raise_series(rc)
         self._states = []
         out = []
         for k, (t, _, _) in enumerate(split):
@@ -1403,9 +1389,7 @@ class FilterFleet:
         state), entry s + 1 after datum s.  ``formats.pfout_csv`` writes the reference's ``Filtered.csv`` lines from them."""
         split = [split_data(d) for d in datas]
         _, _, _, rows, rc = self._fleet.filter_intervals(split, float(interval))
-        for k in range(self.S):
-            if rc[k]:
-                raise _abi.CssmError(int(rc[k]), f"series {k}: " + ("it has no records" if rc[k] == _abi.CSSM_EINVAL_ARG else "its weights were unusable"))
+        self._raise_series(rc, empty_ok=True)
         self._states = []
         return [_interpolate_outs(datas[k], split[k][0], rows[k]) for k in range(self.S)]
 
@@ -1415,11 +1399,7 @@ class FilterFleet:
         ``getMeanForecast`` takes there by default.  ``formats.forecast_out_csv`` writes the reference's lines from them."""
         split = [split_data(d) for d in datas]
         _, _, _, fc, rc, fc_rc = self._fleet.filter_forecasts(split, float(interval))
-        for k in range(self.S):
-            if rc[k]:
-                raise _abi.CssmError(int(rc[k]), f"series {k}: " + ("it has no records" if rc[k] == _abi.CSSM_EINVAL_ARG else "its weights were unusable"))
-            if fc_rc[k]:
-                raise _abi.CssmError(int(fc_rc[k]), self._fleet.lib.cssm_last_error().decode() or f"series {k}: its forecasts were refused")
+        self._raise_series(rc, empty_ok=True, fc_rc=fc_rc)
         self._states = []
         return [_forecast_outs([float(v) for v in split[k][0]], fc[k]) for k in range(self.S)]
 
@@ -1429,9 +1409,7 @@ class FilterFleet:
         ``(ll, [PfOut])`` of length T_k + 1.  The fleet's current states stay valid: the clouds are not touched."""
         split = [split_data(d) for d in datas]
         ll, rows, rc = self._fleet.interpolate(split, float(interval), reference_pairing)
-        for k in range(self.S):
-            if rc[k]:
-                raise _abi.CssmError(int(rc[k]), f"series {k}: " + ("it has no records" if rc[k] == _abi.CSSM_EINVAL_ARG else "its weights were unusable"))
+        self._raise_series(rc, empty_ok=True)
         return [(float(ll[k]), _interpolate_outs(datas[k], split[k][0], rows[k])) for k in range(self.S)]
 
     def interpolate_last_ms(self) -> Tuple[float, float]:
@@ -1475,10 +1453,9 @@ class FilterFleet:
 
     def getIntervals(self) -> List[PfOut]:
         """``ParticleFilter.getIntervals`` (:415-424) of every series' current state."""
-        m, lo, hi, em, el, eu = self._fleet.summary(0.975)
+        rows = self._fleet.summary(0.975)
         st = self._states if self._states and self._states[0]._generation == self._fleet.generation else None
-        return [PfOut(st[k].t if st else float("nan"), st[k].observation if st else None, float(em[k]), CredibleInterval(float(el[k]), float(eu[k])),
-                      m[k], [CredibleInterval(a, b) for a, b in zip(lo[k], hi[k])]) for k in range(self.S)]
+        return [_pfout(st[k].t if st else float("nan"), st[k].observation if st else None, rows, k, bound=lambda v: v) for k in range(self.S)]
 
 
 class ParticleFilter:
@@ -1603,11 +1580,17 @@ class ParticleFilter:
 def _interpolate_outs(data: Sequence[TimedObservation], t, arrays) -> List[PfOut]:
     """The ``PfOut`` list of one interpolated series (examples/Interpolate.scala:42-44) from ``(mean[T + 1, d], lower, upper,
     eta_of_mean[T + 1], eta_lower, eta_upper)``: entry 0 at the smallest time without an observation, entry s + 1 datum s."""
-    m, lo, hi, em, el, eu = arrays
     times = [float(np.min(t))] + [float(v) for v in t]
     obs = [None] + [d.observation for d in data]
-    return [PfOut(times[k], obs[k], float(em[k]), CredibleInterval(float(el[k]), float(eu[k])), m[k].copy(),
-                  [CredibleInterval(float(a), float(b)) for a, b in zip(lo[k], hi[k])]) for k in range(len(times))]
+    return [_pfout(times[k], obs[k], arrays, k) for k in range(len(times))]
+
+
+def _pfout(t, obs, arrays, index, bound=float) -> PfOut:
+    """The ``PfOut`` at ``(t, obs)`` of row ``index`` of ``(mean, lower, upper, eta_of_mean, eta_lower, eta_upper)``, the state a copy
+    (``bound``: what a state interval's bounds are made of -- ``getIntervals`` hands numpy's scalars on as they are)."""
+    m, lo, hi, em, el, eu = arrays
+    return PfOut(t, obs, float(em[index]), CredibleInterval(float(el[index]), float(eu[index])), m[index].copy(),
+                 [CredibleInterval(bound(a), bound(b)) for a, b in zip(lo[index], hi[index])])
 
 
 def _forecast_outs(times: Sequence[float], r) -> List[ForecastOut]:

@@ -237,19 +237,10 @@ def pmmh_native_fleet(unparam: UnparamModel, inits: Sequence[Parameters], datas,
     elif fleet.S != S or fleet.n != int(n):
         raise ValueError(f"the fleet holds {fleet.S} series of {fleet.n} particles, the run needs {S} of {n}")
     try:
-        nt = theta0.shape[1]
-        ll = np.zeros((S, iters)); th = np.zeros((S, iters, nt)); acc = np.zeros((S, iters), dtype=np.int32); last = np.zeros((S, iters, fleet.d))
-        sd = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
-        dp, u64 = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-        fleet.generation += 1
-        _abi.check(fleet.lib.cssm_fleet_pmmh_run(fleet._h, desc.ptr(), theta0.ctypes.data_as(dp), nt, float(delta), off.ctypes.data_as(u64),
-                                                 t.ctypes.data_as(dp), y.ctypes.data_as(dp), has.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                 sd.ctypes.data_as(u64), int(iters), ll.ctypes.data_as(dp), th.ctypes.data_as(dp),
-                                                 acc.ctypes.data_as(C.POINTER(C.c_int32)), last.ctypes.data_as(dp)))
+        return fleet.pmmh_run(desc, theta0, delta, off, t, y, has, seeds, iters)
     finally:
         if own:
             fleet.close()
-    return ll, th, acc, last
 
 
 def pmmh_native_speculative(unparam: UnparamModel, init: Parameters, data, n: int, delta: float, iters: int,
