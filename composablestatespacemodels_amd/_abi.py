@@ -32,6 +32,8 @@ FLEET_MAX_N = 4096   # CSSM_FLEET_MAX_N
 CSSM_OPT_INTERP_CAP = 13
 CSSM_INTERP_REFERENCE_PAIRING = 1
 CSSM_FLEET_NO_ROWS = 0xFFFFFFFF
+CSSM_OPT_FORECAST_CAP = 11
+CSSM_SIM_STEP_ROW0 = 0xFFFFFFFF   # include/cssm_obs_draws.h: the step of the observation drawn at t0
 
 _dp = C.POINTER(C.c_double)
 
@@ -112,6 +114,9 @@ SYMBOLS = [
     ("cssm_pf_forecast_last_ms", C.c_int, [_h, _dp]),
     ("cssm_pf_observation_index", C.c_uint64, [_h]),
     ("cssm_obs_draw", C.c_int, [C.c_int, _dp, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_uint32, _dp, C.c_int]),
+    ("cssm_simulate", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, _dp, C.c_size_t, C.c_size_t, C.c_int, _dp]),
+    ("cssm_simulate_from", C.c_int, [_descp, C.c_uint64, C.c_uint64, _dp, C.c_uint32, C.c_double, _dp, C.c_size_t, C.c_size_t, C.c_int, _dp]),
+    ("cssm_simulate_last_ms", C.c_int, [_dp]),
     ("cssm_pf_interpolate", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_resample_systematic", C.c_int, [_dp, C.c_size_t, C.c_double, _u32p, C.c_int]),
     ("cssm_resample", C.c_int, [C.c_int, _dp, C.c_size_t, C.c_double, C.c_uint64, C.c_uint32, _u32p, C.c_int]),
@@ -195,6 +200,8 @@ SYMBOLS = [
     ("cssm_fleet_forecast", C.c_int, [_h, _u64p, _dp, _u64p, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_fleet_forecast_posterior", C.c_int, [_h, _descp, _u64p, _dp, C.c_size_t, _dp, _dp, _u64p, _dp, _u32p, _u64p, C.c_double,
                                                 _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_simulate", C.c_int, [_h, C.c_uint64, _dp, _u64p, _dp, _u64p, _dp, C.POINTER(C.c_int)]),
+    ("cssm_fleet_simulate_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_interpolate", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_fleet_interpolate_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_window", C.c_int, [_h, C.c_uint32]),

@@ -21,6 +21,8 @@
 #include "cssm_fleet.hip.h"
 #include "cssm_fleet_forecast.hip.h"
 #include "cssm_fleet_interp.hip.h"
+#include "cssm_simulate.hip.h"
+#include "cssm_simulate_plan.h"
 
 static_assert(CSSM_FLEET_MAX_N <= 4096, "k_fleet_summary sorts at most 4096 keys in LDS; k_fleet_series holds 12 bytes per particle there");
 
@@ -89,6 +91,10 @@ struct cssm_fleet {
   FleetBuf d_fc_samp;                   // the samples of one chunk of series (at most fc_samp_max bytes: CSSM_OPT_FORECAST_CAP)
   FleetBuf d_ip, h_ip{true};            // one chunk of cssm_fleet_interpolate as staged (FleetIpStage) and its pinned mirror
   FleetBuf d_ip_hist;                   // ... its lineage history (clouds, then ancestors: at most ip_hist_max bytes, CSSM_OPT_INTERP_CAP)
+  FleetBuf d_sim, h_sim{true};          // cssm_fleet_simulate as staged (FleetSimStage) and its pinned mirror
+  FleetBuf d_sim_out, d_sim_carry;      // ... the rows of one chunk (at most fc_samp_max bytes, one time index at least); the states between
+                                        //     the launches of a series that is run in windows of time indices
+  float ms_simulate = -1.f;             // ... the device time of the last call (cssm_fleet_simulate_last_ms)
   std::vector<FleetSeries> h_ser;
   float ms_call = -1.f, ms_summary = -1.f, ms_forecast = -1.f;
   float ms_upload = -1.f, ms_kernel = -1.f;        // cssm_fleet_filter: ... of its last launch
@@ -1631,6 +1637,155 @@ extern "C" int cssm_fleet_interpolate_last_ms(cssm_fleet* f, double* ms2) {
   if (!f || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
   if (!f->ip_ran) return fail(CSSM_ESTATE, "no interpolation has run on this fleet (cssm_fleet_interpolate first)");
   ms2[0] = f->ms_ip[0]; ms2[1] = f->ms_ip[1];
+  return CSSM_OK;
+}
+
+// ---- SimulateData.simPompModel of every series (model/Data.scala:64-73): cssm_simulate per series, in one launch per chunk of series.
+// The fleet lends its device, stream, contract table, structure and the parameters of cssm_fleet_set_params; nothing it keeps per series
+// is read or written on the device, so no series needs a cloud and none changes.
+struct FleetSimStage {
+  size_t keys, op, start, run, recs, bytes;
+};
+static FleetSimStage fleet_sim_stage(const cssm_fleet* f, size_t rows) {
+  const size_t S = f->S;
+  FleetSimStage st;
+  st.keys = (S + 1u) * 8u;
+  st.op = st.keys + S * 8u;
+  st.start = st.op + fleet_pad8(S * sizeof(cssm_obs_params));
+  st.run = st.start + S * sizeof(SimStart);
+  st.recs = st.run + fleet_pad8(S * 4u);
+  st.bytes = st.recs + rows * CSSM_FLEET_REC_BYTES(f->d);
+  return st;
+}
+
+extern "C" int cssm_fleet_simulate(cssm_fleet* f, uint64_t n_paths, const double* t0, const uint64_t* off, const double* t, const uint64_t* keys,
+                                   double* out, int* rc_out) {
+  if (!f || !t0 || !off || !keys || !out || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (n_paths < 1 || n_paths > 0xffff0000ull) return fail(CSSM_EINVAL_ARG, "n_paths must be in [1, 2^32 - 2^16]");
+  const uint32_t S = f->S;
+  int rc = fleet_off_check(off, S);
+  if (rc) return rc;
+  if (off[S] && !t) return fail(CSSM_EINVAL_ARG, "null argument");
+  const int d = f->d;
+  const uint64_t n = n_paths, npairs = (n + 1) / 2;
+  if (npairs * S > 0x7fffffffull * 64u) return fail(CSSM_EINVAL_ARG, "%u series x %llu paths are more than one launch serves", S, (unsigned long long)n);
+  const size_t rows_all = (size_t)off[S] + S, row_doubles = (size_t)(d + 3) * n, row_bytes = row_doubles * 8u;
+  // the series' own statuses, decided before the first device call
+  std::vector<cssm_obs_params> ops(S);
+  std::vector<uint32_t> run(S, 0u);
+  std::string first_msg;
+  size_t n_run = 0;
+  for (uint32_t k = 0; k < S; ++k) {
+    const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+    rc_out[k] = CSSM_OK;
+    memset(&ops[k], 0, sizeof(cssm_obs_params));
+    int r = CSSM_OK;
+    if (b - a >= 0xffffffffull) r = fail(CSSM_EINVAL_ARG, "too many times (the row at t0 draws its observation under step 2^32 - 1)");
+    if (!r) r = cssm_obs_params_or_fail(f->base.obs_kind, f->obs_has_scale[k], f->obs_scale[k], f->base.obs_df, &ops[k]);
+    if (!r && !std::isfinite(t0[k])) r = fail(CSSM_EINVAL_ARG, "t0 is not finite");
+    if (!r) r = cssm_check_times(t + a, b - a, t0[k], "t0 =");
+    if (r) {
+      if (first_msg.empty()) first_msg = "series " + std::to_string(k) + ": " + cssm_last_error();
+      rc_out[k] = r;
+      continue;
+    }
+    run[k] = 1u;
+    n_run += b - a + 1u;
+  }
+  if (n_run) {
+    HIP_TRY(hipSetDevice(f->device));
+    const size_t RB = CSSM_FLEET_REC_BYTES(d);
+    const FleetSimStage st = fleet_sim_stage(f, rows_all);
+    if (!f->h_sim.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet simulate: %zu bytes of pinned staging", st.bytes);
+    if (!f->d_sim.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet simulate: %zu bytes of records", st.bytes);
+    unsigned long long* h_off = f->h_sim.at<unsigned long long>();
+    unsigned long long* h_keys = f->h_sim.at<unsigned long long>(st.keys);
+    cssm_obs_params* h_op = f->h_sim.at<cssm_obs_params>(st.op);
+    SimStart* h_start = f->h_sim.at<SimStart>(st.start);
+    uint32_t* h_run = f->h_sim.at<uint32_t>(st.run);
+    unsigned char* h_recs = f->h_sim.at<unsigned char>(st.recs);
+    for (uint32_t k = 0; k <= S; ++k) h_off[k] = off[k];
+    for (uint32_t k = 0; k < S; ++k) {
+      const HostModel& m = f->models[k];
+      h_keys[k] = keys[k]; h_op[k] = ops[k]; h_run[k] = run[k];
+      for (int c = 0; c < CSSM_MAX_DIM; ++c) {
+        h_start[k].m0[c] = c < d ? m.comp[c].m0 : 0.0;
+        h_start[k].sd0[c] = c < d ? std::sqrt(m.comp[c].c0) : 0.0;
+      }
+    }
+    fleet_parallel(S, n_run, [&](size_t lo, size_t hi) {
+      for (size_t k = lo; k < hi; ++k) {
+        if (!run[k]) continue;
+        const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+        unsigned char* r = h_recs + (a + k) * RB;
+        fleet_pack_rec(f->models[k], t0[k], t0[k], 0.0, 0, CSSM_SIM_STEP_ROW0, r);
+        double tp = t0[k];
+        for (size_t s = a; s < b; ++s) {
+          fleet_pack_rec(f->models[k], tp, t[s], 0.0, 0, (uint32_t)(s - a), r + (s - a + 1u) * RB);
+          tp = t[s];
+        }
+      }
+    });
+    // chunks of series whose rows fit the cap (one series at least; a series beyond the cap runs alone, in windows of time indices)
+    const size_t cap_rows = std::max<size_t>(1, f->fc_samp_max / row_bytes);
+    std::vector<uint32_t> cut(1, 0u);
+    for (uint32_t k = 0; k < S; ++k)
+      if ((size_t)(off[k + 1] + k + 1u - (off[cut.back()] + cut.back())) > cap_rows && k > cut.back()) cut.push_back(k);
+    cut.push_back(S);
+    size_t most = 0;
+    bool windows = false;
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+      const size_t rws = (size_t)(off[cut[c + 1]] + cut[c + 1] - (off[cut[c]] + cut[c]));
+      windows = windows || rws > cap_rows;
+      most = std::max(most, std::min(rws, cap_rows));
+    }
+    if (!f->d_sim_out.reserve(most * row_bytes, false)) return fail(CSSM_ENOMEM, "fleet simulate: %zu bytes of rows", most * row_bytes);
+    if (windows && !f->d_sim_carry.reserve((size_t)d * n * 8u, false)) return fail(CSSM_ENOMEM, "fleet simulate: %zu bytes of carried states", (size_t)d * n * 8u);
+    CssmTemps tmp;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    for (hipEvent_t& e : ev) HIP_TRY(tmp.event(e));
+    FleetSimArgs a;
+    a.n = n;
+    a.off = f->d_sim.at<const unsigned long long>();
+    a.keys = f->d_sim.at<const unsigned long long>(st.keys);
+    a.op = f->d_sim.at<const cssm_obs_params>(st.op);
+    a.start = f->d_sim.at<const SimStart>(st.start);
+    a.run = f->d_sim.at<const uint32_t>(st.run);
+    a.recs = f->d_sim.at<const unsigned char>(st.recs);
+    a.carry = f->d_sim_carry.at<double>();
+    a.out = f->d_sim_out.at<double>();
+    a.logtab = f->logtab.at<double>(); a.mk = f->base.mk;
+    HIP_TRY(hipEventRecord(ev[0], f->stream));
+    HIP_TRY(hipMemcpyAsync(f->d_sim.p, f->h_sim.p, st.bytes, hipMemcpyHostToDevice, f->stream));
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+      const size_t ra = (size_t)(off[cut[c]] + cut[c]), rb = (size_t)(off[cut[c + 1]] + cut[c + 1]);
+      a.k0 = cut[c]; a.n_series = cut[c + 1] - cut[c];
+      // (a chunk beyond the cap is one series: its time indices in windows of cap_rows, the states carried between them)
+      for (size_t w = 0; w < rb - ra; w += cap_rows) {
+        const size_t wn = std::min(cap_rows, rb - ra - w);
+        a.rb = (uint32_t)w; a.rn = (uint32_t)wn;
+        a.from_carry = w > 0 ? 1 : 0; a.to_carry = w + wn < rb - ra ? 1 : 0;
+        a.out_r0 = ra + w;
+        const int hrc = cssm_fleet_simulate_launch(d, a, f->stream);
+        if (hrc) return fail(CSSM_EHIP, "k_fleet_simulate: %s", hipGetErrorString((hipError_t)hrc));
+        HIP_TRY(hipMemcpyAsync(out + (ra + w) * row_doubles, f->d_sim_out.p, wn * row_bytes, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));   // (the next launch writes the same buffer)
+      }
+    }
+    HIP_TRY(hipEventRecord(ev[1], f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
+    if (hipEventElapsedTime(&f->ms_simulate, ev[0], ev[1]) != hipSuccess) f->ms_simulate = -1.f;
+  }
+  for (uint32_t k = 0; k < S; ++k)
+    if (!run[k]) std::fill(out + (size_t)(off[k] + k) * row_doubles, out + (size_t)(off[k + 1] + k + 1u) * row_doubles, cssm_nan());
+  if (!first_msg.empty()) (void)fail(CSSM_EINVAL_ARG, "%s", first_msg.c_str());   // (the call succeeds; the message names the first such series)
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_simulate_last_ms(cssm_fleet* f, double* ms) {
+  if (!f || !ms) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (f->ms_simulate < 0.f) return fail(CSSM_ESTATE, "no simulation has run on this fleet (cssm_fleet_simulate first)");
+  *ms = (double)f->ms_simulate;
   return CSSM_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "cssm_kernels.hip.h"
 #include "cssm_posterior_move.hip.h"
 #include "../../include/cssm_obs_draws.h"
+#include "cssm_simulate_plan.h"
 
 #include <cmath>
 
@@ -222,30 +223,8 @@ static __global__ __launch_bounds__(CSSM_BLOCK) void k_obs_draw(cssm_obs_params 
   }
 }
 
-// the reference's exception for a model without the scale its observation needs (model/Model.scala:150,179,214,247,291,342),
-// and LogGaussianCox.observation = ??? (:364)
-static int obs_params(int kind, int has_scale, double scale, int df, cssm_obs_params* op) {
-  const int rc = cssm_obs_params_make(kind, has_scale, scale, df, op);
-  if (rc == 0) return CSSM_OK;
-  if (rc == -1) {
-    const char* what = "";
-    switch (kind) {
-      case CSSM_OBS_GAUSSIAN: what = "Must provide SD parameter for LinearModel / No SD parameter provided to SeasonalModel"; break;
-      case CSSM_OBS_NEGBIN: what = "No scale parameter provided to Negativebinomial Model"; break;
-      case CSSM_OBS_ZIP: what = "Must provide probability parameter for zero inflated Poisson Model"; break;
-      case CSSM_OBS_STUDENT_T: what = "No scale parameter provided to Student T Model"; break;
-      default: what = "Must provide shape parameter for Beta Model"; break;
-    }
-    return fail(CSSM_EINVAL_ARG, "the observation model needs the scale parameter of the leftmost leaf (the reference throws Exception(\"%s\"))", what);
-  }
-  if (rc == -3) return fail(CSSM_EINVAL_ARG, "Student-t observations need df >= 1 (got %d)", df);
-  if (kind == CSSM_OBS_LGCP)
-    return fail(CSSM_EINVAL_ARG, "a log-Gaussian Cox process has no observation distribution to draw from "
-                                 "(the reference's LogGaussianCox.observation is ???: scala.NotImplementedError)");
-  return fail(CSSM_EINVAL_ARG, "unknown obs_kind %d", kind);
-}
-// (the fleet's forecasts refuse a series with the same words: cssm_fleet_forecast.hip.h)
-int cssm_obs_params_or_fail(int kind, int has_scale, double scale, int df, cssm_obs_params* op) { return obs_params(kind, has_scale, scale, df, op); }
+// (the observation parameters of a draw, or the reference's exception as the message: cssm_obs_params_or_fail, cssm_model.cpp)
+static int obs_params(int kind, int has_scale, double scale, int df, cssm_obs_params* op) { return cssm_obs_params_or_fail(kind, has_scale, scale, df, op); }
 
 extern "C" int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_scale, double scale, int df, uint64_t key, uint32_t step,
                              double* out, int device) {
@@ -267,18 +246,8 @@ extern "C" int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_
   return CSSM_OK;
 }
 
-// Horizon times after t_start: finite and non-decreasing (`start` names t_start in the message)
-static int check_times(const double* t, size_t H, double t_start, const char* start) {
-  for (size_t h = 0; h < H; ++h) {
-    const double prev = h ? t[h - 1] : t_start;
-    if (!std::isfinite(t[h])) return fail(CSSM_EINVAL_ARG, "t[%zu] is not finite", h);
-    if (!(t[h] >= prev)) {
-      if (h) return fail(CSSM_EINVAL_ARG, "t must be non-decreasing (t[%zu] = %.17g < %.17g)", h, t[h], prev);
-      return fail(CSSM_EINVAL_ARG, "t[%zu] = %.17g is before %s %.17g", h, t[h], start, prev);
-    }
-  }
-  return CSSM_OK;
-}
+// (horizon times after t_start, finite and non-decreasing: cssm_check_times, cssm_model.cpp)
+static int check_times(const double* t, size_t H, double t_start, const char* start) { return cssm_check_times(t, H, t_start, start); }
 
 // The chunked driver of both forecasts.  Per chunk of horizons [h0, h0 + hn): launch(h0, hn, recs of the chunk, carry, from_carry,
 // to_carry, keys, partial, samples, blocks) runs the forecast kernel (nb_f blocks, one thread per particle pair), then one radix

@@ -813,6 +813,40 @@ class NativePfFleet:
         _abi.check(self.lib.cssm_fleet_forecast(self._h, _p(off), _p(tt), _p(keys), float(interval), *ptrs, _p(samples), _p(rc)))
         return arr, samples, rc
 
+    def simulate(self, t0s, times, n_paths: int = 1, keys=None):
+        """cssm_fleet_simulate: every series drawn from its own model (the parameters of ``set_params``) in one launch per chunk.
+        ``t0s``: S start times (a scalar serves every series); ``times``: S arrays (None / empty: the row at t0 alone); ``keys``: S
+        Philox keys (None: ``simulate.fleet_keys(self.seeds)`` = cssm_pf_run_key(seed_k, 2^62 | k)).  ``([rows of series k: [T_k + 1,
+        d + 3, n_paths]], rc[S])`` -- per series what ``simulate.simulate`` returns under its model, key and times; the rows of a
+        series whose rc is not zero read NaN.  The fleet is not touched and no series needs a cloud."""
+        off, t = self.pack_times(times)
+        t0 = np.asarray(t0s, dtype=np.float64)
+        if t0.ndim != 0 and t0.shape != (self.S,):
+            raise ValueError("one t0 per series (or one for all)")
+        t0 = np.ascontiguousarray(np.broadcast_to(t0, (self.S,)), dtype=np.float64)
+        if keys is None:
+            from .simulate import fleet_keys
+            keys = fleet_keys(self.seeds)
+        if len(keys) != self.S:
+            raise ValueError("one key per series")
+        ky = np.ascontiguousarray([int(x) & (2**64 - 1) for x in keys], dtype=np.uint64)
+        out, rc = self.simulate_packed(t0, off, t, ky, n_paths)
+        return self._split(off, out, 1), rc
+
+    def simulate_packed(self, t0, off, t, keys, n_paths: int = 1):
+        """``simulate`` on float64 t0[S], the arrays ``pack_times`` made and uint64 keys[S]: ``(rows [off[-1] + S, d + 3, n_paths], rc[S])``,
+        series k's rows at ``off[k] + k .. off[k + 1] + k``."""
+        R = int(off[-1])
+        tt = t if R else np.zeros(1)
+        out = np.zeros((R + self.S, self.d + 3, int(n_paths)))
+        rc = np.zeros(self.S, dtype=np.int32)
+        _abi.check(self.lib.cssm_fleet_simulate(self._h, int(n_paths), _p(t0), _p(off), _p(tt), _p(keys), _p(out), _p(rc)))
+        return out, rc
+
+    def simulate_last_ms(self) -> float:
+        """Device time (ms: upload, kernels, read-back) of the last ``simulate``."""
+        return self._ms(self.lib.cssm_fleet_simulate_last_ms, 1)[0]
+
     def posterior_key(self, k: int) -> int:
         """The default Philox key of series k's posterior forecast: cssm_pf_run_key(seed_k, 2^63) -- ``forecast_key()`` of a fresh
         ``NativePf`` with that seed, the handle ``ParticleFilter.forecastPosterior`` makes."""
@@ -1446,6 +1480,18 @@ class FilterFleet:
             if r["rc"]:
                 raise _abi.CssmError(r["rc"], self._fleet.lib.cssm_last_error().decode() or f"series {k}: its posterior forecast was refused")
         return [_forecast_outs(ts[k], rs[k]) for k in range(self.S)]
+
+    def simulate(self, t0s, timess, seed: Optional[int] = None):
+        """``SimulateData(mods[k]).simPompModel(t0s[k])(timess[k])`` of every sensor in one device call: per sensor the list of its
+        ``simulate.SimulatedPoint`` (the point at t0, then one per time) -- data that ``llFilter`` / ``filter`` take as they are.  Series
+        k draws under cssm_pf_run_key(seed_k, 2^62 | k), seed_k its filter key (``seed`` given: that of ``keys(seed, S)``).  The fleet's
+        clouds are not touched."""
+        from .simulate import fleet_keys, points_of
+        seeds = self._fleet.seeds if seed is None else self.keys(seed, self.S)
+        t0 = np.broadcast_to(np.asarray(t0s, dtype=np.float64), (self.S,))
+        rows, rc = self._fleet.simulate(t0, timess, 1, fleet_keys(seeds))
+        self._raise_series(None, fc_rc=rc)
+        return [points_of(float(t0[k]), [] if timess[k] is None else timess[k], rows[k]) for k in range(self.S)]
 
     def getMeanForecast(self, ts, interval: float, seed: Optional[int] = None) -> List[ForecastOut]:
         """``ParticleFilter.getMeanForecast`` (:389-409) of every series: one horizon each, ``ts[k]`` its time."""

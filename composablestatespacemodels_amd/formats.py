@@ -13,6 +13,9 @@ Reference (paths relative to src/main/scala/com/github/jonnylaw/model/):
   is recognised by the NUMBER of fields (3 Brownian, 4 GenBrownian, 5 OU) -- jsonFormats.scala:29-77.
 * ``MetropState`` ``{"ll", "params", "sde": {"time", "state"}, "accepted"}`` -- jsonFormats.scala:121-122,
   written one per line by Streaming.pmmhToJson (Streaming.scala:42-58).
+* A simulated point (``ObservationWithState``): the ``Show[Data]`` line ``t, y, eta, gamma, state...`` CsvFormat.scala:19 and the JSON
+  object ``{"t", "observation", "eta", "gamma", "sdeState"}`` of ``jsonFormat5`` jsonFormats.scala:124, as ``Streaming.dataCsvSink`` /
+  ``dataJsonSink`` write them (Streaming.scala:176-185).
 * CSV lines of ``Parameters`` / ``MetropState`` / ``PfOut`` -- CsvFormat.scala:33-47,53-61,75-83; of ``ForecastOut`` --
   CsvFormat.scala:84-85, whose intervals print through the case class's ``toString`` (``CredibleInterval(l,u)``).
 """
@@ -26,6 +29,7 @@ import numpy as np
 from .filter import CredibleInterval, ForecastOut, PfOut, StateSpace
 from .model import (BrownianParameter, GenBrownianParameter, OuParameter, ParamNode, Parameters, TimedObservation)
 from .pmmh import MetropState
+from .simulate import SimulatedPoint
 
 
 # --------------------------------------------------------------------------- observations
@@ -69,6 +73,46 @@ def write_json_observations(path: str, data: Iterable[TimedObservation]) -> None
     with open(path, "w") as f:
         for d in data:
             f.write(observation_to_json(d) + "\n")
+
+
+# --------------------------------------------------------------------------- simulated points
+def simulated_csv(p: SimulatedPoint) -> str:  # Show[Data], the ObservationWithState case, CsvFormat.scala:19
+    y = "NA" if p.observation is None else repr(float(p.observation))
+    return f"{p.t}, {y}, {repr(float(p.eta))}, {repr(float(p.gamma))}, " + ", ".join(repr(float(v)) for v in p.sdeState)
+
+
+def simulated_from_csv(line: str) -> SimulatedPoint:
+    """The inverse of simulated_csv (the latent dimension follows from the number of fields)."""
+    f = [x.strip() for x in line.strip().split(",")]
+    if len(f) < 5:
+        raise ValueError("a simulated point's line has 4 + d fields")
+    return SimulatedPoint(float(f[0]), None if f[1] in ("", "NA") else float(f[1]), float(f[2]), float(f[3]), np.array([float(v) for v in f[4:]]))
+
+
+def simulated_to_json(p: SimulatedPoint, leaf_dims: Sequence[int]) -> str:
+    o = {"t": p.t}
+    if p.observation is not None:   # (spray omits a None field)
+        o["observation"] = p.observation
+    o.update({"eta": p.eta, "gamma": p.gamma, "sdeState": state_to_json_obj(p.sdeState, leaf_dims)})
+    return json.dumps(o)
+
+
+def simulated_from_json(s: str) -> SimulatedPoint:
+    o = json.loads(s)
+    return SimulatedPoint(float(o["t"]), None if o.get("observation") is None else float(o["observation"]), float(o["eta"]), float(o["gamma"]),
+                          state_from_json_obj(o["sdeState"]))
+
+
+def write_csv_simulated(path: str, data: Iterable[SimulatedPoint]) -> None:  # Streaming.dataCsvSink, Streaming.scala:180-185
+    with open(path, "w") as f:
+        for p in data:
+            f.write(simulated_csv(p) + "\n")
+
+
+def write_json_simulated(path: str, data: Iterable[SimulatedPoint], leaf_dims: Sequence[int]) -> None:  # Streaming.dataJsonSink, :176-178
+    with open(path, "w") as f:
+        for p in data:
+            f.write(simulated_to_json(p, leaf_dims) + "\n")
 
 
 # --------------------------------------------------------------------------- state

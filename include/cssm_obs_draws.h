@@ -50,6 +50,16 @@ extern "C++" {
 #endif
 
 #define CSSM_STREAM_OBS 8u          /* observation draws of forecasts: counter (key, gid, horizon, 8, block) */
+/* Simulations from the model (cssm_simulate, cssm_fleet_simulate: SimulateData.simPompModel) under Philox key `key`, n_paths paths:
+ *   x0 of path i      CSSM_STREAM_INIT, gid i, step 0, the paired streams of draw_normals -- the initial draw of a filter of n_paths
+ *                     particles whose key is `key`;
+ *   time index h >= 1 the transition into it on CSSM_STREAM_STEP (paired streams; the unpaired last path of an odd count draws alone)
+ *                     and its observation on CSSM_STREAM_OBS (gid i), both under step h - 1 -- horizon h - 1 of cssm_pf_forecast under
+ *                     the same key;
+ *   time index 0      no transition; its observation on CSSM_STREAM_OBS under step CSSM_SIM_STEP_ROW0, which no horizon can take
+ *                     (a call holds fewer than 2^32 - 1 times).
+ * cssm_simulate_from continues a simulation: time index j of the call moves and draws under step first_step + j. */
+#define CSSM_SIM_STEP_ROW0 0xFFFFFFFFu
 #define CSSM_OBS_PTRS_MIN 10.0      /* Poisson: inversion below, PTRS from here on */
 #define CSSM_OBS_NORMAL_MIN 0x1.0p52 /* Poisson: the normal limit from here on */
 #define CSSM_OBS_MAX_ATTEMPTS 64

@@ -449,6 +449,35 @@ uint64_t cssm_pf_observation_index(const cssm_pf* pf);
 int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_scale, double scale, int df, uint64_t key, uint32_t step,
                   double* out, int device);
 
+/* SimulateData(m).simPompModel(t0) over given times (model/Data.scala:64-73, simStep :186-193; examples/Simulation.scala): n_paths
+ * independent realisations of the model itself, drawn on the device.  Stateless, like cssm_obs_draw and cssm_resample.  Time index 0 is
+ * t0, time index h >= 1 is t[h - 1]; t finite, not before t0, non-decreasing (dt = 0 allowed).  out (host): (T + 1) x (d + 3) x n_paths
+ * doubles in the layout of the forecasts' samples -- row r of time index h for path i at out[(h (d + 3) + r) n_paths + i], the rows
+ * being the d states, gamma = f(x, t), eta = link(gamma) and obs = one draw of mod.observation(gamma).
+ * Counters (include/cssm_obs_draws.h): x0 of path i is the initial draw of a filter of n_paths particles whose Philox key is `key`
+ * (CSSM_STREAM_INIT, id i, step 0, paired streams); the transition into time index h >= 1 and that index's observation use step h - 1 on
+ * CSSM_STREAM_STEP (paired streams) / CSSM_STREAM_OBS -- horizon h - 1 of cssm_pf_forecast under the same key; the observation of time
+ * index 0 is drawn on CSSM_STREAM_OBS under step CSSM_SIM_STEP_ROW0 = 2^32 - 1.  Hence, for a handle of n_paths particles after
+ * cssm_pf_reseed(key) and cssm_pf_init(t0): the states of time index 0 are cssm_pf_get_particles, and time indices 1 .. T are the
+ * samples of cssm_pf_forecast(t, T, key, ...), bit for bit.
+ * rows_per_launch: time indices one launch covers (0: as many as keep a launch's rows within 1 GiB); the states are carried on the device
+ * between launches and the result does not depend on it.
+ * Errors, all but the last decided before the first device call, with nothing written to out: CSSM_EINVAL_ARG (null desc / out, null t
+ * with T > 0; n_paths outside [1, 2^32 - 2^16]; T >= 2^32 - 1; t0 or a time not finite, a time before t0 or decreasing; LGCP, whose
+ * observation the reference leaves unimplemented -- simLGCP is another algorithm and not served; a model without the scale its
+ * observation needs, with the reference's exception named; Student-t with df < 1), CSSM_EINVAL_DESC (a descriptor cssm_pf_create
+ * refuses), CSSM_EHIP without a device. */
+int cssm_simulate(const cssm_model_desc* desc, uint64_t n_paths, uint64_t key, double t0, const double* t, size_t T, size_t rows_per_launch,
+                  int device, double* out);
+/* A simulation continued (SimulateData.simMarkov / simRegular in blocks): the paths stand at x (d x n_paths, x[k n_paths + i], finite) at
+ * time t0 and move through t[0 .. T); time index j of THIS call moves and draws under step first_step + j, so blocks that hand on their last
+ * states and count their steps on are one cssm_simulate.  out: T x (d + 3) x n_paths (no row at t0).  first_step + T must not pass
+ * 2^32 - 1.  Errors as cssm_simulate's, and a null or non-finite x. */
+int cssm_simulate_from(const cssm_model_desc* desc, uint64_t n_paths, uint64_t key, const double* x, uint32_t first_step, double t0,
+                       const double* t, size_t T, size_t rows_per_launch, int device, double* out);
+/* Device time (ms, HIP events around its kernels) of the calling thread's last cssm_simulate / cssm_simulate_from; CSSM_ESTATE before one. */
+int cssm_simulate_last_ms(double* ms);
+
 /* FilterInterpolate (model/ParticleFilter.scala:273-311, ParticleFilter.interpolate :335-337): the filter whose
  * particles are whole paths, so that a weighted step resamples the paths and missing observations are
  * interpolated by the surviving lineages.  The forward pass keeps the history of clouds and ancestor arrays on the
@@ -964,6 +993,23 @@ int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const double* t, con
                         double* eta_mean, double* eta_lower, double* eta_upper,
                         double* obs_mean, double* obs_lower, double* obs_upper,
                         double* samples, int* rc_out);
+/* SimulateData.simPompModel of every series in one launch per chunk: series k is simulated under its own parameters (those of
+ * cssm_fleet_set_params), its own Philox key keys[k], from its own t0[k] over its own ragged times t[off[k] .. off[k + 1]) (off as for
+ * cssm_fleet_forecast; T_k = 0 is allowed).  Every series gets its row at t0, so out (host) holds off[S] + S time indices of
+ * (d + 3) x n_paths doubles each, series k's starting at index off[k] + k -- the indexing of cssm_fleet_filter's path_out.  n_paths is the
+ * call's own (the fleet's N plays no part).  One thread per (series, pair of paths), flattened over the grid.
+ * Series k's block is bit for bit cssm_simulate(descs[k], n_paths, keys[k], t0[k], t_k, T_k, ...).
+ * The fleet is not touched: clouds, ancestors, clocks, keys, windows, ll and ESS stay as they were; no series needs a cloud.
+ * rc_out[S] = the series' OWN status: CSSM_EINVAL_ARG for a t0 or times that are not finite, times before t0[k] or decreasing,
+ * T_k >= 2^32 - 1, and for a model without the scale its observation needs (cssm_last_error names the first such series although the call
+ * succeeds).  Such a series' rows read NaN; every other series is what it is without it.  The call itself fails, before any device call,
+ * for a null f / t0 / off / keys / out / rc_out (t too when off[S] > 0), n_paths outside [1, 2^32 - 2^16], off[0] != 0 or off decreasing.
+ * The fleet runs in chunks of series whose rows fit CSSM_OPT_FORECAST_CAP on the device; a single series beyond the cap runs in windows
+ * of time indices with its states carried on the device.  The result does not depend on the cap. */
+int cssm_fleet_simulate(cssm_fleet* f, uint64_t n_paths, const double* t0, const uint64_t* off, const double* t, const uint64_t* keys,
+                        double* out, int* rc_out);
+/* Device time (ms: upload, kernels, read-back) of the fleet's last cssm_fleet_simulate; CSSM_ESTATE before one. */
+int cssm_fleet_simulate_last_ms(cssm_fleet* f, double* ms);
 /* Posterior-predictive forecasts of every series in one launch: SimulateData.forecast(unparamModel, t, n)(posterior) + summariseForecast
  * (model/Data.scala:196-231) per series, each under its OWN joint posterior sample -- what S chains of cssm_fleet_pmmh_run leave.
  * Ragged posteriors: series k owns the pairs moff[k] .. moff[k+1]-1 (moff[0] = 0, non-decreasing, S + 1 entries; M_k = their number);
