@@ -34,6 +34,9 @@ CSSM_INTERP_REFERENCE_PAIRING = 1
 CSSM_FLEET_NO_ROWS = 0xFFFFFFFF
 CSSM_OPT_FORECAST_CAP = 11
 CSSM_SIM_STEP_ROW0 = 0xFFFFFFFF   # include/cssm_obs_draws.h: the step of the observation drawn at t0
+CSSM_LGCP_SIM_KEEP_GRID = 1       # cssm_simulate_lgcp: download the grid rows too
+CSSM_STREAM_THIN = 10             # include/cssm_obs_draws.h: the candidates of simLGCP's thinning
+CSSM_LGCP_PATH_OK, CSSM_LGCP_PATH_NONFINITE, CSSM_LGCP_PATH_TOO_MANY = 0, 1, 2   # a path's status
 
 _dp = C.POINTER(C.c_double)
 
@@ -117,6 +120,14 @@ SYMBOLS = [
     ("cssm_simulate", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, _dp, C.c_size_t, C.c_size_t, C.c_int, _dp]),
     ("cssm_simulate_from", C.c_int, [_descp, C.c_uint64, C.c_uint64, _dp, C.c_uint32, C.c_double, _dp, C.c_size_t, C.c_size_t, C.c_int, _dp]),
     ("cssm_simulate_last_ms", C.c_int, [_dp]),
+    ("cssm_simulate_lgcp", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_h)]),
+    ("cssm_lgcp_sim_shape", C.c_int, [_h, C.POINTER(C.c_int), _u64p, _u64p, _u64p]),
+    ("cssm_lgcp_sim_grid_times", C.c_int, [_h, _dp]),
+    ("cssm_lgcp_sim_grid", C.c_int, [_h, _dp]),
+    ("cssm_lgcp_sim_paths", C.c_int, [_h, _u64p, _dp, _u32p, _i32p]),
+    ("cssm_lgcp_sim_events", C.c_int, [_h, _dp, _u32p, _dp]),
+    ("cssm_lgcp_sim_destroy", None, [_h]),
+    ("cssm_simulate_lgcp_last_ms", C.c_int, [_dp]),
     ("cssm_pf_interpolate", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_resample_systematic", C.c_int, [_dp, C.c_size_t, C.c_double, _u32p, C.c_int]),
     ("cssm_resample", C.c_int, [C.c_int, _dp, C.c_size_t, C.c_double, C.c_uint64, C.c_uint32, _u32p, C.c_int]),

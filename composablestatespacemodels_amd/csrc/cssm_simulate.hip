@@ -27,17 +27,6 @@ struct SimRec {
   const double* __restrict__ fco;
 };
 
-// the pair's d + 3 rows of one time index: out[r n + i], r = the d states, gamma, eta, obs.  An even n keeps every row 16-byte aligned
-// at an even path, so the pair goes out as one 16-byte store per row and a wave writes 1 KiB of consecutive bytes.
-__device__ __forceinline__ void sim_store(double* __restrict__ row, uint64_t ia, bool hasb, bool vec, double va, double vb) {
-  if (vec) {
-    *reinterpret_cast<double2*>(row + ia) = make_double2(va, vb);
-  } else {
-    row[ia] = va;
-    if (hasb) row[ia + 1] = vb;
-  }
-}
-
 // Time indices g0 .. g0 + hc - 1 of one pair.  `row0`: time index 0 is the row at t0 (no transition, CSSM_SIM_STEP_ROW0); every other
 // time index g moves and draws under step step_base + g - row0.  rec(j) = the record of time index g0 + j.
 template <int D, class RecAt>
@@ -81,20 +70,7 @@ __device__ __forceinline__ void sim_rows(const ModelK& mk, const cssm_obs_params
   }
 }
 
-// where a pair starts: the initial draw (initialiseState, model/ParticleFilter.scala:105-108: k_init's statement) or the carried states
-template <int D>
-__device__ __forceinline__ void sim_begin(const SimStart& st, const double* __restrict__ carry, int from_carry, uint64_t key, uint64_t n, uint64_t i,
-                                          const double* tab, double (&x)[D]) {
-  if (from_carry) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) x[k] = carry[(size_t)k * n + i];
-  } else {
-    double z[D];
-    draw_normals<D>(key, i, 0u, CSSM_STREAM_INIT, tab, z);
-#pragma unroll
-    for (int k = 0; k < D; ++k) x[k] = st.sd0[k] * z[k] + st.m0[k];
-  }
-}
+// where a pair leaves its states for the next launch (sim_begin, which picks them up, and sim_store: cssm_simulate.hip.h)
 template <int D>
 __device__ __forceinline__ void sim_end(double* __restrict__ carry, uint64_t n, uint64_t ia, bool hasb, const double (&xa)[D], const double (&xb)[D]) {
 #pragma unroll

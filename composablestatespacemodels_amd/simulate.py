@@ -6,6 +6,10 @@ Low level: ``simulate`` (n_paths realisations over given times, rows ``[T + 1, d
 ``SimulateData(model).simPompModel(t0)(times)``, ``.simMarkov(dt)`` / ``.simRegular(dt)`` / ``.observations`` (lazy, simulated in blocks
 of rows on the device) and ``.simStep(dt)``, all returning ``SimulatedPoint`` -- one ``ObservationWithState`` (Data.scala:31-36).
 
+Event series of a log-Gaussian Cox process come from ``cssm_simulate_lgcp`` (csrc/cssm_simulate_lgcp.hip), the reference's thinning
+(``simLGCP``, Data.scala:110-149): ``simulate_lgcp`` (n_paths realisations, an ``LgcpSim``), ``SimulateData(model).simLGCP(start, end,
+precision)`` (one path, the reference's vector) and ``lgcp_events_data`` (the chronological events as a filter takes them).
+
 Keys.  ``SimulateData(model, seed)`` draws under ``cssm_pf_run_key(seed, 2^62)``; a fleet's series k under
 ``cssm_pf_run_key(seed_k, 2^62 | k)`` (``fleet_keys``).  Run numbers with bit 62 set and bit 63 clear are taken by nothing else: filters
 run under ``cssm_pf_run_key(seed, k)`` with k a small series or chain index, forecasts under ``cssm_pf_run_key(seed, 2^63 | observation
@@ -15,11 +19,12 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Callable, Iterable, Iterator, List, Optional, Sequence
+from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Union
 
 import numpy as np
 
 from . import _abi
+from ._abi import CssmError
 from .model import Model, TimedObservation
 
 SIM_RUN = 1 << 62
@@ -102,6 +107,84 @@ def points_of(t0: Optional[float], times, rows: np.ndarray, path: int = 0) -> Li
     return [SimulatedPoint(ts[h], float(r[d + 2, path]), float(r[d + 1, path]), float(r[d, path]), r[:d, path].copy()) for h, r in enumerate(rows)]
 
 
+@dataclass(frozen=True)
+class LgcpSim:
+    """What ``cssm_simulate_lgcp`` returns, for every path: the grid (``grid_t [G]``; ``grid [G, d + 3, n_paths]`` -- the d states, gamma,
+    eta, obs = 0.0 -- or None when it was not kept) and the events in path order (path i owns ``ev_off[i] .. ev_off[i + 1] - 1``, in time
+    order: ``ev_t``, the grid index ``ev_idx`` and ``ev_rows [E, d + 3]`` -- the states at that index, gamma, eta, 1.0), with the bound
+    ``upper``, the ``candidates`` taken and the ``status`` (non-zero: the path was not thinned, include/cssm_obs_draws.h) per path."""
+    grid_t: np.ndarray
+    grid: Optional[np.ndarray]
+    ev_off: np.ndarray
+    ev_t: np.ndarray
+    ev_idx: np.ndarray
+    ev_rows: np.ndarray
+    upper: np.ndarray
+    candidates: np.ndarray
+    status: np.ndarray
+
+    def events(self, path: int = 0) -> List[SimulatedPoint]:
+        """The events of one path in time order, each with the state of the grid point before it (observation 1.0)."""
+        a, b = int(self.ev_off[path]), int(self.ev_off[path + 1])
+        d = self.ev_rows.shape[1] - 3
+        return [SimulatedPoint(float(self.ev_t[e]), float(r[d + 2]), float(r[d + 1]), float(r[d]), r[:d].copy())
+                for e, r in zip(range(a, b), self.ev_rows[a:b])]
+
+    def points(self, path: int = 0) -> List[SimulatedPoint]:
+        """The reference's vector (Data.scala:138,144-148): the events newest first, then every grid point in time order (observation
+        0.0).  Needs the grid (``keep_grid``)."""
+        if self.grid is None:
+            raise ValueError("the grid rows were not kept (keep_grid=False): only events() can be formed")
+        return self.events(path)[::-1] + points_of(None, self.grid_t, self.grid, path)
+
+
+def simulate_lgcp(model: Model, start: float, end: float, precision: int, n_paths: int = 1, key: Optional[int] = None, keep_grid: bool = True,
+                  device: int = 0, paths_per_launch: int = 0) -> LgcpSim:
+    """cssm_simulate_lgcp: ``n_paths`` realisations of the Cox process on ``[start, end]`` by thinning, the latent state on the grid of
+    step ``10^-precision``.  ``key``: the Philox key (None: ``sim_key(20260101)``)."""
+    lib = _abi.load_library()
+    desc = model.descriptor()
+    key = sim_key(20260101) if key is None else int(key) & _U64
+    h = C.c_void_p()
+    _abi.check(lib.cssm_simulate_lgcp(desc.ptr(), int(n_paths), key, float(start), float(end), int(precision),
+                                      _abi.CSSM_LGCP_SIM_KEEP_GRID if keep_grid else 0, int(paths_per_launch), int(device), C.byref(h)))
+    try:
+        d, n, G, E = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _abi.check(lib.cssm_lgcp_sim_shape(h, C.byref(d), C.byref(n), C.byref(G), C.byref(E)))
+        d, n, G, E = d.value, n.value, G.value, E.value
+        grid_t = np.zeros(G)
+        grid = np.zeros((G, d + 3, n)) if keep_grid else None
+        ev_off, upper = np.zeros(n + 1, dtype=np.uint64), np.zeros(n)
+        cand, status = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32)
+        ev_t, ev_idx, ev_rows = np.zeros(E), np.zeros(E, dtype=np.uint32), np.zeros((E, d + 3))
+        u64p, u32p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+        _abi.check(lib.cssm_lgcp_sim_grid_times(h, grid_t.ctypes.data_as(_dp)))
+        if keep_grid:
+            _abi.check(lib.cssm_lgcp_sim_grid(h, grid.ctypes.data_as(_dp)))
+        _abi.check(lib.cssm_lgcp_sim_paths(h, ev_off.ctypes.data_as(u64p), upper.ctypes.data_as(_dp), cand.ctypes.data_as(u32p),
+                                           status.ctypes.data_as(i32p)))
+        _abi.check(lib.cssm_lgcp_sim_events(h, ev_t.ctypes.data_as(_dp), ev_idx.ctypes.data_as(u32p), ev_rows.ctypes.data_as(_dp)))
+    finally:
+        lib.cssm_lgcp_sim_destroy(h)
+    return LgcpSim(grid_t, grid, ev_off, ev_t, ev_idx, ev_rows, upper, cand, status)
+
+
+def simulate_lgcp_last_ms() -> tuple:
+    """Device time (ms) of this thread's last ``simulate_lgcp``: (its grid kernels, its thinning launches)."""
+    ms = (C.c_double * 2)()
+    _abi.check(_abi.load_library().cssm_simulate_lgcp_last_ms(ms))
+    return float(ms[0]), float(ms[1])
+
+
+def lgcp_events_data(points_or_sim: Union[LgcpSim, Iterable[SimulatedPoint]], path: int = 0) -> List[TimedObservation]:
+    """The events of a simulated Cox process as the data of a filter: ``TimedObservation(t, 1.0)`` in time order -- from an ``LgcpSim``
+    (its path ``path``) or from the reference's vector of points (``simLGCP``: the points that observed 1.0, newest first)."""
+    if isinstance(points_or_sim, LgcpSim):
+        return [p.to_data() for p in points_or_sim.events(path)]
+    ev = [p.to_data() for p in points_or_sim if p.observation == 1.0]
+    return sorted(ev, key=lambda o: o.t)
+
+
 class SimulateData:
     """``SimulateData(model)`` of the reference (Data.scala:53-100), one path, drawn on the device under ``sim_key(seed)``."""
 
@@ -124,6 +207,21 @@ class SimulateData:
         if first_step is None:
             return simulate(self.model, t0, times, 1, key, self.device)
         return simulate_from(self.model, x, first_step, t0, times, key, self.device)
+
+    def _lgcp(self, key: int, start: float, end: float, precision: int) -> LgcpSim:
+        """The native seam of simLGCP."""
+        return simulate_lgcp(self.model, start, end, precision, 1, key, True, self.device)
+
+    def simLGCP(self, start: float, end: float, precision: int) -> List[SimulatedPoint]:
+        """Data.scala:110-149: the events on ``[start, end]`` newest first (observation 1.0), then the grid of step ``10^-precision`` in
+        time order (observation 0.0).  Raises where the reference would throw or not return: a bound that is not finite, or more
+        candidates than a path may take (include/cssm_obs_draws.h)."""
+        sim = self._lgcp(self.key, float(start), float(end), int(precision))
+        st = int(sim.status[0])
+        if st != _abi.CSSM_LGCP_PATH_OK:
+            what = "is not finite" if st == _abi.CSSM_LGCP_PATH_NONFINITE else "asks for more candidates than a path may take"
+            raise CssmError(_abi.CSSM_ENONFINITE, f"simLGCP: the upper bound of the hazard, {float(sim.upper[0])!r}, {what} (path status {st})")
+        return sim.points(0)
 
     def simPompModel(self, t0: float) -> Callable[[Iterable[float]], List[SimulatedPoint]]:
         """Data.scala:64-73: the point at ``t0``, then one per time (the Flow's scan emits its initial value first)."""

@@ -243,6 +243,56 @@ CSSM_HD double cssm_obs_draw_one(const cssm_obs_params* p, double eta, cssm_obs_
   }
 }
 
+/* ---- SimulateData.simLGCP (model/Data.scala:110-149, simSdeStream :162-176): event times of a Cox process by thinning
+ * (cssm_simulate_lgcp).  Additions only: a new stream tag, no existing counter or variate moves, so the contract version stays.
+ *
+ * Grid.  delta = 10^-precision; t_0 = start, t_k = t_(k-1) + delta (accumulated), kept while t_k <= start + (end - start).  x_0 of path i
+ * is the initial draw of a filter of n_paths particles under `key` (CSSM_STREAM_INIT, step 0, paired streams); the transition into grid
+ * index k >= 1 uses dt = delta exactly and step k - 1 on CSSM_STREAM_STEP (paired streams; the unpaired last path of an odd count draws
+ * alone) -- the counters of cssm_simulate.  eta_k = cssm_exp(gamma_k) is stored per grid index, ub = the exact maximum of the stored
+ * values (a NaN among them makes ub NaN).
+ *
+ * Thinning.  Candidate c = 0, 1, ... of path i is the ONE block (key, gid = i, step = c, CSSM_STREAM_THIN, 0), unpaired:
+ * U = cssm_u01_open0(words 0-1), E = -cssm_log(U) / ub; V = cssm_u01(words 2-3).  t1 = last + E (the sequential sum, last = start
+ * first); the loop ends at the first candidate that is not <= end (the reference's t1 > end; a NaN ends it too: ub = 0 gives E = +inf,
+ * or NaN in the one case U = 1 -- no candidate either way).  k = cssm_lgcp_index = the largest k with t_k <= t1; the candidate is an
+ * event iff V <= eta_k / ub.  Accepted or not, last = t1.
+ *
+ * Bounded work.  Before its loop a path forms ub (end - start): not finite -> CSSM_LGCP_PATH_NONFINITE (the reference would throw on a
+ * rate that is not finite); above CSSM_LGCP_MAX_EXPECTED -> CSSM_LGCP_PATH_TOO_MANY; and a loop that
+ * reaches CSSM_LGCP_MAX_CANDIDATES candidates stops with CSSM_LGCP_PATH_TOO_MANY.  Such a path has zero events; the call succeeds. */
+#define CSSM_STREAM_THIN 10u
+#define CSSM_LGCP_MAX_EXPECTED 0x1.0p20
+#define CSSM_LGCP_MAX_CANDIDATES (1u << 21)
+#define CSSM_LGCP_PATH_OK 0
+#define CSSM_LGCP_PATH_NONFINITE 1
+#define CSSM_LGCP_PATH_TOO_MANY 2
+
+/* the status a path enters its loop with (non-zero: it takes no candidate) */
+CSSM_HD int cssm_lgcp_admit(double ub, double start, double end) {
+  const double expected = ub * (end - start);
+  if (!(expected - expected == 0.0)) return CSSM_LGCP_PATH_NONFINITE;
+  return expected > CSSM_LGCP_MAX_EXPECTED ? CSSM_LGCP_PATH_TOO_MANY : CSSM_LGCP_PATH_OK;
+}
+
+/* candidate c of path i: the waiting time E ~ Exponential(ub) and the acceptance uniform V */
+CSSM_HD void cssm_lgcp_candidate(uint64_t key, uint64_t i, uint32_t c, double ub, double* E, double* V) {
+  const cssm_u32x4 b = cssm_philox_draw(key, i, c, CSSM_STREAM_THIN, 0u);
+  *E = -cssm_log(cssm_u01_open0(b.v[0], b.v[1])) / ub;
+  *V = cssm_u01(b.v[2], b.v[3]);
+}
+
+/* The largest k < n_grid with grid_t[k] <= t1, for start = grid_t[0] <= t1 finite: the guess floor((t1 - start) / delta), corrected
+ * against the accumulated grid times (they drift from start + k delta, about 1.7e-13 over 1000 steps: the guess alone is wrong at
+ * cell edges). */
+CSSM_HD uint32_t cssm_lgcp_index(const double* grid_t, uint32_t n_grid, double start, double delta, double t1) {
+  const double q = __builtin_floor((t1 - start) / delta), top = (double)(n_grid - 1u);
+  uint32_t k = q >= top ? n_grid - 1u : (q > 0.0 ? (uint32_t)q : 0u);
+  while (k + 1u < n_grid && grid_t[k + 1u] <= t1) k += 1u;
+  while (k > 0u && grid_t[k] > t1) k -= 1u;
+  return k;
+}
+
 #ifdef __cplusplus
 }
 #endif

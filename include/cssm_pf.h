@@ -464,7 +464,7 @@ int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_scale, doub
  * between launches and the result does not depend on it.
  * Errors, all but the last decided before the first device call, with nothing written to out: CSSM_EINVAL_ARG (null desc / out, null t
  * with T > 0; n_paths outside [1, 2^32 - 2^16]; T >= 2^32 - 1; t0 or a time not finite, a time before t0 or decreasing; LGCP, whose
- * observation the reference leaves unimplemented -- simLGCP is another algorithm and not served; a model without the scale its
+ * observation the reference leaves unimplemented -- its series come from cssm_simulate_lgcp (simLGCP, by thinning); a model without the scale its
  * observation needs, with the reference's exception named; Student-t with df < 1), CSSM_EINVAL_DESC (a descriptor cssm_pf_create
  * refuses), CSSM_EHIP without a device. */
 int cssm_simulate(const cssm_model_desc* desc, uint64_t n_paths, uint64_t key, double t0, const double* t, size_t T, size_t rows_per_launch,
@@ -477,6 +477,47 @@ int cssm_simulate_from(const cssm_model_desc* desc, uint64_t n_paths, uint64_t k
                        const double* t, size_t T, size_t rows_per_launch, int device, double* out);
 /* Device time (ms, HIP events around its kernels) of the calling thread's last cssm_simulate / cssm_simulate_from; CSSM_ESTATE before one. */
 int cssm_simulate_last_ms(double* ms);
+
+/* SimulateData(m).simLGCP(start, end, precision) (model/Data.scala:110-149, simSdeStream :162-176): the event times of a log-Gaussian
+ * Cox process by thinning, n_paths independent realisations drawn on the device.  Stateless.  The latent state runs over the grid
+ * t_0 = start, t_k = t_(k-1) + delta (delta = 10^-precision, the time accumulated by repeated addition) while
+ * t_k <= start + (end - start), every transition with dt = delta exactly; eta_k = exp(f(x_k, t_k)), upper = max_k eta_k; candidates
+ * t1 = last + Exponential(upper) from last = start until one passes `end`, each accepted iff V <= eta_k / upper at the largest k with
+ * t_k <= t1.  Counters, the index rule and the bounds on a path's work: include/cssm_obs_draws.h (CSSM_STREAM_THIN).  The grid draws
+ * are cssm_simulate's: for the same model with Poisson observations, cssm_simulate over the grid times gives the state rows bit for bit
+ * wherever t_k - t_(k-1) == delta.  `precision` rules here; desc->lgcp_precision (the filter's) is validated and not used, as the
+ * reference takes the two separately.
+ * The number of events is not known before the call, so it returns a result object that holds HOST memory only (no device memory
+ * outlives the call); the caller reads it into buffers of its own and destroys it:
+ *   cssm_lgcp_sim_shape      d, n_paths, grid_points, n_events (all paths);
+ *   cssm_lgcp_sim_grid_times t[grid_points];
+ *   cssm_lgcp_sim_grid       grid_points x (d + 3) x n_paths in cssm_simulate's layout -- the d states, gamma, eta, obs = 0.0 -- with
+ *                            flags & CSSM_LGCP_SIM_KEEP_GRID; without it the rows are never downloaded and this is CSSM_ESTATE;
+ *   cssm_lgcp_sim_paths      ev_off[n_paths + 1] (path i owns the events ev_off[i] .. ev_off[i + 1] - 1, in time order), upper[i],
+ *                            candidates[i] (those not after `end`), status[i] (CSSM_LGCP_PATH_*: a non-zero path has no events -- the
+ *                            reference would throw or not return there -- and the call still succeeds);
+ *   cssm_lgcp_sim_events     per event its time, its grid index and its d + 3 values, row-major per event: the states at that index,
+ *                            gamma, eta and 1.0.
+ * Any output pointer may be NULL.  The reference's vector of one path is its events newest first, then its grid points in time order.
+ * paths_per_launch: paths one pair of launches covers (0: as many as keep the grid rows on the device within 1 GiB), rounded up to a
+ * whole number of pairs of paths; the result does not depend on it.
+ * Errors, all but the last two decided before the first device call, *out untouched: CSSM_EINVAL_ARG (null desc / out; n_paths outside
+ * [1, 2^32 - 2^16]; precision outside [0, 9]; start or end not finite, end < start; a model that is not CSSM_OBS_LGCP -- cssm_simulate
+ * draws those; more than 2^24 grid points; a grid whose d + 3 rows for one pair of paths exceed 1 GiB; unknown flags),
+ * CSSM_EINVAL_DESC (a descriptor cssm_pf_create refuses), CSSM_ENOMEM, CSSM_EHIP without a device. */
+typedef struct cssm_lgcp_sim cssm_lgcp_sim;
+#define CSSM_LGCP_SIM_KEEP_GRID 1
+int cssm_simulate_lgcp(const cssm_model_desc* desc, uint64_t n_paths, uint64_t key, double start, double end, int precision, int flags,
+                       size_t paths_per_launch, int device, cssm_lgcp_sim** out);
+int cssm_lgcp_sim_shape(const cssm_lgcp_sim* sim, int* d, uint64_t* n_paths, uint64_t* grid_points, uint64_t* n_events);
+int cssm_lgcp_sim_grid_times(const cssm_lgcp_sim* sim, double* t);
+int cssm_lgcp_sim_grid(const cssm_lgcp_sim* sim, double* rows);
+int cssm_lgcp_sim_paths(const cssm_lgcp_sim* sim, uint64_t* ev_off, double* upper, uint32_t* candidates, int32_t* status);
+int cssm_lgcp_sim_events(const cssm_lgcp_sim* sim, double* ev_t, uint32_t* ev_idx, double* ev_rows);
+void cssm_lgcp_sim_destroy(cssm_lgcp_sim* sim);
+/* Device time (ms, HIP events) of the calling thread's last cssm_simulate_lgcp: ms2[0] its grid kernels, ms2[1] its thinning launches
+ * (the counting and the writing one); CSSM_ESTATE before a call. */
+int cssm_simulate_lgcp_last_ms(double* ms2);
 
 /* FilterInterpolate (model/ParticleFilter.scala:273-311, ParticleFilter.interpolate :335-337): the filter whose
  * particles are whole paths, so that a weighted step resamples the paths and missing observations are
