@@ -223,6 +223,9 @@ SYMBOLS = [
     ("cssm_fleet_observation_index", C.c_uint64, [_h, C.c_uint32]),
     ("cssm_fleet_pack_record", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32,
                                          _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("cssm_fleet_create_lgcp", C.c_int, [_descp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_h)]),
+    ("cssm_fleet_pack_record_lgcp", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_uint32, _u8p, C.c_size_t,
+                                              C.POINTER(C.c_size_t), _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("cssm_diag_copy_ceiling", C.c_int, [C.c_int, C.c_size_t, C.c_int, _dp]),
     ("cssm_contract_eval", C.c_int, [C.c_int, C.c_int, _dp, C.c_size_t, _dp, C.c_size_t]),
     ("cssm_desc_flatten", C.c_int, [_descp, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -7,9 +7,15 @@
 // Per-observation constants: the host builds every record with cssm_build_rec -- the function the single handle uses, so its bits by
 // construction -- and uploads the compact form (FleetRecHead + 5 d doubles: 80 + 40 d bytes per observation, not sizeof(StepRec)).
 // Records of different series are independent: large calls build them on a few host threads.
+//
+// An LGCP fleet (cssm_fleet_create_lgcp) is the same object with another record and another instantiation of k_fleet_series
+// (cssm_fleet_lgcp.hip.h): every record is an event, built by cssm_build_rec under the series' model as for a handle, and where f depends
+// on time the rows of cssm_build_fsub_table of every event of the launch travel behind the records in the same upload.  What it does
+// not serve is refused at the top of the entry point.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -70,6 +76,7 @@ struct cssm_fleet {
   uint32_t n = 0, S = 0;
   int d = 0, threads = 64;
   size_t lds = 0;
+  bool lgcp = false;                    // made by cssm_fleet_create_lgcp: FilterLgcp's records and launch
   HostModel base;                       // the structure every series shares
   std::vector<HostModel> models;        // per series: parameters, key (HostModel::seed), n_global = n
   std::vector<double> t;                // per series: its clock
@@ -128,6 +135,12 @@ static void fleet_win_drop_all(cssm_fleet* f) {
 }
 
 #define FLEET_SERVED "cssm_pf_* (one handle per series) and cssm_pfb_* (batch of chains) serve it"
+// what an LGCP fleet does not serve, said at the top of the entry point, before anything runs
+#define FLEET_LGCP_REFUSE(f, call, served)                                                                                                    \
+  if ((f) && (f)->lgcp)                                                                                                                       \
+    return fail(CSSM_EINVAL_ARG, call ": an LGCP fleet filters event streams (cssm_fleet_ll_filter, _filter, _init, _step, _summary) and serves " \
+                                      "nothing else yet; " served)
+#define FLEET_LGCP_SERVED "cssm_pf_* (one handle per stream) serves it"
 
 template <class F>
 static void fleet_parallel(size_t count, size_t work, F f) {
@@ -154,6 +167,40 @@ static void fleet_pack_rec(const HostModel& m, double t_prev, double t, double y
   double* tail = reinterpret_cast<double*>(dst + sizeof h);
   for (int k = 0; k < m.d; ++k) for (int q = 0; q < 4; ++q) tail[4 * k + q] = r.coef[k][q];
   for (int k = 0; k < m.d; ++k) tail[4 * m.d + k] = r.fco[k];
+}
+
+// (LGCP fleet) the compact record of the event at t behind t_prev: cssm_build_rec's, and the rows of cssm_build_fsub_table appended to `tab`
+// -- the table of the caller's choice: fsub_off counts from `tab_base` doubles before it (where `tab` starts in the launch's table)
+static int fleet_pack_rec_lgcp(const HostModel& m, double t_prev, double t, uint32_t step, unsigned char* dst, std::vector<double>& tab, size_t tab_base) {
+  StepRec r;
+  cssm_build_rec(&m, t_prev, t, 0.0, 1, step, &r);
+  const int rc = cssm_build_fsub_table(&m, &r, 0, 1, tab);
+  if (rc) return rc;
+  FleetLgcpRecHead h;
+  h.u = r.u; h.dt = r.dt; h.n_sub = r.n_sub; h.step = r.step; h.fsub_off = (uint32_t)(tab_base + r.fsub_off); h.pick = r.pick;
+  memcpy(dst, &h, sizeof h);
+  double* tail = reinterpret_cast<double*>(dst + sizeof h);
+  for (int k = 0; k < m.d; ++k) for (int q = 0; q < 4; ++q) tail[4 * k + q] = r.coef[k][q];
+  for (int k = 0; k < m.d; ++k) tail[4 * m.d + k] = r.fco[k];
+  return CSSM_OK;
+}
+// ... and the doubles of the sub-step table that the events t[0 .. count) behind t_prev take: n_sub x d each, n_sub as cssm_build_rec
+// counts it (0 for a model whose f does not depend on time: no table)
+static size_t fleet_lgcp_rows(const HostModel& m, double t_prev, const double* t, size_t count) {
+  if (!m.lgcp_tdep) return 0;
+  size_t rows = 0;
+  for (size_t s = 0; s < count; ++s) {
+    StepRec r;
+    cssm_build_rec(&m, t_prev, t[s], 0.0, 1, 0u, &r);
+    if (r.n_sub > 0) rows += (size_t)r.n_sub;
+    t_prev = t[s];
+  }
+  return rows * (size_t)m.d;
+}
+// the most a launch's table may hold: cssm_build_fsub_table's own bound for a handle's call
+static int fleet_lgcp_table_fits(size_t doubles) {
+  if (doubles <= ((size_t)1 << 27)) return CSSM_OK;
+  return fail(CSSM_ENOMEM, "the sub-step table of a time-dependent LGCP fleet launch would exceed 1 GiB (%zu coefficients)", doubles);
 }
 
 // getIntervals of every series (model/ParticleFilter.scala:415-424), one block per (series, row); rows 0 .. D-1 the state components,
@@ -231,7 +278,8 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   delete f;   // (every FleetBuf frees itself)
 }
 
-extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out) {
+// cssm_fleet_create and cssm_fleet_create_lgcp: one body behind the question which observation model the call serves
+static int fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out, bool lgcp) {
   if (!out) return fail(CSSM_EINVAL_ARG, "out is null");
   *out = nullptr;
   if (n_particles < 1 || n_particles > CSSM_FLEET_MAX_N)
@@ -241,12 +289,15 @@ extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particl
   HostModel base;
   int rc = cssm_build_model(&base, desc, false);
   if (rc) return rc;
-  if (base.obs_kind == CSSM_OBS_LGCP)
+  if (!lgcp && base.obs_kind == CSSM_OBS_LGCP)
     return fail(CSSM_EINVAL_DESC, "the fleet filter does not serve the LGCP observation model (sub-stepped events); " FLEET_SERVED);
+  if (lgcp && base.obs_kind != CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_DESC, "cssm_fleet_create_lgcp makes a fleet of LGCP event streams (obs_kind %d given): cssm_fleet_create serves every other "
+                                  "observation model", base.obs_kind);
   rc = cssm_use_device(device);
   if (rc) return rc;
   cssm_fleet* f = new cssm_fleet();
-  f->device = device; f->n = (uint32_t)n_particles; f->S = n_series; f->d = base.d;
+  f->device = device; f->n = (uint32_t)n_particles; f->S = n_series; f->d = base.d; f->lgcp = lgcp;
   base.n_global = n_particles; base.seed = 0;
   f->base = base;
   const uint32_t S = n_series, n = f->n;
@@ -271,6 +322,14 @@ extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particl
     return bail(CSSM_EHIP, "uploading the contract's table");
   *out = f;
   return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out) {
+  return fleet_create(desc, n_particles, n_series, device, out, false);
+}
+// FilterLgcp(mod, resample, precision) for S event streams: the descriptor's lgcp_precision is part of the fleet's structure
+extern "C" int cssm_fleet_create_lgcp(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out) {
+  return fleet_create(desc, n_particles, n_series, device, out, true);
 }
 
 extern "C" uint32_t cssm_fleet_num_series(const cssm_fleet* f) { return f ? f->S : 0u; }
@@ -424,13 +483,17 @@ static void fleet_fc_row(int d, const double* src, const int32_t* pit, bool ok, 
 //   path: R sampleOne slots (u32) | ival: [S][d] f coefficients, F at every series' t0 | fcst: R keys (u64), R data (f64), S observation
 //   parameters, R flags (u32) padded to 8 bytes | ring: R slots (u32) and S base slots (u32), each padded to 8 bytes, then the lineage
 //   launch's Q requests (FleetWinReq), Q x L slot words (u32, padded), Q x L x d f coefficients] -- a launch carries one rider at most.
+// An LGCP fleet's launch: the records are FleetLgcpRecHead ones, sampleOne's slots live inside them (no path rider is staged), and the
+// launch's sub-step table (doubles; empty unless f depends on time) comes last.
 // Written by the rider into d_rows, preset to 0xff bytes (NaN; -1 in the counts) for what no block writes:
 //   path: [S][d] last rows, then (asked for) the R + S rows of the paths | ival: `rows` of [d + 1][3] | fcst: `rows` of [d + 2][3], then
 //   `rows` of 2 PIT counts (i32) | ring: Q x L rows of [d + 1][3], written by the lineage launch.
 static_assert(sizeof(cssm_obs_params) == 16, "the [S] array of observation parameters is uploaded as it is");
 struct FleetStage {
   FleetKind kind = FleetKind::plain;
+  bool lgcp = false;
   size_t R = 0, rec_bytes = 0;
+  size_t fsub = 0, fsub_doubles = 0;                                                   // (LGCP fleet) the sub-step table
   size_t ctl = 0, recs = 0, ride = 0, fc_y = 0, fc_op = 0, fc_flags = 0, bytes = 0;   // byte offsets into the staging, and its size
   size_t w_base = 0, w_req = 0, w_words = 0, w_fco = 0;                                // ... of the ring rider
   size_t rows = 0, out_doubles = 0, rows_bytes = 0;   // d_rows: the rows of ival / fcst and their doubles; the bytes of any rider
@@ -441,11 +504,13 @@ struct FleetStageView {   // the staging on the host or on the device; the point
   double* fco0;
   unsigned long long* keys; double* y; cssm_obs_params* op; uint32_t* flags;
   uint32_t *w_slot, *w_base; FleetWinReq* w_req; uint32_t* w_words; double* w_fco;
+  double* fsub;
 };
 static FleetStageView fleet_view(const FleetStage& st, const FleetBuf& b) {
   FleetStageView v{};
   v.off = b.at<unsigned long long>(); v.ctl = b.at<uint32_t>(st.ctl); v.recs = b.at<unsigned char>(st.recs);
-  if (st.kind == FleetKind::path) v.picks = b.at<uint32_t>(st.ride);
+  if (st.kind == FleetKind::path && !st.lgcp) v.picks = b.at<uint32_t>(st.ride);
+  if (st.lgcp) v.fsub = b.at<double>(st.fsub);
   if (st.kind == FleetKind::ival) v.fco0 = b.at<double>(st.ride);
   if (st.kind == FleetKind::fcst) {
     v.keys = b.at<unsigned long long>(st.ride); v.y = b.at<double>(st.fc_y);
@@ -482,6 +547,7 @@ struct FleetRide {
   FleetStage st;                     // the launch's layout (fleet_ensure)
   std::vector<double> out;           // ival / fcst: the rows as the device left them; NaN where no block wrote
   std::vector<int32_t> pit;          // fcst: ... -1 where no block wrote
+  size_t fsub_doubles = 0;           // (LGCP fleet) the doubles of the launch's sub-step table, counted before the launch is laid out
   std::vector<int> fc_rc;            // fcst, [S]: the forecast's own status of every series
   std::string scale_msg;             // fcst: the reference's exception for the first series without the scale its observation needs
 };
@@ -491,13 +557,14 @@ static int fleet_ensure(cssm_fleet* f, size_t R, FleetRide& ride) {
   const size_t S = f->S, d = (size_t)f->d;
   FleetStage& st = ride.st;
   st = FleetStage();
-  st.kind = ride.kind; st.R = R; st.rec_bytes = CSSM_FLEET_REC_BYTES(f->d);
+  st.kind = ride.kind; st.R = R; st.lgcp = f->lgcp;
+  st.rec_bytes = f->lgcp ? CSSM_FLEET_LGCP_REC_BYTES(f->d) : CSSM_FLEET_REC_BYTES(f->d);
   st.ctl = (S + 1u) * 8u;
   st.recs = st.ctl + fleet_pad8(S * 4u);
   st.ride = st.recs + R * st.rec_bytes;
   st.bytes = st.ride;
   if (st.kind == FleetKind::path) {
-    st.bytes += R * 4u;
+    if (!st.lgcp) st.bytes += R * 4u;
     st.rows_bytes = (S * d + (ride.path_out ? (R + S) * d : 0u)) * 8u;
   } else if (st.kind == FleetKind::ival) {
     st.bytes += S * d * 8u;
@@ -518,6 +585,7 @@ static int fleet_ensure(cssm_fleet* f, size_t R, FleetRide& ride) {
     st.out_doubles = st.rows * (d + 1) * 3u;
     st.rows_bytes = st.out_doubles * 8u;
   }
+  if (st.lgcp) { st.fsub = fleet_pad8(st.bytes); st.fsub_doubles = ride.fsub_doubles; st.bytes = st.fsub + st.fsub_doubles * 8u; }
   if (!f->h_stage.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet: %zu bytes of pinned staging", st.bytes);
   if (!f->d_stage.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet: %zu bytes of records", st.bytes);
   const size_t rr = std::max<size_t>(R, 1);
@@ -584,7 +652,8 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
   fleet_series_args(f, l);
   l.args.off = dv.off; l.args.ctl = dv.ctl; l.args.recs = dv.recs;
   l.args.ll_t = f->d_ll_t.at<double>(); l.args.ess_t = f->d_ess_t.at<int32_t>();
-  l.n_series = f->S; l.kind = st.kind;
+  l.n_series = f->S; l.kind = st.kind; l.lgcp = f->lgcp;
+  if (f->lgcp && f->base.lgcp_tdep) l.args.fsub = dv.fsub;   // (otherwise null: f is every record's own)
   if (path) {
     l.args.picks = dv.picks; l.args.last = rows;
     if (ride.path_out) l.args.path = rows + n_last;
@@ -682,10 +751,28 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
   int rc = fleet_off_check(off, S);
   if (rc) return rc;
   const size_t R = (size_t)off[S];
-  if (R && (!t || !y)) return fail(CSSM_EINVAL_ARG, "null data");
+  if (R && (!t || (!y && !f->lgcp))) return fail(CSSM_EINVAL_ARG, "null data");
   HIP_TRY(hipSetDevice(f->device));
   const auto tb0 = std::chrono::steady_clock::now();
   ride.step = false;
+  auto t_min = [&](size_t a, size_t b) {                                   // data.minBy(_.t).t
+    double m = t[a];
+    for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;
+    return m;
+  };
+  std::vector<size_t> toff;   // (LGCP fleet, f depends on time) where series k's rows start in the launch's sub-step table (doubles)
+  if (f->lgcp && f->base.lgcp_tdep) {
+    toff.assign((size_t)S + 1u, 0);
+    fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+      for (size_t k = lo; k < hi; ++k) {
+        const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+        if (b > a) toff[k + 1] = fleet_lgcp_rows(f->models[k], t_min(a, b), t + a, b - a);
+      }
+    });
+    for (uint32_t k = 0; k < S; ++k) toff[k + 1] += toff[k];
+    if ((rc = fleet_lgcp_table_fits(toff[S]))) return rc;
+    ride.fsub_doubles = toff[S];
+  }
   rc = fleet_ensure(f, R, ride);
   if (rc) return rc;
   const FleetStageView h = fleet_view(ride.st, f->h_stage);
@@ -694,15 +781,27 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
   if (fcst) fleet_fc_series(f, ride, h, [&](uint32_t k) { return off[k + 1] > off[k]; });
   for (uint32_t k = 0; k <= S; ++k) h.off[k] = off[k];
   std::vector<double> t0(S, 0.0);
+  std::atomic<int> pack_rc{CSSM_OK};
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
       const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
       h.ctl[k] = (b > a) ? CSSM_FLEET_CTL_INIT : 0u;
       if (h.fco0) for (int c = 0; c < f->d; ++c) h.fco0[k * f->d + c] = 0.0;
       if (b == a) continue;
-      double m = t[a];
-      for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;      // data.minBy(_.t).t
+      const double m = t_min(a, b);
       t0[k] = m;
+      if (f->lgcp) {                                                     // every record an event; the series' rows of the table behind them
+        std::vector<double> tab;
+        double tp = m;
+        for (size_t s = a; s < b; ++s) {
+          const int prc = fleet_pack_rec_lgcp(f->models[k], tp, t[s], (uint32_t)(s - a), h.recs + s * RB, tab, toff.empty() ? 0u : toff[k]);
+          if (prc) pack_rc = prc;
+          tp = t[s];
+        }
+        if (!tab.empty() && tab.size() == toff[k + 1] - toff[k]) memcpy(h.fsub + toff[k], tab.data(), tab.size() * 8u);
+        else if (!tab.empty()) pack_rc = CSSM_ENOMEM;
+        continue;
+      }
       if (h.fco0) {                                                      // F(t0): t0 need not be the first record's time
         StepRec r0;
         cssm_build_rec(&f->models[k], m, m, 0.0, 0, 0u, &r0);
@@ -717,6 +816,7 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
       }
     }
   });
+  if (pack_rc) return fail(pack_rc, "fleet: the sub-step table of the launch could not be built");
   if (ride.kind == FleetKind::path) f->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
   rc = fleet_launch(f, ride, ll_t, ess_t);
   if (rc) return rc;
@@ -750,7 +850,7 @@ extern "C" int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const doubl
   if (!path_out && !last_out)
     return fail(CSSM_EINVAL_ARG, "neither path_out nor last_out is given: cssm_fleet_ll_filter is the call that records no path");
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
-  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  if (!t || (!y && !(f && f->lgcp))) return fail(CSSM_EINVAL_ARG, "null data");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
   FleetRide ride;
   ride.kind = FleetKind::path; ride.path_out = path_out; ride.last_out = last_out;
@@ -763,6 +863,7 @@ extern "C" int cssm_fleet_filter(cssm_fleet* f, const uint64_t* off, const doubl
 extern "C" int cssm_fleet_filter_intervals(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval,
                                            double* ll_out, double* ll_t, int32_t* ess_t, double* state_mean, double* state_lower, double* state_upper,
                                            double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_filter_intervals", FLEET_LGCP_SERVED);
   if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
   if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
@@ -801,6 +902,7 @@ extern "C" int cssm_fleet_filter_forecasts(cssm_fleet* f, const uint64_t* off, c
                                            double* state_lower, double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper,
                                            double* obs_mean, double* obs_lower, double* obs_upper, int32_t* obs_below, int32_t* obs_equal,
                                            int* rc_out, int* fc_rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_filter_forecasts", FLEET_LGCP_SERVED);
   if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
   if (!ll_out || !rc_out || !fc_rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out / fc_rc_out is null");
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
@@ -844,6 +946,7 @@ extern "C" int cssm_fleet_pmmh_run(cssm_fleet* f, const cssm_model_desc* desc, c
   if (rc) return rc;
   if (probe.obs_kind == CSSM_OBS_LGCP)
     return fail(CSSM_EINVAL_DESC, "the fleet does not serve the LGCP observation model (sub-stepped events); " FLEET_PMMH_SERVED);
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_pmmh_run", FLEET_PMMH_SERVED);
   size_t flat = 0;
   rc = cssm_desc_flatten(desc, nullptr, 0, &flat);
   if (rc) return rc;
@@ -940,16 +1043,36 @@ static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t,
   }
   if (ring) ride.win_L = std::min<size_t>((size_t)ride.max_lag + 1u, W);   // (a window never returns more rows than it has slots)
   ride.step = true;
-  int rc = fleet_ensure(f, R, ride);
+  int rc = CSSM_OK;
+  std::vector<size_t> toff;   // (LGCP fleet, f depends on time) where series k's rows start in the launch's sub-step table (doubles)
+  if (f->lgcp && f->base.lgcp_tdep) {
+    toff.assign((size_t)S + 1u, 0);
+    for (uint32_t k = 0; k < S; ++k) toff[k + 1] = toff[k] + (runs(k) ? fleet_lgcp_rows(f->models[k], f->t[k], t + k, 1) : 0u);
+    if ((rc = fleet_lgcp_table_fits(toff[S]))) return rc;
+    ride.fsub_doubles = toff[S];
+  }
+  rc = fleet_ensure(f, R, ride);
   if (rc) return rc;
   const FleetStageView h = fleet_view(ride.st, f->h_stage);
   h.off[0] = 0;
   for (uint32_t k = 0; k < S; ++k) { h.ctl[k] = 0u; h.off[k + 1] = h.off[k] + (runs(k) ? 1u : 0u); }
+  std::atomic<int> pack_rc{CSSM_OK};
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
-    for (size_t k = lo; k < hi; ++k)
-      if (h.off[k + 1] > h.off[k])
-        fleet_pack_rec(f->models[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1, f->step[k], h.recs + (size_t)h.off[k] * ride.st.rec_bytes);
+    for (size_t k = lo; k < hi; ++k) {
+      if (h.off[k + 1] == h.off[k]) continue;
+      unsigned char* dst = h.recs + (size_t)h.off[k] * ride.st.rec_bytes;
+      if (f->lgcp) {
+        std::vector<double> tab;
+        const int prc = fleet_pack_rec_lgcp(f->models[k], f->t[k], t[k], f->step[k], dst, tab, toff.empty() ? 0u : toff[k]);
+        if (prc) pack_rc = prc;
+        if (!tab.empty() && tab.size() == toff[k + 1] - toff[k]) memcpy(h.fsub + toff[k], tab.data(), tab.size() * 8u);
+        else if (!tab.empty()) pack_rc = CSSM_ENOMEM;
+        continue;
+      }
+      fleet_pack_rec(f->models[k], f->t[k], t[k], y[k], has_obs ? (int)has_obs[k] : 1, f->step[k], dst);
+    }
   });
+  if (pack_rc) return fail(pack_rc, "fleet: the sub-step table of the launch could not be built");
   if (fcst) {
     fleet_fc_series(f, ride, h, runs);
     for (uint32_t k = 0; k < S; ++k)
@@ -1038,7 +1161,7 @@ static int fleet_step_all(cssm_fleet* f, const uint8_t* active, const double* t,
 
 extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
                                double* ll_out, int32_t* ess_out, int* rc_out) {
-  if (!f || !t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (!f || !t || (!y && !f->lgcp) || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
   FleetRide ride;
   return fleet_step_all(f, active, t, y, has_obs, ll_out, ess_out, rc_out, ride);
 }
@@ -1048,6 +1171,7 @@ extern "C" int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const doubl
 extern "C" int cssm_fleet_step_intervals(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs, double interval,
                                          double* ll_out, int32_t* ess_out, double* state_mean, double* state_lower, double* state_upper,
                                          double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_step_intervals", FLEET_LGCP_SERVED);
   if (!t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
@@ -1065,6 +1189,7 @@ extern "C" int cssm_fleet_step_forecast(cssm_fleet* f, const uint8_t* active, co
                                         double* state_lower, double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper,
                                         double* obs_mean, double* obs_lower, double* obs_upper, int32_t* obs_below, int32_t* obs_equal,
                                         int* rc_out, int* fc_rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_step_forecast", FLEET_LGCP_SERVED);
   if (!t || !y || !rc_out || !fc_rc_out) return fail(CSSM_EINVAL_ARG, "null argument (t, y, rc_out, fc_rc_out)");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
@@ -1077,6 +1202,7 @@ extern "C" int cssm_fleet_step_forecast(cssm_fleet* f, const uint8_t* active, co
 // The window cssm_fleet_step_interpolate remembers in: `slices` slots per series, a cloud and its ancestors each -- S x slices x N x
 // (8 d + 4) bytes.  Every window restarts.
 extern "C" int cssm_fleet_window(cssm_fleet* f, uint32_t slices) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_window", FLEET_LGCP_SERVED);
   if (slices == 1u) return fail(CSSM_EINVAL_ARG, "a window of 1 slice remembers no record behind its base slice: slices is 0 (no window) or at least 2");
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
   HIP_TRY(hipSetDevice(f->device));
@@ -1111,6 +1237,7 @@ extern "C" int cssm_fleet_step_interpolate(cssm_fleet* f, const uint8_t* active,
                                            const uint32_t* lag, uint32_t max_lag, double interval, double* ll_out, int32_t* ess_out,
                                            uint32_t* rows_out, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
                                            double* eta_lower, double* eta_upper, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_step_interpolate", FLEET_LGCP_SERVED);
   if (!t || !y || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument (t, y, rc_out)");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
   if (max_lag == CSSM_FLEET_NO_ROWS) return fail(CSSM_EINVAL_ARG, "max_lag = %u is CSSM_FLEET_NO_ROWS, not a lag", max_lag);
@@ -1289,6 +1416,7 @@ static int fleet_fc_run(cssm_fleet* f, const uint64_t* off, const std::vector<ui
 extern "C" int cssm_fleet_forecast(cssm_fleet* f, const uint64_t* off, const double* t, const uint64_t* keys, double interval,
                                    double* state_mean, double* state_lower, double* state_upper, double* eta_mean, double* eta_lower,
                                    double* eta_upper, double* obs_mean, double* obs_lower, double* obs_upper, double* samples, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_forecast", FLEET_LGCP_SERVED);
   if (!f || !off || !t || !keys || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
   const uint32_t S = f->S;
   int rc = fleet_off_check(off, S);
@@ -1371,6 +1499,7 @@ extern "C" int cssm_fleet_forecast_posterior(cssm_fleet* f, const cssm_model_des
                                              const uint64_t* keys, double interval, double* state_mean, double* state_lower, double* state_upper,
                                              double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower,
                                              double* obs_upper, double* samples, uint32_t* pick_out, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_forecast_posterior", FLEET_LGCP_SERVED);
   if (!f || !desc || !moff || !theta || !x || !t0 || !off || !t || !keys || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
   const uint32_t S = f->S, n = f->n;
   if (moff[0] != 0) return fail(CSSM_EINVAL_ARG, "moff[0] must be 0");
@@ -1514,6 +1643,7 @@ static FleetIpStage fleet_ip_stage(const cssm_fleet* f, const uint64_t* off, uin
 extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval,
                                       int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
                                       double* eta_lower, double* eta_upper, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_interpolate", FLEET_LGCP_SERVED);
   if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
   if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
@@ -1660,6 +1790,7 @@ static FleetSimStage fleet_sim_stage(const cssm_fleet* f, size_t rows) {
 
 extern "C" int cssm_fleet_simulate(cssm_fleet* f, uint64_t n_paths, const double* t0, const uint64_t* off, const double* t, const uint64_t* keys,
                                    double* out, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_simulate", FLEET_LGCP_SERVED);
   if (!f || !t0 || !off || !keys || !out || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument");
   if (n_paths < 1 || n_paths > 0xffff0000ull) return fail(CSSM_EINVAL_ARG, "n_paths must be in [1, 2^32 - 2^16]");
   const uint32_t S = f->S;
@@ -1833,5 +1964,27 @@ extern "C" int cssm_fleet_pack_record(const cssm_model_desc* desc, uint64_t n_pa
   *bytes = CSSM_FLEET_REC_BYTES(m.d);
   if (cap < *bytes) return fail(CSSM_EINVAL_ARG, "record of %zu bytes, room for %zu", *bytes, cap);
   fleet_pack_rec(m, t_prev, t, y, has_obs, step, out);
+  return CSSM_OK;
+}
+
+// The compact record of one event as an LGCP fleet uploads it, and the rows of the sub-step table it brings (fsub_off = 0: the table is
+// this event's own).  No device.
+extern "C" int cssm_fleet_pack_record_lgcp(const cssm_model_desc* desc, uint64_t n_particles, uint64_t seed, double t_prev, double t, uint32_t step,
+                                           unsigned char* out, size_t cap, size_t* bytes, double* fsub_out, size_t fsub_cap, size_t* fsub_count) {
+  if (!out || !bytes || !fsub_count) return fail(CSSM_EINVAL_ARG, "null argument");
+  HostModel m;
+  const int rc = cssm_build_model(&m, desc, false);
+  if (rc) return rc;
+  if (m.obs_kind != CSSM_OBS_LGCP) return fail(CSSM_EINVAL_DESC, "cssm_fleet_pack_record_lgcp packs LGCP events (obs_kind %d given): cssm_fleet_pack_record", m.obs_kind);
+  m.n_global = n_particles; m.seed = seed;
+  *bytes = CSSM_FLEET_LGCP_REC_BYTES(m.d);
+  *fsub_count = 0;
+  if (cap < *bytes) return fail(CSSM_EINVAL_ARG, "record of %zu bytes, room for %zu", *bytes, cap);
+  std::vector<double> tab;
+  const int prc = fleet_pack_rec_lgcp(m, t_prev, t, step, out, tab, 0);
+  if (prc) return prc;
+  *fsub_count = tab.size();
+  if (tab.size() > fsub_cap || (!tab.empty() && !fsub_out)) return fail(CSSM_EINVAL_ARG, "sub-step table of %zu coefficients, room for %zu", tab.size(), fsub_cap);
+  if (!tab.empty()) memcpy(fsub_out, tab.data(), tab.size() * 8u);
   return CSSM_OK;
 }

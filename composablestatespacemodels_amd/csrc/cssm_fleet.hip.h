@@ -16,6 +16,7 @@
 
 #include "cssm_fleet_intervals.hip.h"
 #include "cssm_fleet_onestep.hip.h"
+#include "cssm_fleet_lgcp.hip.h"
 
 // What the host uploads per (series, observation): the fields of cssm_build_rec's StepRec the kernels of a non-LGCP model read, with
 // exactly the d components in use -- 80 + 40 d bytes (120 at d = 1, 200 at d = 3, 720 at d = 16) instead of sizeof(StepRec).  The
@@ -39,6 +40,8 @@ struct FleetSeries {
   uint32_t err;        // bits 0 / 1 as Scalars::err: a NaN log-weight / no usable weight
   uint32_t fail_rec;   // index (within the launch's records of this series) of the observation that set err
   uint32_t pad_;
+  double next_ref;     // (LGCP fleet) the level predicted for the series' NEXT event, cssm_ref_predict of the last event's max -- contract v8;
+                       // NaN while the cloud has weighed none.  Every other launch writes NaN and reads nothing.
 };
 
 #define CSSM_FLEET_CTL_INIT 1u   /* draw the initial cloud before the series' first record of this launch */
@@ -98,6 +101,9 @@ struct FleetArgs {
   // the window of cssm_fleet_step_interpolate (k_fleet_series<D, false, false, false, false, true> only), behind every field the other
   // instantiations read
   FleetRing ring;
+  // an LGCP fleet's launch (k_fleet_series<D, PATH, false, false, false, false, true> only: cssm_fleet_lgcp.hip.h), behind every field the
+  // other instantiations read.  `recs` are then FleetLgcpRecHead records, CSSM_FLEET_LGCP_REC_BYTES(d) each, and `picks` is not read.
+  const double* fsub;                // the launch's sub-step table (f at the sub-step times of a seasonal leaf), or null: f is the record's own
 };
 
 // a - b mod 2^128 (integers: exact)
@@ -145,7 +151,13 @@ __device__ __forceinline__ void fleet_path_row(const double* buf, const uint32_t
 // record gathers, not yet propagated, in its base slot.  The two cloud copies are loops of their own around step 1, which stays the
 // plain launch's statement for statement.  state / anc / ser ping-pong as in the plain launch.  A template flag as the
 // others: the other five instantiations hold no trace of it.
-template <int D, bool PATH, bool HIST = false, bool IVAL = false, bool FCST = false, bool RING = false>
+// LGCP: llFilter / stepFilter / filter of FilterLgcp (model/ParticleFilter.scala:169-227) -- every record is an event and is weighed.  The
+// records are the LGCP fleet's own (FleetLgcpRecHead: no y, no density constants, sampleOne's slot inside); step 1 walks the event's n_sub
+// sub-steps per particle (fleet_lgcp_weigh) instead of one transition and a density; the level is the one predicted from the series'
+// event before (contract v8), kept in a register from record to record and in FleetSeries::next_ref from launch to launch.  Everything
+// else -- the max, the fixed-point sums, the scan, the resampling -- is the plain launch's statement for statement.  A template flag as
+// the others: the other six instantiations hold no trace of it.
+template <int D, bool PATH, bool HIST = false, bool IVAL = false, bool FCST = false, bool RING = false, bool LGCP = false>
 __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k_fleet_series(const FleetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   __shared__ StepRec s_rec;
@@ -165,6 +177,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   double* st = HIST ? a.hist + (size_t)(r0 + k) * D * n : a.state + (size_t)k * 2u * D * n;   // (HIST: slice 0 of the series)
   uint32_t* ganc = HIST ? a.hanc + (size_t)(r0 + k) * n : a.anc + (size_t)k * n;              // (HIST: ancestor slice 0, never written)
   double ll; int32_t ess; uint32_t err = 0u, fail_rec = 0u;
+  double next_ref = cssm_nan();                                // (LGCP) no event of this cloud yet whose max could predict a level
   if (HIST || (ctl & CSSM_FLEET_CTL_INIT)) {
     // initialiseState (:105-108): x0 = sqrt(c0) z + m0 into buffer 0, identity ancestors, ll = 0, ess = N
     for (uint32_t i = tid; i < n; i += bs) {
@@ -178,13 +191,19 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   } else {
     for (uint32_t i = tid; i < n; i += bs) s_anc[i] = ganc[i];
     ll = a.ser[k].ll; ess = a.ser[k].ess;
+    if constexpr (LGCP) next_ref = a.ser[k].next_ref;
   }
   const bool pow2 = (n & (n - 1u)) == 0u;
   const double inv_n = 1.0 / (double)n;
   const uint32_t it = (n + bs - 1u) / bs;                      // particles per thread of the scan phases (contiguous)
   const uint32_t j0 = tid * it;
   const uint32_t j1 = (j0 + it < n) ? j0 + it : n;             // (j0 >= n: an empty range)
-  constexpr uint32_t RB = (uint32_t)CSSM_FLEET_REC_BYTES(D);
+  constexpr uint32_t RB = LGCP ? (uint32_t)CSSM_FLEET_LGCP_REC_BYTES(D) : (uint32_t)CSSM_FLEET_REC_BYTES(D);
+  // (PATH) sampleOne's slot behind record q of the launch: the rider's array, or (LGCP) inside the record
+  auto pick_of = [&](unsigned long long q) -> uint32_t {
+    if constexpr (LGCP) return reinterpret_cast<const FleetLgcpRecHead*>(a.recs + (size_t)q * RB)->pick;
+    else return a.picks[q];
+  };
   uint32_t cur = 0u;                                           // (PATH) the buffer that holds the cloud: 0 behind the initial draw
   for (unsigned long long r = r0; r < r1; ++r) {               // bounded by the series' length
     __syncthreads();                                            // the cloud / ancestors of the record before; s_rec is free
@@ -194,14 +213,23 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
         const int32_t pr = (int32_t)cssm_philox_draw(seed, 0, 0, CSSM_STREAM_PICK, 0).v[0];
         pick = (uint32_t)((uint64_t)(pr < 0 ? (uint32_t)0 - (uint32_t)pr : (uint32_t)pr) % n);
       } else {
-        pick = a.picks[r - 1];
+        pick = pick_of(r - 1);
       }
       fleet_path_row<D>(st + (size_t)cur * D * n, s_anc, n, pick, a.path + (size_t)(r + k) * D, tid);
     }
     if (IVAL && r == r0 && (ctl & CSSM_FLEET_CTL_INIT))         // (uniform) row 0: the initial cloud, F at the series' t0
       fleet_cloud_intervals<D>(st, s_anc, n, a.iv_np2, a.mk, a.iv_fco0 + (size_t)k * D, a.iv_rk, reinterpret_cast<unsigned long long*>(s_lw),
                                a.iv_out + (size_t)(r0 + k) * (D + 1) * 3u);
-    {
+    if constexpr (LGCP) {
+      const unsigned char* g = a.recs + (size_t)r * RB;
+      const FleetLgcpRecHead* h = reinterpret_cast<const FleetLgcpRecHead*>(g);
+      const double* tail = reinterpret_cast<const double*>(g + sizeof(FleetLgcpRecHead));
+      if (tid == 0) {
+        s_rec.u = h->u; s_rec.dt = h->dt; s_rec.n_sub = h->n_sub; s_rec.step = h->step; s_rec.fsub_off = h->fsub_off; s_rec.has_obs = 1;
+      }
+      if (tid < 4u * D) s_rec.coef[tid >> 2][tid & 3u] = tail[tid];
+      if (tid < (uint32_t)D) s_rec.fco[tid] = tail[4 * D + tid];
+    } else {
       const unsigned char* g = a.recs + (size_t)r * RB;
       const FleetRecHead* h = reinterpret_cast<const FleetRecHead*>(g);
       const double* tail = reinterpret_cast<const double*>(g + sizeof(FleetRecHead));
@@ -215,7 +243,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     __syncthreads();
     const StepRec* rec = &s_rec;
     const uint32_t step = rec->step;
-    const bool weighted = rec->has_obs != 0;
+    const bool weighted = LGCP || rec->has_obs != 0;
     const double* src = st + (size_t)(HIST ? (uint32_t)(r - r0) : (step & 1u)) * D * n;
     double* dst = st + (size_t)(HIST ? (uint32_t)(r - r0) + 1u : ((step & 1u) ^ 1u)) * D * n;
     if (PATH) cur = (step & 1u) ^ 1u;
@@ -247,6 +275,36 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     // 1. gather through the previous ancestors, transition, f, log-density (:118, :123)
     double tmax = -cssm_inf();
     bool bad = false;
+    if constexpr (LGCP) {
+      // (LGCP) 1. gather through the previous ancestors, the event's sub-steps, gamma - hazard (:193-205, :212-217).  W of the thread's
+      //    particles at a time (cssm_fleet_lgcp.hip.h); a lane whose group is short walks its first particle again and stores nothing of it
+      constexpr int W = CSSM_FLEET_LGCP_WIDTH;
+      for (uint32_t i0 = tid; i0 < n; i0 += (uint32_t)W * bs) {
+        double x[W][D], lw[W];
+        uint32_t gid[W];
+#pragma unroll
+        for (int q = 0; q < W; ++q) {
+          const uint32_t i = i0 + (uint32_t)q * bs;
+          gid[q] = (i < n) ? i : i0;
+          const uint32_t j = s_anc[gid[q]];
+#pragma unroll
+          for (int c = 0; c < D; ++c) x[q][c] = src[(size_t)c * n + j];
+        }
+        fleet_lgcp_weigh<D, W>(a.mk, rec, a.fsub, seed, gid, tab, x, lw);
+#pragma unroll
+        for (int q = 0; q < W; ++q) {
+          const uint32_t i = i0 + (uint32_t)q * bs;
+          if (i < n) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) dst[(size_t)c * n + i] = x[q][c];
+            double w = lw[q];
+            if (w != w) { bad = true; w = -cssm_inf(); }
+            tmax = (w > tmax) ? w : tmax;
+            s_lw[i] = w;
+          }
+        }
+      }
+    } else
     for (uint32_t i = tid; i < n; i += bs) {
       const uint32_t j = s_anc[i];
       double x[D];
@@ -296,7 +354,13 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
       err = anybad ? 1u : 2u; fail_rec = (uint32_t)(r - r0);
       break;
     }
-    const double ref = cssm_ref_choose(rec->ref, gmax);
+    double ref;
+    if constexpr (LGCP) {                                       // the level predicted from the event before; this event's max predicts the next
+      ref = cssm_ref_choose(next_ref, gmax);
+      next_ref = cssm_ref_predict(gmax);
+    } else {
+      ref = cssm_ref_choose(rec->ref, gmax);
+    }
     // 3. weights on the 2^-96 grid, their sums, the block scan (:125, :127-128)
     cssm_u128 sa = cssm_u128_zero(), sb = cssm_u128_zero();
     for (uint32_t j = j0; j < j1; ++j) {
@@ -360,17 +424,17 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     }
   }
   if (HIST) {                                                   // the fleet's ancestors and scalars stay as they were
-    if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.hser[k] = o; }
+    if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; o.next_ref = cssm_nan(); a.hser[k] = o; }
     return;
   }
   __syncthreads();
   if (PATH && !err && r1 > r0) {                               // (uniform) the last row: no record follows to write it
-    const uint32_t pick = a.picks[r1 - 1];
+    const uint32_t pick = pick_of(r1 - 1);
     if (a.path) fleet_path_row<D>(st + (size_t)cur * D * n, s_anc, n, pick, a.path + (size_t)(r1 + k) * D, tid);
     fleet_path_row<D>(st + (size_t)cur * D * n, s_anc, n, pick, a.last + (size_t)k * D, tid);
   }
   for (uint32_t i = tid; i < n; i += bs) ganc[i] = s_anc[i];
-  if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; a.ser[k] = o; }
+  if (tid == 0) { FleetSeries o; o.ll = ll; o.ess = ess; o.err = err; o.fail_rec = fail_rec; o.pad_ = 0u; o.next_ref = next_ref; a.ser[k] = o; }
 }
 
 // which k_fleet_series a launch runs: <D, false> | <D, true> | <D, false, true> | <D, false, false, true> | <D, false, false, false, true> |
@@ -380,6 +444,7 @@ struct FleetLaunch {
   FleetArgs args;
   uint32_t n_series;    // blocks; hist: the series args.k0 .. args.k0 + n_series - 1
   FleetKind kind;
+  bool lgcp;            // an LGCP fleet's launch: kind plain or path runs <D, false / true, false, false, false, false, true>
   int threads;
   size_t lds;           // ival, fcst: 8 args.iv_np2 + 4 n bytes
   hipStream_t stream;

@@ -13,6 +13,12 @@
 
 int CSSM_FLEET_NAME(CSSM_FLEET_D)(const FleetLaunch& l) {
 #define CSSM_FLEET_RUN(...) hipLaunchKernelGGL((k_fleet_series<CSSM_FLEET_D, __VA_ARGS__>), dim3(l.n_series), dim3(l.threads), l.lds, l.stream, l.args)
+  if (l.lgcp) {       // an LGCP fleet serves the record calls without a rider and `filter` (cssm_fleet.hip refuses the others before a launch)
+    if (l.kind == FleetKind::path) CSSM_FLEET_RUN(true, false, false, false, false, true);
+    else if (l.kind == FleetKind::plain) CSSM_FLEET_RUN(false, false, false, false, false, true);
+    else return (int)hipErrorInvalidValue;
+    return (int)hipGetLastError();
+  }
   switch (l.kind) {   // (the object holds the kernels in the order they are named here: reordering the cases reorders its code)
     case FleetKind::fcst: CSSM_FLEET_RUN(false, false, false, true); break;
     case FleetKind::ival: CSSM_FLEET_RUN(false, false, true); break;

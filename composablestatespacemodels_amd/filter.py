@@ -378,11 +378,13 @@ class NativePfFleet:
     its own per series; ONE launch advances all of them, one workgroup per series (include/cssm_pf.h, "fleet of independent
     series").  Per series every result has the bits of a ``NativePf`` of its own."""
 
+    _CREATE = "cssm_fleet_create"          # the call that makes the handle (NativeLgcpFleet: cssm_fleet_create_lgcp)
+
     def __init__(self, model: Model, n: int, series: int, device: int = 0):
         self.lib = _abi.load_library()
         self._h = C.c_void_p()
-        self._desc = model.descriptor()
-        _abi.check(self.lib.cssm_fleet_create(self._desc.ptr(), int(n), int(series), int(device), C.byref(self._h)))
+        self._desc = self._descriptor(model)
+        _abi.check(getattr(self.lib, self._CREATE)(self._desc.ptr(), int(n), int(series), int(device), C.byref(self._h)))
         self.S, self.n = int(series), int(n)
         words = (C.c_uint32 * (_abi.MAX_DIM // 4))()
         d = C.c_int32()
@@ -407,11 +409,15 @@ class NativePfFleet:
     def __exit__(self, *a):
         self.close()
 
+    def _descriptor(self, model: Model):
+        """The descriptor a model is handed to the library as (NativeLgcpFleet: with the fleet's precision)."""
+        return model.descriptor()
+
     def set_params(self, models: Sequence[Model]):
         if len(models) != self.S:
             raise ValueError("one model per series")
         cache = {}
-        descs = [cache.setdefault(id(m), m.descriptor()) for m in models]   # (pointers may repeat)
+        descs = [cache.setdefault(id(m), self._descriptor(m)) for m in models]   # (pointers may repeat)
         arr = (_abi._descp * self.S)(*[C.pointer(d.desc) for d in descs])
         _abi.check(self.lib.cssm_fleet_set_params(self._h, arr))
 
@@ -929,6 +935,33 @@ class NativePfFleet:
         return arr, samples, pick_out, rc
 
 
+class NativeLgcpFleet(NativePfFleet):
+    """``cssm_fleet*`` made by ``cssm_fleet_create_lgcp``: S event streams of a log-Gaussian Cox process filtered per launch, each as
+    ``FilterLgcp(model, resample, precision)`` filters it on a handle of its own.  Every record is an event: ``y`` and ``has`` are
+    ignored.  The calls an LGCP fleet does not serve (intervals and forecasts per record, interpolation, simulation, PMMH) raise with
+    the library's refusal."""
+
+    _CREATE = "cssm_fleet_create_lgcp"
+
+    def __init__(self, model: Model, n: int, series: int, precision: int, device: int = 0):
+        self.precision = int(precision)
+        super().__init__(model, n, series, device)
+
+    def _descriptor(self, model: Model):
+        return model.descriptor(self.precision)
+
+    @staticmethod
+    def pack(datas, allow_empty: bool = False):
+        """``NativePfFleet.pack`` that also takes a bare array of event times per series (``simulate.lgcp_fleet_data``) in place of a
+        ``(t, y, has)`` triple: its y reads 1.0 and its has 1, as ``lgcp_events_data`` writes them -- the library reads neither."""
+        def triple(tr):
+            if isinstance(tr, (tuple, list)) and len(tr) in (2, 3) and np.ndim(tr[0]) == 1:
+                return tr
+            t = np.asarray(tr, dtype=np.float64).ravel()
+            return t, np.ones(len(t)), None
+        return NativePfFleet.pack([triple(tr) for tr in datas], allow_empty)
+
+
 class _PfView(NativePf):
     """A chain of a batch seen as a NativePf: the batch owns the handle, closing the view destroys nothing."""
 
@@ -1269,7 +1302,7 @@ class FilterFleet:
         self.mods = list(mods)
         self.S = len(self.mods)
         self.seed = seed
-        self._fleet = NativePfFleet(self.mods[0], n_particles, self.S, device)
+        self._fleet = self._new_fleet(self.mods[0], n_particles, self.S, device)
         try:
             self._fleet.set_option(2, kinds.get(resample, 3))      # CSSM_OPT_RESAMPLER: refused unless systematic
             self._fleet.set_params(self.mods)
@@ -1278,6 +1311,9 @@ class FilterFleet:
             self._fleet.close()
             raise
         self._states: List[FleetState] = []
+
+    def _new_fleet(self, mod: Model, n: int, series: int, device: int) -> NativePfFleet:
+        return NativePfFleet(mod, n, series, device)
 
     @staticmethod
     def keys(seed: int, series: int) -> List[int]:
@@ -1502,6 +1538,20 @@ class FilterFleet:
         rows = self._fleet.summary(0.975)
         st = self._states if self._states and self._states[0]._generation == self._fleet.generation else None
         return [_pfout(st[k].t if st else float("nan"), st[k].observation if st else None, rows, k, bound=lambda v: v) for k in range(self.S)]
+
+
+class FilterLgcpFleet(FilterFleet):
+    """``FilterLgcp(mods[k], resample, precision)`` (ParticleFilter.scala:169-227) for many event streams at once, advanced by one device
+    call: ``FilterFleet`` over a ``NativeLgcpFleet``.  ``initialiseState``, ``stepFilter``, ``llFilter``, ``filter`` and ``getIntervals``
+    are served -- every datum is an event, whatever its ``observation`` --; the other methods raise with the library's refusal.  Series
+    k's key is ``cssm_pf_run_key(seed, k)``."""
+
+    def __init__(self, mods: Sequence[Model], resample, precision: int, n_particles: int, seed: int = 20260101, device: int = 0):
+        self.precision = int(precision)
+        super().__init__(mods, resample, n_particles, seed, device)
+
+    def _new_fleet(self, mod: Model, n: int, series: int, device: int) -> NativePfFleet:
+        return NativeLgcpFleet(mod, n, series, self.precision, device)
 
 
 class ParticleFilter:

@@ -185,6 +185,13 @@ def lgcp_events_data(points_or_sim: Union[LgcpSim, Iterable[SimulatedPoint]], pa
     return sorted(ev, key=lambda o: o.t)
 
 
+def lgcp_fleet_data(sim: LgcpSim) -> List[np.ndarray]:
+    """The events of every path of a simulated Cox process as the data of an LGCP fleet: one array of event times per path, in time
+    order -- what ``filter.NativeLgcpFleet.ll_filter`` takes, series p the path p (``lgcp_events_data(sim, p)`` without the objects)."""
+    off = [int(v) for v in sim.ev_off]
+    return [np.ascontiguousarray(sim.ev_t[a:b], dtype=np.float64) for a, b in zip(off, off[1:])]
+
+
 class SimulateData:
     """``SimulateData(model)`` of the reference (Data.scala:53-100), one path, drawn on the device under ``sim_key(seed)``."""
 

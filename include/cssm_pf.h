@@ -834,8 +834,12 @@ int cssm_model_structure(const cssm_model_desc* desc, uint32_t* words_out, int32
  * Per series k every result has the bits of a handle of its own -- cssm_pf_create(descs[k], N, seeds[k]) driven through the same
  * calls -- and so of the oracle: ll, ll_t, ess_t, cloud, ancestors, observation index, the paired Philox streams.
  *
- * Served: every observation model except LGCP, every transition and composition, d = 1 .. CSSM_MAX_DIM, systematic resampling,
- * 1 <= N <= CSSM_FLEET_MAX_N.  Everything else is refused at cssm_fleet_create / _set_params / _set_option with CSSM_EINVAL_ARG /
+ * Served: every observation model, every transition and composition, d = 1 .. CSSM_MAX_DIM, systematic resampling,
+ * 1 <= N <= CSSM_FLEET_MAX_N.  The LGCP observation model (sub-stepped events, FilterLgcp) is asked for by name, as the reference asks
+ * for FilterLgcp by name: cssm_fleet_create_lgcp makes the fleet, cssm_fleet_create keeps refusing an LGCP descriptor.  An LGCP fleet
+ * serves _destroy, _num_series, _num_particles, _set_params, _reseed, _set_option, _init, _step, _ll_filter, _filter, _summary,
+ * _get_particles, _get_ancestors, _observation_index and _last_ms; every other call on it is CSSM_EINVAL_ARG before anything runs.
+ * Everything else is refused at cssm_fleet_create / _set_params / _set_option with CSSM_EINVAL_ARG /
  * CSSM_EINVAL_DESC and a message naming the reason and the entry points that do serve it (cssm_pf_*, cssm_pfb_*); a fleet call
  * never degenerates into S single-handle runs.  Thread-affinity and device rules as for every entry point: each call selects the
  * fleet's device; the fleet owns a non-blocking stream; a fleet is not re-entrant.
@@ -848,6 +852,17 @@ typedef struct cssm_fleet cssm_fleet;
 /* Errors: CSSM_EINVAL_ARG (N outside [1, CSSM_FLEET_MAX_N], S = 0, device out of range), CSSM_EINVAL_DESC (invalid descriptor,
  * LGCP), CSSM_EHIP (no device), CSSM_ENOMEM (16 d N bytes of state per series). */
 int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out);
+/* A fleet of LGCP event streams: FilterLgcp(mod, resample, precision) (model/ParticleFilter.scala:169-227) for S streams, the bits of
+ * cssm_pf_* under an LGCP descriptor per stream.  desc->obs_kind must be CSSM_OBS_LGCP -- anything else is CSSM_EINVAL_DESC naming
+ * cssm_fleet_create, decided before any device is touched; desc->lgcp_precision is part of the fleet's structure (a cssm_fleet_set_params
+ * descriptor of another precision is CSSM_EINVAL_DESC naming the series).  N, S, device and memory limits and errors as cssm_fleet_create.
+ * Data: every record is an event -- y and has_obs are ignored and may be NULL, the step always weighs; an event at the time of the one
+ * before it (dt == 0) takes no sub-step, weighs gamma - gamma and keeps the state; the sub-step clock, and f at the sub-step times of a
+ * seasonal leaf, are the handle's.  Per-series statuses are the plain fleet's (CSSM_ENONFINITE ends one series, an empty series is
+ * CSSM_EINVAL_ARG, CSSM_ESTATE without a cloud).  Not served, CSSM_EINVAL_ARG with a message that says "LGCP fleet" and names what
+ * serves the request: _filter_intervals, _step_intervals, _filter_forecasts, _step_forecast, _forecast, _forecast_posterior, _interpolate,
+ * _window, _step_interpolate, _simulate, _pmmh_run.  Intervals of a stream: cssm_fleet_summary after a step. */
+int cssm_fleet_create_lgcp(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out);
 void cssm_fleet_destroy(cssm_fleet* f);
 uint32_t cssm_fleet_num_series(const cssm_fleet* f);
 uint64_t cssm_fleet_num_particles(const cssm_fleet* f);
@@ -1173,6 +1188,14 @@ int cssm_fleet_last_ms(cssm_fleet* f, double* ms3);
  * then d x 4 transition coefficients and d f coefficients, each the value cssm_pf_step's record holds. */
 int cssm_fleet_pack_record(const cssm_model_desc* desc, uint64_t n_particles, uint64_t seed, double t_prev, double t, double y,
                            int has_obs, uint32_t step, unsigned char* out, size_t cap, size_t* bytes);
+/* Diagnostic, no device: the compact record an LGCP fleet uploads for the event at t behind t_prev under `desc` (CSSM_OBS_LGCP, else
+ * CSSM_EINVAL_DESC) -- 32 + 40 d bytes: u, dt = 10^-precision (doubles), n_sub = ceil((t - t_prev) / dt) (i32), step, fsub_off, pick
+ * (u32), then d x 4 transition coefficients over dt and d f coefficients at t -- and the rows of the sub-step table it brings:
+ * fsub_count = n_sub x d coefficients of f at the sub-step times where f depends on time (a seasonal leaf), else 0; fsub_off = 0.
+ * fsub_out may be NULL when nothing is brought; a table beyond fsub_cap is CSSM_EINVAL_ARG (fsub_count says what it needs). */
+int cssm_fleet_pack_record_lgcp(const cssm_model_desc* desc, uint64_t n_particles, uint64_t seed, double t_prev, double t,
+                                uint32_t step, unsigned char* out, size_t cap, size_t* bytes,
+                                double* fsub_out, size_t fsub_cap, size_t* fsub_count);
 
 /* ---- errors / build info ------------------------------------------------------------------ */
 const char* cssm_last_error(void);
