@@ -6,11 +6,11 @@ This package is the thin host-side mirror of the reference's interface for that 
 """
 from . import _abi
 from ._abi import CssmError, load_library
-from .filter import FilterFleet, FilterLgcpFleet, ForecastOut, NativeLgcpFleet, NativePfFleet, ObservationWithState, ParticleFilter
+from .filter import FilterFleet, FilterInitFleet, FilterLgcpFleet, ForecastOut, NativeLgcpFleet, NativePfFleet, ObservationWithState, ParticleFilter
 from .simulate import LgcpSim, SimulateData, SimulatedPoint, lgcp_events_data, lgcp_fleet_data, simulate, simulate_from, simulate_lgcp, simulate_lgcp_last_ms
 from .streaming import Streaming
 from .model import (Data, Model, Parameters, ParamNode, Sde, SdeParameter, TimedObservation,
                     UnparamModel, UnparamSde, logistic, logit)
 
-__all__ = ["_abi", "CssmError", "load_library", "FilterFleet", "ForecastOut", "NativePfFleet", "NativeLgcpFleet", "FilterLgcpFleet", "lgcp_fleet_data", "Streaming", "SimulateData", "SimulatedPoint", "simulate", "simulate_from", "LgcpSim", "simulate_lgcp", "simulate_lgcp_last_ms", "lgcp_events_data", "ObservationWithState", "ParticleFilter", "Data", "Model", "Parameters", "ParamNode", "Sde",
+__all__ = ["_abi", "CssmError", "load_library", "FilterFleet", "ForecastOut", "NativePfFleet", "NativeLgcpFleet", "FilterLgcpFleet", "FilterInitFleet", "lgcp_fleet_data", "Streaming", "SimulateData", "SimulatedPoint", "simulate", "simulate_from", "LgcpSim", "simulate_lgcp", "simulate_lgcp_last_ms", "lgcp_events_data", "ObservationWithState", "ParticleFilter", "Data", "Model", "Parameters", "ParamNode", "Sde",
            "SdeParameter", "TimedObservation", "UnparamModel", "UnparamSde", "logistic", "logit"]

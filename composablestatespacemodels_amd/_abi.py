@@ -226,7 +226,11 @@ SYMBOLS = [
     ("cssm_fleet_create_lgcp", C.c_int, [_descp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_h)]),
     ("cssm_fleet_pack_record_lgcp", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_uint32, _u8p, C.c_size_t,
                                               C.POINTER(C.c_size_t), _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
-    ("cssm_diag_copy_ceiling", C.c_int, [C.c_int, C.c_size_t, C.c_int, _dp]),
+    ("cssm_fleet_init_from", C.c_int, [_h, _u8p, _dp, _u64p, _dp, _u32p, _u64p, _u32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_ll_filter_more", C.c_int, [_h, _u64p, _dp, _dp, _u8p, _dp, _dp, _i32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_filter_intervals_more", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_double, _dp, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                   C.POINTER(C.c_int)]),
+    ("cssm_diag_copy_ceiling", C.c_int,[C.c_int, C.c_size_t, C.c_int, _dp]),
     ("cssm_contract_eval", C.c_int, [C.c_int, C.c_int, _dp, C.c_size_t, _dp, C.c_size_t]),
     ("cssm_desc_flatten", C.c_int, [_descp, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("cssm_last_error", C.c_char_p, []),

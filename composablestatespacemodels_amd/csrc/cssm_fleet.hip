@@ -483,6 +483,8 @@ static void fleet_fc_row(int d, const double* src, const int32_t* pit, bool ok, 
 //   path: R sampleOne slots (u32) | ival: [S][d] f coefficients, F at every series' t0 | fcst: R keys (u64), R data (f64), S observation
 //   parameters, R flags (u32) padded to 8 bytes | ring: R slots (u32) and S base slots (u32), each padded to 8 bytes, then the lineage
 //   launch's Q requests (FleetWinReq), Q x L slot words (u32, padded), Q x L x d f coefficients] -- a launch carries one rider at most.
+// A launch that starts clouds from the caller's states (cssm_fleet_init_from; no records, no rider): [S + 1 row offsets (u64)] [S keys
+// (u64)] [M rows of d doubles] [the caller's picks: S x N (u32), padded -- where given]; the rows taken come back in d_rows ([S][N] u32).
 // An LGCP fleet's launch: the records are FleetLgcpRecHead ones, sampleOne's slots live inside them (no path rider is staged), and the
 // launch's sub-step table (doubles; empty unless f depends on time) comes last.
 // Written by the rider into d_rows, preset to 0xff bytes (NaN; -1 in the counts) for what no block writes:
@@ -496,6 +498,8 @@ struct FleetStage {
   size_t fsub = 0, fsub_doubles = 0;                                                   // (LGCP fleet) the sub-step table
   size_t ctl = 0, recs = 0, ride = 0, fc_y = 0, fc_op = 0, fc_flags = 0, bytes = 0;   // byte offsets into the staging, and its size
   size_t w_base = 0, w_req = 0, w_words = 0, w_fco = 0;                                // ... of the ring rider
+  bool from = false;                                                                   // cssm_fleet_init_from's launch ...
+  size_t fr_keys = 0, fr_x = 0, fr_pick = 0;                                           // ... and its offsets (the row offsets are at `ride`)
   size_t rows = 0, out_doubles = 0, rows_bytes = 0;   // d_rows: the rows of ival / fcst and their doubles; the bytes of any rider
 };
 struct FleetStageView {   // the staging on the host or on the device; the pointers of another rider are null
@@ -505,12 +509,17 @@ struct FleetStageView {   // the staging on the host or on the device; the point
   unsigned long long* keys; double* y; cssm_obs_params* op; uint32_t* flags;
   uint32_t *w_slot, *w_base; FleetWinReq* w_req; uint32_t* w_words; double* w_fco;
   double* fsub;
+  unsigned long long *fr_moff, *fr_keys; double* fr_x; uint32_t* fr_pick;
 };
 static FleetStageView fleet_view(const FleetStage& st, const FleetBuf& b) {
   FleetStageView v{};
   v.off = b.at<unsigned long long>(); v.ctl = b.at<uint32_t>(st.ctl); v.recs = b.at<unsigned char>(st.recs);
   if (st.kind == FleetKind::path && !st.lgcp) v.picks = b.at<uint32_t>(st.ride);
   if (st.lgcp) v.fsub = b.at<double>(st.fsub);
+  if (st.from) {
+    v.fr_moff = b.at<unsigned long long>(st.ride); v.fr_keys = b.at<unsigned long long>(st.fr_keys); v.fr_x = b.at<double>(st.fr_x);
+    if (st.fr_pick) v.fr_pick = b.at<uint32_t>(st.fr_pick);
+  }
   if (st.kind == FleetKind::ival) v.fco0 = b.at<double>(st.ride);
   if (st.kind == FleetKind::fcst) {
     v.keys = b.at<unsigned long long>(st.ride); v.y = b.at<double>(st.fc_y);
@@ -534,6 +543,12 @@ static const double* fleet_rec_fco(const FleetStageView& v, int d, size_t r) {
 struct FleetRide {
   FleetKind kind = FleetKind::plain;
   bool step = false;                 // ival / fcst: one row per series (cssm_fleet_step_*), not T_k + 1 / T_k rows per series
+  bool more = false;                 // plain / ival: the records CONTINUE every series from the cloud it holds (cssm_fleet_*_more): none is drawn,
+                                     // ival has a row per record and none for an initial cloud
+  bool from = false;                 // plain, no records: cssm_fleet_init_from -- from_M rows in all, the caller's picks or none, the rows taken
+  size_t from_M = 0;
+  bool from_picks = false;
+  uint32_t* pick_out = nullptr;
   double interval = 0.0;             // ival / fcst
   double *path_out = nullptr, *last_out = nullptr;   // path: receive the rows; either may be null
   const uint64_t* keys = nullptr;    // fcst: the caller's, one per record as the caller counts them ([off[S]], or [S] for a step), or null
@@ -568,7 +583,7 @@ static int fleet_ensure(cssm_fleet* f, size_t R, FleetRide& ride) {
     st.rows_bytes = (S * d + (ride.path_out ? (R + S) * d : 0u)) * 8u;
   } else if (st.kind == FleetKind::ival) {
     st.bytes += S * d * 8u;
-    st.rows = ride.step ? S : R + S;
+    st.rows = ride.step ? S : ride.more ? R : R + S;
     st.out_doubles = st.rows * (d + 1) * 3u;
     st.rows_bytes = st.out_doubles * 8u;
   } else if (st.kind == FleetKind::fcst) {
@@ -584,6 +599,13 @@ static int fleet_ensure(cssm_fleet* f, size_t R, FleetRide& ride) {
     st.rows = ride.win_Q * ride.win_L;
     st.out_doubles = st.rows * (d + 1) * 3u;
     st.rows_bytes = st.out_doubles * 8u;
+  }
+  if (ride.from) {
+    st.from = true;
+    st.fr_keys = st.ride + (S + 1u) * 8u; st.fr_x = st.fr_keys + S * 8u;
+    st.bytes = st.fr_x + ride.from_M * d * 8u;
+    if (ride.from_picks) { st.fr_pick = st.bytes; st.bytes += fleet_pad8(S * f->n * 4u); }
+    st.rows_bytes = ride.pick_out ? S * f->n * 4u : 0u;
   }
   if (st.lgcp) { st.fsub = fleet_pad8(st.bytes); st.fsub_doubles = ride.fsub_doubles; st.bytes = st.fsub + st.fsub_doubles * 8u; }
   if (!f->h_stage.reserve(st.bytes, true)) return fail(CSSM_ENOMEM, "fleet: %zu bytes of pinned staging", st.bytes);
@@ -631,7 +653,7 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
   const bool path = st.kind == FleetKind::path, ival = st.kind == FleetKind::ival, fcst = st.kind == FleetKind::fcst, ring = st.kind == FleetKind::ring;
   if (!f->d_rows.reserve(st.rows_bytes, true))
     return fail(CSSM_ENOMEM, "fleet: %zu bytes of %s", st.rows_bytes,
-                path ? "sampled paths" : ival ? "filtered intervals" : ring ? "fixed-lag rows" : "one-step-ahead forecasts");
+                path ? "sampled paths" : ival ? "filtered intervals" : ring ? "fixed-lag rows" : st.from ? "picks" : "one-step-ahead forecasts");
   if (!ring) {   // the cloud of every series this launch runs is written outside its window
     const FleetStageView hv = fleet_view(st, f->h_stage);
     for (uint32_t k = 0; k < f->S; ++k)
@@ -660,7 +682,7 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
   }
   if (ival || fcst) {
     const FleetRanks r = fleet_ranks(f->n, ride.interval);
-    l.args.iv_rows = ride.step ? 1u : 0u; l.args.iv_np2 = r.np2; l.args.iv_rk = r.rk;
+    l.args.iv_rows = ride.step ? 1u : ride.more ? 2u : 0u; l.args.iv_np2 = r.np2; l.args.iv_rk = r.rk;
     l.lds = (size_t)r.np2 * 8u + (size_t)f->n * 4u;   // the keys of a row's sort take the weights' place
     ride.out.resize(st.out_doubles);
   }
@@ -670,6 +692,10 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
     l.args.fc.stage = f->d_fc_scratch.at<double>();
     l.args.fc.out = rows; l.args.fc.pit = f->d_rows.at<int32_t>(st.out_doubles * 8u);
     ride.pit.resize(st.rows * 2u);
+  }
+  if (st.from) {
+    l.args.fr_moff = dv.fr_moff; l.args.fr_keys = dv.fr_keys; l.args.fr_x = dv.fr_x; l.args.fr_pick = dv.fr_pick;
+    if (ride.pick_out) l.args.fr_pick_out = f->d_rows.at<uint32_t>();
   }
   if (ring) {
     l.args.ring.x = f->win.at<double>(); l.args.ring.a = f->win.at<uint32_t>((size_t)f->S * f->win_slices * f->d * f->n * 8u);
@@ -702,6 +728,7 @@ static int fleet_launch(cssm_fleet* f, FleetRide& ride, double* ll_t, int32_t* e
   if (R && ll_t) HIP_TRY(hipMemcpyAsync(ll_t, f->d_ll_t.p, R * 8, hipMemcpyDeviceToHost, f->stream));
   if (R && ess_t) HIP_TRY(hipMemcpyAsync(ess_t, f->d_ess_t.p, R * 4, hipMemcpyDeviceToHost, f->stream));
   if (st.out_doubles) HIP_TRY(hipMemcpyAsync(ride.out.data(), rows, st.out_doubles * 8u, hipMemcpyDeviceToHost, f->stream));
+  if (st.from && ride.pick_out) HIP_TRY(hipMemcpyAsync(ride.pick_out, f->d_rows.p, st.rows_bytes, hipMemcpyDeviceToHost, f->stream));
   if (fcst && st.rows) HIP_TRY(hipMemcpyAsync(ride.pit.data(), l.args.fc.pit, st.rows * 8u, hipMemcpyDeviceToHost, f->stream));
   HIP_TRY(hipEventRecord(f->ev[EV_CALL_END], f->stream));
   HIP_TRY(hipStreamSynchronize(f->stream));
@@ -744,29 +771,41 @@ static void fleet_fc_record(const cssm_fleet* f, const FleetRide& ride, const Fl
 }
 
 // llFilter / filter of every series: the records of all of them built (threaded above 8192), ONE upload, ONE launch with the call's
-// rider, ONE read-back.
+// rider, ONE read-back.  ride.more: the records continue every series from the cloud it holds (cssm_fleet_ll_filter_more) -- no cloud is
+// drawn, a series' first increment is taken from its clock and its records count on from its observation index, as cssm_fleet_step's one
+// record does; a series without a cloud gets no block, so the launch's records are the caller's without that series' (roff below).
 static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double* ll_out, double* ll_t,
                             int32_t* ess_t, int* rc_out, FleetRide& ride) {
   const uint32_t S = f->S;
+  const bool more = ride.more;
   int rc = fleet_off_check(off, S);
   if (rc) return rc;
-  const size_t R = (size_t)off[S];
-  if (R && (!t || (!y && !f->lgcp))) return fail(CSSM_EINVAL_ARG, "null data");
+  if (off[S] && (!t || (!y && !f->lgcp))) return fail(CSSM_EINVAL_ARG, "null data");
+  if (more) {
+    bool any_live = false;
+    for (uint32_t k = 0; k < S; ++k) any_live = any_live || f->live[k];
+    if (!any_live) return fail(CSSM_ESTATE, "no series of the fleet is initialised (cssm_fleet_init / cssm_fleet_ll_filter first)");
+  }
   HIP_TRY(hipSetDevice(f->device));
   const auto tb0 = std::chrono::steady_clock::now();
   ride.step = false;
+  auto runs = [&](size_t k) { return off[k + 1] > off[k] && (!more || f->live[k]); };
+  std::vector<size_t> roff((size_t)S + 1u, 0);   // series k's records as the launch counts them: the caller's, unless a series is left out
+  for (uint32_t k = 0; k < S; ++k) roff[k + 1] = roff[k] + (runs(k) ? (size_t)(off[k + 1] - off[k]) : 0u);
+  const size_t R = roff[S];
   auto t_min = [&](size_t a, size_t b) {                                   // data.minBy(_.t).t
     double m = t[a];
     for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;
     return m;
   };
+  auto t_start = [&](size_t k) { return more ? f->t[k] : t_min((size_t)off[k], (size_t)off[k + 1]); };   // where a series' first increment starts
   std::vector<size_t> toff;   // (LGCP fleet, f depends on time) where series k's rows start in the launch's sub-step table (doubles)
   if (f->lgcp && f->base.lgcp_tdep) {
     toff.assign((size_t)S + 1u, 0);
     fleet_parallel(S, R, [&](size_t lo, size_t hi) {
       for (size_t k = lo; k < hi; ++k) {
         const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
-        if (b > a) toff[k + 1] = fleet_lgcp_rows(f->models[k], t_min(a, b), t + a, b - a);
+        if (runs(k)) toff[k + 1] = fleet_lgcp_rows(f->models[k], t_start(k), t + a, b - a);
       }
     });
     for (uint32_t k = 0; k < S; ++k) toff[k + 1] += toff[k];
@@ -779,22 +818,21 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
   const size_t RB = ride.st.rec_bytes;
   const bool fcst = ride.kind == FleetKind::fcst;
   if (fcst) fleet_fc_series(f, ride, h, [&](uint32_t k) { return off[k + 1] > off[k]; });
-  for (uint32_t k = 0; k <= S; ++k) h.off[k] = off[k];
-  std::vector<double> t0(S, 0.0);
+  for (uint32_t k = 0; k <= S; ++k) h.off[k] = roff[k];
   std::atomic<int> pack_rc{CSSM_OK};
   fleet_parallel(S, R, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
-      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
-      h.ctl[k] = (b > a) ? CSSM_FLEET_CTL_INIT : 0u;
-      if (h.fco0) for (int c = 0; c < f->d; ++c) h.fco0[k * f->d + c] = 0.0;
-      if (b == a) continue;
-      const double m = t_min(a, b);
-      t0[k] = m;
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1], r0 = roff[k];
+      h.ctl[k] = (b > a && !more) ? CSSM_FLEET_CTL_INIT : 0u;
+      if (h.fco0) for (int c = 0; c < f->d; ++c) h.fco0[k * f->d + c] = 0.0;   // (a launch that continues draws no cloud: not read)
+      if (!runs(k)) continue;
+      const double m = t_start(k);
+      const uint32_t i0 = more ? f->step[k] : 0u;                        // the series' observation index at its first record
       if (f->lgcp) {                                                     // every record an event; the series' rows of the table behind them
         std::vector<double> tab;
         double tp = m;
         for (size_t s = a; s < b; ++s) {
-          const int prc = fleet_pack_rec_lgcp(f->models[k], tp, t[s], (uint32_t)(s - a), h.recs + s * RB, tab, toff.empty() ? 0u : toff[k]);
+          const int prc = fleet_pack_rec_lgcp(f->models[k], tp, t[s], i0 + (uint32_t)(s - a), h.recs + (r0 + s - a) * RB, tab, toff.empty() ? 0u : toff[k]);
           if (prc) pack_rc = prc;
           tp = t[s];
         }
@@ -802,32 +840,45 @@ static int fleet_filter_all(cssm_fleet* f, const uint64_t* off, const double* t,
         else if (!tab.empty()) pack_rc = CSSM_ENOMEM;
         continue;
       }
-      if (h.fco0) {                                                      // F(t0): t0 need not be the first record's time
-        StepRec r0;
-        cssm_build_rec(&f->models[k], m, m, 0.0, 0, 0u, &r0);
-        for (int c = 0; c < f->d; ++c) h.fco0[k * f->d + c] = r0.fco[c];
+      if (h.fco0 && !more) {                                             // F(t0): t0 need not be the first record's time
+        StepRec rec0;
+        cssm_build_rec(&f->models[k], m, m, 0.0, 0, 0u, &rec0);
+        for (int c = 0; c < f->d; ++c) h.fco0[k * f->d + c] = rec0.fco[c];
       }
       double tp = m;
       for (size_t s = a; s < b; ++s) {
         const int has = has_obs ? (int)has_obs[s] : 1;
-        fleet_pack_rec(f->models[k], tp, t[s], y[s], has, (uint32_t)(s - a), h.recs + s * RB, h.picks ? h.picks + s : nullptr);
-        if (fcst) fleet_fc_record(f, ride, h, (uint32_t)k, s, s, (uint32_t)(s - a), tp, t[s], y[s], has);
+        const size_t r = r0 + (s - a);
+        fleet_pack_rec(f->models[k], tp, t[s], y[s], has, i0 + (uint32_t)(s - a), h.recs + r * RB, h.picks ? h.picks + r : nullptr);
+        if (fcst) fleet_fc_record(f, ride, h, (uint32_t)k, r, s, (uint32_t)(s - a), tp, t[s], y[s], has);
         tp = t[s];
       }
     }
   });
   if (pack_rc) return fail(pack_rc, "fleet: the sub-step table of the launch could not be built");
   if (ride.kind == FleetKind::path) f->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-  rc = fleet_launch(f, ride, ll_t, ess_t);
+  // per-observation results: straight into the caller's arrays, unless a series was left out -- then by way of the launch's own order
+  const bool same = R == (size_t)off[S];
+  std::vector<double> r_ll(same || !ll_t ? 0u : R);
+  std::vector<int32_t> r_ess(same || !ess_t ? 0u : R);
+  rc = fleet_launch(f, ride, same ? ll_t : (ll_t ? r_ll.data() : nullptr), same ? ess_t : (ess_t ? r_ess.data() : nullptr));
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) {
     const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+    if (!same) {
+      for (size_t s = a; s < b; ++s) {
+        if (ll_t) ll_t[s] = runs(k) ? r_ll[roff[k] + s - a] : cssm_nan();
+        if (ess_t) ess_t[s] = runs(k) ? r_ess[roff[k] + s - a] : -1;
+      }
+    }
+    if (more && b == a) { rc_out[k] = CSSM_OK; continue; }                 // continued by nothing: untouched
+    if (more && !f->live[k]) { rc_out[k] = CSSM_ESTATE; continue; }        // no cloud: never initialised, or failed since
     if (b == a) { rc_out[k] = CSSM_EINVAL_ARG; ll_out[k] = cssm_nan(); continue; }   // (the reference's minBy throws on an empty Vector)
     const FleetSeries& s = f->h_ser[k];
     if (s.err) {
       rc_out[k] = CSSM_ENONFINITE; ll_out[k] = cssm_nan(); f->live[k] = 0;
     } else {
-      rc_out[k] = CSSM_OK; ll_out[k] = s.ll; f->live[k] = 1; f->t[k] = t[b - 1]; f->step[k] = (uint32_t)(b - a);
+      rc_out[k] = CSSM_OK; ll_out[k] = s.ll; f->live[k] = 1; f->t[k] = t[b - 1]; f->step[k] = (more ? f->step[k] : 0u) + (uint32_t)(b - a);
     }
   }
   return CSSM_OK;
@@ -931,6 +982,57 @@ extern "C" int cssm_fleet_filter_forecasts(cssm_fleet* f, const uint64_t* off, c
   return CSSM_OK;
 }
 
+// cssm_pf_ll_filter_more of every series: T_k MORE records of the filters that are already running, in the ONE launch of
+// cssm_fleet_ll_filter -- fleet_filter_all in its continue mode.  What needs no fleet is refused first, so that it is refused on any host.
+extern "C" int cssm_fleet_ll_filter_more(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                         double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out) {
+  if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
+  if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || (!y && !(f && f->lgcp))) return fail(CSSM_EINVAL_ARG, "null data");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  FleetRide ride;
+  ride.more = true;
+  return fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, rc_out, ride);
+}
+
+// ... and cssm_fleet_summary of the cloud behind every one of those records from the same launch (the IVAL instantiation): a row per
+// record, laid out like t -- none for an initial cloud, since none is drawn.
+extern "C" int cssm_fleet_filter_intervals_more(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                                double interval, double* ll_out, double* ll_t, int32_t* ess_t, double* state_mean, double* state_lower,
+                                                double* state_upper, double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_filter_intervals_more", FLEET_LGCP_SERVED);
+  if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
+  if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const uint32_t S = f->S;
+  std::vector<uint8_t> ran(S);   // (a series that fails loses its cloud: asked before the call)
+  for (uint32_t k = 0; k < S; ++k) ran[k] = f->live[k];
+  FleetRide ride;
+  ride.kind = FleetKind::ival; ride.interval = interval; ride.more = true;
+  int rc = fleet_filter_all(f, off, t, y, has_obs, ll_out, ll_t, ess_t, rc_out, ride);
+  if (rc) return rc;
+  const int d = f->d;
+  const size_t R = (size_t)off[S], rowsz = (size_t)(d + 1) * 3u;
+  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  for (double* p : {state_mean, state_lower, state_upper}) if (p) std::fill(p, p + R * (size_t)d, cssm_nan());
+  for (double* p : {eta_of_mean, eta_lower, eta_upper}) if (p) std::fill(p, p + R, cssm_nan());
+  const FleetStageView h = fleet_view(ride.st, f->h_stage);   // (the staged launch is still there: its own offsets, the f coefficients of every row)
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1], r0 = (size_t)h.off[k];
+      if (b == a || !ran[k]) continue;
+      const FleetSeries& s = f->h_ser[k];
+      const size_t nrows = s.err ? (size_t)s.fail_rec : b - a;   // a failure at record s keeps the rows of the records before it
+      for (size_t i = 0; i < nrows; ++i) fleet_iv_row(f, (uint32_t)k, ride.out.data() + (r0 + i) * rowsz, fleet_rec_fco(h, d, r0 + i), true, o, a + i);
+    }
+  });
+  return CSSM_OK;
+}
+
 // ParticleMetropolisHastings (model/PMMH.scala:68-81,114-123) for S chains in lockstep, a chain per series: chain k is cssm_pmmh_run
 // with theta0[k], seeds[k] and series k's slice of the data -- proposals, filter keys and decisions are cssm_pmmh_chain_*'s, as in
 // every PMMH driver -- and an iteration's S filters are ONE fleet launch that brings back S x d doubles of sampled states.
@@ -1017,6 +1119,72 @@ extern "C" int cssm_fleet_init(cssm_fleet* f, const double* t0) {
   rc = fleet_launch(f, ride, nullptr, nullptr);
   if (rc) return rc;
   for (uint32_t k = 0; k < S; ++k) { f->live[k] = 1; f->t[k] = t0[k]; f->step[k] = 0u; }
+  return CSSM_OK;
+}
+
+// FilterInit(mod, resample, initState).initialiseState (model/ParticleFilter.scala:252-271) of the active series, and its posterior form: the
+// clouds come from the caller -- one row replicated, or the rows of a posterior sample under the caller's picks or the selection
+// cssm_fleet_forecast_posterior makes.  ONE launch without records, as cssm_fleet_init's; a series the call refuses or does not name gets no
+// block and stays exactly as it was.
+extern "C" int cssm_fleet_init_from(cssm_fleet* f, const uint8_t* active, const double* t0, const uint64_t* moff, const double* x,
+                                    const uint32_t* pick, const uint64_t* keys, uint32_t* pick_out, int* rc_out) {
+  if (!t0 || !moff || !x || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument (t0, moff, x, rc_out)");
+  if (moff[0] != 0) return fail(CSSM_EINVAL_ARG, "moff[0] must be 0");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const uint32_t S = f->S, n = f->n;
+  const int d = f->d;
+  int rc = CSSM_OK;
+  for (uint32_t k = 0; k < S; ++k)
+    if ((rc = fleet_off_step("moff", moff, k))) return rc;
+  HIP_TRY(hipSetDevice(f->device));
+  FleetRide ride;
+  ride.from = true; ride.from_M = (size_t)moff[S]; ride.from_picks = pick != nullptr; ride.pick_out = pick_out;
+  rc = fleet_ensure(f, 0, ride);
+  if (rc) return rc;
+  const FleetStageView h = fleet_view(ride.st, f->h_stage);
+  std::vector<std::string> msg(S);
+  for (uint32_t k = 0; k <= S; ++k) { h.off[k] = 0; h.fr_moff[k] = moff[k]; }
+  if (pick) {
+    memcpy(h.fr_pick, pick, (size_t)S * n * 4u);
+    if (((size_t)S * n) & 1u) h.fr_pick[(size_t)S * n] = 0u;   // (the padding travels too)
+  }
+  fleet_parallel(S, (size_t)moff[S] + (pick ? (size_t)S * n : 0u), [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t ma = (size_t)moff[k], M = (size_t)moff[k + 1] - ma;
+      h.ctl[k] = 0u; h.fr_keys[k] = keys ? keys[k] : 0ull; rc_out[k] = CSSM_OK;
+      std::fill(h.fr_x + ma * (size_t)d, h.fr_x + (ma + M) * (size_t)d, 0.0);   // (the rows of a series that is not served travel as zeros)
+      if (active && !active[k]) continue;                                      // untouched: nothing of it is read
+      auto refuse = [&](const std::string& why) { rc_out[k] = CSSM_EINVAL_ARG; msg[k] = why; };
+      if (M == 0) { refuse("no state to start from (M = 0)"); continue; }
+      if (M > 0xffffffffull) { refuse("more than 2^32 - 1 rows"); continue; }
+      if (!std::isfinite(t0[k])) { refuse("t0 is not finite"); continue; }
+      const double* xs = x + ma * (size_t)d;
+      for (size_t m = 0; m < M && !rc_out[k]; ++m)
+        for (int c = 0; c < d; ++c)
+          if (!std::isfinite(xs[m * d + c])) { refuse("x row " + std::to_string(m) + ": component " + std::to_string(c) + " is not finite"); break; }
+      if (rc_out[k]) continue;
+      if (M > 1 && !pick && !keys) { refuse("M = " + std::to_string(M) + " rows and neither pick nor keys to choose among them"); continue; }
+      if (pick)
+        for (uint32_t i = 0; i < n; ++i)
+          if (pick[k * n + i] >= M) {
+            refuse("pick[" + std::to_string(i) + "] = " + std::to_string(pick[k * n + i]) + " is not below M = " + std::to_string(M));
+            break;
+          }
+      if (rc_out[k]) continue;
+      memcpy(h.fr_x + ma * (size_t)d, xs, M * (size_t)d * 8u);
+      h.ctl[k] = CSSM_FLEET_CTL_INIT | CSSM_FLEET_CTL_FROM;
+    }
+  });
+  if (S & 1u) h.ctl[S] = 0u;
+  rc = fleet_launch(f, ride, nullptr, nullptr);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < S; ++k) {
+    const bool served = (h.ctl[k] & CSSM_FLEET_CTL_FROM) != 0u;
+    if (served) { f->live[k] = 1; f->t[k] = t0[k]; f->step[k] = 0u; }
+    else if (pick_out) std::fill(pick_out + (size_t)k * n, pick_out + (size_t)(k + 1) * n, 0u);
+  }
+  for (uint32_t k = 0; k < S; ++k)   // (the call succeeds; the message names the first refused series)
+    if (rc_out[k]) { (void)fail(CSSM_EINVAL_ARG, "series %u: %s", k, msg[k].c_str()); break; }
   return CSSM_OK;
 }
 

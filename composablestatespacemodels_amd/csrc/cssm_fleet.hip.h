@@ -46,6 +46,7 @@ struct FleetSeries {
 
 #define CSSM_FLEET_CTL_INIT 1u   /* draw the initial cloud before the series' first record of this launch */
 #define CSSM_FLEET_CTL_BASE 2u   /* (RING) the series' window restarts: its first record of this launch also keeps the cloud it gathers */
+#define CSSM_FLEET_CTL_FROM 4u   /* (with _INIT) the initial cloud is not drawn: particle i starts at a row of the caller's (FleetArgs::fr_*) */
 
 // The window of cssm_fleet_step_interpolate (k_fleet_series<D, false, false, false, false, true> writes it, k_fleet_window reads it):
 // per series `slices` clouds ([d][n] doubles each) and as many ancestor arrays ([n] each).  The host does the ring arithmetic: a kernel
@@ -90,7 +91,8 @@ struct FleetArgs {
   // more behind every field the other instantiations read.
   const double* iv_fco0;             // [S][d]: F at series k's t0, the f coefficients of its row 0 (read by a launch that draws the cloud)
   double* iv_out;                    // rows of [d + 1][3] (mean, lower, upper), preset to NaN; iv_rows == 0: series k owns rows off[k] + k ..
-                                     // off[k + 1] + k, row 0 the initial cloud; iv_rows == 1 (step): row k is the cloud behind series k's record
+                                     // off[k + 1] + k, row 0 the initial cloud; iv_rows == 1 (step): row k is the cloud behind series k's record;
+                                     // iv_rows == 2 (a launch that continues: no initial cloud): row r is the cloud behind record r of the launch
   uint32_t iv_rows;
   uint32_t iv_np2;                   // the power of two >= max(n, 2): the keys a row's sort holds where the weights were
   FleetRowRanks iv_rk;
@@ -104,7 +106,21 @@ struct FleetArgs {
   // an LGCP fleet's launch (k_fleet_series<D, PATH, false, false, false, false, true> only: cssm_fleet_lgcp.hip.h), behind every field the
   // other instantiations read.  `recs` are then FleetLgcpRecHead records, CSSM_FLEET_LGCP_REC_BYTES(d) each, and `picks` is not read.
   const double* fsub;                // the launch's sub-step table (f at the sub-step times of a seasonal leaf), or null: f is the record's own
+  // the clouds of cssm_fleet_init_from (a series whose control word has CSSM_FLEET_CTL_FROM; FilterInit, model/ParticleFilter.scala:252-271),
+  // behind every field the other launches read.  Series k owns the rows fr_moff[k] .. fr_moff[k + 1] - 1 of fr_x (d doubles each, M_k >= 1 of
+  // them); particle i starts at row fr_pick[k n + i] of them, or without fr_pick at row cssm_posterior_pick(fr_keys[k], i, M_k) -- the
+  // selection k_fleet_forecast_post makes; M_k = 1 reads neither.  fr_pick_out (may be null; [S][n]) receives the rows taken.
+  const double* fr_x;
+  const unsigned long long* fr_moff;
+  const unsigned long long* fr_keys;
+  const uint32_t* fr_pick;
+  uint32_t* fr_pick_out;
 };
+
+// (IVAL) the row of FleetArgs::iv_out that receives the cloud behind record r of series k
+__device__ __forceinline__ size_t fleet_iv_row_of(uint32_t iv_rows, uint32_t k, unsigned long long r) {
+  return iv_rows == 1u ? (size_t)k : iv_rows == 2u ? (size_t)r : (size_t)(r + k + 1u);
+}
 
 // a - b mod 2^128 (integers: exact)
 __device__ __forceinline__ cssm_u128 fleet_u128_sub(cssm_u128 a, cssm_u128 b) {
@@ -126,6 +142,22 @@ __device__ __forceinline__ uint32_t fleet_end_slot(cssm_u128 run, double totd, d
 template <int D>
 __device__ __forceinline__ void fleet_path_row(const double* buf, const uint32_t* s_anc, uint32_t n, uint32_t pick, double* row, uint32_t tid) {
   if (tid < (uint32_t)D) row[tid] = buf[(size_t)tid * n + s_anc[pick]];
+}
+
+// initialiseState of FilterInit (model/ParticleFilter.scala:258-262) and its posterior form: the cloud of a series from its M rows of the
+// caller's (`rows`; FleetArgs::fr_*) into buffer 0, identity ancestors.  `pick` / `pick_out`: the series' own n entries, or null.  Called
+// once per launch by a series that is started this way, before its records.
+template <int D>
+__device__ __forceinline__ void fleet_cloud_from(const double* rows, unsigned long long M, const uint32_t* pick, unsigned long long key,
+                                                 uint32_t* pick_out, double* st, uint32_t* s_anc, uint32_t n, uint32_t tid, uint32_t bs) {
+  for (uint32_t i = tid; i < n; i += bs) {
+    const uint32_t p = (M == 1ull) ? 0u : (pick ? pick[i] : cssm_posterior_pick(key, (uint64_t)i, M));
+    const double* row = rows + (size_t)p * D;
+#pragma unroll
+    for (int c = 0; c < D; ++c) st[(size_t)c * n + i] = row[c];
+    if (pick_out) pick_out[i] = p;
+    s_anc[i] = i;
+  }
 }
 
 // llFilter / stepFilter of series blockIdx.x over its records of this launch (model/ParticleFilter.scala:105-140).
@@ -179,7 +211,13 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
   double ll; int32_t ess; uint32_t err = 0u, fail_rec = 0u;
   double next_ref = cssm_nan();                                // (LGCP) no event of this cloud yet whose max could predict a level
   if (HIST || (ctl & CSSM_FLEET_CTL_INIT)) {
-    // initialiseState (:105-108): x0 = sqrt(c0) z + m0 into buffer 0, identity ancestors, ll = 0, ess = N
+    // initialiseState (:105-108): x0 = sqrt(c0) z + m0 into buffer 0, identity ancestors, ll = 0, ess = N -- or (uniform) the caller's rows
+    // (cssm_fleet_init_from launches the instantiation without a rider: the others hold no trace of its branch)
+    if ((!PATH && !HIST && !IVAL && !FCST && !RING) && (ctl & CSSM_FLEET_CTL_FROM)) {
+      const unsigned long long m0 = a.fr_moff[k];
+      fleet_cloud_from<D>(a.fr_x + (size_t)m0 * D, a.fr_moff[k + 1] - m0, a.fr_pick ? a.fr_pick + (size_t)k * n : nullptr, a.fr_keys[k],
+                          a.fr_pick_out ? a.fr_pick_out + (size_t)k * n : nullptr, st, s_anc, n, tid, bs);
+    } else
     for (uint32_t i = tid; i < n; i += bs) {
       double z[D];
       draw_normals<D>(seed, (uint64_t)i, 0u, CSSM_STREAM_INIT, tab, z);
@@ -336,7 +374,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
       if (IVAL) {                                               // the cloud this record moved, through identity ancestors
         __syncthreads();
         fleet_cloud_intervals<D>(dst, s_anc, n, a.iv_np2, a.mk, s_rec.fco, a.iv_rk, reinterpret_cast<unsigned long long*>(s_lw),
-                                 a.iv_out + (size_t)(a.iv_rows ? k : r + k + 1u) * (D + 1) * 3u);
+                                 a.iv_out + fleet_iv_row_of(a.iv_rows, k, r) * (D + 1) * 3u);
       }
       continue;
     }
@@ -420,7 +458,7 @@ __global__ __launch_bounds__(CSSM_FLEET_MAX_THREADS, CSSM_FLEET_WAVES(D)) void k
     if (IVAL) {                                                 // the cloud this record wrote, through the ancestors that resampled it
       __syncthreads();
       fleet_cloud_intervals<D>(dst, s_anc, n, a.iv_np2, a.mk, s_rec.fco, a.iv_rk, reinterpret_cast<unsigned long long*>(s_lw),
-                               a.iv_out + (size_t)(a.iv_rows ? k : r + k + 1u) * (D + 1) * 3u);
+                               a.iv_out + fleet_iv_row_of(a.iv_rows, k, r) * (D + 1) * 3u);
     }
   }
   if (HIST) {                                                   // the fleet's ancestors and scalars stay as they were

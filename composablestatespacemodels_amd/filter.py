@@ -505,6 +505,45 @@ class NativePfFleet:
         per = {name: cls._split(off, v) for name, v in arr.items()}
         return [{name: rows[k] for name, rows in per.items()} for k in range(len(off) - 1)]
 
+    def ll_filter_more(self, datas):
+        """cssm_fleet_ll_filter_more: T_k MORE records of every running series in one launch -- ``NativePf.run_more`` per series, what a
+        loop of ``step`` does with a launch per record.  ``datas[k]`` may be empty (the series is left alone).  ``(ll[S], [ll_t of series
+        k], [ess_t of series k], rc[S])``: ll[k] accumulated since the series was initialised (NaN for a series the call did not advance);
+        rc[k] -7: records for a series without a cloud, -5: its weights were unusable."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        return self.ll_filter_more_packed(*self.pack(datas, allow_empty=True))
+
+    def ll_filter_more_packed(self, off, t, y, has):
+        """``ll_filter_more`` on arrays ``pack`` made."""
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        ll, rc, ll_t, ess_t = self._record_outputs(R)
+        ll[:] = np.nan
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_ll_filter_more(self._h, _p(off), _p(t), _p(y), _p(has), _p(ll), _p(ll_t), _p(ess_t), _p(rc)))
+        return ll, self._split(off, ll_t), self._split(off, ess_t), rc
+
+    def filter_intervals_more(self, datas, interval: float = 0.975):
+        """cssm_fleet_filter_intervals_more: ``ll_filter_more`` and, from the same launch, ``summary`` of the cloud after every record:
+        ``(ll[S], [ll_t of series k], [ess_t of series k], per-series list of (mean[T_k, d], lower, upper, eta_of_mean[T_k], eta_lower,
+        eta_upper), rc[S])`` -- a row per record, none for an initial cloud; rows behind a failing record and of a series without a cloud
+        read NaN."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        return self.filter_intervals_more_packed(*self.pack(datas, allow_empty=True), interval=interval)
+
+    def filter_intervals_more_packed(self, off, t, y, has, interval: float = 0.975):
+        """``filter_intervals_more`` on arrays ``pack`` made."""
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        ll, rc, ll_t, ess_t = self._record_outputs(R)
+        ll[:] = np.nan
+        rows = _interval_arrays((R,), self.d)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_filter_intervals_more(self._h, _p(off), _p(t), _p(y), _p(has), float(interval), _p(ll), _p(ll_t), _p(ess_t),
+                                                             *map(_p, rows), _p(rc)))
+        per = [self._split(off, a) for a in rows]
+        return ll, self._split(off, ll_t), self._split(off, ess_t), [tuple(r[k] for r in per) for k in range(self.S)], rc
+
     def filter(self, datas, want_path: bool = True):
         """``filter`` of every series (cssm_fleet_filter): ``(ll[S], [ll_t of series k], [ess_t of series k], paths, last[S, d], rc[S])``.
         ``paths``: a list of ``[T_k + 1, d]`` arrays -- row 0 the sampled particle of the initial cloud, row s + 1 the one after
@@ -661,6 +700,51 @@ class NativePfFleet:
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (self.S,)), dtype=np.float64)
         self.generation += 1
         _abi.check(self.lib.cssm_fleet_init(self._h, _p(t0)))
+
+    def pack_states(self, rows):
+        """The ragged states of ``cssm_fleet_init_from`` from a sequence of S arrays ``[M_k, d]`` or ``[d]`` (None or empty: M_k = 0):
+        ``(moff uint64[S + 1], x float64[M, d])``, C-contiguous -- ``pack_posteriors`` without the parameter rows."""
+        if len(rows) != self.S:
+            raise ValueError("one array of states per series (None or empty: none)")
+        post = []
+        for k, r in enumerate(rows):
+            x = np.zeros(0) if r is None else np.asarray(r, dtype=np.float64)
+            if x.size % self.d:
+                raise ValueError(f"series {k}: its states hold {x.size} numbers, no multiple of d = {self.d}")
+            x = x.reshape(-1, self.d)
+            post.append((np.zeros((len(x), 1)), x) if len(x) else None)      # (rows of one placeholder parameter: not handed on)
+        moff, _, x = self.pack_posteriors(post, n_theta=1)
+        return moff, x
+
+    def init_from(self, t0s, rows, picks=None, keys=None, active=None):
+        """cssm_fleet_init_from: the clouds of the active series (``active`` None = all) come from the caller.  ``rows[k]``: ``[d]`` or
+        ``[1, d]`` -- that state replicated, ``FilterInit`` -- or ``[M_k, d]``, a posterior sample of the state at ``t0s[k]`` (a scalar serves
+        every series); particle i of series k then starts at row ``picks[k, i]`` (``picks``: [S, N] indices, series k's below M_k) or, without
+        ``picks``, at the row ``cssm_fleet_forecast_posterior`` selects under ``keys[k]`` (S Philox keys).  ``(pick_out uint32[S, N], rc[S])``;
+        rc[k] != 0 is series k's own refusal (-6: no rows, a non-finite t0 or entry, a pick out of range, M_k > 1 with neither picks nor
+        keys), the series is then left as it was and its picks read 0.  The series continue with ``step`` or ``ll_filter_more``."""
+        moff, x = self.pack_states(rows)
+        t0 = np.asarray(t0s, dtype=np.float64)
+        if t0.ndim != 0 and t0.shape != (self.S,):
+            raise ValueError("one t0 per series (or one for all)")
+        t0 = np.ascontiguousarray(np.broadcast_to(t0, (self.S,)), dtype=np.float64)
+        pk = None
+        if picks is not None:
+            pa = np.asarray(picks)
+            if pa.shape != (self.S, self.n) or (pa < 0).any():
+                raise ValueError(f"picks must hold S x N = {self.S} x {self.n} non-negative indices")
+            pk = np.ascontiguousarray(pa, dtype=np.uint32)
+        ky = None
+        if keys is not None:
+            if len(keys) != self.S:
+                raise ValueError("one key per series")
+            ky = np.ascontiguousarray([int(v) & (2**64 - 1) for v in keys], dtype=np.uint64)
+        xx = x if len(x) else np.zeros((1, self.d))
+        pick_out = np.zeros((self.S, self.n), dtype=np.uint32)
+        rc = np.zeros(self.S, dtype=np.int32)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_init_from(self._h, _p(_u8(active)), _p(t0), _p(moff), _p(xx), _p(pk), _p(ky), _p(pick_out), _p(rc)))
+        return pick_out, rc
 
     def _step_inputs(self, t, y, has, active):
         """What every step call starts with: ``(t, y, has, active)`` as the C call takes them (None stays None), one ``(t, y)`` per
@@ -1244,6 +1328,15 @@ class FilterInit(_FilterBase):
         pf.init_from(t0, self.initState)
         return self._state(t0, None, 0.0, particles)
 
+    def llFilter(self, data: Sequence[TimedObservation], n: int) -> float:
+        """llFilter (:137-140) folds stepFilter from THIS class's initialiseState: the given state at the data's smallest time, then the
+        records in one native call (cssm_pf_ll_filter_more)."""
+        if self._host_resample is not None:
+            return super().llFilter(data, n)
+        t, y, h = split_data(data)
+        self.initialiseState(n, float(np.min(t)))
+        return self._pf.run_more(t, y, h)[0]
+
 
 class FilterLgcp(_FilterBase):
     """``FilterLgcp(mod, resample, precision)``, ParticleFilter.scala:169-227."""
@@ -1339,6 +1432,40 @@ class FilterFleet:
         t0 = np.broadcast_to(np.asarray(t0s, dtype=np.float64), (self.S,))
         self._fleet.init(t0)
         return self._wrap(t0, [None] * self.S, np.zeros(self.S), [self._fleet.n] * self.S)
+
+    def initialiseStateFrom(self, t0s, states, seed: Optional[int] = None) -> List[FleetState]:
+        """``FilterInit(mods[k], resample, states[k]).initialiseState`` of every series, or its posterior form, in one device call: each
+        entry of ``states`` is one state ``[d]`` (replicated) or the ``last_state`` array ``[M_k, d]`` of a posterior -- the second element
+        of each pair from ``pmmh.fleet_posterior_rows`` is accepted as it is --, its states at ``t0s[k]``; particle i then starts at the
+        row ``forecastPosterior`` selects for it.  seed = the Philox key of every series' selection; None: each series' default key
+        (``NativePfFleet.posterior_key``)."""
+        t0 = np.broadcast_to(np.asarray(t0s, dtype=np.float64), (self.S,))
+        keys = [self._fleet.posterior_key(k) for k in range(self.S)] if seed is None else [int(seed)] * self.S
+        _, rc = self._fleet.init_from(t0, states, keys=keys)
+        for k in range(self.S):
+            if rc[k]:
+                raise _abi.CssmError(int(rc[k]), self._fleet.lib.cssm_last_error().decode() or f"series {k}: its states were refused")
+        return self._wrap(t0, [None] * self.S, np.zeros(self.S), [self._fleet.n] * self.S)
+
+    def _more(self, datas, call):
+        """What both continuing calls do around theirs: one (possibly empty) list of data per series, the series' own statuses raised,
+        the states of before forgotten.  Returns ``(split data, what the call returned)``."""
+        split = [split_data(d) if len(d) else (np.zeros(0), np.zeros(0), None) for d in datas]
+        out = call(split)
+        self._raise_series(out[-1], stepping=True)
+        self._states = []
+        return split, out
+
+    def llFilterMore(self, datas: Sequence[Sequence[TimedObservation]]) -> np.ndarray:
+        """The next data of every running series in one device call (one launch; ``datas[k]`` may be empty): the log-likelihoods
+        accumulated since the series were initialised (NaN for a series without new data)."""
+        return self._more(datas, self._fleet.ll_filter_more)[1][0]
+
+    def filterIntervalsMore(self, datas: Sequence[Sequence[TimedObservation]], interval: float = 0.975) -> List[List[PfOut]]:
+        """``llFilterMore`` mapped through ``getIntervals``, from the same launch: per series one ``PfOut`` per datum, as
+        ``filterIntervals`` returns them behind its first."""
+        split, out = self._more(datas, lambda sp: self._fleet.filter_intervals_more(sp, float(interval)))
+        return [[_pfout(d.t, d.observation, out[3][k], i) for i, d in enumerate(datas[k])] for k in range(self.S)]
 
     def stepFilter(self, states: Sequence[FleetState], ys: Sequence[Optional[TimedObservation]]) -> List[FleetState]:
         """``ys[k]`` None = sensor k has nothing new (its state is returned as it is); a TimedObservation whose ``observation`` is None
@@ -1538,6 +1665,28 @@ class FilterFleet:
         rows = self._fleet.summary(0.975)
         st = self._states if self._states and self._states[0]._generation == self._fleet.generation else None
         return [_pfout(st[k].t if st else float("nan"), st[k].observation if st else None, rows, k, bound=lambda v: v) for k in range(self.S)]
+
+
+class FilterInitFleet(FilterFleet):
+    """``FilterInit(mods[k], resample, initStates[k])`` (ParticleFilter.scala:252-271) for many sensors at once: a ``FilterFleet`` whose
+    clouds start as the given states replicated.  ``llFilter`` is two launches: ``init_from`` at each slice's smallest time, then
+    ``ll_filter_more``."""
+
+    def __init__(self, mods: Sequence[Model], resample, initStates, n_particles: int, seed: int = 20260101, device: int = 0):
+        super().__init__(mods, resample, n_particles, seed, device)
+        self.initStates = [np.asarray(s, dtype=np.float64).reshape(1, -1) for s in initStates]
+        if len(self.initStates) != self.S:
+            self.close()
+            raise ValueError("one initial state per series")
+
+    def initialiseState(self, t0s) -> List[FleetState]:
+        return self.initialiseStateFrom(t0s, self.initStates)
+
+    def llFilter(self, datas: Sequence[Sequence[TimedObservation]]) -> np.ndarray:
+        if any(len(d) == 0 for d in datas):
+            raise ValueError("a series has no records (the reference's minBy throws on an empty Vector)")
+        self.initialiseState([min(o.t for o in d) for d in datas])
+        return self.llFilterMore(datas)
 
 
 class FilterLgcpFleet(FilterFleet):

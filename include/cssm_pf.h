@@ -837,8 +837,8 @@ int cssm_model_structure(const cssm_model_desc* desc, uint32_t* words_out, int32
  * Served: every observation model, every transition and composition, d = 1 .. CSSM_MAX_DIM, systematic resampling,
  * 1 <= N <= CSSM_FLEET_MAX_N.  The LGCP observation model (sub-stepped events, FilterLgcp) is asked for by name, as the reference asks
  * for FilterLgcp by name: cssm_fleet_create_lgcp makes the fleet, cssm_fleet_create keeps refusing an LGCP descriptor.  An LGCP fleet
- * serves _destroy, _num_series, _num_particles, _set_params, _reseed, _set_option, _init, _step, _ll_filter, _filter, _summary,
- * _get_particles, _get_ancestors, _observation_index and _last_ms; every other call on it is CSSM_EINVAL_ARG before anything runs.
+ * serves _destroy, _num_series, _num_particles, _set_params, _reseed, _set_option, _init, _init_from, _step, _ll_filter, _ll_filter_more, _filter,
+ * _summary, _get_particles, _get_ancestors, _observation_index and _last_ms; every other call on it is CSSM_EINVAL_ARG before anything runs.
  * Everything else is refused at cssm_fleet_create / _set_params / _set_option with CSSM_EINVAL_ARG /
  * CSSM_EINVAL_DESC and a message naming the reason and the entry points that do serve it (cssm_pf_*, cssm_pfb_*); a fleet call
  * never degenerates into S single-handle runs.  Thread-affinity and device rules as for every entry point: each call selects the
@@ -860,7 +860,7 @@ int cssm_fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint32_
  * before it (dt == 0) takes no sub-step, weighs gamma - gamma and keeps the state; the sub-step clock, and f at the sub-step times of a
  * seasonal leaf, are the handle's.  Per-series statuses are the plain fleet's (CSSM_ENONFINITE ends one series, an empty series is
  * CSSM_EINVAL_ARG, CSSM_ESTATE without a cloud).  Not served, CSSM_EINVAL_ARG with a message that says "LGCP fleet" and names what
- * serves the request: _filter_intervals, _step_intervals, _filter_forecasts, _step_forecast, _forecast, _forecast_posterior, _interpolate,
+ * serves the request: _filter_intervals, _filter_intervals_more, _step_intervals, _filter_forecasts, _step_forecast, _forecast, _forecast_posterior, _interpolate,
  * _window, _step_interpolate, _simulate, _pmmh_run.  Intervals of a stream: cssm_fleet_summary after a step. */
 int cssm_fleet_create_lgcp(const cssm_model_desc* desc, uint64_t n_particles, uint32_t n_series, int device, cssm_fleet** out);
 void cssm_fleet_destroy(cssm_fleet* f);
@@ -955,6 +955,54 @@ int cssm_fleet_pmmh_last_split(cssm_fleet* f, double* ms6);
 int cssm_fleet_init(cssm_fleet* f, const double* t0);
 int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const double* y, const uint8_t* has_obs,
                     double* ll_out, int32_t* ess_out, int* rc_out);
+
+/* FilterInit(mod, resample, initState).initialiseState (model/ParticleFilter.scala:252-271) of the series with active[k] != 0 (active NULL =
+ * every series), and its posterior form: the clouds come from the caller.  Series k owns the rows moff[k] .. moff[k+1]-1 of x, d doubles
+ * each in flatten order, M_k of them (moff[0] = 0, non-decreasing, S + 1 entries, as in cssm_fleet_forecast_posterior).
+ *   M_k = 1: the row replicated N times -- for every call that follows the series has the bits of cssm_pf_init_from(t0[k], row) on a handle
+ *     of its own under the same key and parameters.
+ *   M_k > 1: particle i starts at row pick_i of the series' rows; pick_i = pick[k * N + i] when pick ([S][N], optional) is given, otherwise
+ *     cssm_posterior_pick(keys[k], i, M_k) (include/cssm_obs_draws.h) -- the selection cssm_fleet_forecast_posterior makes under the same
+ *     keys, so a filter started this way stands on the cloud that forecast stands on.  With neither pick nor keys the series is refused.
+ *   pick_out (optional, [S][N]) receives the picks; the rows of series that are inactive or refused read 0.
+ * A served series is left with identity ancestors, ll = 0, ess = N, clock t0[k], observation index 0, its window restarted (a call that
+ * writes a series' cloud: cssm_fleet_step_interpolate, Continuity) and, in an LGCP fleet, no predicted level -- what cssm_fleet_init leaves,
+ * but for the cloud.  LGCP fleets are served.  Inactive series are untouched: cloud, clock, window, rc_out[k] = CSSM_OK; their t0, rows and
+ * picks are not read -- unlike cssm_fleet_init the call can restart some sensors while the others keep streaming.
+ * rc_out[S] = the series' OWN status: CSSM_EINVAL_ARG, the series left exactly as it was and cssm_last_error naming the first such series,
+ * for M_k = 0 on an active series, a non-finite t0[k] or row entry, a pick >= M_k, the missing keys above.  Null t0 / moff / x / rc_out,
+ * moff[0] != 0 and a null fleet are refused with CSSM_EINVAL_ARG before the fleet is looked at; a decreasing moff (S is the fleet's) before
+ * anything of the fleet is changed.  ONE launch without records, as cssm_fleet_init's; the device time is cssm_fleet_last_ms()[0]. */
+int cssm_fleet_init_from(cssm_fleet* f, const uint8_t* active, const double* t0, const uint64_t* moff, const double* x,
+                         const uint32_t* pick, const uint64_t* keys, uint32_t* pick_out, int* rc_out);
+
+/* cssm_pf_ll_filter_more for every series: T_k MORE records of the filters that are already running, in ONE launch -- what a loop of T
+ * cssm_fleet_step calls does with a launch and a host round trip per record.  off / t / y / has_obs / ll_t / ess_t are laid out as in
+ * cssm_fleet_ll_filter.  No cloud is drawn; the first increment of a series is taken from its clock, and record s of the call is
+ * observation (cssm_fleet_observation_index(f, k) + s) of the series -- the Philox counter word and the key of its resampling uniform, as
+ * cssm_fleet_step packs its one record: cssm_fleet_ll_filter(t[0..a)) followed by cssm_fleet_ll_filter_more(t[a..T)) leaves the bits of
+ * cssm_fleet_ll_filter(t[0..T)), and so does the loop of cssm_fleet_step.  ll_out[k] is the log-likelihood accumulated since the series
+ * was initialised.  rc_out[S] = the series' OWN status: a series without records is untouched (CSSM_OK, ll_out[k] not written -- the
+ * inactive series of cssm_fleet_step); one with records but no cloud gets CSSM_ESTATE and is untouched (its ll_t / ess_t read NaN / -1);
+ * CSSM_ENONFINITE at record s as in cssm_fleet_ll_filter (later records skipped, NaN / -1, ll_out[k] NaN, the cloud undefined until the
+ * series is initialised again, no other series notices).  A series the call advances restarts its window.  The call returns CSSM_ESTATE
+ * when no series of the fleet has a cloud.  LGCP fleets are served (y / has_obs may be NULL there).  Null off / ll_out / rc_out / data,
+ * off[0] != 0 and a null fleet are refused with CSSM_EINVAL_ARG before the fleet is looked at; a decreasing off as by
+ * cssm_fleet_ll_filter.  The device time is cssm_fleet_last_ms()[0]. */
+int cssm_fleet_ll_filter_more(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                              double* ll_out, double* ll_t, int32_t* ess_t, int* rc_out);
+
+/* cssm_fleet_ll_filter_more -- the same arguments, bits and statuses -- and cssm_fleet_summary of the cloud after every record, from the
+ * same launch.  There is no row for an initial cloud, since none is drawn: series k owns rows off[k] .. off[k+1]-1, laid out like t, preset
+ * to NaN; state_mean / state_lower / state_upper: [off[S]][d]; eta_of_mean / eta_lower / eta_upper: [off[S]]; any of the six may be NULL.
+ * Order statistics, ranks, clamping, means and eta_of_mean are those of cssm_fleet_filter_intervals.  A series that fails at record s keeps
+ * the rows of the records before it; one without a cloud reads NaN.  An LGCP fleet is refused as by cssm_fleet_filter_intervals; null
+ * off / ll_out / rc_out / t / y, off[0] != 0, an interval outside (0, 1] and a null fleet are refused with CSSM_EINVAL_ARG before the fleet
+ * is looked at. */
+int cssm_fleet_filter_intervals_more(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                                     double interval, double* ll_out, double* ll_t, int32_t* ess_t,
+                                     double* state_mean, double* state_lower, double* state_upper,
+                                     double* eta_of_mean, double* eta_lower, double* eta_upper, int* rc_out);
 
 /* The streaming shape of cssm_fleet_filter_intervals (filterStream, then getIntervals of every state; one observation per sensor per
  * call): cssm_fleet_step -- the same arguments, bits and statuses -- and cssm_fleet_summary of every cloud the call moved, from the same
@@ -1155,8 +1203,8 @@ int cssm_fleet_interpolate_last_ms(cssm_fleet* f, double* ms2);
  *   For a series that is inactive, has no cloud (CSSM_ESTATE) or fails (CSSM_ENONFINITE) no entry is written, as for ll / ess; a failed
  *   series loses its window.
  *   Continuity: a series' window is continuous only across consecutive cssm_fleet_step_interpolate calls that stepped it.  Every other
- *   call that writes its cloud, key or parameters (cssm_fleet_init, _step, _step_intervals, _step_forecast, _ll_filter, _filter,
- *   _filter_intervals, _filter_forecasts, _pmmh_run, _reseed, _set_params) sets its depth to 0, and the next cssm_fleet_step_interpolate
+ *   call that writes its cloud, key or parameters (cssm_fleet_init, _init_from, _step, _step_intervals, _step_forecast, _ll_filter, _ll_filter_more, _filter,
+ *   _filter_intervals, _filter_intervals_more, _filter_forecasts, _pmmh_run, _reseed, _set_params) sets its depth to 0, and the next cssm_fleet_step_interpolate
  *   first records the cloud the series holds then (what cssm_fleet_get_particles returns, identity ancestors) as the base slice at the
  *   series' clock: the rows never reach behind it, and from it on they are the prefix interpolation's.  Calls that only read
  *   (cssm_fleet_summary, the forecasts, cssm_fleet_interpolate, cssm_fleet_get_*) leave the windows alone, and cssm_fleet_interpolate
