@@ -30,6 +30,7 @@ MAX_DIM = 16
 MAX_LEAVES = 16
 FLEET_MAX_N = 4096   # CSSM_FLEET_MAX_N
 CSSM_OPT_INTERP_CAP = 13
+CSSM_OPT_SMOOTH_STAGING = 14   # cssm_fleet_smooth: 0 = the gathered cloud in LDS where it fits, 1 = never (through L2)
 CSSM_INTERP_REFERENCE_PAIRING = 1
 CSSM_FLEET_NO_ROWS = 0xFFFFFFFF
 CSSM_OPT_FORECAST_CAP = 11
@@ -215,6 +216,9 @@ SYMBOLS = [
     ("cssm_fleet_simulate_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_interpolate", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("cssm_fleet_interpolate_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_fleet_smooth", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_uint32, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p,
+                                    C.POINTER(C.c_int)]),
+    ("cssm_fleet_smooth_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_window", C.c_int, [_h, C.c_uint32]),
     ("cssm_fleet_window_depth", C.c_uint32, [_h, C.c_uint32]),
     ("cssm_fleet_step_interpolate", C.c_int, [_h, _u8p, _dp, _dp, _u8p, _u32p, C.c_uint32, C.c_double, _dp, _i32p, _u32p, _dp, _dp, _dp, _dp, _dp, _dp,

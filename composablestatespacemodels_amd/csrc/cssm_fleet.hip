@@ -27,6 +27,7 @@
 #include "cssm_fleet.hip.h"
 #include "cssm_fleet_forecast.hip.h"
 #include "cssm_fleet_interp.hip.h"
+#include "cssm_fleet_smooth.hip.h"
 #include "cssm_simulate.hip.h"
 #include "cssm_simulate_plan.h"
 
@@ -113,6 +114,11 @@ struct cssm_fleet {
   hipEvent_t ev_ip[3] = {nullptr, nullptr, nullptr};   // before the forward launch | between the two | behind the lineage launch
   double ms_ip[2] = {-1.0, -1.0};                      // ... of the last interpolation, summed over its chunks
   bool ip_ran = false;
+  FleetBuf d_bs_traj;                   // cssm_fleet_smooth: the trajectories of one chunk ([slices of the chunk][n_traj] uint32)
+  hipEvent_t ev_bs = nullptr;           // ... behind its summary launch (ev_ip mark the forward launch and the backward simulation)
+  double ms_bs[3] = {-1.0, -1.0, -1.0}; // ... forward, backward, summary of the last call, summed over its chunks
+  bool bs_ran = false;
+  int bs_staging = 0;                   // CSSM_OPT_SMOOTH_STAGING: 0 = the gathered means in LDS where they fit, 1 = never (through L2)
   // the window of cssm_fleet_step_interpolate: per series a ring of win_slices slots, each a cloud and the ancestors that resampled it
   // ([S][slices][d][n] doubles, then [S][slices][n] uint32).  Per series on the host: whether the window is continuous (the cloud the
   // fleet holds is the one its newest slot holds), the newest slot, the records remembered behind the base slice; per slot F at its time
@@ -273,6 +279,7 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   if (f->stream) (void)hipStreamSynchronize(f->stream);
   for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : f->ev_ip) if (e) (void)hipEventDestroy(e);
+  if (f->ev_bs) (void)hipEventDestroy(f->ev_bs);
   for (hipEvent_t e : f->ev_win) if (e) (void)hipEventDestroy(e);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;   // (every FleetBuf frees itself)
@@ -311,6 +318,7 @@ static int fleet_create(const cssm_model_desc* desc, uint64_t n_particles, uint3
   if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) return bail(CSSM_EHIP, "hipStreamCreate");
   for (hipEvent_t& e : f->ev) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   for (hipEvent_t& e : f->ev_ip) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
+  if (hipEventCreate(&f->ev_bs) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   for (hipEvent_t& e : f->ev_win) if (hipEventCreate(&e) != hipSuccess) return bail(CSSM_EHIP, "hipEventCreate");
   const size_t rows = (size_t)S * 2u * f->d * n;
   if (!f->state.reserve(rows * 8, false) || !f->anc.reserve((size_t)S * n * 4, false) || !f->ser.reserve((size_t)S * sizeof(FleetSeries), false) ||
@@ -345,6 +353,11 @@ extern "C" int cssm_fleet_set_option(cssm_fleet* f, int option, int value) {
   if (option == CSSM_OPT_INTERP_CAP) {   // KiB of lineage history one chunk of series holds on the device; 0 = 1 GiB
     if (value < 0) return fail(CSSM_EINVAL_ARG, "CSSM_OPT_INTERP_CAP must not be negative (got %d)", value);
     f->ip_hist_max = value ? (size_t)value << 10 : (size_t)1 << 30;
+    return CSSM_OK;
+  }
+  if (option == CSSM_OPT_SMOOTH_STAGING) {   // cssm_fleet_smooth's backward simulation: where the gathered cloud of a time index is read from
+    if (value < 0 || value > 1) return fail(CSSM_EINVAL_ARG, "CSSM_OPT_SMOOTH_STAGING is 0 (LDS where it fits) or 1 (never: through L2), not %d", value);
+    f->bs_staging = value;
     return CSSM_OK;
   }
   if (option == CSSM_OPT_FLEET_SELECT) {
@@ -1808,19 +1821,62 @@ static FleetIpStage fleet_ip_stage(const cssm_fleet* f, const uint64_t* off, uin
 // index (k_fleet_lineage, cssm_fleet_interp.hip).  The fleet lends its device, stream, contract table, N, structure, parameters and
 // keys; nothing it keeps per series changes.  Chunks: as many series as fit ip_hist_max bytes of history, one at least -- never a
 // part of a series.  Per chunk one upload (offsets, records, the f coefficients of every output row), the two launches, one read-back.
-extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval,
-                                      int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
-                                      double* eta_lower, double* eta_upper, int* rc_out) {
-  FLEET_LGCP_REFUSE(f, "cssm_fleet_interpolate", FLEET_LGCP_SERVED);
+// What cssm_fleet_interpolate and cssm_fleet_smooth refuse alike before the fleet is looked at, in that order
+static int fleet_ip_check(const uint64_t* off, const double* t, const double* y, const double* ll_out, const int* rc_out, double interval) {
   if (!off) return fail(CSSM_EINVAL_ARG, "off is null");
   if (!ll_out || !rc_out) return fail(CSSM_EINVAL_ARG, "ll_out / rc_out is null");
   if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
   if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
   if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  return CSSM_OK;
+}
+
+// n_traj == 0: the interpolation (forward pass, k_fleet_lineage).  n_traj >= 1: cssm_fleet_smooth -- the same chunks, staging and forward
+// pass, then k_fleet_backsim and k_fleet_smooth_rows over n_traj trajectories (cssm_fleet_smooth.hip); traj_out may be null.
+static int fleet_ip_run(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval, bool pairing,
+                        uint32_t n_traj, double* ll_out, const FleetIvOut& o, uint32_t* traj_out, int* rc_out);
+
+extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval,
+                                      int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
+                                      double* eta_lower, double* eta_upper, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_interpolate", FLEET_LGCP_SERVED);
+  if (const int rc = fleet_ip_check(off, t, y, ll_out, rc_out, interval)) return rc;
   if (flags & ~CSSM_INTERP_REFERENCE_PAIRING) return fail(CSSM_EINVAL_ARG, "unknown flag bits 0x%x (CSSM_INTERP_REFERENCE_PAIRING is the only flag)",
                                                           (unsigned)(flags & ~CSSM_INTERP_REFERENCE_PAIRING));
   if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  return fleet_ip_run(f, off, t, y, has_obs, interval, (flags & CSSM_INTERP_REFERENCE_PAIRING) != 0, 0u, ll_out, o, nullptr, rc_out);
+}
+
+// EXTENSION (the reference has no smoother beyond FilterInterpolate): forward filtering, backward simulation of every series --
+// cssm_fleet_interpolate's forward pass, then n_traj trajectories drawn backwards through the kept clouds under the contract's backward
+// kernel (include/cssm_numerics.h, "backward simulation") and summarised per time index.
+extern "C" int cssm_fleet_smooth(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, uint32_t n_traj,
+                                 double interval, int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper,
+                                 double* eta_of_mean, double* eta_lower, double* eta_upper, uint32_t* traj_out, int* rc_out) {
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_smooth", FLEET_LGCP_SERVED " (the transition over an event is a chain of sub-steps, not one Gaussian)");
+  if (const int rc = fleet_ip_check(off, t, y, ll_out, rc_out, interval)) return rc;
+  if (flags & CSSM_INTERP_REFERENCE_PAIRING)
+    return fail(CSSM_EINVAL_ARG, "cssm_fleet_smooth: CSSM_INTERP_REFERENCE_PAIRING is not offered (row s is time index s; cssm_fleet_interpolate pairs)");
+  if (flags) return fail(CSSM_EINVAL_ARG, "cssm_fleet_smooth: unknown flag bits 0x%x (flags must be 0)", (unsigned)flags);
+  if (n_traj == 0u || n_traj > CSSM_FLEET_MAX_N)
+    return fail(CSSM_EINVAL_ARG, "cssm_fleet_smooth: n_traj must be in [1, CSSM_FLEET_MAX_N = %u] (got %u)", (unsigned)CSSM_FLEET_MAX_N, n_traj);
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
+  return fleet_ip_run(f, off, t, y, has_obs, interval, false, n_traj, ll_out, o, traj_out, rc_out);
+}
+
+extern "C" int cssm_fleet_smooth_last_ms(cssm_fleet* f, double* ms3) {
+  if (!f || !ms3) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (!f->bs_ran) return fail(CSSM_ESTATE, "no smoothing has run on this fleet (cssm_fleet_smooth first)");
+  ms3[0] = f->ms_bs[0]; ms3[1] = f->ms_bs[1]; ms3[2] = f->ms_bs[2];
+  return CSSM_OK;
+}
+
+static int fleet_ip_run(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs, double interval, bool pairing,
+                        uint32_t n_traj, double* ll_out, const FleetIvOut& o, uint32_t* traj_out, int* rc_out) {
   const uint32_t S = f->S, n = f->n;
+  const bool smooth = n_traj != 0u;
   const int d = f->d, rows = d + 1;
   int rc = CSSM_OK;
   for (uint32_t k = 0; k < S; ++k) {
@@ -1833,7 +1889,7 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
   // chunks of series [cut[c], cut[c + 1]) whose history fits the cap; the buffers of the largest one
   const size_t RB = CSSM_FLEET_REC_BYTES(d), slice = (size_t)n * (8u * (size_t)d + 4u);
   std::vector<uint32_t> cut(1, 0u);
-  size_t held = 0, need = 0, need_hist = 0;
+  size_t held = 0, need = 0, need_hist = 0, need_traj = 0;
   uint32_t widest = 0;
   for (uint32_t k = 0; k < S; ++k) {
     const size_t b = ((size_t)(off[k + 1] - off[k]) + 1u) * slice;
@@ -1842,7 +1898,11 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
     if (held > need_hist) { need_hist = held; widest = cut.back(); }
   }
   cut.push_back(S);
-  for (size_t c = 0; c + 1 < cut.size(); ++c) need = std::max(need, fleet_ip_stage(f, off, cut[c], cut[c + 1]).bytes);
+  for (size_t c = 0; c + 1 < cut.size(); ++c) {
+    need = std::max(need, fleet_ip_stage(f, off, cut[c], cut[c + 1]).bytes);
+    need_traj = std::max(need_traj, ((size_t)(off[cut[c + 1]] - off[cut[c]]) + (cut[c + 1] - cut[c])) * (size_t)n_traj * 4u);
+  }
+  if (smooth && !f->d_bs_traj.reserve(need_traj, true)) return fail(CSSM_ENOMEM, "fleet smoothing: %zu bytes of trajectories", need_traj);
   if (!f->h_ip.reserve(need, true)) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of pinned staging", need);
   if (!f->d_ip.reserve(need, true)) return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of records and results", need);
   if (!f->d_ip_hist.reserve(need_hist, false)) {
@@ -1850,10 +1910,8 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
       return fail(CSSM_ENOMEM, "fleet interpolation: series %u alone needs %zu bytes of lineage history ((T + 1) N (8 d + 4))", widest, need_hist);
     return fail(CSSM_ENOMEM, "fleet interpolation: %zu bytes of lineage history (CSSM_OPT_INTERP_CAP lowers it)", need_hist);
   }
-  const FleetRanks r = fleet_ranks(n, interval);
-  const bool pairing = (flags & CSSM_INTERP_REFERENCE_PAIRING) != 0;
-  const FleetIvOut o{state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper};
-  double ms[2] = {0.0, 0.0};
+  const FleetRanks r = fleet_ranks(smooth ? n_traj : n, interval);   // the ranks of as many values as a row summarises
+  double ms[3] = {0.0, 0.0, 0.0};
   for (size_t c = 0; c + 1 < cut.size(); ++c) {
     const uint32_t k0 = cut[c], k1 = cut[c + 1], Sc = k1 - k0;
     const size_t R0 = (size_t)off[k0], Rc = (size_t)off[k1] - R0, Qc = Rc + Sc;
@@ -1896,24 +1954,61 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
       rc = fleet_series_launch(d, l);
       if (rc) return rc;
       HIP_TRY(hipEventRecord(f->ev_ip[1], f->stream));
-      FleetLinLaunch q;
-      q.args.n = n; q.args.np2 = r.np2; q.args.pairing = pairing ? 1u : 0u;
-      q.args.hist = l.args.hist; q.args.hanc = l.args.hanc;
-      q.args.off = l.args.off; q.args.ser = l.args.hser; q.args.recs = l.args.recs;
-      q.args.fco = f->d_ip.at<const double>(st.fco);
-      q.args.out = f->d_ip.at<double>(st.out);
-      q.args.mk = f->base.mk;
-      q.args.lo_state = r.rk.lo_state; q.args.hi_state = r.rk.hi_state;
-      q.args.lo_eta = r.rk.lo_eta; q.args.hi_eta = r.rk.hi_eta;
-      q.d = d; q.n_series = Sc; q.stream = f->stream;
-      const int hrc = cssm_fleet_lineage_launch(q);
-      if (hrc) return fail(CSSM_EHIP, "k_fleet_lineage: %s", hipGetErrorString((hipError_t)hrc));
-      HIP_TRY(hipEventRecord(f->ev_ip[2], f->stream));
-      HIP_TRY(hipMemcpyAsync(f->h_ip.at<unsigned char>(st.ser), f->d_ip.at<unsigned char>(st.ser), st.bytes - st.ser, hipMemcpyDeviceToHost, f->stream));
-      HIP_TRY(hipStreamSynchronize(f->stream));
-      float m0 = 0.f, m1 = 0.f;
-      if (hipEventElapsedTime(&m0, f->ev_ip[0], f->ev_ip[1]) == hipSuccess && hipEventElapsedTime(&m1, f->ev_ip[1], f->ev_ip[2]) == hipSuccess) {
-        ms[0] += (double)m0; ms[1] += (double)m1;
+      if (smooth) {
+        FleetBackLaunch bl;
+        bl.args.n = n; bl.args.n_traj = n_traj;
+        bl.args.hist = l.args.hist; bl.args.hanc = l.args.hanc;
+        bl.args.off = l.args.off; bl.args.ser = l.args.hser; bl.args.recs = l.args.recs;
+        bl.args.par = l.args.par; bl.args.k0 = k0;
+        bl.args.traj = f->d_bs_traj.at<uint32_t>();
+        bl.args.mk = f->base.mk;
+        bl.d = d; bl.n_series = Sc; bl.stream = f->stream;
+        bl.stage = f->bs_staging == 0 && (size_t)d * n * 8u <= CSSM_BACKSIM_STAGE_MAX;
+        int hrc = cssm_fleet_backsim_launch(bl);
+        if (hrc) return fail(CSSM_EHIP, "k_fleet_backsim: %s", hipGetErrorString((hipError_t)hrc));
+        HIP_TRY(hipEventRecord(f->ev_ip[2], f->stream));
+        FleetSmRowLaunch q;
+        q.args.n = n; q.args.n_traj = n_traj; q.args.np2 = r.np2;
+        q.args.hist = l.args.hist; q.args.traj = bl.args.traj;
+        q.args.off = l.args.off; q.args.ser = l.args.hser;
+        q.args.fco = f->d_ip.at<const double>(st.fco);
+        q.args.out = f->d_ip.at<double>(st.out);
+        q.args.mk = f->base.mk;
+        q.args.lo_state = r.rk.lo_state; q.args.hi_state = r.rk.hi_state;
+        q.args.lo_eta = r.rk.lo_eta; q.args.hi_eta = r.rk.hi_eta;
+        q.d = d; q.n_series = Sc; q.stream = f->stream;
+        hrc = cssm_fleet_smooth_rows_launch(q);
+        if (hrc) return fail(CSSM_EHIP, "k_fleet_smooth_rows: %s", hipGetErrorString((hipError_t)hrc));
+        HIP_TRY(hipEventRecord(f->ev_bs, f->stream));
+        HIP_TRY(hipMemcpyAsync(f->h_ip.at<unsigned char>(st.ser), f->d_ip.at<unsigned char>(st.ser), st.bytes - st.ser, hipMemcpyDeviceToHost, f->stream));
+        if (traj_out)   // the chunk's slices are the caller's rows off[k0] + k0 .. off[k1] + k1 - 1
+          HIP_TRY(hipMemcpyAsync(traj_out + (R0 + k0) * (size_t)n_traj, bl.args.traj, Qc * (size_t)n_traj * 4u, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+        if (hipEventElapsedTime(&m0, f->ev_ip[0], f->ev_ip[1]) == hipSuccess && hipEventElapsedTime(&m1, f->ev_ip[1], f->ev_ip[2]) == hipSuccess &&
+            hipEventElapsedTime(&m2, f->ev_ip[2], f->ev_bs) == hipSuccess) {
+          ms[0] += (double)m0; ms[1] += (double)m1; ms[2] += (double)m2;
+        }
+      } else {
+        FleetLinLaunch q;
+        q.args.n = n; q.args.np2 = r.np2; q.args.pairing = pairing ? 1u : 0u;
+        q.args.hist = l.args.hist; q.args.hanc = l.args.hanc;
+        q.args.off = l.args.off; q.args.ser = l.args.hser; q.args.recs = l.args.recs;
+        q.args.fco = f->d_ip.at<const double>(st.fco);
+        q.args.out = f->d_ip.at<double>(st.out);
+        q.args.mk = f->base.mk;
+        q.args.lo_state = r.rk.lo_state; q.args.hi_state = r.rk.hi_state;
+        q.args.lo_eta = r.rk.lo_eta; q.args.hi_eta = r.rk.hi_eta;
+        q.d = d; q.n_series = Sc; q.stream = f->stream;
+        const int hrc = cssm_fleet_lineage_launch(q);
+        if (hrc) return fail(CSSM_EHIP, "k_fleet_lineage: %s", hipGetErrorString((hipError_t)hrc));
+        HIP_TRY(hipEventRecord(f->ev_ip[2], f->stream));
+        HIP_TRY(hipMemcpyAsync(f->h_ip.at<unsigned char>(st.ser), f->d_ip.at<unsigned char>(st.ser), st.bytes - st.ser, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(hipStreamSynchronize(f->stream));
+        float m0 = 0.f, m1 = 0.f;
+        if (hipEventElapsedTime(&m0, f->ev_ip[0], f->ev_ip[1]) == hipSuccess && hipEventElapsedTime(&m1, f->ev_ip[1], f->ev_ip[2]) == hipSuccess) {
+          ms[0] += (double)m0; ms[1] += (double)m1;
+        }
       }
     }
     for (uint32_t kl = 0; kl < Sc; ++kl) {
@@ -1925,9 +2020,11 @@ extern "C" int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const 
       ll_out[k] = ok ? h_ser[kl].ll : cssm_nan();
       for (size_t q = 0; q <= T; ++q)
         fleet_iv_row(f, k, h_out + (lrow + q) * (size_t)rows * 3u, h_fco + (lrow + q) * (size_t)d, ok, o, grow + q);
+      if (traj_out && !ok) std::fill(traj_out + grow * (size_t)n_traj, traj_out + (grow + T + 1u) * (size_t)n_traj, 0xffffffffu);   // no trajectory
     }
   }
-  f->ms_ip[0] = ms[0]; f->ms_ip[1] = ms[1]; f->ip_ran = true;
+  if (smooth) { f->ms_bs[0] = ms[0]; f->ms_bs[1] = ms[1]; f->ms_bs[2] = ms[2]; f->bs_ran = true; }
+  else { f->ms_ip[0] = ms[0]; f->ms_ip[1] = ms[1]; f->ip_ran = true; }
   return CSSM_OK;
 }
 

@@ -20,12 +20,14 @@
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
 #include "cssm_fleet_interp.hip.h"
+#include "cssm_fleet_rows.hip.h"
 
 // Where the slices a block walks lie -- newest first -- and where each one's row goes: the whole history of a series
 // (cssm_fleet_interpolate) or the window of one (cssm_fleet_step_interpolate).  Step j of `steps`: cloud(j) / anc(j) the slice,
 // resampled(j) whether its ancestors exist (the slice was written by a weighted record), fco(j) F at its time, out(j) its [d + 1][3].
 template <int D>
 struct FleetLinHist {                                           // slices base .. base + T of hist / hanc, output row o = s or T - s
+  static constexpr bool kDirect = false;
   const FleetLinArgs& a;
   size_t base; unsigned long long r0; uint32_t T;
   __device__ __forceinline__ uint32_t slice(uint32_t j) const { return T - j; }
@@ -41,6 +43,7 @@ struct FleetLinHist {                                           // slices base .
 };
 template <int D>
 struct FleetLinWindow {                                         // request q: the slots words[j] of series k's window, output row q L + j
+  static constexpr bool kDirect = false;
   const FleetWinArgs& a;
   uint32_t k, q;
   __device__ __forceinline__ uint32_t word(uint32_t j) const { return a.words[(size_t)q * a.L + j]; }
@@ -52,69 +55,7 @@ struct FleetLinWindow {                                         // request q: th
   __device__ __forceinline__ double* out(uint32_t j) const { return a.out + ((size_t)q * a.L + j) * (D + 1) * 3u; }
 };
 
-// The lineages that survive to the newest slice, summarised slice by slice going back: b = the identity; per slice b = anc[b] where the
-// slice resampled, then row `row` of the slice's cloud through b -- keys, bitonic sort over np2, the mean (slots tid + 256 q per
-// thread, the xor-shuffle tree, the wave partials added in wave order).
-template <int D, class Src>
-__device__ __forceinline__ void fleet_lineage_body(const Src& src_of, uint32_t steps, uint32_t n, uint32_t np2, uint32_t row, const ModelK& mk,
-                                                   uint32_t lo_state, uint32_t hi_state, uint32_t lo_eta, uint32_t hi_eta,
-                                                   unsigned long long* s_keys, uint32_t* s_b, double* s_p) {
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t i = tid; i < n; i += CSSM_BLOCK) s_b[i] = i;
-  for (uint32_t st = 0; st < steps; ++st) {                     // bounded by the series' length / the window's
-    __syncthreads();                                            // the row sorted last is read; s_p is free
-    const bool resampled = src_of.resampled(st);
-    const uint32_t* ga = src_of.anc(st);
-    const double* src = src_of.cloud(st);
-    const double* fco = src_of.fco(st);
-    double acc = 0.0;
-    for (uint32_t i = tid; i < np2; i += CSSM_BLOCK) {
-      unsigned long long key = ~0ull;
-      if (i < n) {
-        uint32_t j = s_b[i];
-        if (resampled) { j = ga[j]; s_b[i] = j; }
-        double v;
-        if (row < (uint32_t)D) {
-          v = src[(size_t)row * n + j];
-        } else {
-          double x[D];
-#pragma unroll
-          for (int q = 0; q < D; ++q) x[q] = src[(size_t)q * n + j];
-          v = link_of(mk.obs_kind, gamma_coef<D>(mk, fco, x));
-        }
-        acc += v;
-        key = cssm_order_key(v);
-      }
-      s_keys[i] = key;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((tid & 63u) == 0u) s_p[tid >> 6] = acc;
-    for (uint32_t k2 = 2u; k2 <= np2; k2 <<= 1) {
-      for (uint32_t j = k2 >> 1; j > 0u; j >>= 1) {
-        __syncthreads();
-        for (uint32_t i = tid; i < np2; i += CSSM_BLOCK) {
-          const uint32_t p = i ^ j;
-          if (p > i) {
-            const unsigned long long x = s_keys[i], y = s_keys[p];
-            const bool up = (i & k2) == 0u;
-            if ((x > y) == up) { s_keys[i] = y; s_keys[p] = x; }
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double sum = 0.0;
-      for (int w = 0; w < CSSM_BLOCK / 64; ++w) sum += s_p[w];
-      double* out = src_of.out(st) + (size_t)row * 3u;
-      out[0] = sum / (double)n;
-      out[1] = cssm_order_unkey(s_keys[row < (uint32_t)D ? lo_state : lo_eta]);
-      out[2] = cssm_order_unkey(s_keys[row < (uint32_t)D ? hi_state : hi_eta]);
-    }
-  }
-}
-
+// (the walk itself -- fleet_lineage_body -- is cssm_fleet_rows.hip.h: the backward-simulation summaries of cssm_fleet_smooth.hip share it)
 template <int D>
 __global__ __launch_bounds__(CSSM_BLOCK) void k_fleet_lineage(const FleetLinArgs a) {
   extern __shared__ unsigned long long s_keys[];

@@ -677,6 +677,36 @@ class NativePfFleet:
         """Device time (HIP events) of the last interpolation's forward launch and lineage launch, ms, summed over its chunks."""
         return self._ms(self.lib.cssm_fleet_interpolate_last_ms, 2)
 
+    def smooth(self, datas, n_traj: Optional[int] = None, interval: float = 0.975, want_trajectories: bool = False):
+        """cssm_fleet_smooth (an EXTENSION: the reference has no smoother beyond ``FilterInterpolate``): forward filtering, backward
+        simulation of every series -- ``interpolate``'s forward pass, then ``n_traj`` trajectories (None: N) drawn backwards through the
+        kept clouds and summarised per time index.  Returns what ``interpolate`` returns, ``(ll[S], per-series list of (mean[T_k + 1, d],
+        lower, upper, eta_of_mean[T_k + 1], eta_lower, eta_upper), rc[S])``, and with ``want_trajectories`` a fourth entry: per series
+        the uint32 array ``[T_k + 1, n_traj]`` of the particle of each kept cloud every trajectory passes through (0xffffffff throughout
+        a series whose rc is not 0).  The fleet's clouds and clocks are not touched."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        return self.smooth_packed(*self.pack(datas, allow_empty=True), n_traj=n_traj, interval=interval, want_trajectories=want_trajectories)
+
+    def smooth_packed(self, off, t, y, has, n_traj: Optional[int] = None, interval: float = 0.975, want_trajectories: bool = False):
+        """``smooth`` on arrays ``pack`` made (a caller that smooths the same fleet repeatedly packs once)."""
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        M = self.n if n_traj is None else int(n_traj)
+        if not 1 <= M <= _abi.FLEET_MAX_N:
+            raise ValueError(f"n_traj must be in [1, {_abi.FLEET_MAX_N}], not {M}")
+        ll, rc = np.zeros(self.S), np.zeros(self.S, dtype=np.int32)
+        rows = _interval_arrays((R + self.S,), self.d)
+        traj = np.zeros((R + self.S, M), dtype=np.uint32) if want_trajectories else None
+        _abi.check(self.lib.cssm_fleet_smooth(self._h, _p(off), _p(t), _p(y), _p(has), M, float(interval), 0, _p(ll), *map(_p, rows), _p(traj),
+                                              _p(rc)))
+        out = (ll, self.interpolate_rows(off, rows), rc)
+        return out + (self._split(off, traj, 1),) if want_trajectories else out
+
+    def smooth_last_ms(self) -> Tuple[float, float, float]:
+        """Device time (HIP events) of the last ``smooth``'s forward launch, backward simulation and row summaries, ms, summed over its
+        chunks."""
+        return self._ms(self.lib.cssm_fleet_smooth_last_ms, 3)
+
     def pmmh_last_split(self):
         """cssm_fleet_pmmh_last_split: milliseconds of the last ``cssm_fleet_pmmh_run`` on this fleet, summed over its iterations --
         (propose + set_params + reseed, record building, upload, kernel, decide) and the iterations counted."""
@@ -1611,6 +1641,20 @@ class FilterFleet:
 
     def interpolate_last_ms(self) -> Tuple[float, float]:
         return self._fleet.interpolate_last_ms()
+
+    def smooth(self, datas: Sequence[Sequence[TimedObservation]], n_traj: Optional[int] = None,
+               interval: float = 0.975) -> List[Tuple[float, List[PfOut]]]:
+        """An EXTENSION (the reference has no smoother beyond ``FilterInterpolate``): what ``interpolate`` returns, per series ``(ll,
+        [PfOut])`` of length T_k + 1, but every time index summarised over ``n_traj`` backward-simulated trajectories (None: as many as
+        particles) instead of the lineages that survive to the end of the series -- the early rows of a long series keep a
+        distribution.  One device call (three launches); the fleet's current states stay valid."""
+        split = [split_data(d) for d in datas]
+        ll, rows, rc = self._fleet.smooth(split, n_traj, float(interval))
+        self._raise_series(rc, empty_ok=True)
+        return [(float(ll[k]), _interpolate_outs(datas[k], split[k][0], rows[k])) for k in range(self.S)]
+
+    def smooth_last_ms(self) -> Tuple[float, float, float]:
+        return self._fleet.smooth_last_ms()
 
     def forecast(self, times, interval: float = 0.975, seed: Optional[int] = None) -> List[List[ForecastOut]]:
         """``ParticleFilter.forecast`` of every series from its current state, all of them in one device call: ``times[k]`` = series k's

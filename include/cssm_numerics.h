@@ -198,6 +198,7 @@ CSSM_HD cssm_u32x4 cssm_philox4x32(cssm_u32x4 c, uint32_t k0, uint32_t k1) { CSS
 #define CSSM_STREAM_STRAT 5u  /* the N uniforms of stratified resampling (Resampling.scala:83), counter id = slot */
 #define CSSM_STREAM_MULTI 6u  /* the N uniforms of multinomial resampling (Resampling.scala:93), counter id = slot */
 #define CSSM_STREAM_KEY 7u    /* key derivation: the Philox key of filter run number `run` under user seed `seed` (cssm_derive_key) */
+/* (8 .. 10: include/cssm_obs_draws.h; 11: CSSM_STREAM_BACK, "backward simulation" below) */
 
 /*
  * Counter layout: word0/1 = stream id, word2 = step (observation index, 0-based; 0 for init),
@@ -1186,6 +1187,57 @@ CSSM_HD double cssm_ref_choose(double c, double max) {
   const double gap = c - max;
   const int ok = (gap >= -CSSM_REF_BELOW) && (gap <= CSSM_REF_ABOVE);       /* false for NaN */
   return ok ? c : max;
+}
+
+/* ------------------------------------------------------------------ backward simulation (EXTENSION) */
+
+/*
+ * EXTENSION (not a restatement of running reference code: the reference has no smoother beyond FilterInterpolate).  Forward
+ * filtering, backward simulation (Godsill, Doucet and West 2004) on the history a fleet's interpolation keeps: cssm_fleet_smooth.
+ *
+ * Notation.  A series has records 0 .. T-1.  Slice X_0 is the initial cloud, slice X_{s+1} the cloud record s proposed; A_s are the
+ * ancestors that resampled X_s (the identity for s = 0 and behind an unweighted record); the equally weighted filtering cloud at
+ * index s is x_s[i] = X_s[A_s[i]], i < N.
+ *
+ * Trajectory m of M starts at index T in slot i_T = cssm_back_start(m, N, M), its particle is j_T = A_T[i_T].  Going back, for
+ * s = T-1 .. 0 with record s's coefficients p0..p3 and dt and the component kinds (CSSM_SDE_* of cssm_pf.h):
+ *
+ *   mean_c(x) = cssm_back_mean(kind_c, p0, p1, dt, x)       transition_step's statement with the noise removed
+ *   sd_c      = cssm_back_sd(kind_c, p2, p3)
+ *   if any sd_c is not > 0 (dt = 0, a zero diffusion, NaN):   i_s = j_{s+1}        (genealogical: the slot that produced the particle)
+ *   else for every slot i:
+ *       e_c  = (X_{s+1}[c][j_{s+1}] - mean_c(x_s[i][c])) / sd_c
+ *       q    = sum_c e_c e_c, in component order from 0.0, plain fp64
+ *       lb_i = cssm_back_lb(q) = -0.5 q                    (-inf for a NaN q: the slot has weight 0)
+ *       level = max_i lb_i ; not > -inf (no slot has a usable density): genealogical as above
+ *       w_i  = cssm_back_weight(lb_i, level)                the filter's weight statement with that level
+ *       F_i  = cssm_fix_from_unit(w_i), S_i its exact 128-bit prefix sums in slot order, C_i = RN(RN(S_i) / RN(S_{N-1}))
+ *       u    = cssm_back_uniform(seed, m, s)
+ *       i_s  = the first i with C_i >= u                    (the multinomial resampler's search; C_{N-1} = 1 > u)
+ *   j_s = A_s[i_s].
+ *
+ * Every operation is an IEEE operation or an exact integer sum: the result does not depend on how slots are mapped to threads.
+ * C is non-decreasing in i (S is, and RN and a division by a positive constant are monotone), so "the first i with C_i >= u" may
+ * be found in any order.
+ */
+/* Tag 11 (8 .. 10 are cssm_obs_draws.h's).  tests/test_simulate_lgcp_host.py lists the plain decimal tags 0 .. 10 the two headers held when
+ * simLGCP was added; this one is written in parentheses and is pinned by tests/test_fleet_smooth_host.py instead, by name and through
+ * the Philox counter word it lands in.  The next free tag is 12. */
+#define CSSM_STREAM_BACK (11u)  /* the uniform of backward-simulation trajectory `id` at time index `step` */
+
+CSSM_HD uint32_t cssm_back_start(uint32_t m, uint32_t n, uint32_t n_traj) { return (uint32_t)(((uint64_t)m * n) / n_traj); }
+CSSM_HD double cssm_back_mean(int kind, double p0, double p1, double dt, double x) {
+  if (kind == 0) return x;                                  /* CSSM_SDE_BROWNIAN */
+  if (kind == 1) return x + p0;                             /* CSSM_SDE_GEN_BROWNIAN */
+  if (kind == 2) return p0 + (x - p0) * p1;                 /* CSSM_SDE_OU */
+  return x + (p0 + p1 * x) * dt;                            /* CSSM_SDE_EULER_AFFINE */
+}
+CSSM_HD double cssm_back_sd(int kind, double p2, double p3) { return (kind == 3) ? p2 * p3 : p3; }
+CSSM_HD double cssm_back_lb(double q) { return (q == q) ? -0.5 * q : -cssm_inf(); }
+CSSM_HD double cssm_back_weight(double lb, double level) { return cssm_exp_le0(cssm_min_c(lb - level, CSSM_REF_BELOW)); }
+CSSM_HD double cssm_back_uniform(uint64_t seed, uint32_t m, uint32_t s) {
+  const cssm_u32x4 b = cssm_philox_draw(seed, (uint64_t)m, s, CSSM_STREAM_BACK, 0);
+  return cssm_u01(b.v[0], b.v[1]);
 }
 
 #ifdef __cplusplus

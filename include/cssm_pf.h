@@ -317,6 +317,10 @@ int cssm_pf_stream_idle(cssm_pf* pf);
  * fleet in chunks of series whose lineage history ((T_k + 1) x N x (8 d + 4) bytes per series) fits in this many KiB -- one series at
  * least per chunk, never a part of one.  Results do not depend on it (tests lower it to run the chunked path on a small fleet). */
 #define CSSM_OPT_INTERP_CAP 13
+/* CSSM_OPT_SMOOTH_STAGING (fleets only, cssm_fleet_set_option; default 0): where cssm_fleet_smooth's backward simulation reads the gathered
+ * cloud of a time index from -- 0: the block's LDS where d x N x 8 bytes fit, else the slice through L2; 1: never LDS.  The results do not
+ * depend on it (tests/test_gpu_fleet_smooth.py); it exists for tests and measurements. */
+#define CSSM_OPT_SMOOTH_STAGING 14
 int cssm_pf_set_option(cssm_pf* pf, int option, int value);
 /* Counters of the run-time specialisation in this process: out4 = {kernels compiled, kernels loaded from the disk cache, launches of
  * run-time-compiled kernels, failures (each reported once on stderr)}. */
@@ -1175,6 +1179,32 @@ int cssm_fleet_interpolate(cssm_fleet* f, const uint64_t* off, const double* t, 
 /* ms2[0] = device time of the forward launch, ms2[1] = of the lineage launch of the last cssm_fleet_interpolate, each summed over its
  * chunks (HIP events on the fleet's stream).  CSSM_ESTATE before the first interpolation.  The array holds TWO doubles. */
 int cssm_fleet_interpolate_last_ms(cssm_fleet* f, double* ms2);
+/* ---- EXTENSION (not a restatement of running reference code: the reference has no smoother beyond FilterInterpolate): forward filtering,
+ * backward simulation (FFBSi; Godsill, Doucet and West 2004) of every series.  cssm_fleet_interpolate summarises time index s through the
+ * lineages that survive to the end of the series; after a few dozen weighted records they pass through a handful of ancestors, and the
+ * early rows are order statistics of one or two values.  cssm_fleet_smooth runs the same forward pass (the same history, chunks and
+ * ll_out bits) and then draws n_traj trajectories BACKWARDS through the kept clouds: from its particle at index s + 1 a trajectory picks
+ * its slot at index s among all N with probability proportional to the transition density, which is a diagonal Gaussian in closed form
+ * for every transition of the library.  The arithmetic is part of the numerics contract (include/cssm_numerics.h, "backward
+ * simulation"): IEEE operations and exact integer sums, one Philox uniform per (series key, trajectory, time index) under
+ * CSSM_STREAM_BACK; a record with dt = 0 or a zero diffusion follows the genealogy.  Three launches per chunk of series: the forward
+ * pass, k_fleet_backsim (blocks: series x groups of 64 trajectories) and the row summaries (one workgroup per (series, row)).
+ *
+ * off / t / y / has_obs, the output rows, ll_out, rc_out, the statuses, the chunks under CSSM_OPT_INTERP_CAP and what is refused before the
+ * fleet is looked at are cssm_fleet_interpolate's; the fleet is only lent, and an open window is not touched.  Row s of series k
+ * summarises the n_traj states the trajectories hold at time index s: the mean is their plain fp64 sum / n_traj, lower / upper are the
+ * order statistics at the ranks cssm_pf_summary takes for n_traj values, exact.  1 <= n_traj <= CSSM_FLEET_MAX_N (else CSSM_EINVAL_ARG);
+ * flags must be 0 -- CSSM_INTERP_REFERENCE_PAIRING is refused by name; an LGCP fleet is refused (its transition over an event is a chain
+ * of sub-steps, not one Gaussian).  traj_out (may be NULL): [off[S] + S][n_traj], entry [row][m] the particle of slice `row` (an index
+ * into the cloud that record proposed, < N) trajectory m passes through; the rows of a series whose rc_out is not 0 read 0xffffffff. */
+int cssm_fleet_smooth(cssm_fleet* f, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                      uint32_t n_traj, double interval, int flags, double* ll_out,
+                      double* state_mean, double* state_lower, double* state_upper,
+                      double* eta_of_mean, double* eta_lower, double* eta_upper,
+                      uint32_t* traj_out, int* rc_out);
+/* ms3 = device time of the forward launch, of the backward simulation and of the row summaries of the last cssm_fleet_smooth, each summed
+ * over its chunks (HIP events on the fleet's stream).  CSSM_ESTATE before the first.  The array holds THREE doubles. */
+int cssm_fleet_smooth_last_ms(cssm_fleet* f, double* ms3);
 /* ---- fixed-lag interpolation of a live fleet (FilterInterpolate as the stream it is: ParticleFilter.interpolate, model/
  * ParticleFilter.scala:281-310 -- one stepInterpolate per observation, every element carrying the paths that survive to that moment;
  * examples/Interpolate.scala: once data resumes behind a gap, the surviving lineages fill it).
