@@ -31,6 +31,8 @@ MAX_LEAVES = 16
 FLEET_MAX_N = 4096   # CSSM_FLEET_MAX_N
 CSSM_OPT_INTERP_CAP = 13
 CSSM_OPT_SMOOTH_STAGING = 14   # cssm_fleet_smooth: 0 = the gathered cloud in LDS where it fits, 1 = never (through L2)
+CSSM_OPT_SMOOTH_TILE = 15      # cssm_pf_smooth: the slots a block of the backward kernels stages (0 = SMOOTH_TILE; a multiple of 64)
+SMOOTH_TILE = 512              # CSSM_SMOOTH_TILE
 CSSM_INTERP_REFERENCE_PAIRING = 1
 CSSM_FLEET_NO_ROWS = 0xFFFFFFFF
 CSSM_OPT_FORECAST_CAP = 11
@@ -130,6 +132,8 @@ SYMBOLS = [
     ("cssm_lgcp_sim_destroy", None, [_h]),
     ("cssm_simulate_lgcp_last_ms", C.c_int, [_dp]),
     ("cssm_pf_interpolate", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("cssm_pf_smooth", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_uint32, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p]),
+    ("cssm_pf_smooth_last_ms", C.c_int, [_h, _dp]),
     ("cssm_resample_systematic", C.c_int, [_dp, C.c_size_t, C.c_double, _u32p, C.c_int]),
     ("cssm_resample", C.c_int, [C.c_int, _dp, C.c_size_t, C.c_double, C.c_uint64, C.c_uint32, _u32p, C.c_int]),
     ("cssm_resample_residual", C.c_int, [_dp, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.c_int]),

@@ -190,6 +190,10 @@ struct cssm_pf : HostModel {
   double obs_scale = 0.0;
   size_t forecast_cap = 0;
   double forecast_ms[2] = {-1.0, -1.0};
+  // cssm_pf_smooth (cssm_smooth.hip): the slots per block tile of its backward kernels (CSSM_OPT_SMOOTH_TILE; 0 = CSSM_SMOOTH_TILE) and
+  // the device times of the last call (cssm_pf_smooth_last_ms; < 0: none yet)
+  uint32_t smooth_tile = 0;
+  double smooth_ms[3] = {-1.0, -1.0, -1.0};
 };
 
 // begin/end of one profiled launch

@@ -13,6 +13,7 @@
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
 #include "cssm_offspring_wave.hip.h"
+#include "cssm_smooth.hip.h"
 
 static int upload_init_params(cssm_pf* pf) {
   double m0[CSSM_MAX_DIM], sd0[CSSM_MAX_DIM];
@@ -1082,6 +1083,12 @@ extern "C" int cssm_pf_set_option(cssm_pf* pf, int option, int value) {
     pf->forecast_cap = (size_t)value * 1024;
     return CSSM_OK;
   }
+  if (option == CSSM_OPT_SMOOTH_TILE) {   // cssm_pf_smooth: the slots a block of the backward kernels stages; 0 = CSSM_SMOOTH_TILE
+    if (value < 0 || (value != 0 && (value < 64 || value % 64 != 0)))
+      return fail(CSSM_EINVAL_ARG, "CSSM_OPT_SMOOTH_TILE is 0 (the default, %d slots) or a multiple of 64, at least 64 (got %d)", CSSM_SMOOTH_TILE, value);
+    pf->smooth_tile = (uint32_t)value;
+    return CSSM_OK;
+  }
   if (option == CSSM_OPT_SPECIALISE) { pf->opt_spec = (value == 2) ? 2 : (value ? 1 : 0); return CSSM_OK; }
   if (option == CSSM_OPT_WHOLE_TILES) {   // launch geometry only: the arrays hold up to four sub-units per unit either way
     if (pf->sharded) return fail(CSSM_ESTATE, "sharded handles always run whole tiles");
@@ -1261,25 +1268,33 @@ __global__ void k_iota(uint32_t* __restrict__ b, uint64_t n) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) b[i] = (uint32_t)i;
 }
 
-extern "C" int cssm_pf_interpolate(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double interval,
-                                   int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper,
-                                   double* eta_of_mean, double* eta_lower, double* eta_upper) {
-  if (!pf || !t || !y) return fail(CSSM_EINVAL_ARG, "null argument");
-  if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data");
-  if (pf->sharded) return fail(CSSM_ESTATE, "interpolation runs on a single-GPU handle");
-  if (pf->obs_kind == CSSM_OBS_LGCP) return fail(CSSM_EINVAL_ARG, "FilterInterpolate weighs with dataLikelihood; the LGCP filter has no path variant");
-  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
-  HIP_TRY(hipSetDevice(pf->device));
+// The history the forward pass of cssm_pf_interpolate and cssm_pf_smooth keeps: slice s (the cloud X1_s: X1_0 the initial cloud, X1_{s+1}
+// what record s proposed) at hx + s d stride, the ancestors that resampled it at hanc + s stride where weighted[s] (else the identity).
+// While it lives the handle's state and ancestor pointers look into it; interp_history_end puts them back.
+struct InterpHistory {
+  double* hx = nullptr;
+  uint32_t *hanc = nullptr, *bidx = nullptr;             // bidx: the composed genealogy (cssm_pf_interpolate alone)
+  std::vector<uint8_t> weighted;
+  double t0 = 0.0;
+  double* save_state[2] = {nullptr, nullptr};
+  uint32_t* save_anc = nullptr;
+};
+
+// The forward half of both calls: the records, the history's memory (with the genealogy's index array where want_bidx) and the filter
+// writing straight into it; ll_out as cssm_pf_ll_filter has it.  A return before the history exists leaves hist.hx null.
+static int interp_forward(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, bool want_bidx, double* ll_out,
+                          InterpHistory& hist) {
   int rc = cssm_ensure_recs(pf, T);
   if (rc) return rc;
   const int d = pf->d;
   const size_t slab = pf->stride * (size_t)d;
   double* hx = nullptr; uint32_t *hanc = nullptr, *bidx = nullptr;
-  std::vector<uint8_t> weighted(T + 1, 0);
-  double* save_state[2] = {pf->state[0], pf->state[1]};
-  uint32_t* save_anc = pf->anc;
+  std::vector<uint8_t>& weighted = hist.weighted;
+  weighted.assign(T + 1, 0);
+  hist.save_state[0] = pf->state[0]; hist.save_state[1] = pf->state[1];
+  hist.save_anc = pf->anc;
   if (hipMalloc(&hx, (T + 1) * slab * 8 + 64) != hipSuccess) return fail(CSSM_ENOMEM, "history of %zu clouds does not fit (%zu bytes)", T + 1, (T + 1) * slab * 8);
-  if (hipMalloc(&hanc, (T + 1) * pf->stride * 4) != hipSuccess || hipMalloc(&bidx, pf->stride * 4) != hipSuccess) {
+  if (hipMalloc(&hanc, (T + 1) * pf->stride * 4) != hipSuccess || (want_bidx && hipMalloc(&bidx, pf->stride * 4) != hipSuccess)) {
     (void)hipFree(hx); if (hanc) (void)hipFree(hanc);
     return fail(CSSM_ENOMEM, "ancestor history does not fit");
   }
@@ -1288,7 +1303,8 @@ extern "C" int cssm_pf_interpolate(cssm_pf* pf, const double* t, const double* y
   double tp = t0;
   for (size_t s = 0; s < T; ++s) { cssm_build_rec(pf, tp, t[s], y[s], has ? has[s] : 1, (uint32_t)s, &pf->h_recs[s]); tp = t[s]; }
   rc = cssm_build_fsub(pf, 0, T, true);
-  if (rc) return rc;
+  if (rc) { (void)hipFree(hx); (void)hipFree(hanc); if (bidx) (void)hipFree(bidx); return rc; }
+  hist.hx = hx; hist.hanc = hanc; hist.bidx = bidx; hist.t0 = t0;
   rc = cssm_upload_recs(pf, 0, T, false);
   Scalars h;
   for (int attempt = 0; attempt < 2 && !rc; ++attempt) {   // second attempt: see run_filter
@@ -1315,6 +1331,35 @@ extern "C" int cssm_pf_interpolate(cssm_pf* pf, const double* t, const double* y
   pf->safe_sums = false;
   if (!rc) rc = cssm_check_device_err(pf, h);
   if (!rc && ll_out) *ll_out = h.ll;
+  return rc;
+}
+
+// ... and the end of both: the stream idle, the handle's own pointers back (its buffers hold no cloud now), the history released
+static void interp_history_end(cssm_pf* pf, InterpHistory& hist, const double* t, size_t T) {
+  (void)hipStreamSynchronize(pf->stream);
+  pf->state[0] = hist.save_state[0]; pf->state[1] = hist.save_state[1]; pf->anc = hist.save_anc;
+  pf->initialised = false;                               // the handle's own buffers hold no cloud now
+  (void)hipFree(hist.hx); (void)hipFree(hist.hanc); if (hist.bidx) (void)hipFree(hist.bidx);
+  pf->t = t[T - 1]; pf->step = (uint32_t)T;
+}
+
+extern "C" int cssm_pf_interpolate(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double interval,
+                                   int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper,
+                                   double* eta_of_mean, double* eta_lower, double* eta_upper) {
+  if (!pf || !t || !y) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data");
+  if (pf->sharded) return fail(CSSM_ESTATE, "interpolation runs on a single-GPU handle");
+  if (pf->obs_kind == CSSM_OBS_LGCP) return fail(CSSM_EINVAL_ARG, "FilterInterpolate weighs with dataLikelihood; the LGCP filter has no path variant");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  HIP_TRY(hipSetDevice(pf->device));
+  InterpHistory hist;
+  int rc = interp_forward(pf, t, y, has, T, true, ll_out, hist);
+  if (!hist.hx) return rc;
+  const int d = pf->d;
+  const size_t slab = pf->stride * (size_t)d;
+  double* const hx = hist.hx; uint32_t* const hanc = hist.hanc; uint32_t* const bidx = hist.bidx;
+  const std::vector<uint8_t>& weighted = hist.weighted;
+  const double t0 = hist.t0;
   // backward: compose the genealogy and summarise every time index
   if (!rc) {
     hipLaunchKernelGGL(k_iota, dim3(grid_for(pf->n, 256, kGridCap)), dim3(256), 0, pf->stream, bidx, pf->n);
@@ -1331,12 +1376,150 @@ extern "C" int cssm_pf_interpolate(cssm_pf* pf, const double* t, const double* y
                         eta_lower ? eta_lower + o : nullptr, eta_upper ? eta_upper + o : nullptr);
     }
   }
-  (void)hipStreamSynchronize(pf->stream);
-  pf->state[0] = save_state[0]; pf->state[1] = save_state[1]; pf->anc = save_anc;
-  pf->initialised = false;                               // the handle's own buffers hold no cloud now
-  (void)hipFree(hx); (void)hipFree(hanc); (void)hipFree(bidx);
-  pf->t = t[T - 1]; pf->step = (uint32_t)T;
+  interp_history_end(pf, hist, t, T);
   return rc;
+}
+
+// EXTENSION (the reference has no smoother beyond FilterInterpolate): forward filtering, backward simulation on one handle --
+// cssm_pf_interpolate's forward pass, then n_traj trajectories drawn backwards through the kept clouds under the contract's backward
+// kernel (include/cssm_numerics.h, "backward simulation"), the slots tiled over many workgroups (cssm_smooth.hip), and summarised per
+// time index.  The launches of the backward half, per time index from T - 1 down: an index whose record has an sd_c not > 0 -- decided
+// here from the record, uniform for the index -- takes the genealogical step in one launch, every other one the four of the header.
+static int smooth_backward(cssm_pf* pf, const InterpHistory& hist, size_t T, uint32_t n_traj, uint32_t* d_traj, unsigned long long* d_pkey,
+                           cssm_u128* d_psum, double* d_level, uint32_t tile, uint32_t ntile) {
+  const size_t slab = pf->stride * (size_t)pf->d;
+  SmoothLaunch l;
+  l.d = pf->d; l.stream = pf->stream;
+  SmoothArgs& a = l.args;
+  a.n = (uint32_t)pf->n; a.n_traj = n_traj; a.tile = tile; a.ntile = ntile; a.stride = pf->stride;
+  a.seed = pf->seed; a.traj = d_traj; a.pkey = d_pkey; a.psum = d_psum; a.level = d_level; a.mk = pf->mk;
+  auto at = [&](size_t s) {
+    a.s = (uint32_t)s;
+    a.X = hist.hx + s * slab; a.Xn = (s < T) ? hist.hx + (s + 1) * slab : nullptr;
+    a.A = hist.weighted[s] ? hist.hanc + s * pf->stride : nullptr;
+    a.rec = (s < T) ? pf->d_recs + s : nullptr;
+  };
+  auto run = [&](int hrc, const char* what) { return hrc ? fail(CSSM_EHIP, "%s: %s", what, hipGetErrorString((hipError_t)hrc)) : CSSM_OK; };
+  at(T);
+  int rc = run(cssm_smooth_fold_launch(l, SMOOTH_START), "k_smooth_fold");
+  for (size_t s = T; s-- > 0 && !rc;) {
+    const StepRec& r = pf->h_recs[s];
+    bool gen = false;
+    for (int c = 0; c < pf->d; ++c)
+      if (!(cssm_back_sd(pf->mk.kind(c), r.coef[c][2], r.coef[c][3]) > 0.0)) gen = true;
+    at(s);
+    if (gen) { rc = run(cssm_smooth_fold_launch(l, SMOOTH_GEN), "k_smooth_fold"); continue; }
+    rc = run(cssm_smooth_tiles_launch(l, 0), "k_smooth_tiles");
+    if (!rc) rc = run(cssm_smooth_fold_launch(l, SMOOTH_LEVEL), "k_smooth_fold");
+    if (!rc) rc = run(cssm_smooth_tiles_launch(l, 1), "k_smooth_tiles");
+    if (!rc) rc = run(cssm_smooth_fold_launch(l, SMOOTH_SEARCH), "k_smooth_fold");
+  }
+  return rc;
+}
+
+extern "C" int cssm_pf_smooth(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, uint32_t n_traj, double interval,
+                              int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
+                              double* eta_lower, double* eta_upper, uint32_t* traj_out) {
+  if (!pf || !t || !y) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data");
+  if (T > 0xfffffffeull) return fail(CSSM_EINVAL_ARG, "too many records");
+  if (pf->sharded) return fail(CSSM_ESTATE, "cssm_pf_smooth runs on a single-GPU handle");
+  if (pf->obs_kind == CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_ARG, "cssm_pf_smooth: an LGCP handle is not served (the transition over an event is a chain of sub-steps, not one Gaussian)");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (flags & CSSM_INTERP_REFERENCE_PAIRING)
+    return fail(CSSM_EINVAL_ARG, "cssm_pf_smooth: CSSM_INTERP_REFERENCE_PAIRING is not offered (row s is time index s; cssm_pf_interpolate pairs)");
+  if (flags) return fail(CSSM_EINVAL_ARG, "cssm_pf_smooth: unknown flag bits 0x%x (flags must be 0)", (unsigned)flags);
+  if (n_traj == 0u || n_traj > CSSM_FLEET_MAX_N)
+    return fail(CSSM_EINVAL_ARG, "cssm_pf_smooth: n_traj must be in [1, CSSM_FLEET_MAX_N = %u] (got %u)", (unsigned)CSSM_FLEET_MAX_N, n_traj);
+  HIP_TRY(hipSetDevice(pf->device));
+  const int d = pf->d, rows = d + 1;
+  const uint32_t tile = pf->smooth_tile ? pf->smooth_tile : (uint32_t)CSSM_SMOOTH_TILE;
+  const uint32_t ntile = (uint32_t)((pf->n + tile - 1) / tile);
+  if ((size_t)d * tile * 8u > 144u * 1024u)              // (the default tile fits at every d: 64 KiB at d = 16)
+    return fail(CSSM_EINVAL_ARG, "cssm_pf_smooth: a tile of %u slots at d = %d does not fit a block's LDS (%zu bytes; CSSM_OPT_SMOOTH_TILE)", tile, d,
+                (size_t)d * tile * 8u);
+  // the work space first: a refusal here finds the handle as it was
+  uint32_t* d_traj = nullptr; unsigned long long* d_pkey = nullptr; cssm_u128* d_psum = nullptr; double *d_level = nullptr, *d_fco = nullptr, *d_out = nullptr;
+  hipEvent_t ev[4];
+  CssmTemps tmp;
+  const size_t part = (size_t)n_traj * ntile;
+  const size_t work = (T + 1) * (size_t)n_traj * 4 + part * 24 + (size_t)n_traj * 8 + (T + 1) * (size_t)(d + rows * 3) * 8;
+  if (tmp.alloc(d_traj, (T + 1) * (size_t)n_traj * 4) != hipSuccess || tmp.alloc(d_pkey, part * 8) != hipSuccess ||
+      tmp.alloc(d_psum, part * 16) != hipSuccess || tmp.alloc(d_level, (size_t)n_traj * 8) != hipSuccess ||
+      tmp.alloc(d_fco, (T + 1) * (size_t)d * 8) != hipSuccess || tmp.alloc(d_out, (T + 1) * (size_t)rows * 3 * 8) != hipSuccess)
+    return fail(CSSM_ENOMEM, "cssm_pf_smooth: the trajectories, the tiles' partials and the rows do not fit (%zu bytes)", work);
+  for (hipEvent_t& e : ev) HIP_TRY(tmp.event(e));
+  std::vector<double> hfco((T + 1) * (size_t)d), hout((T + 1) * (size_t)rows * 3);
+  {
+    double t0 = t[0];
+    for (size_t s = 1; s < T; ++s) if (t[s] < t0) t0 = t[s];
+    for (size_t q = 0; q <= T; ++q) {                    // F(time of output row q), as cssm_pf_interpolate's summaries build it
+      const double time = q ? t[q - 1] : t0;
+      StepRec rec;
+      cssm_build_rec(pf, time, time, 0.0, 0, 0u, &rec);
+      for (int c = 0; c < d; ++c) hfco[q * (size_t)d + c] = rec.fco[c];
+    }
+  }
+  HIP_TRY(hipEventRecord(ev[0], pf->stream));
+  InterpHistory hist;
+  int rc = interp_forward(pf, t, y, has, T, false, ll_out, hist);
+  if (!hist.hx) return rc;
+  SelState rs, re;
+  sel_ranks(rs, n_traj, interval, true);
+  sel_ranks(re, n_traj, interval, false);
+  auto hip_ok = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(CSSM_EHIP, "cssm_pf_smooth: %s: %s", what, hipGetErrorString(e)); };
+  if (!rc) {
+    hip_ok(hipEventRecord(ev[1], pf->stream), "event");
+    if (!rc) rc = smooth_backward(pf, hist, T, n_traj, d_traj, d_pkey, d_psum, d_level, tile, ntile);
+    hip_ok(hipEventRecord(ev[2], pf->stream), "event");
+  }
+  if (!rc) {
+    SmoothRowLaunch q;
+    q.args.n_traj = n_traj; q.args.np2 = 2u;
+    while (q.args.np2 < n_traj) q.args.np2 <<= 1;
+    q.args.stride = pf->stride; q.args.hist = hist.hx; q.args.traj = d_traj; q.args.fco = d_fco; q.args.out = d_out; q.args.mk = pf->mk;
+    q.args.lo_state = (uint32_t)rs.rank[0]; q.args.hi_state = (uint32_t)rs.rank[1];
+    q.args.lo_eta = (uint32_t)re.rank[0]; q.args.hi_eta = (uint32_t)re.rank[1];
+    q.d = d; q.rows = (uint32_t)(T + 1); q.stream = pf->stream;
+    hip_ok(hipMemcpyAsync(d_fco, hfco.data(), hfco.size() * 8, hipMemcpyHostToDevice, pf->stream), "f coefficients");
+    const int hrc = rc ? 0 : cssm_smooth_rows_launch(q);
+    if (hrc) rc = fail(CSSM_EHIP, "k_smooth_rows: %s", hipGetErrorString((hipError_t)hrc));
+    hip_ok(hipEventRecord(ev[3], pf->stream), "event");
+    hip_ok(hipMemcpyAsync(hout.data(), d_out, hout.size() * 8, hipMemcpyDeviceToHost, pf->stream), "rows");
+    if (traj_out) hip_ok(hipMemcpyAsync(traj_out, d_traj, (T + 1) * (size_t)n_traj * 4, hipMemcpyDeviceToHost, pf->stream), "trajectories");
+    hip_ok(hipStreamSynchronize(pf->stream), "backward pass");
+  }
+  interp_history_end(pf, hist, t, T);
+  if (rc) return rc;
+  float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+  if (hipEventElapsedTime(&m0, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&m1, ev[1], ev[2]) == hipSuccess &&
+      hipEventElapsedTime(&m2, ev[2], ev[3]) == hipSuccess) {
+    pf->smooth_ms[0] = (double)m0; pf->smooth_ms[1] = (double)m1; pf->smooth_ms[2] = (double)m2;
+  } else {
+    pf->smooth_ms[0] = pf->smooth_ms[1] = pf->smooth_ms[2] = 0.0;
+  }
+  for (size_t q = 0; q <= T; ++q) {                      // eta of the mean is formed here (model/ParticleFilter.scala:420) from the row's own f coefficients
+    const double* src = hout.data() + q * (size_t)rows * 3;
+    double mean[CSSM_MAX_DIM];
+    for (int c = 0; c < d; ++c) {
+      mean[c] = src[3 * c];
+      if (state_mean) state_mean[q * d + c] = mean[c];
+      if (state_lower) state_lower[q * d + c] = src[3 * c + 1];
+      if (state_upper) state_upper[q * d + c] = src[3 * c + 2];
+    }
+    if (eta_lower) eta_lower[q] = src[3 * d + 1];
+    if (eta_upper) eta_upper[q] = src[3 * d + 2];
+    if (eta_of_mean) eta_of_mean[q] = cssm_eta_of_mean(*pf, hfco.data() + q * (size_t)d, mean);
+  }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_pf_smooth_last_ms(cssm_pf* pf, double* ms3) {
+  if (!pf || !ms3) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (pf->smooth_ms[0] < 0.0) return fail(CSSM_ESTATE, "no smoothing has run on this handle (cssm_pf_smooth first)");
+  ms3[0] = pf->smooth_ms[0]; ms3[1] = pf->smooth_ms[1]; ms3[2] = pf->smooth_ms[2];
+  return CSSM_OK;
 }
 
 // ------------------------------------------------------------------------------------ stateless resampler

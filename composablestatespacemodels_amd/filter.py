@@ -297,6 +297,36 @@ class NativePf:
         _abi.check(rc)
         return (ll.value,) + rows
 
+    def smooth(self, t, y, has=None, n_traj: Optional[int] = None, interval: float = 0.975, want_trajectories: bool = False):
+        """cssm_pf_smooth (an EXTENSION: the reference has no smoother beyond ``FilterInterpolate``): ``interpolate``'s forward pass, then
+        ``n_traj`` trajectories (None: min(N, 4096)) drawn backwards through the kept clouds and summarised per time index.  Returns what
+        ``interpolate`` returns, ``(ll, mean[T+1,d], lower, upper, eta_of_mean[T+1], eta_lower, eta_upper)``, and with
+        ``want_trajectories`` one more entry: the uint32 array ``[T + 1, n_traj]`` of the particle of each kept cloud every trajectory
+        passes through.  The handle must be re-initialised before further streaming calls."""
+        M = min(self.n, _abi.FLEET_MAX_N) if n_traj is None else int(n_traj)
+        if not 1 <= M <= _abi.FLEET_MAX_N:
+            raise ValueError(f"n_traj must be in [1, {_abi.FLEET_MAX_N}], not {M}")
+        if not 0.0 < float(interval) <= 1.0:
+            raise ValueError(f"interval must be in (0, 1], not {interval}")
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        T = len(t)
+        has = _u8(has)
+        rows = _interval_arrays((T + 1,), self.d)
+        traj = np.zeros((T + 1, M), dtype=np.uint32) if want_trajectories else None
+        ll = C.c_double()
+        rc = self.lib.cssm_pf_smooth(self._h, _p(t), _p(y), _p(has), T, M, float(interval), 0, C.byref(ll), *map(_p, rows), _p(traj))
+        self.generation += 1
+        _abi.check(rc)
+        out = (ll.value,) + rows
+        return out + (traj,) if want_trajectories else out
+
+    def smooth_last_ms(self) -> Tuple[float, float, float]:
+        """Device time (HIP events) of the last ``smooth``'s forward pass, backward simulation and row summaries, ms."""
+        ms = np.zeros(3)
+        _abi.check(self.lib.cssm_pf_smooth_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
     def particles(self) -> np.ndarray:
         out = np.zeros((self.d, self.n))
         _abi.check(self.lib.cssm_pf_get_particles(self._h, _p(out)))
@@ -1390,6 +1420,15 @@ class FilterInterpolate(_FilterBase):
                     reference_pairing: bool = False) -> Tuple[float, List[PfOut]]:
         t, y, h = split_data(data)
         ll, *arrays = self._ensure(particles).interpolate(t, y, h, interval, reference_pairing)
+        return ll, _interpolate_outs(data, t, arrays)
+
+    def smooth(self, data: Sequence[TimedObservation], particles: int, n_traj: Optional[int] = None,
+               interval: float = 0.975) -> Tuple[float, List[PfOut]]:
+        """EXTENSION (the reference has none): forward filtering, backward simulation -- ``interpolate``'s forward pass, then ``n_traj``
+        trajectories (None: min(particles, 4096)) drawn backwards through the kept clouds (``NativePf.smooth``).  Returns what
+        ``interpolate`` returns, in the chronological pairing."""
+        t, y, h = split_data(data)
+        ll, *arrays = self._ensure(particles).smooth(t, y, h, n_traj, interval)
         return ll, _interpolate_outs(data, t, arrays)
 
 

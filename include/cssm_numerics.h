@@ -1194,6 +1194,8 @@ CSSM_HD double cssm_ref_choose(double c, double max) {
 /*
  * EXTENSION (not a restatement of running reference code: the reference has no smoother beyond FilterInterpolate).  Forward
  * filtering, backward simulation (Godsill, Doucet and West 2004) on the history a fleet's interpolation keeps: cssm_fleet_smooth.
+ * cssm_pf_smooth is the section's second user: the same statements on the history cssm_pf_interpolate keeps, with seed = the handle's
+ * Philox key and the slots tiled over many workgroups (a tile's max, a tile's exact sum, the first tile whose end value reaches u).
  *
  * Notation.  A series has records 0 .. T-1.  Slice X_0 is the initial cloud, slice X_{s+1} the cloud record s proposed; A_s are the
  * ancestors that resampled X_s (the identity for s = 0 and behind an unweighted record); the equally weighted filtering cloud at

@@ -321,6 +321,11 @@ int cssm_pf_stream_idle(cssm_pf* pf);
  * cloud of a time index from -- 0: the block's LDS where d x N x 8 bytes fit, else the slice through L2; 1: never LDS.  The results do not
  * depend on it (tests/test_gpu_fleet_smooth.py); it exists for tests and measurements. */
 #define CSSM_OPT_SMOOTH_STAGING 14
+/* CSSM_OPT_SMOOTH_TILE (single handles only, cssm_pf_set_option; default 0 = CSSM_SMOOTH_TILE): the slots a block of cssm_pf_smooth's
+ * backward kernels stages in LDS -- a multiple of 64, at least 64; anything else is CSSM_EINVAL_ARG and changes nothing.  The results do
+ * not depend on it (tests/test_gpu_smooth.py lowers it to put many tiles under a small cloud). */
+#define CSSM_OPT_SMOOTH_TILE 15
+#define CSSM_SMOOTH_TILE 512
 int cssm_pf_set_option(cssm_pf* pf, int option, int value);
 /* Counters of the run-time specialisation in this process: out4 = {kernels compiled, kernels loaded from the disk cache, launches of
  * run-time-compiled kernels, failures (each reported once on stderr)}. */
@@ -537,6 +542,31 @@ int cssm_simulate_lgcp_last_ms(double* ms2);
 int cssm_pf_interpolate(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T, double interval,
                         int flags, double* ll_out, double* state_mean, double* state_lower, double* state_upper,
                         double* eta_of_mean, double* eta_lower, double* eta_upper);
+/* ---- EXTENSION (not a restatement of running reference code: the reference has no smoother beyond FilterInterpolate): forward filtering,
+ * backward simulation of ONE series on a cloud of any size the handle holds -- cssm_fleet_smooth (below) for the single handle, whose
+ * backward kernels tile the SLOTS over many workgroups instead of keeping a cloud inside one.  The forward pass is cssm_pf_interpolate's
+ * (the same code, history and ll_out bits); then n_traj trajectories are drawn backwards through the kept clouds under the contract's
+ * backward kernel (include/cssm_numerics.h, "backward simulation") with seed = the handle's Philox key, and summarised per time index.
+ * Per time index, going back, launches on the handle's stream: the level (per trajectory and tile of CSSM_SMOOTH_TILE slots, then folded
+ * over the tiles), the exact 128-bit sums of the weights per tile, and the search (tile, then slot); an index whose record has a
+ * component with sd not > 0 takes the genealogical step in one launch.
+ *
+ * t / y / has_obs / T, the T + 1 output rows (row 0 the initial cloud; row s is time index s) and the handle's state afterwards are
+ * cssm_pf_interpolate's: its own buffers hold no cloud, it must be re-initialised before further streaming calls.  Row s summarises
+ * the n_traj states the trajectories hold at index s: the mean is their plain fp64 sum / n_traj, lower / upper the order statistics at
+ * the ranks cssm_pf_summary takes for n_traj values, eta as cssm_fleet_smooth forms it.  Any output may be NULL.  traj_out (may be
+ * NULL): [T + 1][n_traj], entry [row][m] the particle of slice `row` (an index into the cloud that record proposed, < N) trajectory m
+ * passes through.  1 <= n_traj <= CSSM_FLEET_MAX_N and flags must be 0 (CSSM_INTERP_REFERENCE_PAIRING is refused by name), else
+ * CSSM_EINVAL_ARG; an LGCP handle is CSSM_EINVAL_ARG (its transition over an event is a chain of sub-steps, not one Gaussian), a sharded
+ * one CSSM_ESTATE; every resampler is served.  History or work space that does not fit is CSSM_ENOMEM naming the bytes. */
+int cssm_pf_smooth(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T,
+                   uint32_t n_traj, double interval, int flags, double* ll_out,
+                   double* state_mean, double* state_lower, double* state_upper,
+                   double* eta_of_mean, double* eta_lower, double* eta_upper,
+                   uint32_t* traj_out);
+/* ms3 = device time (HIP events on the handle's stream) of the forward pass, of the backward simulation and of the row summaries of the
+ * last cssm_pf_smooth.  CSSM_ESTATE before the first.  The array holds THREE doubles. */
+int cssm_pf_smooth_last_ms(cssm_pf* pf, double* ms3);
 
 /* ---- stateless resampler: the `Resample[A]` seam (model/package.scala:23) ------------------ */
 
