@@ -9,8 +9,9 @@ from ._abi import CssmError, load_library
 from .filter import FilterFleet, FilterInitFleet, FilterLgcpFleet, ForecastOut, NativeLgcpFleet, NativePfFleet, ObservationWithState, ParticleFilter
 from .simulate import LgcpSim, SimulateData, SimulatedPoint, lgcp_events_data, lgcp_fleet_data, simulate, simulate_from, simulate_lgcp, simulate_lgcp_last_ms
 from .streaming import Streaming
+from .smc2 import SMC2, FleetEngine, Smc2State
 from .model import (Data, Model, Parameters, ParamNode, Sde, SdeParameter, TimedObservation,
                     UnparamModel, UnparamSde, logistic, logit)
 
-__all__ = ["_abi", "CssmError", "load_library", "FilterFleet", "ForecastOut", "NativePfFleet", "NativeLgcpFleet", "FilterLgcpFleet", "FilterInitFleet", "lgcp_fleet_data", "Streaming", "SimulateData", "SimulatedPoint", "simulate", "simulate_from", "LgcpSim", "simulate_lgcp", "simulate_lgcp_last_ms", "lgcp_events_data", "ObservationWithState", "ParticleFilter", "Data", "Model", "Parameters", "ParamNode", "Sde",
+__all__ = ["_abi", "CssmError", "load_library", "FilterFleet", "ForecastOut", "NativePfFleet", "NativeLgcpFleet", "FilterLgcpFleet", "FilterInitFleet", "lgcp_fleet_data", "Streaming", "SMC2", "Smc2State", "FleetEngine", "SimulateData", "SimulatedPoint", "simulate", "simulate_from", "LgcpSim", "simulate_lgcp", "simulate_lgcp_last_ms", "lgcp_events_data", "ObservationWithState", "ParticleFilter", "Data", "Model", "Parameters", "ParamNode", "Sde",
            "SdeParameter", "TimedObservation", "UnparamModel", "UnparamSde", "logistic", "logit"]

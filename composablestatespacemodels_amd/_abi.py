@@ -35,6 +35,8 @@ CSSM_OPT_SMOOTH_TILE = 15      # cssm_pf_smooth: the slots a block of the backwa
 SMOOTH_TILE = 512              # CSSM_SMOOTH_TILE
 CSSM_INTERP_REFERENCE_PAIRING = 1
 CSSM_FLEET_NO_ROWS = 0xFFFFFFFF
+CSSM_FLEET_COPY_KEEP = -1         # cssm_fleet_copy_series, a map entry: leave the series exactly as it is
+CSSM_FLEET_COPY_KEYS = 1          # ... flags: the Philox key travels too
 CSSM_OPT_FORECAST_CAP = 11
 CSSM_SIM_STEP_ROW0 = 0xFFFFFFFF   # include/cssm_obs_draws.h: the step of the observation drawn at t0
 CSSM_LGCP_SIM_KEEP_GRID = 1       # cssm_simulate_lgcp: download the grid rows too
@@ -235,6 +237,7 @@ SYMBOLS = [
     ("cssm_fleet_pack_record_lgcp", C.c_int, [_descp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_uint32, _u8p, C.c_size_t,
                                               C.POINTER(C.c_size_t), _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("cssm_fleet_init_from", C.c_int, [_h, _u8p, _dp, _u64p, _dp, _u32p, _u64p, _u32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_copy_series", C.c_int, [_h, _h, _u64p, C.c_int, C.POINTER(C.c_int)]),   # (map: int64 entries, -1 = keep, in the header's uint64_t)
     ("cssm_fleet_ll_filter_more", C.c_int, [_h, _u64p, _dp, _dp, _u8p, _dp, _dp, _i32p, C.POINTER(C.c_int)]),
     ("cssm_fleet_filter_intervals_more", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_double, _dp, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp,
                                                    C.POINTER(C.c_int)]),

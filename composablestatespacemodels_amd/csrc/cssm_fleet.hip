@@ -12,6 +12,9 @@
 // (cssm_fleet_lgcp.hip.h): every record is an event, built by cssm_build_rec under the series' model as for a handle, and where f depends
 // on time the rows of cssm_build_fsub_table of every event of the launch travel behind the records in the same upload.  What it does
 // not serve is refused at the top of the entry point.
+//
+// cssm_fleet_copy_series (EXTENSION; k_fleet_copy, cssm_fleet_copy.hip.h) copies whole series between the series of one fleet or from a
+// second fleet: what SMC2's resampling and adoption need of a fleet whose series are parameter particles.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +28,7 @@
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
 #include "cssm_fleet.hip.h"
+#include "cssm_fleet_copy.hip.h"
 #include "cssm_fleet_forecast.hip.h"
 #include "cssm_fleet_interp.hip.h"
 #include "cssm_fleet_smooth.hip.h"
@@ -131,6 +135,8 @@ struct cssm_fleet {
   hipEvent_t ev_win[3] = {nullptr, nullptr, nullptr};   // before the forward launch | between the two | behind the lineage launch
   double ms_win[2] = {-1.0, -1.0};
   bool win_ran = false;
+  FleetBuf d_copy;                      // cssm_fleet_copy_series within one fleet: the ancestors ([S][n] uint32) and scalars ([S] FleetSeries) between its two launches
+  hipEvent_t ev_copy = nullptr;         // ... from a second fleet: recorded on the source's stream, waited for on this one
 };
 // series k's cloud, key or parameters are about to be written by another call than cssm_fleet_step_interpolate: its window restarts
 static void fleet_win_drop(cssm_fleet* f, uint32_t k) {
@@ -281,6 +287,7 @@ extern "C" void cssm_fleet_destroy(cssm_fleet* f) {
   for (hipEvent_t e : f->ev_ip) if (e) (void)hipEventDestroy(e);
   if (f->ev_bs) (void)hipEventDestroy(f->ev_bs);
   for (hipEvent_t e : f->ev_win) if (e) (void)hipEventDestroy(e);
+  if (f->ev_copy) (void)hipEventDestroy(f->ev_copy);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;   // (every FleetBuf frees itself)
 }
@@ -1198,6 +1205,120 @@ extern "C" int cssm_fleet_init_from(cssm_fleet* f, const uint8_t* active, const 
   }
   for (uint32_t k = 0; k < S; ++k)   // (the call succeeds; the message names the first refused series)
     if (rc_out[k]) { (void)fail(CSSM_EINVAL_ARG, "series %u: %s", k, msg[k].c_str()); break; }
+  return CSSM_OK;
+}
+
+// EXTENSION (the reference has no operation that writes one filter's cloud from another's; SMC2's resampling and adoption need it):
+// dst series k <- src series map[k], simultaneously.  The moved series are compacted into a table of moves (staged like a launch's
+// records) and k_fleet_copy gathers them (cssm_fleet_copy.hip.h).  Two fleets: one launch behind an event on the source's stream, every
+// cloud straight into the half its observation index selects.  One fleet: that half is, in lockstep use, the destination's own live
+// half, which another block may be reading as ITS source -- and nothing waits on another block inside a kernel.  So the first launch
+// writes every moved cloud into the destination's NON-live half (nobody reads one: conflict-free for any map) and the ancestors and
+// scalars into d_copy; the second launch settles, within each series, the clouds whose required half is the other one and brings
+// ancestors and scalars home.  A destination without a cloud has no live half: its cloud goes straight where it belongs.
+extern "C" int cssm_fleet_copy_series(cssm_fleet* dst, cssm_fleet* src, const uint64_t* umap, int flags, int* rc_out) {
+  const int64_t* map = reinterpret_cast<const int64_t*>(umap);   // (signed entries in the header's unsigned type: include/cssm_pf.h)
+  if (!dst || !src || !umap || !rc_out) return fail(CSSM_EINVAL_ARG, "null argument (dst, src, map, rc_out)");
+  if (flags & ~CSSM_FLEET_COPY_KEYS) return fail(CSSM_EINVAL_ARG, "cssm_fleet_copy_series: unknown flag bits 0x%x", (unsigned)(flags & ~CSSM_FLEET_COPY_KEYS));
+  const uint32_t S = dst->S, n = dst->n;
+  const bool same = src == dst;
+  for (uint32_t k = 0; k < S; ++k)
+    if (map[k] < CSSM_FLEET_COPY_KEEP || map[k] >= (int64_t)src->S)
+      return fail(CSSM_EINVAL_ARG, "map[%u] = %lld is neither CSSM_FLEET_COPY_KEEP nor a series of the source (0 .. %u)", k, (long long)map[k], src->S - 1u);
+  if (src->n != n) return fail(CSSM_EINVAL_ARG, "the fleets hold clouds of different sizes (%u and %u particles)", src->n, n);
+  if (src->device != dst->device) return fail(CSSM_EINVAL_ARG, "the fleets live on different devices (%d and %d)", src->device, dst->device);
+  if (src->lgcp != dst->lgcp) return fail(CSSM_EINVAL_ARG, "one fleet is an LGCP fleet and the other is not");
+  {
+    const HostModel &a = src->base, &b = dst->base;
+    std::string diff;
+    auto differs = [&](const char* what) { diff += diff.empty() ? "" : ", "; diff += what; };
+    bool comps = a.d == b.d && a.n_leaves == b.n_leaves;
+    for (int c = 0; comps && c < a.d; ++c)
+      comps = a.comp[c].kind == b.comp[c].kind && a.comp[c].leaf == b.comp[c].leaf && a.comp[c].idx == b.comp[c].idx &&
+              a.comp[c].f_kind == b.comp[c].f_kind && a.comp[c].period == b.comp[c].period;
+    for (int w = 0; comps && w < CSSM_MAX_DIM / 4; ++w) comps = a.mk.comp[w] == b.mk.comp[w];
+    if (!comps) differs("the components (cssm_model_structure)");
+    if (a.obs_kind != b.obs_kind) differs("obs_kind");
+    if (a.obs_df != b.obs_df) differs("obs_df");
+    if (a.precision != b.precision) differs("lgcp_precision");
+    if (!diff.empty()) return fail(CSSM_EINVAL_DESC, "the fleets differ in model structure: %s", diff.c_str());
+  }
+  const int d = dst->d;
+  const size_t dn = (size_t)d * n;
+  std::vector<uint32_t> moved;
+  int64_t first_dead = -1;
+  for (uint32_t k = 0; k < S; ++k) {
+    rc_out[k] = CSSM_OK;
+    const int64_t j = map[k];
+    if (j < 0 || (same && j == (int64_t)k)) continue;
+    if (!src->live[(size_t)j]) { rc_out[k] = CSSM_ESTATE; if (first_dead < 0) first_dead = (int64_t)k; continue; }
+    moved.push_back(k);
+  }
+  const size_t M = moved.size();
+  if (M) {
+    HIP_TRY(hipSetDevice(dst->device));
+    const size_t table = M * sizeof(FleetCopyMove), anc_bytes = fleet_pad8((size_t)S * n * 4u);
+    if (!dst->h_stage.reserve(2u * table, true) || !dst->d_stage.reserve(2u * table, true)) return fail(CSSM_ENOMEM, "fleet copy: %zu bytes of moves", 2u * table);
+    if (same && !dst->d_copy.reserve(anc_bytes + (size_t)S * sizeof(FleetSeries), false))
+      return fail(CSSM_ENOMEM, "fleet copy: %zu bytes between its two launches", anc_bytes + (size_t)S * sizeof(FleetSeries));
+    if (!same && !dst->ev_copy && hipEventCreateWithFlags(&dst->ev_copy, hipEventDisableTiming) != hipSuccess) return fail(CSSM_EHIP, "hipEventCreate");
+    FleetCopyMove* h1 = dst->h_stage.at<FleetCopyMove>();
+    FleetCopyMove* h2 = h1 + M;
+    for (size_t q = 0; q < M; ++q) {
+      const uint32_t k = moved[q], j = (uint32_t)map[k];
+      const uint32_t need = src->step[j] & 1u;                                              // the half the source's observation index selects
+      const uint32_t first = (same && dst->live[k]) ? 1u - (dst->step[k] & 1u) : need;     // one fleet: the destination's non-live half
+      h1[q] = FleetCopyMove{((size_t)j * 2u + need) * dn, ((size_t)k * 2u + first) * dn, j, k, CSSM_FLEET_COPY_CLOUD, 0u};
+      h2[q] = FleetCopyMove{((size_t)k * 2u + first) * dn, ((size_t)k * 2u + need) * dn, k, k, first != need ? CSSM_FLEET_COPY_CLOUD : 0u, 0u};
+    }
+    if (!same) {   // behind everything the source's stream still holds
+      HIP_TRY(hipEventRecord(dst->ev_copy, src->stream));
+      HIP_TRY(hipStreamWaitEvent(dst->stream, dst->ev_copy, 0));
+    }
+    HIP_TRY(hipEventRecord(dst->ev[EV_CALL_BEGIN], dst->stream));
+    HIP_TRY(hipMemcpyAsync(dst->d_stage.p, dst->h_stage.p, (same ? 2u : 1u) * table, hipMemcpyHostToDevice, dst->stream));
+    FleetCopyArgs a{};
+    a.dn = (uint32_t)dn; a.n = n; a.tiles = (uint32_t)((dn + CSSM_FLEET_COPY_TILE - 1u) / CSSM_FLEET_COPY_TILE);
+    a.moves = dst->d_stage.at<FleetCopyMove>();
+    a.src_state = src->state.at<double>(); a.dst_state = dst->state.at<double>();
+    a.src_anc = src->anc.at<uint32_t>(); a.src_ser = src->ser.at<FleetSeries>();
+    a.dst_anc = same ? dst->d_copy.at<uint32_t>() : dst->anc.at<uint32_t>();
+    a.dst_ser = same ? dst->d_copy.at<FleetSeries>(anc_bytes) : dst->ser.at<FleetSeries>();
+    int hrc = fleet_copy_launch(a, (uint32_t)M, dst->stream);
+    if (!hrc && same) {   // settle: every block reads only what the first launch finished, within its own series
+      a.moves += M;
+      a.src_state = a.dst_state;
+      a.src_anc = a.dst_anc; a.src_ser = a.dst_ser;
+      a.dst_anc = dst->anc.at<uint32_t>(); a.dst_ser = dst->ser.at<FleetSeries>();
+      hrc = fleet_copy_launch(a, (uint32_t)M, dst->stream);
+    }
+    if (hrc) return fail(CSSM_EHIP, "k_fleet_copy: %s", hipGetErrorString((hipError_t)hrc));
+    HIP_TRY(hipEventRecord(dst->ev[EV_CALL_END], dst->stream));
+    HIP_TRY(hipStreamSynchronize(dst->stream));
+    if (hipEventElapsedTime(&dst->ms_call, dst->ev[EV_CALL_BEGIN], dst->ev[EV_CALL_END]) != hipSuccess) dst->ms_call = -1.f;
+    // the host's side of every moved series, read before any is written (the assignment is simultaneous)
+    struct Host { HostModel m; double t; uint32_t step; int has_scale; double scale; };
+    std::vector<Host> from(M);
+    for (size_t q = 0; q < M; ++q) {
+      const size_t j = (size_t)map[moved[q]];
+      from[q] = Host{src->models[j], src->t[j], src->step[j], src->obs_has_scale[j], src->obs_scale[j]};
+    }
+    for (size_t q = 0; q < M; ++q) {
+      const uint32_t k = moved[q];
+      const uint64_t own = dst->models[k].seed;
+      dst->models[k] = from[q].m;
+      if (!(flags & CSSM_FLEET_COPY_KEYS)) dst->models[k].seed = own;
+      dst->t[k] = from[q].t; dst->step[k] = from[q].step; dst->live[k] = 1;
+      dst->obs_has_scale[k] = from[q].has_scale; dst->obs_scale[k] = from[q].scale;
+      fleet_win_drop(dst, k);
+    }
+    dst->par_dirty = true;
+  } else {
+    dst->ms_call = 0.f;
+  }
+  if (first_dead >= 0)   // (the call succeeds; the message names the first such series)
+    (void)fail(CSSM_ESTATE, "series %lld: its source, series %lld, has no cloud (not initialised, or its weights were unusable)", (long long)first_dead,
+               (long long)map[first_dead]);
   return CSSM_OK;
 }
 

@@ -806,6 +806,25 @@ class NativePfFleet:
         _abi.check(self.lib.cssm_fleet_init_from(self._h, _p(_u8(active)), _p(t0), _p(moff), _p(xx), _p(pk), _p(ky), _p(pick_out), _p(rc)))
         return pick_out, rc
 
+    def copy_series(self, map, src: Optional["NativePfFleet"] = None, keys: bool = False):
+        """cssm_fleet_copy_series (EXTENSION): series k <- series ``map[k]`` of ``src`` (None = this fleet), simultaneously and on the
+        device -- cloud, ancestors, ll / ess, clock, observation index, parameters; with ``keys`` the Philox key too (by default series k
+        keeps its own).  ``map``: S integers, -1 or None = keep.  ``rc[S]``: -7 where the source series has no cloud (series k is then
+        left as it was)."""
+        if len(map) != self.S:
+            raise ValueError(f"one map entry per series ({self.S}), not {len(map)}")
+        mp = np.ascontiguousarray([_abi.CSSM_FLEET_COPY_KEEP if v is None else int(v) for v in map], dtype=np.int64)
+        other = self if src is None else src
+        rc = np.zeros(self.S, dtype=np.int32)
+        self.generation += 1
+        _abi.check(self.lib.cssm_fleet_copy_series(self._h, other._h, _p(mp.view(np.uint64)), _abi.CSSM_FLEET_COPY_KEYS if keys else 0, _p(rc)))
+        if keys:   # (forecast_key reads them)
+            old = list(other.seeds)
+            for k in range(self.S):
+                if mp[k] >= 0 and rc[k] == 0:
+                    self.seeds[k] = old[int(mp[k])]
+        return rc
+
     def _step_inputs(self, t, y, has, active):
         """What every step call starts with: ``(t, y, has, active)`` as the C call takes them (None stays None), one ``(t, y)`` per
         series or a refusal.  The caller holds them across its C call."""

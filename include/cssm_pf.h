@@ -1010,6 +1010,40 @@ int cssm_fleet_step(cssm_fleet* f, const uint8_t* active, const double* t, const
 int cssm_fleet_init_from(cssm_fleet* f, const uint8_t* active, const double* t0, const uint64_t* moff, const double* x,
                          const uint32_t* pick, const uint64_t* keys, uint32_t* pick_out, int* rc_out);
 
+/* ---- EXTENSION (not a restatement of running reference code: the reference has no online parameter learner -- its ParamFilterState,
+ * model/ParticleFilter.scala:89-94, is never used -- and nothing there writes one filter's cloud from another's): whole series copied
+ * between the series of one fleet, or from a second fleet of the same shape, on the device.  It is what SMC2 (composablestatespacemodels_amd/
+ * smc2.py: Chopin, Jacob and Papaspiliopoulos 2013) needs of a fleet whose series are its parameter particles: resampling them
+ * (series k <- series a[k]) and adopting the freshly filtered cloud of a proposal fleet.
+ *
+ * map has cssm_fleet_num_series(dst) entries; src may be dst.  An entry is a SIGNED 64-bit number (an int64_t in two's complement: -1 is
+ * CSSM_FLEET_COPY_KEEP) in the unsigned 64-bit type every other index array of the fleet section has -- an int64_t array is passed as it
+ * is, with a cast.  The assignment is SIMULTANEOUS: every read sees the state before the call,
+ * so a rotation, a swap and "everybody from series 0" are well defined.  For map[k] = j >= 0 with a source series j that has a cloud,
+ * series k of dst afterwards holds series j's cloud (cssm_fleet_get_particles is bit-equal; it sits in the half of state[S][2][d][n] that
+ * j's observation index selects), ancestors, ll, ess and (LGCP fleet) predicted level, clock, observation index (Philox counter word and
+ * buffer parity), liveness and parameters (the parameter block is uploaded again before the next launch) -- and j's Philox key only under
+ * CSSM_FLEET_COPY_KEYS: by default the destination keeps its own.  Series k's window restarts (a call that writes a series' cloud:
+ * cssm_fleet_step_interpolate, Continuity); the source's is untouched.  map[k] = CSSM_FLEET_COPY_KEEP, and map[k] = k with src == dst,
+ * leave series k entirely untouched (rc_out[k] = CSSM_OK).
+ *   Continuity: after the call every fleet call on dst series k has the bits of a series that was created with series j's parameters and
+ *   key, driven through series j's calls and then -- unless CSSM_FLEET_COPY_KEYS -- given series k's key by cssm_fleet_reseed
+ *   (cssm_pf_reseed on a handle of its own).
+ * rc_out[S] = the series' OWN status: CSSM_ESTATE when the source series has no cloud (never initialised, or failed since) -- the
+ * destination is then left exactly as it was and cssm_last_error names the first such series.  Refused for the whole call, before anything
+ * changes: CSSM_EINVAL_ARG for a null dst / src / map / rc_out (before either fleet is looked at), a map entry outside [-1, S_src), unknown
+ * flag bits, another N, another device, one fleet LGCP and the other not; CSSM_EINVAL_DESC for another model structure (the
+ * cssm_model_structure words, obs_kind, obs_df, lgcp_precision: the message names what differs).  LGCP fleets are served: no record and
+ * no transition is touched.
+ * One gather kernel over (moved series x tiles of a cloud), k_fleet_copy; kept, self-mapped and dead-source series get no block.  From a
+ * second fleet: one launch, ordered behind the source fleet's stream by an event.  Within one fleet nothing waits on another block; the
+ * call stages instead: the first launch writes every moved cloud into the destination's own NON-live half -- nobody reads one, so any
+ * map is free of conflicts -- and the ancestors and scalars into scratch; a second launch settles, within each series, the clouds whose
+ * required half is the other one and brings ancestors and scalars home.  The device time is cssm_fleet_last_ms()[0]. */
+#define CSSM_FLEET_COPY_KEEP (-1)   /* map entry: leave the series exactly as it is */
+#define CSSM_FLEET_COPY_KEYS 1      /* flags: the Philox key travels too (default: the destination keeps its own key) */
+int cssm_fleet_copy_series(cssm_fleet* dst, cssm_fleet* src, const uint64_t* map, int flags, int* rc_out);
+
 /* cssm_pf_ll_filter_more for every series: T_k MORE records of the filters that are already running, in ONE launch -- what a loop of T
  * cssm_fleet_step calls does with a launch and a host round trip per record.  off / t / y / has_obs / ll_t / ess_t are laid out as in
  * cssm_fleet_ll_filter.  No cloud is drawn; the first increment of a series is taken from its clock, and record s of the call is
