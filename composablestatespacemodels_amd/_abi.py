@@ -41,6 +41,8 @@ CSSM_OPT_FORECAST_CAP = 11
 CSSM_SIM_STEP_ROW0 = 0xFFFFFFFF   # include/cssm_obs_draws.h: the step of the observation drawn at t0
 CSSM_LGCP_SIM_KEEP_GRID = 1       # cssm_simulate_lgcp: download the grid rows too
 CSSM_STREAM_THIN = 10             # include/cssm_obs_draws.h: the candidates of simLGCP's thinning
+CSSM_STREAM_IF2 = 12              # include/cssm_numerics.h: the perturbation normals of iterated filtering
+IF2_MAX_THETA = 81                # CSSM_IF2_MAX_THETA
 CSSM_LGCP_PATH_OK, CSSM_LGCP_PATH_NONFINITE, CSSM_LGCP_PATH_TOO_MANY = 0, 1, 2   # a path's status
 
 _dp = C.POINTER(C.c_double)
@@ -225,6 +227,11 @@ SYMBOLS = [
     ("cssm_fleet_smooth", C.c_int, [_h, _u64p, _dp, _dp, _u8p, C.c_uint32, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p,
                                     C.POINTER(C.c_int)]),
     ("cssm_fleet_smooth_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_fleet_if2", C.c_int, [_h, _descp, _dp, _dp, C.c_size_t, _dp, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, _dp, _dp, _u8p,
+                                 _dp, _dp, _dp, _dp, _i32p, _dp, _u32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_if2_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_fleet_if2_cooling", C.c_int, [C.c_double, C.c_uint32, C.c_uint32, _dp]),
+    ("cssm_fleet_if2_layout", C.c_int, [_descp, _i32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("cssm_fleet_window", C.c_int, [_h, C.c_uint32]),
     ("cssm_fleet_window_depth", C.c_uint32, [_h, C.c_uint32]),
     ("cssm_fleet_step_interpolate", C.c_int, [_h, _u8p, _dp, _dp, _u8p, _u32p, C.c_uint32, C.c_double, _dp, _i32p, _u32p, _dp, _dp, _dp, _dp, _dp, _dp,

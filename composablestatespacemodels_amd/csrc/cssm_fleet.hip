@@ -32,6 +32,7 @@
 #include "cssm_fleet_forecast.hip.h"
 #include "cssm_fleet_interp.hip.h"
 #include "cssm_fleet_smooth.hip.h"
+#include "cssm_fleet_if2.hip.h"
 #include "cssm_simulate.hip.h"
 #include "cssm_simulate_plan.h"
 
@@ -123,6 +124,7 @@ struct cssm_fleet {
   double ms_bs[3] = {-1.0, -1.0, -1.0}; // ... forward, backward, summary of the last call, summed over its chunks
   bool bs_ran = false;
   int bs_staging = 0;                   // CSSM_OPT_SMOOTH_STAGING: 0 = the gathered means in LDS where they fit, 1 = never (through L2)
+  double ms_if2 = -1.0;                 // cssm_fleet_if2: the device time of the last call's launches (cssm_fleet_if2_last_ms)
   // the window of cssm_fleet_step_interpolate: per series a ring of win_slices slots, each a cloud and the ancestors that resampled it
   // ([S][slices][d][n] doubles, then [S][slices][n] uint32).  Per series on the host: whether the window is continuous (the cloud the
   // fleet holds is the one its newest slot holds), the newest slot, the records remembered behind the base slice; per slot F at its time
@@ -1991,6 +1993,179 @@ extern "C" int cssm_fleet_smooth_last_ms(cssm_fleet* f, double* ms3) {
   if (!f || !ms3) return fail(CSSM_EINVAL_ARG, "null argument");
   if (!f->bs_ran) return fail(CSSM_ESTATE, "no smoothing has run on this fleet (cssm_fleet_smooth first)");
   ms3[0] = f->ms_bs[0]; ms3[1] = f->ms_bs[1]; ms3[2] = f->ms_bs[2];
+  return CSSM_OK;
+}
+
+// EXTENSION (the reference has no likelihood maximiser): iterated filtering (IF2; Ionides, Nguyen, Atchade, Stoev and King 2015) -- S
+// independent searches, one workgroup each, every iteration and record of a search inside k_fleet_if2 (cssm_fleet_if2.hip).  The
+// arithmetic is the contract's (include/cssm_numerics.h, "iterated filtering").  The fleet lends its device, stream, contract table, N
+// and structure; the swarm, the states and the records live in buffers of the call.
+#define FLEET_IF2_SERVED "cssm_pmmh_run / cssm_pmmh_run_batched explore the parameters of a single handle's model"
+extern "C" int cssm_fleet_if2(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, const double* swarm0, size_t n_theta,
+                              const double* rw_sd, double cooling_fraction_50, uint32_t first_iter, uint32_t n_iters, uint32_t iters_per_launch,
+                              const uint64_t* seeds, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                              double* theta_mean, double* ll, double* swarm_out, double* ll_t, int32_t* ess_t, double* x_out,
+                              uint32_t* anc_out, int* rc_out) {
+  if (!desc || !rw_sd || !seeds || !off) return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: null argument (desc, rw_sd, seeds, off)");
+  if (!theta0 && !swarm0) return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: theta0 and swarm0 are both null (a starting row per series, or a whole swarm)");
+  if (!theta_mean || !ll || !rc_out) return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: null output (theta_mean, ll, rc_out)");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  for (size_t j = 0; j < n_theta; ++j)
+    if (!(rw_sd[j] >= 0.0) || !std::isfinite(rw_sd[j]))
+      return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: rw_sd[%zu] = %g must be finite and not negative (0 keeps the slot fixed)", j, rw_sd[j]);
+  if (n_iters < 1u || n_iters > 1000000u) return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: n_iters must be in [1, 1000000] (got %u)", n_iters);
+  if ((uint64_t)first_iter + n_iters > (1ull << 31)) return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: first_iter + n_iters must not exceed 2^31");
+  std::vector<double> cool(n_iters);                            // one array for the kernel and for whoever restates the search
+  if (const int crc = cssm_fleet_if2_cooling(cooling_fraction_50, first_iter, n_iters, cool.data())) return crc;
+  HostModel probe;
+  int rc = cssm_build_model(&probe, desc, false);
+  if (rc) return rc;
+  if (probe.obs_kind == CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_DESC, "cssm_fleet_if2: the LGCP observation model (sub-stepped events) is not served; " FLEET_IF2_SERVED);
+  If2Map map;
+  if ((rc = cssm_if2_map_build(desc, &map))) return rc;
+  if ((size_t)map.n_theta != n_theta)
+    return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: n_theta = %zu, the descriptor flattens to %d (cssm_desc_flatten)", n_theta, (int)map.n_theta);
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_if2", FLEET_IF2_SERVED);
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const uint32_t S = f->S, n = f->n;
+  const int d = f->d;
+  for (uint32_t k = 0; k < S; ++k) {
+    if ((rc = fleet_off_step("off", off, k))) return rc;
+    if (off[k + 1] - off[k] > 0xfffffffeull) return fail(CSSM_EINVAL_ARG, "series %u: too many records", k);
+  }
+  {   // the structure must be the fleet's
+    HostModel same = f->base;
+    rc = cssm_build_model(&same, desc, true);
+    if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "cssm_fleet_if2: desc is not of the fleet's model structure (%s)", keep.c_str()); }
+  }
+  HIP_TRY(hipSetDevice(f->device));
+  const size_t nt = n_theta, R = (size_t)off[S], RB = CSSM_FLEET_IF2_REC_BYTES(d);
+  // staged upload: offsets | seeds | rw_sd | cool | records
+  const size_t o_seeds = ((size_t)S + 1u) * 8u, o_sd = o_seeds + (size_t)S * 8u, o_cool = o_sd + nt * 8u, o_recs = o_cool + (size_t)n_iters * 8u;
+  std::vector<unsigned char> stage(o_recs + R * RB);
+  memcpy(stage.data(), off, ((size_t)S + 1u) * 8u);
+  memcpy(stage.data() + o_seeds, seeds, (size_t)S * 8u);
+  memcpy(stage.data() + o_sd, rw_sd, nt * 8u);
+  memcpy(stage.data() + o_cool, cool.data(), (size_t)n_iters * 8u);
+  const bool own_level = probe.obs_kind == CSSM_OBS_GAUSSIAN || probe.obs_kind == CSSM_OBS_STUDENT_T;
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+      if (b == a) continue;
+      double tp = t[a];
+      for (size_t s = a + 1; s < b; ++s) tp = (t[s] < tp) ? t[s] : tp;     // data.minBy(_.t).t
+      for (size_t s = a; s < b; ++s) {
+        StepRec rec;                                                      // (dt and F(t) as every fleet record has them)
+        cssm_build_rec(&f->base, tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), &rec);
+        FleetIf2Rec h;
+        h.y = y[s]; h.ypart = cssm_obs_ypart(probe.obs_kind, y[s], (double)probe.obs_df);
+        h.ref = own_level ? 0.0 : cssm_if2_level(probe.obs_kind, y[s], 1.0, (double)probe.obs_df);
+        h.dt = rec.dt; h.has_obs = rec.has_obs; h.step = rec.step;
+        unsigned char* dst = stage.data() + o_recs + s * RB;
+        memcpy(dst, &h, sizeof h);
+        memcpy(dst + sizeof h, rec.fco, (size_t)d * 8u);
+        tp = t[s];
+      }
+    }
+  });
+  CssmTemps tmp;
+  unsigned char* d_stage = nullptr;
+  double *d_swarm = nullptr, *d_theta = nullptr, *d_x = nullptr, *d_mean = nullptr, *d_ll = nullptr, *d_ll_t = nullptr;
+  int32_t* d_ess_t = nullptr; uint32_t* d_anc = nullptr; FleetIf2Series* d_ser = nullptr;
+  const size_t sw_bytes = (size_t)S * nt * n * 8u, x_bytes = (size_t)S * 2u * d * n * 8u, mean_bytes = (size_t)S * n_iters * nt * 8u;
+  HIP_ALLOC(tmp, d_stage, stage.size());
+  HIP_ALLOC(tmp, d_swarm, sw_bytes);
+  HIP_ALLOC(tmp, d_theta, 2u * sw_bytes);
+  HIP_ALLOC(tmp, d_x, x_bytes);
+  HIP_ALLOC(tmp, d_mean, mean_bytes);
+  HIP_ALLOC(tmp, d_ll, (size_t)S * n_iters * 8u);
+  HIP_ALLOC(tmp, d_ser, (size_t)S * sizeof(FleetIf2Series));
+  if (ll_t && R) HIP_ALLOC(tmp, d_ll_t, R * 8u);
+  if (ess_t && R) HIP_ALLOC(tmp, d_ess_t, R * 4u);
+  if (anc_out) HIP_ALLOC(tmp, d_anc, (size_t)S * n * 4u);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIP_TRY(tmp.event(e0)); HIP_TRY(tmp.event(e1));
+  HIP_TRY(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, f->stream));
+  {   // the starting swarm: the caller's, or every particle of series k at theta0[k]
+    std::vector<double> sw;
+    const double* src = swarm0;
+    if (!swarm0) {
+      sw.resize((size_t)S * nt * n);
+      for (size_t k = 0; k < S; ++k)
+        for (size_t j = 0; j < nt; ++j) std::fill_n(sw.data() + (k * nt + j) * n, n, theta0[k * nt + j]);
+      src = sw.data();
+    }
+    HIP_TRY(hipMemcpyAsync(d_swarm, src, sw_bytes, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));   // (stage and sw are pageable)
+  }
+  HIP_TRY(hipMemsetAsync(d_ser, 0, (size_t)S * sizeof(FleetIf2Series), f->stream));
+  HIP_TRY(hipMemsetAsync(d_mean, 0xff, mean_bytes, f->stream));   // (rows no iteration writes are not read back)
+  HIP_TRY(hipMemsetAsync(d_ll, 0xff, (size_t)S * n_iters * 8u, f->stream));
+  if (d_ll_t) HIP_TRY(hipMemsetAsync(d_ll_t, 0xff, R * 8u, f->stream));
+  if (d_ess_t) HIP_TRY(hipMemsetAsync(d_ess_t, 0xff, R * 4u, f->stream));
+  FleetIf2Launch l{};
+  l.args.n = n; l.args.n_theta = (uint32_t)nt; l.args.n_iters = n_iters; l.args.first_iter = first_iter;
+  l.args.swarm = d_swarm; l.args.theta = d_theta; l.args.x = d_x; l.args.ser = d_ser;
+  l.args.off = reinterpret_cast<const unsigned long long*>(d_stage);
+  l.args.seeds = reinterpret_cast<const unsigned long long*>(d_stage + o_seeds);
+  l.args.rw_sd = reinterpret_cast<const double*>(d_stage + o_sd);
+  l.args.cool = reinterpret_cast<const double*>(d_stage + o_cool);
+  l.args.recs = d_stage + o_recs;
+  l.args.theta_mean = d_mean; l.args.ll = d_ll; l.args.ll_t = d_ll_t; l.args.ess_t = d_ess_t;
+  l.args.logtab = f->logtab.at<const double>();
+  l.args.df = (double)probe.obs_df; l.args.mk = f->base.mk; l.args.map = map;
+  l.n_series = S; l.d = d; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+  const uint32_t per = (iters_per_launch == 0u || iters_per_launch > n_iters) ? n_iters : iters_per_launch;
+  HIP_TRY(hipEventRecord(e0, f->stream));
+  for (uint32_t it0 = 0; it0 < n_iters && R; it0 += per) {      // (the result does not depend on the split: a launch leaves the swarm in HBM)
+    l.args.it0 = it0; l.args.it1 = std::min(n_iters, it0 + per);
+    l.args.anc_out = (l.args.it1 == n_iters) ? d_anc : nullptr;
+    const int hrc = cssm_fleet_if2_launch(l);
+    if (hrc) return fail(CSSM_EHIP, "k_fleet_if2: %s", hipGetErrorString((hipError_t)hrc));
+  }
+  HIP_TRY(hipEventRecord(e1, f->stream));
+  std::vector<double> h_mean((size_t)S * n_iters * nt), h_ll((size_t)S * n_iters), h_x(x_out ? x_bytes / 8u : 0u);
+  std::vector<FleetIf2Series> h_ser(S);
+  HIP_TRY(hipMemcpyAsync(h_mean.data(), d_mean, mean_bytes, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(h_ll.data(), d_ll, h_ll.size() * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(h_ser.data(), d_ser, (size_t)S * sizeof(FleetIf2Series), hipMemcpyDeviceToHost, f->stream));
+  if (swarm_out) HIP_TRY(hipMemcpyAsync(swarm_out, d_swarm, sw_bytes, hipMemcpyDeviceToHost, f->stream));
+  if (d_ll_t) HIP_TRY(hipMemcpyAsync(ll_t, d_ll_t, R * 8u, hipMemcpyDeviceToHost, f->stream));
+  if (d_ess_t) HIP_TRY(hipMemcpyAsync(ess_t, d_ess_t, R * 4u, hipMemcpyDeviceToHost, f->stream));
+  if (x_out) HIP_TRY(hipMemcpyAsync(h_x.data(), d_x, x_bytes, hipMemcpyDeviceToHost, f->stream));
+  if (anc_out) HIP_TRY(hipMemcpyAsync(anc_out, d_anc, (size_t)S * n * 4u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  float ms = 0.f;
+  f->ms_if2 = (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : -1.0;
+  for (uint32_t k = 0; k < S; ++k) {
+    const size_t a = (size_t)off[k], T = (size_t)off[k + 1] - a;
+    const bool failed = T != 0 && h_ser[k].err != 0u;
+    const uint32_t done = T == 0 ? 0u : (failed ? h_ser[k].fail_iter : n_iters);   // the iterations whose rows stand
+    rc_out[k] = failed ? CSSM_ENONFINITE : CSSM_OK;
+    for (uint32_t m = 0; m < n_iters; ++m) {
+      const size_t row = (size_t)k * n_iters + m;
+      ll[row] = m < done ? h_ll[row] : cssm_nan();
+      for (size_t j = 0; j < nt; ++j) theta_mean[row * nt + j] = m < done ? h_mean[row * nt + j] : cssm_nan();
+    }
+    const bool whole = T != 0 && !failed;                        // the last iteration's diagnostics exist
+    if (ll_t && !whole) std::fill(ll_t + a, ll_t + a + T, cssm_nan());
+    if (ess_t && !whole) std::fill(ess_t + a, ess_t + a + T, -1);
+    if (anc_out && !whole) std::fill(anc_out + (size_t)k * n, anc_out + ((size_t)k + 1u) * n, 0xffffffffu);
+    if (x_out) {                                                 // the cloud the last record proposed: record T - 1 wrote buffer T & 1
+      double* dst = x_out + (size_t)k * d * n;
+      if (whole) memcpy(dst, h_x.data() + ((size_t)k * 2u + (T & 1u)) * d * n, (size_t)d * n * 8u);
+      else std::fill(dst, dst + (size_t)d * n, cssm_nan());
+    }
+  }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_if2_last_ms(cssm_fleet* f, double* ms) {
+  if (!f || !ms) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (f->ms_if2 < 0.0) return fail(CSSM_ESTATE, "no search has run on this fleet (cssm_fleet_if2 first)");
+  *ms = f->ms_if2;
   return CSSM_OK;
 }
 

@@ -35,7 +35,6 @@ extern "C" const char* cssm_version(void) { return "cssm_pf 0.5 (gfx950, numeric
 // ------------------------------------------------------------------------------------ model
 
 static double rep(const double* v, int n, int i) { return v[i % n]; }               // Sde.buildParamRepeat, model/Sde.scala:177-179
-static double logistic(double x) { return 1.0 / (1.0 + cssm_exp(-x)); }              // model/SdeParameters.scala:214-216
 
 // Constraint transforms of the SDE constructors: model/Sde.scala:70-73 (GenBrownian),
 // :99-102 (Brownian), :133-137 (OU, logistic applied to the stored value).
@@ -91,18 +90,12 @@ static int build_model_into(HostModel* pf, const cssm_model_desc* desc) {
       Comp& c = pf->comp[d + i];
       c = Comp{};
       c.kind = L->sde_kind; c.leaf = l; c.idx = i; c.f_kind = L->f_kind; c.period = L->period;
-      c.m0 = rep(L->m0, L->n_m0, i);
-      c.c0 = cssm_exp(rep(L->c0, L->n_c0, i));
-      switch (L->sde_kind) {
-        case CSSM_SDE_BROWNIAN: c.sigma = cssm_exp(rep(L->sigma, L->n_sigma, i)); break;
-        case CSSM_SDE_GEN_BROWNIAN: c.mu = rep(L->mu, L->n_mu, i); c.sigma = cssm_exp(rep(L->sigma, L->n_sigma, i)); break;
-        case CSSM_SDE_OU:
-          c.phi = logistic(rep(L->phi, L->n_phi, i));
-          c.mu = rep(L->mu, L->n_mu, i);
-          c.sigma = cssm_exp(rep(L->sigma, L->n_sigma, i));
-          break;
-        default: c.mu = rep(L->mu, L->n_mu, i); c.phi = rep(L->phi, L->n_phi, i); c.sigma = rep(L->sigma, L->n_sigma, i); break;
-      }
+      // (the expressions are cssm_constrain's -- include/cssm_numerics.h: the IF2 kernel forms them per particle from the same text)
+      c.m0 = cssm_constrain(L->sde_kind, CSSM_FIELD_M0, rep(L->m0, L->n_m0, i));
+      c.c0 = cssm_constrain(L->sde_kind, CSSM_FIELD_C0, rep(L->c0, L->n_c0, i));
+      if (need_mu) c.mu = cssm_constrain(L->sde_kind, CSSM_FIELD_MU, rep(L->mu, L->n_mu, i));
+      if (need_phi) c.phi = cssm_constrain(L->sde_kind, CSSM_FIELD_PHI, rep(L->phi, L->n_phi, i));
+      c.sigma = cssm_constrain(L->sde_kind, CSSM_FIELD_SIGMA, rep(L->sigma, L->n_sigma, i));
     }
     d += L->dim;
   }
@@ -175,34 +168,10 @@ void cssm_build_rec(const HostModel* pf, double t_prev, double t, double y, int 
       r->fco[k] = (c.idx & 1) ? sn : cs;
     }
   }
-  const long long k = (long long)y;                            // y.toInt
-  r->y = y;
-  switch (pf->obs_kind) {
-    case CSSM_OBS_POISSON:                                     // c0 = lgamma(k+1)
-      r->y = (double)k; r->c[0] = cssm_lgamma_kp1(k); break;
-    case CSSM_OBS_GAUSSIAN:                                    // c0 = log(sqrt(2 pi) sd), c1 = sd
-      r->c[0] = cssm_log(2.5066282746310002 * pf->scale_sd); r->c[1] = pf->scale_sd; break;
-    case CSSM_OBS_NEGBIN: {                                    // c0 = lgamma(size+k) - lgamma(k+1) - lgamma(size), c1 = size
-      const double size = pf->scale_sd;
-      r->y = (double)k;
-      r->c[0] = cssm_lgamma(size + (double)k) - cssm_lgamma_kp1(k) - cssm_lgamma(size); r->c[1] = size;
-      break;
-    }
-    case CSSM_OBS_ZIP: {                                       // c0 = p, c1 = -log(1 + exp(v)), c2 = lgamma(k+1)
-      const double ev = cssm_exp(pf->scale_raw);
-      r->y = (double)k;
-      r->c[0] = ev / (1.0 + ev); r->c[1] = -cssm_log(1.0 + ev); r->c[2] = cssm_lgamma_kp1(k);
-      break;
-    }
-    case CSSM_OBS_STUDENT_T: {                                 // c0 = -logNormalizer, c1 = v, c2 = (df+1)/2, c3 = 1/v
-      const double df = (double)pf->obs_df, v = pf->scale_sd;
-      r->c[0] = cssm_lgamma((df + 1.0) / 2.0) - cssm_lgamma(df / 2.0) - 0.5 * cssm_log(3.14159265358979311600 * df);
-      r->c[1] = v; r->c[2] = (df + 1.0) / 2.0; r->c[3] = 1.0 / v; r->cdf = df;
-      break;
-    }
-    case CSSM_OBS_BETA: r->c[0] = cssm_log(y); break;          // c0 = log(y)
-    default: break;                                            // Bernoulli, LGCP: no constants
-  }
+  // the constants of the density: c[], cdf and the count models' (double)y.toInt (cssm_obs_consts, include/cssm_numerics.h -- the IF2
+  // kernel evaluates the same text per particle)
+  r->y = cssm_obs_y(pf->obs_kind, y);
+  cssm_obs_consts(pf->obs_kind, y, cssm_obs_ypart(pf->obs_kind, y, (double)pf->obs_df), pf->scale_sd, pf->scale_raw, (double)pf->obs_df, r->c, &r->cdf);
   // reference level of the step's weights (include/cssm_numerics.h); NaN = rescale by the max
   // (LGCP: predicted on the device from the previous weighted observation's max -- StepRec::predict; NaN until it is)
   r->ref = (pf->obs_kind == CSSM_OBS_LGCP) ? cssm_nan() : cssm_ref_level(pf->obs_kind, y, pf->scale_sd, (double)pf->obs_df);
@@ -280,6 +249,67 @@ static int own_desc(const cssm_model_desc* in, OwnedDesc* o) {
     else if (L.sde_kind == CSSM_SDE_OU || L.sde_kind == CSSM_SDE_EULER_AFFINE) { push(L.phi, L.n_phi); push(L.mu, L.n_mu); }  // m0 ++ c0 ++ phi ++ mu ++ sigma
     push(L.sigma, L.n_sigma);
   }
+  return CSSM_OK;
+}
+
+// (IF2, EXTENSION) where the flattened stored vector -- own_desc's order -- holds what every component reads, and which slots only feed
+// the initial draw.  The descriptor has been validated (build_model_into).
+int cssm_if2_map_build(const cssm_model_desc* desc, If2Map* map) {
+  memset(map, 0xff, sizeof *map);                               // every slot -1
+  memset(map->ivp, 0, sizeof map->ivp);
+  int at = 0, k = 0;
+  map->scale_slot = desc->leaves[0].has_scale ? 0 : -1;
+  for (int l = 0; l < desc->n_leaves; ++l) {
+    const cssm_leaf_desc& L = desc->leaves[l];
+    int first[5] = {-1, -1, -1, -1, -1}, len[5] = {1, 1, 1, 1, 1};
+    auto take = [&](int field, int n) { first[field] = at; len[field] = n; at += n; };
+    if (L.has_scale) ++at;
+    take(CSSM_FIELD_M0, L.n_m0); take(CSSM_FIELD_C0, L.n_c0);
+    if (L.sde_kind == CSSM_SDE_GEN_BROWNIAN) take(CSSM_FIELD_MU, L.n_mu);
+    else if (L.sde_kind == CSSM_SDE_OU || L.sde_kind == CSSM_SDE_EULER_AFFINE) { take(CSSM_FIELD_PHI, L.n_phi); take(CSSM_FIELD_MU, L.n_mu); }
+    take(CSSM_FIELD_SIGMA, L.n_sigma);
+    if (at > CSSM_IF2_MAX_THETA)
+      return fail(CSSM_EINVAL_DESC, "cssm_fleet_if2: the descriptor flattens to more than %d parameters (vectors longer than their leaf's dimension?)",
+                  CSSM_IF2_MAX_THETA);
+    for (int q = first[CSSM_FIELD_M0]; q < first[CSSM_FIELD_C0] + len[CSSM_FIELD_C0]; ++q) map->ivp[q] = 1;   // m0 ++ c0 are adjacent
+    for (int i = 0; i < L.dim; ++i, ++k)
+      for (int fld = 0; fld < 5; ++fld) map->slot[k][fld] = (int16_t)(first[fld] < 0 ? -1 : first[fld] + i % len[fld]);
+  }
+  map->n_theta = (int16_t)at;
+  return CSSM_OK;
+}
+
+// cool[q] = c^((first_iter + q) / 50), q < n_iters: the array cssm_fleet_if2 hands its kernel, for whoever restates a search (include/cssm_pf.h)
+extern "C" int cssm_fleet_if2_cooling(double cooling_fraction_50, uint32_t first_iter, uint32_t n_iters, double* cool) {
+  if (!cool) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (!(cooling_fraction_50 > 0.0 && cooling_fraction_50 <= 1.0))
+    return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2: cooling_fraction_50 = %g must be in (0, 1] (the factor the random walk shrinks by over 50 iterations)",
+                cooling_fraction_50);
+  for (uint32_t q = 0; q < n_iters; ++q) cool[q] = std::pow(cooling_fraction_50, ((double)first_iter + (double)q) / 50.0);
+  return CSSM_OK;
+}
+
+// Diagnostic, no device: the table above as integers (include/cssm_pf.h)
+extern "C" int cssm_fleet_if2_layout(const cssm_model_desc* desc, int32_t* out, size_t cap, size_t* count) {
+  if (!desc || !count) return fail(CSSM_EINVAL_ARG, "null argument");
+  HostModel m;
+  int rc = build_model_into(&m, desc);
+  if (rc) return rc;
+  If2Map map;
+  rc = cssm_if2_map_build(desc, &map);
+  if (rc) return rc;
+  const size_t need = 5u + 10u * (size_t)m.d + (size_t)map.n_theta;
+  *count = need;
+  if (!out) return CSSM_OK;
+  if (cap < need) return fail(CSSM_EINVAL_ARG, "cssm_fleet_if2_layout: %zu integers needed, room for %zu", need, cap);
+  out[0] = m.d; out[1] = map.n_theta; out[2] = m.obs_kind; out[3] = m.obs_df; out[4] = map.scale_slot;
+  for (int k = 0; k < m.d; ++k) {
+    const Comp& c = m.comp[k];
+    int32_t* o = out + 5 + 10 * k;
+    o[0] = c.kind; o[1] = c.leaf; o[2] = c.idx; o[3] = c.f_kind; o[4] = c.period;
+    for (int fld = 0; fld < 5; ++fld) o[5 + fld] = map.slot[k][fld];
+  }
+  for (int j = 0; j < map.n_theta; ++j) out[5 + 10 * m.d + j] = map.ivp[j];
   return CSSM_OK;
 }
 

@@ -80,6 +80,18 @@ struct HostModel {
   uint64_t n_global = 0, seed = 0;   // (build_rec: sampleOne's index, the Philox key of the resampling uniform)
 };
 
+// (cssm_fleet_if2, EXTENSION) Where a particle's own parameter vector -- the flattened STORED vector, cssm_desc_flatten's order -- holds
+// what a component reads: slot[k][CSSM_FIELD_*] (-1: the component's SDE has no such field; the transform is cssm_constrain's, by kind
+// and field), the leftmost leaf's scale, and which slots only feed the initial draw (m0, c0).  Host-built (cssm_if2_map_build), passed
+// to k_fleet_if2 by value.
+#define CSSM_IF2_MAX_THETA 81   /* 16 components x 5 fields + the scale */
+struct If2Map {
+  int16_t slot[CSSM_MAX_DIM][5];
+  int16_t scale_slot, n_theta;
+  uint8_t ivp[CSSM_IF2_MAX_THETA + 3];
+};
+int cssm_if2_map_build(const cssm_model_desc* desc, If2Map* map);
+
 // ---- cssm_model.cpp (host only) ----
 // one PMMH chain's state (model/PMMH.scala:68-81): shared by the sequential and the batched driver
 struct cssm_pmmh_chain;

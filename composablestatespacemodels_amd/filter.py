@@ -737,6 +737,48 @@ class NativePfFleet:
         chunks."""
         return self._ms(self.lib.cssm_fleet_smooth_last_ms, 3)
 
+    def if2(self, desc, datas, rw_sd, cooling: float, iters: int, seeds, theta0=None, swarm0=None, first_iter: int = 0, iters_per_launch: int = 0,
+            want_swarm: bool = False, want_last: bool = False):
+        """cssm_fleet_if2 (an EXTENSION: the reference has no likelihood maximiser): iterated filtering, a search per series from the rows
+        of ``theta0[S, n_theta]`` (or the swarm ``swarm0[S, n_theta, N]`` of an earlier call, continued at ``first_iter``) under
+        ``seeds``; ``desc`` is the descriptor the rows flatten, ``rw_sd[n_theta]`` the random-walk standard deviations, ``cooling`` the
+        factor they shrink by over 50 iterations.  Returns a dict: ``theta_mean[S, iters, n_theta]``, ``ll[S, iters]``, ``rc[S]``; with
+        ``want_swarm`` also ``swarm[S, n_theta, N]``; with ``want_last`` the last iteration's ``ll_t`` / ``ess_t`` (per series),
+        ``x[S, d, N]`` and ``anc[S, N]``.  The fleet's clouds and clocks are not touched."""
+        if len(datas) != self.S:
+            raise ValueError("one (t, y, has) triple per series")
+        off, t, y, has = self.pack(datas, allow_empty=True)
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        if theta0 is None and swarm0 is None:
+            raise ValueError("theta0 (a starting row per series) or swarm0 (a whole swarm) is needed")
+        nt = self.n_theta
+        th0 = None if theta0 is None else np.ascontiguousarray(theta0, dtype=np.float64).reshape(self.S, nt)
+        sw0 = None if swarm0 is None else np.ascontiguousarray(swarm0, dtype=np.float64).reshape(self.S, nt, self.n)
+        sd = np.ascontiguousarray(rw_sd, dtype=np.float64)
+        if sd.shape != (nt,):
+            raise ValueError(f"rw_sd must hold n_theta = {nt} standard deviations")
+        keys = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
+        if len(keys) != self.S:
+            raise ValueError("one seed per series")
+        iters = int(iters)
+        out = {"theta_mean": np.full((self.S, max(iters, 0), nt), np.nan), "ll": np.full((self.S, max(iters, 0)), np.nan),
+               "rc": np.zeros(self.S, dtype=np.int32)}
+        swarm = np.zeros((self.S, nt, self.n)) if want_swarm else None
+        ll_t, ess_t = (np.zeros(max(R, 1)), np.zeros(max(R, 1), dtype=np.int32)) if want_last else (None, None)
+        x, anc = (np.zeros((self.S, self.d, self.n)), np.zeros((self.S, self.n), dtype=np.uint32)) if want_last else (None, None)
+        _abi.check(self.lib.cssm_fleet_if2(self._h, desc.ptr(), _p(th0), _p(sw0), nt, _p(sd), float(cooling), int(first_iter), iters,
+                                           int(iters_per_launch), _p(keys), _p(off), _p(t), _p(y), _p(has), _p(out["theta_mean"]), _p(out["ll"]),
+                                           _p(swarm), _p(ll_t), _p(ess_t), _p(x), _p(anc), _p(out["rc"])))
+        if want_swarm:
+            out["swarm"] = swarm
+        if want_last:
+            out.update(ll_t=self._split(off, ll_t[:R]), ess_t=self._split(off, ess_t[:R]), x=x, anc=anc)
+        return out
+
+    def if2_last_ms(self) -> float:
+        """Device time (HIP events) of the launches of the last ``if2``, ms."""
+        return self._ms(self.lib.cssm_fleet_if2_last_ms, 1)[0]
+
     def pmmh_last_split(self):
         """cssm_fleet_pmmh_last_split: milliseconds of the last ``cssm_fleet_pmmh_run`` on this fleet, summed over its iterations --
         (propose + set_params + reseed, record building, upload, kernel, decide) and the iterations counted."""

@@ -1242,6 +1242,136 @@ CSSM_HD double cssm_back_uniform(uint64_t seed, uint32_t m, uint32_t s) {
   return cssm_u01(b.v[0], b.v[1]);
 }
 
+/* ------------------------------------------------------------------ iterated filtering (EXTENSION) */
+
+/*
+ * EXTENSION (not a restatement of running reference code: the reference has no likelihood maximiser).  IF2 of Ionides, Nguyen,
+ * Atchade, Stoev and King (PNAS 2015; `mif2` of the R package pomp) for a fleet: cssm_fleet_if2, one search per series.  Nothing above
+ * this line changes and the contract version stays what it is.  This section states one search so that a sequential program written
+ * from this header reproduces the device bit for bit (tests/cpp/if2_twin.c is that program).
+ *
+ * Parameter vector.  A particle carries the flattened STORED (unconstrained) vector of the model in cssm_desc_flatten order, n_theta
+ * slots: per leaf [scale] m0.. c0.. [mu.. | phi.. mu..] sigma...  Component k of a leaf (index idx within it) reads field F from slot
+ * first_F + idx % n_F (cyclic repetition of short vectors).  Slots of m0 and c0 only feed the initial draw ("ivp" slots).
+ *
+ * Iteration m = 0, 1, .. of a search with user seed `seed`, swarm theta[j][i] (slot j, particle i < N), records r = 0 .. T-1:
+ *   key   = cssm_derive_key(seed, m + 1)                                   (cssm_pf_run_key: as PMMH keys its filters)
+ *   sdc_j = rw_sd[j] * cool[m],  cool[m] = c^(m / 50) handed in by the host (one array for the device and the twin)
+ *   perturbation `when` (0: before x0 is drawn; r + 1: before record r) of slot j of particle i:
+ *       theta = cssm_if2_perturb(theta, sdc_j, cssm_if2_normal(key, i, when, j, tab))        = theta + sdc_j * z
+ *     when = 0 perturbs every slot, when = r + 1 every slot that is not an ivp slot -- unobserved records included.  rw_sd[j] == 0
+ *     leaves the slot's bits untouched and needs no draw; the normal of slot j does not depend on which other slots are free.
+ *   x0[c] = cssm_sqrt(C0_c) * z_c + M0_c, z = the initial draw of the filter under `key` (CSSM_STREAM_INIT, particle i, step 0), x is
+ *     drawn anew in every iteration; ancestors = the identity.
+ *   record r (observation index `step` = r, dt = t_r - t_{r-1}, t_{-1} = the smallest time of the series), particle i with ancestor a:
+ *     theta[.][i] = perturbed theta[.][a];  constrained values by cssm_constrain (the expressions of the descriptor path), the
+ *     observation scale sd = cssm_exp(stored scale), raw = the stored scale;
+ *     coefficients p0..p3 of every component from (kind, MU, PHI, SIGMA, dt) by the filter's coefficient function (cssm_sde_coef), the
+ *     transition by the filter's statement (transition_step) on x[.][a] with the normals of (key, particle i, step r, CSSM_STREAM_STEP);
+ *     unobserved record: nothing else happens (ancestors = the identity, ll and ess stay).
+ *     log-weight lw_i = cssm_obs_logdens(kind, cssm_obs_y(kind, y), c, cdf, gamma), c / cdf = cssm_obs_consts(kind, y,
+ *       cssm_obs_ypart(kind, y, df), sd, raw, df), gamma = f(x, t_r) as the filter forms it.  A NaN lw_i counts as -inf (weight 0): a
+ *       perturbed parameter may be bad for one particle without ending the search.
+ *     level: c_i = cssm_ref_level(kind, y, sd_i, df) (kinds 1 and 6; for every other kind it does not depend on the particle), NaN
+ *       counted as -inf; ref = cssm_ref_choose(max_i c_i, max_i lw_i), the maxima under the order of cssm_order_key.  max_i lw_i not
+ *       finite, or a zero sum of weights: the search ENDS here (CSSM_ENONFINITE) -- no particle of the record has a usable weight.
+ *     w_i = cssm_exp_le0(cssm_min_c(lw_i - ref, CSSM_REF_BELOW)), S = sum cssm_fix_from_unit(w_i), S2 = sum cssm_fix_from_unit(w_i w_i)
+ *       (exact), ll += ref + cssm_log(cssm_fix_to_double(S) / N), ess as the filter's, systematic resampling as the filter's with
+ *       u = cssm_u01 of Philox(key, 0, r, CSSM_STREAM_U, 0).  The next record reads theta and x through the ancestors.
+ *   after the last record: swarm[j][i] = theta[j][anc[i]] (the starting swarm of iteration m + 1; x is dropped),
+ *     mean_j = s_0^L / N with s_i^0 = swarm[j][i], cnt_0 = N; s_i^{l+1} = s_{2i}^l + (2i + 1 < cnt_l ? s_{2i+1}^l : 0.0),
+ *     cnt_{l+1} = ceil(cnt_l / 2), L the first level with cnt_L = 1 -- a pairwise tree over the particle index alone: block size and
+ *     wave mapping cannot matter.  ll of the iteration is the perturbed filter's estimate, a diagnostic.
+ */
+/* Tag 12 (0 .. 11 are taken; written in parentheses as CSSM_STREAM_BACK is, pinned by tests/test_fleet_if2_host.py).  The next free tag is 13. */
+#define CSSM_STREAM_IF2 (12u)  /* the perturbation normal of slot `pair * 2 + element` of particle `id` at perturbation `step` */
+
+/* Constraint transforms of the SDE constructors (model/Sde.scala:70-73,99-102,133-137; SdeParameters.scala:214-216), per stored field:
+ * 0 = m0, 1 = c0, 2 = mu, 3 = phi, 4 = sigma; kind = CSSM_SDE_* (0 Brownian, 1 generalised Brownian, 2 OU, 3 Euler affine). */
+#define CSSM_FIELD_M0 0
+#define CSSM_FIELD_C0 1
+#define CSSM_FIELD_MU 2
+#define CSSM_FIELD_PHI 3
+#define CSSM_FIELD_SIGMA 4
+CSSM_HD double cssm_logistic(double x) { return 1.0 / (1.0 + cssm_exp(-x)); }
+CSSM_HD double cssm_constrain(int kind, int field, double v) {
+  switch (field) {
+    case CSSM_FIELD_C0: return cssm_exp(v);
+    case CSSM_FIELD_PHI: return (kind == 2) ? cssm_logistic(v) : v;
+    case CSSM_FIELD_SIGMA: return (kind == 3) ? v : cssm_exp(v);
+    default: return v;
+  }
+}
+
+/* The constants of the observation density (kinds: CSSM_OBS_* of cssm_pf.h).  cssm_obs_ypart depends on (y, df) alone and may be formed
+ * once per observation; cssm_obs_consts adds what depends on the scale: sd = cssm_exp(stored scale), raw = the stored scale. */
+CSSM_HD double cssm_obs_y(int kind, double y) { return (kind == 0 || kind == 3 || kind == 4) ? (double)(long long)y : y; }
+CSSM_HD double cssm_obs_ypart(int kind, double y, double df) {
+  switch (kind) {
+    case 0: case 3: case 4: return cssm_lgamma_kp1((long long)y);                                      /* lgamma(k + 1) */
+    case 6: return cssm_lgamma((df + 1.0) / 2.0) - cssm_lgamma(df / 2.0) - 0.5 * cssm_log(3.14159265358979311600 * df);
+    case 7: return cssm_log(y);
+    default: return 0.0;
+  }
+}
+CSSM_HD void cssm_obs_consts(int kind, double y, double ypart, double sd, double raw, double df, double* c, double* cdf) {
+  c[0] = 0.0; c[1] = 0.0; c[2] = 0.0; c[3] = 0.0; *cdf = 0.0;
+  switch (kind) {
+    case 0: c[0] = ypart; break;                                             /* Poisson: c0 = lgamma(k+1) */
+    case 1: c[0] = cssm_log(2.5066282746310002 * sd); c[1] = sd; break;      /* Gaussian: c0 = log(sqrt(2 pi) sd), c1 = sd */
+    case 3: {                                                                /* NegBin: c0 = lgamma(size+k) - lgamma(k+1) - lgamma(size), c1 = size */
+      const double k = (double)(long long)y;
+      c[0] = cssm_lgamma(sd + k) - ypart - cssm_lgamma(sd); c[1] = sd;
+      break;
+    }
+    case 4: {                                                                /* ZIP: c0 = p, c1 = -log(1 + exp(v)), c2 = lgamma(k+1) */
+      const double ev = cssm_exp(raw);
+      c[0] = ev / (1.0 + ev); c[1] = -cssm_log(1.0 + ev); c[2] = ypart;
+      break;
+    }
+    case 6: c[0] = ypart; c[1] = sd; c[2] = (df + 1.0) / 2.0; c[3] = 1.0 / sd; *cdf = df; break;   /* Student-t: -logNormalizer, v, (df+1)/2, 1/v */
+    case 7: c[0] = ypart; break;                                             /* Beta: c0 = log(y) */
+    default: break;                                                          /* Bernoulli, LGCP: no constants */
+  }
+}
+/* dataLikelihood(gamma, y) on those constants, y = cssm_obs_y(kind, .): the filter's log-density statement for statement
+ * (model/Model.scala:155-160,186-195,252-258,273,298-307,318-336,349-352); the tests hold the two equal bit for bit. */
+CSSM_HD double cssm_obs_logdens(int kind, double y, const double* c, double cdf, double g) {
+  switch (kind) {
+    case 0: return -cssm_exp(g) + y * g - c[0];
+    case 1: { const double dd = (y - g) / c[1]; return -(dd * dd) / 2.0 - c[0]; }
+    case 3: { const double size = c[1], mu = cssm_exp(g); return c[0] + size * cssm_log(size / (mu + size)) + y * cssm_log(mu / (mu + size)); }
+    case 4:
+      if (y == 0.0) return cssm_log(c[0] + (1.0 - c[0]) * cssm_exp(-cssm_exp(g)));
+      return ((c[1] + y * g) - cssm_exp(g)) - c[2];
+    case 5: {
+      const double link = (g > 6.0) ? 1.0 : ((g < -6.0) ? 0.0 : 1.0 / (1.0 + cssm_exp(-g)));
+      if (y == 1.0) return (link == 0.0) ? -1e99 : cssm_log(link);
+      return (link == 1.0) ? -1e99 : cssm_log(1.0 - link);
+    }
+    case 6: { const double x = (y - g) / c[1]; return c[3] * (c[0] - c[2] * cssm_log(1.0 + (x * x) / cdf)); }
+    default: return (cssm_exp(-g) - 1.0) * c[0] - g;
+  }
+}
+
+/* the perturbation: normal number j of the stream (key, particle i, perturbation `when`, CSSM_STREAM_IF2) -- element j & 1 of pair j >> 1 */
+CSSM_HD double cssm_if2_normal(uint64_t key, uint64_t i, uint32_t when, uint32_t j, const double* tab) {
+  double z0, z1;
+  cssm_normal_pair_of(key, i, when, CSSM_STREAM_IF2, j >> 1, tab, &z0, &z1);
+  return (j & 1u) ? z1 : z0;
+}
+CSSM_HD double cssm_if2_perturb(double theta, double sdc, double z) { return theta + sdc * z; }
+/* a particle's level candidate: NaN counts as -inf */
+CSSM_HD double cssm_if2_level(int kind, double y, double sd, double df) {
+  const double c = cssm_ref_level(kind, y, sd, df);
+  return (c == c) ? c : -cssm_inf();
+}
+/* the resampling uniform of record `step` under the iteration's key (the filter's: cssm_build_rec) */
+CSSM_HD double cssm_if2_uniform(uint64_t key, uint32_t step) {
+  const cssm_u32x4 b = cssm_philox_draw(key, 0, step, CSSM_STREAM_U, 0);
+  return cssm_u01(b.v[0], b.v[1]);
+}
+
 #ifdef __cplusplus
 }
 #endif

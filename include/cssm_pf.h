@@ -1269,6 +1269,53 @@ int cssm_fleet_smooth(cssm_fleet* f, const uint64_t* off, const double* t, const
 /* ms3 = device time of the forward launch, of the backward simulation and of the row summaries of the last cssm_fleet_smooth, each summed
  * over its chunks (HIP events on the fleet's stream).  CSSM_ESTATE before the first.  The array holds THREE doubles. */
 int cssm_fleet_smooth_last_ms(cssm_fleet* f, double* ms3);
+/* ---- EXTENSION (not a restatement of running reference code: the reference has no likelihood maximiser; examples/DetermineParameters.scala
+ * assumes the starting value of its chains): maximum likelihood by iterated filtering -- IF2 of Ionides, Nguyen, Atchade, Stoev and King
+ * (PNAS 2015), the `mif2` of the R package pomp.  S independent searches, one per series of the fleet and one workgroup each: every
+ * particle carries its own parameter vector (the flattened STORED vector, cssm_desc_flatten order, n_theta slots), which random-walks
+ * with a shrinking step before the initial draw and before every record and is resampled together with the state; after a few dozen
+ * passes over the data the swarm sits at the maximum of the likelihood.  All n_iters iterations x T_k records of a search run inside
+ * ONE launch (k_fleet_if2): transition coefficients and density constants are formed per particle on the device.  The arithmetic is
+ * part of the numerics contract (include/cssm_numerics.h, "iterated filtering").
+ *
+ * The fleet is only LENT (device, stream, contract table, N, structure): clouds, clocks, keys, windows and parameters of its series stay
+ * as they were, as cssm_fleet_smooth leaves them.  `desc` gives the structure (the fleet's, else CSSM_EINVAL_DESC) -- its parameter values
+ * are not read.  Start: theta0[S][n_theta], one row per series that every particle starts from, or swarm0[S][n_theta][N] (wins when both
+ * are given), the swarm_out of an earlier call.  The call runs iterations m = first_iter .. first_iter + n_iters - 1 of the search:
+ * iteration m runs under cssm_pf_run_key(seeds[k], m + 1) and cools by cool_m = cooling_fraction_50^(m / 50) (cssm_fleet_if2_cooling),
+ * so a search continued from swarm_out with first_iter = the iterations done so far is bit for bit the uninterrupted one.  rw_sd[n_theta] >= 0, finite:
+ * the random-walk standard deviation per slot at m = 0; 0 keeps a slot's bits.  The slots of m0 and c0 are perturbed once per iteration,
+ * before x0 is drawn (pomp's ivp), all others before x0 and before every record.  off / t / y / has_obs: the ragged data of
+ * cssm_fleet_ll_filter.  iters_per_launch bounds the iterations one launch runs (0: all of them); the result does not depend on it.
+ *
+ * Outputs: theta_mean[S][n_iters][n_theta] (the swarm's mean per slot after each iteration of the call, a pairwise tree over the particle index),
+ * ll[S][n_iters] (the perturbed filter's log-likelihood estimate, a diagnostic -- not the likelihood at the mean), rc_out[S]; optional
+ * (may be NULL) swarm_out[S][n_theta][N] (the final swarm), and of the LAST iteration ll_t / ess_t (per record, off's layout),
+ * x_out[S][d][N] (the cloud the last record proposed) and anc_out[S][N] (the ancestors that resampled it).  A record none of whose
+ * particles has a usable weight ends that series' search: rc_out[k] = CSSM_ENONFINITE, its rows from the failing iteration on read NaN,
+ * its swarm_out is the swarm that iteration started from, its last-iteration outputs read NaN / -1 / 0xffffffff; the others run on, bit
+ * for bit what they are without it.  (A NaN log-weight of one particle is weight zero, not a failure.)  A series without records is
+ * untouched: rc_out[k] = CSSM_OK, its rows read NaN.
+ *
+ * Refused before the fleet is looked at (CSSM_EINVAL_ARG unless said): null desc / rw_sd / seeds / off / theta_mean / ll / rc_out / t / y,
+ * theta0 and swarm0 both null, off[0] != 0, a negative or non-finite rw_sd, n_iters outside [1, 1000000] or first_iter + n_iters beyond 2^31, cooling_fraction_50 outside
+ * (0, 1], an invalid descriptor or the LGCP observation model (CSSM_EINVAL_DESC), n_theta other than the descriptor flattens to (at most
+ * 81), an LGCP fleet (by name), a null fleet; then a decreasing off and another structure than the fleet's (CSSM_EINVAL_DESC). */
+int cssm_fleet_if2(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, const double* swarm0, size_t n_theta,
+                   const double* rw_sd, double cooling_fraction_50, uint32_t first_iter, uint32_t n_iters, uint32_t iters_per_launch,
+                   const uint64_t* seeds, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                   double* theta_mean, double* ll, double* swarm_out, double* ll_t, int32_t* ess_t, double* x_out,
+                   uint32_t* anc_out, int* rc_out);
+/* *ms = device time of the launches of the last cssm_fleet_if2 (HIP events on the fleet's stream); CSSM_ESTATE before the first. */
+int cssm_fleet_if2_last_ms(cssm_fleet* f, double* ms);
+/* No device: cool[q] = cooling_fraction_50^((first_iter + q) / 50), q < n_iters, the array the call cools by (whoever restates a search
+ * takes it from here, not from another pow). */
+int cssm_fleet_if2_cooling(double cooling_fraction_50, uint32_t first_iter, uint32_t n_iters, double* cool);
+/* Diagnostic, no device: where the flattened vector of `desc` holds what each latent component reads.  out = d, n_theta, obs_kind,
+ * obs_df, the scale's slot (-1: none); per component 10 integers: sde_kind, leaf, index in the leaf, f_kind, period, then the slots of
+ * m0, c0, mu, phi, sigma (-1: the SDE has no such field); then n_theta flags: 1 = the slot only feeds the initial draw.  *count = the
+ * integers that is (5 + 10 d + n_theta); out may be NULL to ask for it. */
+int cssm_fleet_if2_layout(const cssm_model_desc* desc, int32_t* out, size_t cap, size_t* count);
 /* ---- fixed-lag interpolation of a live fleet (FilterInterpolate as the stream it is: ParticleFilter.interpolate, model/
  * ParticleFilter.scala:281-310 -- one stepInterpolate per observation, every element carrying the paths that survive to that moment;
  * examples/Interpolate.scala: once data resumes behind a gap, the surviving lineages fill it).
