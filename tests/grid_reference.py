@@ -34,6 +34,22 @@ The error bound: the same computation with every spacing divided by 1.5; the bou
 The smoothers: the fixed-interval smoothing distributions p(x_s | y_1..T) that the rows of interpolate converge to (row 0 the initial
 state at min(t), row s+1 the state at t[s]) -- `rts` in closed form for the Gaussian-observation models, `grid_smoother` /
 `smoother_reference` by a backward pass over the grids and matrices the forward pass built, with the same error-bound conventions.
+
+The predictive truth: what a forecast converges to (ParticleFilter.getForecast, :368-382: the cloud moved by stepFunction(t - s.t),
+gamma = f(x, t), eta = link(gamma), an observation drawn from observation(gamma); horizon h continues horizon h - 1).
+* `compose`: the transitions over several horizons compose in closed form into one (A, b, q) per component from the cloud's time;
+  a repeated time adds the identity, so a later horizon's cumulative q stays positive.
+* `predictive`: the filtering density on its grid convolved with that Gaussian.  Every statistic is then an integral of a SMOOTH
+  function against the grid -- P(x_k <= c) = sum_j p_j Phi((c - A_k x_jk - b_k) / sqrt(q_k)), likewise gamma = H(t_h) . x (at
+  d > 1 the grid's nodes are projected onto gamma and binned at 1/64 of the noise sd) -- which is why it is exact where a histogram
+  of the grid would not be.  A horizon at the cloud's own time (q = 0) at the head of the list is refused by name: the integrand is
+  not smooth there, and the filtering distribution itself is what GridResult holds.  Row 0 (the prior) is Gaussian and exact at any dt.
+* `mixture_predictive`: M pairs (theta_m, x_m) at t0 are an M-component Gaussian mixture with per-pair (A_m, b_m, q_m): closed
+  form at any latent dimension; with a variance per pair it is the prior.
+* links and observation laws (`link_of`, `obs_mean_given`, `obs_cdf_given`) are written from Model.scala's leaves with
+  scipy.stats, in the parametrisations of log_potential; E[eta], E[Y] and P(Y <= c) integrate them against gamma's mixture on
+  a uniform axis.  Continuous kinds have a quantile function (the root of the mixture CDF), counts their CDF at the integers.
+* the error bound is the module's: everything again at spacing / 1.5 (grid, binning and gamma axis), the absolute difference.
 """
 from __future__ import annotations
 
@@ -533,3 +549,401 @@ def smoother_reference(model, t, y, has=None, budget=POINT_BUDGET) -> SmoothResu
         fb.lost = max(fa.lost, fb.lost)
         _SMOOTH_CACHE[key] = b
     return _SMOOTH_CACHE[key]
+
+
+# ------------------------------------------------------------------------------------------------ the predictive truth
+# Written from Model.scala's link / observation of each leaf (:145-345) and ParticleFilter.getForecast (:368-382): the state is
+# moved by stepFunction(t - s.t), gamma = f(x, t), eta = link(gamma), the observation is drawn from observation(gamma) -- with
+# scipy.stats for every law, in the parametrisations of log_potential above and tests/golden/make_golden.py.
+COUNT_KINDS = ("poisson", "negbin", "zip", "bernoulli")
+
+
+def link_of(obs, gamma):
+    """eta = link(gamma) of the leftmost leaf, elementwise."""
+    gamma = np.asarray(gamma, dtype=np.float64)
+    if obs in ("poisson", "negbin", "zip"):
+        return np.exp(gamma)
+    if obs in ("linear", "seasonal", "studentt"):
+        return gamma
+    if obs == "bernoulli":
+        return np.where(gamma > 6, 1.0, np.where(gamma < -6, 0.0, expit(gamma)))
+    if obs == "beta":
+        return np.exp(-gamma)
+    raise ValueError(obs)
+
+
+def link_decreases(obs):
+    return obs == "beta"
+
+
+def obs_mean_given(obs, scale, df, eta):
+    """E[Y | eta], elementwise."""
+    if obs in ("poisson", "negbin", "bernoulli", "linear", "seasonal"):
+        return eta
+    if obs == "studentt":
+        if df <= 1:
+            raise ValueError("a Student-t with df <= 1 has no mean")
+        return eta
+    if obs == "zip":
+        return (1.0 - expit(scale)) * eta
+    if obs == "beta":                                            # Beta(eta, scale): the stored scale as it is
+        return eta / (eta + scale)
+    raise ValueError(obs)
+
+
+def obs_cdf_given(obs, scale, df, eta, c):
+    """P(Y <= c | eta) by scipy.stats, broadcasting eta against c."""
+    from scipy import stats
+    if obs == "poisson":
+        return stats.poisson.cdf(c, eta)
+    if obs in ("linear", "seasonal"):
+        return stats.norm.cdf(c, eta, math.exp(scale))
+    if obs == "studentt":
+        return stats.t.cdf(c, df, loc=eta, scale=math.exp(scale))
+    if obs == "negbin":
+        size = math.exp(scale)
+        return stats.nbinom.cdf(c, size, size / (size + eta))
+    if obs == "zip":
+        p = expit(scale)
+        return p * (np.asarray(c) >= 0) + (1.0 - p) * stats.poisson.cdf(c, eta)
+    if obs == "bernoulli":
+        return stats.bernoulli.cdf(c, eta)
+    if obs == "beta":
+        return stats.beta.cdf(c, eta, scale)
+    raise ValueError(obs)
+
+
+def compose(spec: Spec, t0, times):
+    """The cumulative (A, b, q) per component from t0 to each horizon, horizon h continuing horizon h - 1 (which matters for the
+    Euler-Maruyama step, whose two steps are not one step of the sum); a repeated time adds the identity."""
+    d = spec.d
+    A, b, q = np.ones(d), np.zeros(d), np.zeros(d)
+    now, out = float(t0), []
+    for th in times:
+        dt = float(th) - now
+        if dt < 0:
+            raise ValueError("horizon times must not decrease, nor precede the cloud's time")
+        if dt != 0:
+            A1, b1, q1 = spec.transition(dt)
+            A, b, q = A1 * A, A1 * b + b1, A1 * A1 * q + q1
+        now = float(th)
+        out.append((A.copy(), b.copy(), q.copy()))
+    return out
+
+
+class GaussMix:
+    """A one-dimensional Gaussian mixture sum_j w_j N(mu_j, var_j), every var_j > 0."""
+
+    def __init__(self, mu, w, var):
+        self.mu = np.atleast_1d(np.asarray(mu, dtype=np.float64))
+        self.w = np.broadcast_to(np.asarray(w, dtype=np.float64), self.mu.shape).copy()
+        self.sd = np.sqrt(np.broadcast_to(np.asarray(var, dtype=np.float64), self.mu.shape))
+        if not np.all(self.sd > 0):
+            raise ValueError("dt = 0 predictive: a component without transition noise is not a smooth integrand")
+
+    def mean(self):
+        return float((self.w * self.mu).sum() / self.w.sum())
+
+    def cdf(self, c):
+        c = np.asarray(c, dtype=np.float64)
+        return (self.w * ndtr((c[..., None] - self.mu) / self.sd)).sum(axis=-1) / self.w.sum()
+
+    def pdf(self, c):
+        z = (np.asarray(c, dtype=np.float64)[..., None] - self.mu) / self.sd
+        return (self.w / self.sd * np.exp(-0.5 * z * z)).sum(axis=-1) / (math.sqrt(2 * math.pi) * self.w.sum())
+
+    def span(self, k=SD_COVER):
+        return float(np.min(self.mu - k * self.sd)), float(np.max(self.mu + k * self.sd))
+
+    def quantile(self, p):
+        from scipy.optimize import brentq
+        lo, hi = self.span()
+        return float(brentq(lambda c: float(self.cdf(c)) - p, lo, hi, xtol=1e-13, rtol=1e-14))
+
+    @staticmethod
+    def join(parts, weights):
+        return GaussMix(np.concatenate([m.mu for m in parts]), np.concatenate([wt * m.w / m.w.sum() for m, wt in zip(parts, weights)]),
+                        np.concatenate([m.sd ** 2 for m in parts]))
+
+
+@dataclass
+class _Group:
+    """A share of the predictive under one parameter set: its weight, its observation law and its mixture of gamma."""
+    weight: float
+    obs: str
+    scale: float
+    df: int
+    gamma: GaussMix
+
+
+class Horizon:
+    """The exact predictive at one horizon: a Gaussian mixture per state component, and per parameter set a mixture of gamma that
+    the link and the observation law are integrated against on a uniform axis (spacing 1/8 of the smallest component sd, divided
+    by `refine`: the integrand is smooth, so the sum converges faster than any power of the spacing)."""
+
+    def __init__(self, state: List[GaussMix], groups: List[_Group], refine=1.0):
+        self.state, self.groups, self.refine = state, groups, refine
+        tot = sum(g.weight for g in groups)
+        for g in groups:
+            g.weight = g.weight / tot
+        self.obs = groups[0].obs
+        self.gamma = groups[0].gamma if len(groups) == 1 else GaussMix.join([g.gamma for g in groups], [g.weight for g in groups])
+        self._quad = None
+
+    def quad(self):
+        """per group (gamma axis, probability of each node)"""
+        if self._quad is None:
+            self._quad = []
+            for g in self.groups:
+                lo, hi = g.gamma.span(10.0)
+                h = float(np.min(g.gamma.sd)) / 8.0 / self.refine
+                n = int(math.ceil((hi - lo) / h)) + 1
+                if n > 400_000:
+                    raise ValueError("the gamma axis of this predictive would need %d nodes" % n)
+                gg = lo + h * np.arange(n)
+                pg = np.zeros(n)
+                for i in range(0, n, 4096):                       # (blocks: the pdf is a [nodes, components] array)
+                    pg[i:i + 4096] = g.gamma.pdf(gg[i:i + 4096]) * h
+                self._quad.append((gg, pg))
+        return self._quad
+
+    def state_mean(self):
+        return np.array([m.mean() for m in self.state])
+
+    def state_quantile(self, p):
+        p = np.broadcast_to(np.asarray(p, dtype=np.float64), (len(self.state),))
+        return np.array([m.quantile(float(pk)) for m, pk in zip(self.state, p)])
+
+    def gamma_mean(self):
+        return self.gamma.mean()
+
+    def eta_mean(self):
+        return float(sum(g.weight * float((pg * link_of(g.obs, gg)).sum()) for g, (gg, pg) in zip(self.groups, self.quad())))
+
+    def eta_quantile(self, p):
+        return float(link_of(self.obs, self.gamma.quantile(1.0 - p if link_decreases(self.obs) else p)))
+
+    def obs_mean(self):
+        return float(sum(g.weight * float((pg * obs_mean_given(g.obs, g.scale, g.df, link_of(g.obs, gg))).sum())
+                         for g, (gg, pg) in zip(self.groups, self.quad())))
+
+    def obs_cdf(self, c):
+        c = np.atleast_1d(np.asarray(c, dtype=np.float64))
+        out = np.zeros(c.shape)
+        for g, (gg, pg) in zip(self.groups, self.quad()):
+            keep = pg > 0
+            F = obs_cdf_given(g.obs, g.scale, g.df, link_of(g.obs, gg[keep])[None, :], c[:, None])
+            out += g.weight * (F * pg[keep][None, :]).sum(axis=1)
+        return out
+
+    def obs_quantile(self, p):
+        """continuous kinds: the root of the mixture CDF"""
+        from scipy.optimize import brentq
+        if self.obs in COUNT_KINDS:
+            raise ValueError("a count has an integer quantile: obs_int_quantile")
+        if self.obs == "beta":
+            lo, hi = 0.0, 1.0
+        else:
+            lo, hi = self.gamma.span()
+            w = 10.0 * math.exp(self.groups[0].scale)
+            while float(self.obs_cdf(lo)[0]) > p:
+                lo -= w; w *= 2
+            w = 10.0 * math.exp(self.groups[0].scale)
+            while float(self.obs_cdf(hi)[0]) < p:
+                hi += w; w *= 2
+        return float(brentq(lambda c: float(self.obs_cdf(c)[0]) - p, lo, hi, xtol=1e-12, rtol=1e-13))
+
+    def obs_int_cdf(self, kmax=None):
+        """counts: (integers 0..K, their CDF), K the first integer whose CDF passes 1 - 1e-5 (or kmax): every probability a test
+        looks up lies below 0.9995 + its margin"""
+        K = 64 if kmax is None else max(int(kmax), 1)
+        while True:
+            k = np.arange(K + 1)
+            F = self.obs_cdf(k)
+            if kmax is not None or F[-1] >= 1.0 - 1e-5 or self.obs == "bernoulli":
+                break
+            K *= 2
+        if self.obs == "bernoulli":
+            return k[:2], F[:2]
+        if kmax is not None:
+            return k[:kmax + 1], F[:kmax + 1]
+        last = int(np.argmax(F >= 1.0 - 1e-5))
+        return k[:last + 1], F[:last + 1]
+
+    def obs_int_quantile(self, p, table=None):
+        """the exact integer quantile function: the smallest k with P(Y <= k) >= p"""
+        k, F = table if table is not None else self.obs_int_cdf()
+        i = int(np.searchsorted(F, p, side="left"))
+        return int(k[min(i, len(k) - 1)])
+
+
+class Predictive:
+    """The predictive at spacing h (`coarse`) and h / 1.5 (`fine`): every statistic is returned from the finer one together with
+    the absolute difference of the two as its error bound."""
+
+    def __init__(self, times, coarse: List[Horizon], fine: List[Horizon]):
+        self.times, self.coarse, self.fine = np.asarray(times, dtype=np.float64), coarse, fine
+        self.d = len(fine[0].state)
+        self.obs = fine[0].obs
+
+    def _both(self, f):
+        a = np.array([f(h) for h in self.coarse], dtype=np.float64)
+        b = np.array([f(h) for h in self.fine], dtype=np.float64)
+        return b, np.abs(b - a)
+
+    def state_mean(self):                                        # ([H, d], err)
+        return self._both(lambda h: h.state_mean())
+
+    def state_quantile(self, p):
+        return self._both(lambda h: h.state_quantile(p))
+
+    def gamma_mean(self):
+        return self._both(lambda h: h.gamma_mean())
+
+    def eta_mean(self):                                          # ([H], err)
+        return self._both(lambda h: h.eta_mean())
+
+    def eta_quantile(self, p):
+        return self._both(lambda h: h.eta_quantile(p))
+
+    def gamma_quantile(self, p):
+        return self._both(lambda h: h.gamma.quantile(p))
+
+    def obs_mean(self):
+        return self._both(lambda h: h.obs_mean())
+
+    def obs_quantile(self, p):
+        return self._both(lambda h: h.obs_quantile(p))
+
+    def obs_cdf(self, h, c):                                     # ([len(c)], err) at horizon h
+        a, b = self.coarse[h].obs_cdf(c), self.fine[h].obs_cdf(c)
+        return b, np.abs(b - a)
+
+    def obs_int_cdf(self, h):                                    # (integers, CDF, err)
+        k, F = self.fine[h].obs_int_cdf()
+        _, Fa = self.coarse[h].obs_int_cdf(kmax=int(k[-1]))
+        return k, F, np.abs(F - Fa)
+
+
+@dataclass
+class _Row:
+    """A filtering density reduced to what a predictive reads: the axes, the marginal probabilities per axis and the nodes that
+    carry mass (all but 1e-13 of it) as flat indices with their probabilities."""
+    axes: List[np.ndarray]
+    marg: List[np.ndarray]
+    shape: tuple
+    idx: np.ndarray
+    p: np.ndarray
+
+
+_ROWS: Dict[tuple, tuple] = {}
+
+
+def _rows_of(spec, t, y, has, refine, budget):
+    keep = []
+    grid_filter(spec, t, y, has, 0, refine, budget, keep=keep)
+    rows = []
+    for entry in keep:
+        G = _Grid(entry[0], entry[1])
+        marg = []
+        for k in range(spec.d):
+            f = G.marginal(k) * G.h[k]
+            marg.append(f / f.sum())
+        flat = G.p.ravel()
+        idx = np.flatnonzero(flat > flat.max() * 1e-14 / max(1.0, flat.size / 1e3))
+        p = flat[idx]
+        rows.append(_Row(G.axes, marg, G.p.shape, idx.astype(np.int64), p / p.sum()))
+    return rows
+
+
+def filtering_rows(model, t, y, has=None, budget=POINT_BUDGET):
+    """The filtering densities of `reference` (row 0 the initial state, row s + 1 after datum s) at both spacings; cached."""
+    key = _key(model, t, y, has, 0) + (budget,)
+    if key not in _ROWS:
+        spec = spec_of(model)
+        _ROWS[key] = (_rows_of(spec, t, y, has, 1.0, budget), _rows_of(spec, t, y, has, REFINE, budget * REFINE ** spec.d))
+    return _ROWS[key]
+
+
+def _bin(u, w, width):
+    """Weighted points moved onto a uniform axis of the given width, each shared between its two neighbours in proportion
+    (mass and mean are kept; the variance added is at most width^2 / 4)."""
+    lo = float(u.min())
+    pos = (u - lo) / width
+    i = np.floor(pos).astype(np.int64)
+    f = pos - i
+    n = int(i.max()) + 2
+    acc = np.bincount(i, weights=w * (1.0 - f), minlength=n) + np.bincount(i + 1, weights=w * f, minlength=n)
+    nz = np.flatnonzero(acc > 0)
+    return lo + width * nz, acc[nz]
+
+
+def _horizons_from_row(spec: Spec, row: _Row, t_row, times, refine):
+    out = []
+    d = spec.d
+    for (A, b, q), th in zip(compose(spec, t_row, times), times):
+        if not np.all(q > 0):
+            raise ValueError("dt = 0 predictive from a grid: the integrand is not smooth; ask for a later time or the filtering "
+                             "distribution itself (GridResult)")
+        state = [GaussMix(A[k] * row.axes[k] + b[k], row.marg[k], q[k]) for k in range(d)]
+        H = spec.H(float(th))
+        Q = float((H * H * q).sum())
+        if d == 1:
+            gm = GaussMix(H[0] * (A[0] * row.axes[0] + b[0]), row.marg[0], Q)
+        else:
+            sub = np.unravel_index(row.idx, row.shape)
+            u = np.zeros(len(row.idx))
+            for k in range(d):
+                if H[k] != 0.0:
+                    u += H[k] * (A[k] * row.axes[k][sub[k]] + b[k])
+            # (the nodes of the joint grid projected onto gamma: binned at 1/64 of the noise sd, finer with `refine`, so the
+            #  refinement difference bounds the binning as well: its error in a CDF is at most 0.24 width^2 / (8 Q) = 7e-6)
+            mu, w = _bin(u, row.p, math.sqrt(Q) / 64.0 / refine)
+            gm = GaussMix(mu, w, Q)
+        out.append(Horizon(state, [_Group(1.0, spec.obs, spec.scale, spec.df, gm)], refine))
+    return out
+
+
+def predictive(model, t, y, has, times, row=None, budget=POINT_BUDGET) -> Predictive:
+    """The exact predictive distributions at `times` given the records up to row `row` of the filtering rows (default: all of
+    them; row s + 1 is the state after datum s, row 0 the prior at min(t)): the filtering density on its grid convolved with the
+    closed-form transition to each horizon.  Row 0 is the Gaussian prior itself (`mixture_predictive`), at any dt >= 0."""
+    spec = spec_of(model)
+    t = np.asarray(t, dtype=np.float64)
+    if spec.obs == "lgcp":
+        raise ValueError("no forecast for the LGCP")
+    row = len(t) if row is None else row
+    if row == 0:
+        return mixture_predictive([(model, spec.m0, spec.c0)], float(t.min()), times)
+    a, b = filtering_rows(model, t, y, has, budget)
+    t_row = float(t[row - 1])
+    return Predictive(times, _horizons_from_row(spec, a[row], t_row, times, 1.0), _horizons_from_row(spec, b[row], t_row, times, REFINE))
+
+
+def mixture_predictive(pairs, t0, times, weights=None) -> Predictive:
+    """The closed-form predictive of M pairs (model_m, x_m[, var_m]) at t0: per pair the state at a horizon is
+    N(A_m x_m + b_m, A_m^2 var_m + q_m) per component (var_m = 0: a point; the prior: x = m0, var = c0), gamma Gaussian likewise,
+    and the predictive is their mixture (equal weights unless given).  Exact at any latent dimension; only the link and the
+    observation law are integrated numerically (Horizon), which is what the two refinements differ in."""
+    M = len(pairs)
+    weights = np.full(M, 1.0 / M) if weights is None else np.asarray(weights, dtype=np.float64) / np.sum(weights)
+    specs = [spec_of(p[0]) for p in pairs]
+    comps = [compose(s, t0, times) for s in specs]
+    d = specs[0].d
+
+    def build(refine):
+        out = []
+        for h, th in enumerate(times):
+            mus, vs, groups = np.zeros((M, d)), np.zeros((M, d)), []
+            for m, (pair, spec) in enumerate(zip(pairs, specs)):
+                x = np.asarray(pair[1], dtype=np.float64)
+                v0 = np.zeros(d) if len(pair) < 3 else np.asarray(pair[2], dtype=np.float64)
+                A, b, q = comps[m][h]
+                mus[m], vs[m] = A * x + b, A * A * v0 + q
+                H = spec.H(float(th))
+                groups.append(_Group(float(weights[m]), spec.obs, spec.scale, spec.df,
+                                     GaussMix([float(H @ mus[m])], [1.0], [float((H * H * vs[m]).sum())])))
+            state = [GaussMix(mus[:, k], weights, vs[:, k]) for k in range(d)]
+            out.append(Horizon(state, groups, refine))
+        return out
+    return Predictive(times, build(1.0), build(REFINE))
