@@ -43,6 +43,7 @@ CSSM_LGCP_SIM_KEEP_GRID = 1       # cssm_simulate_lgcp: download the grid rows t
 CSSM_STREAM_THIN = 10             # include/cssm_obs_draws.h: the candidates of simLGCP's thinning
 CSSM_STREAM_IF2 = 12              # include/cssm_numerics.h: the perturbation normals of iterated filtering
 IF2_MAX_THETA = 81                # CSSM_IF2_MAX_THETA
+CSSM_FN_EXP_LE0, CSSM_FN_LGAMMA, CSSM_FN_LGAMMA_KP1 = 8, 9, 10   # cssm_contract_eval: the contract functions evaluated per lane
 CSSM_LGCP_PATH_OK, CSSM_LGCP_PATH_NONFINITE, CSSM_LGCP_PATH_TOO_MANY = 0, 1, 2   # a path's status
 
 _dp = C.POINTER(C.c_double)

@@ -964,6 +964,9 @@ __global__ void k_contract_eval(int fn, const double* __restrict__ x, size_t n, 
     else if (fn == CSSM_FN_SINCOS2PI) { double sn, cs; cssm_sincos2pi(v, &sn, &cs); out[2 * i] = sn; out[2 * i + 1] = cs; }
     else if (fn == CSSM_FN_SINCOS_U24) { double sn, cs; cssm_sincos_u24((uint32_t)v, tab, &sn, &cs); out[2 * i] = sn; out[2 * i + 1] = cs; }
     else if (fn == CSSM_FN_SQRT_RADIUS) out[i] = cssm_sqrt_radius(v);
+    else if (fn == CSSM_FN_EXP_LE0) out[i] = cssm_exp_le0(v);
+    else if (fn == CSSM_FN_LGAMMA) out[i] = cssm_lgamma(v);
+    else if (fn == CSSM_FN_LGAMMA_KP1) out[i] = cssm_lgamma_kp1((long long)v);
     else { const cssm_u128 q = cssm_fix_from_double(v); out[2 * i] = cssm_u2d(q.lo); out[2 * i + 1] = cssm_u2d(q.hi); }
   }
 }
@@ -991,7 +994,8 @@ extern "C" int cssm_contract_eval(int device, int fn, const double* x, size_t n,
     if (d < 1 || d > CSSM_MAX_DIM) return fail(CSSM_EINVAL_ARG, "d out of range");
     np = n_out / d; need = np * d;
     if (np < 1) return fail(CSSM_EINVAL_ARG, "out is too small");
-  } else if ((fn < CSSM_FN_EXP || fn > CSSM_FN_FIX) && fn != CSSM_FN_SINCOS_U24 && fn != CSSM_FN_SQRT_RADIUS) return fail(CSSM_EINVAL_ARG, "unknown contract function %d", fn);
+  } else if ((fn < CSSM_FN_EXP || fn > CSSM_FN_FIX) && fn != CSSM_FN_SINCOS_U24 && fn != CSSM_FN_SQRT_RADIUS &&
+             fn != CSSM_FN_EXP_LE0 && fn != CSSM_FN_LGAMMA && fn != CSSM_FN_LGAMMA_KP1) return fail(CSSM_EINVAL_ARG, "unknown contract function %d", fn);
   if (n_out < need) return fail(CSSM_EINVAL_ARG, "out holds %zu doubles, %zu needed", n_out, need);
   CssmTemps tmp;
   double *dx = nullptr, *dout = nullptr, *dtab = nullptr;

@@ -919,7 +919,8 @@ CSSM_HD void cssm_normal_pair_of(uint64_t seed, uint64_t stream, uint32_t step, 
 
 /*
  * log(k!) for the Poisson density (model/Model.scala:273, breeze Poisson.logProbabilityOf).
- * It depends only on the observation, so it is evaluated once per observation on the host.
+ * It depends only on the observation, so a filter evaluates it once per observation on the host (the
+ * IF2 kernel per lane: cssm_obs_consts).
  * k < 256: sequential sum of cssm_log(i); otherwise the Stirling series (error < 1e-17).
  */
 CSSM_HD double cssm_lgamma_kp1(long long k) {
@@ -936,9 +937,11 @@ CSSM_HD double cssm_lgamma_kp1(long long k) {
 }
 
 /*
- * log Gamma(x) for real x > 0 (host-side, once per observation: the constants of the negative
- * binomial and Student-t densities, model/Model.scala:191,158).  Argument shifted to z >= 24 by the
- * recurrence, then the Stirling series; ~1e-15 relative.
+ * log Gamma(x) for real x > 0: on the host once per observation (the constants of the negative
+ * binomial and Student-t densities, model/Model.scala:191,158), and on the device per lane -- PTRS's
+ * acceptance test (cssm_obs_draws.h) and the IF2 kernel, whose particles carry their own size and
+ * scale.  Argument shifted to z >= 24 by the recurrence (a loop of up to 24 trips, data dependent),
+ * then the Stirling series; ~1e-15 relative (tests/test_oracle_pins.py: 3e-14 max(1, |value|) up to 2^52).
  */
 CSSM_HD double cssm_lgamma(double x) {
   if (!(x > 0.0)) return cssm_nan();

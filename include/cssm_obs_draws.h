@@ -19,14 +19,23 @@
  *   Poisson(lambda)           lambda < 10: inversion by sequential search on one uniform (block 0 words 0-1); the search
  *                             stops where the cumulative sum no longer grows (u within rounding of 1).  10 <= lambda < 2^52:
  *                             PTRS (Hoermann 1993, "The transformed rejection method for generating Poisson random
- *                             variables"), one block per attempt (U from words 0-1, V from words 2-3).  lambda >= 2^52:
- *                             floor(lambda + sqrt(lambda) z) (the normal limit; doubles are integers there).
- *                             lambda = 0 -> 0; lambda = +inf -> +inf; NaN or lambda < 0 -> NaN.
+ *                             variables"), one block per attempt (U from words 0-1, V from words 2-3).  Its acceptance
+ *                             test needs log pmf(k) = -lambda + k log(lambda) - lgamma(k + 1) to far better than 1:
+ *                             below CSSM_OBS_PTRS_DELTA_MIN = 2^26 it is that expression as written (terms of size
+ *                             lambda log(lambda) cancel: absolute error < 2^-20 there, 1.1e-6 in the octave above, 4e-2
+ *                             at 1e14, 43 at 2^52 -- DESIGN.md section 2 has the measured table); from 2^26 on it is
+ *                             formed from delta = k - lambda (cssm_obs_ptrs_logpmf_delta: only terms of size
+ *                             delta^2 / lambda are left to cancel, error < 1e-13 up to 2^52).  Draws below 2^26 are
+ *                             bit for bit those of contract v8; from 2^26 to 2^52 the attempts and their blocks are
+ *                             the same and only the decisions the old error got wrong differ (contract v9).
+ *                             lambda >= 2^52: floor(lambda + sqrt(lambda) z) (the normal limit; doubles are integers
+ *                             there).  lambda = 0 -> 0; lambda = +inf -> +inf; NaN or lambda < 0 -> NaN.
  *   Gaussian(eta, sd)         eta + sd z, z = first normal of block 0; sd = exp(scale).
  *   Gamma(shape, scale)       Marsaglia & Tsang (2000): shape >= 1 one block per attempt (z from words 0-1 through
  *                             cssm_normal_pair64, U from words 2-3, the squeeze U < 1 - 0.0331 z^4 first); shape < 1:
  *                             Gamma(shape + 1) U^(1/shape), the boost uniform U from block 0 and the attempts from block 1.
- *                             shape <= 0 or NaN -> NaN; shape = +inf -> +inf.
+ *                             shape <= 0 or NaN -> NaN; shape = +inf -> +inf.  A boost below e^-708 is 0 (cssm_exp), so a
+ *                             value that would be below DBL_MIN comes out 0 (half of all draws at shape 1e-3).
  *   NegBin(eta, size)         Gamma(size, scale = eta / size), then Poisson of it; size = exp(scale).
  *   ZIP(eta, p)               u < p ? 0 : Poisson(eta), u from block 0, the Poisson from block 1; p = logistic(scale).
  *   Bernoulli(eta)            u < eta (eta already clamped to {0, 1} beyond |gamma| > 6 by link).
@@ -61,6 +70,9 @@ extern "C++" {
  * cssm_simulate_from continues a simulation: time index j of the call moves and draws under step first_step + j. */
 #define CSSM_SIM_STEP_ROW0 0xFFFFFFFFu
 #define CSSM_OBS_PTRS_MIN 10.0      /* Poisson: inversion below, PTRS from here on */
+#ifndef CSSM_OBS_PTRS_DELTA_MIN     /* (a test moves it to 2^52 to rebuild the sampler of contract v8) */
+#define CSSM_OBS_PTRS_DELTA_MIN 0x1.0p26 /* Poisson: PTRS forms its exponent from k - lambda from here on */
+#endif
 #define CSSM_OBS_NORMAL_MIN 0x1.0p52 /* Poisson: the normal limit from here on */
 #define CSSM_OBS_MAX_ATTEMPTS 64
 
@@ -125,6 +137,23 @@ CSSM_HD cssm_u32x4 cssm_obs_next(cssm_obs_stream* s) {
   return b;
 }
 
+/* PTRS's exponent log pmf(k) = -lambda + k log(lambda) - lgamma(k + 1), as written: every draw below CSSM_OBS_PTRS_DELTA_MIN, and the
+ * far tail above it (|k - lambda| >= lambda 2^-10, where the value is below -lambda 2^-21 <= -32 and its error, at most 43, decides
+ * nothing: the left side is above -120). */
+CSSM_HD double cssm_obs_ptrs_logpmf_direct(double lam, double loglam, double k) {
+  return (-lam + k * loglam) - cssm_lgamma(k + 1.0);
+}
+/* The same for lambda >= CSSM_OBS_PTRS_DELTA_MIN and |k - lambda| < lambda 2^-10, from delta = k - lambda (exact) and x = delta / lambda:
+ *   -lambda + k log(lambda) - log k! = delta - k log1p(x) - log(2 pi k) / 2 - 1 / (12 k) + O(k^-3)      (Stirling; k^-3 / 360 < 1e-25)
+ *   delta - k log1p(x) = -delta x - k g(x),  g(x) = log1p(x) - x = -x^2/2 + x^3/3 - ... + x^7/7         (lambda x = delta; k x^8 / 8 < 5e-10,
+ *                                                                                                        < 1e-30 within 6 sd)
+ * The rounding of x enters in second order only: with x' = x - r / lambda, k log1p(x) = k log1p(x') + r and k x' = delta - r + delta x'. */
+CSSM_HD double cssm_obs_ptrs_logpmf_delta(double lam, double k) {
+  const double delta = k - lam, x = delta / lam;
+  const double g = (x * x) * (-1.0 / 2.0 + x * (1.0 / 3.0 + x * (-1.0 / 4.0 + x * (1.0 / 5.0 + x * (-1.0 / 6.0 + x * (1.0 / 7.0))))));
+  return ((-(delta * x) - k * g) - 0.5 * cssm_log(6.28318530717958623200 * k)) - 1.0 / (12.0 * k);
+}
+
 /* Poisson(lambda) */
 CSSM_HD double cssm_obs_poisson(double lam, cssm_obs_stream* s, const double* tab) {
   if (lam != lam || lam < 0.0) return cssm_nan();
@@ -166,7 +195,8 @@ CSSM_HD double cssm_obs_poisson(double lam, cssm_obs_stream* s, const double* ta
     if (us >= 0.07 && V <= vr) return k;
     if (k < 0.0 || (us < 0.013 && V > us)) continue;
     const double lhs = (cssm_log(V) + log_invalpha) - cssm_log(a / (us * us) + bb);
-    const double rhs = (-lam + k * loglam) - cssm_lgamma(k + 1.0);
+    const double rhs = (lam >= CSSM_OBS_PTRS_DELTA_MIN && __builtin_fabs(k - lam) < lam * 0x1.0p-10)
+                           ? cssm_obs_ptrs_logpmf_delta(lam, k) : cssm_obs_ptrs_logpmf_direct(lam, loglam, k);
     if (lhs <= rhs) return k;
   }
   return __builtin_floor(lam);

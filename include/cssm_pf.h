@@ -365,6 +365,9 @@ int cssm_pf_profile_read(cssm_pf* pf, double* total_ms, uint64_t* launches);
 #define CSSM_FN_PAIRED_NORMALS 5
 #define CSSM_FN_SINCOS_U24 6   /* out[2i] = sin, out[2i+1] = cos of 2 pi k / 2^24, k = (uint32_t)x[i] < 2^24 (cssm_sincos_u24) */
 #define CSSM_FN_SQRT_RADIUS 7  /* out[i] = cssm_sqrt_radius(x[i]), x[i] = +-0 or in [2^-39, 55.5] */
+#define CSSM_FN_EXP_LE0 8      /* out[i] = cssm_exp_le0(x[i]), x[i] <= 2^-20 and not NaN (-inf allowed) */
+#define CSSM_FN_LGAMMA 9       /* out[i] = cssm_lgamma(x[i]): the samplers and the IF2 kernel evaluate it per lane */
+#define CSSM_FN_LGAMMA_KP1 10  /* out[i] = cssm_lgamma_kp1((long long)x[i]), x[i] an integer in [0, 2^62] */
 int cssm_contract_eval(int device, int fn, const double* x, size_t n, double* out, size_t n_out);
 
 /* On-box streaming ceiling: GB/s (read + write) of a plain 16-bytes-per-lane device-to-device copy of `bytes` bytes,

@@ -1000,6 +1000,9 @@ void oracle_c_paired_normals_v(uint64_t seed, uint64_t gid0, uint32_t step, uint
     }
   }
 }
+void oracle_c_exp_le0_v(const double* x, double* y, size_t n) { for (size_t i = 0; i < n; ++i) y[i] = cssm_exp_le0(x[i]); }
+void oracle_c_lgamma_v(const double* x, double* y, size_t n) { for (size_t i = 0; i < n; ++i) y[i] = cssm_lgamma(x[i]); }
+void oracle_c_lgamma_kp1_v(const double* k, double* y, size_t n) { for (size_t i = 0; i < n; ++i) y[i] = cssm_lgamma_kp1((long long)k[i]); }
 void oracle_c_log_v(const double* x, double* y, size_t n) { for (size_t i = 0; i < n; ++i) y[i] = cssm_log(x[i]); }
 void oracle_c_sincos_u24_v(const uint32_t* k, double* s, double* c, size_t n) { for (size_t i = 0; i < n; ++i) cssm_sincos_u24(k[i], CSSM_LOG_TAB, &s[i], &c[i]); }
 void oracle_c_sincos2pi_v(const double* u, double* s, double* c, size_t n) { for (size_t i = 0; i < n; ++i) cssm_sincos2pi(u[i], &s[i], &c[i]); }

@@ -116,6 +116,9 @@ def lib() -> C.CDLL:
             "oracle_c_multi_u_v": (None, [C.c_uint64, C.c_uint32, C.c_uint64, _dp]),
             "oracle_c_exp_v": (None, [_dp, _dp, C.c_size_t]),
             "oracle_c_log_v": (None, [_dp, _dp, C.c_size_t]),
+            "oracle_c_exp_le0_v": (None, [_dp, _dp, C.c_size_t]),
+            "oracle_c_lgamma_v": (None, [_dp, _dp, C.c_size_t]),
+            "oracle_c_lgamma_kp1_v": (None, [_dp, _dp, C.c_size_t]),
             "oracle_c_sincos2pi_v": (None, [_dp, _dp, _dp, C.c_size_t]),
             "oracle_c_sincos_u24_v": (None, [C.POINTER(C.c_uint32), _dp, _dp, C.c_size_t]),
             "oracle_c_normals_v": (None, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _dp, C.c_size_t]),
@@ -322,6 +325,19 @@ def c_exp(x):
 
 def c_log(x):
     x = np.ascontiguousarray(x, dtype=np.float64); y = np.empty_like(x); lib().oracle_c_log_v(_p(x), _p(y), x.size); return y
+
+
+def c_exp_le0(x):
+    x = np.ascontiguousarray(x, dtype=np.float64); y = np.empty_like(x); lib().oracle_c_exp_le0_v(_p(x), _p(y), x.size); return y
+
+
+def c_lgamma(x):
+    x = np.ascontiguousarray(x, dtype=np.float64); y = np.empty_like(x); lib().oracle_c_lgamma_v(_p(x), _p(y), x.size); return y
+
+
+def c_lgamma_kp1(k):
+    """cssm_lgamma_kp1 at the integers k (given as doubles)"""
+    k = np.ascontiguousarray(k, dtype=np.float64); y = np.empty_like(k); lib().oracle_c_lgamma_kp1_v(_p(k), _p(y), k.size); return y
 
 
 def c_sincos2pi(u):

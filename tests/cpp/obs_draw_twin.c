@@ -42,3 +42,7 @@ double twin_poisson_from(double lam, uint64_t key, uint64_t gid, uint32_t step, 
   s.block = block;
   return cssm_obs_poisson(lam, &s, CSSM_TAB);
 }
+
+/* PTRS's exponent log pmf(k) in its two forms (tests/test_obs_draw_laws.py holds both to mpmath over the range each serves) */
+double twin_ptrs_logpmf_direct(double lam, double k) { return cssm_obs_ptrs_logpmf_direct(lam, cssm_log(lam), k); }
+double twin_ptrs_logpmf_delta(double lam, double k) { return cssm_obs_ptrs_logpmf_delta(lam, k); }

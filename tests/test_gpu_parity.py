@@ -685,6 +685,22 @@ def test_contract_functions_on_the_device_match_the_host():
                         [0.0, 1.0, 2.0 ** -96, 2.0 ** -97, 5e-324, 511.99999999999994, 512.0, np.inf, np.nan, 403.4287934927351]])
     fx = _contract_eval(4, w, 2 * w.size).view(np.uint64).reshape(-1, 2)
     assert np.array_equal(fx, oracle.c_fix(w))
+    # the functions the samplers and the IF2 kernel evaluate per lane.  exp_le0: arguments <= 0 down to -745.2 and -inf, both sides of -708
+    xe = np.concatenate([-rng.uniform(0, 745.2, 300000), -np.exp(rng.uniform(-700, 7, 100000)), -708.0 + rng.uniform(-1e-9, 1e-9, 20000),
+                         [0.0, -0.0, 2.0 ** -20, -708.0, np.nextafter(-708.0, 0.0), np.nextafter(-708.0, -1e9), -745.0, -745.2, -1e300, -np.inf, -5e-324]])
+    assert np.array_equal(_contract_eval(8, xe, xe.size).view(np.uint64), oracle.c_exp_le0(xe).view(np.uint64))
+    # lgamma: (0, 24] dense (neighbouring lanes leave the recurrence loop after different trip counts), 24 .. 1e300, subnormal, and the NaN
+    # of 0, negative and NaN arguments
+    xg = np.concatenate([rng.uniform(0, 24, 400000), np.arange(1, 49) * 0.5, np.nextafter(np.arange(1.0, 25.0), 0.0), np.exp(rng.uniform(np.log(24.0), np.log(1e300), 200000)),
+                         np.exp(rng.uniform(-745, 0, 100000)), [5e-324, 1e-310, 2.2250738585072014e-308, 24.0, 1e300, 2.0 ** 52 + 1.0,
+                                                               0.0, -0.0, -1.0, -0.5, -np.inf, np.nan]])
+    rng.shuffle(xg)
+    got, want = _contract_eval(9, xg, xg.size), oracle.c_lgamma(xg)
+    assert np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(np.isnan(want), ~(xg > 0.0))
+    assert np.array_equal(got[xg > 0.0].view(np.uint64), want[xg > 0.0].view(np.uint64))
+    # lgamma(k + 1): k = 0 .. 300 across the switch from the sum of logarithms to Stirling at 256, then large k
+    kk = np.concatenate([np.arange(0, 301), rng.integers(0, 301, 2000), [1e6, 2.0 ** 31, 2.0 ** 52, 2.0 ** 52 - 1.0]]).astype(np.float64)
+    assert np.array_equal(_contract_eval(10, kk, kk.size).view(np.uint64), oracle.c_lgamma_kp1(kk).view(np.uint64))
     for d in (1, 2, 3, 4, 9, 16):
         for first in (0, 7):   # even and odd first particle: both parities of the pair streams
             z = _contract_eval(5, np.array([cases.SEED, first, 3, 0, d], dtype=np.float64), 1001 * d).reshape(-1, d)

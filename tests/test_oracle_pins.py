@@ -62,6 +62,29 @@ def test_lgamma_real_argument():
         assert abs(oracle.lib().oracle_c_lgamma(x) - ref) <= 3e-14 * max(1.0, abs(ref))
 
 
+def test_lgamma_against_mpmath_over_the_arguments_the_device_passes():
+    """The same bound against mpmath at 50 digits over the samples tests/test_gpu_parity.py compares device and host on: (0, 24] dense (a
+    recurrence of up to 24 trips), 24 .. 1e300, subnormal arguments, and k + 1 up to 2^52 as PTRS's acceptance test passes them; 0,
+    negative and NaN arguments give NaN."""
+    mp = pytest.importorskip("mpmath")
+    rng = np.random.default_rng(24)
+    lam = 2.0 ** rng.uniform(3.4, 52, 400)
+    xs = np.concatenate([rng.uniform(0, 24, 1500), np.arange(1, 49) * 0.5, np.nextafter(np.arange(1.0, 25.0), 0.0),
+                         np.exp(rng.uniform(np.log(24.0), np.log(1e300), 600)), np.exp(rng.uniform(-745, 0, 300)),
+                         np.floor(lam + rng.uniform(-4, 4, 400) * np.sqrt(lam)) + 1.0,
+                         [5e-324, 1e-310, 2.2250738585072014e-308, 24.0, 1e300, 2.0 ** 52, 2.0 ** 52 + 1.0, 2.0 ** 52 - 1.0]])
+    got = oracle.c_lgamma(xs)
+    worst = 0.0
+    with mp.workdps(50):
+        for x, g in zip(xs, got):
+            ref = mp.loggamma(mp.mpf(float(x)))
+            err = float(abs(mp.mpf(float(g)) - ref) / max(mp.mpf(1), abs(ref)))
+            worst = max(worst, err)
+            assert err <= 3e-14, (x, g, float(ref))
+    print("cssm_lgamma: worst error relative to max(1, |value|) = %.3g over %d arguments" % (worst, xs.size))
+    assert np.all(np.isnan(oracle.c_lgamma(np.array([0.0, -0.0, -1.0, -0.5, -np.inf, np.nan]))))
+
+
 # ----------------------------------------------------------------------------- K2 transitions
 def test_k2_double_logistic_on_ou_phi():
     # ouParameter(...)(0.2) stores logistic(0.2); OuProcess applies logistic again (Sde.scala:136)
