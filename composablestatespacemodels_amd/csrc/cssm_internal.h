@@ -194,6 +194,9 @@ struct cssm_pf : HostModel {
   // the device times of the last call (cssm_pf_smooth_last_ms; < 0: none yet)
   uint32_t smooth_tile = 0;
   double smooth_ms[3] = {-1.0, -1.0, -1.0};
+  // cssm_pf_filter_intervals (cssm_intervals.hip): the selection's scratch, the call's row buffer and its timing (IvScratch; made at the
+  // first call, freed by cssm_iv_free)
+  void* iv = nullptr;
 };
 
 // begin/end of one profiled launch
@@ -267,3 +270,10 @@ int cssm_prop_items(int d);   // PropItems<D>
 int cssm_use_device(int device);   // the device exists and is current, or the error
 double cssm_eta_of_mean(const HostModel& m, const double* fco, const double* mean);   // link(f(stateMean, t)), ParticleFilter.scala:420
 void cssm_peer_free(cssm_pf* pf);   // cssm_shard.hip: the peer-written exchange's windows, mappings and device table
+// ---- filtered intervals of the single handle: cssm_intervals.hip enqueues the rows, cssm_pf.hip's drivers say when
+int cssm_iv_row(cssm_pf* pf, size_t row);        // the summary of the current cloud as row `row` of the running call (8 launches, no host work)
+int cssm_iv_results(cssm_pf* pf, size_t nrows);  // behind the call's last launch: its rows on their way to the host
+void cssm_iv_free(cssm_pf* pf);
+// cssm_pf_ll_filter / cssm_pf_ll_filter_more (cont) with a row behind the initial cloud (not cont) and behind every record; cssm_pf_step with one
+int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont);
+int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out);

@@ -215,6 +215,7 @@ extern "C" void cssm_pf_destroy(cssm_pf* pf) {
   (void)hipSetDevice(pf->device);
   if (pf->stream) (void)hipStreamSynchronize(pf->stream);
   cssm_peer_free(pf);
+  cssm_iv_free(pf);
   void* ptrs[] = {pf->sm_keys, pf->sm_partial, pf->sm_st, pf->sm_rec, pf->s2buf, pf->fineS, pf->fineS2, pf->state[0], pf->state[1], pf->logw, pf->endslot, pf->anc, pf->tileS, pf->tileS2, pf->tileP, pf->unitPre, pf->tileW, pf->sc,
                   pf->d_m0, pf->d_sd0, pf->d_logtab, pf->d_fsub, pf->cum, pf->d_recs, pf->d_ll_t, pf->d_ess_t, pf->d_path, pf->cand, pf->cand_end, pf->cand_idx, pf->d_bounds, pf->d_xch, pf->d_need};
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -674,7 +675,8 @@ extern "C" int cssm_pf_init_from(cssm_pf* pf, double t0, const double* state_d) 
   return CSSM_OK;
 }
 
-extern "C" int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out) {
+// rows: cssm_pf_step_intervals -- the summary of the resampled cloud is enqueued behind the step (after a redo: again) and travels with its scalars
+static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out, bool rows) {
   if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
   if (!pf->initialised) return fail(CSSM_ESTATE, "cssm_pf_step before cssm_pf_init");
   if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
@@ -691,8 +693,9 @@ extern "C" int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, doub
   pf->gen++;
   rc = launch_step(pf, pf->d_recs, weighted, pf->step);
   if (rc) return rc;
+  if (rows) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
   Scalars& h = *pf->h_sc;
-  rc = read_scalars(pf, 0, false, false, /*poll=*/true);   // (the completion word, not the stream: 40.4 -> 38.0 us per streaming step at N = 2^20)
+  rc = read_scalars(pf, 0, false, false, /*poll=*/!rows);   // (the completion word, not the stream: 40.4 -> 38.0 us per streaming step at N = 2^20)
   if (rc) return rc;
   if ((h.err & 64u) && !(h.err & 3u)) {   // the max ruled the reference level out: this observation again, relative to the max
     const uint32_t cleared = h.err & ~64u, none = 0xffffffffu;
@@ -700,6 +703,7 @@ extern "C" int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, doub
     HIP_TRY(hipMemcpyAsync(&pf->sc->fail_step, &none, sizeof(uint32_t), hipMemcpyHostToDevice, pf->stream));
     rc = redo_observation(pf, before, pf->d_recs, nullptr, nullptr, 0);
     if (rc) return rc;
+    if (rows) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
     rc = read_scalars(pf);
     if (rc) return rc;
   }
@@ -707,6 +711,12 @@ extern "C" int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, doub
   if (ll_out) *ll_out = h.ll;
   if (ess_out) *ess_out = h.ess;
   return cssm_check_device_err(pf, h);
+}
+extern "C" int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out) {
+  return step_impl(pf, t, obs, has_obs, ll_out, ess_out, false);
+}
+int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out) {
+  return step_impl(pf, t, obs, has_obs, ll_out, ess_out, true);
 }
 // ---- an arbitrary Resample[A] on the host (model/package.scala:23): the step split at the resampler ----------------------
 // cssm_pf_propagate = lines :117-124 of stepFilter (propagate, weigh); the caller fetches the proposed cloud and the
@@ -768,19 +778,19 @@ extern "C" int cssm_pf_adopt(cssm_pf* pf, const double* state_dN, double ll, int
 // ------------------------------------------------------------------------------------ batch API
 
 static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
-                           double* ll_t, int32_t* ess_t, double* path, bool* retry, bool cont = false);
+                           double* ll_t, int32_t* ess_t, double* path, bool* retry, bool cont = false, bool rows = false);
 
 // The series is enqueued without a host round trip per step, with the sums formed inside k_propagate relative to
 // each observation's reference level.  If the max of some step rules its level out (err bit 2; an outlying
 // observation), the series is run again with the sums in their own pass: every step then applies the same rule
 // (cssm_ref_choose), so both runs define the same result and only the second one can compute it.
 static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
-                      double* ll_t, int32_t* ess_t, double* path) {
+                      double* ll_t, int32_t* ess_t, double* path, bool rows = false) {
   bool retry = false;
-  int rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, path, &retry);
+  int rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, path, &retry, false, rows);
   if (rc == CSSM_OK && retry) {
     pf->safe_sums = true;
-    rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, path, &retry);
+    rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, path, &retry, false, rows);   // (rows: every one is enqueued, and written, again)
     pf->safe_sums = false;
   }
   return rc;
@@ -789,7 +799,7 @@ static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8
 // cont: the observations CONTINUE the filter from its current state (cssm_pf_ll_filter_more): no initial cloud is drawn, the
 // first time increment is taken from the handle's clock, observation s of this call is observation pf->step + s of the filter.
 static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
-                           double* ll_t, int32_t* ess_t, double* path, bool* retry, bool cont) {
+                           double* ll_t, int32_t* ess_t, double* path, bool* retry, bool cont, bool rows) {
   *retry = false;
   if (!pf || !t || !y) return fail(CSSM_EINVAL_ARG, "null argument");
   if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data (the reference's minBy throws on an empty Vector)");
@@ -831,7 +841,9 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
   if (!cont) {
     rc = cssm_launch_init(pf, t0);
     if (rc) return rc;
+    if (rows) { rc = cssm_iv_row(pf, 0); if (rc) return rc; }   // (cssm_pf_filter_intervals: row 0 = the initial cloud)
   }
+  const size_t row0 = cont ? 0 : 1;   // (rows) the row behind record s is row0 + s
   // host-side state at the first observation of this call (launch_init: cur = 0, wparity = 0)
   const int cur0 = pf->cur, wpar0 = pf->wparity;
   const bool anc_valid0 = pf->anc_valid;
@@ -876,6 +888,7 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
       }
       if (rc) return rc;
       if (rest_pending) { rc = build_rest(); if (rc) return rc; }
+      if (rows) { rc = cssm_iv_row(pf, row0 + s); if (rc) return rc; }   // (a series on hold: these launches return at once like the filter's)
       folded = path && s + 1 < T && uses_sums_kernel(pf);   // (the last entry has no following propagate)
       if (path && !folded)
         hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, pf->stream, pf->src, pf->src_stride,
@@ -887,7 +900,8 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
     if (pf->opt_events) HIP_TRY(hipEventRecord(pf->ev1, pf->stream));
     HIP_TRY(hipGetLastError());
     if (path) HIP_TRY(hipMemcpyAsync(path, pf->d_path, (T + 1) * (size_t)d * 8, hipMemcpyDeviceToHost, pf->stream));
-    rc = read_scalars(pf, (uint32_t)T, ll_t != nullptr, ess_t != nullptr, /*poll=*/path == nullptr);   // (k_finish: a pending ESS formed, results into host-mapped memory)
+    if (rows) { rc = cssm_iv_results(pf, row0 + T); if (rc) return rc; }
+    rc = read_scalars(pf, (uint32_t)T, ll_t != nullptr, ess_t != nullptr, /*poll=*/path == nullptr && !rows);   // (k_finish: a pending ESS formed, results into host-mapped memory)
     if (rc) return rc;
     const Scalars& hh = *pf->h_sc;
     if (!may_hold || !(hh.err & 64u) || (hh.err & 3u)) break;   // (NaN / unusable weights: reported below)
@@ -908,6 +922,7 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
     pf->h_step_for_resample = base + (uint32_t)sf;
     rc = redo_observation(pf, before, pf->d_recs + sf, pf->d_ll_t, pf->d_ess_t, (uint32_t)sf);
     if (rc) return rc;
+    if (rows) { rc = cssm_iv_row(pf, row0 + sf); if (rc) return rc; }   // (the held record's row is formed behind its redo)
     folded = path && sf + 1 < T && uses_sums_kernel(pf);
     if (path && !folded)
       hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, pf->stream, pf->src, pf->src_stride, (const uint32_t*)pf->anc,
@@ -943,6 +958,14 @@ extern "C" int cssm_pf_ll_filter_more(cssm_pf* pf, const double* t, const double
                                       double* ll_out, double* ll_t, int32_t* ess_t) {
   bool retry = false;
   int rc = run_filter_once(pf, t, y, has_obs, T, ll_out, ll_t, ess_t, nullptr, &retry, /*cont=*/true);
+  if (rc == CSSM_OK && retry) return fail(CSSM_ESTATE, "a continued series cannot be repeated from its start");   // (not reached: batch series are held in place)
+  return rc;
+}
+
+int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont) {
+  if (!cont) return run_filter(pf, t, y, has, T, ll_out, ll_t, ess_t, nullptr, true);
+  bool retry = false;
+  int rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, nullptr, &retry, /*cont=*/true, /*rows=*/true);
   if (rc == CSSM_OK && retry) return fail(CSSM_ESTATE, "a continued series cannot be repeated from its start");   // (not reached: batch series are held in place)
   return rc;
 }

@@ -224,6 +224,51 @@ class NativePf:
         _abi.check(self.lib.cssm_pf_summary(self._h, float(interval), _p(m), _p(lo), _p(hi), C.byref(em), C.byref(el), C.byref(eu)))
         return m, lo, hi, em.value, el.value, eu.value
 
+    def _filter_intervals(self, fn, t, y, has, interval, nrows_extra):
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        T = len(t)
+        has = _u8(has)
+        rows = _interval_arrays((T + nrows_extra,), self.d)
+        ll = C.c_double()
+        ll_t = np.zeros(T)
+        ess_t = np.zeros(T, dtype=np.int32)
+        rc = fn(self._h, _p(t), _p(y), _p(has), T, float(interval), C.byref(ll), _p(ll_t), _p(ess_t), *map(_p, rows))
+        self.generation += 1
+        _abi.check(rc)
+        return (ll.value, ll_t, ess_t) + rows
+
+    def filter_intervals(self, t, y, has=None, interval: float = 0.975):
+        """cssm_pf_filter_intervals: ``run`` with the ``summary`` of the initial cloud (row 0) and of the cloud behind every record (row
+        s + 1) from the same call: ``(ll, ll_t[T], ess_t[T], state_mean[T+1,d], state_lower, state_upper, eta_of_mean[T+1], eta_lower,
+        eta_upper)``, every row with the bits of ``summary`` at that moment of the loop init; summary; (step; summary)*."""
+        return self._filter_intervals(self.lib.cssm_pf_filter_intervals, t, y, has, interval, 1)
+
+    def filter_intervals_more(self, t, y, has=None, interval: float = 0.975):
+        """cssm_pf_filter_intervals_more: ``run_more`` with the ``summary`` behind every record: the same tuple with T rows (no initial row)."""
+        return self._filter_intervals(self.lib.cssm_pf_filter_intervals_more, t, y, has, interval, 0)
+
+    def step_intervals(self, t: float, y: Optional[float], has_obs: Optional[bool] = None, interval: float = 0.975):
+        """cssm_pf_step_intervals: ``step`` and the ``summary`` of the cloud it leaves in one call: ``(ll, ess, state_mean[d], state_lower[d],
+        state_upper[d], eta_of_mean, eta_lower, eta_upper)``."""
+        if has_obs is None:
+            has_obs = y is not None
+        ll, ess = C.c_double(), C.c_int32()
+        m, lo, hi = np.zeros(self.d), np.zeros(self.d), np.zeros(self.d)
+        em, el, eu = C.c_double(), C.c_double(), C.c_double()
+        rc = self.lib.cssm_pf_step_intervals(self._h, float(t), 0.0 if y is None else float(y), 1 if has_obs else 0, float(interval),
+                                             C.byref(ll), C.byref(ess), _p(m), _p(lo), _p(hi), C.byref(em), C.byref(el), C.byref(eu))
+        self.generation += 1
+        _abi.check(rc)
+        return ll.value, ess.value, m, lo, hi, em.value, el.value, eu.value
+
+    def intervals_last_ms(self) -> Tuple[float, float]:
+        """Device milliseconds of the last ``filter_intervals`` / ``filter_intervals_more`` / ``step_intervals``: (the whole call, its summary
+        launches alone) (cssm_pf_intervals_last_ms)."""
+        ms = np.zeros(2)
+        _abi.check(self.lib.cssm_pf_intervals_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1])
+
     def observation_index(self) -> int:
         """Observations the current cloud has seen (cssm_pf_observation_index)."""
         return int(self.lib.cssm_pf_observation_index(self._h))
@@ -1318,6 +1363,22 @@ class StateSpace:  # Sde.scala:170
     state: np.ndarray
 
 
+def _pfout_of(t, observation, row) -> PfOut:
+    """One ``PfOut`` from the six values of a summary, in ``NativePf.summary``'s order."""
+    m, lo, hi, em, el, eu = row
+    return PfOut(float(t), observation, float(em), CredibleInterval(float(el), float(eu)), np.array(m, dtype=np.float64),
+                 [CredibleInterval(float(a), float(b)) for a, b in zip(lo, hi)])
+
+
+def pfouts_from_rows(times, observations, rows) -> List[PfOut]:
+    """The ``PfOut`` of every row of ``NativePf.filter_intervals``' six arrays (state_mean[R, d], state_lower, state_upper, eta_of_mean[R],
+    eta_lower, eta_upper), with the rows' times and observations."""
+    m, lo, hi, em, el, eu = rows
+    if not (len(times) == len(observations) == len(m) == len(lo) == len(hi) == len(em) == len(el) == len(eu)):
+        raise ValueError("times, observations and the six row arrays must have one entry per row")
+    return [_pfout_of(times[r], observations[r], (m[r], lo[r], hi[r], em[r], el[r], eu[r])) for r in range(len(times))]
+
+
 # --------------------------------------------------------------------------- filters
 class _FilterBase:
     lgcp_precision = 0
@@ -1422,6 +1483,42 @@ class _FilterBase:
         times = [float(np.min(t))] + [float(v) for v in t]
         return ll, [StateSpace(tt, path[i].copy()) for i, tt in enumerate(times)]
 
+    # examples/Filtering.scala:23-32: filter, then getIntervals of every emitted state
+    def _batch_intervals(self, pf: NativePf, t, y, h, interval: float):
+        """(ll, rows) of the batch path: the six row arrays of T + 1 entries (cssm_pf_filter_intervals)."""
+        r = pf.filter_intervals(t, y, h, interval)
+        return r[0], r[3:]
+
+    def filterIntervals(self, data: Sequence[TimedObservation], particles: int, interval: float = 0.975) -> Tuple[float, List[PfOut]]:
+        """``filter`` followed by ``getIntervals`` of every emitted state, in one native call: the log-likelihood and T + 1 ``PfOut`` --
+        the first of the initial cloud at the data's smallest time with ``observation = None``, as ``filterStream`` emits the initial
+        state, then one per record.  Each equals what ``ParticleFilter.getIntervals`` returns for that state of a ``filterStream`` run
+        (at the given ``interval``), so ``formats.pfout_csv`` writes the reference's ``Filtered.csv`` lines from them.
+        With a host ``Resample[A]`` (any function but the three native resamplers, the residual extension included) there is no batch
+        path: the records go through ``stepFilter`` one by one with a ``summary`` behind each."""
+        data = list(data)
+        if self._host_resample is not None:
+            st = self.initialiseState(particles, min(d.t for d in data))
+            outs = [_pfout_of(st.t, None, self._pf.summary(interval))]
+            for d in data:
+                st = self.stepFilter(st, d)
+                outs.append(_pfout_of(d.t, d.observation, self._pf.summary(interval)))
+            return st.ll, outs
+        t, y, h = split_data(data)
+        ll, rows = self._batch_intervals(self._ensure(particles), t, y, h, interval)
+        return ll, pfouts_from_rows([float(np.min(t))] + [d.t for d in data], [None] + [d.observation for d in data], rows)
+
+    def stepIntervals(self, s: PfState, y: TimedObservation, interval: float = 0.975) -> Tuple[PfState, PfOut]:
+        """``stepFilter`` and ``getIntervals`` of the state it returns, in one native call (cssm_pf_step_intervals; with a host
+        ``Resample[A]``: ``stepFilter``, then ``summary``)."""
+        if s._owner is not self._pf or s._generation != self._pf.generation:
+            raise RuntimeError("stepIntervals must be applied to the filter's current PfState")
+        if self._host_resample is not None:
+            st = self.stepFilter(s, y)
+            return st, _pfout_of(y.t, y.observation, self._pf.summary(interval))
+        r = self._pf.step_intervals(y.t, y.observation, interval=interval)
+        return self._state(y.t, y.observation, r[0], r[1]), _pfout_of(y.t, y.observation, r[2:])
+
     # ParticleFilter.scala:163-166: Flow[Data].scan(init)(stepFilter) -- emits init, then one state per datum
     def filterStream(self, t0: float, particles: int) -> Callable[[Iterable[TimedObservation]], Iterator[PfState]]:
         def flow(source: Iterable[TimedObservation]) -> Iterator[PfState]:
@@ -1457,6 +1554,14 @@ class FilterInit(_FilterBase):
         t, y, h = split_data(data)
         self.initialiseState(n, float(np.min(t)))
         return self._pf.run_more(t, y, h)[0]
+
+    def _batch_intervals(self, pf: NativePf, t, y, h, interval: float):
+        """The given state at the data's smallest time and its summary (row 0), then the records with their rows in one native call
+        (cssm_pf_filter_intervals_more)."""
+        self.initialiseState(pf.n, float(np.min(t)))
+        first = pf.summary(interval)
+        r = pf.filter_intervals_more(t, y, h, interval)
+        return r[0], tuple(np.concatenate([np.asarray(a)[None], b]) for a, b in zip(first, r[3:]))
 
 
 class FilterLgcp(_FilterBase):

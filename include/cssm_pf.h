@@ -409,6 +409,41 @@ int cssm_pf_get_proposed(cssm_pf* pf, double* out_dN);
 int cssm_pf_summary(cssm_pf* pf, double interval, double* state_mean, double* state_lower, double* state_upper,
                     double* eta_of_mean, double* eta_lower, double* eta_upper);
 
+/* Filtered intervals of every observation in ONE call: `filter`, then getIntervals of every emitted state
+ * (examples/Filtering.scala:23-32) -- cssm_pf_ll_filter with a cssm_pf_summary row behind the initial cloud and behind every record,
+ * enqueued between the observations' launches with no host round trip and one synchronisation per call.
+ *   row 0      the initial cloud, at t0 = min t
+ *   row s + 1  the resampled cloud behind record s (a record without a datum: the moved cloud through identity ancestors)
+ * state_mean / state_lower / state_upper: [T + 1][d]; eta_of_mean / eta_lower / eta_upper: [T + 1]; any output may be NULL.  Every row
+ * has the BITS cssm_pf_summary(pf, interval, ...) gives at that moment of the loop cssm_pf_init; summary; (cssm_pf_step; summary) x T;
+ * ll_out, ll_t, ess_t and the handle (cloud, ancestors, clock, observation index, LGCP level) are cssm_pf_ll_filter's.  Served: every
+ * handle cssm_pf_ll_filter serves (every observation model, the LGCP, the three native resamplers); a sharded handle is CSSM_ESTATE.
+ * Refused before any work, with cssm_pf_ll_filter's / cssm_pf_summary's codes: a null handle, t or y and T = 0 (CSSM_EINVAL_ARG), an
+ * interval outside (0, 1] (CSSM_EINVAL_ARG).  On an error return the rows are unspecified.
+ * The order statistics are exact: a two-rank selection over equal sub-ranges of each row's key range (cssm_intervals.hip), 8 launches
+ * per row and the cloud or its keys read 3 times in the ordinary case; its scratch lives on the handle (allocated at the first call,
+ * freed by cssm_pf_destroy).  The means are cssm_pf_summary's sums, block for block. */
+int cssm_pf_filter_intervals(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T, double interval,
+                             double* ll_out, double* ll_t, int32_t* ess_t,
+                             double* state_mean, double* state_lower, double* state_upper,
+                             double* eta_of_mean, double* eta_lower, double* eta_upper);
+/* The same for T MORE observations of a running filter, as cssm_pf_ll_filter_more continues one: T rows (row s behind record s), no
+ * initial row.  CSSM_ESTATE on a handle that was never initialised.  cssm_pf_filter_intervals(t[0..a)) followed by
+ * cssm_pf_filter_intervals_more(t[a..T)) gives the rows of cssm_pf_filter_intervals(t[0..T)). */
+int cssm_pf_filter_intervals_more(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T, double interval,
+                                  double* ll_out, double* ll_t, int32_t* ess_t,
+                                  double* state_mean, double* state_lower, double* state_upper,
+                                  double* eta_of_mean, double* eta_lower, double* eta_upper);
+/* One streaming step with its row: cssm_pf_step, and the summary of the cloud it leaves, in one call and one synchronisation
+ * (state outputs: d doubles each; any may be NULL).  The row has the bits of cssm_pf_summary called behind cssm_pf_step. */
+int cssm_pf_step_intervals(cssm_pf* pf, double t, double obs, int has_obs, double interval, double* ll_out, int32_t* ess_out,
+                           double* state_mean, double* state_lower, double* state_upper,
+                           double* eta_of_mean, double* eta_lower, double* eta_upper);
+/* Device time of the last of these three calls on the handle, in milliseconds: ms2[0] the whole call (HIP events around everything it
+ * enqueued), ms2[1] the summary launches alone (the GPU's constant 100 MHz clock, stamped by the first block of every row's first
+ * launch and read by its last).  CSSM_ESTATE before the first such call has completed. */
+int cssm_pf_intervals_last_ms(cssm_pf* pf, double* ms2);
+
 /* Forecasts from the current cloud: SimulateData.forecast + summariseForecast (model/Data.scala:196-231) -- the scan of
  * ParticleFilter.getMeanForecast (model/ParticleFilter.scala:389-409) over the future times t[0..H) -- in one call.  The source is
  * exactly the cloud cssm_pf_summary summarises (also between cssm_pf_propagate and cssm_pf_adopt); horizon h starts from the states

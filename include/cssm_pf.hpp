@@ -172,6 +172,14 @@ struct Resampling {
 
 // ParticleFilter.scala:14, :71-78 (one per forecast time: SimulateData.forecast + summariseForecast, Data.scala:196-231)
 struct CredibleInterval { double lower, upper; };
+struct PfOut {                                          // ParticleFilter.scala:20-26
+  double time;
+  std::optional<double> observation;
+  double eta;
+  CredibleInterval etaIntervals;
+  Vec state;
+  std::vector<CredibleInterval> stateIntervals;
+};
 struct ForecastOut {
   double t;
   double obs;
@@ -220,6 +228,42 @@ class Filter {
     for (size_t s = 0; s <= t.size(); ++s) out.push_back({s == 0 ? t0 : t[s - 1], Vec(path.begin() + s * d_, path.begin() + (s + 1) * d_)});
     return {ll, out};
   }
+  // filter, then getIntervals of every emitted state (examples/Filtering.scala:23-32) in one native call: T + 1 entries, the first of the
+  // initial cloud at the data's smallest time without an observation
+  std::pair<double, std::vector<PfOut>> filterIntervals(const std::vector<Data>& data, double interval = 0.975) {
+    Vec t, y; std::vector<uint8_t> has; split(data, t, y, has);
+    const size_t R = t.size() + 1;
+    Vec sm(R * d_), sl(R * d_), su(R * d_), em(R), el(R), eu(R);
+    double ll;
+    check(cssm_pf_filter_intervals(h_, t.data(), y.data(), has.data(), t.size(), interval, &ll, nullptr, nullptr, sm.data(), sl.data(), su.data(),
+                                   em.data(), el.data(), eu.data()));
+    double t0 = t[0];
+    for (double v : t) t0 = std::min(t0, v);
+    std::vector<PfOut> out;
+    for (size_t r = 0; r < R; ++r)
+      out.push_back(pf_out(r == 0 ? t0 : t[r - 1], r == 0 ? std::nullopt : data[r - 1].observation, &sm[r * d_], &sl[r * d_], &su[r * d_], em[r], el[r], eu[r]));
+    return {ll, out};
+  }
+  // ... for MORE records of the running filter (cssm_pf_filter_intervals_more): one entry per record, no initial one
+  std::pair<double, std::vector<PfOut>> filterIntervalsMore(const std::vector<Data>& data, double interval = 0.975) {
+    Vec t, y; std::vector<uint8_t> has; split(data, t, y, has);
+    const size_t R = t.size();
+    Vec sm(R * d_), sl(R * d_), su(R * d_), em(R), el(R), eu(R);
+    double ll;
+    check(cssm_pf_filter_intervals_more(h_, t.data(), y.data(), has.data(), R, interval, &ll, nullptr, nullptr, sm.data(), sl.data(), su.data(),
+                                        em.data(), el.data(), eu.data()));
+    std::vector<PfOut> out;
+    for (size_t r = 0; r < R; ++r) out.push_back(pf_out(t[r], data[r].observation, &sm[r * d_], &sl[r * d_], &su[r * d_], em[r], el[r], eu[r]));
+    return {ll, out};
+  }
+  // stepFilter and getIntervals of the state it returns (cssm_pf_step_intervals)
+  std::pair<PfState, PfOut> stepIntervals(const PfState&, const Data& y, double interval = 0.975) {
+    double ll, em, el, eu; int32_t ess;
+    Vec sm(d_), sl(d_), su(d_);
+    check(cssm_pf_step_intervals(h_, y.t, y.observation.value_or(0.0), y.observation ? 1 : 0, interval, &ll, &ess, sm.data(), sl.data(), su.data(),
+                                 &em, &el, &eu));
+    return {PfState{y.t, y.observation, ll, ess}, pf_out(y.t, y.observation, sm.data(), sl.data(), su.data(), em, el, eu)};
+  }
   Vec particles() { Vec out((size_t)d_ * n_); check(cssm_pf_get_particles(h_, out.data())); return out; }   // SoA [d][N]
   void setParams(const ParamModel& mod, uint64_t seed) { check(cssm_pf_set_params(h_, mod.desc())); check(cssm_pf_reseed(h_, seed)); seed_ = seed; }
   // forecasts of the current cloud at `times` (ParticleFilter.getMeanForecast, :389-409, scanned as Data.scala:196-231) under the
@@ -250,6 +294,11 @@ class Filter {
   cssm_pf* handle() { return h_; }
 
  private:
+  PfOut pf_out(double t, std::optional<double> obs, const double* m, const double* lo, const double* hi, double em, double el, double eu) const {
+    PfOut o{t, obs, em, {el, eu}, Vec(m, m + d_), {}};
+    for (int k = 0; k < d_; ++k) o.stateIntervals.push_back({lo[k], hi[k]});
+    return o;
+  }
   std::vector<ForecastOut> forecast_outs(const Vec& times, const Vec& sm, const Vec& sl, const Vec& su, const Vec& em, const Vec& el,
                                          const Vec& eu, const Vec& om, const Vec& ol, const Vec& ou) const {
     std::vector<ForecastOut> out;
