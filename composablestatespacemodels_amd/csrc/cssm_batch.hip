@@ -145,9 +145,7 @@ static int batch_step(cssm_pf* p0, const ChainBase* d_chains, int B, uint32_t s,
   else hipLaunchKernelGGL((k_offspring_batch<CSSM_RESAMPLE_SYSTEMATIC, 2, false>), dim3(grid, B), dim3(CSSM_BLOCK), 0, p0->stream, OFFB_ARGS);
 #undef OFFB_ARGS
   HIP_TRY(hipGetLastError());
-  p0->wparity = (p0->wparity + 1) % CSSM_MAXSETS;
-  p0->anc_valid = true; p0->wmode = true; p0->have_level = true;
-  p0->s2_par ^= 1;
+  cssm_note_resampled(p0, true);
   return CSSM_OK;
 }
 // the other chains went through exactly what chain 0's bookkeeping records
@@ -195,7 +193,7 @@ extern "C" int cssm_pfb_num_chains(const cssm_pfb* b) { return b ? b->B : 0; }
 extern "C" cssm_pf* cssm_pfb_chain(cssm_pfb* b, int k) { return (b && k >= 0 && k < b->B) ? b->ch[(size_t)k] : nullptr; }
 
 // whether the batched launches serve this handle's configuration (else every chain runs through the single-handle driver)
-static bool batch_serves(const cssm_pf* pf) { return cssm_batch_ok(pf) != 0; }
+static bool batch_serves(const cssm_pf* pf) { return cssm_batch_ok(*pf, *pf) != 0; }
 
 // `filter` (model/ParticleFilter.scala:152-158) of every chain: chain k under descs[k] (the structure the batch was created with)
 // and seeds[k]; ll_out[k], path_out (may be NULL) [k][(T + 1) * d], rc_out[k] = the chain's own status (CSSM_ENONFINITE: its weights
@@ -226,22 +224,14 @@ extern "C" int cssm_pfb_filter(cssm_pfb* b, const cssm_model_desc* const* descs,
     for (int k = 0; k < B; ++k) run_alone(k);
     return CSSM_OK;
   }
-  double t0 = t[0];
-  for (size_t s = 1; s < T; ++s) if (t[s] < t0) t0 = t[s];
+  const double t0 = cssm_series_t0(t, T);
   // records (the chains' parameters differ), the chain table
   for (int k = 0; k < B; ++k) {
     cssm_pf* pf = b->ch[(size_t)k];
     int rc = cssm_ensure_recs(pf, T);
     if (rc) return rc;
-    if (want_path && pf->path_cap < (T + 1) * (size_t)d) {
-      HIP_TRY(hipStreamSynchronize(b->stream));
-      if (pf->d_path) (void)hipFree(pf->d_path);
-      pf->d_path = nullptr;
-      HIP_TRY(hipMalloc(&pf->d_path, (T + 1) * (size_t)d * 8));
-      pf->path_cap = (T + 1) * (size_t)d;
-    }
-    double tp = t0;
-    for (size_t s = 0; s < T; ++s) { cssm_build_rec(pf, tp, t[s], y[s], has ? has[s] : 1, (uint32_t)s, &pf->h_recs[s]); tp = t[s]; }
+    if (want_path) { rc = cssm_ensure_path(pf, T); if (rc) return rc; }
+    cssm_build_recs(pf, t0, t, y, has, 0, T, 0u);
     rc = cssm_upload_recs(pf, 0, T, false);
     if (rc) return rc;
     cssm_batch_fresh(pf, t0);                 // host-side state of a freshly drawn cloud; gen, done_seq advanced

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "cssm_host.h"
+#include "cssm_launch_plan.h"
 
 #define fail cssm_fail
 #define HIP_TRY(expr)                                                                         \
@@ -60,34 +61,22 @@ struct CssmTemps {
 #define CSSM_NKERNELS CSSM_PROFILE_NKERNELS
 
 
-struct cssm_pf : HostModel {
+// (CssmLaunchFields: the sizes, options and running state every launch decision reads -- cssm_launch_plan.h)
+struct cssm_pf : HostModel, CssmLaunchFields {
   int device = 0;
   int n_cus = 256;             // compute units of the device (launch geometry decisions)
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  // sizes
-  uint64_t first = 0, n = 0;   // (n_global, seed: HostModel)
-  size_t stride = 0;
-  uint32_t ntiles = 0;
-  uint32_t sup = 1, nunits = 0;   // tiles per scan unit, number of units (<= ~1K)
-  uint32_t split = 1;             // k_propagate blocks per unit (each owns a contiguous sub-unit and its sums)
-  bool safe_sums = false;         // form the sums in their own pass after the max is known (retry of a step whose
-                                  // reference level was ruled out by the max; always for LGCP)
-  bool last_optimistic = false;   // the last launch_propagate formed the sums itself (and stored weights in place of log-weights)
   bool wmode = false;             // the log-weight buffer holds the WEIGHTS exp(min(w - c, 2^-20)) of the last weighted observation
-  bool have_level = false;        // LGCP (contract v8): a weighted observation has run natively since the cloud was drawn / adopted -- its
-                                  //   publisher left the next observation's predicted level (Scalars::next_ref), so the propagate may form the sums
   bool sums_ready = false;        // sharded: the unit sums of the last propagated observation exist (k_propagate<SUMS> or cssm_pf_shard_sums)
   // ESS pending (Scalars::pend): k_offspring's blocks leave partial sums of squared weights in s2buf[par * s2_stride + block]
   cssm_u128* s2buf = nullptr;     // 2 x s2_stride entries
-  uint32_t s2_stride = 0;
-  int s2_par = 0;                 // buffer the next weighted observation's k_offspring writes
+  uint32_t s2_stride = 0;          // (= nsums)
   uint32_t gen = 0;               // generation of the batch call / streaming step that owns d_ess_t
   int32_t ess_host = 0;           // ESS of the last completed observation as the host knows it
   void* last_comm = nullptr;      // RCCL communicator the library last enqueued collectives on (bounded_sync)
   std::vector<double> h_fsub;     // host copy of the sub-step coefficient table of the records last built
   double* d_fsub = nullptr; size_t fsub_cap = 0;
-  bool sharded = false;
   // device memory
   double* state[2] = {nullptr, nullptr};
   int cur = 0;                 // state[cur] = propagated cloud of the last step (x1)
@@ -100,22 +89,11 @@ struct cssm_pf : HostModel {
   uint32_t* endslot = nullptr;
   uint32_t* anc = nullptr;
   bool anc_valid = false;
-  int wparity = 0;             // max-slot set (0 .. CSSM_MAXSETS - 1) of the next weighted step (single-GPU path); a shard: the set of GROUP
-                               //   sums (Scalars::grp / grp2) of the next weighted observation -- its max slots stay in set 0
   int opt_exact = 0;           // CSSM_OPT_EXACT_OFFSPRING
-  int opt_fused = 0;           // CSSM_OPT_FUSED_SUMS (set to 1 for sharded handles at creation)
   cssm_u128 *fineS = nullptr, *fineS2 = nullptr;   // large clouds: the sums of k_propagate's single-tile blocks (k_reduce_units folds them into tileS / tileS2)
   size_t fine_cap = 0;
-  int opt_whole = 0;           // CSSM_OPT_WHOLE_TILES
-  int opt_grp = 1;             // CSSM_OPT_GROUP_SUMS
-  uint32_t grp_min_units = 2u * CSSM_GRP_UNITS;   // smallest cloud (in units) whose propagate accumulates group sums (CSSM_GRP_MIN_UNITS: tests run small clouds through them)
   int opt_spec = 1;            // CSSM_OPT_SPECIALISE
-  bool last_grp = false;       // the last launch_propagate's blocks accumulated the sums of groups of units (Scalars::grp)
-  int grp_layout = 0;          // ... in layout 1 (<= 32 groups of 32 units) or 2 (<= 64 groups of 64 units); 0: not at all
-  bool last_ws = false;        // ... and its waves stored the exact sums of their quarter units (tileW): k_offspring_wave may run
-  int opt_wave = 1;            // CSSM_OPT_WAVE_SUMS
   cssm_u128* tileW = nullptr;  // four per unit: the quarter units' sums (k_propagate_self<..., SUMS = 1, ONE = 2>, bit 13 of its set argument)
-  int resampler = CSSM_RESAMPLE_SYSTEMATIC;
   double* cum = nullptr;       // multinomial: cumulative normalised weights
   const long long *send_first_dev = nullptr, *send_count_dev = nullptr;   // last shard_offspring outputs (device)
   cssm_u128 *tileS = nullptr, *tileS2 = nullptr, *tileP = nullptr;
@@ -257,6 +235,11 @@ static const int kGridCap = 4096;
 // ---- defined in cssm_pf.hip, used by cssm_shard.hip as well
 int cssm_build_fsub(cssm_pf* pf, size_t first, size_t count, bool reset);   // sub-step table of records [first, +count) -> device
 int cssm_ensure_recs(cssm_pf* pf, size_t T);
+double cssm_series_t0(const double* t, size_t T);   // the time of a series' initial cloud: its earliest
+// records [first, first + count) of a series into h_recs, record s as observation base + s; t_prev: the time before record 0
+void cssm_build_recs(cssm_pf* pf, double t_prev, const double* t, const double* y, const uint8_t* has, size_t first, size_t count, uint32_t base);
+int cssm_ensure_path(cssm_pf* pf, size_t T);        // d_path holds the T + 1 states of a sampled path
+void cssm_note_resampled(cssm_pf* pf, bool optimistic);   // the handle's bookkeeping behind a resampling launch
 int cssm_upload_recs(cssm_pf* pf, size_t first, size_t count, bool chain);   // records -> device (+ the predicted level of the first one: LGCP)
 int cssm_launch_init(cssm_pf* pf, double t0);
 // batched launch (cssm_batch.hip): the chains of the launch; `pf` is chain 0, whose bookkeeping stands for all of them
@@ -264,9 +247,7 @@ struct CssmBatchLaunch { const void* chains; int nchains; uint32_t rec_idx; int 
 int cssm_launch_propagate(cssm_pf* pf, const StepRec* d_rec, double* pick_out = nullptr, uint32_t pick_slot = 0, const CssmBatchLaunch* batch = nullptr);
 int cssm_pf_create_on_stream(const cssm_model_desc* desc, uint64_t n_particles, uint64_t seed, int device, hipStream_t stream, cssm_pf** out);
 void cssm_batch_fresh(cssm_pf* pf, double t0);   // host-side state of a freshly drawn cloud; the call's generation and completion number
-int cssm_batch_ok(const cssm_pf* pf);            // the batched launches serve this handle's configuration
 int cssm_check_device_err(cssm_pf* pf, const Scalars& h);
-int cssm_prop_items(int d);   // PropItems<D>
 int cssm_use_device(int device);   // the device exists and is current, or the error
 double cssm_eta_of_mean(const HostModel& m, const double* fco, const double* mean);   // link(f(stateMean, t)), ParticleFilter.scala:420
 void cssm_peer_free(cssm_pf* pf);   // cssm_shard.hip: the peer-written exchange's windows, mappings and device table

@@ -542,11 +542,7 @@ static int iv_filter(cssm_pf* pf, const double* t, const double* y, const uint8_
   if (cont && !pf->initialised) return fail(CSSM_ESTATE, "continuing a filter needs an initialised handle (and records no path)");
   std::vector<double> times;
   times.reserve(T + 1);
-  if (!cont) {
-    double t0 = t[0];
-    for (size_t q = 1; q < T; ++q) if (t[q] < t0) t0 = t[q];
-    times.push_back(t0);
-  }
+  if (!cont) times.push_back(cssm_series_t0(t, T));
   times.insert(times.end(), t, t + T);
   rc = iv_begin(pf, times, interval);
   if (rc) return rc;

@@ -289,7 +289,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(CSSM_BLOCK, CSSM_BLOCK), a
     // noted and redone behind the loop through the contract's predicate on exact sums (see below) -- inlined at this point that path's
     // registers (128-bit sums, a division, the counting loops) took the kernel from 63 vector registers to 110.
     const bool deferred = force_exact != 0 || __any(unsafe != 0u || prev_unsafe);
-    if (deferred) cold |= 1u << ((base - w_lo) >> 8);
+    // (a bit per chunk of the wave's quarter unit; the host turns the wave sums on for units of at most CSSM_GRP_MAX_UNIT particles only:
+    //  want_ws, cssm_launch_plan.cpp)
+    static_assert(CSSM_TILE / 4 == 256 && CSSM_GRP_MAX_UNIT / CSSM_TILE <= 32, "cold: one bit per chunk of 256 particles, at most 32 chunks per quarter unit");
+    if (deferred) cold |= 1u << ((base - w_lo) / (uint32_t)(CSSM_TILE / 4));
     else {
     // the slots this wave's 256 particles own, assembled in the wave's LDS region and written as whole lines
     uint32_t wb = (uint32_t)__builtin_amdgcn_readfirstlane((int)prev);

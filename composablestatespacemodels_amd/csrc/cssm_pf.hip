@@ -49,38 +49,11 @@ int cssm_build_fsub(cssm_pf* pf, size_t first, size_t count, bool reset) {
 
 // ------------------------------------------------------------------------------------ create / destroy
 
-#ifndef CSSM_PROP_IT_LO
-#define CSSM_PROP_IT_LO 2
-#endif
-#ifndef CSSM_SPLIT_MAX_N
-#define CSSM_SPLIT_MAX_N (1u << 20)
-#endif
-int cssm_prop_items(int d) { return d <= 2 ? CSSM_PROP_IT_LO : (d <= 8 ? CSSM_PROP_IT_MID : 1); }   // PropItems<D>
-
-// k_propagate blocks per 1024-particle unit on a single-GPU handle: one tile of the kernel per block below 2^20 particles
-static uint32_t auto_split(const cssm_pf* pf) {
-  // (measured and dropped: a shard of an LGCP filter on blocks of 1024 particles where a unit has 2048 -- k_propagate 71.8 -> 68.4 us at
-  //  2^21 particles per rank, one round of whole-unit blocks running in lockstep being 12 % slower per particle than the same kernel on
-  //  several rounds; but the exchange kernel's header and prefix blocks, which every block of every rank waits for, then total twice
-  //  the sums: 18.5 -> 20.4 us, the step 89.5 -> 90.3)
-  if (pf->sharded) {
-    // an LGCP shard whose units have several tiles: blocks of HALF a unit -- whole-unit blocks all start together (1024 of them, one
-    // round) and run in lockstep, so every memory wait of the prologue and of the tile boundaries is exposed; half-unit blocks run in
-    // two staggered rounds (k_propagate 71.8 -> 68.4 us at 2^21 particles per rank).  The exchange kernels do not see the difference
-    // any more: they read the sums of groups of units (Scalars::grp), to which every block adds its own.  CSSM_SHARD_LGCP_SPLIT: 1, 2, 4.
-    if (pf->obs_kind != CSSM_OBS_LGCP || pf->sup < 2) return 1u;
-    uint32_t want = 2u;
-    if (const char* e = getenv("CSSM_SHARD_LGCP_SPLIT")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) want = (uint32_t)v; }
-    // (whole tiles of 1024: the exchange's pack blocks take the prefix of a boundary block's tiles from the blocks' sums only then --
-    //  quarter-unit blocks of 512 particles at 2^21 per rank sent them down their recompute path: 39 us per exchange)
-    while (want > 1u && ((uint64_t)pf->sup * CSSM_TILE / want) % (uint64_t)CSSM_TILE != 0) want >>= 1;
-    const uint64_t unit_particles = (uint64_t)pf->sup * CSSM_TILE;
-    if (!(pf->opt_grp && pf->nunits >= pf->grp_min_units && pf->nunits <= (uint32_t)(CSSM_GRP_SMALL * CSSM_GRP_UNITS) && unit_particles <= CSSM_GRP_MAX_UNIT)) want = 1u;   // (no group sums: whole units)
-    return want;
-  }
-  if (pf->sup != 1 || pf->n >= CSSM_SPLIT_MAX_N) return 1u;
-  return cssm_prop_items(pf->d) == 1 ? 4u : 2u;   // one tile of the kernel: half of 1024 (two particles per thread), a quarter (one)
-}
+// the kernels' constants as the host-only launch plan mirrors them (cssm_launch_plan.h)
+static_assert(CSSM_PLAN_BLOCK == CSSM_BLOCK && CSSM_PLAN_TILE == CSSM_TILE && CSSM_PLAN_MAXSETS == CSSM_MAXSETS && CSSM_PLAN_GRP_UNITS == CSSM_GRP_UNITS &&
+              CSSM_PLAN_GRP_MAX == CSSM_GRP_MAX && CSSM_PLAN_GRP_SMALL == CSSM_GRP_SMALL && CSSM_PLAN_GRP_MAX_UNIT == CSSM_GRP_MAX_UNIT &&
+              CSSM_PLAN_PROP_IT_MID == CSSM_PROP_IT_MID,
+              "cssm_launch_plan.h mirrors the kernels' constants");
 
 static int alloc_handle(cssm_pf* pf) {
   HIP_TRY(hipSetDevice(pf->device));
@@ -94,36 +67,12 @@ static int alloc_handle(cssm_pf* pf) {
   { const char* e = getenv("CSSM_WAVE_SUMS"); if (e) pf->opt_wave = atoi(e) == 2 ? 2 : (atoi(e) ? 1 : 0); }   // (A/B: the default of CSSM_OPT_WAVE_SUMS)
   { const char* e = getenv("CSSM_GRP_MIN_UNITS"); if (e && atoi(e) >= 1) pf->grp_min_units = (uint32_t)atoi(e); }   // (tests: small clouds through the group sums)
   HIP_TRY(hipDeviceGetAttribute(&pf->n_cus, hipDeviceAttributeMultiprocessorCount, pf->device));
-  pf->stride = (size_t)((pf->n + CSSM_TILE - 1) / CSSM_TILE) * CSSM_TILE;   // rows start 16-B aligned
-  pf->ntiles = (uint32_t)((pf->n + CSSM_TILE - 1) / CSSM_TILE);
-  pf->sup = (pf->ntiles + 1023u) / 1024u;
-  // Single GPU, clouds beyond 2^22 particles: units of 4 tiles while that gives at most 4096 of them (2^23: 2048 units, 2^24: 4096), larger
-  // units beyond -- instead of 1024 units of ever more tiles (16 at 2^24: 1025 k_offspring blocks walking 16 tiles each through three
-  // barriers per tile, 1024 k_propagate blocks on 1536 resident slots at d = 1).  k_offspring finds its prefix through the sums of up
-  // to 64 groups of 64 units (Scalars::grp, layout 2).  A shard keeps at most 1024 units (its exchange kernels' geometry).
-  // CSSM_UNIT_MAX_TILES (A/B): the tiles per unit to aim for (default 4; 0: the old rule).
-  if (!pf->sharded && pf->sup > 4u) {
-    uint32_t want = 4u;
-    if (const char* e = getenv("CSSM_UNIT_MAX_TILES")) want = (uint32_t)atoi(e);
-    if (want >= 1u) {
-      const uint32_t least = (pf->ntiles + (uint32_t)(CSSM_GRP_MAX * 64) - 1u) / (uint32_t)(CSSM_GRP_MAX * 64);   // at most 4096 units
-      const uint32_t sup2 = want > least ? want : least;
-      if (sup2 < pf->sup) pf->sup = sup2;
-    }
+  {   // the geometry: cssm_launch_plan.cpp (the two A/B variables are read here)
+    const char* e = getenv("CSSM_UNIT_MAX_TILES");
+    const char* e2 = getenv("CSSM_SHARD_LGCP_SPLIT");
+    cssm_plan_geometry(*pf, *pf, e ? (uint32_t)atoi(e) : 4u, e2 ? atoi(e2) : 0);
   }
-  pf->nunits = (pf->ntiles + pf->sup - 1) / pf->sup;
-  {   // k_propagate: a block owns unit/split particles, a multiple of its CSSM_BLOCK * IT particles per iteration
-    // (the kernel pipelines its tiles through LDS and wants several of them: one block per unit)
-    // Clouds below 2^20 particles on one GPU: one tile of the kernel per block.  Up to ~2^18 particles every SIMD holds at
-    // most one or two waves and a kernel's duration is the length of ONE wave's dependent instruction stream (~3 ns per
-    // instruction, tools/launch_floor.hip; the launch itself is 3.1 us): one pair of particles per thread instead of two, in the
-    // single-tile instantiation k_propagate_self<..., ONE> that requests everything position-dependent in its first round of
-    // loads and draws its normals while the gathered rows travel.  Per observation, bench model, same process (tools/ab_fine.py):
-    // 17.1 -> 12.6 us at N = 100 000, 21.9 -> 19.3 at 2^19, 28.1 -> 25.8 at 3 * 2^18.  From 2^20 particles on: whole units per
-    // block (launch_propagate).
-    pf->split = auto_split(pf);
-  }
-  const size_t nsums = (size_t)(pf->ntiles > 4 * pf->nunits ? pf->ntiles : 4 * pf->nunits);   // (up to four sub-units per unit)
+  const size_t nsums = pf->nsums;
   const size_t row = pf->stride * 8;
   for (int b = 0; b < 2; ++b) {
     if (hipMalloc(&pf->state[b], row * pf->d + 64) != hipSuccess)   // + spare bytes: k_propagate fetches 16 bytes per element
@@ -291,17 +240,6 @@ int cssm_launch_init(cssm_pf* pf, double t0) {
 
 // propagate + weight of one datum (record already on the device)
 
-// whether launch_propagate will use the kernels that also form the sums (and can record sampleOne's pick on the way)
-// (LGCP, contract v8: once a weighted observation has run natively its max predicts the next one's level -- Scalars::next_ref --
-//  and the sums are formed inside the propagate like everybody else's; the first observation's level is its max)
-static bool uses_sums_kernel(const cssm_pf* pf) {
-  return pf->opt_fused && !pf->safe_sums && (pf->obs_kind != CSSM_OBS_LGCP || pf->have_level) && pf->resampler != CSSM_RESAMPLE_MULTINOMIAL;
-}
-// ... ever, in the series that is being enqueued (whether an observation can put it on hold)
-static bool may_use_sums_kernel(const cssm_pf* pf) {
-  return pf->opt_fused && !pf->safe_sums && pf->resampler != CSSM_RESAMPLE_MULTINOMIAL;
-}
-
 // Records [first, first + count) of the handle's host buffer -> the device.  chain (the records CONTINUE a running filter): where
 // the level is predicted from the observation before (LGCP: StepRec::predict) the first record's comes from Scalars::next_ref,
 // on the stream; later records of the call get theirs from the kernels that publish their predecessors (publish_next_level).
@@ -351,39 +289,10 @@ int cssm_upload_recs(cssm_pf* pf, size_t first, size_t count, bool chain) {
   return CSSM_OK;
 }
 
-// Launch geometry of the sums kernels on clouds of 2^20 particles and more (one GPU; whole units of 1024 * sup particles).
-// In-process A/B (tools/ab_opt.py option 6, tools/ab_fine.py; per observation; boxes of this pool differ by +-5 %, only runs of
-// one process compare):
-//   LOOP    one block per unit running the single-tile-style kernel tile after tile (k_propagate_self<..., ONE>: no software-
-//           pipeline state, no spill, 5-6 waves per SIMD; co-resident waves cover the round trips).  While a block has at most
-//           CSSM_LOOP_MAX_TILES tiles it beats everything else: d = 3: 31.0 vs 33.2 (half tiles) / 32.5 (pipelined) us at 2^20,
-//           50.7 vs 53.3 at 2^21, 90.0 vs 93.0 at 2^22, a tie at 2^23, 376 vs 368 at 2^24; d = 1: 23.6 vs 26.9 at 2^20, a tie at 2^22,
-//           252 vs 241 at 2^24; d = 4: 108 vs 120 at 2^22; d = 9: 57.6 vs 63.4 at 2^20, 105 vs 114 at 2^21; d = 16 at 2^22 (16 tiles): 329 vs 313.
-//   FINE    one tile per block + k_reduce_units (~5 us): larger clouds of d >= 4 (d = 9: 194 vs 203 us pipelined at 2^22; d = 16: 287 vs 343)
-//   PIPE    one block per unit, the software-pipelined kernel: larger clouds of d <= 3 (a tie with FINE at d = 3, a few per cent better at d <= 2)
-#ifndef CSSM_FINE_MIN_D
-#define CSSM_FINE_MIN_D 4
-#endif
-#ifndef CSSM_LOOP_MAX_TILES
-#define CSSM_LOOP_MAX_TILES 8
-#endif
-enum { GEO_PIPE = 0, GEO_LOOP = 1, GEO_FINE = 2 };
-static int large_geometry(const cssm_pf* pf) {
-  if (pf->sharded || pf->split != 1 || pf->first != 0 || pf->n != pf->n_global || pf->resampler == CSSM_RESAMPLE_MULTINOMIAL) return GEO_PIPE;
-  if (pf->opt_whole == 1) return GEO_LOOP;
-  if (pf->opt_whole == 2) return GEO_PIPE;
-  if (pf->opt_whole == 3) return GEO_FINE;
-  const uint32_t tiles = pf->sup * (uint32_t)CSSM_TILE / (uint32_t)(CSSM_BLOCK * cssm_prop_items(pf->d));
-  if (tiles <= CSSM_LOOP_MAX_TILES) return GEO_LOOP;
-  return pf->d >= CSSM_FINE_MIN_D ? GEO_FINE : GEO_PIPE;
-}
-
 void cssm_batch_fresh(cssm_pf* pf, double t0) { fresh_host_state(pf, t0); pf->gen++; pf->done_seq++; }
-int cssm_batch_ok(const cssm_pf* pf) {
-  return pf->opt_fused && !pf->safe_sums && pf->obs_kind != CSSM_OBS_LGCP && pf->resampler == CSSM_RESAMPLE_SYSTEMATIC && !pf->sharded &&
-         large_geometry(pf) != GEO_FINE;
-}
 
+// One propagate launch: every decision is cssm_plan_propagate's (cssm_launch_plan.cpp); this function checks the record, grows the
+// per-block sums the plan asks for, hands plan and pointers to the dispatcher of the handle's dimension and records what it reports.
 int cssm_launch_propagate(cssm_pf* pf, const StepRec* d_rec, double* pick_out, uint32_t pick_slot, const CssmBatchLaunch* batch) {
   // The observation's index travels as a kernel argument (the slim kernels use it before any load lands): every record a
   // propagate is launched on lives in the handle's record buffer, and the HOST copy of that record -- h_recs mirrors d_recs from
@@ -392,77 +301,40 @@ int cssm_launch_propagate(cssm_pf* pf, const StepRec* d_rec, double* pick_out, u
   // anything of the handle changes: a refused launch leaves no trace.
   if (!pf->h_recs || d_rec < pf->d_recs || d_rec >= pf->d_recs + std::min(pf->h_recs_cap, pf->recs_cap))
     return fail(CSSM_ESTATE, "propagate launched on a record outside the handle's record buffer");
-  const uint32_t rec_step = pf->h_recs[d_rec - pf->d_recs].step;
-  // one block per sub-unit: contiguous ranges, so that (with do_sums) the block's fixed-point sums are the
-  // sub-unit sums k_offspring scans
-  uint64_t chunk = (uint64_t)pf->sup * CSSM_TILE / pf->split;
-  double* dst = pf->state[pf->cur ^ 1];
-  const uint32_t* anc = pf->anc_valid ? pf->anc : nullptr;
-  const int do_sums = uses_sums_kernel(pf) ? 1 : 0;
-  pf->last_optimistic = do_sums != 0;
-  const int geo = do_sums ? large_geometry(pf) : GEO_PIPE;
-  const bool fine = geo == GEO_FINE;
-  const uint64_t unit_particles = (uint64_t)pf->sup * CSSM_TILE;
-  if (fine) chunk = (uint64_t)CSSM_BLOCK * cssm_prop_items(pf->d);   // (divides the unit: 1024 * sup)
-  const int grid = (int)((pf->n + chunk - 1) / chunk);
-  if (fine && pf->fine_cap < (size_t)grid) {
+  PropLaunch a;
+  a.step = pf->h_recs[d_rec - pf->d_recs].step;
+  a.anc = pf->anc_valid ? pf->anc : nullptr;
+  a.src2 = a.anc ? pf->src2 : nullptr; a.src2_stride = pf->src2_stride; a.n_split = pf->n_split; a.logtab = pf->d_logtab;
+  a.fsub = pf->lgcp_tdep ? pf->d_fsub : nullptr;
+  CssmPropFacts facts;
+  facts.batch = batch != nullptr; facts.pick = pick_out != nullptr; facts.src2 = a.src2 != nullptr; facts.src2_stride = a.src2_stride; facts.fsub = a.fsub != nullptr;
+  const CssmPropPlan plan = cssm_plan_propagate(*pf, *pf, facts);
+  pf->last_optimistic = plan.do_sums != 0;
+  if (plan.reduce && pf->fine_cap < (size_t)plan.grid) {
     HIP_TRY(hipStreamSynchronize(pf->stream));
     if (pf->fineS) (void)hipFree(pf->fineS);
     if (pf->fineS2) (void)hipFree(pf->fineS2);
     pf->fineS = pf->fineS2 = nullptr; pf->fine_cap = 0;
-    if (hipMalloc(&pf->fineS, (size_t)grid * sizeof(cssm_u128)) != hipSuccess || hipMalloc(&pf->fineS2, (size_t)grid * sizeof(cssm_u128)) != hipSuccess)
-      return fail(CSSM_ENOMEM, "hipMalloc of the per-block sums (%d blocks)", grid);
-    pf->fine_cap = (size_t)grid;
+    if (hipMalloc(&pf->fineS, (size_t)plan.grid * sizeof(cssm_u128)) != hipSuccess || hipMalloc(&pf->fineS2, (size_t)plan.grid * sizeof(cssm_u128)) != hipSuccess)
+      return fail(CSSM_ENOMEM, "hipMalloc of the per-block sums (%d blocks)", plan.grid);
+    pf->fine_cap = (size_t)plan.grid;
   }
   prof_begin(pf, CSSM_K_PROPAGATE);
-  PropLaunch a;
   a.chains = nullptr; a.nchains = 0; a.cur = pf->cur; a.anc_valid = pf->anc_valid ? 1 : 0; a.want_pick = 0; a.rec_idx = 0;
   if (batch) { a.chains = batch->chains; a.nchains = batch->nchains; a.want_pick = batch->want_pick; a.rec_idx = batch->rec_idx; }
-  a.grid = grid; a.stream = pf->stream;
+  a.grid = plan.grid; a.stream = pf->stream;
   a.lgcp = pf->obs_kind == CSSM_OBS_LGCP;
   a.sharded = pf->sharded ? 1 : 0;
   a.obs = (pf->obs_kind == CSSM_OBS_POISSON || pf->obs_kind == CSSM_OBS_GAUSSIAN) ? pf->obs_kind : -1;
-  a.sums = do_sums;
-  a.src = pf->src; a.src_stride = pf->src_stride; a.anc = anc; a.dst = dst; a.dst_stride = pf->stride; a.logw = pf->logw;
+  a.sums = plan.do_sums;
+  a.src = pf->src; a.src_stride = pf->src_stride; a.dst = pf->state[pf->cur ^ 1]; a.dst_stride = pf->stride; a.logw = pf->logw;
   a.n = pf->n; a.gid0 = pf->first; a.seed = pf->seed; a.rec = d_rec; a.mk = pf->mk; a.sc = pf->sc;
-  a.slot_set = pf->sharded ? 0 : pf->wparity;
-  // one fused-sums block per unit of a single-GPU cloud: the blocks also accumulate the sums of groups of 32 units (Scalars::grp,
-  // bit 8 of the set argument of k_propagate_self and k_offspring_self), which k_offspring then reads instead of every unit sum
-  // (a shard: the same, in Scalars::grp and grp2 -- both sums travel in the exchange's headers --, the set rotating with the handle's
-  //  weighted observations while its max slots stay in set 0; the exchange kernels read 32 group sums instead of every unit sum)
-  // layout 1: at most 32 groups of 32 units; layout 2 (single GPU, not the batched chains): at most 64 groups of 64 units
-  const bool big = pf->nunits > (uint32_t)(CSSM_GRP_SMALL * CSSM_GRP_UNITS);
-  pf->last_grp = do_sums && !fine && chunk * pf->split == unit_particles && (pf->sharded ? pf->split <= 4u : (pf->split == 1 && pf->first == 0 && pf->n == pf->n_global)) &&
-                 pf->nunits >= pf->grp_min_units && (big ? (!pf->sharded && batch == nullptr && pf->nunits <= (uint32_t)(CSSM_GRP_MAX * 64)) : true) &&
-                 unit_particles <= CSSM_GRP_MAX_UNIT && pf->opt_grp;
-  pf->grp_layout = pf->last_grp ? (big ? 2 : 1) : 0;
-  const bool want_grp = pf->last_grp;
-  // bits 11-12: log2(blocks per group / 32) -- the blocks per unit of a shard's split launch, or the 64-unit groups of layout 2
-  if (want_grp) a.slot_set |= 0x100 | (pf->wparity << 9) | ((big ? 1 : (pf->split == 4u ? 2 : (pf->split == 2u ? 1 : 0))) << 11);
-  // ... and, on the single GPU's tile-after-tile launch behind systematic resampling, the exact sums of the waves' quarter units (bit 13;
-  // the array travels in the slot of the sums of squares, which these kernels leave to k_offspring): k_offspring_wave then needs neither
-  // a conversion nor a 128-bit scan per weight (CSSM_OPT_WAVE_SUMS = 0: k_offspring_self as before)
-  const bool want_ws = want_grp && geo == GEO_LOOP && !pf->sharded && batch == nullptr && pf->resampler == CSSM_RESAMPLE_SYSTEMATIC &&
-                       pf->obs_kind != CSSM_OBS_LGCP && pick_out == nullptr && 4 * (size_t)pf->nunits <= (size_t)pf->s2_stride &&
-                       // (where it pays: units of several tiles -- clouds beyond 2^20 particles: at one tile per unit the resampling kernel gains
-                       //  nothing back -- and at most two latent components: a block on wave ranges streams 4 x (d rows + weights) ranges instead
-                       //  of d + 1, and from d = 3 on the propagate loses to that what the resampling kernel gains (same-box A/B of round 6: the
-                       //  step -1.2 % on slower boxes, +0-5 % on the fastest, where the block-wide propagate runs at 0.68 of the HBM peak; d = 1:
-                       //  -4.8 % .. 0).  CSSM_OPT_WAVE_SUMS = 2 forces it wherever the geometry allows.)
-                       (pf->opt_wave == 2 || (pf->opt_wave != 0 && pf->sup >= 2u && pf->d <= 2));
-  if (want_ws) a.slot_set |= 0x2000;
-  a.src2 = anc ? pf->src2 : nullptr; a.src2_stride = pf->src2_stride; a.n_split = pf->n_split; a.logtab = pf->d_logtab;
-  a.chunk = chunk; a.do_sums = do_sums; a.subS = fine ? pf->fineS : pf->tileS; a.subS2 = want_ws ? pf->tileW : (fine ? pf->fineS2 : pf->tileS2);
+  a.slot_set = plan.slot_set;
+  // (the waves' sums travel in the slot of the sums of squares, which those kernels leave to k_offspring)
+  a.chunk = plan.chunk; a.do_sums = plan.do_sums; a.subS = plan.reduce ? pf->fineS : pf->tileS; a.subS2 = plan.want_ws ? pf->tileW : (plan.reduce ? pf->fineS2 : pf->tileS2);
   a.pick_out = pick_out; a.pick_slot = pick_slot;
-  a.step = rec_step;
-  a.fsub = pf->lgcp_tdep ? pf->d_fsub : nullptr;
-  a.one = (chunk == (uint64_t)CSSM_BLOCK * cssm_prop_items(pf->d)) ? 1 : (geo == GEO_LOOP ? 2 : 0);
+  a.one = plan.one; a.shard_slim = plan.shard_slim;
   a.specialise = pf->opt_spec; a.obs_kind = pf->obs_kind;
-  // sharded handle on the single-collective exchange (received rows read in place: src2_stride == 0) or before its first exchange:
-  // slim launch, tile after tile while a unit has at most CSSM_LOOP_MAX_TILES tiles; whole pairs per thread (d <= 8) need an even first id
-  a.shard_slim = pf->sharded && do_sums && !a.lgcp && (a.src2 == nullptr || a.src2_stride == 0) && a.fsub == nullptr && pick_out == nullptr &&
-                 ((pf->first & 1ull) == 0ull || cssm_prop_items(pf->d) == 1) && (a.slot_set & 0xff) == 0;
-  if (a.shard_slim && pf->sup * (uint32_t)CSSM_TILE / (uint32_t)(CSSM_BLOCK * cssm_prop_items(pf->d)) <= CSSM_LOOP_MAX_TILES) a.one = 2;
   int launched = 0;   // CSSM_PROP_LAUNCHED_* of the kernel the dispatcher chose
   switch (pf->d) {
 #define CSSM_CASE_PROP(D) case D: launched = cssm_prop_launch_d##D(a); break;
@@ -472,13 +344,14 @@ int cssm_launch_propagate(cssm_pf* pf, const StepRec* d_rec, double* pick_out, u
 #undef CSSM_CASE_PROP
   }
   // k_offspring reads the group sums only where the kernel that ran accumulated them (the unit sums exist either way)
-  pf->last_grp = want_grp && (launched & CSSM_PROP_LAUNCHED_GRP) != 0;
-  pf->last_ws = pf->last_grp && want_ws && (launched & CSSM_PROP_LAUNCHED_WS) != 0;
+  pf->last_grp = plan.want_grp && (launched & CSSM_PROP_LAUNCHED_GRP) != 0;
+  pf->grp_layout = plan.grp_layout;
+  pf->last_ws = pf->last_grp && plan.want_ws && (launched & CSSM_PROP_LAUNCHED_WS) != 0;
   prof_end(pf);
-  if (fine) {   // the blocks' sums -> the units' (the kernel itself skips unweighted observations and series on hold)
+  if (plan.reduce) {   // the blocks' sums -> the units' (the kernel itself skips unweighted observations and series on hold)
     prof_begin(pf, CSSM_K_REDUCE);
-    hipLaunchKernelGGL(k_reduce_units, dim3((pf->nunits + CSSM_BLOCK / 64 - 1) / (CSSM_BLOCK / 64)), dim3(CSSM_BLOCK), 0, pf->stream,
-                       (const cssm_u128*)pf->fineS, (const cssm_u128*)nullptr, (uint32_t)grid, (uint32_t)(unit_particles / chunk), pf->nunits,
+    hipLaunchKernelGGL(k_reduce_units, dim3(plan.reduce_grid), dim3(CSSM_BLOCK), 0, pf->stream,
+                       (const cssm_u128*)pf->fineS, (const cssm_u128*)nullptr, (uint32_t)plan.grid, plan.reduce_per_unit, pf->nunits,
                        pf->tileS, pf->tileS2, (const Scalars*)pf->sc, d_rec);   // (single GPU: the squares are k_offspring's)
     prof_end(pf);
   }
@@ -488,9 +361,19 @@ int cssm_launch_propagate(cssm_pf* pf, const StepRec* d_rec, double* pick_out, u
   return CSSM_OK;
 }
 
+// the handle's bookkeeping behind a resampling launch (cssm_batch.hip's too)
+void cssm_note_resampled(cssm_pf* pf, bool optimistic) {
+  pf->wparity = (pf->wparity + 1) % CSSM_MAXSETS;
+  pf->anc_valid = true;
+  pf->wmode = optimistic;
+  pf->have_level = true;        // (the publisher of this launch leaves the next observation's predicted level: LGCP)
+  if (optimistic) pf->s2_par ^= 1;
+}
+
 // sums (unless k_propagate formed them) -> end slots -> ancestors, single GPU.  After a k_propagate<SUMS> the buffer holds the
 // weights themselves (raw = 2) and k_offspring forms the sum of squares on the way: that observation's ESS stays pending until
 // the next weighted observation's publisher block, or the host at the end of the call, totals the blocks' partials.
+// Which kernels run is cssm_plan_resample's decision (cssm_launch_plan.cpp).
 // (allow_grp = false: a REDONE observation -- the set of group sums it would add to still holds the sums of its first attempt)
 static int launch_resample(cssm_pf* pf, const StepRec* d_rec, double* ll_t = nullptr, int32_t* ess_t = nullptr, uint32_t rec_idx = 0, bool allow_grp = true) {
 #ifdef CSSM_OFF_STAMPS
@@ -499,69 +382,62 @@ static int launch_resample(cssm_pf* pf, const StepRec* d_rec, double* ll_t = nul
   if (pf->resampler == CSSM_RESAMPLE_MULTINOMIAL && !pf->cum) {
     if (hipMalloc(&pf->cum, pf->stride * 8) != hipSuccess) return fail(CSSM_ENOMEM, "hipMalloc cumulative weights");
   }
-  const bool optimistic = pf->last_optimistic;
-  const int tgrid = (int)pf->nunits;
-  const int split = optimistic ? (int)pf->split : 1;
-  // the sums as a pass of their own on a cloud of many units (systematic resampling, one GPU): k_tile_sums adds the units' sums to their
-  // groups' too, and k_offspring_self<..., 0, GRP> finds its prefix through those instead of every block reading every unit sum (at
-  // 4096 units: 64 KiB per block, 100 us per launch at N = 2^24 against 67)
-  int lean_layout = 0;
-  if (!optimistic && allow_grp && !pf->sharded && pf->opt_grp && pf->resampler == CSSM_RESAMPLE_SYSTEMATIC && pf->first == 0 && pf->n == pf->n_global &&
-      pf->nunits >= pf->grp_min_units && pf->nunits <= (uint32_t)(CSSM_GRP_MAX * 64) && (uint64_t)pf->sup * CSSM_TILE <= CSSM_GRP_MAX_UNIT)
-    lean_layout = pf->nunits > (uint32_t)(CSSM_GRP_SMALL * CSSM_GRP_UNITS) ? 2 : 1;
-  if (!optimistic) {
+  static const bool no_offw = getenv("CSSM_NO_OFFW") != nullptr;   // (A/B: the wave-range propagate in front of k_offspring_self)
+  const CssmResamplePlan plan = cssm_plan_resample(*pf, *pf, allow_grp, no_offw);
+  if (plan.tile_sums) {
     prof_begin(pf, CSSM_K_TILE_SUMS);
-    hipLaunchKernelGGL(k_tile_sums, dim3(tgrid), dim3(CSSM_BLOCK), 0, pf->stream, pf->logw, pf->n, pf->sc, pf->tileS, pf->tileS2, pf->ntiles,
+    hipLaunchKernelGGL(k_tile_sums, dim3(pf->nunits), dim3(CSSM_BLOCK), 0, pf->stream, pf->logw, pf->n, pf->sc, pf->tileS, pf->tileS2, pf->ntiles,
                        pf->sup, pf->nunits, 0, pf->wparity, (const double*)nullptr, pf->d_logtab, d_rec, 0u, (const unsigned long long*)nullptr, 0,
-                       lean_layout ? (0x100 | (pf->wparity << 9) | ((lean_layout == 2 ? 1 : 0) << 11)) : 0);
+                       plan.tile_sums_flags);
     prof_end(pf);
   }
-  const int s2_par = optimistic ? pf->s2_par : -1;
   prof_begin(pf, CSSM_K_OFFSPRING);   // unit prefix, ll (ess), end slots and their expansion to ancestors in one kernel (one block per unit + the publisher)
-#define OFF_ARGS pf->logw, pf->n, pf->sc, (const cssm_u128*)pf->tileS, (const cssm_u128*)pf->tileS2, d_rec, pf->anc, pf->ntiles, pf->sup, pf->nunits, \
-                 pf->wparity, ll_t, ess_t, rec_idx, pf->opt_exact, split, pf->seed, pf->cum, pf->s2buf, pf->s2_stride, s2_par, pf->gen
-  const int ogrid = tgrid + 1;   // one block per unit + the publisher
-#define OFF_WAVE_ARGS pf->logw, pf->n, pf->sc, (const cssm_u128*)pf->tileS, (const cssm_u128*)pf->tileW, d_rec, pf->anc, pf->sup, pf->nunits, pf->wparity, \
-                      ll_t, ess_t, rec_idx, pf->opt_exact, pf->s2buf, pf->s2_stride, s2_par, pf->gen
-  static const bool no_offw = getenv("CSSM_NO_OFFW") != nullptr;   // (A/B: the wave-range propagate in front of k_offspring_self)
-#define OFF_GO(RS) do { if (optimistic && pf->last_grp && pf->last_ws && !no_offw && RS == CSSM_RESAMPLE_SYSTEMATIC) { \
-                          if (pf->grp_layout == 2) hipLaunchKernelGGL((k_offspring_wave<2>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_WAVE_ARGS); \
-                          else hipLaunchKernelGGL((k_offspring_wave<1>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_WAVE_ARGS); \
-                        } else if (optimistic && pf->last_grp && pf->grp_layout == 2 && RS == CSSM_RESAMPLE_SYSTEMATIC) \
-                          hipLaunchKernelGGL((k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 2, 2>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_ARGS); \
-                        else if (optimistic && pf->last_grp && RS == CSSM_RESAMPLE_SYSTEMATIC) \
-                          hipLaunchKernelGGL((k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 2, 1>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_ARGS); \
-                        else if (optimistic) hipLaunchKernelGGL((k_offspring_self<RS, 2>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_ARGS); \
-                        else if (lean_layout == 2 && RS == CSSM_RESAMPLE_SYSTEMATIC) \
-                          hipLaunchKernelGGL((k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 0, 2>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_ARGS); \
-                        else if (lean_layout == 1 && RS == CSSM_RESAMPLE_SYSTEMATIC) \
-                          hipLaunchKernelGGL((k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 0, 1>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_ARGS); \
-                        else hipLaunchKernelGGL((k_offspring_self<RS, 0>), dim3(ogrid), dim3(CSSM_BLOCK), 0, pf->stream, OFF_ARGS); } while (0)
-  if (pf->resampler == CSSM_RESAMPLE_STRATIFIED) OFF_GO(CSSM_RESAMPLE_STRATIFIED);
-  else if (pf->resampler == CSSM_RESAMPLE_MULTINOMIAL) OFF_GO(CSSM_RESAMPLE_MULTINOMIAL);
-  else OFF_GO(CSSM_RESAMPLE_SYSTEMATIC);
-#undef OFF_GO
-#undef OFF_ARGS
-#undef OFF_WAVE_ARGS
+  const dim3 ogrid(pf->nunits + 1), oblock(CSSM_BLOCK);   // one block per unit + the publisher
+  auto self = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, ogrid, oblock, 0, pf->stream, pf->logw, pf->n, pf->sc, (const cssm_u128*)pf->tileS, (const cssm_u128*)pf->tileS2, d_rec, pf->anc,
+                       pf->ntiles, pf->sup, pf->nunits, pf->wparity, ll_t, ess_t, rec_idx, pf->opt_exact, plan.split, pf->seed, pf->cum, pf->s2buf, pf->s2_stride,
+                       plan.s2_par, pf->gen);
+  };
+  auto wave = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, ogrid, oblock, 0, pf->stream, pf->logw, pf->n, pf->sc, (const cssm_u128*)pf->tileS, (const cssm_u128*)pf->tileW, d_rec, pf->anc,
+                       pf->sup, pf->nunits, pf->wparity, ll_t, ess_t, rec_idx, pf->opt_exact, pf->s2buf, pf->s2_stride, plan.s2_par, pf->gen);
+  };
+  switch (plan.kernel) {
+    case CSSM_OFF_WAVE_1: wave(k_offspring_wave<1>); break;
+    case CSSM_OFF_WAVE_2: wave(k_offspring_wave<2>); break;
+    case CSSM_OFF_SELF_SYS_FUSED_GRP1: self(k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 2, 1>); break;
+    case CSSM_OFF_SELF_SYS_FUSED_GRP2: self(k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 2, 2>); break;
+    case CSSM_OFF_SELF_SYS_FUSED: self(k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 2>); break;
+    case CSSM_OFF_SELF_STRAT_FUSED: self(k_offspring_self<CSSM_RESAMPLE_STRATIFIED, 2>); break;
+    case CSSM_OFF_SELF_MULTI_FUSED: self(k_offspring_self<CSSM_RESAMPLE_MULTINOMIAL, 2>); break;
+    case CSSM_OFF_SELF_SYS_GRP1: self(k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 0, 1>); break;
+    case CSSM_OFF_SELF_SYS_GRP2: self(k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 0, 2>); break;
+    case CSSM_OFF_SELF_SYS: self(k_offspring_self<CSSM_RESAMPLE_SYSTEMATIC, 0>); break;
+    case CSSM_OFF_SELF_STRAT: self(k_offspring_self<CSSM_RESAMPLE_STRATIFIED, 0>); break;
+    case CSSM_OFF_SELF_MULTI: self(k_offspring_self<CSSM_RESAMPLE_MULTINOMIAL, 0>); break;
+  }
   if (pf->resampler == CSSM_RESAMPLE_MULTINOMIAL)
     hipLaunchKernelGGL(k_multinomial, dim3(grid_for(pf->n, 256, kGridCap)), dim3(256), 0, pf->stream, pf->cum, pf->n, pf->seed,
                        pf->h_step_for_resample, pf->anc);
   prof_end(pf);
-  pf->wparity = (pf->wparity + 1) % CSSM_MAXSETS;
   HIP_TRY(hipGetLastError());
-  pf->anc_valid = true;
-  pf->wmode = optimistic;
-  pf->have_level = true;        // (the publisher of this launch leaves the next observation's predicted level: LGCP)
-  if (optimistic) pf->s2_par ^= 1;
+  cssm_note_resampled(pf, pf->last_optimistic);
   return CSSM_OK;
 }
+
+// One observation, enqueued: its propagate, then its resampling -- or, unweighted, the record of its unchanged ll and ess where the
+// caller keeps them per record (ll_t).  Every single-handle driver enqueues its observations through this.
+// anc_out: where the resampling writes its ancestors, in place of the array the propagate read the previous ones from (the history
+// of cssm_pf_interpolate and cssm_pf_smooth); it is the handle's ancestor array from then on.
 static int launch_step(cssm_pf* pf, const StepRec* d_rec, int weighted, uint32_t step_index, double* ll_t = nullptr, int32_t* ess_t = nullptr,
-                       uint32_t rec_idx = 0, double* pick_out = nullptr, uint32_t pick_slot = 0) {
+                       uint32_t rec_idx = 0, double* pick_out = nullptr, uint32_t pick_slot = 0, uint32_t* anc_out = nullptr) {
   pf->h_step_for_resample = step_index;
   int rc = cssm_launch_propagate(pf, d_rec, pick_out, pick_slot);
   if (rc) return rc;
-  if (weighted) rc = launch_resample(pf, d_rec, ll_t, ess_t, rec_idx);
-  else if (ll_t) hipLaunchKernelGGL(k_record, dim3(1), dim3(1), 0, pf->stream, pf->sc, ll_t, ess_t, rec_idx);
+  if (weighted) {
+    if (anc_out) pf->anc = anc_out;
+    rc = launch_resample(pf, d_rec, ll_t, ess_t, rec_idx);
+  } else if (ll_t) hipLaunchKernelGGL(k_record, dim3(1), dim3(1), 0, pf->stream, pf->sc, ll_t, ess_t, rec_idx);
   return rc;
 }
 
@@ -571,6 +447,13 @@ int cssm_check_device_err(cssm_pf* pf, const Scalars& h) {
   if (h.err & 16u) return fail(CSSM_ESHARD, "peer-written exchange: a rank's segment did not arrive within the wait bound");
   (void)pf;
   return CSSM_OK;
+}
+// ... of a single-GPU handle: bit 2 (a whole series to be run again with the sums in their own pass) is a shard's and the stateless
+// resampler's -- k_offspring_self and k_offspring_wave hold the series at the observation instead (bit 6), which the drivers resolve
+static int single_handle_err(cssm_pf* pf, const Scalars& h) {
+  const int rc = cssm_check_device_err(pf, h);
+  if (rc == CSSM_OK && (h.err & 4u)) return fail(CSSM_ESTATE, "the device asks for the whole series again (err bit 2), which no kernel of a single-GPU handle does");
+  return rc;
 }
 // The end of a call: k_finish forms an ESS that is still pending, and writes the scalars the host reads (and, with T > 0, the
 // call's ll_t / ess_t) into host-mapped memory; the host synchronises the stream -- no device-to-host copy.  *pf->h_sc is valid
@@ -609,6 +492,18 @@ static int read_scalars(cssm_pf* pf, uint32_t T = 0, bool want_ll_t = false, boo
 // Host-side state of a single-GPU handle right before a propagate: what redoing that observation starts from.
 struct PreState { int cur; const double* src; size_t src_stride; bool anc_valid; int wparity; };
 static inline PreState pre_state(const cssm_pf* pf) { return {pf->cur, pf->src, pf->src_stride, pf->anc_valid, pf->wparity}; }
+// ... right before the propagate of record sf of a call whose record 0 started from `start`: every propagate flips cur, every weighted
+// observation advances the max-slot set; the ancestors are those of the observation before it, if that one resampled
+static PreState pre_state_of_record(const cssm_pf* pf, const PreState& start, size_t sf) {
+  PreState q;
+  q.cur = (int)(((size_t)start.cur + sf) & 1);
+  q.src = pf->state[q.cur]; q.src_stride = pf->stride;
+  q.anc_valid = sf == 0 ? start.anc_valid : (pf->h_recs[sf - 1].has_obs != 0);
+  int wp = start.wparity;
+  for (size_t r = 0; r < sf; ++r) wp = (wp + (pf->h_recs[r].has_obs ? 1 : 0)) % CSSM_MAXSETS;
+  q.wparity = wp;
+  return q;
+}
 // An observation whose reference level the max ruled out (err bit 6: k_offspring put the series on hold AT it; its propagate
 // is done, the cloud it read and the previous ancestors are untouched) is done AGAIN: the same propagate with log-weights
 // stored (the weights relative to the level it first assumed are useless), sums relative to the max (k_tile_sums), resampling.
@@ -619,6 +514,17 @@ static int redo_observation(cssm_pf* pf, const PreState& q, const StepRec* d_rec
   pf->safe_sums = false;
   if (rc) return rc;
   return launch_resample(pf, d_rec, ll_t, ess_t, rec_idx, /*allow_grp=*/false);
+}
+// whether the scalars a call read back (read_scalars) report a series on hold that the host resolves (NaN / unusable weights: reported as they are)
+static inline bool on_hold(const Scalars& h) { return (h.err & 64u) && !(h.err & 3u); }
+// The hold is lifted on the device and the observation it was put on -- observation `step_index` of the filter, whose propagate started
+// from `before` -- is redone.  What the kernels behind it skipped is the caller's to enqueue again.
+static int resolve_hold(cssm_pf* pf, const PreState& before, const StepRec* d_rec, uint32_t step_index, double* ll_t, int32_t* ess_t, uint32_t rec_idx) {
+  const uint32_t cleared = pf->h_sc->err & ~64u, none = 0xffffffffu;   // (pageable sources: staged before the calls return)
+  HIP_TRY(hipMemcpyAsync(&pf->sc->err, &cleared, sizeof(uint32_t), hipMemcpyHostToDevice, pf->stream));
+  HIP_TRY(hipMemcpyAsync(&pf->sc->fail_step, &none, sizeof(uint32_t), hipMemcpyHostToDevice, pf->stream));
+  pf->h_step_for_resample = step_index;
+  return redo_observation(pf, before, d_rec, ll_t, ess_t, rec_idx);
 }
 
 // ------------------------------------------------------------------------------------ streaming API
@@ -649,6 +555,30 @@ int cssm_ensure_recs(cssm_pf* pf, size_t T) {
     HIP_TRY(hipHostGetDevicePointer((void**)&pf->hd_ess_t, pf->h_ess_t, 0));
     pf->recs_cap = T;
   }
+  return CSSM_OK;
+}
+
+// data.minBy(_.t).t (model/ParticleFilter.scala:138): the time of a series' initial cloud
+double cssm_series_t0(const double* t, size_t T) {
+  double t0 = t[0];
+  for (size_t s = 1; s < T; ++s) if (t[s] < t0) t0 = t[s];
+  return t0;
+}
+// Records [first, first + count) of a call's series into the handle's host buffer: record s is observation base + s of the filter;
+// t_prev is the time before record 0 (the initial cloud's, or the handle's clock where the call continues a filter)
+void cssm_build_recs(cssm_pf* pf, double t_prev, const double* t, const double* y, const uint8_t* has, size_t first, size_t count, uint32_t base) {
+  double tp = first ? t[first - 1] : t_prev;
+  for (size_t s = first; s < first + count; ++s) { cssm_build_rec(pf, tp, t[s], y[s], has ? has[s] : 1, base + (uint32_t)s, &pf->h_recs[s]); tp = t[s]; }
+}
+// the buffer of a sampled path over T observations (T + 1 states)
+int cssm_ensure_path(cssm_pf* pf, size_t T) {
+  const size_t need = (T + 1) * (size_t)pf->d;
+  if (pf->path_cap >= need) return CSSM_OK;
+  HIP_TRY(hipStreamSynchronize(pf->stream));
+  if (pf->d_path) (void)hipFree(pf->d_path);
+  pf->d_path = nullptr; pf->path_cap = 0;
+  HIP_TRY(hipMalloc(&pf->d_path, need * 8));
+  pf->path_cap = need;
   return CSSM_OK;
 }
 
@@ -697,11 +627,8 @@ static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_
   Scalars& h = *pf->h_sc;
   rc = read_scalars(pf, 0, false, false, /*poll=*/!rows);   // (the completion word, not the stream: 40.4 -> 38.0 us per streaming step at N = 2^20)
   if (rc) return rc;
-  if ((h.err & 64u) && !(h.err & 3u)) {   // the max ruled the reference level out: this observation again, relative to the max
-    const uint32_t cleared = h.err & ~64u, none = 0xffffffffu;
-    HIP_TRY(hipMemcpyAsync(&pf->sc->err, &cleared, sizeof(uint32_t), hipMemcpyHostToDevice, pf->stream));
-    HIP_TRY(hipMemcpyAsync(&pf->sc->fail_step, &none, sizeof(uint32_t), hipMemcpyHostToDevice, pf->stream));
-    rc = redo_observation(pf, before, pf->d_recs, nullptr, nullptr, 0);
+  if (on_hold(h)) {   // the max ruled the reference level out: this observation again, relative to the max
+    rc = resolve_hold(pf, before, pf->d_recs, pf->step, nullptr, nullptr, 0);
     if (rc) return rc;
     if (rows) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
     rc = read_scalars(pf);
@@ -710,7 +637,7 @@ static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_
   pf->t = t; pf->step++;
   if (ll_out) *ll_out = h.ll;
   if (ess_out) *ess_out = h.ess;
-  return cssm_check_device_err(pf, h);
+  return single_handle_err(pf, h);
 }
 extern "C" int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out) {
   return step_impl(pf, t, obs, has_obs, ll_out, ess_out, false);
@@ -777,30 +704,11 @@ extern "C" int cssm_pf_adopt(cssm_pf* pf, const double* state_dN, double ll, int
 }
 // ------------------------------------------------------------------------------------ batch API
 
-static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
-                           double* ll_t, int32_t* ess_t, double* path, bool* retry, bool cont = false, bool rows = false);
-
-// The series is enqueued without a host round trip per step, with the sums formed inside k_propagate relative to
-// each observation's reference level.  If the max of some step rules its level out (err bit 2; an outlying
-// observation), the series is run again with the sums in their own pass: every step then applies the same rule
-// (cssm_ref_choose), so both runs define the same result and only the second one can compute it.
-static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
-                      double* ll_t, int32_t* ess_t, double* path, bool rows = false) {
-  bool retry = false;
-  int rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, path, &retry, false, rows);
-  if (rc == CSSM_OK && retry) {
-    pf->safe_sums = true;
-    rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, path, &retry, false, rows);   // (rows: every one is enqueued, and written, again)
-    pf->safe_sums = false;
-  }
-  return rc;
-}
-
 // cont: the observations CONTINUE the filter from its current state (cssm_pf_ll_filter_more): no initial cloud is drawn, the
 // first time increment is taken from the handle's clock, observation s of this call is observation pf->step + s of the filter.
-static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
-                           double* ll_t, int32_t* ess_t, double* path, bool* retry, bool cont, bool rows) {
-  *retry = false;
+// rows: a row of filtered intervals behind the initial cloud (not cont) and behind every record (cssm_intervals.hip).
+static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
+                      double* ll_t, int32_t* ess_t, double* path, bool cont = false, bool rows = false) {
   if (!pf || !t || !y) return fail(CSSM_EINVAL_ARG, "null argument");
   if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data (the reference's minBy throws on an empty Vector)");
   // CSSM_CALL_TIMING=1: host-side phases of the call on stderr (tools/archive/leg_overhead.py)
@@ -813,22 +721,21 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
   int rc = cssm_ensure_recs(pf, T);
   if (rc) return rc;
   if (cont && (!pf->initialised || path)) return fail(CSSM_ESTATE, "continuing a filter needs an initialised handle (and records no path)");
-  double t0 = t[0];
-  for (size_t s = 1; s < T; ++s) if (t[s] < t0) t0 = t[s];     // data.minBy(_.t).t, model/ParticleFilter.scala:138
+  const double t0 = cssm_series_t0(t, T);
   const uint32_t base = cont ? pf->step : 0u;                  // index of this call's first observation in the filter's series
-  double tp = cont ? pf->t : t0;
+  const double t_prev = cont ? pf->t : t0;
   // The first observation's record goes ahead of the others (a continued call of a model without per-observation tables): the queue
   // has its first kernels while the host is still building records 1 .. T-1 (4 us for 20 of them, on the critical path otherwise).
   const bool head_first = cont && T > 1 && pf->obs_kind != CSSM_OBS_LGCP;
   size_t built = 0;
   if (head_first) {
-    cssm_build_rec(pf, tp, t[0], y[0], has ? has[0] : 1, base, &pf->h_recs[0]); tp = t[0]; built = 1;
+    cssm_build_recs(pf, t_prev, t, y, has, 0, 1, base); built = 1;
     rc = cssm_upload_recs(pf, 0, 1, cont);
     if (rc) return rc;
   }
   bool rest_pending = head_first;
   auto build_rest = [&]() -> int {      // records built .. T-1: built and sent (head_first: behind the first observation's launches)
-    for (size_t s = built; s < T; ++s) { cssm_build_rec(pf, tp, t[s], y[s], has ? has[s] : 1, base + (uint32_t)s, &pf->h_recs[s]); tp = t[s]; }
+    cssm_build_recs(pf, t_prev, t, y, has, built, T - built, base);
     int r = cssm_build_fsub(pf, 0, T, true);
     if (r) return r;
     ph_rec = since(tp0);
@@ -844,19 +751,13 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
     if (rows) { rc = cssm_iv_row(pf, 0); if (rc) return rc; }   // (cssm_pf_filter_intervals: row 0 = the initial cloud)
   }
   const size_t row0 = cont ? 0 : 1;   // (rows) the row behind record s is row0 + s
-  // host-side state at the first observation of this call (launch_init: cur = 0, wparity = 0)
-  const int cur0 = pf->cur, wpar0 = pf->wparity;
-  const bool anc_valid0 = pf->anc_valid;
+  const PreState start = pre_state(pf);   // host-side state at the first observation of this call (launch_init: cur = 0, wparity = 0)
   const int32_t ess0 = pf->ess_host;      // what an unweighted first observation reports (ll and ess unchanged, :121)
   pf->gen++;
   const int d = pf->d;
   if (path) {
-    if (pf->path_cap < (T + 1) * (size_t)d) {
-      if (pf->d_path) (void)hipFree(pf->d_path);
-      pf->d_path = nullptr;
-      HIP_TRY(hipMalloc(&pf->d_path, (T + 1) * (size_t)d * 8));
-      pf->path_cap = (T + 1) * (size_t)d;
-    }
+    rc = cssm_ensure_path(pf, T);
+    if (rc) return rc;
     const int32_t pr = (int32_t)cssm_philox_draw(pf->seed, 0, 0, CSSM_STREAM_PICK, 0).v[0];
     const uint32_t pa = pr < 0 ? (uint32_t)0 - (uint32_t)pr : (uint32_t)pr;
     hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, pf->stream, pf->src, pf->src_stride, (const uint32_t*)nullptr,
@@ -875,21 +776,16 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
   // propagate again, storing log-weights; sums relative to the max: k_tile_sums + k_offspring) and enqueues the rest again.
   size_t s_from = 0;
   for (;;) {
-    const bool may_hold = may_use_sums_kernel(pf);
+    const bool may_hold = cssm_may_use_sums_kernel(*pf);
     for (size_t s = s_from; s < T; ++s) {
       const int weighted = pf->h_recs[s].has_obs;
       double* pick_out = (folded && s >= 1) ? pf->d_path + s * (size_t)d : nullptr;
       const uint32_t pick_slot = s >= 1 ? pf->h_recs[s - 1].pick : 0u;
-      pf->h_step_for_resample = base + (uint32_t)s;
-      rc = cssm_launch_propagate(pf, pf->d_recs + s, pick_out, pick_slot);
-      if (!rc) {
-        if (weighted) rc = launch_resample(pf, pf->d_recs + s, pf->d_ll_t, pf->d_ess_t, (uint32_t)s);
-        else hipLaunchKernelGGL(k_record, dim3(1), dim3(1), 0, pf->stream, pf->sc, pf->d_ll_t, pf->d_ess_t, (uint32_t)s);
-      }
+      rc = launch_step(pf, pf->d_recs + s, weighted, base + (uint32_t)s, pf->d_ll_t, pf->d_ess_t, (uint32_t)s, pick_out, pick_slot);
       if (rc) return rc;
       if (rest_pending) { rc = build_rest(); if (rc) return rc; }
       if (rows) { rc = cssm_iv_row(pf, row0 + s); if (rc) return rc; }   // (a series on hold: these launches return at once like the filter's)
-      folded = path && s + 1 < T && uses_sums_kernel(pf);   // (the last entry has no following propagate)
+      folded = path && s + 1 < T && cssm_uses_sums_kernel(*pf, *pf);   // (the last entry has no following propagate)
       if (path && !folded)
         hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, pf->stream, pf->src, pf->src_stride,
                            (const uint32_t*)(pf->anc_valid ? pf->anc : nullptr), (uint64_t)pf->h_recs[s].pick, d,
@@ -904,26 +800,13 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
     rc = read_scalars(pf, (uint32_t)T, ll_t != nullptr, ess_t != nullptr, /*poll=*/path == nullptr && !rows);   // (k_finish: a pending ESS formed, results into host-mapped memory)
     if (rc) return rc;
     const Scalars& hh = *pf->h_sc;
-    if (!may_hold || !(hh.err & 64u) || (hh.err & 3u)) break;   // (NaN / unusable weights: reported below)
+    if (!may_hold || !on_hold(hh)) break;                       // (NaN / unusable weights: reported below)
     const size_t sf = (size_t)hh.fail_step - base;              // (the record's index in this call)
     if (hh.fail_step < base || sf >= T) return fail(CSSM_ESTATE, "held series reports observation %u; this call holds %u .. %zu", hh.fail_step, base, base + T - 1);
-    const uint32_t cleared = hh.err & ~64u, none = 0xffffffffu;
-    HIP_TRY(hipMemcpyAsync(&pf->sc->err, &cleared, sizeof(uint32_t), hipMemcpyHostToDevice, pf->stream));
-    HIP_TRY(hipMemcpyAsync(&pf->sc->fail_step, &none, sizeof(uint32_t), hipMemcpyHostToDevice, pf->stream));
-    // host-side state right BEFORE the propagate of observation sf (every propagate flips cur, every weighted observation
-    // advances the max-slot set; the ancestors are those of the observation before it, if that one resampled)
-    PreState before;
-    before.cur = (int)(((size_t)cur0 + sf) & 1);
-    before.src = pf->state[before.cur]; before.src_stride = pf->stride;
-    before.anc_valid = sf == 0 ? anc_valid0 : (pf->h_recs[sf - 1].has_obs != 0);
-    int wp = wpar0;
-    for (size_t q = 0; q < sf; ++q) wp = (wp + (pf->h_recs[q].has_obs ? 1 : 0)) % CSSM_MAXSETS;
-    before.wparity = wp;
-    pf->h_step_for_resample = base + (uint32_t)sf;
-    rc = redo_observation(pf, before, pf->d_recs + sf, pf->d_ll_t, pf->d_ess_t, (uint32_t)sf);
+    rc = resolve_hold(pf, pre_state_of_record(pf, start, sf), pf->d_recs + sf, base + (uint32_t)sf, pf->d_ll_t, pf->d_ess_t, (uint32_t)sf);
     if (rc) return rc;
     if (rows) { rc = cssm_iv_row(pf, row0 + sf); if (rc) return rc; }   // (the held record's row is formed behind its redo)
-    folded = path && sf + 1 < T && uses_sums_kernel(pf);
+    folded = path && sf + 1 < T && cssm_uses_sums_kernel(*pf, *pf);
     if (path && !folded)
       hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, pf->stream, pf->src, pf->src_stride, (const uint32_t*)pf->anc,
                          (uint64_t)pf->h_recs[sf].pick, d, pf->d_path + (sf + 1) * (size_t)d);
@@ -944,9 +827,8 @@ static int run_filter_once(cssm_pf* pf, const double* t, const double* y, const 
   if (timing) fprintf(stderr, "cssm call T=%zu: records built %.1f us, upload enqueued %.1f, %zu steps enqueued %.1f, results back %.1f (device loop %.1f us)\n",
                       T, ph_rec, ph_up, T, ph_enq, since(tp0), pf->last_ms * 1e3);
   pf->t = t[T - 1]; pf->step = base + (uint32_t)T;
-  if ((h.err & 4u) && !(h.err & 1u) && !pf->safe_sums) { *retry = true; return CSSM_OK; }
   if (ll_out) *ll_out = h.ll;
-  return cssm_check_device_err(pf, h);
+  return single_handle_err(pf, h);
 }
 
 extern "C" int cssm_pf_ll_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T,
@@ -956,18 +838,11 @@ extern "C" int cssm_pf_ll_filter(cssm_pf* pf, const double* t, const double* y, 
 
 extern "C" int cssm_pf_ll_filter_more(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T,
                                       double* ll_out, double* ll_t, int32_t* ess_t) {
-  bool retry = false;
-  int rc = run_filter_once(pf, t, y, has_obs, T, ll_out, ll_t, ess_t, nullptr, &retry, /*cont=*/true);
-  if (rc == CSSM_OK && retry) return fail(CSSM_ESTATE, "a continued series cannot be repeated from its start");   // (not reached: batch series are held in place)
-  return rc;
+  return run_filter(pf, t, y, has_obs, T, ll_out, ll_t, ess_t, nullptr, /*cont=*/true);
 }
 
 int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont) {
-  if (!cont) return run_filter(pf, t, y, has, T, ll_out, ll_t, ess_t, nullptr, true);
-  bool retry = false;
-  int rc = run_filter_once(pf, t, y, has, T, ll_out, ll_t, ess_t, nullptr, &retry, /*cont=*/true, /*rows=*/true);
-  if (rc == CSSM_OK && retry) return fail(CSSM_ESTATE, "a continued series cannot be repeated from its start");   // (not reached: batch series are held in place)
-  return rc;
+  return run_filter(pf, t, y, has, T, ll_out, ll_t, ess_t, nullptr, cont, /*rows=*/true);
 }
 
 extern "C" int cssm_pf_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T,
@@ -1120,7 +995,7 @@ extern "C" int cssm_pf_set_option(cssm_pf* pf, int option, int value) {
   if (option == CSSM_OPT_WHOLE_TILES) {   // launch geometry only: the arrays hold up to four sub-units per unit either way
     if (pf->sharded) return fail(CSSM_ESTATE, "sharded handles always run whole tiles");
     pf->opt_whole = value < 0 ? 0 : (value > 3 ? 3 : value);
-    pf->split = value ? 1u : auto_split(pf);
+    pf->split = value ? 1u : cssm_plan_split(*pf, *pf, 0);   // (a single-GPU handle: no shard's split)
     return CSSM_OK;
   }
   if (option == CSSM_OPT_RESAMPLER) {
@@ -1325,38 +1200,34 @@ static int interp_forward(cssm_pf* pf, const double* t, const double* y, const u
     (void)hipFree(hx); if (hanc) (void)hipFree(hanc);
     return fail(CSSM_ENOMEM, "ancestor history does not fit");
   }
-  double t0 = t[0];
-  for (size_t s = 1; s < T; ++s) if (t[s] < t0) t0 = t[s];
-  double tp = t0;
-  for (size_t s = 0; s < T; ++s) { cssm_build_rec(pf, tp, t[s], y[s], has ? has[s] : 1, (uint32_t)s, &pf->h_recs[s]); tp = t[s]; }
+  const double t0 = cssm_series_t0(t, T);
+  cssm_build_recs(pf, t0, t, y, has, 0, T, 0u);
   rc = cssm_build_fsub(pf, 0, T, true);
   if (rc) { (void)hipFree(hx); (void)hipFree(hanc); if (bidx) (void)hipFree(bidx); return rc; }
   hist.hx = hx; hist.hanc = hanc; hist.bidx = bidx; hist.t0 = t0;
   rc = cssm_upload_recs(pf, 0, T, false);
   Scalars h;
-  for (int attempt = 0; attempt < 2 && !rc; ++attempt) {   // second attempt: see run_filter
+  // The one whole-series rerun left in the library: the history has no per-observation redo, so a series that some observation put on
+  // hold (err bit 6: its level was ruled out) runs a second time from its initial cloud with the sums in their own pass, where every
+  // observation applies the same rule (cssm_ref_choose) -- both attempts define the same result and only the second can compute it.
+  for (int attempt = 0; attempt < 2 && !rc; ++attempt) {
     pf->safe_sums = (attempt == 1);
     pf->state[0] = hx;                                   // X1_0 = the initial cloud
     rc = cssm_launch_init(pf, t0);
     for (size_t s = 0; s < T && !rc; ++s) {
-      // step s+1 reads X1_s through anc_s (launch_propagate uses pf->anc / pf->anc_valid) and writes X1_{s+1}
+      // step s+1 reads X1_s through anc_s (launch_propagate uses pf->anc / pf->anc_valid) and writes X1_{s+1} and, weighted, anc_{s+1}
       pf->state[pf->cur ^ 1] = hx + (s + 1) * slab;
       pf->anc = hanc + s * pf->stride;
       const int w = pf->h_recs[s].has_obs;
-      pf->h_step_for_resample = (uint32_t)s;
-      rc = cssm_launch_propagate(pf, pf->d_recs + s);
-      if (!rc && w) {
-        pf->anc = hanc + (s + 1) * pf->stride;
-        rc = launch_resample(pf, pf->d_recs + s);
-        weighted[s + 1] = 1;
-      }
+      rc = launch_step(pf, pf->d_recs + s, w, (uint32_t)s, nullptr, nullptr, 0, nullptr, 0, hanc + (s + 1) * pf->stride);
+      if (!rc && w) weighted[s + 1] = 1;
     }
     if (!rc && hipMemcpyAsync(CSSM_SC_TAIL_ARGS(&h, pf->sc), hipMemcpyDeviceToHost, pf->stream) != hipSuccess) rc = fail(CSSM_EHIP, "scalars");
     if (!rc && hipStreamSynchronize(pf->stream) != hipSuccess) rc = fail(CSSM_EHIP, "forward pass");
-    if (rc || !(h.err & 64u) || (h.err & 3u)) break;   // (bit 6: some observation's level was ruled out -- again, sums in their own pass)
+    if (rc || !on_hold(h)) break;
   }
   pf->safe_sums = false;
-  if (!rc) rc = cssm_check_device_err(pf, h);
+  if (!rc) rc = single_handle_err(pf, h);
   if (!rc && ll_out) *ll_out = h.ll;
   return rc;
 }
@@ -1479,8 +1350,7 @@ extern "C" int cssm_pf_smooth(cssm_pf* pf, const double* t, const double* y, con
   for (hipEvent_t& e : ev) HIP_TRY(tmp.event(e));
   std::vector<double> hfco((T + 1) * (size_t)d), hout((T + 1) * (size_t)rows * 3);
   {
-    double t0 = t[0];
-    for (size_t s = 1; s < T; ++s) if (t[s] < t0) t0 = t[s];
+    const double t0 = cssm_series_t0(t, T);
     for (size_t q = 0; q <= T; ++q) {                    // F(time of output row q), as cssm_pf_interpolate's summaries build it
       const double time = q ? t[q - 1] : t0;
       StepRec rec;

@@ -321,10 +321,8 @@ extern "C" int cssm_pf_shard_begin(cssm_pf* pf, const double* t, const double* y
   if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data");
   rc = cssm_ensure_recs(pf, T);
   if (rc) return rc;
-  double t0 = t[0];
-  for (size_t s = 1; s < T; ++s) if (t[s] < t0) t0 = t[s];
-  double tp = t0;
-  for (size_t s = 0; s < T; ++s) { cssm_build_rec(pf, tp, t[s], y[s], has_obs ? has_obs[s] : 1, (uint32_t)s, &pf->h_recs[s]); tp = t[s]; }
+  const double t0 = cssm_series_t0(t, T);
+  cssm_build_recs(pf, t0, t, y, has_obs, 0, T, 0u);
   rc = cssm_build_fsub(pf, 0, T, true);
   if (rc) return rc;
   rc = cssm_upload_recs(pf, 0, T, false);   // (a new cloud: no observation precedes the first record)
@@ -357,8 +355,7 @@ extern "C" int cssm_pf_shard_continue(cssm_pf* pf, const double* t, const double
   if (rc) return rc;
   rc = cssm_ensure_recs(pf, T);
   if (rc) return rc;
-  double tp = pf->t;
-  for (size_t s = 0; s < T; ++s) { cssm_build_rec(pf, tp, t[s], y[s], has_obs ? has_obs[s] : 1, pf->step + (uint32_t)s, &pf->h_recs[s]); tp = t[s]; }
+  cssm_build_recs(pf, pf->t, t, y, has_obs, 0, T, pf->step);
   rc = cssm_build_fsub(pf, 0, T, true);
   if (rc) return rc;
   rc = cssm_upload_recs(pf, 0, T, true);

@@ -606,6 +606,29 @@ def test_outlying_observation_batch_rerun_matches_oracle(name, where, fused):
     g.close()
 
 
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("n", [1000, 5000])
+def test_outlying_observations_inside_a_continued_call(n, fused):
+    """A held observation inside a CONTINUED call (run on records 0..3, run_more on 4..9): outliers at the continued call's first record
+    and at its last; record 5 carries no datum, so the max-slot set and the validity of the ancestors at a held record are not functions
+    of its index.  The state each redo starts from is derived from the call's starting state: against the oracle's filter of the whole
+    series, bit for bit."""
+    model = cases.c2_model()
+    t, y, has = _outlier_series(10, (4, 9))
+    has = has.copy(); has[5] = 0
+    g = NativePf(model, n, cases.SEED)
+    g.set_option(3, fused)
+    _, ll_a, ess_a, _ = g.run(t[:4], y[:4], has[:4])
+    gl, ll_b, ess_b = g.run_more(t[4:], y[4:], has[4:])
+    o = oracle.OraclePf(model.descriptor(), n, cases.SEED)
+    ol, oll, oess, _ = o.filter(t, y, has)
+    assert gl == ol
+    np.testing.assert_array_equal(np.concatenate([ll_a, ll_b]), oll)
+    np.testing.assert_array_equal(np.concatenate([ess_a, ess_b]), oess)
+    np.testing.assert_array_equal(g.particles(), o.particles())
+    g.close()
+
+
 def test_outlying_gaussian_observation_and_pmmh_path():
     model = cases.linear_model()
     n = 4096
