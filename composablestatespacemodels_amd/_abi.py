@@ -123,6 +123,13 @@ SYMBOLS = [
     ("cssm_pf_filter_intervals_more", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_double, _dp, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_pf_step_intervals", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_double, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_pf_intervals_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_pf_filter_forecasts", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, _u64p, C.c_double, _dp, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp,
+                                           _dp, _dp, _dp, _i32p, _i32p]),
+    ("cssm_pf_filter_forecasts_more", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, _u64p, C.c_double, _dp, _dp, _i32p, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                _dp, _dp, _dp, _i32p, _i32p]),
+    ("cssm_pf_step_forecast", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_int, C.c_double, _dp, _i32p, _dp, _dp, _dp, _dp,
+                                        _dp, _dp, _dp, _dp, _dp, _i32p, _i32p]),
+    ("cssm_pf_forecasts_last_ms", C.c_int, [_h, _dp]),
     ("cssm_pf_forecast", C.c_int, [_h, _dp, C.c_size_t, C.c_uint64, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_pf_forecast_posterior", C.c_int, [_h, _descp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp, C.c_size_t, _u32p, C.c_uint64,
                                              C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p]),

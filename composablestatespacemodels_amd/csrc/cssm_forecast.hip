@@ -14,6 +14,8 @@
 // records) and k_forecast_post<D> with PostSrc (a pair of a posterior sample per particle: its state, its own parameters).  A source
 // says where a particle starts, what moves a pair one step and which observation parameters each particle draws with; both step
 // whole pairs through pair_normals_feed and a component through transition_step (cssm_posterior_move.hip.h, cssm_device.hip.h).
+// A third entry point, k_forecast_row<D>, is the body with the compile-time flag ROW over CloudSrc: the first launch of a row of
+// cssm_pf_filter_forecasts (one horizon, enqueued between a batch filter's observations; the rest of the row: cssm_intervals.hip).
 #include "cssm_internal.h"
 #include "cssm_kernels.hip.h"
 #include "cssm_posterior_move.hip.h"
@@ -22,16 +24,91 @@
 
 #include <cmath>
 
+// (forecast_body<ROW>) what a block holds in LDS of its waves' extremes and PIT counts
+template <int D>
+struct FcRowShared {
+  unsigned long long mm[CSSM_BLOCK / 64][D + 2][2];
+  uint32_t pit[CSSM_BLOCK / 64][2];
+};
+template <int D>
+__device__ __forceinline__ FcRowShared<D>& fc_row_shared() {
+  __shared__ FcRowShared<D> s;
+  return s;
+}
 // What the two forecasts share -- everything but where a particle starts and what moves it.  One thread per particle PAIR; a source
 // `s` answers: begin (what it needs of the pair before the first load), x0 (component k of particle i, the pair's particle b, before
 // the first chunk), step (one transition of the pair, or of its first particle alone) and obs (the observation parameters b draws with).
-template <int D, class Src>
+// ROW (k_forecast_row: a row of cssm_pf_filter_forecasts, enqueued between the observations of a batch filter): the one horizon of a
+// forecast, and what the exact selection of cssm_intervals.hip starts from -- per block and row the smallest and the largest key
+// (pmm), the block's two PIT counts against the record's datum (pit) --; the blocks clear the selection's histograms and counters, and
+// a series on hold returns at once.  Geometry, keys and partial sums are the forecast's, so the means keep cssm_pf_forecast's bits.
+struct FcRowOut {
+  const Scalars* sc; unsigned long long* pmm /*[gridDim.x][D + 2][2]*/; uint32_t* pit /*[gridDim.x][2]*/; uint32_t* zero; size_t zero_words;
+  unsigned long long* stamp; double y; int has_y;
+};
+__device__ __forceinline__ unsigned long long fc_shfl_xor(unsigned long long v, int off) {
+  const uint32_t lo = __shfl_xor((uint32_t)v, off, 64), hi = __shfl_xor((uint32_t)(v >> 32), off, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// (ROW) The wave's smallest and largest key of each of the D + 2 rows and its two PIT counts into LDS, a row at a time (nothing of it
+// lives in registers across rows); threads without a particle are neutral.  All threads of the block call it.
+template <int D>
+__device__ __forceinline__ void fc_row_extremes(const FcRowOut* ro, bool live, bool hasb, const double (&xa)[D], const double (&xb)[D], double ea,
+                                                double eb, double oa, double ob) {
+  FcRowShared<D>& s = fc_row_shared<D>();
+#pragma unroll
+  for (int k = 0; k < D + 2; ++k) {
+    const unsigned long long ka = cssm_order_key((k < D) ? xa[k % D] : (k == D ? ea : oa));
+    const unsigned long long kb = cssm_order_key((k < D) ? xb[k % D] : (k == D ? eb : ob));
+    unsigned long long mn = live ? ka : ~0ull, mx = live ? ka : 0ull;
+    if (hasb) { mn = kb < mn ? kb : mn; mx = kb > mx ? kb : mx; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long on = fc_shfl_xor(mn, off), ox = fc_shfl_xor(mx, off);
+      mn = on < mn ? on : mn; mx = ox > mx ? ox : mx;
+    }
+    if ((threadIdx.x & 63) == 0) { s.mm[threadIdx.x >> 6][k][0] = mn; s.mm[threadIdx.x >> 6][k][1] = mx; }
+  }
+  const bool wy = ro->has_y != 0;
+  uint32_t below = (uint32_t)(live && wy && oa < ro->y) + (uint32_t)(hasb && wy && ob < ro->y);
+  uint32_t equal = (uint32_t)(live && wy && oa == ro->y) + (uint32_t)(hasb && wy && ob == ro->y);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { below += __shfl_xor(below, off, 64); equal += __shfl_xor(equal, off, 64); }
+  if ((threadIdx.x & 63) == 0) { s.pit[threadIdx.x >> 6][0] = below; s.pit[threadIdx.x >> 6][1] = equal; }
+}
+// ... and, behind the block's barrier, the block's own into memory
+template <int D>
+__device__ __forceinline__ void fc_row_store(const FcRowOut* ro) {
+  FcRowShared<D>& s = fc_row_shared<D>();
+  if (threadIdx.x < D + 2) {
+    unsigned long long a = ~0ull, b = 0ull;
+    for (int w = 0; w < CSSM_BLOCK / 64; ++w) {
+      const unsigned long long oa = s.mm[w][threadIdx.x][0], ob = s.mm[w][threadIdx.x][1];
+      a = oa < a ? oa : a; b = ob > b ? ob : b;
+    }
+    ro->pmm[((size_t)blockIdx.x * (D + 2) + threadIdx.x) * 2] = a;
+    ro->pmm[((size_t)blockIdx.x * (D + 2) + threadIdx.x) * 2 + 1] = b;
+  }
+  if (threadIdx.x >= 64 && threadIdx.x < 66) {
+    uint32_t c = 0;
+    for (int w = 0; w < CSSM_BLOCK / 64; ++w) c += s.pit[w][threadIdx.x - 64];
+    ro->pit[(size_t)blockIdx.x * 2 + (threadIdx.x - 64)] = c;
+  }
+}
+template <int D, class Src, bool ROW = false>
 __device__ __forceinline__ void forecast_body(Src& s, double* __restrict__ carry, int from_carry, int to_carry, uint64_t n,
                                               const StepRec* __restrict__ recs, uint32_t h0, uint32_t hc, const ModelK& mk, uint64_t key,
                                               const double* __restrict__ logtab, unsigned long long* __restrict__ keys,
-                                              double* __restrict__ partial, double* __restrict__ samples) {
+                                              double* __restrict__ partial, double* __restrict__ samples, const FcRowOut* ro = nullptr) {
   constexpr int R = D + 2;   // rows per horizon: the D state components, eta, the observation
   __shared__ double s_p[CSSM_BLOCK / 64][R];
+  if constexpr (ROW) {
+    // (uniform: an earlier launch of the stream set it.  Bits 0 and 1 -- the weights of an earlier record were unusable: the call
+    //  fails, its rows are unspecified, and nothing is drawn from a cloud nobody resampled)
+    if (ro->sc->err & (IV_HELD | 3u)) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ro->stamp[0] = __builtin_amdgcn_s_memrealtime();
+    for (size_t w = (size_t)blockIdx.x * CSSM_BLOCK + threadIdx.x; w < ro->zero_words; w += (size_t)gridDim.x * CSSM_BLOCK) ro->zero[w] = 0u;
+  }
   const double* tab = stage_log_table(logtab);
   const uint64_t npairs = (n + 1) / 2;
   const uint64_t p = (uint64_t)blockIdx.x * CSSM_BLOCK + threadIdx.x;
@@ -91,12 +168,14 @@ __device__ __forceinline__ void forecast_body(Src& s, double* __restrict__ carry
       for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
       if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6][k] = v;
     }
+    if constexpr (ROW) fc_row_extremes<D>(ro, live, hasb, xa, xb, ea, eb, oa, ob);
     __syncthreads();
     if (threadIdx.x < R) {
       double v = 0.0;
       for (int w = 0; w < CSSM_BLOCK / 64; ++w) v += s_p[w][threadIdx.x];
       partial[(size_t)blockIdx.x * rows + (size_t)j * R + threadIdx.x] = v;
     }
+    if constexpr (ROW) fc_row_store<D>(ro);
     __syncthreads();
   }
   if (to_carry && live) {
@@ -142,6 +221,17 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_forecast(const double* __restric
                                                          double* __restrict__ samples) {
   CloudSrc<D> s{src, src_stride, anc, src2, src2_stride, n_split, op};
   forecast_body<D>(s, carry, from_carry, to_carry, n, recs, h0, hc, mk, key, logtab, keys, partial, samples);
+}
+
+// A row of cssm_pf_filter_forecasts: the single horizon `rec` from the cloud as it stands on the stream (forecast_body<ROW>).
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_forecast_row(const double* __restrict__ src, size_t src_stride, const uint32_t* __restrict__ anc,
+                                                             const double* __restrict__ src2, size_t src2_stride, uint32_t n_split, uint64_t n,
+                                                             const StepRec* __restrict__ rec, ModelK mk, uint64_t key, cssm_obs_params op,
+                                                             const double* __restrict__ logtab, unsigned long long* __restrict__ keys,
+                                                             double* __restrict__ partial, FcRowOut ro) {
+  CloudSrc<D> s{src, src_stride, anc, src2, src2_stride, n_split, op};
+  forecast_body<D, CloudSrc<D>, true>(s, nullptr, 0, 0, n, rec, 0u, 1u, mk, key, logtab, keys, partial, nullptr, &ro);
 }
 
 // ---- forecasts from a joint posterior sample (cssm_pf_forecast_posterior): particle i starts from the state of pair pick_i and
@@ -243,6 +333,27 @@ extern "C" int cssm_obs_draw(int obs_kind, const double* eta, size_t n, int has_
   hipLaunchKernelGGL(k_obs_draw, dim3(grid_for(n, CSSM_BLOCK, kGridCap)), dim3(CSSM_BLOCK), 0, 0, op, de, (uint64_t)n, key, step, dtab, dout);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
+  return CSSM_OK;
+}
+
+// cssm_pf_filter_forecasts (cssm_intervals.hip): what cssm_pf_forecast refuses of the handle's model, in its words ...
+int cssm_forecast_refuse_model(const cssm_pf* pf) {
+  cssm_obs_params op;
+  return obs_params(pf->obs_kind, pf->obs_has_scale, pf->obs_scale, pf->obs_df, &op);
+}
+// ... and the first launch of a row: the horizon of the device record `d_rec` under `key` from the cloud cssm_pf_forecast would read now
+// (src / anc / src2 as the host holds them at this point of the enqueueing), one thread per particle pair
+int cssm_forecast_row_launch(cssm_pf* pf, const StepRec* d_rec, uint64_t key, double y, int has_y, unsigned long long* keys, double* partial,
+                             unsigned long long* pmm, uint32_t* pit, uint32_t* zero, size_t zero_words, unsigned long long* stamp, int nb_f) {
+  cssm_obs_params op;
+  int rc = obs_params(pf->obs_kind, pf->obs_has_scale, pf->obs_scale, pf->obs_df, &op);
+  if (rc) return rc;
+  const bool use_anc = pf->anc_valid;
+  const FcRowOut ro{pf->sc, pmm, pit, zero, zero_words, stamp, y, has_y};
+  DISPATCH_D(pf->d, hipLaunchKernelGGL(k_forecast_row<D>, dim3(nb_f), dim3(CSSM_BLOCK), 0, pf->stream, pf->src, pf->src_stride,
+                                       (const uint32_t*)(use_anc ? pf->anc : nullptr), use_anc ? pf->src2 : nullptr, pf->src2_stride, pf->n_split,
+                                       (uint64_t)pf->n, d_rec, pf->mk, key, op, (const double*)pf->d_logtab, keys, partial, ro));
+  HIP_TRY(hipGetLastError());
   return CSSM_OK;
 }
 

@@ -175,6 +175,8 @@ struct cssm_pf : HostModel, CssmLaunchFields {
   // cssm_pf_filter_intervals (cssm_intervals.hip): the selection's scratch, the call's row buffer and its timing (IvScratch; made at the
   // first call, freed by cssm_iv_free)
   void* iv = nullptr;
+  // cssm_pf_filter_forecasts (cssm_intervals.hip): the same for its rows of d + 2 (a sibling IvScratch)
+  void* fc = nullptr;
 };
 
 // begin/end of one profiled launch
@@ -256,5 +258,19 @@ int cssm_iv_row(cssm_pf* pf, size_t row);        // the summary of the current c
 int cssm_iv_results(cssm_pf* pf, size_t nrows);  // behind the call's last launch: its rows on their way to the host
 void cssm_iv_free(cssm_pf* pf);
 // cssm_pf_ll_filter / cssm_pf_ll_filter_more (cont) with a row behind the initial cloud (not cont) and behind every record; cssm_pf_step with one
-int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont);
-int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out);
+// rows: CSSM_ROWS_INTERVALS (cssm_pf_filter_intervals) or CSSM_ROWS_FORECASTS (cssm_pf_filter_forecasts: a row BEFORE every record)
+#define CSSM_ROWS_NONE 0
+#define CSSM_ROWS_INTERVALS 1
+#define CSSM_ROWS_FORECASTS 2
+int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont,
+                         int rows = CSSM_ROWS_INTERVALS);
+int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out, int rows = CSSM_ROWS_INTERVALS);
+// ---- one-step-ahead forecasts of the single handle (cssm_pf_filter_forecasts): cssm_intervals.hip holds the rows and the selection,
+// cssm_forecast.hip the row's first launch, cssm_pf.hip's drivers say when (before the record's launch_step)
+// Scalars::err bits under which every kernel of a row returns at once: a series on hold or waiting for its second run
+#define IV_HELD (4u | 8u | 16u | 64u)
+int cssm_fc_row(cssm_pf* pf, size_t row);        // the forecast of record `row` of the running call from the cloud as it stands (8 launches, no host work)
+int cssm_fc_results(cssm_pf* pf, size_t nrows);
+int cssm_forecast_refuse_model(const cssm_pf* pf);   // what cssm_pf_forecast refuses of the handle's model, in its words
+int cssm_forecast_row_launch(cssm_pf* pf, const StepRec* d_rec, uint64_t key, double y, int has_y, unsigned long long* keys, double* partial,
+                             unsigned long long* pmm, uint32_t* pit, uint32_t* zero, size_t zero_words, unsigned long long* stamp, int nb_f);

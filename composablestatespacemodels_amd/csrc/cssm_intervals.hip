@@ -1,4 +1,6 @@
-// cssm_intervals.hip -- cssm_pf_filter_intervals, cssm_pf_filter_intervals_more, cssm_pf_step_intervals (include/cssm_pf.h): the
+// cssm_intervals.hip -- the rows a batch filter of ONE large cloud forms between its observations: filtered intervals behind every record,
+// one-step-ahead forecasts before every record (below), both on one exact two-rank selection.
+// cssm_pf_filter_intervals, cssm_pf_filter_intervals_more, cssm_pf_step_intervals (include/cssm_pf.h): the
 // filtered intervals of ONE large cloud, a row per observation, enqueued between the observations of the batch filter with no host
 // round trip.  A row has the bits of cssm_pf_summary at that moment of the loop init; summary; (step; summary)*.
 //
@@ -22,6 +24,23 @@
 // picked sub-range): 3 reads against 9.  A row whose picked sub-range holds more than a quarter of the row AND more than one key
 // (heavy ties next to other values) reads its keys again, at most CSSM_IV_ROUNDS times in all.
 // A series on hold (Scalars::err bit 6) or waiting for its second run: every kernel returns at once, as the filter's own do.
+//
+// cssm_pf_filter_forecasts, cssm_pf_filter_forecasts_more, cssm_pf_step_forecast: the one-step-ahead forecast of every record's time
+// from the cloud BEFORE the record, a row enqueued in front of the record's own launches.  A row has the bits of
+// cssm_pf_forecast(pf, &t[s], 1, key_s, ...) issued at that moment.  Per row 8 launches (cssm_pf_forecast: 18, with eight
+// allocations, three events and a blocking read-back) and no allocation:
+//   k_forecast_row<D>   (cssm_forecast.hip) forecast_body in k_forecast's geometry -- one thread per particle pair, no cap on the blocks,
+//                       the blocks' partial sums of all d + 2 rows: the means keep their bits --: transition, gamma, eta, the observation
+//                       draw, the order keys; per block and row the smallest and the largest key, per block the two PIT counts; its
+//                       blocks clear the row's histograms and slot counters.
+//   k_iv_round x 6      the selection above over d + 2 rows; the observation row takes eta's ranks (getOrderStatistic).
+//   k_fc_finish         a block per row: the last derivation and the remaining passes in LDS; EVERY row's mean by k_forecast_finish's
+//                       combine (thread-strided over the blocks, the wave butterfly, the waves in order); the PIT counts added up.
+// The cloud is read once (through its ancestors), its keys twice in the ordinary case of a state or eta row.  An observation row of
+// counts (Poisson at rate 2: about ten distinct keys; Bernoulli: two) is the heavy-ties case above as a matter of course: its keys are
+// read again, at most CSSM_IV_ROUNDS times.  The records the rows move under are StepRecs of their own (horizon index 0), uploaded with
+// the call; under a hold the rows behind the held record return at once and are enqueued again with the records, the held record's
+// own row was formed before the hold and stands.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,7 +50,6 @@
 #include "cssm_kernels.hip.h"
 #include "cssm_intervals.hip.h"
 
-#define IV_HELD (4u | 8u | 16u | 64u)
 #define IV_ITEMS 8
 #define IV_CHUNK (CSSM_BLOCK * IV_ITEMS)   /* keys a block reads per iteration */
 #define IV_PART_KEYS 16384                 /* keys per block of a pass: a block merges its histogram with up to 2 x 2048 atomics, so not too few */
@@ -42,9 +60,9 @@ struct IvRow { cssm_iv_target tg[2]; };
 struct IvArgs {
   const unsigned long long* keys;   // [rows][n]
   uint64_t n;
-  int rows, d, nblocks;             // nblocks: k_iv_fill's grid
+  int rows, d, nblocks;             // rows: d + 1, or a forecast's d + 2; nblocks: the grid of k_iv_fill, or of k_forecast_row
   const unsigned long long* pmm;    // [nblocks][rows][2]: the blocks' min and max key
-  const double* partial;            // [nblocks][d]
+  const double* partial;            // [nblocks][d] (a forecast: [nblocks][rows])
   uint32_t* hist;                   // [CSSM_IV_ROUNDS][rows][2][CSSM_IV_BINS]
   uint32_t* ccnt;                   // [2][rows][2]: candidate slots handed out, of the long and of the short buffer
   unsigned long long* cand;         // [rows][2][cand_max]
@@ -195,7 +213,7 @@ __device__ __forceinline__ IvRow iv_derive(const IvArgs& a, int r, int row, uint
     mn = ~0ull; mx = 0ull;
     for (int w = 0; w < CSSM_BLOCK / 64; ++w) { mn = s.red[w][0] < mn ? s.red[w][0] : mn; mx = s.red[w][1] > mx ? s.red[w][1] : mx; }
     __syncthreads();
-    const int e = row == a.d ? 2 : 0;
+    const int e = row >= a.d ? 2 : 0;   // (eta, and a forecast's observation row behind it: getOrderStatistic's ranks)
     S.tg[0] = cssm_iv_start(mn, mx, a.rank[e], a.n);
     S.tg[1] = cssm_iv_start(mn, mx, a.rank[e + 1], a.n);
     return S;
@@ -312,21 +330,12 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_iv_round(const IvArgs a, int r) 
   }
 }
 
-// the row: one block per row of the cloud
-__global__ __launch_bounds__(CSSM_BLOCK) void k_iv_finish(const IvArgs a, double* __restrict__ out /*[3][rows]: mean, lower, upper*/,
-                                                          unsigned long long* __restrict__ stamp /*[0] the fill's start, [1] ticks so far*/) {
-  __shared__ uint32_t s_h[2 * CSSM_IV_BINS];
-  __shared__ IvShared s;
-  __shared__ unsigned long long s_k[CSSM_IV_CAP];
-  __shared__ double s_part[1024];                                 // the fill's partial sums of this row (its grid: at most 1024 blocks)
-  __shared__ uint32_t s_m;
-  if (a.sc->err & IV_HELD) return;
-  const int row = blockIdx.x;
+// The two selected keys of a row behind its last pass, by the row's one block: the last derivation, and a target with at most CSSM_IV_CAP
+// candidates in range runs its remaining passes in LDS (s_h: [2][CSSM_IV_BINS], s_k: [CSSM_IV_CAP]).  Ends on a block barrier.
+__device__ __forceinline__ void iv_final_keys(const IvArgs& a, int row, uint32_t* s_h, IvShared& s, unsigned long long* s_k, uint32_t& s_m,
+                                              unsigned long long (&key)[2]) {
   const uint32_t tid = threadIdx.x;
-  // (the whole block fetches the partial sums: one thread adding them up straight from memory waited for 1024 loads in turn, 400 us)
-  if (row < a.d) for (int b = (int)tid; b < a.nblocks && b < 1024; b += CSSM_BLOCK) s_part[b] = a.partial[(size_t)b * a.d + row];
   const IvRow S = iv_derive(a, CSSM_IV_ROUNDS, row, s_h, s);
-  unsigned long long key[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     cssm_iv_target g = S.tg[t];
@@ -363,6 +372,23 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_iv_finish(const IvArgs a, double
     }
   }
   __syncthreads();
+}
+
+// the row: one block per row of the cloud
+__global__ __launch_bounds__(CSSM_BLOCK) void k_iv_finish(const IvArgs a, double* __restrict__ out /*[3][rows]: mean, lower, upper*/,
+                                                          unsigned long long* __restrict__ stamp /*[0] the fill's start, [1] ticks so far*/) {
+  __shared__ uint32_t s_h[2 * CSSM_IV_BINS];
+  __shared__ IvShared s;
+  __shared__ unsigned long long s_k[CSSM_IV_CAP];
+  __shared__ double s_part[1024];                                 // the fill's partial sums of this row (its grid: at most 1024 blocks)
+  __shared__ uint32_t s_m;
+  if (a.sc->err & IV_HELD) return;
+  const int row = blockIdx.x;
+  const uint32_t tid = threadIdx.x;
+  // (the whole block fetches the partial sums: one thread adding them up straight from memory waited for 1024 loads in turn, 400 us)
+  if (row < a.d) for (int b = (int)tid; b < a.nblocks && b < 1024; b += CSSM_BLOCK) s_part[b] = a.partial[(size_t)b * a.d + row];
+  unsigned long long key[2];
+  iv_final_keys(a, row, s_h, s, s_k, s_m, key);
   if (tid == 0) {
     if (row < a.d) {
       double sum = 0.0;                                           // k_summary_finish's sequential combine over the blocks
@@ -378,14 +404,61 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_iv_finish(const IvArgs a, double
   }
 }
 
+// The row of a one-step-ahead forecast (cssm_pf_filter_forecasts): one block per row of the d + 2.  Every row has a mean, formed as
+// k_forecast_finish (cssm_forecast.hip) combines the partial sums of k_forecast's blocks -- thread-strided over the blocks, the wave
+// butterfly, the waves in order --; the block of the observation row also adds up the blocks' PIT counts (integers).
+__global__ __launch_bounds__(CSSM_BLOCK) void k_fc_finish(const IvArgs a, const uint32_t* __restrict__ pit /*[nblocks][2]*/,
+                                                          double* __restrict__ out /*[3][rows]: mean, lower, upper; then the two counts (int32)*/,
+                                                          unsigned long long* __restrict__ stamp) {
+  __shared__ uint32_t s_h[2 * CSSM_IV_BINS];
+  __shared__ IvShared s;
+  __shared__ unsigned long long s_k[CSSM_IV_CAP];
+  __shared__ double s_w[CSSM_BLOCK / 64];
+  __shared__ uint32_t s_c[2];
+  __shared__ uint32_t s_m;
+  if (a.sc->err & IV_HELD) return;
+  const int row = blockIdx.x;
+  const uint32_t tid = threadIdx.x;
+  if (tid < 2u) s_c[tid] = 0u;
+  double v = 0.0;
+  for (int b = (int)tid; b < a.nblocks; b += CSSM_BLOCK) v += a.partial[(size_t)b * a.rows + row];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((tid & 63u) == 0u) s_w[tid >> 6] = v;
+  __syncthreads();
+  if (row == a.rows - 1) {                                        // (uniform)
+    uint32_t c0 = 0u, c1 = 0u;
+    for (int b = (int)tid; b < a.nblocks; b += CSSM_BLOCK) { c0 += pit[(size_t)b * 2]; c1 += pit[(size_t)b * 2 + 1]; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { c0 += __shfl_xor(c0, off, 64); c1 += __shfl_xor(c1, off, 64); }
+    if ((tid & 63u) == 0u) { atomicAdd(&s_c[0], c0); atomicAdd(&s_c[1], c1); }
+  }
+  unsigned long long key[2];
+  iv_final_keys(a, row, s_h, s, s_k, s_m, key);
+  if (tid == 0) {
+    double sum = 0.0;
+    for (int w = 0; w < CSSM_BLOCK / 64; ++w) sum += s_w[w];
+    out[row] = sum / (double)a.n;
+    out[a.rows + row] = cssm_order_unkey(key[0]);
+    out[2 * a.rows + row] = cssm_order_unkey(key[1]);
+    if (row == a.rows - 1) {
+      int32_t* cnt = reinterpret_cast<int32_t*>(out + 3 * (size_t)a.rows);
+      cnt[0] = (int32_t)s_c[0]; cnt[1] = (int32_t)s_c[1];
+    }
+    if (row == 0) stamp[1] += __builtin_amdgcn_s_memrealtime() - stamp[0];
+  }
+}
+
 // ------------------------------------------------------------------------------------ host side
-// The selection's scratch lives on the handle: made at the first call, the per-call parts grown on demand, freed with the handle.
+// The selection's scratch lives on the handle: made at the first call, the per-call parts grown on demand, freed with the handle.  One
+// per kind of row: cssm_pf::iv (filtered intervals, d + 1 rows from k_iv_fill) and cssm_pf::fc (forecasts, d + 2 rows from k_forecast_row).
 struct IvScratch {
   unsigned long long *keys = nullptr, *pmm = nullptr, *cand = nullptr, *cand2 = nullptr, *stamp = nullptr;
   double *partial = nullptr, *fco = nullptr, *rows = nullptr, *h_rows = nullptr;
   uint32_t* zero = nullptr;      // the histograms, then the slot counters
   IvRow* st = nullptr;
   size_t zero_words = 0, fco_cap = 0, rows_cap = 0;
+  size_t out_stride = 0;         // doubles per row of the call's row buffer: 3 per row of the cloud (a forecast: + 1, its two PIT counts)
   uint64_t cand_max = 0;
   int nblocks = 0;
   uint64_t rank[4] = {0, 0, 0, 0};
@@ -393,18 +466,30 @@ struct IvScratch {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   double ms[2] = {-1.0, -1.0};
+  // forecasts: the blocks' PIT counts; the call's records (apart from the filter's), and per record its key, its datum and whether
+  // cssm_pf_forecast would refuse its time (no launch, a NaN row)
+  uint32_t* pit = nullptr;
+  StepRec* recs = nullptr;
+  std::vector<StepRec> h_recs;
+  std::vector<uint64_t> key;
+  std::vector<double> y;
+  std::vector<uint8_t> has, refused;
 };
 
-void cssm_iv_free(cssm_pf* pf) {
-  IvScratch* s = static_cast<IvScratch*>(pf->iv);
+static void iv_free_one(void*& slot) {
+  IvScratch* s = static_cast<IvScratch*>(slot);
   if (!s) return;
-  void* ptrs[] = {s->keys, s->pmm, s->cand, s->cand2, s->stamp, s->partial, s->fco, s->rows, s->zero, s->st};
+  void* ptrs[] = {s->keys, s->pmm, s->cand, s->cand2, s->stamp, s->partial, s->fco, s->rows, s->zero, s->st, s->pit, s->recs};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (s->h_rows) (void)hipHostFree(s->h_rows);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   delete s;
-  pf->iv = nullptr;
+  slot = nullptr;
+}
+void cssm_iv_free(cssm_pf* pf) {
+  iv_free_one(pf->iv);
+  iv_free_one(pf->fc);
 }
 
 #define IV_ALLOC(p, bytes)                                                                                               \
@@ -414,21 +499,25 @@ void cssm_iv_free(cssm_pf* pf) {
     p = static_cast<decltype(p)>(q__);                                                                                   \
   } while (0)
 
-// scratch for calls of up to nrows rows; the ranks of `interval`
-static int iv_ensure(cssm_pf* pf, size_t nrows, double interval) {
-  if (!pf->iv) pf->iv = new IvScratch();
-  IvScratch* s = static_cast<IvScratch*>(pf->iv);
-  const int d = pf->d, rows = d + 1;
+// scratch (the handle's `slot`) for calls of up to nrows rows; the ranks of `interval`.  fc: rows of a forecast -- d + 2 of them, the first
+// launch in k_forecast's geometry (one thread per particle pair, no cap on the blocks: the partial sums are the forecast's)
+static int iv_ensure(cssm_pf* pf, void*& slot, bool fc, size_t nrows, double interval) {
+  if (!slot) slot = new IvScratch();
+  IvScratch* s = static_cast<IvScratch*>(slot);
+  const int d = pf->d, rows = fc ? d + 2 : d + 1;
   const uint64_t n = pf->n;
+  s->out_stride = 3 * (size_t)rows + (fc ? 1 : 0);
   if (!s->keys) {
     // (an earlier attempt that ran out of memory half way: start over)
-    void** part[] = {(void**)&s->pmm, (void**)&s->partial, (void**)&s->cand, (void**)&s->cand2, (void**)&s->zero, (void**)&s->st, (void**)&s->stamp};
+    void** part[] = {(void**)&s->pmm, (void**)&s->partial, (void**)&s->cand, (void**)&s->cand2, (void**)&s->zero, (void**)&s->st, (void**)&s->stamp,
+                     (void**)&s->pit};
     for (void** p : part) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    s->nblocks = grid_for(n, CSSM_BLOCK, 1024);
+    s->nblocks = fc ? (int)(((n + 1) / 2 + CSSM_BLOCK - 1) / CSSM_BLOCK) : grid_for(n, CSSM_BLOCK, 1024);
     s->cand_max = cssm_iv_cand_max(n);
     s->zero_words = (size_t)CSSM_IV_ROUNDS * rows * 2 * CSSM_IV_BINS + (size_t)rows * 4;
     IV_ALLOC(s->pmm, (size_t)s->nblocks * rows * 2 * 8);
-    IV_ALLOC(s->partial, (size_t)s->nblocks * d * 8);
+    IV_ALLOC(s->partial, (size_t)s->nblocks * (fc ? rows : d) * 8);
+    if (fc) IV_ALLOC(s->pit, (size_t)s->nblocks * 2 * 4);
     IV_ALLOC(s->cand, (size_t)rows * 2 * s->cand_max * 8);
     IV_ALLOC(s->cand2, (size_t)rows * 2 * CSSM_IV_CAP * 8);
     IV_ALLOC(s->zero, s->zero_words * 4);
@@ -442,12 +531,14 @@ static int iv_ensure(cssm_pf* pf, size_t nrows, double interval) {
     HIP_TRY(hipStreamSynchronize(pf->stream));
     if (s->fco) (void)hipFree(s->fco);
     if (s->rows) (void)hipFree(s->rows);
+    if (s->recs) (void)hipFree(s->recs);
     if (s->h_rows) (void)hipHostFree(s->h_rows);
-    s->fco = s->rows = s->h_rows = nullptr; s->fco_cap = s->rows_cap = 0;
+    s->fco = s->rows = s->h_rows = nullptr; s->recs = nullptr; s->fco_cap = s->rows_cap = 0;
     const size_t cap = nrows < 1024 ? 1024 : nrows + nrows / 2;
-    IV_ALLOC(s->fco, cap * CSSM_MAX_DIM * 8);
-    IV_ALLOC(s->rows, cap * 3 * rows * 8);
-    HIP_TRY(hipHostMalloc((void**)&s->h_rows, cap * 3 * rows * 8 + 16, hipHostMallocDefault));
+    if (fc) IV_ALLOC(s->recs, cap * sizeof(StepRec));
+    else IV_ALLOC(s->fco, cap * CSSM_MAX_DIM * 8);
+    IV_ALLOC(s->rows, cap * s->out_stride * 8);
+    HIP_TRY(hipHostMalloc((void**)&s->h_rows, cap * s->out_stride * 8 + 16, hipHostMallocDefault));
     s->fco_cap = s->rows_cap = cap;
   }
   cssm_iv_ranks(n, interval, 1, &s->rank[0], &s->rank[1]);
@@ -456,36 +547,61 @@ static int iv_ensure(cssm_pf* pf, size_t nrows, double interval) {
 }
 
 // The summary of the handle's current cloud, enqueued as row `row` of the call (its f coefficients: row `row` of the call's table).
+// the selection's arguments over the `rows` rows of the scratch `s`, and its passes behind the row's first launch
+static IvArgs iv_args(const cssm_pf* pf, const IvScratch* s, int rows) {
+  IvArgs a;
+  a.keys = s->keys; a.n = pf->n; a.rows = rows; a.d = pf->d; a.nblocks = s->nblocks; a.pmm = s->pmm; a.partial = s->partial;
+  a.hist = s->zero; a.ccnt = s->zero + (size_t)CSSM_IV_ROUNDS * rows * 2 * CSSM_IV_BINS; a.cand = s->cand; a.cand2 = s->cand2; a.cand_max = s->cand_max;
+  a.st = s->st; a.sc = pf->sc;
+  for (int q = 0; q < 4; ++q) a.rank[q] = s->rank[q];
+  return a;
+}
+static void iv_launch_rounds(cssm_pf* pf, const IvArgs& a) {
+  const uint64_t parts64 = (a.n + IV_PART_KEYS - 1) / IV_PART_KEYS;
+  const int parts = (int)(parts64 < 1 ? 1 : (parts64 > IV_MAX_PARTS ? IV_MAX_PARTS : parts64));
+  for (int r = 1; r <= CSSM_IV_ROUNDS; ++r) hipLaunchKernelGGL(k_iv_round, dim3(parts, a.rows), dim3(CSSM_BLOCK), 0, pf->stream, a, r);
+}
+
 int cssm_iv_row(cssm_pf* pf, size_t row) {
   IvScratch* s = static_cast<IvScratch*>(pf->iv);
   if (!s || !s->keys || row >= s->rows_cap) return fail(CSSM_ESTATE, "a row of filtered intervals outside the call's row buffer");
   const int d = pf->d, rows = d + 1;
   const uint64_t n = pf->n;
-  IvArgs a;
-  a.keys = s->keys; a.n = n; a.rows = rows; a.d = d; a.nblocks = s->nblocks; a.pmm = s->pmm; a.partial = s->partial;
-  a.hist = s->zero; a.ccnt = s->zero + (size_t)CSSM_IV_ROUNDS * rows * 2 * CSSM_IV_BINS; a.cand = s->cand; a.cand2 = s->cand2; a.cand_max = s->cand_max;
-  a.st = s->st; a.sc = pf->sc;
-  for (int q = 0; q < 4; ++q) a.rank[q] = s->rank[q];
+  const IvArgs a = iv_args(pf, s, rows);
   DISPATCH_D(d, k_iv_fill<D><<<dim3(s->nblocks), dim3(CSSM_BLOCK), 0, pf->stream>>>(
                     pf->src, pf->src_stride, pf->anc_valid ? pf->anc : nullptr, n, s->fco + row * CSSM_MAX_DIM, pf->mk, s->keys, s->partial,
                     s->pmm, s->zero, s->zero_words, pf->sc, s->stamp));
-  const uint64_t parts64 = (n + IV_PART_KEYS - 1) / IV_PART_KEYS;
-  const int parts = (int)(parts64 < 1 ? 1 : (parts64 > IV_MAX_PARTS ? IV_MAX_PARTS : parts64));
-  for (int r = 1; r <= CSSM_IV_ROUNDS; ++r) hipLaunchKernelGGL(k_iv_round, dim3(parts, rows), dim3(CSSM_BLOCK), 0, pf->stream, a, r);
-  hipLaunchKernelGGL(k_iv_finish, dim3(rows), dim3(CSSM_BLOCK), 0, pf->stream, a, s->rows + row * 3 * (size_t)rows, s->stamp);
+  iv_launch_rounds(pf, a);
+  hipLaunchKernelGGL(k_iv_finish, dim3(rows), dim3(CSSM_BLOCK), 0, pf->stream, a, s->rows + row * s->out_stride, s->stamp);
+  HIP_TRY(hipGetLastError());
+  return CSSM_OK;
+}
+
+// The forecast of record `row` of the running call from the cloud as the host-side source fields describe it now, enqueued as that row.
+int cssm_fc_row(cssm_pf* pf, size_t row) {
+  IvScratch* s = static_cast<IvScratch*>(pf->fc);
+  if (!s || !s->keys || row >= s->rows_cap || row >= s->refused.size()) return fail(CSSM_ESTATE, "a forecast row outside the call's row buffer");
+  if (s->refused[row]) return CSSM_OK;   // (a time cssm_pf_forecast refuses from this cloud: a NaN row, made by the host)
+  const int rows = pf->d + 2;
+  const IvArgs a = iv_args(pf, s, rows);
+  const int rc = cssm_forecast_row_launch(pf, s->recs + row, s->key[row], s->y[row], s->has[row], s->keys, s->partial, s->pmm, s->pit, s->zero,
+                                          s->zero_words, s->stamp, s->nblocks);
+  if (rc) return rc;
+  iv_launch_rounds(pf, a);
+  hipLaunchKernelGGL(k_fc_finish, dim3(rows), dim3(CSSM_BLOCK), 0, pf->stream, a, (const uint32_t*)s->pit, s->rows + row * s->out_stride, s->stamp);
   HIP_TRY(hipGetLastError());
   return CSSM_OK;
 }
 
 // Behind the call's last launch: the end of its device time, and the rows (with the summaries' ticks) on their way to the host.
-int cssm_iv_results(cssm_pf* pf, size_t nrows) {
-  IvScratch* s = static_cast<IvScratch*>(pf->iv);
-  const size_t rows = (size_t)pf->d + 1;
+static int iv_results(cssm_pf* pf, IvScratch* s, size_t nrows) {
   HIP_TRY(hipEventRecord(s->ev1, pf->stream));
-  HIP_TRY(hipMemcpyAsync(s->h_rows, s->rows, nrows * 3 * rows * 8, hipMemcpyDeviceToHost, pf->stream));
-  HIP_TRY(hipMemcpyAsync(s->h_rows + s->rows_cap * 3 * rows, s->stamp, 16, hipMemcpyDeviceToHost, pf->stream));
+  HIP_TRY(hipMemcpyAsync(s->h_rows, s->rows, nrows * s->out_stride * 8, hipMemcpyDeviceToHost, pf->stream));
+  HIP_TRY(hipMemcpyAsync(s->h_rows + s->rows_cap * s->out_stride, s->stamp, 16, hipMemcpyDeviceToHost, pf->stream));
   return CSSM_OK;
 }
+int cssm_iv_results(cssm_pf* pf, size_t nrows) { return iv_results(pf, static_cast<IvScratch*>(pf->iv), nrows); }
+int cssm_fc_results(cssm_pf* pf, size_t nrows) { return iv_results(pf, static_cast<IvScratch*>(pf->fc), nrows); }
 
 // what every call checks before any work, in its neighbours' words
 static int iv_refuse(cssm_pf* pf, double interval) {
@@ -497,7 +613,7 @@ static int iv_refuse(cssm_pf* pf, double interval) {
 // the call's table of f coefficients, one row of CSSM_MAX_DIM per summary: F(t) of the row's time, as cssm_pf_summary builds it
 static int iv_begin(cssm_pf* pf, const std::vector<double>& times, double interval) {
   HIP_TRY(hipSetDevice(pf->device));
-  int rc = iv_ensure(pf, times.size(), interval);
+  int rc = iv_ensure(pf, pf->iv, false, times.size(), interval);
   if (rc) return rc;
   IvScratch* s = static_cast<IvScratch*>(pf->iv);
   s->h_fco.assign(times.size() * CSSM_MAX_DIM, 0.0);
@@ -519,7 +635,7 @@ static void iv_unpack(cssm_pf* pf, size_t nrows, double* state_mean, double* sta
   IvScratch* s = static_cast<IvScratch*>(pf->iv);
   const int d = pf->d, rows = d + 1;
   for (size_t r = 0; r < nrows; ++r) {
-    const double* h = s->h_rows + r * 3 * (size_t)rows;
+    const double* h = s->h_rows + r * s->out_stride;
     for (int k = 0; k < d; ++k) {
       if (state_mean) state_mean[r * d + k] = h[k];
       if (state_lower) state_lower[r * d + k] = h[rows + k];
@@ -579,20 +695,141 @@ extern "C" int cssm_pf_step_intervals(cssm_pf* pf, double t, double obs, int has
   return CSSM_OK;
 }
 
-extern "C" int cssm_pf_intervals_last_ms(cssm_pf* pf, double* ms2) {
-  if (!pf || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
-  IvScratch* s = static_cast<IvScratch*>(pf->iv);
-  if (!s || !s->timed) return fail(CSSM_ESTATE, "no call of filtered intervals has completed on this handle");
+// the device times of the last completed call on the scratch `s`: the event pair, and the ticks its rows' launches added up
+static int iv_last_ms(cssm_pf* pf, IvScratch* s, double* ms2, const char* what) {
+  if (!s || !s->timed) return fail(CSSM_ESTATE, "no call of %s has completed on this handle", what);
   if (s->ms[0] < 0.0) {
     HIP_TRY(hipSetDevice(pf->device));
     float ms = 0.f;
     HIP_TRY(hipEventSynchronize(s->ev1));
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     unsigned long long ticks = 0;
-    memcpy(&ticks, reinterpret_cast<const char*>(s->h_rows + s->rows_cap * 3 * ((size_t)pf->d + 1)) + 8, 8);
+    memcpy(&ticks, reinterpret_cast<const char*>(s->h_rows + s->rows_cap * s->out_stride) + 8, 8);
     s->ms[0] = (double)ms;
     s->ms[1] = (double)ticks * 1e-5;   // 100 MHz
   }
   ms2[0] = s->ms[0]; ms2[1] = s->ms[1];
   return CSSM_OK;
+}
+
+extern "C" int cssm_pf_intervals_last_ms(cssm_pf* pf, double* ms2) {
+  if (!pf || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
+  return iv_last_ms(pf, static_cast<IvScratch*>(pf->iv), ms2, "filtered intervals");
+}
+
+// ------------------------------------------------------------------------------------ one-step-ahead forecasts
+// The call's forecast records, apart from the filter's: record s moves the cloud before it over t[s] - (the time before it) at horizon
+// index 0, as forecast_chunks builds the one record of cssm_pf_forecast(&t[s], 1); its key, its datum (for the PIT counts) and whether
+// cssm_pf_forecast would refuse its time (cssm_check_times: not finite, or before the cloud's time).  t_prev: the time before record 0;
+// base: the observation index of the cloud before record 0.
+static int fc_begin(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, const uint64_t* keys, double interval,
+                    double t_prev, uint32_t base) {
+  HIP_TRY(hipSetDevice(pf->device));
+  int rc = iv_ensure(pf, pf->fc, true, T, interval);
+  if (rc) return rc;
+  IvScratch* s = static_cast<IvScratch*>(pf->fc);
+  s->h_recs.resize(T); s->key.resize(T); s->y.resize(T); s->has.resize(T); s->refused.resize(T);
+  for (size_t r = 0; r < T; ++r) {
+    const double tp = r ? t[r - 1] : t_prev;
+    s->refused[r] = !(std::isfinite(t[r]) && t[r] >= tp);
+    if (!s->refused[r]) cssm_build_rec(pf, tp, t[r], 0.0, 0, 0, &s->h_recs[r]);
+    else memset(&s->h_recs[r], 0, sizeof(StepRec));
+    s->key[r] = keys ? keys[r] : cssm_pf_run_key(pf->seed, (1ull << 63) | (uint64_t)(base + (uint32_t)r));
+    s->has[r] = has ? (has[r] != 0) : 1;
+    s->y[r] = y[r];
+  }
+  HIP_TRY(hipMemcpyAsync(s->recs, s->h_recs.data(), T * sizeof(StepRec), hipMemcpyHostToDevice, pf->stream));
+  HIP_TRY(hipMemsetAsync(s->stamp, 0, 16, pf->stream));
+  s->timed = false; s->ms[0] = s->ms[1] = -1.0;
+  HIP_TRY(hipEventRecord(s->ev0, pf->stream));
+  return CSSM_OK;
+}
+
+struct FcOut {
+  double *state_mean, *state_lower, *state_upper, *eta_mean, *eta_lower, *eta_upper, *obs_mean, *obs_lower, *obs_upper;
+  int32_t *obs_below, *obs_equal;
+};
+
+// the downloaded rows -> the caller's arrays (a refused time: NaN and -1; a record without a datum: counts of -1)
+static void fc_unpack(cssm_pf* pf, size_t nrows, const FcOut& o) {
+  IvScratch* s = static_cast<IvScratch*>(pf->fc);
+  const int d = pf->d, rows = d + 2;
+  std::vector<double> nan_row(s->out_stride, cssm_nan());
+  for (size_t r = 0; r < nrows; ++r) {
+    const bool bad = s->refused[r] != 0;
+    const double* h = bad ? nan_row.data() : s->h_rows + r * s->out_stride;
+    for (int k = 0; k < d; ++k) {
+      if (o.state_mean) o.state_mean[r * d + k] = h[k];
+      if (o.state_lower) o.state_lower[r * d + k] = h[rows + k];
+      if (o.state_upper) o.state_upper[r * d + k] = h[2 * rows + k];
+    }
+    if (o.eta_mean) o.eta_mean[r] = h[d];
+    if (o.eta_lower) o.eta_lower[r] = h[rows + d];
+    if (o.eta_upper) o.eta_upper[r] = h[2 * rows + d];
+    if (o.obs_mean) o.obs_mean[r] = h[d + 1];
+    if (o.obs_lower) o.obs_lower[r] = h[rows + d + 1];
+    if (o.obs_upper) o.obs_upper[r] = h[2 * rows + d + 1];
+    int32_t cnt[2] = {-1, -1};
+    if (!bad && s->has[r]) memcpy(cnt, h + 3 * (size_t)rows, 8);
+    if (o.obs_below) o.obs_below[r] = cnt[0];
+    if (o.obs_equal) o.obs_equal[r] = cnt[1];
+  }
+  s->timed = true;
+}
+
+static int fc_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T, const uint64_t* keys, double interval, bool cont,
+                     double* ll_out, double* ll_t, int32_t* ess_t, const FcOut& o) {
+  if (!pf || !t || !y) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data (the reference's minBy throws on an empty Vector)");
+  int rc = iv_refuse(pf, interval);
+  if (rc) return rc;
+  if (cont && !pf->initialised) return fail(CSSM_ESTATE, "continuing a filter needs an initialised handle (and records no path)");
+  rc = cssm_forecast_refuse_model(pf);
+  if (rc) return rc;
+  rc = fc_begin(pf, t, y, has_obs, T, keys, interval, cont ? pf->t : cssm_series_t0(t, T), cont ? pf->step : 0u);
+  if (rc) return rc;
+  rc = cssm_run_filter_rows(pf, t, y, has_obs, T, ll_out, ll_t, ess_t, cont, CSSM_ROWS_FORECASTS);
+  if (rc) return rc;
+  fc_unpack(pf, T, o);
+  return CSSM_OK;
+}
+
+extern "C" int cssm_pf_filter_forecasts(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T, const uint64_t* keys,
+                                        double interval, double* ll_out, double* ll_t, int32_t* ess_t, double* state_mean, double* state_lower,
+                                        double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper, double* obs_mean,
+                                        double* obs_lower, double* obs_upper, int32_t* obs_below, int32_t* obs_equal) {
+  return fc_filter(pf, t, y, has_obs, T, keys, interval, false, ll_out, ll_t, ess_t,
+                   FcOut{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal});
+}
+
+extern "C" int cssm_pf_filter_forecasts_more(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T, const uint64_t* keys,
+                                             double interval, double* ll_out, double* ll_t, int32_t* ess_t, double* state_mean,
+                                             double* state_lower, double* state_upper, double* eta_mean, double* eta_lower, double* eta_upper,
+                                             double* obs_mean, double* obs_lower, double* obs_upper, int32_t* obs_below, int32_t* obs_equal) {
+  return fc_filter(pf, t, y, has_obs, T, keys, interval, true, ll_out, ll_t, ess_t,
+                   FcOut{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal});
+}
+
+extern "C" int cssm_pf_step_forecast(cssm_pf* pf, double t, double obs, int has_obs, uint64_t key, int use_key, double interval, double* ll_out,
+                                     int32_t* ess_out, double* state_mean, double* state_lower, double* state_upper, double* eta_mean,
+                                     double* eta_lower, double* eta_upper, double* obs_mean, double* obs_lower, double* obs_upper,
+                                     int32_t* obs_below, int32_t* obs_equal) {
+  if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
+  if (!pf->initialised) return fail(CSSM_ESTATE, "cssm_pf_step before cssm_pf_init");
+  int rc = cssm_forecast_refuse_model(pf);
+  if (rc) return rc;
+  const uint8_t has = has_obs ? 1 : 0;
+  rc = fc_begin(pf, &t, &obs, &has, 1, use_key ? &key : nullptr, interval, pf->t, pf->step);
+  if (rc) return rc;
+  rc = cssm_step_rows(pf, t, obs, has_obs, ll_out, ess_out, CSSM_ROWS_FORECASTS);
+  if (rc) return rc;
+  fc_unpack(pf, 1, FcOut{state_mean, state_lower, state_upper, eta_mean, eta_lower, eta_upper, obs_mean, obs_lower, obs_upper, obs_below, obs_equal});
+  return CSSM_OK;
+}
+
+extern "C" int cssm_pf_forecasts_last_ms(cssm_pf* pf, double* ms2) {
+  if (!pf || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
+  return iv_last_ms(pf, static_cast<IvScratch*>(pf->fc), ms2, "one-step-ahead forecasts");
 }

@@ -605,8 +605,9 @@ extern "C" int cssm_pf_init_from(cssm_pf* pf, double t0, const double* state_d) 
   return CSSM_OK;
 }
 
-// rows: cssm_pf_step_intervals -- the summary of the resampled cloud is enqueued behind the step (after a redo: again) and travels with its scalars
-static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out, bool rows) {
+// rows: cssm_pf_step_intervals -- the summary of the resampled cloud is enqueued behind the step (after a redo: again) and travels with its scalars;
+// cssm_pf_step_forecast -- the forecast of the record's time is enqueued BEFORE the step, from the cloud the step reads (a redo leaves it alone)
+static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out, int rows) {
   if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
   if (!pf->initialised) return fail(CSSM_ESTATE, "cssm_pf_step before cssm_pf_init");
   if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
@@ -621,16 +622,18 @@ static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_
   const int weighted = pf->h_recs[0].has_obs;
   const PreState before = pre_state(pf);
   pf->gen++;
+  if (rows == CSSM_ROWS_FORECASTS) { rc = cssm_fc_row(pf, 0); if (rc) return rc; }
   rc = launch_step(pf, pf->d_recs, weighted, pf->step);
   if (rc) return rc;
-  if (rows) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
+  if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
+  if (rows == CSSM_ROWS_FORECASTS) { rc = cssm_fc_results(pf, 1); if (rc) return rc; }
   Scalars& h = *pf->h_sc;
   rc = read_scalars(pf, 0, false, false, /*poll=*/!rows);   // (the completion word, not the stream: 40.4 -> 38.0 us per streaming step at N = 2^20)
   if (rc) return rc;
   if (on_hold(h)) {   // the max ruled the reference level out: this observation again, relative to the max
     rc = resolve_hold(pf, before, pf->d_recs, pf->step, nullptr, nullptr, 0);
     if (rc) return rc;
-    if (rows) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
+    if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
     rc = read_scalars(pf);
     if (rc) return rc;
   }
@@ -640,10 +643,10 @@ static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_
   return single_handle_err(pf, h);
 }
 extern "C" int cssm_pf_step(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out) {
-  return step_impl(pf, t, obs, has_obs, ll_out, ess_out, false);
+  return step_impl(pf, t, obs, has_obs, ll_out, ess_out, CSSM_ROWS_NONE);
 }
-int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out) {
-  return step_impl(pf, t, obs, has_obs, ll_out, ess_out, true);
+int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out, int rows) {
+  return step_impl(pf, t, obs, has_obs, ll_out, ess_out, rows);
 }
 // ---- an arbitrary Resample[A] on the host (model/package.scala:23): the step split at the resampler ----------------------
 // cssm_pf_propagate = lines :117-124 of stepFilter (propagate, weigh); the caller fetches the proposed cloud and the
@@ -706,9 +709,10 @@ extern "C" int cssm_pf_adopt(cssm_pf* pf, const double* state_dN, double ll, int
 
 // cont: the observations CONTINUE the filter from its current state (cssm_pf_ll_filter_more): no initial cloud is drawn, the
 // first time increment is taken from the handle's clock, observation s of this call is observation pf->step + s of the filter.
-// rows: a row of filtered intervals behind the initial cloud (not cont) and behind every record (cssm_intervals.hip).
+// rows: CSSM_ROWS_INTERVALS -- a row of filtered intervals behind the initial cloud (not cont) and behind every record;
+// CSSM_ROWS_FORECASTS -- a one-step-ahead forecast of every record's time, enqueued before the record (cssm_intervals.hip).
 static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out,
-                      double* ll_t, int32_t* ess_t, double* path, bool cont = false, bool rows = false) {
+                      double* ll_t, int32_t* ess_t, double* path, bool cont = false, int rows = CSSM_ROWS_NONE) {
   if (!pf || !t || !y) return fail(CSSM_EINVAL_ARG, "null argument");
   if (T < 1) return fail(CSSM_EINVAL_ARG, "empty data (the reference's minBy throws on an empty Vector)");
   // CSSM_CALL_TIMING=1: host-side phases of the call on stderr (tools/archive/leg_overhead.py)
@@ -748,7 +752,7 @@ static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8
   if (!cont) {
     rc = cssm_launch_init(pf, t0);
     if (rc) return rc;
-    if (rows) { rc = cssm_iv_row(pf, 0); if (rc) return rc; }   // (cssm_pf_filter_intervals: row 0 = the initial cloud)
+    if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_row(pf, 0); if (rc) return rc; }   // (cssm_pf_filter_intervals: row 0 = the initial cloud)
   }
   const size_t row0 = cont ? 0 : 1;   // (rows) the row behind record s is row0 + s
   const PreState start = pre_state(pf);   // host-side state at the first observation of this call (launch_init: cur = 0, wparity = 0)
@@ -781,10 +785,13 @@ static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8
       const int weighted = pf->h_recs[s].has_obs;
       double* pick_out = (folded && s >= 1) ? pf->d_path + s * (size_t)d : nullptr;
       const uint32_t pick_slot = s >= 1 ? pf->h_recs[s - 1].pick : 0u;
+      // (the forecast of record s reads the cloud its propagate is about to read, and none it writes; behind a held record it returns at
+      //  once and is enqueued again with the rest -- the held record's own row was formed before the hold and stands)
+      if (rows == CSSM_ROWS_FORECASTS) { rc = cssm_fc_row(pf, s); if (rc) return rc; }
       rc = launch_step(pf, pf->d_recs + s, weighted, base + (uint32_t)s, pf->d_ll_t, pf->d_ess_t, (uint32_t)s, pick_out, pick_slot);
       if (rc) return rc;
       if (rest_pending) { rc = build_rest(); if (rc) return rc; }
-      if (rows) { rc = cssm_iv_row(pf, row0 + s); if (rc) return rc; }   // (a series on hold: these launches return at once like the filter's)
+      if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_row(pf, row0 + s); if (rc) return rc; }   // (a series on hold: these launches return at once like the filter's)
       folded = path && s + 1 < T && cssm_uses_sums_kernel(*pf, *pf);   // (the last entry has no following propagate)
       if (path && !folded)
         hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, pf->stream, pf->src, pf->src_stride,
@@ -796,7 +803,8 @@ static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8
     if (pf->opt_events) HIP_TRY(hipEventRecord(pf->ev1, pf->stream));
     HIP_TRY(hipGetLastError());
     if (path) HIP_TRY(hipMemcpyAsync(path, pf->d_path, (T + 1) * (size_t)d * 8, hipMemcpyDeviceToHost, pf->stream));
-    if (rows) { rc = cssm_iv_results(pf, row0 + T); if (rc) return rc; }
+    if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_results(pf, row0 + T); if (rc) return rc; }
+    if (rows == CSSM_ROWS_FORECASTS) { rc = cssm_fc_results(pf, T); if (rc) return rc; }
     rc = read_scalars(pf, (uint32_t)T, ll_t != nullptr, ess_t != nullptr, /*poll=*/path == nullptr && !rows);   // (k_finish: a pending ESS formed, results into host-mapped memory)
     if (rc) return rc;
     const Scalars& hh = *pf->h_sc;
@@ -805,7 +813,7 @@ static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8
     if (hh.fail_step < base || sf >= T) return fail(CSSM_ESTATE, "held series reports observation %u; this call holds %u .. %zu", hh.fail_step, base, base + T - 1);
     rc = resolve_hold(pf, pre_state_of_record(pf, start, sf), pf->d_recs + sf, base + (uint32_t)sf, pf->d_ll_t, pf->d_ess_t, (uint32_t)sf);
     if (rc) return rc;
-    if (rows) { rc = cssm_iv_row(pf, row0 + sf); if (rc) return rc; }   // (the held record's row is formed behind its redo)
+    if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_row(pf, row0 + sf); if (rc) return rc; }   // (the held record's row is formed behind its redo)
     folded = path && sf + 1 < T && cssm_uses_sums_kernel(*pf, *pf);
     if (path && !folded)
       hipLaunchKernelGGL(k_pick, dim3(1), dim3(64), 0, pf->stream, pf->src, pf->src_stride, (const uint32_t*)pf->anc,
@@ -841,8 +849,9 @@ extern "C" int cssm_pf_ll_filter_more(cssm_pf* pf, const double* t, const double
   return run_filter(pf, t, y, has_obs, T, ll_out, ll_t, ess_t, nullptr, /*cont=*/true);
 }
 
-int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont) {
-  return run_filter(pf, t, y, has, T, ll_out, ll_t, ess_t, nullptr, cont, /*rows=*/true);
+int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont,
+                         int rows) {
+  return run_filter(pf, t, y, has, T, ll_out, ll_t, ess_t, nullptr, cont, rows);
 }
 
 extern "C" int cssm_pf_filter(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T,

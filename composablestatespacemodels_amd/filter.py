@@ -292,6 +292,65 @@ class NativePf:
         out["key"] = key
         return out
 
+    def default_forecast_keys(self, first_index: int, count: int) -> np.ndarray:
+        """The keys ``forecast_key`` returns for the clouds of observation indices first_index .. first_index + count - 1."""
+        return np.array([int(self.lib.cssm_pf_run_key(self.seed, (1 << 63) | (int(first_index) + s))) for s in range(count)], dtype=np.uint64)
+
+    def _filter_forecasts(self, fn, t, y, has, keys, interval, first_index):
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        T = len(t)
+        has = _u8(has)
+        if keys is None:
+            used, ky = self.default_forecast_keys(first_index, T), None
+        else:
+            ky = used = np.ascontiguousarray([int(x) & (2**64 - 1) for x in np.asarray(keys, dtype=object).ravel()], dtype=np.uint64)
+            if len(ky) != T:
+                raise ValueError(f"one key per record ({T}), not {len(ky)}")
+        out, ptrs = _forecast_arrays(self.d, T)
+        ll = C.c_double()
+        ll_t = np.zeros(T)
+        ess_t = np.zeros(T, dtype=np.int32)
+        rc = fn(self._h, _p(t), _p(y), _p(has), T, _p(ky), float(interval), C.byref(ll), _p(ll_t), _p(ess_t), *ptrs)
+        self.generation += 1
+        _abi.check(rc)
+        out.update(ll=ll.value, ll_t=ll_t, ess_t=ess_t, keys=used)
+        return out
+
+    def filter_forecasts(self, t, y, has=None, keys=None, interval: float = 0.975):
+        """cssm_pf_filter_forecasts: ``run`` and, from the same call, before every record is stepped, ``forecast`` of the record's time
+        from the cloud before it (``ParticleFilter.getMeanForecast`` mapped over the filter stream).  ``forecast``'s dict with [T] rows
+        (state_* [T, d]) plus ``ll``, ``ll_t``, ``ess_t``, the PIT counts ``obs_below`` / ``obs_equal`` (draws strictly below / equal to
+        the datum; -1 without one) and ``keys`` (the Philox key of every row; ``keys=None``: the rule of ``forecast_key`` per record).
+        A record whose time ``forecast`` would refuse reads NaN and -1."""
+        return self._filter_forecasts(self.lib.cssm_pf_filter_forecasts, t, y, has, keys, interval, 0)
+
+    def filter_forecasts_more(self, t, y, has=None, keys=None, interval: float = 0.975):
+        """cssm_pf_filter_forecasts_more: ``run_more`` with the forecast before every record: the same dict."""
+        return self._filter_forecasts(self.lib.cssm_pf_filter_forecasts_more, t, y, has, keys, interval, self.observation_index())
+
+    def step_forecast(self, t: float, y: Optional[float], has_obs: Optional[bool] = None, key: Optional[int] = None, interval: float = 0.975):
+        """cssm_pf_step_forecast: ``forecast([t], key)`` of the current cloud, then ``step``, in one call: ``(ll, ess, fc)``; ``fc`` is
+        ``forecast``'s dict with one row ([1, d] / [1]), the PIT counts and ``key`` (None: ``forecast_key()``)."""
+        if has_obs is None:
+            has_obs = y is not None
+        used = self.forecast_key() if key is None else int(key) & (2**64 - 1)
+        out, ptrs = _forecast_arrays(self.d, 1)
+        ll, ess = C.c_double(), C.c_int32()
+        rc = self.lib.cssm_pf_step_forecast(self._h, float(t), 0.0 if y is None else float(y), 1 if has_obs else 0, used if key is not None else 0,
+                                            0 if key is None else 1, float(interval), C.byref(ll), C.byref(ess), *ptrs)
+        self.generation += 1
+        _abi.check(rc)
+        out["key"] = used
+        return ll.value, ess.value, out
+
+    def forecasts_last_ms(self) -> Tuple[float, float]:
+        """Device milliseconds of the last ``filter_forecasts`` / ``filter_forecasts_more`` / ``step_forecast``: (the whole call, its forecast
+        rows' launches alone) (cssm_pf_forecasts_last_ms)."""
+        ms = np.zeros(2)
+        _abi.check(self.lib.cssm_pf_forecasts_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1])
+
     def forecast_posterior(self, theta, x, t0: float, times, key: Optional[int] = None, interval: float = 0.975, pick=None,
                            want_samples: bool = False):
         """cssm_pf_forecast_posterior: forecasts from a joint posterior sample of M pairs -- theta[M, n_theta] in flatten order and
@@ -1519,6 +1578,40 @@ class _FilterBase:
         r = self._pf.step_intervals(y.t, y.observation, interval=interval)
         return self._state(y.t, y.observation, r[0], r[1]), _pfout_of(y.t, y.observation, r[2:])
 
+    # ParticleFilter.scala:389-409 mapped over the filter stream: the forecast of every record's time from the state before it
+    def _batch_forecasts(self, pf: NativePf, t, y, h, interval: float):
+        """The dict of the batch path (cssm_pf_filter_forecasts): T rows, the first from the initial cloud at the data's smallest time."""
+        return pf.filter_forecasts(t, y, h, None, interval)
+
+    def filterForecasts(self, data: Sequence[TimedObservation], particles: int, interval: float = 0.975) -> Tuple[float, List[ForecastOut]]:
+        """The prequential check in one native call: the log-likelihood and T ``ForecastOut``, entry s what
+        ``ParticleFilter.getMeanForecast(state before record s, mod, data[s].t, interval)`` returns on a ``filterStream`` run, formed before
+        record s is weighed, so ``formats.forecast_out_csv`` writes the same lines.  With a host ``Resample[A]`` (any function but the
+        three native resamplers) there is no batch path: the loop of ``getMeanForecast`` then ``stepFilter`` runs record by record.
+        ``FilterLgcp`` raises the library's refusal (``CssmError``): the reference's ``LogGaussianCox.observation`` is unimplemented."""
+        data = list(data)
+        if self._host_resample is not None:
+            st = self.initialiseState(particles, min(d.t for d in data))
+            outs = []
+            for d in data:
+                outs.append(ParticleFilter.getMeanForecast(st, self.mod, d.t, interval))
+                st = self.stepFilter(st, d)
+            return st.ll, outs
+        t, y, h = split_data(data)
+        r = self._batch_forecasts(self._ensure(particles), t, y, h, interval)
+        return r["ll"], _forecast_outs([d.t for d in data], r)
+
+    def stepForecast(self, s: PfState, y: TimedObservation, interval: float = 0.975) -> Tuple[PfState, ForecastOut]:
+        """``getMeanForecast(s, mod, y.t, interval)`` and ``stepFilter(s, y)`` in one native call (cssm_pf_step_forecast; with a host
+        ``Resample[A]``: the two calls)."""
+        if s._owner is not self._pf or s._generation != self._pf.generation:
+            raise RuntimeError("stepForecast must be applied to the filter's current PfState")
+        if self._host_resample is not None:
+            out = ParticleFilter.getMeanForecast(s, self.mod, y.t, interval)
+            return self.stepFilter(s, y), out
+        ll, ess, fc = self._pf.step_forecast(y.t, y.observation, interval=interval)
+        return self._state(y.t, y.observation, ll, ess), _forecast_outs([y.t], fc)[0]
+
     # ParticleFilter.scala:163-166: Flow[Data].scan(init)(stepFilter) -- emits init, then one state per datum
     def filterStream(self, t0: float, particles: int) -> Callable[[Iterable[TimedObservation]], Iterator[PfState]]:
         def flow(source: Iterable[TimedObservation]) -> Iterator[PfState]:
@@ -1562,6 +1655,12 @@ class FilterInit(_FilterBase):
         first = pf.summary(interval)
         r = pf.filter_intervals_more(t, y, h, interval)
         return r[0], tuple(np.concatenate([np.asarray(a)[None], b]) for a, b in zip(first, r[3:]))
+
+    def _batch_forecasts(self, pf: NativePf, t, y, h, interval: float):
+        """The given state at the data's smallest time, then the records with their forecasts in one native call
+        (cssm_pf_filter_forecasts_more)."""
+        self.initialiseState(pf.n, float(np.min(t)))
+        return pf.filter_forecasts_more(t, y, h, None, interval)
 
 
 class FilterLgcp(_FilterBase):

@@ -444,6 +444,59 @@ int cssm_pf_step_intervals(cssm_pf* pf, double t, double obs, int has_obs, doubl
  * launch and read by its last).  CSSM_ESTATE before the first such call has completed. */
 int cssm_pf_intervals_last_ms(cssm_pf* pf, double* ms2);
 
+/* One-step-ahead forecasts of ONE large cloud inside the batch filter: ParticleFilter.getMeanForecast mapped over a filter stream
+ * (model/ParticleFilter.scala:368-409) -- from every PfState the forecast of the time of the NEXT observation, before that observation
+ * is weighed: the prequential check.  The single handle's counterpart of cssm_fleet_filter_forecasts.
+ *   The filter part.  t / y / has_obs / T / ll_out / ll_t / ess_t are cssm_pf_ll_filter's arguments bit for bit, and the handle afterwards
+ *   (cloud, ancestors, clock, observation index, sums state) is the one it leaves.
+ *   The forecast of record s.  T rows laid out like t: state_* [T][d], eta_* / obs_* / obs_below / obs_equal [T]; any of them may be NULL.
+ *   Row s is bit for bit -- means and order statistics -- what cssm_pf_forecast(pf, &t[s], 1, keys[s], interval, ...) returns when issued
+ *   just before record s is stepped: the source is the cloud before record s through its ancestors (record 0: the initial cloud at
+ *   min t); one transition over t[s] - clock on the paired CSSM_STREAM_STEP streams under keys[s], horizon index 0 (dt = 0 allowed);
+ *   gamma and eta at t[s]; one observation draw on CSSM_STREAM_OBS; ranks and clamping as documented at cssm_pf_forecast.  The record's
+ *   own y plays no part in its row; a record without a datum gets a row like any other.  keys == NULL: keys[s] = cssm_pf_run_key(seed,
+ *   2^63 | observation index of the cloud before the record), the rule of thumb of cssm_pf_forecast.
+ *   EXTENSION (the reference has none): obs_below[s] / obs_equal[s] = how many of the N drawn observations are strictly below / equal to
+ *   y[s] -- the counts of the probability integral transform; both read -1 for a record without a datum and for a NaN row.
+ *   A record whose time cssm_pf_forecast would refuse from that cloud (not finite, or before the cloud's time) has a NaN row and counts
+ *   of -1; the filter treats the record as cssm_pf_ll_filter does.
+ * Refused before any work: a null handle, t or y and T = 0 (CSSM_EINVAL_ARG), an interval outside (0, 1] (CSSM_EINVAL_ARG), a sharded
+ * handle (CSSM_ESTATE), and with cssm_pf_forecast's code and message an LGCP handle and a model without the scale its observation draw
+ * needs.  On an error return of the filter part the rows are unspecified.  Samples are not offered: cssm_pf_forecast serves a caller who
+ * wants them for one state.  Served: the three native resamplers.
+ * A row is 8 launches on the handle's stream between the observations' own, no allocation, event or host round trip between records,
+ * one synchronisation per call: the forecast kernel in cssm_pf_forecast's geometry (so the means keep its bits), the exact two-rank
+ * selection of cssm_pf_filter_intervals over d + 2 rows, a finish; the scratch lives on the handle and is freed by cssm_pf_destroy. */
+int cssm_pf_filter_forecasts(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T,
+                             const uint64_t* keys, double interval, double* ll_out, double* ll_t, int32_t* ess_t,
+                             double* state_mean, double* state_lower, double* state_upper,
+                             double* eta_mean, double* eta_lower, double* eta_upper,
+                             double* obs_mean, double* obs_lower, double* obs_upper,
+                             int32_t* obs_below, int32_t* obs_equal);
+/* The same for T MORE observations of a running filter, as cssm_pf_ll_filter_more continues one (record 0 starts from the handle's cloud
+ * at its clock).  CSSM_ESTATE on a handle that was never initialised.  cssm_pf_filter_forecasts(t[0..a)) followed by
+ * cssm_pf_filter_forecasts_more(t[a..T)) gives the rows of cssm_pf_filter_forecasts(t[0..T)). */
+int cssm_pf_filter_forecasts_more(cssm_pf* pf, const double* t, const double* y, const uint8_t* has_obs, size_t T,
+                                  const uint64_t* keys, double interval, double* ll_out, double* ll_t, int32_t* ess_t,
+                                  double* state_mean, double* state_lower, double* state_upper,
+                                  double* eta_mean, double* eta_lower, double* eta_upper,
+                                  double* obs_mean, double* obs_lower, double* obs_upper,
+                                  int32_t* obs_below, int32_t* obs_equal);
+/* The streaming shape: cssm_pf_step -- t / obs / has_obs / ll_out / ess_out are its arguments and bits -- and, before the record is
+ * stepped, cssm_pf_forecast of the single horizon t under `key` (use_key = 0: the rule above with the handle's current observation
+ * index), in one call and one synchronisation.  state_* [d], the others one value each; any may be NULL.  CSSM_ESTATE before
+ * cssm_pf_init; the other refusals as above. */
+int cssm_pf_step_forecast(cssm_pf* pf, double t, double obs, int has_obs, uint64_t key, int use_key, double interval,
+                          double* ll_out, int32_t* ess_out,
+                          double* state_mean, double* state_lower, double* state_upper,
+                          double* eta_mean, double* eta_lower, double* eta_upper,
+                          double* obs_mean, double* obs_lower, double* obs_upper,
+                          int32_t* obs_below, int32_t* obs_equal);
+/* Device time of the last of these three calls on the handle, in milliseconds: ms2[0] the whole call (HIP events around everything it
+ * enqueued), ms2[1] the forecast rows' launches alone (the GPU's constant 100 MHz clock, as cssm_pf_intervals_last_ms).  CSSM_ESTATE
+ * before the first such call has completed. */
+int cssm_pf_forecasts_last_ms(cssm_pf* pf, double* ms2);
+
 /* Forecasts from the current cloud: SimulateData.forecast + summariseForecast (model/Data.scala:196-231) -- the scan of
  * ParticleFilter.getMeanForecast (model/ParticleFilter.scala:389-409) over the future times t[0..H) -- in one call.  The source is
  * exactly the cloud cssm_pf_summary summarises (also between cssm_pf_propagate and cssm_pf_adopt); horizon h starts from the states

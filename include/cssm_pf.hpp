@@ -291,9 +291,37 @@ class Filter {
                                      nullptr, nullptr));
     return forecast_outs(times, sm, sl, su, em, el, eu, om, ol, ou);
   }
+  // the prequential check in one native call (cssm_pf_filter_forecasts): the log-likelihood and, per record, getMeanForecast of the
+  // record's time from the state before it, formed before the record is weighed; default keys (cssm_pf_run_key(seed, 2^63 | index))
+  std::pair<double, std::vector<ForecastOut>> filterForecasts(const std::vector<Data>& data, double interval = 0.975) {
+    return filter_forecasts(cssm_pf_filter_forecasts, data, interval);
+  }
+  // ... for MORE records of the running filter (cssm_pf_filter_forecasts_more)
+  std::pair<double, std::vector<ForecastOut>> filterForecastsMore(const std::vector<Data>& data, double interval = 0.975) {
+    return filter_forecasts(cssm_pf_filter_forecasts_more, data, interval);
+  }
+  // getMeanForecast(s, mod, y.t, interval), then stepFilter(s, y) (cssm_pf_step_forecast)
+  std::pair<PfState, ForecastOut> stepForecast(const PfState&, const Data& y, double interval = 0.975) {
+    double ll; int32_t ess;
+    const Vec times(1, y.t);
+    Vec sm(d_), sl(d_), su(d_), em(1), el(1), eu(1), om(1), ol(1), ou(1);
+    check(cssm_pf_step_forecast(h_, y.t, y.observation.value_or(0.0), y.observation ? 1 : 0, 0, 0, interval, &ll, &ess, sm.data(), sl.data(),
+                                su.data(), em.data(), el.data(), eu.data(), om.data(), ol.data(), ou.data(), nullptr, nullptr));
+    return {PfState{y.t, y.observation, ll, ess}, forecast_outs(times, sm, sl, su, em, el, eu, om, ol, ou)[0]};
+  }
   cssm_pf* handle() { return h_; }
 
  private:
+  template <class Call>
+  std::pair<double, std::vector<ForecastOut>> filter_forecasts(Call call, const std::vector<Data>& data, double interval) {
+    Vec t, y; std::vector<uint8_t> has; split(data, t, y, has);
+    const size_t R = t.size();
+    Vec sm(R * d_), sl(R * d_), su(R * d_), em(R), el(R), eu(R), om(R), ol(R), ou(R);
+    double ll;
+    check(call(h_, t.data(), y.data(), has.data(), R, nullptr, interval, &ll, nullptr, nullptr, sm.data(), sl.data(), su.data(), em.data(),
+               el.data(), eu.data(), om.data(), ol.data(), ou.data(), nullptr, nullptr));
+    return {ll, forecast_outs(t, sm, sl, su, em, el, eu, om, ol, ou)};
+  }
   PfOut pf_out(double t, std::optional<double> obs, const double* m, const double* lo, const double* hi, double em, double el, double eu) const {
     PfOut o{t, obs, em, {el, eu}, Vec(m, m + d_), {}};
     for (int k = 0; k < d_; ++k) o.stateIntervals.push_back({lo[k], hi[k]});
