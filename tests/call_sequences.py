@@ -16,6 +16,20 @@ reused handles; this module drives them the same way.
   run_sequence(subject,..) the runner; `subject` is a NativePf (GPU) or a CarriedOracle (one oracle object carried through the whole
                            sequence: the check that the expectation itself has no stale state, which runs without a GPU)
 
+The SECOND vocabulary (V2: STATE_KINDS_V2, sequence_v2, SEQUENCES_V2, committed_sequences_v2) adds the calls that came behind the first:
+the rows calls (cssm_pf_filter_intervals / _more / cssm_pf_step_intervals, cssm_pf_filter_forecasts / _more / cssm_pf_step_forecast),
+cssm_pf_smooth and cssm_pmmh_run on THIS handle.  The first vocabulary -- sequence(), SEQUENCES, pair_allowed, pair_snippet,
+committed_sequences() -- produces op for op what it produced before (tests/test_call_sequences_host.py holds a digest of it); the V2
+generator draws from a random.Random of its own.  Expectations, all from the fresh-replay oracle: interval rows = the oracle's init;
+summary; (step; summary)* with the means formed exactly (summary_row); forecast row s = test_gpu_forecast.expected from the oracle's cloud
+BEFORE record s under the key the reference derives; smooth = smooth_expected; pmmh = OraclePf.pmmh.
+pmmh is used on EVERY spec of SPECS: cssm_pmmh_run is set_params + reseed + cssm_pf_filter per iteration on the handle as it stands (its
+resampler option, its LGCP precision, a run-time-compiled structure included), and oracle_pmmh_run is the same loop over oracle_pf_filter
+under the resampler flag the oracle was created with -- neither refuses a structure the filter serves.  The header promises nothing about
+the parameters and the key cssm_pmmh_run leaves: behind it only set_params, reseed, set_option and refused calls are legal until a
+set_params and a reseed have both followed, and then a call that draws a new cloud (HostState.cloud_unknown, the shape of
+resampler_pending).  smooth and pmmh stay at N <= 5000 (M <= 64, T <= 12; iters <= 4, T <= 6): their expectations are the slowest.
+
 Plain module: no fixtures, no test functions.
 """
 from __future__ import annotations
@@ -75,11 +89,59 @@ ILLEGAL_KINDS = ("refused", "fails")
 STEP_VARIANTS = ("step_missing", "step_dt0", "step_outlier")
 
 
+# ---- the second vocabulary (V2): the calls that form rows inside the filtering call, the smoother, and PMMH on a handle that lives on.
+# The first vocabulary above stays as it is; sequence() never emits one of these.
+#   run_intervals(T, dseed, interval, outlier_at)           cssm_pf_filter_intervals         draws a new cloud (every spec)
+#   run_intervals_more(T, dseed, interval, outlier_at)      cssm_pf_filter_intervals_more    continues
+#   step_intervals(t, y, has, interval)                     cssm_pf_step_intervals           one step
+#   run_forecasts(T, dseed, keyed, interval, outlier_at)    cssm_pf_filter_forecasts         draws a new cloud (not LGCP)
+#   run_forecasts_more(T, dseed, keyed, interval, outlier_at)  cssm_pf_filter_forecasts_more continues (not LGCP)
+#   step_forecast(t, y, has, key or None, interval)         cssm_pf_step_forecast            one step (not LGCP)
+#   smooth(T, dseed, M, interval)                           cssm_pf_smooth                   like interpolate: re-initialise afterwards (not LGCP)
+#   pmmh(T, dseed, iters, delta, seed)                      cssm_pmmh_run on THIS handle     leaves parameters, key and cloud unknown
+INTERVAL_KINDS = ("run_intervals", "run_intervals_more", "step_intervals")
+FORECAST_KINDS = ("run_forecasts", "run_forecasts_more", "step_forecast")
+ROW_KINDS = INTERVAL_KINDS + FORECAST_KINDS
+NEW_KINDS = ROW_KINDS + ("smooth", "pmmh")
+STATE_KINDS_V2 = STATE_KINDS + NEW_KINDS
+NEW_RESTARTS = ("run_intervals", "run_forecasts", "smooth", "pmmh")
+ALL_RESTARTS = RESTARTS + NEW_RESTARTS
+BATCH_ROWS = ("run_intervals", "run_intervals_more", "run_forecasts", "run_forecasts_more")
+CONTINUING = ("run_intervals_more", "step_intervals", "run_forecasts_more", "step_forecast")   # need a running filter
+STEP_ROWS = ("step_intervals", "step_forecast")
+SMOOTH_MAX_M = 4096              # CSSM_FLEET_MAX_N
+
+
 def state_kind(o: Op) -> Optional[str]:
     """The state-changing kind of an op for the pair table, None for read-only and refused calls."""
     if o.kind == "set_option":
         return f"opt{o[1]}" if o[1] in OPTION_VALUES else None
-    return o.kind if o.kind in STATE_KINDS else None
+    return o.kind if o.kind in STATE_KINDS_V2 else None
+
+
+def interval_of(o: Op) -> Optional[float]:
+    """The interval argument of a V2 op (None: the kind has none)."""
+    k = o.kind
+    if k in ("run_intervals", "run_intervals_more"):
+        return o[3]
+    if k in ("step_intervals", "run_forecasts", "run_forecasts_more", "smooth", "smooth_pairing"):
+        return o[4]
+    if k == "step_forecast":
+        return o[5]
+    return None
+
+
+def outlier_at(o: Op) -> Optional[int]:
+    k = o.kind
+    if k in ("run_intervals", "run_intervals_more"):
+        return o[4]
+    if k in ("run_forecasts", "run_forecasts_more"):
+        return o[5]
+    return None
+
+
+def _bad_interval(v) -> bool:
+    return not (0.0 < v <= 1.0)
 
 
 # --------------------------------------------------------------------------------------------- models and data
@@ -155,6 +217,27 @@ def series(spec: Spec, T: int, dseed: int, t_start: float, continuing: bool):
     return t, y, has
 
 
+def data_of(spec: Spec, o: Op, clock: float):
+    """(t, y, has) of a batch op of either vocabulary: series() of its (T, dseed), continued behind `clock` for the *_more kinds, a new
+    series otherwise; the record at outlier_at takes spec.outlier as its datum (its level is ruled out by the max: held and redone)."""
+    cont = o.kind in ("run_more", "run_intervals_more", "run_forecasts_more")
+    t, y, has = series(spec, o[1], o[2], clock if cont else float(o[2] % 3), cont)
+    at = outlier_at(o)
+    if at is not None:
+        y, has = y.copy(), has.copy()
+        y[at], has[at] = spec.outlier, 1
+    return t, y, has
+
+
+def row_keys(dseed: int, T: int) -> np.ndarray:
+    """The given keys of a forecast call with keyed = 1: a function of (dseed, record) alone."""
+    return np.array([int(oracle.lib().oracle_c_derive_key(0xF0CA57 + int(dseed), s + 1)) for s in range(T)], dtype=np.uint64)
+
+
+def theta_of(model: Model) -> np.ndarray:
+    return np.asarray(Parameters([node for _, node, _ in model.leaves]).flattenParams(), dtype=np.float64)
+
+
 def substeps(spec: Spec, dt: float) -> int:
     """Transitions per particle of one observation (LGCP: FilterLgcp's sub-steps) -- the unit of the oracle-time budget."""
     if not spec.lgcp:
@@ -185,6 +268,8 @@ class HostState:
         self.pending_adopt = False
         self.resampler_pending = False  # option 2 changed: the next state change must draw a new cloud
         self.after_run_more = False
+        # V2: cssm_pmmh_run re-parameterises and reseeds the handle every iteration and promises nothing about what it leaves
+        self.cloud_unknown = self.params_unknown = self.seed_unknown = False
         self.opts = dict(OPTION_DEFAULTS)
         self.model_k = 0
         self.last_state_kind: Optional[str] = None
@@ -197,8 +282,14 @@ class HostState:
     def legal(self, o: Op) -> Optional[str]:
         """None if `o` is legal now, else the reason."""
         k = o.kind
-        if self.resampler_pending and k not in RESTARTS + ("set_option", "set_params", "reseed", "refused"):
+        if self.resampler_pending and k not in ALL_RESTARTS + ("set_option", "set_params", "reseed", "refused"):
             return "after a change of the resampler only a call that draws a new cloud may follow"
+        if self.cloud_unknown:
+            if k in ALL_RESTARTS:
+                if self.params_unknown or self.seed_unknown:
+                    return "after pmmh the parameters and the key are unknown until a set_params and a reseed have both followed"
+            elif k not in ("set_option", "set_params", "reseed", "refused"):
+                return "after pmmh only set_params, reseed, set_option and refused calls may come before a new cloud"
         if k == "refused":
             code, inner = o[1], o[2]
             ik = inner.kind
@@ -210,10 +301,12 @@ class HostState:
                 return None
             if code == "EINVAL_DESC" and ik == "set_params_other":
                 return None
+            if ik in NEW_KINDS or ik == "smooth_pairing":
+                return self._refusal_v2(code, inner)
             return "no documented refusal of this call"
         if k == "fails":
             inner = o[2]
-            if o[1] != "ENONFINITE" or inner.kind != "step" or self.spec.lgcp:
+            if o[1] != "ENONFINITE" or inner.kind not in ("step",) + STEP_ROWS or self.spec.lgcp:
                 return "only a weighted step back in time is a documented mid-series failure (not LGCP: its sub-step count is dt / delta)"
             if not self.usable() or not (inner[1] < self.t) or not inner[3]:
                 return "a failing step needs a running filter, a time before the clock and an observation"
@@ -254,7 +347,61 @@ class HostState:
             return None if not self.spec.lgcp else "the reference leaves LGCP's observation unimplemented"
         if k in ("summary", "particles", "proposed", "ancestors", "observation_index", "forecast_key"):
             return None if self.usable() else "needs a running filter"
+        if k in NEW_KINDS:
+            return self._legal_v2(o)
         return f"unknown op kind {k!r}"
+
+    def _legal_v2(self, o: Op) -> Optional[str]:
+        k, lg = o.kind, self.spec.lgcp
+        if lg and (k in FORECAST_KINDS or k == "smooth"):
+            return "the forecast kinds and the smoother do not serve an LGCP handle"
+        iv = interval_of(o)
+        if iv is not None and _bad_interval(iv):
+            return "an interval outside (0, 1] is refused"
+        if k in STEP_ROWS:
+            if not self.usable():
+                return "needs a running filter"
+            return None if o[1] >= self.t else "time before the clock"
+        if o[1] < 1:
+            return "empty data is refused"
+        at = outlier_at(o)
+        if at is not None and (lg or not 0 <= at < o[1]):
+            return "the outlier sits on a record of the call (LGCP has no datum to replace)"
+        if k in CONTINUING and not self.usable():
+            return "needs a running filter"
+        if k == "smooth" and not 1 <= o[3] <= SMOOTH_MAX_M:
+            return "n_traj outside [1, CSSM_FLEET_MAX_N]"
+        if k == "pmmh" and o[3] < 1:
+            return "no iteration"
+        return None
+
+    def _refusal_v2(self, code: str, inner: Op) -> Optional[str]:
+        """The documented refusals of the V2 calls: CSSM_ESTATE for a continuing call on a handle never initialised; CSSM_EINVAL_ARG for
+        T = 0, an interval outside (0, 1], n_traj = 0, CSSM_INTERP_REFERENCE_PAIRING, and what an LGCP handle is not served."""
+        ik, lg = inner.kind, self.spec.lgcp
+        if self.resampler_pending:
+            return "between a change of the resampler and the new cloud the reference has no cloud to compare behind a refusal"
+        if code == "ESTATE":
+            if ik in CONTINUING:
+                return None if not self.initialised else "refused(ESTATE) needs an uninitialised handle"
+            return "no documented refusal of this call"
+        if code != "EINVAL_ARG":
+            return "no documented refusal of this call"
+        if ik in CONTINUING and not self.usable():
+            return "a continuing call is refused with CSSM_ESTATE first where no filter runs"
+        if ik in STEP_ROWS and not inner[1] >= self.t:
+            return "a step back in time is a failure, not a refusal"
+        if ik in ("smooth", "smooth_pairing"):
+            if lg or ik == "smooth_pairing" or inner[3] == 0 or _bad_interval(inner[4]):
+                return None
+            return "the call would be accepted"
+        if ik in FORECAST_KINDS and lg:
+            return None
+        if ik in BATCH_ROWS and inner[1] == 0:
+            return None
+        if ik in ROW_KINDS and _bad_interval(interval_of(inner)):
+            return None
+        return "the call would be accepted"
 
     # -- the state afterwards
     def apply(self, o: Op) -> None:
@@ -286,15 +433,32 @@ class HostState:
             self.weighted = self.weighted or bool(has.any())
             self.pending_adopt = False
             self.after_run_more = True
-        elif k in ("step", "propagate"):
+        elif k in NEW_RESTARTS:
+            t, _, has = data_of(self.spec, o, 0.0)
+            self._fresh(float(np.min(t)))
+            self.t, self.obs = float(t[-1]), len(t)
+            self.weighted = bool(has.any())
+            if k == "smooth":
+                self.initialised = False   # "The handle must be re-initialised before further streaming calls."
+            if k == "pmmh":
+                self.cloud_unknown = self.params_unknown = self.seed_unknown = True
+        elif k in ("run_intervals_more", "run_forecasts_more"):
+            t, _, has = data_of(self.spec, o, self.t)
+            self.t, self.obs = float(t[-1]), self.obs + len(t)
+            self.weighted = self.weighted or bool(has.any())
+            self.pending_adopt = False
+        elif k in ("step", "propagate") + STEP_ROWS:
             has = bool(o[3]) or self.spec.lgcp
             self.t, self.obs = float(o[1]), self.obs + 1
             self.weighted = self.weighted or has
             self.pending_adopt = (k == "propagate") and has
         elif k == "adopt":
             self.pending_adopt = False
+        elif k == "reseed":
+            self.seed_unknown = False
         elif k == "set_params":
             self.model_k = o[1]
+            self.params_unknown = False
         elif k == "set_option":
             if o[1] == OPT_RESAMPLER:
                 self.resampler_pending = True    # (also where the value stays: one rule for the generator and the pair table)
@@ -306,6 +470,7 @@ class HostState:
     def _fresh(self, t0):
         self.initialised, self.failed, self.t, self.obs = True, False, float(t0), 0
         self.weighted = self.pending_adopt = self.resampler_pending = False
+        self.cloud_unknown = False
 
 
 def check_legal(spec: Spec, seq: Sequence[Op]) -> HostState:
@@ -327,6 +492,12 @@ def is_weighted_op(spec: Spec, st: HostState, o: Op) -> bool:
         return True                      # (the first observation of a new series always carries a datum)
     if k == "run_more":
         return bool(series(spec, o[1], o[2], st.t, True)[2].any())
+    if k in STEP_ROWS:
+        return bool(o[3]) or spec.lgcp
+    if k in NEW_RESTARTS:
+        return True
+    if k in ("run_intervals_more", "run_forecasts_more"):
+        return bool(data_of(spec, o, st.t)[2].any())
     return False
 
 
@@ -541,6 +712,8 @@ SEQUENCES: List[Tuple[int, str, int, int]] = [
 SLOW_SEQUENCES: List[Tuple[int, str, int, int]] = [(71, "c1", (1 << 20) + 77, 15), (72, "c2", 1 << 20, 15)]
 COMPLETION = ("c2", 1000)        # model and size of the sequences that hold the pairs the seeded draws left out
 COMPLETION_CHUNK = 12            # pair snippets per completion sequence
+SMOOTH_TWIN_PER_STEP = 4         # backward weights of the smoother twin (one Gaussian density each) that cost what one particle-step costs
+FORECAST_ROW_COST = 2            # particle-steps per particle of one forecast row's expectation (init_from of a new oracle, one transition)
 BUDGET = 6e7                     # particle-steps of fresh replay of the non-slow sequences together (about a minute of oracle time)
 
 
@@ -577,6 +750,337 @@ def committed_sequences():
     return _committed
 
 
+# --------------------------------------------------------------------------------------------- the V2 generator
+V2_INTERVALS = (0.975, 0.9, 1.0)
+
+
+def sequence_v2(seed: int, spec_name: str, n: int, length: int, max_T: int = 0) -> List[Op]:
+    """`length` ops of BOTH vocabularies on one handle, the V2 kinds about half of them: a function of its arguments alone (a
+    random.Random of its own: sequence() is not touched).  max_T > 0 bounds every series length."""
+    spec = SPECS[spec_name]
+    rng = random.Random(f"call-sequences-v2/{seed}/{spec_name}/{n}/{length}/{max_T}")
+    st = HostState(spec)
+    small = n <= 5000                    # smooth and pmmh stay at n <= 5000 (their expectation is the slowest)
+    big = n > 20000
+    seq: List[Op] = []
+    rows_calls = smooths = 0
+    last_smooth_T = 0
+    after_long = [False]                 # a call of more than 1024 records is followed by a new cloud (its replay at every checkpoint is dear)
+
+    def emit(o: Op):
+        st.apply(o)
+        seq.append(o)
+
+    def an_interval():
+        return rng.choice(V2_INTERVALS + (0.975, 0.25 / n))        # (the last: floor(interval N) = 0, the rank clamps)
+
+    def a_T(long_ok=True):
+        nonlocal rows_calls
+        rows_calls += 1
+        if max_T:
+            return rng.choice(range(1, max_T + 1))
+        if big:
+            return rng.choice((1, 2, 3, 4))
+        if long_ok and 63 <= n <= 1000 and spec.precision != 2 and rows_calls == 3:
+            after_long[0] = True
+            return 1030 + rng.randrange(20)                         # behind a shorter rows call: the record and row buffers regrow
+        return rng.choice((1, 2, 3, 5, 7, 12))
+
+    def an_outlier(T):
+        return rng.randrange(T) if (not spec.lgcp and rng.random() < 0.3) else None
+
+    def next_t():
+        return st.t + rng.choice(_DTS_LGCP if spec.lgcp else _DTS)
+
+    def step_args():
+        r = rng.random()
+        if spec.lgcp:
+            return next_t(), 1.0, 1
+        if r < 0.15:
+            return next_t(), 0.0, 0
+        if r < 0.25:
+            return st.t, _y(spec, rng), 1
+        if r < 0.37:
+            return next_t(), spec.outlier, 1
+        return next_t(), _y(spec, rng), 1
+
+    def rows_batch(kind):
+        T = a_T()
+        if T > 1024 and n > 513:
+            kind = kind.replace("forecasts", "intervals")           # (a forecast row's expectation is a new oracle per record: kept to the smaller clouds)
+        if kind.startswith("run_intervals"):
+            return op(kind, T, rng.randrange(1000), an_interval(), an_outlier(T))
+        return op(kind, T, rng.randrange(1000), int(rng.random() < 0.5), an_interval(), an_outlier(T))
+
+    def a_smooth():
+        nonlocal smooths, last_smooth_T
+        smooths += 1
+        T = rng.choice((2, 3, 5)) if last_smooth_T >= 9 else rng.choice((3, 9, 12, 12))    # a shorter one behind a longer one
+        if max_T:
+            T = min(T, max_T)
+        last_smooth_T = T
+        return op("smooth", T, rng.randrange(1000), rng.choice((1, 7, 63, 64)), an_interval())
+
+    def a_pmmh():
+        return op("pmmh", min(rng.choice((2, 4, 6)), max_T or 6), rng.randrange(1000), rng.choice((1, 2, 4)), rng.choice((0.01, 0.0025)),
+                  rng.randrange(1 << 30))
+
+    def a_restart():
+        kinds = ["run_intervals"] * 3 + ["init", "run"]
+        if not spec.lgcp:
+            kinds += ["run_forecasts"] * 3
+            if small:
+                kinds += ["smooth"] * 2
+        if small and not st.cloud_unknown:
+            kinds += ["pmmh"] * 2
+        k = rng.choice(kinds)
+        if k == "init":
+            return op("init", float(rng.choice((0.0, 1.0, 2.5))))
+        if k == "run":
+            return op("run", min(a_T(False), 25), rng.randrange(1000), 0)
+        if k == "smooth":
+            return a_smooth()
+        if k == "pmmh":
+            return a_pmmh()
+        return rows_batch(k)
+
+    def a_refusal():
+        running, lg = st.usable(), spec.lgcp
+        pool = [op("refused", "EINVAL_ARG", op("run_intervals", 0, 0, 0.975, None)),
+                op("refused", "EINVAL_ARG", op("run_intervals", 3, 1, rng.choice((0.0, 1.5)), None)),
+                op("refused", "EINVAL_ARG", op("run_forecasts", 0, 0, 0, 0.975, None)),
+                op("refused", "EINVAL_ARG", op("run_forecasts", 3, 1, 0, rng.choice((0.0, 1.5)), None)),
+                op("refused", "EINVAL_ARG", op("smooth", 3, 1, 0, 0.975)),
+                op("refused", "EINVAL_ARG", op("smooth", 3, 1, 8, rng.choice((0.0, 1.5)))),
+                op("refused", "EINVAL_ARG", op("smooth_pairing", 3, 1, 8, 0.975))]
+        if lg:
+            pool += [op("refused", "EINVAL_ARG", op("smooth", 3, 1, 8, 0.975))] * 6 + [op("refused", "EINVAL_ARG", op("run_forecasts", 3, 1, 0, 0.975, None))] * 3
+        if running:
+            pool += [op("refused", "EINVAL_ARG", op("run_intervals_more", 0, 0, 0.975, None)),
+                     op("refused", "EINVAL_ARG", op("run_intervals_more", 2, 1, rng.choice((0.0, 1.5)), None)),
+                     op("refused", "EINVAL_ARG", op("step_intervals", st.t + 1.0, 1.0, 1, rng.choice((0.0, 1.5)))),
+                     op("refused", "EINVAL_ARG", op("run_forecasts_more", 0, 0, 0, 0.975, None)),
+                     op("refused", "EINVAL_ARG", op("run_forecasts_more", 2, 1, 0, rng.choice((0.0, 1.5)), None)),
+                     op("refused", "EINVAL_ARG", op("step_forecast", st.t + 1.0, 1.0, 1, None, rng.choice((0.0, 1.5))))]
+            if lg:
+                pool += [op("refused", "EINVAL_ARG", op("run_forecasts_more", 2, 1, 0, 0.975, None)),
+                         op("refused", "EINVAL_ARG", op("step_forecast", st.t + 1.0, 1.0, 1, None, 0.975))] * 3
+        return rng.choice(pool)
+
+    def a_read():
+        kinds = ["summary", "particles", "ancestors", "observation_index", "forecast_key", "proposed"]
+        if st.weighted:
+            kinds += ["weights", "logw"]
+        k = rng.choice(kinds)
+        return op(k, an_interval()) if k == "summary" else op(k)
+
+    while len(seq) < length:
+        if st.cloud_unknown and (st.params_unknown or st.seed_unknown):
+            r = rng.random()
+            if r < 0.2:
+                emit(a_refusal())
+            elif r < 0.35:
+                emit(op("set_option", *rng.choice(((3, 0), (3, 1), (6, 1), (6, 0), (10, 2), (10, 1), (7, 0), (7, 1)))))
+            elif st.params_unknown and (r < 0.7 or not st.seed_unknown):
+                emit(op("set_params", rng.randrange(4)))
+            else:
+                emit(op("reseed", rng.randrange(1 << 40)))
+            continue
+        if not st.usable() or st.resampler_pending or st.cloud_unknown:
+            r = rng.random()
+            if not st.initialised and not st.resampler_pending and r < 0.45:
+                emit(op("refused", "ESTATE", rng.choice((op("run_intervals_more", 2, 5, 0.975, None), op("step_intervals", 1.0, 1.0, 1, 0.975),
+                                                          op("run_forecasts_more", 2, 5, 0, 0.975, None), op("step_forecast", 1.0, 1.0, 1, None, 0.975)))))
+            elif r < 0.4:
+                emit(rng.choice((op("reseed", rng.randrange(1 << 40)), op("set_params", rng.randrange(4)),
+                                 a_refusal() if not st.resampler_pending else op("set_option", 8, rng.choice((0, 1, 2))))))
+            else:
+                emit(a_restart())
+            continue
+        r = rng.random()
+        if after_long[0]:
+            after_long[0] = False
+            emit(op("particles"))
+            emit(a_restart())
+        elif st.pending_adopt and r < 0.6:
+            emit(op("adopt", rng.choice((0.0, 0.3125, 0.9990234375))))
+        elif r < 0.10:
+            emit(op("step_intervals", *step_args(), an_interval()))
+        elif r < 0.20:
+            emit(op("step_forecast", *step_args(), rng.randrange(1 << 30) if rng.random() < 0.5 else None, an_interval()) if not spec.lgcp else a_refusal())
+        elif r < 0.29:
+            emit(rows_batch("run_intervals_more"))
+        elif r < 0.38:
+            emit(rows_batch("run_forecasts_more") if not spec.lgcp else a_refusal())
+        elif r < 0.50:
+            emit(a_restart())
+        elif r < 0.54:
+            emit(op("step", *step_args()))
+        elif r < 0.59:
+            t, y, has = step_args()
+            emit(op("propagate", t, y if y != spec.outlier else _y(spec, rng), has))
+        elif r < 0.62:
+            emit(op("run_more", min(a_T(False), 12), rng.randrange(1000)))
+        elif r < 0.66:
+            emit(op("set_params", rng.randrange(4)))
+        elif r < 0.70:
+            emit(op("reseed", rng.randrange(1 << 40)))
+        elif r < 0.78:
+            k = rng.choice([q for q in OPTION_VALUES if q != OPT_RESAMPLER])
+            emit(op("set_option", k, rng.choice([v for v in OPTION_VALUES[k] if v != st.opts[k]])))
+        elif r < 0.80:
+            emit(op("set_option", OPT_RESAMPLER, rng.choice((0, 1, 2))))
+        elif r < 0.84 and not spec.lgcp:
+            emit(op("fails", "ENONFINITE", rng.choice((op("step_intervals", st.t - 1.0, _y(spec, rng), 1, 0.975),
+                                                       op("step_forecast", st.t - 1.0, _y(spec, rng), 1, None, 0.975)))))
+        elif r < 0.95:
+            emit(a_refusal())
+        else:
+            emit(a_read())
+    # as in sequence(): the end is a running filter that has just taken a weighted step of a V2 kind, and the last state is compared
+    while st.cloud_unknown and (st.params_unknown or st.seed_unknown):
+        emit(op("set_params", 1) if st.params_unknown else op("reseed", 4242))
+    if st.resampler_pending or not st.usable() or st.cloud_unknown:
+        emit(op("init", 0.0))
+    emit(op("step_intervals", st.t + (0.25 if spec.lgcp else 1.0), _y(spec, rng), 1, 0.975))
+    return seq
+
+
+def pair_allowed_v2(spec: Spec, a: str, b: str) -> bool:
+    """pair_allowed over STATE_KINDS_V2: whether kind b may follow kind a DIRECTLY in some state."""
+    new_a, new_b = a in NEW_KINDS, b in NEW_KINDS
+    if not new_a and not new_b:
+        return pair_allowed(spec, a, b)
+    lgcp_refused = FORECAST_KINDS + ("smooth", "interpolate")
+    if spec.lgcp and (a in lgcp_refused or b in lgcp_refused):
+        return False
+    needs_running = ("step", "propagate", "adopt", "run_more") + CONTINUING
+    if a in ("opt2", "interpolate", "smooth") and b in needs_running:
+        return False                     # a new cloud comes first
+    if a == "pmmh":
+        return b in ("set_params", "reseed") or b.startswith("opt")     # parameters and key are unknown: both are set, then a new cloud
+    if b == "adopt":
+        return a == "propagate" or a in ("set_params", "reseed") or a.startswith("opt")
+    return True
+
+
+def pair_snippet_v2(spec: Spec, a: str, b: str, salt: int) -> List[Op]:
+    """pair_snippet over STATE_KINDS_V2: from a clean running state to a then b directly, then a weighted step and a look at the cloud."""
+    dt = 0.25 if spec.lgcp else 1.0
+    y = 1.0 if spec.data != "gaussian" else 0.5
+    iv = V2_INTERVALS[salt % 3]
+
+    def make(kind: str, t: float, alt: int) -> Tuple[Op, float]:
+        T, ds = 3 + alt, 11 + salt
+        if kind == "init":
+            return op("init", 1.0), 1.0
+        if kind == "init_from":
+            return op("init_from", 0.5, 0.25), 0.5
+        if kind in ("step", "propagate"):
+            return op(kind, t + dt, y + 1.0, 1), t + dt
+        if kind == "step_intervals":
+            return op(kind, t + dt, y + 1.0, 1, iv), t + dt
+        if kind == "step_forecast":
+            return op(kind, t + dt, y + 1.0, 1, None if (salt + alt) % 2 else 977 + salt, iv), t + dt
+        if kind == "adopt":
+            return op("adopt", 0.3125), t
+        if kind == "set_params":
+            return op("set_params", 1 + (salt + alt) % 3), t
+        if kind == "reseed":
+            return op("reseed", 1000 + 7 * salt + alt), t
+        if kind.startswith("opt"):
+            k = int(kind[3:])
+            vals = OPTION_VALUES[k]
+            return op("set_option", k, vals[(salt + alt + 1) % len(vals)]), t
+        o = {"run": op("run", T, ds, alt), "run_more": op("run_more", T, ds), "interpolate": op("interpolate", T, ds, 0.975),
+             "run_intervals": op(kind, T, ds, iv, None), "run_intervals_more": op(kind, T, ds, iv, (salt % T) if salt % 4 == 0 and not spec.lgcp else None),
+             "run_forecasts": op(kind, T, ds, (salt + alt) % 2, iv, None), "run_forecasts_more": op(kind, T, ds, (salt + alt) % 2, iv, None),
+             "smooth": op(kind, T, ds, 16 + salt % 5, iv), "pmmh": op(kind, T, ds, 2, 0.01, 500 + salt)}[kind]
+        return o, float(data_of(spec, o, t)[0][-1])
+
+    out: List[Op] = [op("set_option", OPT_RESAMPLER, 0), op("init", 0.0), op("step", dt, y, 1)]
+    t = dt
+    if b == "adopt" and a != "propagate" or a == "adopt":
+        out.append(op("propagate", t + dt, y, 1)); t += dt
+    for kind, alt in ((a, 0), (b, 1)):
+        o, t = make(kind, t, alt)
+        out.append(o)
+    st = check_legal(spec, out)
+    if st.cloud_unknown:
+        out += ([op("set_params", 0)] if st.params_unknown else []) + ([op("reseed", 20260101 + salt)] if st.seed_unknown else [])
+    if st.resampler_pending or not st.usable() or st.cloud_unknown:
+        out.append(op("init", t))
+    st = check_legal(spec, out)
+    out += [op("step_intervals", st.t + dt, y + 2.0, 1, 0.975) if salt % 2 else op("step", st.t + dt, y + 2.0, 1), op("particles")]
+    return out
+
+
+# (seed, model, N, length, max_T).  1, 2, 63: the smallest clouds; 512 / 513: the block edge of the pair kernel k_forecast_row; 1000: the
+# mid size; 4097: above CSSM_IV_CAP; 5000: the largest size of smooth and pmmh; 70 * 1024 + 3: group sums; (c2, 131073): the second turn of
+# k_fc_finish's block-strided loops; (c1, 300001), slow: the summary's grid-stride loops.
+SEQUENCES_V2: List[Tuple[int, str, int, int, int]] = [
+    (101, "c1", 1, 40, 0), (102, "c1", 63, 40, 0), (103, "c1", 513, 40, 0), (104, "c1", 1000, 45, 0), (105, "c1", 5000, 35, 0),
+    (111, "c2", 2, 40, 0), (112, "c2", 512, 40, 0), (113, "c2", 1000, 45, 0), (114, "c2", 4097, 35, 0), (115, "c2", 70 * 1024 + 3, 13, 0),
+    (121, "c3", 63, 40, 0), (122, "c3", 513, 35, 0), (123, "c3", 5000, 30, 0),
+    (131, "linear", 2, 40, 0), (132, "linear", 1000, 45, 0), (133, "linear", 4097, 35, 0),
+    (141, "studentt", 512, 40, 0), (142, "negbin", 1000, 40, 0), (143, "negbin", 5000, 30, 0),
+    (151, "c4p1", 63, 35, 0), (152, "c4p1", 1000, 35, 0), (153, "c4p1", 4097, 25, 0), (154, "c4p1", 513, 40, 0),
+    (161, "rtc", 513, 40, 0), (162, "rtc", 1000, 40, 0), (163, "rtc", 5000, 30, 0),
+    (171, "c2", 131073, 10, 3),
+]
+SLOW_SEQUENCES_V2: List[Tuple[int, str, int, int, int]] = [(181, "c1", 300001, 11, 3)]
+
+_committed_v2 = None
+
+
+def pair_table_v2(seqs: Sequence[Sequence[Op]]) -> Dict[Tuple[str, str], int]:
+    """pair_table restricted to the pairs with a V2 kind in them."""
+    return {p: c for p, c in pair_table(seqs).items() if p[0] in NEW_KINDS or p[1] in NEW_KINDS}
+
+
+def option_sweep_v2() -> List[Op]:
+    """Every documented value of every option, followed by one of the V2 weighted kinds in turn before that option changes again."""
+    out: List[Op] = [op("init", 0.0), op("step", 1.0, 2.0, 1)]
+    i = 0
+    for k, vals in OPTION_VALUES.items():
+        for v in vals + (OPTION_DEFAULTS[k],):
+            out.append(op("set_option", k, v))
+            t = check_legal(SPECS[COMPLETION[0]], out).t
+            new_cloud = (op("run_intervals", 3, 40 + i, 0.9, 1), op("run_forecasts", 3, 40 + i, 0, 0.975, None), op("smooth", 4, 40 + i, 9, 0.9),
+                         op("run_forecasts", 2, 40 + i, 1, 1.0, 0))
+            going_on = (op("step_intervals", t + 1.0, 3.0, 1, 0.975), op("run_forecasts_more", 3, 40 + i, 0, 0.9, 2), op("step_forecast", t + 0.5, 1.0, 1, None, 0.9),
+                        op("run_intervals_more", 3, 40 + i, 1.0, 0))
+            if k == OPT_RESAMPLER:
+                out.append(new_cloud[i % 4])
+                if new_cloud[i % 4].kind == "smooth":
+                    out.append(op("init", 0.0))
+            else:
+                out.append(going_on[i % 4])
+            i += 1
+    return out + [op("step_intervals", check_legal(SPECS[COMPLETION[0]], out).t + 1.0, 2.0, 1, 0.975), op("particles")]
+
+
+def committed_sequences_v2():
+    """[(id, spec name, n, ops, slow)] of the second vocabulary: the seeded sequences, the option sweep, then the completion sequences
+    -- every pair pair_allowed_v2 allows with a V2 kind in it that the seeded ones left out, as snippets in a fixed order."""
+    global _committed_v2
+    if _committed_v2 is None:
+        out = [(f"v{seed}-{name}-{n}", name, n, sequence_v2(seed, name, n, length, mt), False) for seed, name, n, length, mt in SEQUENCES_V2]
+        out += [(f"v{seed}-{name}-{n}", name, n, sequence_v2(seed, name, n, length, mt), True) for seed, name, n, length, mt in SLOW_SEQUENCES_V2]
+        out.append((f"voptions-{COMPLETION[0]}-{COMPLETION[1]}", COMPLETION[0], COMPLETION[1], option_sweep_v2(), False))
+        spec = SPECS[COMPLETION[0]]
+        tab = pair_table([s[3] for s in out])
+        missing = [(a, b) for a in STATE_KINDS_V2 for b in STATE_KINDS_V2
+                   if (a in NEW_KINDS or b in NEW_KINDS) and pair_allowed_v2(spec, a, b) and (a, b) not in tab]
+        for c in range(0, len(missing), COMPLETION_CHUNK):
+            ops: List[Op] = []
+            for i, (a, b) in enumerate(missing[c:c + COMPLETION_CHUNK]):
+                ops += pair_snippet_v2(spec, a, b, c + i)
+            out.append((f"vpairs{c // COMPLETION_CHUNK}-{COMPLETION[0]}-{COMPLETION[1]}", COMPLETION[0], COMPLETION[1], ops, False))
+        _committed_v2 = out
+    return _committed_v2
+
+
 # --------------------------------------------------------------------------------------------- the expectation
 def adopt_inputs(proposed: np.ndarray, logw: np.ndarray, u: float, ll_prev: float):
     """What a host resampler hands cssm_pf_adopt (model/ParticleFilter.scala:124-130): systematic ancestors of w1 = exp(w - max)
@@ -603,9 +1107,74 @@ def _oracle_call(f, *a):
         raise Failed(ENONFINITE if e.code == oracle.ENONFINITE else e.code) from None
 
 
-def apply_to_oracle(o: oracle.OraclePf, spec: Spec, x: Op, st: HostState, ll_prev: float):
-    """One state-changing op on an initialised oracle; returns what the call returns.  `st` is the state BEFORE the op."""
+def _rows6(rows):
+    return tuple(np.array([r[q] for r in rows]) for q in range(6))
+
+
+def summary_row(o: oracle.OraclePf, interval: float):
+    """The oracle's summary with its two means formed exactly (math.fsum over its cloud; eta_of_mean = its eta_of of that mean).  The
+    oracle adds the N values one after the other: behind a record whose level was ruled out the cloud is N copies of a few particles,
+    every addition rounds the same way, and the sum is off by up to N eps / 2 relative -- 7e-12 at N = 131073, measured 2.6e-12 --
+    which is more than the 1e-12 the means are held to.  The order statistics are the oracle's own."""
+    _, lo, hi, _, el, eu = o.summary(interval)
+    m = np.array([math.fsum(row) for row in o.particles()]) / o.n
+    return m, lo, hi, o.eta_of(m), el, eu
+
+
+def _stepped(o: oracle.OraclePf, t, y, has, st: HostState, new_cloud: bool, interval=None, hook=None):
+    """The route the rows calls replaced, on the oracle: [init; summary;] (step; summary)*.  `hook(s, cloud, clock, observation index,
+    t_s, y_s, has_s)` sees the cloud BEFORE record s is stepped (the source of that record's forecast row).  (ll_t, ess_t, rows)."""
+    rows = []
+    clock, obs = st.t, st.obs
+    if new_cloud:
+        clock, obs = float(np.min(t)), 0
+        o.init(clock)
+        if interval is not None:
+            rows.append(summary_row(o, interval))
+    ll_t, ess_t = np.zeros(len(t)), np.zeros(len(t), dtype=np.int32)
+    for s in range(len(t)):
+        if hook is not None:
+            hook(s, o.particles(), clock, obs + s, float(t[s]), float(y[s]), bool(has[s]))
+        ll_t[s], ess_t[s] = _oracle_call(o.step, float(t[s]), float(y[s]), bool(has[s]))
+        clock = float(t[s])
+        if interval is not None:
+            rows.append(summary_row(o, interval))
+    return ll_t, ess_t, rows
+
+
+def smooth_expected(o: oracle.OraclePf, model: Model, n: int, seed: int, t, y, has, M: int, interval: float):
+    """What cssm_pf_smooth returns, from the oracle `o` (of `model`, n particles, key `seed`): ll of its interpolate (the header: the
+    forward pass is that code), the backward simulation of the sequential twin on its history (the route of test_gpu_smooth.twin_of),
+    the oracle's summary of the states the trajectories pass through.  (ll, mean, lower, upper, eta_of_mean, eta_lower, eta_upper, traj)"""
+    from test_fleet_smooth_host import kinds_of, pack_records, twin_traj
+    from test_smooth_host import twin_rows
+    ll = _oracle_call(o.interpolate, t, y, has, interval)[0]
+    o.init(float(np.min(t)))
+    X, Anc, ll_h = [o.particles()], [o.ancestors()], 0.0
+    for s in range(len(t)):
+        ll_h, _ = _oracle_call(o.step, float(t[s]), float(y[s]), bool(has[s]))
+        X.append(o.proposed()); Anc.append(o.ancestors())
+    if ll_h != ll:
+        raise StaleOracle(f"the oracle's interpolate ll {ll!r} is not its stepped history's {ll_h!r}")
+    X = np.array(X)
+    traj = twin_traj(X, np.array(Anc), pack_records(model, n, seed, t, y, has), kinds_of(model), seed, M)
+    return (ll,) + twin_rows(model, X, traj, t, interval) + (traj,)
+
+
+def apply_to_oracle(o: oracle.OraclePf, spec: Spec, x: Op, st: HostState, ll_prev: float, rows: bool = False, hook=None):
+    """One state-changing op on an initialised oracle; returns what the call returns.  `st` is the state BEFORE the op.  `rows`: form
+    the summary rows of the V2 interval kinds too, `hook`: see _stepped (a replay at a checkpoint wants neither)."""
     k = x.kind
+    if k in ROW_KINDS:
+        if k in STEP_ROWS:
+            t, y, has = np.array([x[1]]), np.array([x[2]]), np.array([x[3]], dtype=np.uint8)
+        else:
+            t, y, has = data_of(spec, x, st.t)
+        iv = interval_of(x) if (rows and k in INTERVAL_KINDS) else None
+        ll_t, ess_t, r = _stepped(o, t, y, has, st, k in NEW_RESTARTS, iv, hook)
+        if k in STEP_ROWS:
+            return (float(ll_t[0]), int(ess_t[0])) + (tuple(r[0]) if r else ())
+        return (float(ll_t[-1]), ll_t, ess_t) + (_rows6(r) if r else ())
     if k == "init":
         o.init(x[1]); return (0.0, o.n)
     if k == "init_from":
@@ -661,12 +1230,14 @@ class Ref:
         self.last_y: Optional[float] = None   # datum of the last weighted native step (None: LGCP, or none yet)
         self.wmode: Optional[str] = None      # "w", "log", or None where only the handle can tell
         self.particle_steps = 0
+        self.hook = None                 # the runner's look at the cloud before every record of a forecast call (see _stepped)
 
     def _new(self) -> oracle.OraclePf:
         k, seed, rs = self.base
         return oracle.OraclePf(self.spec.model(k).descriptor(self.spec.precision), self.n, seed, RESAMPLER_FLAGS[rs])
 
-    def _cost(self, x: Op, st: HostState) -> int:
+    def _cost(self, x: Op, st: HostState, rows: bool = True) -> int:
+        """Particle-steps of oracle work of one op (rows: with the expectation of a forecast call's rows, which a replay does not form)."""
         k = x.kind
         if k in ("step", "propagate"):
             return self.n * substeps(self.spec, x[1] - st.t)
@@ -676,7 +1247,35 @@ class Ref:
             return self.n * int(sum(substeps(self.spec, float(d)) for d in t - prev)) + (self.n if k != "run_more" else 0)
         if k in ("init", "init_from"):
             return self.n
+        if k in STEP_ROWS:
+            return self.n * (substeps(self.spec, x[1] - st.t) + (FORECAST_ROW_COST if k == "step_forecast" and rows else 0))
+        if k in BATCH_ROWS or k in ("smooth", "pmmh"):
+            cont = k in CONTINUING
+            t = data_of(self.spec, x, st.t)[0]
+            prev = np.concatenate(([st.t if cont else t[0]], t[:-1]))
+            c = self.n * int(sum(substeps(self.spec, float(d)) for d in t - prev)) + (0 if cont else self.n)
+            if k in FORECAST_KINDS and rows:
+                c += FORECAST_ROW_COST * self.n * len(t)          # per row: a new oracle of the cloud, one transition
+            if k == "smooth":
+                c = 2 * c + x[3] * self.n * len(t) // SMOOTH_TWIN_PER_STEP   # interpolate, the stepped history, the twin: M trajectories x N parents
+            if k == "pmmh":
+                c *= x[3]
+            return c
         return 0
+
+    def _new_cloud_oracle(self) -> oracle.OraclePf:
+        """A new oracle under the model, key and resampler of this moment."""
+        return oracle.OraclePf(self.spec.model(self.model_k).descriptor(self.spec.precision), self.n, self.seed,
+                               RESAMPLER_FLAGS[self.st.opts[OPT_RESAMPLER]])
+
+    def _smooth(self, x: Op):
+        t, y, has = data_of(self.spec, x, 0.0)
+        return smooth_expected(self._new_cloud_oracle(), self.spec.model(self.model_k), self.n, self.seed, t, y, has, x[3], x[4])
+
+    def _pmmh(self, x: Op):
+        t, y, has = data_of(self.spec, x, 0.0)
+        model = self.spec.model(self.model_k)
+        return _oracle_call(self._new_cloud_oracle().pmmh, model.descriptor(self.spec.precision), theta_of(model), x[4], t, y, has, x[5], x[3])
 
     def apply(self, x: Op):
         """Advance by one legal op; returns the expected return value of a state-changing call (None otherwise)."""
@@ -695,11 +1294,15 @@ class Ref:
         elif state_kind(x) is not None:
             if k == "set_option":
                 pass
-            elif k in RESTARTS:
+            elif k == "smooth":
+                exp = self._smooth(x)
+            elif k == "pmmh":
+                exp = self._pmmh(x)
+            elif k in ALL_RESTARTS:
                 self.base = (self.model_k, self.seed, st.opts[OPT_RESAMPLER])
                 self.prefix = [x]
                 self.o = self._new()
-                exp = apply_to_oracle(self.o, self.spec, x, st, 0.0)
+                exp = apply_to_oracle(self.o, self.spec, x, st, 0.0, True, self.hook)
             else:
                 if k == "set_params":
                     self.model_k = x[1]
@@ -707,11 +1310,11 @@ class Ref:
                     self.seed = int(x[1])
                 if self.o is not None and st.usable():
                     self.prefix.append(x)
-                    exp = apply_to_oracle(self.o, self.spec, x, st, self.ll)
+                    exp = apply_to_oracle(self.o, self.spec, x, st, self.ll, True, self.hook)
             self.particle_steps += self._cost(x, st)
             self._track(x, exp)
         st.apply(x)
-        if k == "interpolate":
+        if k in ("interpolate", "smooth", "pmmh"):
             self.o = None                # nothing of the cloud is defined until the handle is initialised again
             self.prefix = []
         return exp
@@ -728,6 +1331,19 @@ class Ref:
         elif k in ("run", "run_more"):
             t, y, has = series(sp, x[1], x[2], st.t if k == "run_more" else float(x[2] % 3), k == "run_more")
             if k == "run":
+                self.wmode = "log"
+            self.ll = exp[0]
+            self.ess = int(exp[2][-1])
+            w = np.nonzero(has)[0]
+            if len(w):
+                self._mode_after_native(None if sp.lgcp else float(y[w[-1]]))
+        elif k in STEP_ROWS:
+            self.ll, self.ess = exp[0], exp[1]
+            if x[3] or sp.lgcp:
+                self._mode_after_native(None if sp.lgcp else x[2])
+        elif k in BATCH_ROWS:
+            t, y, has = data_of(sp, x, st.t)
+            if k in NEW_RESTARTS:
                 self.wmode = "log"
             self.ll = exp[0]
             self.ess = int(exp[2][-1])
@@ -760,10 +1376,10 @@ class Ref:
         ll = 0.0
         for x in self.prefix:
             r = apply_to_oracle(fresh, self.spec, x, st, ll)
-            self.particle_steps += self._cost(x, st)
-            if x.kind in ("step",):
+            self.particle_steps += self._cost(x, st, rows=False)
+            if x.kind in ("step",) + STEP_ROWS:
                 ll = r[0]
-            elif x.kind in ("run", "run_more"):
+            elif x.kind in ("run", "run_more") + BATCH_ROWS:
                 ll = r[0]
             elif x.kind == "adopt":
                 ll = r[1]
@@ -811,10 +1427,14 @@ def replay_cost(spec_name: str, n: int, seq: Sequence[Op], checkpoints=True) -> 
         if x.kind in ("forecast", "forecast_posterior"):
             c = n * (x[1] if x.kind == "forecast" else 3 * 2)
         total += c
-        if x.kind in RESTARTS:
-            prefix_cost = c
+        if x.kind in ("smooth", "pmmh"):
+            prefix_cost = 0
+        elif x.kind in ALL_RESTARTS:
+            prefix_cost = c - (FORECAST_ROW_COST * n * x[1] if x.kind == "run_forecasts" else 0)   # (a replay forms no rows)
         elif x.kind == "fails":
             prefix_cost = 0
+        elif x.kind in FORECAST_KINDS:
+            prefix_cost += c - FORECAST_ROW_COST * n * (1 if x.kind == "step_forecast" else x[1])
         elif state_kind(x) is not None:
             prefix_cost += c
         cp, pending_switch = _is_checkpoint(x, i == len(seq) - 1, pending_switch)
@@ -829,9 +1449,9 @@ def _is_checkpoint(x: Op, last: bool, pending_switch: bool):
     k = x.kind
     if k == "set_option":
         return last, True
-    if k in ("step", "run_more") and pending_switch:
+    if k in ("step", "run_more") + STEP_ROWS and pending_switch:
         return True, False
-    if k == "run":
+    if k == "run" or k in BATCH_ROWS:
         return True, False
     return last, pending_switch
 
@@ -924,6 +1544,68 @@ class CarriedOracle:
         self._need_init()
         return self.o.summary(interval)
 
+    # -- the V2 calls: the route each of them replaced, on the carried object
+    def _rows(self, t, y, has, interval, new_cloud, lgcp_refused=False):
+        if not new_cloud:
+            self._need_init()
+        if (lgcp_refused and self.spec.lgcp) or len(t) < 1 or _bad_interval(interval):
+            raise Failed(EINVAL_ARG)
+        obs0 = 0 if new_cloud else self.obs
+        try:
+            ll_t, ess_t, rows = _stepped(self.o, t, y, has, self, new_cloud, None if lgcp_refused else interval)
+        finally:
+            self.init_ok, self.t, self.obs, self.last = True, float(t[-1]), obs0 + len(t), "run" if new_cloud else "step"
+        self.ll = float(ll_t[-1])
+        return (self.ll, ll_t, ess_t) + (_rows6(rows) if rows else ())
+
+    def filter_intervals(self, t, y, has, interval):
+        return self._rows(t, y, has, interval, True)
+
+    def filter_intervals_more(self, t, y, has, interval):
+        return self._rows(t, y, has, interval, False)
+
+    def step_intervals(self, t, y, has, interval):
+        self._need_init()
+        if _bad_interval(interval):
+            raise Failed(EINVAL_ARG)
+        return self.step(t, y, has) + summary_row(self.o, interval)
+
+    def default_forecast_keys(self, first, count):
+        return np.array([int(oracle.lib().oracle_c_derive_key(self.seed, (1 << 63) | (first + s))) for s in range(count)], dtype=np.uint64)
+
+    def _forecasts(self, t, y, has, keys, interval, new_cloud):
+        if not new_cloud:
+            self._need_init()
+        used = self.default_forecast_keys(0 if new_cloud else self.obs, len(t)) if keys is None else np.asarray(keys, dtype=np.uint64)
+        r = self._rows(t, y, has, interval, new_cloud, lgcp_refused=True)
+        return dict(ll=r[0], ll_t=r[1], ess_t=r[2], keys=used)
+
+    def filter_forecasts(self, t, y, has, keys, interval):
+        return self._forecasts(t, y, has, keys, interval, True)
+
+    def filter_forecasts_more(self, t, y, has, keys, interval):
+        return self._forecasts(t, y, has, keys, interval, False)
+
+    def step_forecast(self, t, y, has, key, interval):
+        self._need_init()
+        if self.spec.lgcp or _bad_interval(interval):
+            raise Failed(EINVAL_ARG)
+        used = self.forecast_key() if key is None else int(key)
+        return self.step(t, y, has) + ({"key": used},)
+
+    def smooth(self, t, y, has, n_traj, interval, want_trajectories=True, flags=0):
+        if self.spec.lgcp or flags or not 1 <= n_traj <= SMOOTH_MAX_M or _bad_interval(interval) or len(t) < 1:
+            raise Failed(EINVAL_ARG)
+        try:
+            return smooth_expected(self.o, self.model, self.n, self.seed, t, y, has, n_traj, interval)
+        finally:
+            self.init_ok = False
+
+    def pmmh(self, model, delta, t, y, has, seed, iters):
+        r = _oracle_call(self.o.pmmh, model.descriptor(self.spec.precision), theta_of(model), delta, t, y, has, seed, iters)
+        self.init_ok, self.t, self.obs, self.last = True, float(t[-1]), len(t), "run"
+        return r
+
     def particles(self):
         return self.o.particles()
 
@@ -954,6 +1636,39 @@ def _native_call(f, *a, **kw):
         if e.code == EHIP:
             raise                        # a HIP error ends the run: nothing is replayed, nothing goes on
         raise Failed(e.code) from None
+
+
+def _native_smooth_raw(g, t, y, has, M, interval, flags):
+    """cssm_pf_smooth itself, for the arguments NativePf.smooth refuses on the Python side (n_traj = 0, an interval outside (0, 1],
+    CSSM_INTERP_REFERENCE_PAIRING): the status must be the library's."""
+    import ctypes as C
+    from composablestatespacemodels_amd import CssmError
+    t, y = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
+    has = np.ascontiguousarray(has, dtype=np.uint8)
+    dp = C.POINTER(C.c_double)
+    ll = C.c_double()
+    rc = g.lib.cssm_pf_smooth(g._h, t.ctypes.data_as(dp), y.ctypes.data_as(dp), has.ctypes.data_as(C.POINTER(C.c_uint8)), len(t), int(M),
+                              float(interval), int(flags), C.byref(ll), *([None] * 6), None)
+    if rc:
+        raise CssmError(rc, "cssm_pf_smooth")
+    return (ll.value,)
+
+
+def _native_pmmh(g, model, precision, delta, t, y, has, seed, iters):
+    """cssm_pmmh_run on the handle of g (composablestatespacemodels_amd.pmmh.pmmh_native creates a handle of its own and closes it)."""
+    import ctypes as C
+    from composablestatespacemodels_amd import _abi
+    t, y = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
+    has = np.ascontiguousarray(has, dtype=np.uint8)
+    theta0 = np.ascontiguousarray(theta_of(model))
+    nt = theta0.size
+    ll, th, acc, last = np.zeros(iters), np.zeros((iters, nt)), np.zeros(iters, dtype=np.int32), np.zeros((iters, g.d))
+    dp = C.POINTER(C.c_double)
+    desc = model.descriptor(precision)
+    _abi.check(g.lib.cssm_pmmh_run(g._h, desc.ptr(), theta0.ctypes.data_as(dp), nt, float(delta), t.ctypes.data_as(dp), y.ctypes.data_as(dp),
+                                   has.ctypes.data_as(C.POINTER(C.c_uint8)), len(t), int(seed), int(iters), ll.ctypes.data_as(dp),
+                                   th.ctypes.data_as(dp), acc.ctypes.data_as(C.POINTER(C.c_int32)), last.ctypes.data_as(dp)))
+    return ll, th, acc, last
 
 
 # --------------------------------------------------------------------------------------------- the runner
@@ -1033,6 +1748,29 @@ class Runner:
             return call(g.set_option, x[1], x[2])
         if k == "summary":
             return call(g.summary, x[1])
+        if k in ("run_intervals", "run_intervals_more"):
+            t, y, has = data_of(sp, x, st.t)
+            return call(g.filter_intervals if k == "run_intervals" else g.filter_intervals_more, t, y, has, x[3])
+        if k == "step_intervals":
+            return call(g.step_intervals, x[1], x[2], bool(x[3]), x[4])
+        if k in ("run_forecasts", "run_forecasts_more"):
+            t, y, has = data_of(sp, x, st.t)
+            return call(g.filter_forecasts if k == "run_forecasts" else g.filter_forecasts_more, t, y, has,
+                        row_keys(x[2], x[1]) if x[3] else None, x[4])
+        if k == "step_forecast":
+            return call(g.step_forecast, x[1], x[2], bool(x[3]), x[4], x[5])
+        if k in ("smooth", "smooth_pairing"):
+            t, y, has = data_of(sp, x, 0.0)
+            flags = 1 if k == "smooth_pairing" else 0        # CSSM_INTERP_REFERENCE_PAIRING
+            if self.native and (flags or not 1 <= x[3] <= SMOOTH_MAX_M or _bad_interval(x[4])):
+                return call(_native_smooth_raw, g, t, y, has, x[3], x[4], flags)
+            return call(g.smooth, t, y, has, x[3], x[4], True, **({} if self.native else {"flags": flags}))
+        if k == "pmmh":
+            t, y, has = data_of(sp, x, 0.0)
+            model = sp.model(self.ref.model_k)
+            if self.native:
+                return call(_native_pmmh, g, model, sp.precision, x[4], t, y, has, x[5], x[3])
+            return call(g.pmmh, model, x[4], t, y, has, x[5], x[3])
         raise AssertionError(f"not a state call: {x!r}")
 
     def _do(self, x: Op):
@@ -1066,6 +1804,29 @@ class Runner:
         if k == "adopt":
             exp = ref.apply(x)
             call(g.adopt, exp[0], exp[1], exp[2])
+            return
+        if k in FORECAST_KINDS:
+            # the subject first: the reference then holds every row against the cloud it has BEFORE that record, as it steps
+            pre = HostState.__new__(HostState); pre.__dict__.update(st.__dict__)
+            got = self._state_call(x, pre)
+            fc = got[2] if k == "step_forecast" else got
+            T = 1 if k == "step_forecast" else x[1]
+            given = ([x[4]] if x[4] is not None else None) if k == "step_forecast" else (row_keys(x[2], T) if x[3] else None)
+            used: List[int] = []
+
+            def hook(s, cloud, clock, obs_index, ts, ys, hs):
+                key = int(given[s]) if given is not None else int(oracle.lib().oracle_c_derive_key(ref.seed, (1 << 63) | obs_index))
+                used.append(key)
+                if self.native:
+                    self._forecast_row(fc, s, cloud, clock, ts, ys, hs, key, interval_of(x))
+            ref.hook = hook
+            try:
+                exp = ref.apply(x)
+            finally:
+                ref.hook = None
+            _eq("forecast keys", np.atleast_1d(np.asarray(fc["key"] if k == "step_forecast" else fc["keys"], dtype=np.uint64)),
+                np.array(used, dtype=np.uint64))
+            self._compare_return(x, got, exp)
             return
         if state_kind(x) is not None:
             pre = HostState.__new__(HostState); pre.__dict__.update(st.__dict__)
@@ -1121,6 +1882,29 @@ class Runner:
         elif k == "interpolate":
             _eq("interpolate ll", got[0], exp[0])
             _compare_summary(got[1:], exp[1:], "interpolate")
+        elif k in ("run_intervals", "run_intervals_more"):
+            _eq("ll", got[0], exp[0]); _eq("ll_t", got[1], exp[1]); _eq("ess_t", got[2], exp[2])
+            _compare_summary(got[3:9], exp[3:9], k + " rows")
+        elif k == "step_intervals":
+            _eq("ll", got[0], exp[0]); _eq("ess", got[1], exp[1])
+            _compare_summary(got[2:8], exp[2:8], k + " row")
+        elif k in ("run_forecasts", "run_forecasts_more"):
+            _eq("ll", got["ll"], exp[0]); _eq("ll_t", got["ll_t"], exp[1]); _eq("ess_t", got["ess_t"], exp[2])
+        elif k == "step_forecast":
+            _eq("ll", got[0], exp[0]); _eq("ess", got[1], exp[1])
+        elif k == "smooth":
+            _eq("smooth ll", got[0], exp[0])
+            _eq("smooth trajectories", got[7], exp[7])
+            for q, name in ((2, "lower"), (3, "upper"), (5, "eta lower"), (6, "eta upper")):
+                _eq("smooth " + name, got[q], exp[q])
+            for q, name in ((1, "mean"), (4, "eta of mean")):
+                try:
+                    np.testing.assert_allclose(got[q], exp[q], rtol=1e-12, atol=0)    # (test_gpu_smooth.assert_equals_fleet: plain fp64 sums)
+                except AssertionError as e:
+                    raise _Mismatch(f"smooth {name}: {e}") from None
+        elif k == "pmmh":
+            for name, a, b in zip(("ll", "theta", "accepted", "last_state"), got, exp):
+                _eq("pmmh " + name, a, b)
         elif k == "propagate":
             call = _native_call if self.native else (lambda f, *a, **kw: f(*a, **kw))
             _eq("proposed() after propagate", call(self.g.proposed), self.ref.o.proposed())
@@ -1183,6 +1967,24 @@ class Runner:
             check_forecast(r, *expected(model, ref.particles(), ref.st.t, times, r["key"], self.twin), interval=interval)
         except AssertionError as e:
             raise _Mismatch(f"forecast: {e}") from None
+
+    def _forecast_row(self, fc, s, cloud, clock, ts, ys, hs, key, interval):
+        """Row s of a forecast call against test_gpu_forecast.expected from the cloud the reference has before that record; the PIT
+        counts against numpy counts over the expected observation row (-1 for a record without a datum)."""
+        from composablestatespacemodels_amd.filter import FORECAST_NAMES
+        from test_gpu_forecast import check_forecast, expected
+        model = self.spec.model(self.ref.model_k)
+        states, etas, obs = expected(model, cloud, clock, [ts], key, self.twin)
+        r = {name: np.asarray(fc[name])[s:s + 1] for name in FORECAST_NAMES}
+        r["samples"] = None
+        try:
+            check_forecast(r, states, etas, obs, interval=interval)
+        except AssertionError as e:
+            raise _Mismatch(f"forecast row {s} (t = {ts!r}, key {key:#x}) is not the forecast of the cloud before that record: "
+                            f"{str(e).strip() or 'an order statistic differs'}") from None
+        below, equal = (int(np.sum(obs[0] < ys)), int(np.sum(obs[0] == ys))) if hs else (-1, -1)
+        _eq(f"obs_below of row {s}", fc["obs_below"][s], below)
+        _eq(f"obs_equal of row {s}", fc["obs_equal"][s], equal)
 
     def _forecast_posterior(self, x: Op):
         M, key = x[1], x[2]
