@@ -35,6 +35,7 @@ CSSM_OPT_SMOOTH_TILE = 15      # cssm_pf_smooth: the slots a block of the backwa
 SMOOTH_TILE = 512              # CSSM_SMOOTH_TILE
 CSSM_INTERP_REFERENCE_PAIRING = 1
 CSSM_FLEET_NO_ROWS = 0xFFFFFFFF
+CSSM_PF_NO_ROWS = 0xFFFFFFFF      # cssm_pf_step_interpolate: step and remember, no rows
 CSSM_FLEET_COPY_KEEP = -1         # cssm_fleet_copy_series, a map entry: leave the series exactly as it is
 CSSM_FLEET_COPY_KEYS = 1          # ... flags: the Philox key travels too
 CSSM_OPT_FORECAST_CAP = 11
@@ -150,6 +151,10 @@ SYMBOLS = [
     ("cssm_pf_interpolate", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_pf_smooth", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_uint32, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p]),
     ("cssm_pf_smooth_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_pf_window", C.c_int, [_h, C.c_uint32]),
+    ("cssm_pf_window_depth", C.c_uint32, [_h]),
+    ("cssm_pf_step_interpolate", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_double, _dp, _i32p, _u32p, _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("cssm_pf_step_interpolate_last_ms", C.c_int, [_h, _dp]),
     ("cssm_resample_systematic", C.c_int, [_dp, C.c_size_t, C.c_double, _u32p, C.c_int]),
     ("cssm_resample", C.c_int, [C.c_int, _dp, C.c_size_t, C.c_double, C.c_uint64, C.c_uint32, _u32p, C.c_int]),
     ("cssm_resample_residual", C.c_int, [_dp, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.c_int]),

@@ -11,6 +11,7 @@
 
 #include "cssm_host.h"
 #include "cssm_launch_plan.h"
+#include "cssm_window.h"
 
 #define fail cssm_fail
 #define HIP_TRY(expr)                                                                         \
@@ -177,6 +178,12 @@ struct cssm_pf : HostModel, CssmLaunchFields {
   void* iv = nullptr;
   // cssm_pf_filter_forecasts (cssm_intervals.hip): the same for its rows of d + 2 (a sibling IvScratch)
   void* fc = nullptr;
+  // cssm_pf_window / cssm_pf_step_interpolate (cssm_intervals.hip): the ring's bookkeeping (cssm_window.h; slices = 0: no window), the ring
+  // itself with its slices' times (PfWindow) and the selection's scratch of the lineage rows (a third IvScratch).  Every call that writes
+  // the cloud, the key or the parameters restarts the window: three integer stores, whether a window is open or not.
+  cssm_window wring = {0u, 0u, 0u};
+  void* win = nullptr;
+  void* li = nullptr;
 };
 
 // begin/end of one profiled launch
@@ -262,6 +269,7 @@ void cssm_iv_free(cssm_pf* pf);
 #define CSSM_ROWS_NONE 0
 #define CSSM_ROWS_INTERVALS 1
 #define CSSM_ROWS_FORECASTS 2
+#define CSSM_ROWS_LINEAGE 3      /* cssm_pf_step_interpolate: the step's slice into the window and the lineage rows, enqueued behind the step (after a redo: again) */
 int cssm_run_filter_rows(cssm_pf* pf, const double* t, const double* y, const uint8_t* has, size_t T, double* ll_out, double* ll_t, int32_t* ess_t, bool cont,
                          int rows = CSSM_ROWS_INTERVALS);
 int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out, int rows = CSSM_ROWS_INTERVALS);
@@ -269,6 +277,8 @@ int cssm_step_rows(cssm_pf* pf, double t, double obs, int has_obs, double* ll_ou
 // cssm_forecast.hip the row's first launch, cssm_pf.hip's drivers say when (before the record's launch_step)
 // Scalars::err bits under which every kernel of a row returns at once: a series on hold or waiting for its second run
 #define IV_HELD (4u | 8u | 16u | 64u)
+int cssm_li_enqueue(cssm_pf* pf);                 // the slice the step just proposed into the window's newest slot, the call's lineage rows, their way to the host
+bool cssm_li_has_rows(const cssm_pf* pf);         // whether the running cssm_pf_step_interpolate returns rows (else it only remembers its slice)
 int cssm_fc_row(cssm_pf* pf, size_t row);        // the forecast of record `row` of the running call from the cloud as it stands (8 launches, no host work)
 int cssm_fc_results(cssm_pf* pf, size_t nrows);
 int cssm_forecast_refuse_model(const cssm_pf* pf);   // what cssm_pf_forecast refuses of the handle's model, in its words

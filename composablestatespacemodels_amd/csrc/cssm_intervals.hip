@@ -151,6 +151,96 @@ __global__ __launch_bounds__(CSSM_BLOCK) void k_iv_fill(const double* __restrict
   }
 }
 
+// cssm_pf_step_interpolate: k_compose and k_iv_fill in one launch -- row j of the call summarises slice (newest - j) of the handle's window
+// through the lineages that survive to the newest cloud.  X: the slice's cloud (rows `stride` apart), A: the ancestors that resampled it
+// (null, a slice without a datum: none did), b: the lineage composed so far, one index per slot, read and written by the slot's own thread
+// alone (b_in = b; null for row 0, which starts from the identity -- so b carries nothing from one call to the next): j = A[b[i]], left in
+// b[i] for the row of the slice before.  Everything else is k_iv_fill's body, grid, loop and reduction order, line for line: the means keep
+// cssm_pf_summary's bits.  (A kernel of its own, not a flag of k_iv_fill: that kernel's code is the parent's, instruction for instruction.)
+template <int D>
+__global__ __launch_bounds__(CSSM_BLOCK) void k_lineage_fill(const double* __restrict__ X, size_t stride, const uint32_t* __restrict__ A,
+                                                             const uint32_t* b_in, uint32_t* b, uint64_t n, const double* __restrict__ fco, ModelK mk,
+                                                             unsigned long long* __restrict__ keys, double* __restrict__ partial /*[gridDim.x][D]*/,
+                                                             unsigned long long* __restrict__ pmm /*[gridDim.x][D + 1][2]*/,
+                                                             uint32_t* __restrict__ zero, size_t zero_words, const Scalars* __restrict__ sc,
+                                                             unsigned long long* __restrict__ stamp) {
+  __shared__ double s_p[CSSM_BLOCK / 64][D];
+  __shared__ unsigned long long s_mm[CSSM_BLOCK / 64][D + 1][2];
+  if (sc->err & IV_HELD) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) stamp[0] = __builtin_amdgcn_s_memrealtime();
+  for (size_t w = (size_t)blockIdx.x * CSSM_BLOCK + threadIdx.x; w < zero_words; w += (size_t)gridDim.x * CSSM_BLOCK) zero[w] = 0u;
+  double acc[D];
+  unsigned long long kmin[D + 1], kmax[D + 1];
+#pragma unroll
+  for (int k = 0; k < D; ++k) acc[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k <= D; ++k) { kmin[k] = ~0ull; kmax[k] = 0ull; }
+  for (uint64_t i = (uint64_t)blockIdx.x * CSSM_BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * CSSM_BLOCK) {
+    uint32_t q = b_in ? b_in[i] : (uint32_t)i;
+    if (A) q = A[q];
+    b[i] = q;
+    const size_t j = (size_t)q;
+    double x[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      x[k] = X[(size_t)k * stride + j];
+      const unsigned long long key = cssm_order_key(x[k]);
+      keys[(size_t)k * n + i] = key;
+      kmin[k] = key < kmin[k] ? key : kmin[k]; kmax[k] = key > kmax[k] ? key : kmax[k];
+      acc[k] += x[k];
+    }
+    const unsigned long long key = cssm_order_key(link_of(mk.obs_kind, gamma_coef<D>(mk, fco, x)));
+    keys[(size_t)D * n + i] = key;
+    kmin[D] = key < kmin[D] ? key : kmin[D]; kmax[D] = key > kmax[D] ? key : kmax[D];
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6][k] = v;
+  }
+#pragma unroll
+  for (int k = 0; k <= D; ++k) {
+    unsigned long long a = kmin[k], c = kmax[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long oa = iv_shfl_xor(a, off), ob = iv_shfl_xor(c, off);
+      a = oa < a ? oa : a; c = ob > c ? ob : c;
+    }
+    if ((threadIdx.x & 63) == 0) { s_mm[threadIdx.x >> 6][k][0] = a; s_mm[threadIdx.x >> 6][k][1] = c; }
+  }
+  __syncthreads();
+  if (threadIdx.x < D) {
+    double v = 0.0;
+    for (int w = 0; w < CSSM_BLOCK / 64; ++w) v += s_p[w][threadIdx.x];
+    partial[(size_t)blockIdx.x * D + threadIdx.x] = v;
+  }
+  if (threadIdx.x <= D) {
+    unsigned long long a = ~0ull, c = 0ull;
+    for (int w = 0; w < CSSM_BLOCK / 64; ++w) {
+      const unsigned long long oa = s_mm[w][threadIdx.x][0], ob = s_mm[w][threadIdx.x][1];
+      a = oa < a ? oa : a; c = ob > c ? ob : c;
+    }
+    pmm[((size_t)blockIdx.x * (D + 1) + threadIdx.x) * 2] = a;
+    pmm[((size_t)blockIdx.x * (D + 1) + threadIdx.x) * 2 + 1] = c;
+  }
+}
+
+// A cloud into a slot of the window: row k of the slot is row k of `src` -- gathered through `gather` for the base slice (the cloud as
+// cssm_pf_get_particles returns it), as it is for the cloud a step proposed --, and where ancestors resampled it (anc_src) they go beside
+// it.  Returns at once on a held series, like the step's own kernels: the slice is put again behind the redo.
+__global__ __launch_bounds__(256) void k_slice_put(const double* __restrict__ src, size_t src_stride, const uint32_t* __restrict__ gather,
+                                                   const uint32_t* __restrict__ anc_src, uint64_t n, int d, double* __restrict__ dst,
+                                                   size_t dst_stride, uint32_t* __restrict__ anc_dst, const Scalars* __restrict__ sc) {
+  if (sc->err & IV_HELD) return;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    const size_t j = gather ? (size_t)gather[i] : (size_t)i;
+    for (int k = 0; k < d; ++k) dst[(size_t)k * dst_stride + i] = src[(size_t)k * src_stride + j];
+    if (anc_src) anc_dst[i] = anc_src[i];
+  }
+}
+
 // what the block's LDS holds beside the histograms
 struct IvShared {
   uint32_t part[CSSM_BLOCK];
@@ -487,9 +577,12 @@ static void iv_free_one(void*& slot) {
   delete s;
   slot = nullptr;
 }
+static void window_free(cssm_pf* pf);
 void cssm_iv_free(cssm_pf* pf) {
   iv_free_one(pf->iv);
   iv_free_one(pf->fc);
+  iv_free_one(pf->li);
+  window_free(pf);
 }
 
 #define IV_ALLOC(p, bytes)                                                                                               \
@@ -630,9 +723,8 @@ static int iv_begin(cssm_pf* pf, const std::vector<double>& times, double interv
 }
 
 // the downloaded rows -> the caller's arrays
-static void iv_unpack(cssm_pf* pf, size_t nrows, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
+static void iv_unpack(cssm_pf* pf, IvScratch* s, size_t nrows, double* state_mean, double* state_lower, double* state_upper, double* eta_of_mean,
                       double* eta_lower, double* eta_upper) {
-  IvScratch* s = static_cast<IvScratch*>(pf->iv);
   const int d = pf->d, rows = d + 1;
   for (size_t r = 0; r < nrows; ++r) {
     const double* h = s->h_rows + r * s->out_stride;
@@ -664,7 +756,7 @@ static int iv_filter(cssm_pf* pf, const double* t, const double* y, const uint8_
   if (rc) return rc;
   rc = cssm_run_filter_rows(pf, t, y, has_obs, T, ll_out, ll_t, ess_t, cont);
   if (rc) return rc;
-  iv_unpack(pf, times.size(), state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper);
+  iv_unpack(pf, static_cast<IvScratch*>(pf->iv), times.size(), state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper);
   return CSSM_OK;
 }
 
@@ -691,7 +783,7 @@ extern "C" int cssm_pf_step_intervals(cssm_pf* pf, double t, double obs, int has
   if (rc) return rc;
   rc = cssm_step_rows(pf, t, obs, has_obs, ll_out, ess_out);
   if (rc) return rc;
-  iv_unpack(pf, 1, state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper);
+  iv_unpack(pf, static_cast<IvScratch*>(pf->iv), 1, state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper);
   return CSSM_OK;
 }
 
@@ -832,4 +924,195 @@ extern "C" int cssm_pf_step_forecast(cssm_pf* pf, double t, double obs, int has_
 extern "C" int cssm_pf_forecasts_last_ms(cssm_pf* pf, double* ms2) {
   if (!pf || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
   return iv_last_ms(pf, static_cast<IvScratch*>(pf->fc), ms2, "one-step-ahead forecasts");
+}
+
+// ------------------------------------------------------------------------------------ fixed-lag lineages of a live handle
+// cssm_pf_window / cssm_pf_step_interpolate (include/cssm_pf.h): FilterInterpolate as the stream it is, for ONE large cloud.  The handle
+// keeps a ring of its `slices` most recent clouds and of the ancestors that resampled them; cssm_pf_step_interpolate is cssm_pf_step, a
+// copy of the cloud the step proposed into the ring (k_slice_put, behind the step's launches) and, for the last lag + 1 time indices, a
+// row each of 8 launches: k_lineage_fill, the selection's six passes, k_iv_finish.  Which slot is which: cssm_window.h.
+struct PfWindow {
+  double* X = nullptr;          // [slices][d][stride]: the clouds
+  uint32_t* A = nullptr;        // [slices][stride]: the ancestors that resampled them (where weighted)
+  uint32_t* b = nullptr;        // [n]: the lineage composed so far, within one call
+  std::vector<double> time;     // per slot: the slice's time
+  std::vector<uint8_t> weighted;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  uint32_t nrows = 0;           // rows of the running (then of the last completed) call
+  bool timed = false;
+  unsigned long long ticks = 0;
+  double ms0 = -1.0;
+};
+
+static void window_free(cssm_pf* pf) {
+  PfWindow* W = static_cast<PfWindow*>(pf->win);
+  cssm_window_open(&pf->wring, 0u);
+  if (!W) return;
+  if (W->X) (void)hipFree(W->X);
+  if (W->A) (void)hipFree(W->A);
+  if (W->b) (void)hipFree(W->b);
+  if (W->ev0) (void)hipEventDestroy(W->ev0);
+  if (W->ev1) (void)hipEventDestroy(W->ev1);
+  delete W;
+  pf->win = nullptr;
+}
+
+// what cssm_pf_window and cssm_pf_step_interpolate refuse of the handle itself
+static int li_refuse_handle(const cssm_pf* pf) {
+  if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
+  if (pf->obs_kind == CSSM_OBS_LGCP) return fail(CSSM_EINVAL_ARG, "FilterInterpolate weighs with dataLikelihood; the LGCP filter has no path variant");
+  return CSSM_OK;
+}
+
+extern "C" int cssm_pf_window(cssm_pf* pf, uint32_t slices) {
+  if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
+  int rc = li_refuse_handle(pf);
+  if (rc) return rc;
+  if (slices == 1u) return fail(CSSM_EINVAL_ARG, "a window holds at least 2 slices (the base slice and a record); 0 frees it");
+  HIP_TRY(hipSetDevice(pf->device));
+  if (pf->win) { HIP_TRY(hipStreamSynchronize(pf->stream)); window_free(pf); }
+  if (slices == 0u) return CSSM_OK;
+  // slices x stride x (8 d + 4) bytes and the index array, without overflow: stride < 2^33 and d <= 16, so a slice is below 2^41 bytes
+  const size_t per_x = pf->stride * (size_t)pf->d * 8, per_a = pf->stride * 4, idx = (size_t)pf->n * 4;
+  const size_t limit = ~(size_t)0 - idx - 64;
+  if ((size_t)slices > limit / (per_x + per_a))
+    return fail(CSSM_ENOMEM, "a window of %u slices of %zu bytes each does not fit (more than 2^64 bytes)", slices, per_x + per_a);
+  const size_t bytes = (size_t)slices * (per_x + per_a) + idx;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (bytes > total_b) return fail(CSSM_ENOMEM, "a window of %u slices does not fit (%zu bytes; the device has %zu)", slices, bytes, total_b);
+  PfWindow* W = new PfWindow();
+  pf->win = W;
+  if (hipMalloc((void**)&W->X, (size_t)slices * per_x) != hipSuccess || hipMalloc((void**)&W->A, (size_t)slices * per_a) != hipSuccess ||
+      hipMalloc((void**)&W->b, idx) != hipSuccess) {
+    (void)hipGetLastError();
+    window_free(pf);
+    return fail(CSSM_ENOMEM, "a window of %u slices does not fit (%zu bytes)", slices, bytes);
+  }
+  if (hipEventCreate(&W->ev0) != hipSuccess || hipEventCreate(&W->ev1) != hipSuccess) { window_free(pf); return fail(CSSM_EHIP, "hipEventCreate for the window"); }
+  W->time.assign(slices, 0.0);
+  W->weighted.assign(slices, 0);
+  cssm_window_open(&pf->wring, slices);
+  return CSSM_OK;
+}
+
+extern "C" uint32_t cssm_pf_window_depth(const cssm_pf* pf) { return (pf && pf->win) ? cssm_window_depth(&pf->wring) : 0u; }
+
+static void li_put(cssm_pf* pf, PfWindow* W, uint32_t slot, const double* src, size_t src_stride, const uint32_t* gather, const uint32_t* anc_src) {
+  const size_t slab = pf->stride * (size_t)pf->d;
+  hipLaunchKernelGGL(k_slice_put, dim3(grid_for(pf->n, 256, kGridCap)), dim3(256), 0, pf->stream, src, src_stride, gather, anc_src, (uint64_t)pf->n,
+                     pf->d, W->X + (size_t)slot * slab, (size_t)pf->stride, W->A + (size_t)slot * pf->stride, (const Scalars*)pf->sc);
+}
+
+// Behind the step's launches (after a redo: again): the cloud the step proposed and the ancestors that resampled it into the newest slot,
+// then row j = 0 .. nrows - 1 from slice (newest - j), each composing the lineage one slice further back; the end of the call's device
+// time; the rows and their ticks on their way to the host.  No allocation, event or read-back between the rows.
+int cssm_li_enqueue(cssm_pf* pf) {
+  PfWindow* W = static_cast<PfWindow*>(pf->win);
+  IvScratch* s = static_cast<IvScratch*>(pf->li);
+  if (!W || pf->wring.count < 2u || (W->nrows && (!s || !s->keys || W->nrows > s->rows_cap)) || W->nrows > pf->wring.count)
+    return fail(CSSM_ESTATE, "lineage rows outside the handle's window");
+  const uint32_t newest = pf->wring.newest;
+  W->weighted[newest] = pf->anc_valid ? 1 : 0;
+  li_put(pf, W, newest, pf->src, pf->src_stride, nullptr, pf->anc_valid ? pf->anc : nullptr);
+  if (W->nrows) {
+    const int d = pf->d, rows = d + 1;
+    const size_t slab = pf->stride * (size_t)d;
+    const IvArgs a = iv_args(pf, s, rows);
+    for (uint32_t j = 0; j < W->nrows; ++j) {
+      const uint32_t slot = cssm_window_slot(&pf->wring, j);
+      DISPATCH_D(d, k_lineage_fill<D><<<dim3(s->nblocks), dim3(CSSM_BLOCK), 0, pf->stream>>>(
+                        W->X + (size_t)slot * slab, (size_t)pf->stride, W->weighted[slot] ? W->A + (size_t)slot * pf->stride : nullptr,
+                        j ? W->b : nullptr, W->b, (uint64_t)pf->n, s->fco + (size_t)j * CSSM_MAX_DIM, pf->mk, s->keys, s->partial, s->pmm, s->zero,
+                        s->zero_words, pf->sc, s->stamp));
+      iv_launch_rounds(pf, a);
+      hipLaunchKernelGGL(k_iv_finish, dim3(rows), dim3(CSSM_BLOCK), 0, pf->stream, a, s->rows + (size_t)j * s->out_stride, s->stamp);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(W->ev1, pf->stream));
+  if (W->nrows) {
+    HIP_TRY(hipMemcpyAsync(s->h_rows, s->rows, (size_t)W->nrows * s->out_stride * 8, hipMemcpyDeviceToHost, pf->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_rows + s->rows_cap * s->out_stride, s->stamp, 16, hipMemcpyDeviceToHost, pf->stream));
+  }
+  return CSSM_OK;
+}
+
+bool cssm_li_has_rows(const cssm_pf* pf) { return pf->win && static_cast<const PfWindow*>(pf->win)->nrows != 0u; }
+
+extern "C" int cssm_pf_step_interpolate(cssm_pf* pf, double t, double obs, int has_obs, uint32_t lag, double interval, double* ll_out,
+                                        int32_t* ess_out, uint32_t* rows_out, double* state_mean, double* state_lower, double* state_upper,
+                                        double* eta_of_mean, double* eta_lower, double* eta_upper) {
+  if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
+  if (!(interval > 0.0 && interval <= 1.0)) return fail(CSSM_EINVAL_ARG, "interval must be in (0, 1]");
+  int rc = li_refuse_handle(pf);
+  if (rc) return rc;
+  PfWindow* W = static_cast<PfWindow*>(pf->win);
+  if (!W) return fail(CSSM_ESTATE, "the handle has no window: cssm_pf_window first");
+  const bool want = lag != CSSM_PF_NO_ROWS;
+  if (want && lag >= pf->wring.slices)
+    return fail(CSSM_EINVAL_ARG, "a lag of %u reaches behind a window of %u slices (at most slices - 1)", lag, pf->wring.slices);
+  if (!pf->initialised) return fail(CSSM_ESTATE, "cssm_pf_step before cssm_pf_init");
+  HIP_TRY(hipSetDevice(pf->device));
+  if (want) { rc = iv_ensure(pf, pf->li, false, (size_t)lag + 1, interval); if (rc) return rc; }   // (before the window moves: a refusal leaves it as it was)
+  IvScratch* s = static_cast<IvScratch*>(pf->li);
+  W->timed = false; W->ms0 = -1.0; W->ticks = 0ull;
+  HIP_TRY(hipEventRecord(W->ev0, pf->stream));
+  if (pf->wring.count == 0u) {   // a window that (re)starts: the cloud the handle holds now is its base slice, at the handle's clock
+    const uint32_t slot = cssm_window_put(&pf->wring);
+    W->time[slot] = pf->t; W->weighted[slot] = 0;
+    li_put(pf, W, slot, pf->src, pf->src_stride, pf->anc_valid ? pf->anc : nullptr, nullptr);
+  }
+  const uint32_t slot = cssm_window_put(&pf->wring);
+  W->time[slot] = t;
+  W->nrows = want ? cssm_window_rows(&pf->wring, lag) : 0u;
+  if (want) {   // the f coefficients of every row: F(t) of its slice's time, as cssm_pf_summary builds them -- one upload
+    s->h_fco.assign((size_t)W->nrows * CSSM_MAX_DIM, 0.0);
+    StepRec hrec;
+    for (uint32_t j = 0; j < W->nrows; ++j) {
+      const double time = W->time[cssm_window_slot(&pf->wring, j)];
+      cssm_build_rec(pf, time, time, 0.0, 0, pf->step, &hrec);
+      memcpy(&s->h_fco[(size_t)j * CSSM_MAX_DIM], hrec.fco, sizeof hrec.fco);
+    }
+    rc = hipMemcpyAsync(s->fco, s->h_fco.data(), s->h_fco.size() * 8, hipMemcpyHostToDevice, pf->stream) == hipSuccess &&
+                 hipMemsetAsync(s->stamp, 0, 16, pf->stream) == hipSuccess
+             ? CSSM_OK
+             : fail(CSSM_EHIP, "the f coefficients of the lineage rows");
+  }
+  if (!rc) rc = cssm_step_rows(pf, t, obs, has_obs, ll_out, ess_out, CSSM_ROWS_LINEAGE);
+  if (rc) { cssm_window_restart(&pf->wring); return rc; }   // (a failed step leaves no slice to build on)
+  if (want) {
+    iv_unpack(pf, s, W->nrows, state_mean, state_lower, state_upper, eta_of_mean, eta_lower, eta_upper);
+    memcpy(&W->ticks, reinterpret_cast<const char*>(s->h_rows + s->rows_cap * s->out_stride) + 8, 8);
+    const int d = pf->d;
+    for (size_t r = W->nrows; r <= (size_t)lag; ++r) {   // rows the window does not reach
+      for (int k = 0; k < d; ++k) {
+        if (state_mean) state_mean[r * d + k] = cssm_nan();
+        if (state_lower) state_lower[r * d + k] = cssm_nan();
+        if (state_upper) state_upper[r * d + k] = cssm_nan();
+      }
+      if (eta_of_mean) eta_of_mean[r] = cssm_nan();
+      if (eta_lower) eta_lower[r] = cssm_nan();
+      if (eta_upper) eta_upper[r] = cssm_nan();
+    }
+  }
+  if (rows_out) *rows_out = W->nrows;
+  W->timed = true;
+  return CSSM_OK;
+}
+
+extern "C" int cssm_pf_step_interpolate_last_ms(cssm_pf* pf, double* ms2) {
+  if (!pf || !ms2) return fail(CSSM_EINVAL_ARG, "null argument");
+  PfWindow* W = static_cast<PfWindow*>(pf->win);
+  if (!W || !W->timed) return fail(CSSM_ESTATE, "no call of cssm_pf_step_interpolate has completed on this handle's window");
+  if (W->ms0 < 0.0) {
+    HIP_TRY(hipSetDevice(pf->device));
+    float ms = 0.f;
+    HIP_TRY(hipEventSynchronize(W->ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, W->ev0, W->ev1));
+    W->ms0 = (double)ms;
+  }
+  ms2[0] = W->ms0;
+  ms2[1] = W->nrows ? (double)W->ticks * 1e-5 : 0.0;   // 100 MHz
+  return CSSM_OK;
 }

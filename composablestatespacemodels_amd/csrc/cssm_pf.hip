@@ -15,6 +15,9 @@
 #include "cssm_offspring_wave.hip.h"
 #include "cssm_smooth.hip.h"
 
+// cssm_pf_window: a call that writes the handle's cloud, key or parameters leaves the slices remembered so far behind (cssm_window.h)
+static inline void window_restart(cssm_pf* pf) { if (pf->wring.slices) cssm_window_restart(&pf->wring); }
+
 static int upload_init_params(cssm_pf* pf) {
   double m0[CSSM_MAX_DIM], sd0[CSSM_MAX_DIM];
   for (int k = 0; k < pf->d; ++k) { m0[k] = pf->comp[k].m0; sd0[k] = std::sqrt(pf->comp[k].c0); }
@@ -183,6 +186,7 @@ extern "C" void cssm_pf_destroy(cssm_pf* pf) {
 extern "C" int cssm_pf_set_params(cssm_pf* pf, const cssm_model_desc* desc) {
   if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
   HIP_TRY(hipSetDevice(pf->device));
+  window_restart(pf);
   int rc = cssm_build_model(pf, desc, true);
   if (rc) return rc;
   pf->obs_has_scale = desc->leaves[0].has_scale; pf->obs_scale = desc->leaves[0].scale;
@@ -192,6 +196,7 @@ extern "C" int cssm_pf_set_params(cssm_pf* pf, const cssm_model_desc* desc) {
 extern "C" int cssm_pf_reseed(cssm_pf* pf, uint64_t seed) {
   if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
   pf->seed = seed;
+  window_restart(pf);
   return CSSM_OK;
 }
 
@@ -224,6 +229,7 @@ static void fresh_host_state(cssm_pf* pf, double t0) {
   pf->t = t0; pf->step = 0; pf->initialised = true; pf->wparity = 0;
   pf->wmode = false; pf->sums_ready = false; pf->last_optimistic = false; pf->last_grp = false; pf->have_level = false;
   pf->ess_host = (int32_t)(pf->n_global < 2147483647ull ? pf->n_global : 2147483647ull);
+  window_restart(pf);
 }
 
 int cssm_launch_init(cssm_pf* pf, double t0) {
@@ -605,13 +611,15 @@ extern "C" int cssm_pf_init_from(cssm_pf* pf, double t0, const double* state_d) 
   return CSSM_OK;
 }
 
-// rows: cssm_pf_step_intervals -- the summary of the resampled cloud is enqueued behind the step (after a redo: again) and travels with its scalars;
+// rows: cssm_pf_step_interpolate -- the slice the step proposed goes into the handle's window and the lineage rows are enqueued behind the step (after a redo: again);
+// cssm_pf_step_intervals -- the summary of the resampled cloud is enqueued behind the step (after a redo: again) and travels with its scalars;
 // cssm_pf_step_forecast -- the forecast of the record's time is enqueued BEFORE the step, from the cloud the step reads (a redo leaves it alone)
 static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_out, int32_t* ess_out, int rows) {
   if (!pf) return fail(CSSM_EINVAL_ARG, "null handle");
   if (!pf->initialised) return fail(CSSM_ESTATE, "cssm_pf_step before cssm_pf_init");
   if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
   HIP_TRY(hipSetDevice(pf->device));
+  if (rows != CSSM_ROWS_LINEAGE) window_restart(pf);
   int rc = cssm_ensure_recs(pf, 1);
   if (rc) return rc;
   cssm_build_rec(pf, pf->t, t, obs, has_obs, pf->step, &pf->h_recs[0]);
@@ -627,13 +635,17 @@ static int step_impl(cssm_pf* pf, double t, double obs, int has_obs, double* ll_
   if (rc) return rc;
   if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
   if (rows == CSSM_ROWS_FORECASTS) { rc = cssm_fc_results(pf, 1); if (rc) return rc; }
+  if (rows == CSSM_ROWS_LINEAGE) { rc = cssm_li_enqueue(pf); if (rc) return rc; }
   Scalars& h = *pf->h_sc;
-  rc = read_scalars(pf, 0, false, false, /*poll=*/!rows);   // (the completion word, not the stream: 40.4 -> 38.0 us per streaming step at N = 2^20)
+  // (rows travel by a copy on the stream, which the host waits for; a step that only remembers its slice has none, like a plain step)
+  const bool rows_back = rows && !(rows == CSSM_ROWS_LINEAGE && !cssm_li_has_rows(pf));
+  rc = read_scalars(pf, 0, false, false, /*poll=*/!rows_back);   // (the completion word, not the stream: 40.4 -> 38.0 us per streaming step at N = 2^20)
   if (rc) return rc;
   if (on_hold(h)) {   // the max ruled the reference level out: this observation again, relative to the max
     rc = resolve_hold(pf, before, pf->d_recs, pf->step, nullptr, nullptr, 0);
     if (rc) return rc;
     if (rows == CSSM_ROWS_INTERVALS) { rc = cssm_iv_row(pf, 0); if (!rc) rc = cssm_iv_results(pf, 1); if (rc) return rc; }
+    if (rows == CSSM_ROWS_LINEAGE) { rc = cssm_li_enqueue(pf); if (rc) return rc; }   // (the slice and the rows behind the hold returned at once)
     rc = read_scalars(pf);
     if (rc) return rc;
   }
@@ -658,6 +670,7 @@ extern "C" int cssm_pf_propagate(cssm_pf* pf, double t, double obs, int has_obs)
   if (!pf->initialised) return fail(CSSM_ESTATE, "cssm_pf_propagate before cssm_pf_init");
   if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
   HIP_TRY(hipSetDevice(pf->device));
+  window_restart(pf);
   int rc = cssm_ensure_recs(pf, 1);
   if (rc) return rc;
   cssm_build_rec(pf, pf->t, t, obs, has_obs, pf->step, &pf->h_recs[0]);
@@ -694,6 +707,7 @@ extern "C" int cssm_pf_adopt(cssm_pf* pf, const double* state_dN, double ll, int
   if (!pf->initialised) return fail(CSSM_ESTATE, "cssm_pf_adopt before cssm_pf_init");
   if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
   HIP_TRY(hipSetDevice(pf->device));
+  window_restart(pf);
   // the resampled cloud becomes the current one, in place of the proposed cloud (the next propagate reads it directly)
   HIP_TRY(hipMemcpy2DAsync(pf->state[pf->cur], pf->stride * 8, state_dN, pf->n * 8, pf->n * 8, pf->d, hipMemcpyHostToDevice, pf->stream));
   HIP_TRY(hipMemcpyAsync(&pf->sc->ll, &ll, sizeof(double), hipMemcpyHostToDevice, pf->stream));
@@ -722,6 +736,7 @@ static int run_filter(cssm_pf* pf, const double* t, const double* y, const uint8
   double ph_rec = 0, ph_up = 0, ph_enq = 0;
   if (pf->sharded) return fail(CSSM_ESTATE, "a sharded handle is driven through the cssm_pf_shard_* stages");
   HIP_TRY(hipSetDevice(pf->device));
+  window_restart(pf);
   int rc = cssm_ensure_recs(pf, T);
   if (rc) return rc;
   if (cont && (!pf->initialised || path)) return fail(CSSM_ESTATE, "continuing a filter needs an initialised handle (and records no path)");
@@ -1013,6 +1028,7 @@ extern "C" int cssm_pf_set_option(cssm_pf* pf, int option, int value) {
     //  ancestors from every rank -- a general gather, not the boundary rows of two neighbours)
     if (pf->sharded && value == CSSM_RESAMPLE_MULTINOMIAL) return fail(CSSM_ESTATE, "sharded handles resample systematically or stratified");
     pf->resampler = value;
+    window_restart(pf);
     return CSSM_OK;
   }
   return fail(CSSM_EINVAL_ARG, "unknown option %d", option);

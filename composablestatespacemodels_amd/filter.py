@@ -431,6 +431,43 @@ class NativePf:
         _abi.check(self.lib.cssm_pf_smooth_last_ms(self._h, _p(ms)))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
+    def window(self, slices: int):
+        """cssm_pf_window: remember the ``slices`` most recent clouds and ancestor arrays on the device (slices x stride x (8 d + 4) bytes)
+        for ``step_interpolate``; 0 frees them.  Every call restarts the window."""
+        if not 0 <= int(slices) < _abi.CSSM_PF_NO_ROWS:
+            raise ValueError("slices must be in 0 .. 2^32 - 2")
+        _abi.check(self.lib.cssm_pf_window(self._h, int(slices)))
+
+    def window_depth(self) -> int:
+        """The records remembered behind the window's base slice (cssm_pf_window_depth): 0 .. slices - 1."""
+        return int(self.lib.cssm_pf_window_depth(self._h))
+
+    def step_interpolate(self, t: float, y: Optional[float], has_obs: Optional[bool] = None, lag: Optional[int] = None, interval: float = 0.975):
+        """cssm_pf_step_interpolate: ``step``, which also remembers the cloud it proposed in the handle's window, and the fixed-lag
+        interpolation behind it: ``(ll, ess, nrows, (state_mean[lag + 1, d], state_lower, state_upper, eta_of_mean[lag + 1], eta_lower,
+        eta_upper))``.  Row j summarises time index (newest - j) through the lineages that survive to the cloud just written; ``nrows`` =
+        min(lag, window_depth()) + 1 rows are filled, the others read NaN.  ``lag=None``: step and remember only -- ``nrows`` = 0 and
+        six arrays of one NaN row that the call does not touch."""
+        if has_obs is None:
+            has_obs = y is not None
+        if lag is not None and not 0 <= int(lag) < _abi.CSSM_PF_NO_ROWS:
+            raise ValueError("lag must be in 0 .. 2^32 - 2 (None asks for no rows)")
+        ll, ess, nrows = C.c_double(), C.c_int32(), C.c_uint32()
+        rows = _interval_arrays(((0 if lag is None else int(lag)) + 1,), self.d, np.nan)
+        rc = self.lib.cssm_pf_step_interpolate(self._h, float(t), 0.0 if y is None else float(y), 1 if has_obs else 0,
+                                               _abi.CSSM_PF_NO_ROWS if lag is None else int(lag), float(interval), C.byref(ll), C.byref(ess),
+                                               C.byref(nrows), *map(_p, rows))
+        self.generation += 1
+        _abi.check(rc)
+        return ll.value, ess.value, int(nrows.value), rows
+
+    def step_interpolate_last_ms(self) -> Tuple[float, float]:
+        """Device milliseconds of the last ``step_interpolate``: (the whole call, its row launches alone -- 0 without rows)
+        (cssm_pf_step_interpolate_last_ms)."""
+        ms = np.zeros(2)
+        _abi.check(self.lib.cssm_pf_step_interpolate_last_ms(self._h, _p(ms)))
+        return float(ms[0]), float(ms[1])
+
     def particles(self) -> np.ndarray:
         out = np.zeros((self.d, self.n))
         _abi.check(self.lib.cssm_pf_get_particles(self._h, _p(out)))
@@ -1695,6 +1732,31 @@ class FilterInterpolate(_FilterBase):
         t, y, h = split_data(data)
         ll, *arrays = self._ensure(particles).smooth(t, y, h, n_traj, interval)
         return ll, _interpolate_outs(data, t, arrays)
+
+    def window(self, slices: int):
+        """``NativePf.window`` on the filter's handle (``initialiseState`` or ``n_particles`` first): the device memory ``stepInterpolate``
+        remembers in (0 frees it)."""
+        if self._pf is None:
+            raise RuntimeError("window needs the filter's handle: initialiseState (or n_particles) first")
+        self._pf.window(slices)
+        self._win_hist = []
+
+    def stepInterpolate(self, s: PfState, y: TimedObservation, lag: Optional[int], interval: float = 0.975) -> Tuple[PfState, List[PfOut]]:
+        """The stream itself (``ParticleFilter.interpolate``, ParticleFilter.scala:281-310), one element per call: ``stepFilter``, and the
+        ``PfOut`` of the last ``lag + 1`` time indices through the paths that survive to this datum, oldest first as ``interpolate``
+        returns them (fewer while the window holds fewer; ``lag=None``: an empty list).  ``window(slices)`` first; one of the three
+        native resamplers."""
+        if self._pf is None or s._owner is not self._pf or s._generation != self._pf.generation:
+            raise RuntimeError("stepInterpolate must be applied to the filter's current PfState")
+        if self._host_resample is not None:
+            raise RuntimeError("stepInterpolate remembers the device's ancestors: it needs one of the three native resamplers")
+        hist = getattr(self, "_win_hist", [])             # the (t, observation) of the window's slices, oldest first
+        if self._pf.window_depth() == 0:                   # a window that restarts takes the state before this datum as its base slice
+            hist = [(s.t, s.observation)]
+        ll, ess, nrows, rows = self._pf.step_interpolate(y.t, y.observation, lag=lag, interval=interval)
+        hist = (hist + [(y.t, y.observation)])[-(self._pf.window_depth() + 1):]
+        self._win_hist = hist
+        return self._state(y.t, y.observation, ll, ess), [_pfout(*hist[-1 - j], rows, j) for j in range(nrows - 1, -1, -1)]
 
 
 @dataclass(frozen=True)

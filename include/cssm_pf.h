@@ -659,6 +659,55 @@ int cssm_pf_smooth(cssm_pf* pf, const double* t, const double* y, const uint8_t*
  * last cssm_pf_smooth.  CSSM_ESTATE before the first.  The array holds THREE doubles. */
 int cssm_pf_smooth_last_ms(cssm_pf* pf, double* ms3);
 
+/* ---- fixed-lag interpolation of a live handle: FilterInterpolate as the stream it is (ParticleFilter.interpolate, model/
+ * ParticleFilter.scala:281-310 -- one stepInterpolate per observation, every element carrying the paths that survive to that moment;
+ * examples/Interpolate.scala: once data resumes behind a gap, the surviving lineages fill it) for ONE cloud of any size the handle
+ * holds.  The semantics are those of cssm_fleet_window / cssm_fleet_step_interpolate (below), for one series.
+ *
+ * cssm_pf_window(pf, slices): the handle remembers its `slices` most recent clouds and the ancestor arrays that resampled them in a ring
+ * on the device -- slices x stride x (8 d + 4) bytes and one uint32[N] index array (about 470 MB at N = 2^20, d = 3, 16 slices).
+ * slices >= 2 allocates and sets the depth to 0 (re-opening, with the same size or another, restarts the window); 0 frees; 1 is
+ * CSSM_EINVAL_ARG.  An allocation that does not fit is CSSM_ENOMEM naming the bytes (counted without overflow; a count beyond the
+ * device's memory is refused without allocating), and the handle goes on without a window.  cssm_pf_destroy frees the ring.  A sharded
+ * handle is CSSM_ESTATE, an LGCP handle refused in cssm_pf_interpolate's words.
+ * cssm_pf_window_depth(pf): the records remembered behind the base slice, 0 .. slices - 1 (the base slice is not counted; a full ring
+ * overwrites its oldest slice and the depth stays slices - 1); 0 for a null handle or no window.
+ *
+ * cssm_pf_step_interpolate: cssm_pf_step -- t / obs / has_obs / ll_out / ess_out, their bits, the hold-and-redo of an observation and
+ * the handle left afterwards (cloud, ancestors, clock, observation index, level state) are exactly cssm_pf_step's -- which also copies
+ * the cloud the step proposed and the ancestors that resampled it (a record without a datum: none, the identity) into the window's newest
+ * slot, behind the step's own launches, with the slice's time; and, unless lag == CSSM_PF_NO_ROWS, returns the last min(lag, depth) + 1
+ * time indices through the lineages that survive to the cloud just written, row 0 the newest: per row 8 launches (k_lineage_fill, which
+ * composes the lineage one slice further back and fills the selection's keys in one pass; the six passes of the exact two-rank
+ * selection; k_iv_finish), no allocation, event or read-back between the rows, one synchronisation per call as cssm_pf_step_intervals.
+ *   Outputs: state_* = [lag + 1][d], eta_* = [lag + 1]; any may be NULL.  For a handle stepped through records 0 .. m by this call only,
+ *   its window open since before record 0, row j (0 <= j <= min(lag, depth)) is bit for bit row m + 1 - j of cssm_pf_interpolate over
+ *   records 0 .. m (flags 0, the same t0, parameters, key and resampler), the means included; row 0 therefore has the bits of
+ *   cssm_pf_summary behind the step.  Rows min(lag, depth) < j <= lag read NaN; rows_out = min(lag, depth) + 1, or 0 under
+ *   CSSM_PF_NO_ROWS, where nothing of the rows is written.  The bounded ring changes no row it still returns: the lineages are only ever
+ *   composed from the newest index back.  The f coefficients of a row are F(t) of its slice's time.
+ *   Continuity: the window is continuous only across consecutive cssm_pf_step_interpolate calls.  Every other call that writes the
+ *   handle's cloud, key or parameters (cssm_pf_init, _init_from, _step, _step_intervals, _step_forecast, _propagate, _adopt, _ll_filter,
+ *   _ll_filter_more, _filter, _filter_intervals(_more), _filter_forecasts(_more), _interpolate, _smooth, cssm_pmmh_run, _reseed,
+ *   _set_params, _set_option(CSSM_OPT_RESAMPLER)) sets the depth to 0, and the next cssm_pf_step_interpolate first records the cloud the
+ *   handle holds then (what cssm_pf_get_particles returns, identity ancestors) as the base slice at the handle's clock: the rows never
+ *   reach behind it.  Calls that only read (cssm_pf_summary, _forecast, _forecast_posterior, _get_*) leave the window alone.  An open
+ *   window changes nothing any other call returns.  A call that fails after the step has begun restarts the window.
+ *   Errors, before any work: a null handle and an interval outside (0, 1] are CSSM_EINVAL_ARG; a sharded handle CSSM_ESTATE; an LGCP
+ *   handle cssm_pf_interpolate's refusal; a handle without a window CSSM_ESTATE naming cssm_pf_window; a lag >= slices other than
+ *   CSSM_PF_NO_ROWS CSSM_EINVAL_ARG naming both numbers; a handle that is not initialised cssm_pf_step's CSSM_ESTATE.
+ * cssm_pf_step_interpolate_last_ms: ms2[0] = device time of the whole last call (an event pair round everything it enqueued), ms2[1] =
+ * of its row launches alone (the GPU's constant 100 MHz clock, as cssm_pf_intervals_last_ms; 0 without rows); CSSM_ESTATE before the
+ * first call on the window.  The array holds TWO doubles. */
+#define CSSM_PF_NO_ROWS 0xffffffffu
+int cssm_pf_window(cssm_pf* pf, uint32_t slices);
+uint32_t cssm_pf_window_depth(const cssm_pf* pf);
+int cssm_pf_step_interpolate(cssm_pf* pf, double t, double obs, int has_obs, uint32_t lag, double interval,
+                             double* ll_out, int32_t* ess_out, uint32_t* rows_out,
+                             double* state_mean, double* state_lower, double* state_upper,
+                             double* eta_of_mean, double* eta_lower, double* eta_upper);
+int cssm_pf_step_interpolate_last_ms(cssm_pf* pf, double* ms2);
+
 /* ---- stateless resampler: the `Resample[A]` seam (model/package.scala:23) ------------------ */
 
 /* Resampling.systematicResampling (model/Resampling.scala:63-72) on host arrays: weights w[n]
