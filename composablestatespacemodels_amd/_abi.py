@@ -44,6 +44,7 @@ CSSM_LGCP_SIM_KEEP_GRID = 1       # cssm_simulate_lgcp: download the grid rows t
 CSSM_STREAM_THIN = 10             # include/cssm_obs_draws.h: the candidates of simLGCP's thinning
 CSSM_STREAM_IF2 = 12              # include/cssm_numerics.h: the perturbation normals of iterated filtering
 IF2_MAX_THETA = 81                # CSSM_IF2_MAX_THETA
+CSSM_PRIOR_FLAT, CSSM_PRIOR_NORMAL, CSSM_PRIOR_UNIFORM = 0, 1, 2   # cssm_prior.kind
 CSSM_FN_EXP_LE0, CSSM_FN_LGAMMA, CSSM_FN_LGAMMA_KP1 = 8, 9, 10   # cssm_contract_eval: the contract functions evaluated per lane
 CSSM_LGCP_PATH_OK, CSSM_LGCP_PATH_NONFINITE, CSSM_LGCP_PATH_TOO_MANY = 0, 1, 2   # a path's status
 
@@ -65,6 +66,11 @@ class ModelDesc(C.Structure):
         ("n_leaves", C.c_int32), ("obs_kind", C.c_int32), ("lgcp_precision", C.c_int32),
         ("obs_df", C.c_int32), ("leaves", C.POINTER(LeafDesc)),
     ]
+
+
+class Prior(C.Structure):
+    """cssm_prior: one slot's prior on the STORED value (cssm_fleet_pmmh_chains)."""
+    _fields_ = [("kind", C.c_int32), ("pad_", C.c_int32), ("a", C.c_double), ("b", C.c_double)]
 
 
 class PeerHandle(C.Structure):
@@ -249,6 +255,9 @@ SYMBOLS = [
     ("cssm_fleet_if2_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_if2_cooling", C.c_int, [C.c_double, C.c_uint32, C.c_uint32, _dp]),
     ("cssm_fleet_if2_layout", C.c_int, [_descp, _i32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("cssm_fleet_pmmh_chains", C.c_int, [_h, _descp, _dp, C.c_size_t, _dp, C.c_int, C.c_void_p, _dp, _dp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         _u64p, _u64p, _dp, _dp, _u8p, _dp, _dp, _i32p, _dp, _u32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_pmmh_chains_last_ms", C.c_int, [_h, _dp]),
     ("cssm_fleet_window", C.c_int, [_h, C.c_uint32]),
     ("cssm_fleet_window_depth", C.c_uint32, [_h, C.c_uint32]),
     ("cssm_fleet_step_interpolate", C.c_int, [_h, _u8p, _dp, _dp, _u8p, _u32p, C.c_uint32, C.c_double, _dp, _i32p, _u32p, _dp, _dp, _dp, _dp, _dp, _dp,

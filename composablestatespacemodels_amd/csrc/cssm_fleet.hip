@@ -33,6 +33,7 @@
 #include "cssm_fleet_interp.hip.h"
 #include "cssm_fleet_smooth.hip.h"
 #include "cssm_fleet_if2.hip.h"
+#include "cssm_fleet_pmmh.hip.h"
 #include "cssm_simulate.hip.h"
 #include "cssm_simulate_plan.h"
 
@@ -125,6 +126,7 @@ struct cssm_fleet {
   bool bs_ran = false;
   int bs_staging = 0;                   // CSSM_OPT_SMOOTH_STAGING: 0 = the gathered means in LDS where they fit, 1 = never (through L2)
   double ms_if2 = -1.0;                 // cssm_fleet_if2: the device time of the last call's launches (cssm_fleet_if2_last_ms)
+  double ms_pmmh_chains = -1.0;         // cssm_fleet_pmmh_chains: the device time of the last call's launches (cssm_fleet_pmmh_chains_last_ms)
   // the window of cssm_fleet_step_interpolate: per series a ring of win_slices slots, each a cloud and the ancestors that resampled it
   // ([S][slices][d][n] doubles, then [S][slices][n] uint32).  Per series on the host: whether the window is continuous (the cloud the
   // fleet holds is the one its newest slot holds), the newest slot, the records remembered behind the base slice; per slot F at its time
@@ -1996,6 +1998,36 @@ extern "C" int cssm_fleet_smooth_last_ms(cssm_fleet* f, double* ms3) {
   return CSSM_OK;
 }
 
+// The records of cssm_fleet_if2 and cssm_fleet_pmmh_chains: per (series, record) what does not depend on the parameters (FleetIf2Rec and
+// the d f coefficients behind it) -- dt and F(t) as every fleet record has them.
+static void fleet_if2_recs(const cssm_fleet* f, const HostModel& probe, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                           unsigned char* recs) {
+  const uint32_t S = f->S;
+  const int d = f->d;
+  const size_t R = (size_t)off[S], RB = CSSM_FLEET_IF2_REC_BYTES(d);
+  const bool own_level = probe.obs_kind == CSSM_OBS_GAUSSIAN || probe.obs_kind == CSSM_OBS_STUDENT_T;
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+      if (b == a) continue;
+      double tp = t[a];
+      for (size_t s = a + 1; s < b; ++s) tp = (t[s] < tp) ? t[s] : tp;     // data.minBy(_.t).t
+      for (size_t s = a; s < b; ++s) {
+        StepRec rec;
+        cssm_build_rec(&f->base, tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), &rec);
+        FleetIf2Rec h;
+        h.y = y[s]; h.ypart = cssm_obs_ypart(probe.obs_kind, y[s], (double)probe.obs_df);
+        h.ref = own_level ? 0.0 : cssm_if2_level(probe.obs_kind, y[s], 1.0, (double)probe.obs_df);
+        h.dt = rec.dt; h.has_obs = rec.has_obs; h.step = rec.step;
+        unsigned char* dst = recs + s * RB;
+        memcpy(dst, &h, sizeof h);
+        memcpy(dst + sizeof h, rec.fco, (size_t)d * 8u);
+        tp = t[s];
+      }
+    }
+  });
+}
+
 // EXTENSION (the reference has no likelihood maximiser): iterated filtering (IF2; Ionides, Nguyen, Atchade, Stoev and King 2015) -- S
 // independent searches, one workgroup each, every iteration and record of a search inside k_fleet_if2 (cssm_fleet_if2.hip).  The
 // arithmetic is the contract's (include/cssm_numerics.h, "iterated filtering").  The fleet lends its device, stream, contract table, N
@@ -2049,27 +2081,7 @@ extern "C" int cssm_fleet_if2(cssm_fleet* f, const cssm_model_desc* desc, const 
   memcpy(stage.data() + o_seeds, seeds, (size_t)S * 8u);
   memcpy(stage.data() + o_sd, rw_sd, nt * 8u);
   memcpy(stage.data() + o_cool, cool.data(), (size_t)n_iters * 8u);
-  const bool own_level = probe.obs_kind == CSSM_OBS_GAUSSIAN || probe.obs_kind == CSSM_OBS_STUDENT_T;
-  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
-    for (size_t k = lo; k < hi; ++k) {
-      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
-      if (b == a) continue;
-      double tp = t[a];
-      for (size_t s = a + 1; s < b; ++s) tp = (t[s] < tp) ? t[s] : tp;     // data.minBy(_.t).t
-      for (size_t s = a; s < b; ++s) {
-        StepRec rec;                                                      // (dt and F(t) as every fleet record has them)
-        cssm_build_rec(&f->base, tp, t[s], y[s], has_obs ? (int)has_obs[s] : 1, (uint32_t)(s - a), &rec);
-        FleetIf2Rec h;
-        h.y = y[s]; h.ypart = cssm_obs_ypart(probe.obs_kind, y[s], (double)probe.obs_df);
-        h.ref = own_level ? 0.0 : cssm_if2_level(probe.obs_kind, y[s], 1.0, (double)probe.obs_df);
-        h.dt = rec.dt; h.has_obs = rec.has_obs; h.step = rec.step;
-        unsigned char* dst = stage.data() + o_recs + s * RB;
-        memcpy(dst, &h, sizeof h);
-        memcpy(dst + sizeof h, rec.fco, (size_t)d * 8u);
-        tp = t[s];
-      }
-    }
-  });
+  fleet_if2_recs(f, probe, off, t, y, has_obs, stage.data() + o_recs);
   CssmTemps tmp;
   unsigned char* d_stage = nullptr;
   double *d_swarm = nullptr, *d_theta = nullptr, *d_x = nullptr, *d_mean = nullptr, *d_ll = nullptr, *d_ll_t = nullptr;
@@ -2166,6 +2178,173 @@ extern "C" int cssm_fleet_if2_last_ms(cssm_fleet* f, double* ms) {
   if (!f || !ms) return fail(CSSM_EINVAL_ARG, "null argument");
   if (f->ms_if2 < 0.0) return fail(CSSM_ESTATE, "no search has run on this fleet (cssm_fleet_if2 first)");
   *ms = f->ms_if2;
+  return CSSM_OK;
+}
+
+// ParticleMetropolisHastings with the reference's prior argument and Parameters.perturbMvn (model/PMMH.scala:32,68-81; model/
+// Parameters.scala:111-123) -- S whole chains, one workgroup each, every iteration and record of a chain inside k_fleet_pmmh
+// (cssm_fleet_pmmh.hip).  The arithmetic is the contract's (include/cssm_numerics.h, "PMMH chains on the device").  The fleet lends its
+// device, stream, contract table, N and structure; the chains, the states and the records live in buffers of the call.
+static int fleet_pmmh_chol_check(const double* L, size_t nt, size_t which) {
+  for (size_t i = 0; i < nt; ++i)
+    for (size_t j = 0; j < nt; ++j) {
+      const double v = L[i * nt + j];
+      if (!std::isfinite(v)) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: chol %zu [%zu][%zu] is not finite", which, i, j);
+      if (j > i && v != 0.0)
+        return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: chol %zu [%zu][%zu] = %g lies above the diagonal (a lower-triangular factor, row-major)",
+                    which, i, j, v);
+    }
+  return CSSM_OK;
+}
+extern "C" int cssm_fleet_pmmh_chains(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, size_t n_theta, const double* chol,
+                                      int chol_per_chain, const void* priors_, const double* ll0, const double* state0, uint32_t first_iter,
+                                      uint32_t n_iters, uint32_t iters_per_launch, const uint64_t* seeds, const uint64_t* off, const double* t,
+                                      const double* y, const uint8_t* has_obs, double* ll, double* theta, int32_t* accepted, double* last_state,
+                                      uint32_t* diag_out, int* rc_out) {
+  if (!desc || !theta0 || !chol || !seeds || !off) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: null argument (desc, theta0, chol, seeds, off)");
+  const cssm_prior* priors = static_cast<const cssm_prior*>(priors_);
+  if (!ll || !theta || !accepted || !last_state || !rc_out)
+    return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: null output (ll, theta, accepted, last_state, rc_out)");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t || !y) return fail(CSSM_EINVAL_ARG, "null data");
+  HostModel probe;
+  int rc = cssm_build_model(&probe, desc, false);
+  if (rc) return rc;
+  if (probe.obs_kind == CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_DESC, "cssm_fleet_pmmh_chains: the LGCP observation model (sub-stepped events) is not served; " FLEET_PMMH_SERVED);
+  If2Map map;
+  if ((rc = cssm_if2_map_build(desc, &map))) return rc;
+  if ((size_t)map.n_theta != n_theta)
+    return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: n_theta = %zu, the descriptor flattens to %d (cssm_desc_flatten)", n_theta, (int)map.n_theta);
+  const size_t nt = n_theta;
+  if ((rc = fleet_pmmh_chol_check(chol, nt, 0))) return rc;
+  std::vector<cssm_prior> pri(nt);
+  for (size_t j = 0; j < nt; ++j) {
+    cssm_prior p{};
+    if (priors) p = priors[j];
+    p.pad_ = 0;
+    if (p.kind == CSSM_PRIOR_FLAT) { p.a = 0.0; p.b = 0.0; }
+    else if (p.kind == CSSM_PRIOR_NORMAL) {
+      if (!std::isfinite(p.a) || !std::isfinite(p.b) || !(p.b > 0.0))
+        return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: priors[%zu]: a NORMAL prior needs a finite mean and a finite sd > 0 (got %g, %g)", j, p.a, p.b);
+    } else if (p.kind == CSSM_PRIOR_UNIFORM) {
+      if (!(p.a <= p.b)) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: priors[%zu]: a UNIFORM prior needs a <= b (got %g, %g)", j, p.a, p.b);
+    } else {
+      return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: priors[%zu]: unknown kind %d", j, (int)p.kind);
+    }
+    pri[j] = p;
+  }
+  if (n_iters < 1u || n_iters > 1000000u) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: n_iters must be in [1, 1000000] (got %u)", n_iters);
+  if ((uint64_t)first_iter + n_iters > (1ull << 31)) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: first_iter + n_iters must not exceed 2^31");
+  FLEET_LGCP_REFUSE(f, "cssm_fleet_pmmh_chains", FLEET_PMMH_SERVED);
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  const uint32_t S = f->S, n = f->n;
+  const int d = f->d;
+  for (uint32_t k = 0; k < S; ++k) {
+    if ((rc = fleet_off_step("off", off, k))) return rc;
+    if (off[k + 1] - off[k] > 0xfffffffeull) return fail(CSSM_EINVAL_ARG, "series %u: too many records", k);
+  }
+  {   // the structure must be the fleet's
+    HostModel same = f->base;
+    rc = cssm_build_model(&same, desc, true);
+    if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "cssm_fleet_pmmh_chains: desc is not of the fleet's model structure (%s)", keep.c_str()); }
+  }
+  for (uint32_t k = 1; k < S && chol_per_chain; ++k)
+    if ((rc = fleet_pmmh_chol_check(chol + (size_t)k * nt * nt, nt, k))) return rc;
+  // the chains as they start: cur_ll | lp_cur | cur | cur_state
+  const size_t CR = CSSM_FLEET_PMMH_ROW(nt, d);
+  std::vector<double> chain((size_t)S * CR);
+  for (uint32_t k = 0; k < S; ++k) {
+    double* row = chain.data() + (size_t)k * CR;
+    const double* th = theta0 + (size_t)k * nt;
+    double lp = 0.0;
+    for (size_t j = 0; j < nt; ++j)
+      if (pri[j].kind != CSSM_PRIOR_FLAT) lp = lp + cssm_prior_term(pri[j].kind, pri[j].a, pri[j].b, th[j]);
+    if (!(lp > -cssm_inf()))
+      return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: chain %u: theta0 lies outside the prior's support (its log-prior is %g)", k, lp);
+    row[0] = ll0 ? ll0[k] : -1e99;
+    row[1] = lp;
+    memcpy(row + 2, th, nt * 8u);
+    for (int c = 0; c < d; ++c) row[2 + nt + c] = state0 ? state0[(size_t)k * d + c] : 0.0;
+  }
+  HIP_TRY(hipSetDevice(f->device));
+  const size_t R = (size_t)off[S], RB = CSSM_FLEET_IF2_REC_BYTES(d);
+  const size_t n_chol = chol_per_chain ? (size_t)S : (size_t)1;
+  // staged upload: offsets | seeds | chol | priors | chains | records
+  const size_t o_seeds = ((size_t)S + 1u) * 8u, o_chol = o_seeds + (size_t)S * 8u, o_pri = o_chol + n_chol * nt * nt * 8u,
+               o_chain = o_pri + nt * sizeof(cssm_prior), o_recs = o_chain + chain.size() * 8u;
+  std::vector<unsigned char> stage(o_recs + R * RB);
+  memcpy(stage.data(), off, ((size_t)S + 1u) * 8u);
+  memcpy(stage.data() + o_seeds, seeds, (size_t)S * 8u);
+  memcpy(stage.data() + o_chol, chol, n_chol * nt * nt * 8u);
+  memcpy(stage.data() + o_pri, pri.data(), nt * sizeof(cssm_prior));
+  memcpy(stage.data() + o_chain, chain.data(), chain.size() * 8u);
+  fleet_if2_recs(f, probe, off, t, y, has_obs, stage.data() + o_recs);
+  CssmTemps tmp;
+  unsigned char* d_stage = nullptr;
+  double *d_x = nullptr, *d_ll = nullptr, *d_theta = nullptr, *d_last = nullptr;
+  int32_t* d_acc = nullptr; uint32_t* d_count = nullptr;
+  const size_t rows = (size_t)S * n_iters;
+  HIP_ALLOC(tmp, d_stage, stage.size());
+  HIP_ALLOC(tmp, d_x, (size_t)S * 2u * d * n * 8u);
+  HIP_ALLOC(tmp, d_ll, rows * 8u);
+  HIP_ALLOC(tmp, d_theta, rows * nt * 8u);
+  HIP_ALLOC(tmp, d_last, rows * d * 8u);
+  HIP_ALLOC(tmp, d_acc, rows * 4u);
+  HIP_ALLOC(tmp, d_count, (size_t)S * 16u);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIP_TRY(tmp.event(e0)); HIP_TRY(tmp.event(e1));
+  HIP_TRY(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));   // (stage is pageable)
+  HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)S * 16u, f->stream));
+  FleetPmmhLaunch l{};
+  l.args.n = n; l.args.n_theta = (uint32_t)nt; l.args.n_iters = n_iters; l.args.first_iter = first_iter;
+  l.args.chol_stride = chol_per_chain ? (uint32_t)(nt * nt) : 0u;
+  l.args.x = d_x; l.args.chain = reinterpret_cast<double*>(d_stage + o_chain); l.args.count = d_count;
+  l.args.off = reinterpret_cast<const unsigned long long*>(d_stage);
+  l.args.seeds = reinterpret_cast<const unsigned long long*>(d_stage + o_seeds);
+  l.args.chol = reinterpret_cast<const double*>(d_stage + o_chol);
+  l.args.priors = reinterpret_cast<const cssm_prior*>(d_stage + o_pri);
+  l.args.recs = d_stage + o_recs;
+  l.args.ll = d_ll; l.args.theta = d_theta; l.args.accepted = d_acc; l.args.last = d_last;
+  l.args.logtab = f->logtab.at<const double>();
+  l.args.df = (double)probe.obs_df; l.args.mk = f->base.mk; l.args.map = map;
+  l.n_series = S; l.d = d; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+  const uint32_t per = (iters_per_launch == 0u || iters_per_launch > n_iters) ? n_iters : iters_per_launch;
+  HIP_TRY(hipEventRecord(e0, f->stream));
+  for (uint32_t it0 = 0; it0 < n_iters && R; it0 += per) {      // (the result does not depend on the split: a launch leaves the chains in HBM)
+    l.args.it0 = it0; l.args.it1 = std::min(n_iters, it0 + per);
+    const int hrc = cssm_fleet_pmmh_launch(l);
+    if (hrc) return fail(CSSM_EHIP, "k_fleet_pmmh: %s", hipGetErrorString((hipError_t)hrc));
+  }
+  HIP_TRY(hipEventRecord(e1, f->stream));
+  std::vector<uint32_t> h_count((size_t)S * 4u);
+  HIP_TRY(hipMemcpyAsync(ll, d_ll, rows * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(theta, d_theta, rows * nt * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(last_state, d_last, rows * d * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(accepted, d_acc, rows * 4u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(h_count.data(), d_count, (size_t)S * 16u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  float ms = 0.f;
+  f->ms_pmmh_chains = (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : -1.0;
+  for (uint32_t k = 0; k < S; ++k) {
+    const bool ran = off[k + 1] > off[k];
+    rc_out[k] = ran ? CSSM_OK : CSSM_EINVAL_ARG;
+    if (diag_out) { diag_out[2u * k] = ran ? h_count[4u * k + 1u] : 0u; diag_out[2u * k + 1u] = ran ? h_count[4u * k + 2u] : 0u; }
+    if (ran) continue;                                           // no records: no block ran, its rows read NaN
+    const size_t r0 = (size_t)k * n_iters;
+    std::fill(ll + r0, ll + r0 + n_iters, cssm_nan());
+    std::fill(theta + r0 * nt, theta + (r0 + n_iters) * nt, cssm_nan());
+    std::fill(last_state + r0 * d, last_state + (r0 + n_iters) * d, cssm_nan());
+    std::fill(accepted + r0, accepted + r0 + n_iters, -1);
+  }
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_pmmh_chains_last_ms(cssm_fleet* f, double* ms) {
+  if (!f || !ms) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (f->ms_pmmh_chains < 0.0) return fail(CSSM_ESTATE, "no chains have run on this fleet (cssm_fleet_pmmh_chains first)");
+  *ms = f->ms_pmmh_chains;
   return CSSM_OK;
 }
 

@@ -939,6 +939,45 @@ class NativePfFleet:
                                                 _p(ll), _p(th), _p(acc), _p(last)))
         return ll, th, acc, last
 
+    def pmmh_chains(self, desc, theta0, chol, off, t, y, has, seeds, iters, priors=None, first_iter: int = 0, ll0=None, state0=None,
+                    iters_per_launch: int = 0):
+        """cssm_fleet_pmmh_chains: whole Metropolis chains on the device, a chain per series from the rows of ``theta0[S, n_theta]`` under
+        ``seeds``, on the arrays ``pack`` made (``allow_empty``: a series without records is left alone, its rows read NaN).  ``chol``:
+        the proposal's lower-triangular factor ``[n_theta, n_theta]``, or one per chain ``[S, n_theta, n_theta]``; ``priors``: None (all
+        flat) or ``n_theta`` ``_abi.Prior`` entries (``pmmh.priors_for``); ``first_iter`` / ``ll0[S]`` / ``state0[S, d]`` continue chains.
+        Returns ``(ll[S, iters], theta[S, iters, n_theta], accepted[S, iters], last_state[S, iters, d], diag[S, 2], rc[S])``.  The fleet's
+        clouds, clocks, keys and parameters are not touched."""
+        nt = self.n_theta
+        theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+        if theta0.shape != (self.S, nt):
+            raise ValueError(f"theta0 must be [S, n_theta] = [{self.S}, {nt}]")
+        chol = np.ascontiguousarray(chol, dtype=np.float64)
+        if chol.shape not in ((nt, nt), (self.S, nt, nt)):
+            raise ValueError(f"chol must be [n_theta, n_theta] or [S, n_theta, n_theta] with n_theta = {nt}, S = {self.S}")
+        pri = None
+        if priors is not None:
+            if len(priors) != nt:
+                raise ValueError(f"priors must hold n_theta = {nt} entries")
+            pri = (_abi.Prior * nt)(*priors)
+        keys = np.ascontiguousarray([int(x) & (2**64 - 1) for x in seeds], dtype=np.uint64)
+        if len(keys) != self.S:
+            raise ValueError("one seed per chain")
+        l0 = None if ll0 is None else np.ascontiguousarray(ll0, dtype=np.float64).reshape(self.S)
+        s0 = None if state0 is None else np.ascontiguousarray(state0, dtype=np.float64).reshape(self.S, self.d)
+        R, t, y, has = self._record_inputs(off, t, y, has)
+        iters = int(iters)
+        rows = max(iters, 0)
+        ll, th, last = np.zeros((self.S, rows)), np.zeros((self.S, rows, nt)), np.zeros((self.S, rows, self.d))
+        acc, diag, rc = np.zeros((self.S, rows), dtype=np.int32), np.zeros((self.S, 2), dtype=np.uint32), np.zeros(self.S, dtype=np.int32)
+        _abi.check(self.lib.cssm_fleet_pmmh_chains(self._h, desc.ptr(), _p(theta0), nt, _p(chol), int(chol.ndim == 3), pri, _p(l0), _p(s0),
+                                                   int(first_iter), iters, int(iters_per_launch), _p(keys), _p(off), _p(t), _p(y), _p(has), _p(ll),
+                                                   _p(th), _p(acc), _p(last), _p(diag), _p(rc)))
+        return ll, th, acc, last, diag, rc
+
+    def pmmh_chains_last_ms(self) -> float:
+        """Device time (HIP events) of the launches of the last ``pmmh_chains``, ms."""
+        return self._ms(self.lib.cssm_fleet_pmmh_chains_last_ms, 1)[0]
+
     def init(self, t0):
         t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (self.S,)), dtype=np.float64)
         self.generation += 1

@@ -10,6 +10,9 @@ work is one native filter run.  Two entry points:
 * ``pmmh_native`` -- the wiring of examples/DetermineParameters.scala:58-80 (``perturb(delta)``
   proposal, symmetric transition, flat prior) executed by ``cssm_pmmh_run`` inside the library with
   the contract's Philox streams, so a CPU restatement reproduces the chain bit for bit.
+* ``pmmh_fleet_chains`` -- whole chains on the device (``cssm_fleet_pmmh_chains``), a chain per series of a fleet, with the reference's
+  ``prior`` argument (``Prior``, ``priors_for``) and its tuned proposal ``Parameters.perturbMvn(chol)`` (``covariance``,
+  ``chol_from_pilot``; ``perturbMvn`` / ``perturbMvnEigen`` are the same proposals for the generic loop above).
 """
 from __future__ import annotations
 
@@ -238,6 +241,140 @@ def pmmh_native_fleet(unparam: UnparamModel, inits: Sequence[Parameters], datas,
         raise ValueError(f"the fleet holds {fleet.S} series of {fleet.n} particles, the run needs {S} of {n}")
     try:
         return fleet.pmmh_run(desc, theta0, delta, off, t, y, has, seeds, iters)
+    finally:
+        if own:
+            fleet.close()
+
+
+class Prior:
+    """A slot's prior on the STORED (unconstrained) value, as ``cssm_fleet_pmmh_chains`` takes it (``cssm_prior``): the reference's
+    ``prior: P => LogLikelihood`` (PMMH.scala:32,72-73) as a sum of independent terms over the flattened parameters."""
+
+    @staticmethod
+    def flat() -> _abi.Prior:
+        return _abi.Prior(_abi.CSSM_PRIOR_FLAT, 0, 0.0, 0.0)
+
+    @staticmethod
+    def normal(mean: float, sd: float) -> _abi.Prior:
+        """``-(z z) / 2``, ``z = (theta - mean) / sd`` (constants dropped: only differences decide)."""
+        return _abi.Prior(_abi.CSSM_PRIOR_NORMAL, 0, float(mean), float(sd))
+
+    @staticmethod
+    def uniform(lo: float, hi: float) -> _abi.Prior:
+        """0 on ``[lo, hi]``, -inf outside."""
+        return _abi.Prior(_abi.CSSM_PRIOR_UNIFORM, 0, float(lo), float(hi))
+
+
+def param_names(params: Parameters):
+    """A name per slot of ``params.flattenParams()``: ``"<leaf>.scale"`` and ``"<leaf>.<field>[<i>]"`` (the SDE parameter's own field
+    names, e.g. ``"0.phi[0]"``)."""
+    import dataclasses
+    names = []
+    for l, node in enumerate(params.leaves):
+        if node.scale is not None:
+            names.append(f"{l}.scale")
+        for fld in dataclasses.fields(node.sdeParam):
+            names.extend(f"{l}.{fld.name}[{i}]" for i in range(len(getattr(node.sdeParam, fld.name))))
+    return names
+
+
+def priors_for(params: Parameters, priors) -> list:
+    """The ``n_theta`` priors of ``pmmh_fleet_chains`` from a dict ``{slot index or name (param_names): Prior}``; every other slot is
+    flat.  An unknown slot is refused."""
+    names = param_names(params)
+    out = [Prior.flat() for _ in names]
+    for key, pr in dict(priors).items():
+        if isinstance(key, str):
+            if key not in names:
+                raise ValueError(f"no parameter named {key!r} (the names are {names})")
+            j = names.index(key)
+        else:
+            j = int(key)
+            if not 0 <= j < len(names):
+                raise ValueError(f"slot {j} outside the {len(names)} flattened parameters")
+        if not isinstance(pr, _abi.Prior):
+            raise ValueError(f"slot {key!r}: a Prior.flat() / .normal(mean, sd) / .uniform(lo, hi) is needed")
+        out[j] = pr
+    return out
+
+
+def covariance(theta_rows) -> np.ndarray:
+    """``Parameters.covariance(samples)`` (Parameters.scala:135-139): the sample covariance (denominator ``n - 1``) of flattened rows
+    ``theta_rows[n, n_theta]`` -- a chain's ``theta`` output, or a sequence of Parameters."""
+    rows = [np.asarray(r.flattenParams() if isinstance(r, Parameters) else r, dtype=np.float64) for r in theta_rows]
+    m = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    if m.shape[0] < 2:
+        raise ValueError("the covariance of a sample needs two rows at least")
+    return np.atleast_2d(np.cov(m, rowvar=False))
+
+
+def perturbMvn(chol):
+    """``Parameters.perturbMvn(chol)`` (Parameters.scala:111-114) as a proposal of the generic ``MetropolisHastings.pmmhState`` loop:
+    ``p + chol z``, z standard normal, the innovations added in flatten order."""
+    chol = np.atleast_2d(np.asarray(chol, dtype=np.float64))
+
+    def proposal(p: Parameters, rng: np.random.Generator) -> Parameters:
+        return p.add(chol @ rng.standard_normal(chol.shape[1]))
+    return proposal
+
+
+def perturbMvnEigen(eigvals, eigvecs):
+    """``Parameters.perturbMvnEigen(eigen)`` (Parameters.scala:116-123): ``p + Q z`` with ``Q = eigvecs diag(sqrt(eigvals))`` -- the
+    same innovation covariance as ``perturbMvn`` of the Cholesky factor."""
+    q = np.asarray(eigvecs, dtype=np.float64) * np.sqrt(np.asarray(eigvals, dtype=np.float64))[None, :]
+
+    def proposal(p: Parameters, rng: np.random.Generator) -> Parameters:
+        return p.add(q @ rng.standard_normal(q.shape[1]))
+    return proposal
+
+
+def chol_from_pilot(theta_rows, scale: Optional[float] = None, jitter: float = 1e-12) -> np.ndarray:
+    """The lower-triangular proposal factor of ``pmmh_fleet_chains`` from a pilot chain's rows ``theta_rows[n, n_theta]``:
+    ``chol(scale * covariance + jitter I)`` over the slots that moved, zero rows (a fixed parameter) on those that did not.
+    ``scale``: None = ``2.38**2 / n_free`` (Roberts, Gelman and Gilks 1997), n_free the slots that moved."""
+    m = np.atleast_2d(np.asarray(theta_rows, dtype=np.float64))
+    nt = m.shape[1]
+    free = np.flatnonzero(m.max(axis=0) > m.min(axis=0))
+    L = np.zeros((nt, nt))
+    if free.size == 0:
+        return L
+    s = 2.38 ** 2 / free.size if scale is None else float(scale)
+    cov = covariance(m[:, free]) * s + jitter * np.eye(free.size)
+    L[np.ix_(free, free)] = np.linalg.cholesky(cov)
+    return L
+
+
+def pmmh_fleet_chains(unparam: UnparamModel, inits: Sequence[Parameters], datas, n: int, chol, priors=None, iters: int = 1000,
+                      seeds: Optional[Sequence[int]] = None, first_iter: int = 0, ll0=None, state0=None, iters_per_launch: int = 0,
+                      device: int = 0, fleet: Optional[NativePfFleet] = None):
+    """``len(inits)`` whole chains on the device (``cssm_fleet_pmmh_chains``), a chain per series and every iteration of a chain inside
+    one launch: the reference's PMMH with its ``prior`` argument (PMMH.scala:32,72-73) and its tuned proposal ``Parameters.perturbMvn``
+    (Parameters.scala:111-114).  ``chol``: the proposal's lower-triangular factor ``[n_theta, n_theta]`` (``chol_from_pilot``; one per
+    chain as ``[S, n_theta, n_theta]``); ``math.sqrt(delta) * np.eye(n_theta)`` with no priors is ``pmmh_native_fleet`` bit for bit.
+    ``priors``: None, ``n_theta`` entries, or a dict for ``priors_for``.  ``first_iter`` / ``ll0`` / ``state0`` continue chains from their
+    last rows.  Returns ``(ll[S, iters], theta[S, iters, n_theta], accepted[S, iters], last_state[S, iters, d], diag[S, 2])`` -- what
+    ``pmmh_native_fleet`` returns, then per chain the proposals rejected unfiltered (outside the prior's support) and those whose filter
+    had no usable weight; ``fleet_posterior_rows`` takes the first four as they are."""
+    S = len(inits)
+    if S < 1 or seeds is None or len(seeds) != S:
+        raise ValueError("one seed per chain")
+    theta0 = [np.asarray(p.flattenParams(), dtype=np.float64) for p in inits]
+    if any(th.shape != theta0[0].shape for th in theta0):
+        raise ValueError("every chain's initial parameters must flatten to the same length")
+    theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+    if isinstance(priors, dict):
+        priors = priors_for(inits[0], priors)
+    off, t, y, has = pmmh_fleet_pack(datas, S)
+    model = unparam.run(inits[0])
+    desc = model.descriptor()
+    own = fleet is None
+    if own:
+        fleet = NativePfFleet(model, n, S, device)
+    elif fleet.S != S or fleet.n != int(n):
+        raise ValueError(f"the fleet holds {fleet.S} series of {fleet.n} particles, the run needs {S} of {n}")
+    try:
+        return fleet.pmmh_chains(desc, theta0, chol, off, t, y, has, seeds, iters, priors=priors, first_iter=first_iter, ll0=ll0,
+                                 state0=state0, iters_per_launch=iters_per_launch)[:5]
     finally:
         if own:
             fleet.close()

@@ -1375,6 +1375,70 @@ CSSM_HD double cssm_if2_uniform(uint64_t key, uint32_t step) {
   return cssm_u01(b.v[0], b.v[1]);
 }
 
+/* ------------------------------------------------------------------ PMMH chains on the device */
+
+/*
+ * cssm_fleet_pmmh_chains: ParticleMetropolisHastings (model/PMMH.scala:68-81) with the reference's own `prior: P => LogLikelihood`
+ * (:32,72-73) and its tuned proposal Parameters.perturbMvn(chol) (model/Parameters.scala:111-123), a chain per series, every iteration
+ * of a chain inside k_fleet_pmmh.  Nothing above this line changes and the contract version stays what it is.  This section states one
+ * chain so that a sequential program written from this header reproduces the device bit for bit (tests/pmmh_chain_twin.py is that
+ * program).  -ffp-contract=off holds: every product and every sum below is rounded on its own.
+ *
+ * State of chain k (user seed `seed`): cur[j] (the flattened STORED vector, cssm_desc_flatten order, n_theta slots), cur_ll, lp_cur,
+ * cur_state[d], accepted.  At the start of a call cur = theta0, cur_ll = ll0 (absent: -1e99, PMMH.scala:121), cur_state = state0 (absent:
+ * zeros), accepted = 0, lp_cur = lp(theta0) (below; -inf or NaN refuses the call).
+ *
+ * Iteration it = first_iter + q, q = 0 .. n_iters - 1 (the counters of cssm_pmmh_run):
+ *   proposal:  z_j = element j & 1 of cssm_normal_pair_of(seed, it, j >> 1, CSSM_STREAM_HOST, 0, tab), j < n_theta;
+ *              prop_i = cssm_chain_propose(L_i, z, i, cur_i), L_i = row i of the lower-triangular factor (row-major, n_theta doubles a
+ *              row): s_i = the left-to-right sum over increasing j <= i of L[i][j] * z_j over the entries with L[i][j] != 0.0, the first
+ *              term starting the sum, prop_i = cur_i + s_i; a row without a non-zero entry leaves the slot's bits untouched (a fixed
+ *              parameter).  L = sqrt(delta) I is Parameters.perturb(delta), cssm_pmmh_run's proposal, exactly.
+ *   prior:     lp' = cssm_chain_lp(prior terms of prop): lp = 0.0, then lp = lp + cssm_prior_term(kind_j, a_j, b_j, prop_j) over the
+ *              slots j = 0 .. n_theta - 1 whose kind is not 0 (flat).  All flat: exactly 0.0.
+ *   unfiltered rejection: !(lp' > -inf) (outside the prior's support) rejects without a filter run; the draws are counter-based, so
+ *              skipping shifts nothing.  (What the descriptor path refuses -- cssm_build_model -- is structure only: leaves, dimensions,
+ *              kinds, a missing scale.  A proposal changes values alone and can violate none of it, so the block has no second test;
+ *              values whose constrained form is not finite reach the filter and end as the next case.)
+ *   filter:    key = cssm_derive_key(seed, it + 1).  cssm_fleet_filter with last_out only, under the proposal and the key: constrained
+ *              fields by cssm_constrain, sd = cssm_exp(stored scale), x0[c] = cssm_sqrt(C0_c) * z_c + M0_c (CSSM_STREAM_INIT, particle i,
+ *              step 0), then per record r (observation index r, dt = t_r - t_{r-1}, t_{-1} = the smallest time of the series): the
+ *              coefficients by cssm_sde_coef, the density constants by cssm_obs_consts, the level cssm_ref_level(kind, y, sd, df), the
+ *              uniform cssm_if2_uniform(key, r); transition, log-density, level choice, 2^-96 sums, ll, systematic resampling as the
+ *              fleet filter's statements.  A NaN log-weight, a maximum that is not finite or a zero sum of weights: the filter has no
+ *              usable weight, ll' = -inf (a rejection).  Otherwise ll' = its ll and state' = row T of its sampled path: the cloud behind
+ *              the last record through its ancestors at slot |int32(Philox(key, 0, T, CSSM_STREAM_PICK, 0).v[0])| mod N.
+ *   decision:  u = cssm_u01_open0 of Philox(seed, it, 0xffffffff, CSSM_STREAM_HOST, 1).v[0..1];
+ *              a = cssm_chain_log_ratio(ll', lp', cur_ll, lp_cur) = ((ll' + lp') - cur_ll) - lp_cur   (PMMH.scala:72-73, a symmetric
+ *              transition); accept iff cssm_log(u) < a (false for a NaN a).  Accept: cur = prop, cur_ll = ll', lp_cur = lp', cur_state =
+ *              state', accepted += 1.  The iteration's row is (cur_ll, cur, accepted, cur_state) after the decision.
+ * A chain continued with first_iter = the iterations done, theta0 / ll0 / state0 = its last row is the uninterrupted chain bit for bit
+ * (accepted restarts at 0): lp_cur recomputed from the same bits is the same number.
+ */
+#define CSSM_PRIOR_KIND_FLAT 0
+#define CSSM_PRIOR_KIND_NORMAL 1
+#define CSSM_PRIOR_KIND_UNIFORM 2
+/* one slot's term on the STORED value (constants dropped: only differences decide) */
+CSSM_HD double cssm_prior_term(int kind, double a, double b, double theta) {
+  if (kind == CSSM_PRIOR_KIND_NORMAL) { const double z = (theta - a) / b; return -(z * z) / 2.0; }
+  if (kind == CSSM_PRIOR_KIND_UNIFORM) return (a <= theta && theta <= b) ? 0.0 : -cssm_inf();
+  return 0.0;
+}
+/* prop_i from row i of L (n = i + 1 entries are read) */
+CSSM_HD double cssm_chain_propose(const double* Li, const double* z, uint32_t i, double cur) {
+  double s = 0.0;
+  int any = 0;
+  for (uint32_t j = 0; j <= i; ++j) {
+    if (Li[j] != 0.0) {
+      const double p = Li[j] * z[j];
+      s = any ? s + p : p;
+      any = 1;
+    }
+  }
+  return any ? cur + s : cur;
+}
+CSSM_HD double cssm_chain_log_ratio(double ll_prop, double lp_prop, double ll_cur, double lp_cur) { return ((ll_prop + lp_prop) - ll_cur) - lp_cur; }
+
 #ifdef __cplusplus
 }
 #endif

@@ -1456,6 +1456,49 @@ int cssm_fleet_if2_cooling(double cooling_fraction_50, uint32_t first_iter, uint
  * m0, c0, mu, phi, sigma (-1: the SDE has no such field); then n_theta flags: 1 = the slot only feeds the initial draw.  *count = the
  * integers that is (5 + 10 d + n_theta); out may be NULL to ask for it. */
 int cssm_fleet_if2_layout(const cssm_model_desc* desc, int32_t* out, size_t cap, size_t* count);
+
+/* ---- whole PMMH chains on the device (model/PMMH.scala:32,68-81 with the reference's own prior argument; Parameters.perturbMvn,
+ * model/Parameters.scala:111-123).  S chains, a chain per series and ONE WORKGROUP PER CHAIN: every iteration and every record of a
+ * chain runs inside k_fleet_pmmh, the record built in the block from the chain's own parameter row, so the host does nothing between
+ * iterations.  The arithmetic is the contract's (include/cssm_numerics.h, "PMMH chains on the device").
+ *
+ * Chain k starts at theta0[k * n_theta ..] (cssm_desc_flatten order of `desc`, which gives the STRUCTURE only), runs under seeds[k] and
+ * sees series k's slice of the data (off / t / y / has_obs as cssm_fleet_ll_filter).  chol: the lower-triangular factor L of the
+ * proposal's covariance, row-major [n_theta][n_theta] -- one for all chains (chol_per_chain = 0) or one per chain (!= 0, [S][..][..]);
+ * entries above the diagonal must be 0.0, a row of zeros fixes its slot, L = sqrt(delta) I is cssm_fleet_pmmh_run's proposal.  priors:
+ * [n_theta] cssm_prior, one per slot, on the STORED value; NULL = all flat (declared const void*, as every fleet call takes scalar
+ * pointers and handles only; a const cssm_prior* converts implicitly).  ll0 / state0: the chain's current log-likelihood and sampled state ([S], [S][d]);
+ * NULL = -1e99 / zeros, a fresh chain (PMMH.scala:121).  Iteration q of the call is iteration first_iter + q of the chain: a chain
+ * continued with first_iter = the iterations done, theta0 / ll0 / state0 = its last row is the uninterrupted chain bit for bit (accepted
+ * restarts at 0 per call).  iters_per_launch (0 = all) bounds a launch without changing a bit.  Outputs chain-major as
+ * cssm_fleet_pmmh_run: ll[k * n_iters + q], theta[(k * n_iters + q) * n_theta + j], accepted[..], last_state[(k * n_iters + q) * d + c].
+ * diag_out (may be NULL; [S][2]): proposals rejected unfiltered (outside the prior's support) | proposals whose filter had no usable
+ * weight.  With all priors flat and a diagonal L the rows are cssm_fleet_pmmh_run's bit for bit.
+ * Unlike cssm_fleet_pmmh_run, which ends the whole run on a proposal the descriptor path refuses, a proposal that is not filtered is a
+ * REJECTION here and the chain goes on; and a series without records is not refused: it is untouched, its rows read NaN (accepted -1),
+ * rc_out[k] = CSSM_EINVAL_ARG.  Every other series has rc_out[k] = CSSM_OK.
+ * The fleet is only LENT (as to cssm_fleet_if2): device, stream, contract table, N and structure; clouds, clocks, keys, windows and
+ * parameters stay as they were, the call keeps buffers of its own.
+ * Refused before the fleet is looked at (CSSM_EINVAL_ARG unless said): null desc / theta0 / chol / seeds / off / t / y or outputs (ll,
+ * theta, accepted, last_state, rc_out); off[0] != 0; an LGCP descriptor (CSSM_EINVAL_DESC); n_theta other than the descriptor flattens to
+ * (at most CSSM_IF2_MAX_THETA = 81); a chol entry that is not finite or lies above the diagonal and is not 0.0; a NORMAL prior whose b is
+ * not finite and positive or whose a is not finite, a UNIFORM prior with a > b or a NaN bound, an unknown kind; n_iters outside
+ * [1, 1000000]; first_iter + n_iters > 2^31; an LGCP fleet.  After the fleet is looked at (it says how many chains there are): off
+ * decreasing, a descriptor of another structure than the fleet's (CSSM_EINVAL_DESC), a theta0 row whose prior is -inf or NaN (outside
+ * the support), a chol_per_chain factor beyond the first that fails the test above.
+ * Not served (cssm_pmmh_run / _run_batched / _run_speculative keep the flat prior and the isotropic proposal): single handles and
+ * batches, LGCP fleets, covariance updates inside the kernel. */
+#define CSSM_PRIOR_FLAT    0   /* contributes nothing */
+#define CSSM_PRIOR_NORMAL  1   /* on the STORED value: -(z*z)/2.0, z = (theta - a) / b, b > 0 (constants dropped: only differences decide) */
+#define CSSM_PRIOR_UNIFORM 2   /* 0.0 if a <= theta <= b, else -inf */
+typedef struct { int32_t kind; int32_t pad_; double a, b; } cssm_prior;
+int cssm_fleet_pmmh_chains(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, size_t n_theta,
+                           const double* chol, int chol_per_chain, const void* priors, const double* ll0, const double* state0,
+                           uint32_t first_iter, uint32_t n_iters, uint32_t iters_per_launch,
+                           const uint64_t* seeds, const uint64_t* off, const double* t, const double* y, const uint8_t* has_obs,
+                           double* ll, double* theta, int32_t* accepted, double* last_state, uint32_t* diag_out, int* rc_out);
+/* *ms = device time of the launches of the last cssm_fleet_pmmh_chains (HIP events on the fleet's stream); CSSM_ESTATE before the first. */
+int cssm_fleet_pmmh_chains_last_ms(cssm_fleet* f, double* ms);
 /* ---- fixed-lag interpolation of a live fleet (FilterInterpolate as the stream it is: ParticleFilter.interpolate, model/
  * ParticleFilter.scala:281-310 -- one stepInterpolate per observation, every element carrying the paths that survive to that moment;
  * examples/Interpolate.scala: once data resumes behind a gap, the surviving lineages fill it).
