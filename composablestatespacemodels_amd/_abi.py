@@ -44,6 +44,7 @@ CSSM_LGCP_SIM_KEEP_GRID = 1       # cssm_simulate_lgcp: download the grid rows t
 CSSM_STREAM_THIN = 10             # include/cssm_obs_draws.h: the candidates of simLGCP's thinning
 CSSM_STREAM_IF2 = 12              # include/cssm_numerics.h: the perturbation normals of iterated filtering
 IF2_MAX_THETA = 81                # CSSM_IF2_MAX_THETA
+IF2_TILE = 1024                   # CSSM_IF2_TILE: the particles a block of cssm_pf_if2's tile launches owns
 CSSM_PRIOR_FLAT, CSSM_PRIOR_NORMAL, CSSM_PRIOR_UNIFORM = 0, 1, 2   # cssm_prior.kind
 CSSM_FN_EXP_LE0, CSSM_FN_LGAMMA, CSSM_FN_LGAMMA_KP1 = 8, 9, 10   # cssm_contract_eval: the contract functions evaluated per lane
 CSSM_LGCP_PATH_OK, CSSM_LGCP_PATH_NONFINITE, CSSM_LGCP_PATH_TOO_MANY = 0, 1, 2   # a path's status
@@ -157,6 +158,9 @@ SYMBOLS = [
     ("cssm_pf_interpolate", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("cssm_pf_smooth", C.c_int, [_h, _dp, _dp, _u8p, C.c_size_t, C.c_uint32, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _u32p]),
     ("cssm_pf_smooth_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_pf_if2", C.c_int, [_h, _dp, _dp, C.c_size_t, _dp, C.c_double, C.c_uint32, C.c_uint32, C.c_uint64, _dp, _dp, _u8p, C.c_size_t,
+                              _dp, _dp, _dp, _dp, _i32p, _dp, _u32p]),
+    ("cssm_pf_if2_last_ms", C.c_int, [_h, _dp]),
     ("cssm_pf_window", C.c_int, [_h, C.c_uint32]),
     ("cssm_pf_window_depth", C.c_uint32, [_h]),
     ("cssm_pf_step_interpolate", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_double, _dp, _i32p, _u32p, _dp, _dp, _dp, _dp, _dp, _dp]),

@@ -184,6 +184,11 @@ struct cssm_pf : HostModel, CssmLaunchFields {
   cssm_window wring = {0u, 0u, 0u};
   void* win = nullptr;
   void* li = nullptr;
+  // cssm_pf_if2 (cssm_if2.hip): where the flattened vector of the descriptor the handle was created with holds what a component reads
+  // (not built for an LGCP handle, which the call refuses), and the device time of the last call (cssm_pf_if2_last_ms; < 0: none yet)
+  If2Map if2_map;
+  bool if2_map_ok = false;
+  double if2_ms = -1.0;
 };
 
 // begin/end of one profiled launch

@@ -142,6 +142,7 @@ static int create_common(const cssm_model_desc* desc, uint64_t n_global, uint64_
                             // N = 100 000, 34.0 vs 35.4 at 2^20, 336 vs 356 at 2^24); an outlying observation is redone in place
   rc = cssm_build_model(pf, desc, false);
   if (rc == CSSM_OK) { pf->obs_has_scale = desc->leaves[0].has_scale; pf->obs_scale = desc->leaves[0].scale; }
+  if (rc == CSSM_OK && pf->obs_kind != CSSM_OBS_LGCP) pf->if2_map_ok = cssm_if2_map_build(desc, &pf->if2_map) == CSSM_OK;   // (cssm_pf_if2)
   if (rc == CSSM_OK) rc = alloc_handle(pf);
   if (rc != CSSM_OK) { const std::string keep = cssm_last_error(); cssm_pf_destroy(pf); return fail(rc, "%s", keep.c_str()); }
   *out = pf;

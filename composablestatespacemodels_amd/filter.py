@@ -431,6 +431,51 @@ class NativePf:
         _abi.check(self.lib.cssm_pf_smooth_last_ms(self._h, _p(ms)))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
+    def if2(self, t, y, has, rw_sd, cooling: float, iters: int, seed: int, theta0=None, swarm0=None, first_iter: int = 0,
+            want_swarm: bool = False, want_last: bool = False):
+        """cssm_pf_if2 (an EXTENSION: the reference has no likelihood maximiser): one search of iterated filtering with the handle's N
+        particles, from the row ``theta0[n_theta]`` (or the swarm ``swarm0[n_theta, N]`` of an earlier call, continued at ``first_iter``)
+        under ``seed``; ``rw_sd[n_theta]`` the random-walk standard deviations, ``cooling`` the factor they shrink by over 50
+        iterations.  Returns a dict with the keys of one series of ``NativePfFleet.if2``: ``theta_mean[iters, n_theta]``, ``ll[iters]``,
+        ``rc`` (-5: some record left no particle a usable weight; the rows read NaN from that iteration on -- a status, not an
+        exception); with ``want_swarm`` also ``swarm[n_theta, N]``; with ``want_last`` the last iteration's ``ll_t[T]``, ``ess_t[T]``,
+        ``x[d, N]`` and ``anc[N]``.  The handle is only lent: its cloud, clock, key and options are afterwards what they were."""
+        if theta0 is None and swarm0 is None:
+            raise ValueError("theta0 (a starting row) or swarm0 (a whole swarm) is needed")
+        sd = np.ascontiguousarray(rw_sd, dtype=np.float64)
+        if sd.ndim != 1:
+            raise ValueError("rw_sd must be a vector of n_theta standard deviations")
+        nt = int(sd.shape[0])
+        th0 = None if theta0 is None else np.ascontiguousarray(theta0, dtype=np.float64).reshape(nt)
+        sw0 = None if swarm0 is None else np.ascontiguousarray(swarm0, dtype=np.float64).reshape(nt, self.n)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        T = len(t)
+        if len(y) != T:
+            raise ValueError("t and y must have one entry per record")
+        has = _u8(has)
+        iters = int(iters)
+        out = {"theta_mean": np.full((max(iters, 0), nt), np.nan), "ll": np.full(max(iters, 0), np.nan)}
+        swarm = np.zeros((nt, self.n)) if want_swarm else None
+        ll_t, ess_t = (np.zeros(max(T, 1)), np.zeros(max(T, 1), dtype=np.int32)) if want_last else (None, None)
+        x, anc = (np.zeros((self.d, self.n)), np.zeros(self.n, dtype=np.uint32)) if want_last else (None, None)
+        rc = self.lib.cssm_pf_if2(self._h, _p(th0), _p(sw0), nt, _p(sd), float(cooling), int(first_iter), iters, int(seed) & (2**64 - 1),
+                                  _p(t), _p(y), _p(has), T, _p(out["theta_mean"]), _p(out["ll"]), _p(swarm), _p(ll_t), _p(ess_t), _p(x), _p(anc))
+        if rc != _abi.CSSM_ENONFINITE:
+            _abi.check(rc)
+        out["rc"] = int(rc)
+        if want_swarm:
+            out["swarm"] = swarm
+        if want_last:
+            out.update(ll_t=ll_t[:T], ess_t=ess_t[:T], x=x, anc=anc)
+        return out
+
+    def if2_last_ms(self) -> float:
+        """Device time (HIP events) of the launches of the last ``if2``, ms."""
+        ms = np.zeros(1)
+        _abi.check(self.lib.cssm_pf_if2_last_ms(self._h, _p(ms)))
+        return float(ms[0])
+
     def window(self, slices: int):
         """cssm_pf_window: remember the ``slices`` most recent clouds and ancestor arrays on the device (slices x stride x (8 d + 4) bytes)
         for ``step_interpolate``; 0 frees them.  Every call restarts the window."""

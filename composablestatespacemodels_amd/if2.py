@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .filter import NativePfFleet
+from .filter import NativePf, NativePfFleet
 from .model import Parameters, UnparamModel
 from .pmmh import pmmh_fleet_pack
 
@@ -54,3 +54,28 @@ def IF2(unparam: UnparamModel, starts: Sequence[Parameters], datas, n: int, rw_s
         if own:
             fleet.close()
     return If2Result(starts, out)
+
+
+def IF2Single(unparam: UnparamModel, start: Parameters, data, n: int, rw_sd, cooling: float, iters: int, seed: int, device: int = 0,
+              handle: Optional[NativePf] = None, swarm0=None, first_iter: int = 0) -> If2Result:
+    """One search with ``n`` particles on a single handle (``cssm_pf_if2``): the swarm is tiled over many workgroups, so ``n`` is not bound
+    by a fleet's 4096 -- the point estimate a PMMH chain at N = 100 000 should start from.  Arguments as ``IF2``'s, for one search; the
+    result is shaped as one search (S = 1), so ``.parameters(0)`` is the final mean.  ``handle``: a ``NativePf`` of the model's structure
+    and ``n`` particles to lend (its cloud, clock and key stay what they were)."""
+    off, t, y, has = pmmh_fleet_pack(data, 1)
+    theta0 = np.ascontiguousarray(start.flattenParams(), dtype=np.float64)
+    own = handle is None
+    if own:
+        handle = NativePf(unparam.run(start), n, int(seed), device)
+    elif handle.n != int(n):
+        raise ValueError(f"the handle holds {handle.n} particles, the search needs {n}")
+    try:
+        a, b = int(off[0]), int(off[1])
+        one = handle.if2(t[a:b], y[a:b], has[a:b], rw_sd, cooling, iters, seed, theta0=theta0, swarm0=swarm0, first_iter=first_iter,
+                         want_swarm=True)
+    finally:
+        if own:
+            handle.close()
+    out = {"theta_mean": one["theta_mean"][None], "ll": one["ll"][None], "rc": np.asarray([one["rc"]], dtype=np.int32),
+           "swarm": one["swarm"][None]}
+    return If2Result([start], out)

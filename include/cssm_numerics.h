@@ -1251,7 +1251,8 @@ CSSM_HD double cssm_back_uniform(uint64_t seed, uint32_t m, uint32_t s) {
  * EXTENSION (not a restatement of running reference code: the reference has no likelihood maximiser).  IF2 of Ionides, Nguyen,
  * Atchade, Stoev and King (PNAS 2015; `mif2` of the R package pomp) for a fleet: cssm_fleet_if2, one search per series.  Nothing above
  * this line changes and the contract version stays what it is.  This section states one search so that a sequential program written
- * from this header reproduces the device bit for bit (tests/cpp/if2_twin.c is that program).
+ * from this header reproduces the device bit for bit (tests/cpp/if2_twin.c is that program).  cssm_pf_if2 runs the same search for a
+ * cloud of any size, its particles tiled over many workgroups.
  *
  * Parameter vector.  A particle carries the flattened STORED (unconstrained) vector of the model in cssm_desc_flatten order, n_theta
  * slots: per leaf [scale] m0.. c0.. [mu.. | phi.. mu..] sigma...  Component k of a leaf (index idx within it) reads field F from slot

@@ -659,6 +659,39 @@ int cssm_pf_smooth(cssm_pf* pf, const double* t, const double* y, const uint8_t*
  * last cssm_pf_smooth.  CSSM_ESTATE before the first.  The array holds THREE doubles. */
 int cssm_pf_smooth_last_ms(cssm_pf* pf, double* ms3);
 
+/* ---- EXTENSION (the reference has no likelihood maximiser): iterated filtering for ONE swarm of any size the handle holds -- one search
+ * of cssm_fleet_if2 (below), whose swarm ends at CSSM_FLEET_MAX_N particles because a workgroup keeps it.  Here the particles are tiled
+ * over many workgroups (CSSM_IF2_TILE a block), the swarm lives in device memory as theta[2][n_theta][N] beside x[2][d][N], and what needs
+ * a value of the whole cloud is a launch of its own: 5 launches per weighted record, 1 per unweighted one, 3 per iteration (cssm_if2.hip),
+ * all enqueued ahead on the handle's stream with one synchronisation per call.  The arithmetic is the contract's (include/
+ * cssm_numerics.h, "iterated filtering"): bit for bit a one-series cssm_fleet_if2 where that exists, and the sequential twin beyond.
+ *
+ * The semantics are those of one series of cssm_fleet_if2.  Start: theta0[n_theta] or swarm0[n_theta][N] (wins when both are given).
+ * Iteration first_iter + q runs under cssm_pf_run_key(seed, first_iter + q + 1) and cools by cssm_fleet_if2_cooling.  Outputs:
+ * theta_mean[n_iters][n_theta], ll[n_iters]; optional swarm_out[n_theta][N]; optional, of the last iteration: ll_t[T], ess_t[T],
+ * x_out[d][N] (the cloud the last record proposed), anc_out[N].  A record that leaves no particle a usable weight ends the search:
+ * CSSM_ENONFINITE, rows from the failing iteration on read NaN, swarm_out is the swarm that iteration started from, the last-iteration
+ * outputs read NaN / -1 / 0xffffffff.  T = 0 leaves everything untouched: the rows read NaN, CSSM_OK.  A search continued from swarm_out
+ * with first_iter = the iterations done is bit for bit the uninterrupted one.
+ *
+ * The handle is only LENT: its device, stream, contract table, N and the structure of the descriptor it was created with.  Its parameter
+ * values are not read; cloud, ancestors, clock, key, window ring, options and ll / ess are afterwards what they were.  The search keeps
+ * buffers of its own, allocated up front: N (24 n_theta + 16 d + 16) + ceil(N / CSSM_IF2_TILE) (48 + 8 n_theta) bytes and the rows;
+ * CSSM_ENOMEM names the bytes if they do not fit.
+ * Refused before the handle is looked at (CSSM_EINVAL_ARG): null rw_sd, theta_mean or ll; null t / y with T > 0; theta0 and swarm0 both
+ * null; a negative or non-finite rw_sd; n_iters outside [1, 1000000] or first_iter + n_iters beyond 2^31; a cooling fraction outside
+ * (0, 1]; a null handle.  Then: an LGCP handle (CSSM_EINVAL_ARG, by name), a sharded handle (CSSM_ESTATE), a handle whose
+ * CSSM_OPT_RESAMPLER is not systematic (CSSM_ESTATE, naming the option: the contract's search resamples systematically), n_theta other
+ * than the handle's descriptor flattens to (CSSM_EINVAL_ARG).  A refused call leaves a handle that filters as before. */
+#define CSSM_IF2_TILE 1024u
+int cssm_pf_if2(cssm_pf* pf, const double* theta0, const double* swarm0, size_t n_theta,
+                const double* rw_sd, double cooling_fraction_50, uint32_t first_iter, uint32_t n_iters,
+                uint64_t seed, const double* t, const double* y, const uint8_t* has_obs, size_t T,
+                double* theta_mean, double* ll, double* swarm_out, double* ll_t, int32_t* ess_t,
+                double* x_out, uint32_t* anc_out);
+/* *ms = device time of the launches of the last cssm_pf_if2 (HIP events on the handle's stream); CSSM_ESTATE before the first. */
+int cssm_pf_if2_last_ms(cssm_pf* pf, double* ms);
+
 /* ---- fixed-lag interpolation of a live handle: FilterInterpolate as the stream it is (ParticleFilter.interpolate, model/
  * ParticleFilter.scala:281-310 -- one stepInterpolate per observation, every element carrying the paths that survive to that moment;
  * examples/Interpolate.scala: once data resumes behind a gap, the surviving lineages fill it) for ONE cloud of any size the handle
