@@ -11,9 +11,9 @@ from .simulate import LgcpSim, SimulateData, SimulatedPoint, lgcp_events_data, l
 from .streaming import Streaming
 from .smc2 import SMC2, FleetEngine, Smc2State
 from .if2 import IF2, IF2Single, If2Result
-from .pmmh import Prior, pmmh_fleet_chains
+from .pmmh import Prior, pmmh_fleet_chains, pmmh_lgcp_fleet_chains
 from .model import (Data, Model, Parameters, ParamNode, Sde, SdeParameter, TimedObservation,
                     UnparamModel, UnparamSde, logistic, logit)
 
-__all__ = ["_abi", "CssmError", "load_library", "FilterFleet", "ForecastOut", "NativePfFleet", "NativeLgcpFleet", "FilterLgcpFleet", "FilterInitFleet", "lgcp_fleet_data", "Streaming", "SMC2", "Smc2State", "FleetEngine", "IF2", "IF2Single", "If2Result", "Prior", "pmmh_fleet_chains", "SimulateData", "SimulatedPoint", "simulate", "simulate_from", "LgcpSim", "simulate_lgcp", "simulate_lgcp_last_ms", "lgcp_events_data", "ObservationWithState", "ParticleFilter", "Data", "Model", "Parameters", "ParamNode", "Sde",
+__all__ = ["_abi", "CssmError", "load_library", "FilterFleet", "ForecastOut", "NativePfFleet", "NativeLgcpFleet", "FilterLgcpFleet", "FilterInitFleet", "lgcp_fleet_data", "Streaming", "SMC2", "Smc2State", "FleetEngine", "IF2", "IF2Single", "If2Result", "Prior", "pmmh_fleet_chains", "pmmh_lgcp_fleet_chains", "SimulateData", "SimulatedPoint", "simulate", "simulate_from", "LgcpSim", "simulate_lgcp", "simulate_lgcp_last_ms", "lgcp_events_data", "ObservationWithState", "ParticleFilter", "Data", "Model", "Parameters", "ParamNode", "Sde",
            "SdeParameter", "TimedObservation", "UnparamModel", "UnparamSde", "logistic", "logit"]

@@ -262,6 +262,11 @@ SYMBOLS = [
     ("cssm_fleet_pmmh_chains", C.c_int, [_h, _descp, _dp, C.c_size_t, _dp, C.c_int, C.c_void_p, _dp, _dp, C.c_uint32, C.c_uint32, C.c_uint32,
                                          _u64p, _u64p, _dp, _dp, _u8p, _dp, _dp, _i32p, _dp, _u32p, C.POINTER(C.c_int)]),
     ("cssm_fleet_pmmh_chains_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_fleet_pmmh_chains_lgcp", C.c_int, [_h, _descp, _dp, C.c_size_t, _dp, C.c_int, C.c_void_p, _dp, _dp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              _u64p, _u64p, _dp, _dp, _dp, _i32p, _dp, _u32p, C.POINTER(C.c_int)]),
+    ("cssm_fleet_pmmh_chains_lgcp_last_ms", C.c_int, [_h, _dp]),
+    ("cssm_fleet_pmmh_lgcp_pack_record", C.c_int, [_descp, C.c_double, C.c_double, C.c_uint32, _u8p, C.c_size_t, C.POINTER(C.c_size_t), _dp,
+                                                   C.c_size_t, C.POINTER(C.c_size_t)]),
     ("cssm_fleet_window", C.c_int, [_h, C.c_uint32]),
     ("cssm_fleet_window_depth", C.c_uint32, [_h, C.c_uint32]),
     ("cssm_fleet_step_interpolate", C.c_int, [_h, _u8p, _dp, _dp, _u8p, _u32p, C.c_uint32, C.c_double, _dp, _i32p, _u32p, _dp, _dp, _dp, _dp, _dp, _dp,

@@ -34,6 +34,7 @@
 #include "cssm_fleet_smooth.hip.h"
 #include "cssm_fleet_if2.hip.h"
 #include "cssm_fleet_pmmh.hip.h"
+#include "cssm_fleet_pmmh_lgcp.hip.h"
 #include "cssm_simulate.hip.h"
 #include "cssm_simulate_plan.h"
 
@@ -127,6 +128,7 @@ struct cssm_fleet {
   int bs_staging = 0;                   // CSSM_OPT_SMOOTH_STAGING: 0 = the gathered means in LDS where they fit, 1 = never (through L2)
   double ms_if2 = -1.0;                 // cssm_fleet_if2: the device time of the last call's launches (cssm_fleet_if2_last_ms)
   double ms_pmmh_chains = -1.0;         // cssm_fleet_pmmh_chains: the device time of the last call's launches (cssm_fleet_pmmh_chains_last_ms)
+  double ms_pmmh_lgcp = -1.0;           // cssm_fleet_pmmh_chains_lgcp: ... (cssm_fleet_pmmh_chains_lgcp_last_ms)
   // the window of cssm_fleet_step_interpolate: per series a ring of win_slices slots, each a cloud and the ancestors that resampled it
   // ([S][slices][d][n] doubles, then [S][slices][n] uint32).  Per series on the host: whether the window is continuous (the cloud the
   // fleet holds is the one its newest slot holds), the newest slot, the records remembered behind the base slice; per slot F at its time
@@ -2185,16 +2187,69 @@ extern "C" int cssm_fleet_if2_last_ms(cssm_fleet* f, double* ms) {
 // Parameters.scala:111-123) -- S whole chains, one workgroup each, every iteration and record of a chain inside k_fleet_pmmh
 // (cssm_fleet_pmmh.hip).  The arithmetic is the contract's (include/cssm_numerics.h, "PMMH chains on the device").  The fleet lends its
 // device, stream, contract table, N and structure; the chains, the states and the records live in buffers of the call.
-static int fleet_pmmh_chol_check(const double* L, size_t nt, size_t which) {
+static int fleet_pmmh_chol_check(const char* call, const double* L, size_t nt, size_t which) {
   for (size_t i = 0; i < nt; ++i)
     for (size_t j = 0; j < nt; ++j) {
       const double v = L[i * nt + j];
-      if (!std::isfinite(v)) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: chol %zu [%zu][%zu] is not finite", which, i, j);
+      if (!std::isfinite(v)) return fail(CSSM_EINVAL_ARG, "%s: chol %zu [%zu][%zu] is not finite", call, which, i, j);
       if (j > i && v != 0.0)
-        return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: chol %zu [%zu][%zu] = %g lies above the diagonal (a lower-triangular factor, row-major)",
-                    which, i, j, v);
+        return fail(CSSM_EINVAL_ARG, "%s: chol %zu [%zu][%zu] = %g lies above the diagonal (a lower-triangular factor, row-major)", call, which, i, j, v);
     }
   return CSSM_OK;
+}
+// the n_theta priors as the kernel reads them (null: all flat), or the refusal of one
+static int fleet_pmmh_priors(const char* call, const cssm_prior* priors, size_t nt, std::vector<cssm_prior>& pri) {
+  pri.resize(nt);
+  for (size_t j = 0; j < nt; ++j) {
+    cssm_prior p{};
+    if (priors) p = priors[j];
+    p.pad_ = 0;
+    if (p.kind == CSSM_PRIOR_FLAT) { p.a = 0.0; p.b = 0.0; }
+    else if (p.kind == CSSM_PRIOR_NORMAL) {
+      if (!std::isfinite(p.a) || !std::isfinite(p.b) || !(p.b > 0.0))
+        return fail(CSSM_EINVAL_ARG, "%s: priors[%zu]: a NORMAL prior needs a finite mean and a finite sd > 0 (got %g, %g)", call, j, p.a, p.b);
+    } else if (p.kind == CSSM_PRIOR_UNIFORM) {
+      if (!(p.a <= p.b)) return fail(CSSM_EINVAL_ARG, "%s: priors[%zu]: a UNIFORM prior needs a <= b (got %g, %g)", call, j, p.a, p.b);
+    } else {
+      return fail(CSSM_EINVAL_ARG, "%s: priors[%zu]: unknown kind %d", call, j, (int)p.kind);
+    }
+    pri[j] = p;
+  }
+  return CSSM_OK;
+}
+// the chains as they start, [S] rows of cur_ll | lp_cur | cur | cur_state, or the refusal of a theta0 row outside the prior's support
+static int fleet_pmmh_start(const char* call, uint32_t S, size_t nt, int d, const std::vector<cssm_prior>& pri, const double* theta0, const double* ll0,
+                            const double* state0, std::vector<double>& chain) {
+  const size_t CR = CSSM_FLEET_PMMH_ROW(nt, d);
+  chain.assign((size_t)S * CR, 0.0);
+  for (uint32_t k = 0; k < S; ++k) {
+    double* row = chain.data() + (size_t)k * CR;
+    const double* th = theta0 + (size_t)k * nt;
+    double lp = 0.0;
+    for (size_t j = 0; j < nt; ++j)
+      if (pri[j].kind != CSSM_PRIOR_FLAT) lp = lp + cssm_prior_term(pri[j].kind, pri[j].a, pri[j].b, th[j]);
+    if (!(lp > -cssm_inf())) return fail(CSSM_EINVAL_ARG, "%s: chain %u: theta0 lies outside the prior's support (its log-prior is %g)", call, k, lp);
+    row[0] = ll0 ? ll0[k] : -1e99;
+    row[1] = lp;
+    memcpy(row + 2, th, nt * 8u);
+    for (int c = 0; c < d; ++c) row[2 + nt + c] = state0 ? state0[(size_t)k * d + c] : 0.0;
+  }
+  return CSSM_OK;
+}
+// what a chains call returns per chain: its status and counters; a chain without records ran no block, its rows read NaN
+static void fleet_pmmh_finish(uint32_t S, size_t nt, int d, uint32_t n_iters, const uint64_t* off, const std::vector<uint32_t>& h_count, double* ll,
+                              double* theta, int32_t* accepted, double* last_state, uint32_t* diag_out, int* rc_out) {
+  for (uint32_t k = 0; k < S; ++k) {
+    const bool ran = off[k + 1] > off[k];
+    rc_out[k] = ran ? CSSM_OK : CSSM_EINVAL_ARG;
+    if (diag_out) { diag_out[2u * k] = ran ? h_count[4u * k + 1u] : 0u; diag_out[2u * k + 1u] = ran ? h_count[4u * k + 2u] : 0u; }
+    if (ran) continue;
+    const size_t r0 = (size_t)k * n_iters;
+    std::fill(ll + r0, ll + r0 + n_iters, cssm_nan());
+    std::fill(theta + r0 * nt, theta + (r0 + n_iters) * nt, cssm_nan());
+    std::fill(last_state + r0 * d, last_state + (r0 + n_iters) * d, cssm_nan());
+    std::fill(accepted + r0, accepted + r0 + n_iters, -1);
+  }
 }
 extern "C" int cssm_fleet_pmmh_chains(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, size_t n_theta, const double* chol,
                                       int chol_per_chain, const void* priors_, const double* ll0, const double* state0, uint32_t first_iter,
@@ -2217,23 +2272,9 @@ extern "C" int cssm_fleet_pmmh_chains(cssm_fleet* f, const cssm_model_desc* desc
   if ((size_t)map.n_theta != n_theta)
     return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: n_theta = %zu, the descriptor flattens to %d (cssm_desc_flatten)", n_theta, (int)map.n_theta);
   const size_t nt = n_theta;
-  if ((rc = fleet_pmmh_chol_check(chol, nt, 0))) return rc;
-  std::vector<cssm_prior> pri(nt);
-  for (size_t j = 0; j < nt; ++j) {
-    cssm_prior p{};
-    if (priors) p = priors[j];
-    p.pad_ = 0;
-    if (p.kind == CSSM_PRIOR_FLAT) { p.a = 0.0; p.b = 0.0; }
-    else if (p.kind == CSSM_PRIOR_NORMAL) {
-      if (!std::isfinite(p.a) || !std::isfinite(p.b) || !(p.b > 0.0))
-        return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: priors[%zu]: a NORMAL prior needs a finite mean and a finite sd > 0 (got %g, %g)", j, p.a, p.b);
-    } else if (p.kind == CSSM_PRIOR_UNIFORM) {
-      if (!(p.a <= p.b)) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: priors[%zu]: a UNIFORM prior needs a <= b (got %g, %g)", j, p.a, p.b);
-    } else {
-      return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: priors[%zu]: unknown kind %d", j, (int)p.kind);
-    }
-    pri[j] = p;
-  }
+  if ((rc = fleet_pmmh_chol_check("cssm_fleet_pmmh_chains", chol, nt, 0))) return rc;
+  std::vector<cssm_prior> pri;
+  if ((rc = fleet_pmmh_priors("cssm_fleet_pmmh_chains", priors, nt, pri))) return rc;
   if (n_iters < 1u || n_iters > 1000000u) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: n_iters must be in [1, 1000000] (got %u)", n_iters);
   if ((uint64_t)first_iter + n_iters > (1ull << 31)) return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: first_iter + n_iters must not exceed 2^31");
   FLEET_LGCP_REFUSE(f, "cssm_fleet_pmmh_chains", FLEET_PMMH_SERVED);
@@ -2250,23 +2291,9 @@ extern "C" int cssm_fleet_pmmh_chains(cssm_fleet* f, const cssm_model_desc* desc
     if (rc) { const std::string keep = cssm_last_error(); return fail(rc, "cssm_fleet_pmmh_chains: desc is not of the fleet's model structure (%s)", keep.c_str()); }
   }
   for (uint32_t k = 1; k < S && chol_per_chain; ++k)
-    if ((rc = fleet_pmmh_chol_check(chol + (size_t)k * nt * nt, nt, k))) return rc;
-  // the chains as they start: cur_ll | lp_cur | cur | cur_state
-  const size_t CR = CSSM_FLEET_PMMH_ROW(nt, d);
-  std::vector<double> chain((size_t)S * CR);
-  for (uint32_t k = 0; k < S; ++k) {
-    double* row = chain.data() + (size_t)k * CR;
-    const double* th = theta0 + (size_t)k * nt;
-    double lp = 0.0;
-    for (size_t j = 0; j < nt; ++j)
-      if (pri[j].kind != CSSM_PRIOR_FLAT) lp = lp + cssm_prior_term(pri[j].kind, pri[j].a, pri[j].b, th[j]);
-    if (!(lp > -cssm_inf()))
-      return fail(CSSM_EINVAL_ARG, "cssm_fleet_pmmh_chains: chain %u: theta0 lies outside the prior's support (its log-prior is %g)", k, lp);
-    row[0] = ll0 ? ll0[k] : -1e99;
-    row[1] = lp;
-    memcpy(row + 2, th, nt * 8u);
-    for (int c = 0; c < d; ++c) row[2 + nt + c] = state0 ? state0[(size_t)k * d + c] : 0.0;
-  }
+    if ((rc = fleet_pmmh_chol_check("cssm_fleet_pmmh_chains", chol + (size_t)k * nt * nt, nt, k))) return rc;
+  std::vector<double> chain;
+  if ((rc = fleet_pmmh_start("cssm_fleet_pmmh_chains", S, nt, d, pri, theta0, ll0, state0, chain))) return rc;
   HIP_TRY(hipSetDevice(f->device));
   const size_t R = (size_t)off[S], RB = CSSM_FLEET_IF2_REC_BYTES(d);
   const size_t n_chol = chol_per_chain ? (size_t)S : (size_t)1;
@@ -2327,17 +2354,7 @@ extern "C" int cssm_fleet_pmmh_chains(cssm_fleet* f, const cssm_model_desc* desc
   HIP_TRY(hipStreamSynchronize(f->stream));
   float ms = 0.f;
   f->ms_pmmh_chains = (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : -1.0;
-  for (uint32_t k = 0; k < S; ++k) {
-    const bool ran = off[k + 1] > off[k];
-    rc_out[k] = ran ? CSSM_OK : CSSM_EINVAL_ARG;
-    if (diag_out) { diag_out[2u * k] = ran ? h_count[4u * k + 1u] : 0u; diag_out[2u * k + 1u] = ran ? h_count[4u * k + 2u] : 0u; }
-    if (ran) continue;                                           // no records: no block ran, its rows read NaN
-    const size_t r0 = (size_t)k * n_iters;
-    std::fill(ll + r0, ll + r0 + n_iters, cssm_nan());
-    std::fill(theta + r0 * nt, theta + (r0 + n_iters) * nt, cssm_nan());
-    std::fill(last_state + r0 * d, last_state + (r0 + n_iters) * d, cssm_nan());
-    std::fill(accepted + r0, accepted + r0 + n_iters, -1);
-  }
+  fleet_pmmh_finish(S, nt, d, n_iters, off, h_count, ll, theta, accepted, last_state, diag_out, rc_out);
   return CSSM_OK;
 }
 
@@ -2345,6 +2362,200 @@ extern "C" int cssm_fleet_pmmh_chains_last_ms(cssm_fleet* f, double* ms) {
   if (!f || !ms) return fail(CSSM_EINVAL_ARG, "null argument");
   if (f->ms_pmmh_chains < 0.0) return fail(CSSM_ESTATE, "no chains have run on this fleet (cssm_fleet_pmmh_chains first)");
   *ms = f->ms_pmmh_chains;
+  return CSSM_OK;
+}
+
+// ParticleMetropolisHastings over FilterLgcp (model/ParticleFilter.scala:169-227) -- cssm_fleet_pmmh_chains for an LGCP fleet, asked for by
+// name as cssm_fleet_create_lgcp is: S whole chains, one workgroup each, every iteration and event of a chain inside k_fleet_pmmh_lgcp
+// (cssm_fleet_pmmh_lgcp.hip).  The arithmetic is the contract's (include/cssm_numerics.h, "PMMH chains on the device: LGCP").  The fleet
+// lends its device, stream, contract table, N and structure; the chains, the states, the records and the sub-step table live in buffers
+// of the call.
+//
+// The record of the event at t behind t_prev that does not depend on the parameters: cssm_build_rec's n_sub, dt and F(t), and the rows of
+// cssm_build_fsub_table appended to `tab` (fsub_off counts from `tab_base` doubles before it), as fleet_pack_rec_lgcp takes them.
+static int fleet_pmmh_lgcp_pack(const HostModel& m, double t_prev, double t, uint32_t step, unsigned char* dst, std::vector<double>& tab, size_t tab_base) {
+  StepRec r;
+  cssm_build_rec(&m, t_prev, t, 0.0, 1, step, &r);
+  const int rc = cssm_build_fsub_table(&m, &r, 0, 1, tab);
+  if (rc) return rc;
+  FleetPmmhLgcpRec h;
+  h.dt = r.dt; h.n_sub = r.n_sub; h.step = r.step; h.fsub_off = (uint32_t)(tab_base + r.fsub_off); h.pad_ = 0u;
+  memcpy(dst, &h, sizeof h);
+  memcpy(dst + sizeof h, r.fco, (size_t)m.d * 8u);
+  return CSSM_OK;
+}
+#define FLEET_PMMH_LGCP "cssm_fleet_pmmh_chains_lgcp"
+extern "C" int cssm_fleet_pmmh_chains_lgcp(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, size_t n_theta, const double* chol,
+                                           int chol_per_chain, const void* priors_, const double* ll0, const double* state0, uint32_t first_iter,
+                                           uint32_t n_iters, uint32_t iters_per_launch, const uint64_t* seeds, const uint64_t* off, const double* t,
+                                           double* ll, double* theta, int32_t* accepted, double* last_state, uint32_t* diag_out, int* rc_out) {
+  if (!desc || !theta0 || !chol || !seeds || !off) return fail(CSSM_EINVAL_ARG, FLEET_PMMH_LGCP ": null argument (desc, theta0, chol, seeds, off)");
+  const cssm_prior* priors = static_cast<const cssm_prior*>(priors_);
+  if (!ll || !theta || !accepted || !last_state || !rc_out)
+    return fail(CSSM_EINVAL_ARG, FLEET_PMMH_LGCP ": null output (ll, theta, accepted, last_state, rc_out)");
+  if (off[0] != 0) return fail(CSSM_EINVAL_ARG, "off[0] must be 0");
+  if (!t) return fail(CSSM_EINVAL_ARG, "null data");
+  HostModel probe;
+  int rc = cssm_build_model(&probe, desc, false);
+  if (rc) return rc;
+  if (probe.obs_kind != CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_DESC, FLEET_PMMH_LGCP " runs chains over LGCP event streams (obs_kind %d given): cssm_fleet_pmmh_chains serves every other "
+                                  "observation model", probe.obs_kind);
+  If2Map map;
+  if ((rc = cssm_if2_map_build(desc, &map))) return rc;
+  if ((size_t)map.n_theta != n_theta)
+    return fail(CSSM_EINVAL_ARG, FLEET_PMMH_LGCP ": n_theta = %zu, the descriptor flattens to %d (cssm_desc_flatten)", n_theta, (int)map.n_theta);
+  const size_t nt = n_theta;
+  if ((rc = fleet_pmmh_chol_check(FLEET_PMMH_LGCP, chol, nt, 0))) return rc;
+  std::vector<cssm_prior> pri;
+  if ((rc = fleet_pmmh_priors(FLEET_PMMH_LGCP, priors, nt, pri))) return rc;
+  if (n_iters < 1u || n_iters > 1000000u) return fail(CSSM_EINVAL_ARG, FLEET_PMMH_LGCP ": n_iters must be in [1, 1000000] (got %u)", n_iters);
+  if ((uint64_t)first_iter + n_iters > (1ull << 31)) return fail(CSSM_EINVAL_ARG, FLEET_PMMH_LGCP ": first_iter + n_iters must not exceed 2^31");
+  if (!f) return fail(CSSM_EINVAL_ARG, "null fleet");
+  if (!f->lgcp)
+    return fail(CSSM_EINVAL_ARG, FLEET_PMMH_LGCP ": the fleet was not made by cssm_fleet_create_lgcp; cssm_fleet_pmmh_chains runs the chains of every "
+                                 "other fleet");
+  const uint32_t S = f->S, n = f->n;
+  const int d = f->d;
+  for (uint32_t k = 0; k < S; ++k) {
+    if ((rc = fleet_off_step("off", off, k))) return rc;
+    if (off[k + 1] - off[k] > 0xfffffffeull) return fail(CSSM_EINVAL_ARG, "series %u: too many records", k);
+  }
+  {   // the structure, the precision with it, must be the fleet's
+    HostModel same = f->base;
+    rc = cssm_build_model(&same, desc, true);
+    if (rc) { const std::string keep = cssm_last_error(); return fail(rc, FLEET_PMMH_LGCP ": desc is not of the fleet's model structure (%s)", keep.c_str()); }
+  }
+  for (uint32_t k = 1; k < S && chol_per_chain; ++k)
+    if ((rc = fleet_pmmh_chol_check(FLEET_PMMH_LGCP, chol + (size_t)k * nt * nt, nt, k))) return rc;
+  std::vector<double> chain;
+  if ((rc = fleet_pmmh_start(FLEET_PMMH_LGCP, S, nt, d, pri, theta0, ll0, state0, chain))) return rc;
+  HIP_TRY(hipSetDevice(f->device));
+  const size_t R = (size_t)off[S], RB = CSSM_FLEET_PMMH_LGCP_REC_BYTES(d);
+  const size_t n_chol = chol_per_chain ? (size_t)S : (size_t)1;
+  auto t_min = [&](size_t a, size_t b) {                        // data.minBy(_.t).t: where a fresh series' first increment starts
+    double m = t[a];
+    for (size_t s = a + 1; s < b; ++s) m = (t[s] < m) ? t[s] : m;
+    return m;
+  };
+  // (f depends on time) where chain k's rows start in the call's sub-step table (doubles): theta-independent, uploaded once
+  std::vector<size_t> toff((size_t)S + 1u, 0);
+  if (f->base.lgcp_tdep) {
+    fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+      for (size_t k = lo; k < hi; ++k) {
+        const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+        if (b > a) toff[k + 1] = fleet_lgcp_rows(f->base, t_min(a, b), t + a, b - a);
+      }
+    });
+    for (uint32_t k = 0; k < S; ++k) toff[k + 1] += toff[k];
+    if ((rc = fleet_lgcp_table_fits(toff[S]))) return rc;
+  }
+  // staged upload: offsets | seeds | chol | priors | chains | records | sub-step table
+  const size_t o_seeds = ((size_t)S + 1u) * 8u, o_chol = o_seeds + (size_t)S * 8u, o_pri = o_chol + n_chol * nt * nt * 8u,
+               o_chain = o_pri + nt * sizeof(cssm_prior), o_recs = o_chain + chain.size() * 8u, o_fsub = o_recs + fleet_pad8(R * RB);
+  std::vector<unsigned char> stage(o_fsub + toff[S] * 8u);
+  memcpy(stage.data(), off, ((size_t)S + 1u) * 8u);
+  memcpy(stage.data() + o_seeds, seeds, (size_t)S * 8u);
+  memcpy(stage.data() + o_chol, chol, n_chol * nt * nt * 8u);
+  memcpy(stage.data() + o_pri, pri.data(), nt * sizeof(cssm_prior));
+  memcpy(stage.data() + o_chain, chain.data(), chain.size() * 8u);
+  std::atomic<int> pack_rc{CSSM_OK};
+  fleet_parallel(S, R, [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const size_t a = (size_t)off[k], b = (size_t)off[k + 1];
+      if (b == a) continue;
+      std::vector<double> tab;
+      double tp = t_min(a, b);
+      for (size_t s = a; s < b; ++s) {
+        const int prc = fleet_pmmh_lgcp_pack(f->base, tp, t[s], (uint32_t)(s - a), stage.data() + o_recs + s * RB, tab, toff[k]);
+        if (prc) pack_rc = prc;
+        tp = t[s];
+      }
+      if (tab.size() != toff[k + 1] - toff[k]) pack_rc = CSSM_ENOMEM;
+      else if (!tab.empty()) memcpy(stage.data() + o_fsub + toff[k] * 8u, tab.data(), tab.size() * 8u);
+    }
+  });
+  if (pack_rc) return fail(pack_rc, FLEET_PMMH_LGCP ": the sub-step table of the call could not be built");
+  CssmTemps tmp;
+  unsigned char* d_stage = nullptr;
+  double *d_x = nullptr, *d_ll = nullptr, *d_theta = nullptr, *d_last = nullptr;
+  int32_t* d_acc = nullptr; uint32_t* d_count = nullptr;
+  const size_t rows = (size_t)S * n_iters;
+  HIP_ALLOC(tmp, d_stage, stage.size());
+  HIP_ALLOC(tmp, d_x, (size_t)S * 2u * d * n * 8u);
+  HIP_ALLOC(tmp, d_ll, rows * 8u);
+  HIP_ALLOC(tmp, d_theta, rows * nt * 8u);
+  HIP_ALLOC(tmp, d_last, rows * d * 8u);
+  HIP_ALLOC(tmp, d_acc, rows * 4u);
+  HIP_ALLOC(tmp, d_count, (size_t)S * 16u);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIP_TRY(tmp.event(e0)); HIP_TRY(tmp.event(e1));
+  HIP_TRY(hipMemcpyAsync(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));   // (stage is pageable)
+  HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)S * 16u, f->stream));
+  FleetPmmhLgcpLaunch l{};
+  l.args.n = n; l.args.n_theta = (uint32_t)nt; l.args.n_iters = n_iters; l.args.first_iter = first_iter;
+  l.args.chol_stride = chol_per_chain ? (uint32_t)(nt * nt) : 0u;
+  l.args.delta = std::pow(10.0, -f->base.precision);            // cssm_build_rec's expression: the sub-step of every record with n_sub > 0
+  l.args.x = d_x; l.args.chain = reinterpret_cast<double*>(d_stage + o_chain); l.args.count = d_count;
+  l.args.off = reinterpret_cast<const unsigned long long*>(d_stage);
+  l.args.seeds = reinterpret_cast<const unsigned long long*>(d_stage + o_seeds);
+  l.args.chol = reinterpret_cast<const double*>(d_stage + o_chol);
+  l.args.priors = reinterpret_cast<const cssm_prior*>(d_stage + o_pri);
+  l.args.recs = d_stage + o_recs;
+  l.args.fsub = f->base.lgcp_tdep ? reinterpret_cast<const double*>(d_stage + o_fsub) : nullptr;   // (otherwise null: f is every record's own)
+  l.args.ll = d_ll; l.args.theta = d_theta; l.args.accepted = d_acc; l.args.last = d_last;
+  l.args.logtab = f->logtab.at<const double>();
+  l.args.mk = f->base.mk; l.args.map = map;
+  l.n_series = S; l.d = d; l.threads = f->threads; l.lds = f->lds; l.stream = f->stream;
+  const uint32_t per = (iters_per_launch == 0u || iters_per_launch > n_iters) ? n_iters : iters_per_launch;
+  HIP_TRY(hipEventRecord(e0, f->stream));
+  for (uint32_t it0 = 0; it0 < n_iters && R; it0 += per) {      // (the result does not depend on the split: a launch leaves the chains in HBM)
+    l.args.it0 = it0; l.args.it1 = std::min(n_iters, it0 + per);
+    const int hrc = cssm_fleet_pmmh_lgcp_launch(l);
+    if (hrc) return fail(CSSM_EHIP, "k_fleet_pmmh_lgcp: %s", hipGetErrorString((hipError_t)hrc));
+  }
+  HIP_TRY(hipEventRecord(e1, f->stream));
+  std::vector<uint32_t> h_count((size_t)S * 4u);
+  HIP_TRY(hipMemcpyAsync(ll, d_ll, rows * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(theta, d_theta, rows * nt * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(last_state, d_last, rows * d * 8u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(accepted, d_acc, rows * 4u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(h_count.data(), d_count, (size_t)S * 16u, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  float ms = 0.f;
+  f->ms_pmmh_lgcp = (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : -1.0;
+  fleet_pmmh_finish(S, nt, d, n_iters, off, h_count, ll, theta, accepted, last_state, diag_out, rc_out);
+  return CSSM_OK;
+}
+
+extern "C" int cssm_fleet_pmmh_chains_lgcp_last_ms(cssm_fleet* f, double* ms) {
+  if (!f || !ms) return fail(CSSM_EINVAL_ARG, "null argument");
+  if (f->ms_pmmh_lgcp < 0.0) return fail(CSSM_ESTATE, "no chains have run on this fleet (" FLEET_PMMH_LGCP " first)");
+  *ms = f->ms_pmmh_lgcp;
+  return CSSM_OK;
+}
+
+// The theta-independent record of one event as cssm_fleet_pmmh_chains_lgcp uploads it, and the rows of the sub-step table it brings
+// (fsub_off = 0: the table is this event's own).  No device.
+extern "C" int cssm_fleet_pmmh_lgcp_pack_record(const cssm_model_desc* desc, double t_prev, double t, uint32_t step, unsigned char* out, size_t cap,
+                                                size_t* bytes, double* fsub_out, size_t fsub_cap, size_t* fsub_count) {
+  if (!out || !bytes || !fsub_count) return fail(CSSM_EINVAL_ARG, "null argument");
+  HostModel m;
+  const int rc = cssm_build_model(&m, desc, false);
+  if (rc) return rc;
+  if (m.obs_kind != CSSM_OBS_LGCP)
+    return fail(CSSM_EINVAL_DESC, "cssm_fleet_pmmh_lgcp_pack_record packs LGCP events (obs_kind %d given)", m.obs_kind);
+  m.n_global = 1; m.seed = 0;                                   // (the uniform and sampleOne's slot are not part of this record)
+  *bytes = CSSM_FLEET_PMMH_LGCP_REC_BYTES(m.d);
+  *fsub_count = 0;
+  if (cap < *bytes) return fail(CSSM_EINVAL_ARG, "record of %zu bytes, room for %zu", *bytes, cap);
+  std::vector<double> tab;
+  const int prc = fleet_pmmh_lgcp_pack(m, t_prev, t, step, out, tab, 0);
+  if (prc) return prc;
+  *fsub_count = tab.size();
+  if (tab.size() > fsub_cap || (!tab.empty() && !fsub_out)) return fail(CSSM_EINVAL_ARG, "sub-step table of %zu coefficients, room for %zu", tab.size(), fsub_cap);
+  if (!tab.empty()) memcpy(fsub_out, tab.data(), tab.size() * 8u);
   return CSSM_OK;
 }
 

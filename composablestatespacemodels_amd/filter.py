@@ -992,6 +992,15 @@ class NativePfFleet:
         flat) or ``n_theta`` ``_abi.Prior`` entries (``pmmh.priors_for``); ``first_iter`` / ``ll0[S]`` / ``state0[S, d]`` continue chains.
         Returns ``(ll[S, iters], theta[S, iters, n_theta], accepted[S, iters], last_state[S, iters, d], diag[S, 2], rc[S])``.  The fleet's
         clouds, clocks, keys and parameters are not touched."""
+        def data():
+            return self._record_inputs(off, t, y, has)[1:]
+        return self._chains_call(self.lib.cssm_fleet_pmmh_chains, desc, theta0, chol, seeds, iters, priors, first_iter, ll0, state0,
+                                 iters_per_launch, off, data)
+
+    def _chains_call(self, call, desc, theta0, chol, seeds, iters, priors, first_iter, ll0, state0, iters_per_launch, off, data):
+        """What ``pmmh_chains`` and ``NativeLgcpFleet.pmmh_chains_lgcp`` share: the chains' inputs checked and laid out, ``call`` with
+        ``off`` and the arrays ``data()`` returns (the packed records, checked, as that call takes them) between them and the outputs, and
+        the six arrays they return."""
         nt = self.n_theta
         theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
         if theta0.shape != (self.S, nt):
@@ -1009,14 +1018,14 @@ class NativePfFleet:
             raise ValueError("one seed per chain")
         l0 = None if ll0 is None else np.ascontiguousarray(ll0, dtype=np.float64).reshape(self.S)
         s0 = None if state0 is None else np.ascontiguousarray(state0, dtype=np.float64).reshape(self.S, self.d)
-        R, t, y, has = self._record_inputs(off, t, y, has)
+        arrays = data()
         iters = int(iters)
         rows = max(iters, 0)
         ll, th, last = np.zeros((self.S, rows)), np.zeros((self.S, rows, nt)), np.zeros((self.S, rows, self.d))
         acc, diag, rc = np.zeros((self.S, rows), dtype=np.int32), np.zeros((self.S, 2), dtype=np.uint32), np.zeros(self.S, dtype=np.int32)
-        _abi.check(self.lib.cssm_fleet_pmmh_chains(self._h, desc.ptr(), _p(theta0), nt, _p(chol), int(chol.ndim == 3), pri, _p(l0), _p(s0),
-                                                   int(first_iter), iters, int(iters_per_launch), _p(keys), _p(off), _p(t), _p(y), _p(has), _p(ll),
-                                                   _p(th), _p(acc), _p(last), _p(diag), _p(rc)))
+        _abi.check(call(self._h, desc.ptr(), _p(theta0), nt, _p(chol), int(chol.ndim == 3), pri, _p(l0), _p(s0), int(first_iter), iters,
+                        int(iters_per_launch), _p(keys), _p(off), *[_p(a) for a in arrays], _p(ll), _p(th), _p(acc), _p(last), _p(diag),
+                        _p(rc)))
         return ll, th, acc, last, diag, rc
 
     def pmmh_chains_last_ms(self) -> float:
@@ -1368,8 +1377,8 @@ class NativePfFleet:
 class NativeLgcpFleet(NativePfFleet):
     """``cssm_fleet*`` made by ``cssm_fleet_create_lgcp``: S event streams of a log-Gaussian Cox process filtered per launch, each as
     ``FilterLgcp(model, resample, precision)`` filters it on a handle of its own.  Every record is an event: ``y`` and ``has`` are
-    ignored.  The calls an LGCP fleet does not serve (intervals and forecasts per record, interpolation, simulation, PMMH) raise with
-    the library's refusal."""
+    ignored.  The calls an LGCP fleet does not serve (intervals and forecasts per record, interpolation, simulation, ``pmmh_run`` and
+    ``pmmh_chains``) raise with the library's refusal; ``pmmh_chains_lgcp`` runs whole PMMH chains over its event streams."""
 
     _CREATE = "cssm_fleet_create_lgcp"
 
@@ -1390,6 +1399,26 @@ class NativeLgcpFleet(NativePfFleet):
             t = np.asarray(tr, dtype=np.float64).ravel()
             return t, np.ones(len(t)), None
         return NativePfFleet.pack([triple(tr) for tr in datas], allow_empty)
+
+    def pmmh_chains_lgcp(self, desc, theta0, chol, off, t, seeds, iters, priors=None, first_iter: int = 0, ll0=None, state0=None,
+                         iters_per_launch: int = 0):
+        """cssm_fleet_pmmh_chains_lgcp: ``NativePfFleet.pmmh_chains`` for event streams -- whole Metropolis chains on the device, a chain
+        per stream from the rows of ``theta0[S, n_theta]`` under ``seeds``, on the ``off`` and ``t`` that ``pack`` made (every record is
+        an event: no ``y``, no ``has``; ``allow_empty``: a stream without events is left alone, its rows read NaN).  ``desc``: an LGCP
+        descriptor of the fleet's structure and precision.  ``chol``, ``priors``, ``first_iter`` / ``ll0`` / ``state0`` and
+        ``iters_per_launch`` (0 = all iterations in one launch) as there.  Returns ``(ll[S, iters], theta[S, iters, n_theta],
+        accepted[S, iters], last_state[S, iters, d], diag[S, 2], rc[S])``.  The fleet's clouds, clocks, keys, parameters and predicted
+        levels are not touched."""
+        def data():
+            R = int(off[-1]) if isinstance(off, np.ndarray) and off.ndim == 1 and len(off) else 0
+            self._check_packed(off, t, np.zeros(R), np.zeros(R, dtype=np.uint8))
+            return (t if R else np.zeros(1),)
+        return self._chains_call(self.lib.cssm_fleet_pmmh_chains_lgcp, desc, theta0, chol, seeds, iters, priors, first_iter, ll0, state0,
+                                 iters_per_launch, off, data)
+
+    def pmmh_chains_lgcp_last_ms(self) -> float:
+        """Device time (HIP events) of the launches of the last ``pmmh_chains_lgcp``, ms."""
+        return self._ms(self.lib.cssm_fleet_pmmh_chains_lgcp_last_ms, 1)[0]
 
 
 class _PfView(NativePf):

@@ -13,6 +13,8 @@ work is one native filter run.  Two entry points:
 * ``pmmh_fleet_chains`` -- whole chains on the device (``cssm_fleet_pmmh_chains``), a chain per series of a fleet, with the reference's
   ``prior`` argument (``Prior``, ``priors_for``) and its tuned proposal ``Parameters.perturbMvn(chol)`` (``covariance``,
   ``chol_from_pilot``; ``perturbMvn`` / ``perturbMvnEigen`` are the same proposals for the generic loop above).
+* ``pmmh_lgcp_fleet_chains`` -- the same for log-Gaussian Cox processes (``cssm_fleet_pmmh_chains_lgcp``): a chain per event stream of
+  an LGCP fleet.
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ from typing import Callable, Iterator, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .filter import NativePf, NativePfFleet, Resampling
+from .filter import NativeLgcpFleet, NativePf, NativePfFleet, Resampling
 from .model import Parameters, UnparamModel, split_data
 
 
@@ -375,6 +377,54 @@ def pmmh_fleet_chains(unparam: UnparamModel, inits: Sequence[Parameters], datas,
     try:
         return fleet.pmmh_chains(desc, theta0, chol, off, t, y, has, seeds, iters, priors=priors, first_iter=first_iter, ll0=ll0,
                                  state0=state0, iters_per_launch=iters_per_launch)[:5]
+    finally:
+        if own:
+            fleet.close()
+
+
+LGCP_ITERS_PER_LAUNCH = 100   # the driver's default launch length for event streams (pmmh_lgcp_fleet_chains)
+
+
+def pmmh_lgcp_fleet_chains(unparam: UnparamModel, inits: Sequence[Parameters], streams, n: int, precision: int, chol, priors=None,
+                           iters: int = 1000, seeds: Optional[Sequence[int]] = None, first_iter: int = 0, ll0=None, state0=None,
+                           iters_per_launch: Optional[int] = None, device: int = 0, fleet: Optional[NativeLgcpFleet] = None):
+    """``pmmh_fleet_chains`` for log-Gaussian Cox processes (``cssm_fleet_pmmh_chains_lgcp``): ``len(inits)`` whole chains on the device
+    over ``FilterLgcp(model, resample, precision)``, a chain per stream and every iteration and event of a chain inside one launch.
+    ``unparam``: an LGCP model (``Model.lgcp``).  ``streams``: ONE array of event times (every chain sees it) or one per chain -- what
+    ``NativeLgcpFleet.pack`` takes, e.g. ``simulate.lgcp_fleet_data``.  ``chol``, ``priors`` (None, ``n_theta`` entries, or a dict for
+    ``priors_for``), ``first_iter`` / ``ll0`` / ``state0`` as ``pmmh_fleet_chains``; ``math.sqrt(delta) * np.eye(n_theta)`` with no priors
+    is ``cssm_pmmh_run`` on an LGCP handle per chain, bit for bit.  ``iters_per_launch``: None = ``LGCP_ITERS_PER_LAUNCH`` (an event
+    is a chain of sub-steps, so an iteration is heavy: at the recorded 3.54 ms per fleet filter of S = 1024, N = 1000 and 12 547 events
+    that is about a third of a second per launch -- derived, not measured; a default, not a limit: 0 = all iterations in one launch);
+    it never changes a bit.  ``fleet``: a NativeLgcpFleet of S streams, n particles and this precision to reuse.  Returns ``(ll[S,
+    iters], theta[S, iters, n_theta], accepted[S, iters], last_state[S, iters, d], diag[S, 2])``; ``fleet_posterior_rows`` takes the
+    first four as they are."""
+    S = len(inits)
+    if S < 1 or seeds is None or len(seeds) != S:
+        raise ValueError("one seed per chain")
+    theta0 = [np.asarray(p.flattenParams(), dtype=np.float64) for p in inits]
+    if any(th.shape != theta0[0].shape for th in theta0):
+        raise ValueError("every chain's initial parameters must flatten to the same length")
+    theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+    if isinstance(priors, dict):
+        priors = priors_for(inits[0], priors)
+    shared = len(streams) == 0 or np.ndim(streams[0]) == 0        # one array of times: every chain sees it
+    streams = [streams] * S if shared else list(streams)
+    if len(streams) != S:
+        raise ValueError(f"one array of event times, or one per chain ({S}), not {len(streams)}")
+    off, t, _, _ = NativeLgcpFleet.pack(streams)                  # (refuses a stream without events, before any device call)
+    model = unparam.run(inits[0])
+    desc = model.descriptor(int(precision))
+    per = LGCP_ITERS_PER_LAUNCH if iters_per_launch is None else int(iters_per_launch)
+    own = fleet is None
+    if own:
+        fleet = NativeLgcpFleet(model, n, S, int(precision), device)
+    elif fleet.S != S or fleet.n != int(n) or getattr(fleet, "precision", None) != int(precision):
+        raise ValueError(f"the fleet holds {fleet.S} streams of {fleet.n} particles at precision {getattr(fleet, 'precision', None)}, "
+                         f"the run needs {S} of {n} at {int(precision)}")
+    try:
+        return fleet.pmmh_chains_lgcp(desc, theta0, chol, off, t, seeds, iters, priors=priors, first_iter=first_iter, ll0=ll0,
+                                      state0=state0, iters_per_launch=per)[:5]
     finally:
         if own:
             fleet.close()

@@ -1440,6 +1440,27 @@ CSSM_HD double cssm_chain_propose(const double* Li, const double* z, uint32_t i,
 }
 CSSM_HD double cssm_chain_log_ratio(double ll_prop, double lp_prop, double ll_cur, double lp_cur) { return ((ll_prop + lp_prop) - ll_cur) - lp_cur; }
 
+/*
+ * PMMH chains on the device: LGCP.  cssm_fleet_pmmh_chains_lgcp is the chain above with FilterLgcp (model/ParticleFilter.scala:169-227)
+ * as its filter, every iteration and event of a chain inside k_fleet_pmmh_lgcp.  No arithmetic above changes and the contract version
+ * stays v8.  State, proposal, prior, unfiltered rejection, key and decision are the section's, word for word; a sequential program takes
+ * them from tests/pmmh_chain_twin.py and the filter from the oracle (tests/pmmh_lgcp_twin.py).  With all priors flat and L = sqrt(delta) I
+ * the chain is cssm_pmmh_run on an LGCP handle of N particles.
+ *   filter:    cssm_pf_filter on an LGCP handle under the proposal and the key: the constrained fields and x0 as above, no scale, no y.
+ *              delta = pow(10.0, -precision) as cssm_build_rec forms it.  The transition coefficients are cssm_sde_coef(kind_c, MU_c,
+ *              PHI_c, SIGMA_c, delta), formed ONCE PER ITERATION: every sub-step of every event has the increment delta, so these are
+ *              the bits cssm_build_rec writes into each LGCP record of the proposal; an event with n_sub == 0 does not read them.
+ *              Per event r (observation index r, dt = t_r - t_{r-1}, t_{-1} = the smallest time of the series): n_sub = 0 if dt == 0,
+ *              else ceil(dt / delta); F at t_r and, where f depends on time, at the sub-step times (cssm_build_fsub_table) do not depend
+ *              on theta and come from the host; the uniform is cssm_if2_uniform(key, r); the sub-step walk, gamma - hazard, the NaN
+ *              guard and the maximum are the LGCP fleet filter's statements (fleet_lgcp_weigh; k_fleet_series<..., LGCP = true>).
+ *   level:     the predicted level of contract v8 belongs to ONE filter run: next_ref = NaN at the start of every iteration's filter,
+ *              then per event ref = cssm_ref_choose(next_ref, max), next_ref = cssm_ref_predict(max).  Nothing of it crosses an iteration,
+ *              a chain or the fleet that lends itself (its FleetSeries::next_ref is neither read nor written).
+ *   the rest:  2^-96 sums, ll, systematic resampling, "no usable weight" (ll' = -inf, a rejection) and state' = row T of the sampled
+ *              path at slot |int32(Philox(key, 0, T, CSSM_STREAM_PICK, 0).v[0])| mod N, as above.
+ */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1045,7 +1045,8 @@ int cssm_model_structure(const cssm_model_desc* desc, uint32_t* words_out, int32
  * 1 <= N <= CSSM_FLEET_MAX_N.  The LGCP observation model (sub-stepped events, FilterLgcp) is asked for by name, as the reference asks
  * for FilterLgcp by name: cssm_fleet_create_lgcp makes the fleet, cssm_fleet_create keeps refusing an LGCP descriptor.  An LGCP fleet
  * serves _destroy, _num_series, _num_particles, _set_params, _reseed, _set_option, _init, _init_from, _step, _ll_filter, _ll_filter_more, _filter,
- * _summary, _get_particles, _get_ancestors, _observation_index and _last_ms; every other call on it is CSSM_EINVAL_ARG before anything runs.
+ * _summary, _get_particles, _get_ancestors, _observation_index, _last_ms and _pmmh_chains_lgcp (whole PMMH chains over its event streams;
+ * _pmmh_chains keeps refusing it by name); every other call on it is CSSM_EINVAL_ARG before anything runs.
  * Everything else is refused at cssm_fleet_create / _set_params / _set_option with CSSM_EINVAL_ARG /
  * CSSM_EINVAL_DESC and a message naming the reason and the entry points that do serve it (cssm_pf_*, cssm_pfb_*); a fleet call
  * never degenerates into S single-handle runs.  Thread-affinity and device rules as for every entry point: each call selects the
@@ -1520,7 +1521,8 @@ int cssm_fleet_if2_layout(const cssm_model_desc* desc, int32_t* out, size_t cap,
  * decreasing, a descriptor of another structure than the fleet's (CSSM_EINVAL_DESC), a theta0 row whose prior is -inf or NaN (outside
  * the support), a chol_per_chain factor beyond the first that fails the test above.
  * Not served (cssm_pmmh_run / _run_batched / _run_speculative keep the flat prior and the isotropic proposal): single handles and
- * batches, LGCP fleets, covariance updates inside the kernel. */
+ * batches, covariance updates inside the kernel.  LGCP fleets and LGCP descriptors are refused here by name: cssm_fleet_pmmh_chains_lgcp
+ * (below) runs their chains. */
 #define CSSM_PRIOR_FLAT    0   /* contributes nothing */
 #define CSSM_PRIOR_NORMAL  1   /* on the STORED value: -(z*z)/2.0, z = (theta - a) / b, b > 0 (constants dropped: only differences decide) */
 #define CSSM_PRIOR_UNIFORM 2   /* 0.0 if a <= theta <= b, else -inf */
@@ -1532,6 +1534,35 @@ int cssm_fleet_pmmh_chains(cssm_fleet* f, const cssm_model_desc* desc, const dou
                            double* ll, double* theta, int32_t* accepted, double* last_state, uint32_t* diag_out, int* rc_out);
 /* *ms = device time of the launches of the last cssm_fleet_pmmh_chains (HIP events on the fleet's stream); CSSM_ESTATE before the first. */
 int cssm_fleet_pmmh_chains_last_ms(cssm_fleet* f, double* ms);
+/* ---- whole PMMH chains for LGCP fleets: cssm_fleet_pmmh_chains over FilterLgcp (model/ParticleFilter.scala:169-227), asked for by name
+ * as cssm_fleet_create_lgcp is.  One workgroup per chain: every iteration and every event of a chain runs inside k_fleet_pmmh_lgcp; the
+ * arithmetic is the contract's (include/cssm_numerics.h, "PMMH chains on the device: LGCP").  With all priors flat and L = sqrt(delta) I
+ * chain k is cssm_pmmh_run on an LGCP handle of N particles under seeds[k], bit for bit.
+ *
+ * The semantics are cssm_fleet_pmmh_chains's word for word -- chol (one for all chains or one per chain), priors, ll0 / state0,
+ * first_iter, iters_per_launch (0 = all; never changes a bit), chain-major outputs, diag_out[S][2], a series without events untouched
+ * (NaN rows, accepted -1, rc_out[k] = CSSM_EINVAL_ARG) -- with these differences: f is an LGCP fleet; every record is an event, so there
+ * is no y and no has_obs; desc is an LGCP descriptor whose lgcp_precision is part of the structure and must be the fleet's.  A series'
+ * first increment starts at its smallest time, as in cssm_fleet_filter on a fresh series.
+ * The fleet is only LENT: clouds, ancestors, ll / ess, clocks, observation indices, keys, parameters and every series' predicted level
+ * are afterwards what they were; the call keeps buffers of its own, among them the per-event records (24 + 8 d bytes: what does not
+ * depend on the parameters) and, where f depends on time, the sub-step table of all chains (at most 1 GiB, else CSSM_ENOMEM), both
+ * uploaded once per call.
+ * Refused before the fleet is looked at (CSSM_EINVAL_ARG unless said): null desc / theta0 / chol / seeds / off / t or outputs (ll, theta,
+ * accepted, last_state, rc_out); off[0] != 0; a descriptor that is not LGCP (CSSM_EINVAL_DESC, naming cssm_fleet_pmmh_chains); n_theta
+ * other than the descriptor flattens to; a bad chol entry; a bad prior; n_iters outside [1, 1000000]; first_iter + n_iters > 2^31; a null
+ * fleet.  Then: a fleet that cssm_fleet_create_lgcp did not make (naming cssm_fleet_pmmh_chains); off decreasing; a descriptor of
+ * another structure or precision than the fleet's (CSSM_EINVAL_DESC); a theta0 row outside the prior's support; a chol_per_chain
+ * factor beyond the first that fails the test.
+ * Not served: cssm_fleet_pmmh_run and cssm_fleet_if2 for LGCP fleets, the C++ mirror and JNI, other resamplers than systematic,
+ * covariance updates inside the kernel. */
+int cssm_fleet_pmmh_chains_lgcp(cssm_fleet* f, const cssm_model_desc* desc, const double* theta0, size_t n_theta,
+                                const double* chol, int chol_per_chain, const void* priors, const double* ll0, const double* state0,
+                                uint32_t first_iter, uint32_t n_iters, uint32_t iters_per_launch,
+                                const uint64_t* seeds, const uint64_t* off, const double* t,
+                                double* ll, double* theta, int32_t* accepted, double* last_state, uint32_t* diag_out, int* rc_out);
+/* *ms = device time of the launches of the last cssm_fleet_pmmh_chains_lgcp (HIP events on the fleet's stream); CSSM_ESTATE before the first. */
+int cssm_fleet_pmmh_chains_lgcp_last_ms(cssm_fleet* f, double* ms);
 /* ---- fixed-lag interpolation of a live fleet (FilterInterpolate as the stream it is: ParticleFilter.interpolate, model/
  * ParticleFilter.scala:281-310 -- one stepInterpolate per observation, every element carrying the paths that survive to that moment;
  * examples/Interpolate.scala: once data resumes behind a gap, the surviving lineages fill it).
@@ -1601,6 +1632,13 @@ int cssm_fleet_pack_record(const cssm_model_desc* desc, uint64_t n_particles, ui
 int cssm_fleet_pack_record_lgcp(const cssm_model_desc* desc, uint64_t n_particles, uint64_t seed, double t_prev, double t,
                                 uint32_t step, unsigned char* out, size_t cap, size_t* bytes,
                                 double* fsub_out, size_t fsub_cap, size_t* fsub_count);
+/* Diagnostic, no device: the record cssm_fleet_pmmh_chains_lgcp uploads for the event at t behind t_prev under `desc` (CSSM_OBS_LGCP,
+ * else CSSM_EINVAL_DESC) -- the part of the record above that does not depend on the parameters or the key, 24 + 8 d bytes: dt =
+ * 10^-precision (double; 0 where n_sub == 0), n_sub (i32), step, fsub_off, a zero word (u32), then the d f coefficients at t -- and the
+ * rows of the sub-step table it brings, as above. */
+int cssm_fleet_pmmh_lgcp_pack_record(const cssm_model_desc* desc, double t_prev, double t, uint32_t step,
+                                     unsigned char* out, size_t cap, size_t* bytes,
+                                     double* fsub_out, size_t fsub_cap, size_t* fsub_count);
 
 /* ---- errors / build info ------------------------------------------------------------------ */
 const char* cssm_last_error(void);
